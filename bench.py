@@ -8,7 +8,10 @@ re-sorts on any camera translation (src/GSplatRenderer.C:165-186).  Inputs are
 resident in HBM before the timed region (uploaded once, as the reference stages
 textures once).
 
-  python bench.py --gpus 1 --steps 60 --warmup 5
+  python bench.py --gpus 1 --steps 60 --warmup 5    (set-up, warm-up, the timed steps and the line: nothing else)
+  python bench.py --full ...                        (+ the last timed frame checked bit for bit, the extra legs, the measured HBM
+                                                     peak and the CPU baseline)
+  python bench.py ... --dump-outputs DIR            (+ the last timed frame as DIR/frame.npy)
   python bench.py --gpus N ...          (no launcher: ONE process drives the N GPUs through gsr_multi_* -- the form the
                                          reference's single draw thread implies, src/DM_GSplatHook.C:30-39; RCCL gather)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -138,7 +141,33 @@ def parse_args():
     ap.add_argument("--no-verify", action="store_true",
                     help="N>1: skip the check (after the timed region) that the last stitched frame is bit-identical to the same frame "
                          "rendered unsharded on rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the check of the last timed frame against a context that culls nothing, "
+                         "the extra legs (latency, per-stage times, culling off, cold frames, depth-tested frames, the boundary, other "
+                         "configs, host target), the measured HBM peak and the CPU baseline.  Without it a run only sets up, warms up, "
+                         "times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame the last one rendered (what gsr_render hands its caller) to "
+                         "DIR/frame.npy, float32 [H, W, 4]; a frame over 64 MB is written as a fixed sample of its pixels "
+                         "(DIR/frame_sample.npy [K, 4] and their flat indices DIR/frame_sample_index.npy, float64)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21          # 16 B of RGBA + 8 B of index each: 48 MB
+
+
+def dump_outputs(out_dir: str, frame) -> None:
+    """--dump-outputs: the last timed frame as float32 .npy (inputs and cameras are seeded, so two builds compare pixel for pixel)"""
+    os.makedirs(out_dir, exist_ok=True)
+    img = frame.detach().cpu().numpy().astype(np.float32, copy=False)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "frame_sample_index.npy"), idx.astype(np.float64))
 
 
 def cpu_baseline(oracle, splats, cam0, pkg, budget_s: float) -> dict:
@@ -424,9 +453,11 @@ def main_single_process(args):
         step(args.warmup + i)
     sync_all()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final)
 
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         ref = reference_frame(pkg, torch, devices[0], stream, splats, cams[args.warmup + args.steps - 1], W, H, exact=True)
         verified = bool(torch.equal(final, ref)) and bool(ref[..., 3].max() > 0)
         if not verified:
@@ -436,7 +467,7 @@ def main_single_process(args):
     # extra leg (untimed): per-rank stage times (HIP events around every stage) and the gather on the root's transfer stream
     stage = None
     gather_ms = None
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         M.set_option(E.OPT_STAGE_TIMING, 2)
         last = args.warmup + args.steps
         for i in range(max(0, last - 12), max(0, last - 10)):
@@ -475,7 +506,7 @@ def main_single_process(args):
                 "note": "gather_ms = HIP events on the root's transfer stream around the grouped ncclRecv x (N-1) (+ the root's own band copy); the "
                         "peers send concurrently, each over its own link: per-link rate = the largest peer band / gather_ms"
                         + ("" if M.transport == E.TRANSPORT_RCCL else " -- COPY transport on shared GPUs: NOT a link measurement")}
-    hbm = measured_hbm_peak()
+    hbm = measured_hbm_peak() if args.full else None
     per_rank = []
     for g in range(N):
         own_px = sum(min(16, H - r * 16) for r in pkg.multigpu.owned_tile_rows(H, g, N, args.shard_layout)) * W
@@ -712,12 +743,16 @@ def main():
         edges = [round(k * args.steps / 5) for k in range(6)]
         windows = [(edges[k + 1] - edges[k]) / (stamps[edges[k + 1]] - stamps[edges[k]]) for k in range(5) if stamps[edges[k + 1]] > stamps[edges[k]]]
 
-    # Is the last TIMED frame the full frame?  The same camera from a second context on this GPU that culls nothing
+    # --full: is the last TIMED frame the full frame?  The same camera from a second context on this GPU that culls nothing
     # (GSR_OPT_OCCLUSION_CULL = 0, GSR_OPT_CLUSTER_CULL = 0, unsharded): bit for bit.
+    verify = args.full and not args.no_verify and (world > 1 or args.emulate_shard <= 1)
+    extra = args.full and not args.no_extra_legs
+    shown = current_frame() if (verify or args.dump_outputs) else None     # the last step's frame on rank 0 (every rank: a gather)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, shown)
     verified = None
-    if not args.no_verify and (world > 1 or args.emulate_shard <= 1):
+    if verify:
         last = cams[args.warmup + args.steps - 1]
-        shown = current_frame()                                 # the last step's frame on rank 0
         if rank == 0:
             ref = reference_frame(pkg, torch, dev_index, stream, splats, last, W, H, exact=True, depth=depth_t)
             verified = bool(torch.equal(shown, ref)) and bool(ref[..., 3].max() > 0)
@@ -732,7 +767,7 @@ def main():
     # extra leg: LATENCY -- BASELINE.md section 5 defines fps as 1 / median wall-clock of a synchronous gsr_render; `value` above is the
     # throughput of back-to-back frames (the queue never drains).  Here every frame is waited for before the next is issued.
     latency = None
-    if not args.no_extra_legs:
+    if extra:
         lat = []
         last = args.warmup + args.steps
         k_lat = min(30, last)
@@ -749,7 +784,7 @@ def main():
     # extra leg (untimed, informational): a few more frames with HIP events around EVERY stage -> per-stage breakdown and the
     # k_preprocess / k_colour_prefix durations.  Kept out of the timed region: six extra events per frame stall the queue ~35 us.
     st_stage = None
-    if not args.no_extra_legs:
+    if extra:
         # ... in the regime of the timed region: the orbit simply continues (re-rendering its last frames), and the leg's first
         # two frames -- which still see the horizons / hints of the frame before the leg -- are not counted
         eng.set_option(pkg.engine.OPT_STAGE_TIMING, 2)
@@ -767,7 +802,7 @@ def main():
         dist.barrier()
     # extra leg (informational, single GPU): the same frames with occlusion culling switched off
     unculled = None
-    if world == 1 and args.cull and not args.no_extra_legs:
+    if world == 1 and args.cull and extra:
         eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 0)
         for i in range(min(5, args.warmup + args.steps)):
             step(i)
@@ -784,7 +819,7 @@ def main():
     # horizons.  Under the library's policy (a culled attempt that breaks is re-rendered as a front-slab frame; culling backs off) and
     # with occlusion culling inside the frame only (GSR_OPT_OCCLUSION_CULL = 3: every frame a front-slab frame)
     cold = None
-    if world == 1 and args.cull and not args.no_extra_legs and args.emulate_shard <= 1:
+    if world == 1 and args.cull and extra and args.emulate_shard <= 1:
         k3 = min(40, args.steps)
         # (a rotation about a ball-shaped cloud leaves its depth horizons valid; what makes a frame cold is a jump in DISTANCE:
         #  every other frame from 1.3 x as far, 111 degrees further round)
@@ -817,7 +852,7 @@ def main():
     # to back in this leg's own loop: plain (no depth buffer), a depth buffer cleared to the far plane, and one with an opaque sphere
     # among the splats covering ~30 % of the screen.  Each variant's last frame is checked bit for bit against a context that culls nothing.
     depth_leg = None
-    if world == 1 and not args.no_extra_legs and args.emulate_shard <= 1 and args.depth == "none":
+    if world == 1 and extra and args.emulate_shard <= 1 and args.depth == "none":
         k4 = min(60, args.steps)
         depth_leg = {}
         for name in ("plain", "far_plane", "occluder"):
@@ -877,7 +912,7 @@ def main():
     # verbs (string ids, a staging plan rebuilt and compared every redraw) cost beside the direct line.  `restage`: every frame brings
     # a new cache version of the three details (an animated sequence: registerUpdate x 3 -> re-stage -> frame), with the upload's stages.
     shim_leg = None
-    if world == 1 and not args.no_extra_legs and args.emulate_shard <= 1 and args.depth == "none":
+    if world == 1 and extra and args.emulate_shard <= 1 and args.depth == "none":
         E = pkg.engine
         R = pkg.GSplatRenderer(dev_index)
         R_eng = pkg.load_library().gsplat_renderer_engine(R.h)
@@ -982,7 +1017,7 @@ def main():
     # extra leg (informational, single GPU, the default run of the headline config only): the other BASELINE configs, the same
     # library and options, serial frames -- so that their frame rates are on the driver's record too, not only in DESIGN.md
     other = None
-    if world == 1 and args.config == "C4" and args.splats is None and not args.no_extra_legs and not args.no_other_configs and args.emulate_shard <= 1:
+    if world == 1 and args.config == "C4" and args.splats is None and extra and not args.no_other_configs and args.emulate_shard <= 1:
         other = {}
         for oc in ("C1", "C2", "C3", "C5", "T1", "S1", "R1"):
             osp, ocfg = pkg.scenes.make_config(oc)
@@ -1015,7 +1050,7 @@ def main():
             torch.cuda.empty_cache()
     # extra leg: the PCIe-inclusive rate -- gsr_render into a HOST buffer, what a caller without GL interop gets (never `value`)
     host_leg = None
-    if world == 1 and not args.no_extra_legs and args.emulate_shard <= 1 and not args.via_multi:
+    if world == 1 and extra and args.emulate_shard <= 1 and not args.via_multi:
         host_leg = host_target_leg(eng, cams[:min(len(cams), 50)], W, H)
     # blend-kernel roofline, measured with HIP events on the kernel's own stream
     shards = args.emulate_shard if (world == 1 and args.emulate_shard > 1) else world
@@ -1023,7 +1058,7 @@ def main():
     own_px = sum(min(16, H - r * 16) for r in pkg.multigpu.owned_tile_rows(H, srank, shards, args.shard_layout)) * W
     regime = "culled" if st["frames_culled"] * 2 > st["frames"] else ("slab" if st["frames_slab"] * 2 > st["frames"] else "unculled")
     tj, traffic_from = load_traffic(regime, world == 1 and args.config == "C4" and args.splats is None)
-    hbm = measured_hbm_peak() if rank == 0 else None
+    hbm = measured_hbm_peak() if (rank == 0 and args.full) else None
     peak_meas = hbm["peak_GBps"] if hbm else None
     roofline = blend_roofline(st, own_px, regime, hbm, tj, traffic_from)
     stages = {k: st_stage[k] for k in ("ms_preprocess", "ms_depth_sort", "ms_emit", "ms_tile_sort", "ms_blend", "ms_total")} if st_stage else {}
@@ -1127,7 +1162,7 @@ def main():
                 line["sharded_frame_bit_identical"] = verified
         if rccl_info is not None:
             line["rccl_rank_of_root"], line["rccl_comm_count"] = rccl_info
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             oracle = ge.load_oracle()
             cam0 = pkg.camera.make_camera(W, H, sh_order=order, frame=0)
             line["cpu_baseline"] = cpu_baseline(oracle, splats, cam0, pkg, args.cpu_seconds)

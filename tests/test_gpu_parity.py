@@ -1605,7 +1605,7 @@ def test_bench_launches_itself_on_several_gpus(pkg):
     the COPY transport (a functional run, flagged as such); the line is the driver's contract and the stitched frame is the
     unsharded frame bit for bit.  Without enough GPUs (and without the override) the line carries an error and the exit code says so."""
     ndev = int(pkg.load_library().gsr_device_count())
-    res, line = _run_bench(["--gpus", "2", "--config", "C3", "--steps", "12", "--warmup", "4", "--no-cpu-baseline"],
+    res, line = _run_bench(["--gpus", "2", "--config", "C3", "--steps", "12", "--warmup", "4", "--no-cpu-baseline", "--full"],
                            {"GSR_BENCH_ALLOW_DUP": "1"})
     assert res.returncode == 0, res.stderr[-2000:]
     assert line is not None and line["n_gpus"] == 2 and line["sharded_frame_bit_identical"] is True and line["value"] > 0
@@ -1614,7 +1614,7 @@ def test_bench_launches_itself_on_several_gpus(pkg):
     if ndev >= 2:
         assert line["rccl_ranks"] == [0, 1] and line["rccl_comm_count"] == 2
     # interleaved rows through the same door
-    res, line = _run_bench(["--gpus", "3", "--config", "C2", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--shard-layout", "0", "--no-extra-legs"],
+    res, line = _run_bench(["--gpus", "3", "--config", "C2", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--shard-layout", "0", "--no-extra-legs", "--full"],
                            {"GSR_BENCH_ALLOW_DUP": "1"})
     assert res.returncode == 0 and line["sharded_frame_bit_identical"] is True, res.stderr[-2000:]
     if ndev < 64:
@@ -1638,7 +1638,7 @@ def test_bench_one_rank_through_the_multi_gpu_door_matches_the_single_context(pk
     # (a performance figure inside the correctness suite: wide enough not to flake on a shared or throttled GPU -- the two doors run the
     #  same kernels; a real regression of the multi-GPU door at N = 1 is tens of per cent, from an extra copy or a lost overlap)
     assert abs(max(multi) / max(single) - 1.0) < 0.15, (single, multi)
-    res, line = _run_bench(["--gpus", "2", "--config", "C2", "--steps", "8", "--warmup", "3", "--no-cpu-baseline"], {"GSR_BENCH_ALLOW_DUP": "1"})
+    res, line = _run_bench(["--gpus", "2", "--config", "C2", "--steps", "8", "--warmup", "3", "--no-cpu-baseline", "--full"], {"GSR_BENCH_ALLOW_DUP": "1"})
     assert res.returncode == 0, res.stderr[-2000:]
     gl = line["gather_links"]
     assert gl["bytes_per_peer"] == [line["config"]["width"] * 16 * sum(min(16, line["config"]["height"] - r * 16) for r in range(23, 45))]
@@ -1653,7 +1653,7 @@ def test_bench_takes_an_inria_ply(pkg, oracle, tmp_path):
     v["x"] += 5.0; v["z"] -= 2.0                                   # (somewhere else than the origin: the orbit has to find it)
     path = str(tmp_path / "capture.ply")
     pkg.scenes.write_inria_ply(path, v)
-    res, line = _run_bench(["--ply", path, "--steps", "30", "--warmup", "5", "--cpu-seconds", "4", "--no-other-configs"], {})
+    res, line = _run_bench(["--ply", path, "--steps", "30", "--warmup", "5", "--cpu-seconds", "4", "--no-other-configs", "--full"], {})
     assert res.returncode == 0, res.stderr[-2000:]
     assert line["value"] > 0 and line["timed_frame_bit_identical"] is True and line["data"].startswith("INRIA PLY")
     assert line["config"]["workload"].startswith("PLY capture.ply: 60000 splats") and line["config"]["n_splats"] == 60000
@@ -1672,10 +1672,38 @@ def test_bench_takes_an_inria_ply(pkg, oracle, tmp_path):
 
 
 def test_bench_single_gpu_line_says_whether_the_timed_frame_is_the_full_frame(pkg):
-    res, line = _run_bench(["--config", "C3", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs"], {})
+    res, line = _run_bench(["--config", "C3", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-other-configs", "--full"], {})
     assert res.returncode == 0, res.stderr[-2000:]
     assert line["timed_frame_bit_identical"] is True and line["occlusion_culling"]["frames_culled"] > 0
     assert line["roofline"]["peak_measured"] is None or line["roofline"]["peak_measured"] > 3000
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_frame(pkg, tmp_path):
+    """`bench.py` without --full: the timed steps and the line, nothing else; --dump-outputs writes the frame of the last timed step,
+    which is the frame a context that culls nothing renders for the same camera"""
+    steps, warmup = 10, 3
+    res, line = _run_bench(["--config", "C2", "--steps", str(steps), "--warmup", str(warmup), "--dump-outputs", str(tmp_path)], {})
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert line["steps"] == steps and line["value"] > 0 and abs(line["ms_per_step"] * line["value"] / 1e3 - 1.0) < 1e-9
+    assert line["latency"] is None and line["roofline"]["peak_measured"] is None and line["occlusion_culling"]["without"] is None
+    assert not {"timed_frame_bit_identical", "depth_tested", "boundary", "cold_frames", "host_target", "cpu_baseline"} & set(line)
+    img = np.load(tmp_path / "frame.npy")
+    splats, cfg = pkg.scenes.make_config("C2")
+    w, h = cfg["width"], cfg["height"]
+    assert img.dtype == np.float32 and img.shape == (h, w, 4)
+    cam = pkg.scenes.config_camera("C2", pkg.camera, w, h, cfg["sh_order"], warmup + steps - 1)
+    hb = HipBuffers()
+    try:
+        with pkg.Engine(0) as eng:
+            eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 0)
+            eng.set_option(pkg.engine.OPT_CLUSTER_CULL, 0)
+            eng.upload(splats)
+            out = hb.alloc(w * h * 16)
+            eng.render_struct_to_device(pkg.engine.camera_struct(cam), out)
+            want = hb.download(out, (h, w, 4))
+    finally:
+        hb.free()
+    assert want[..., 3].max() > 0 and np.array_equal(img, want)
 
 
 def test_multi_gpu_gather_overlaps_the_next_frame_and_keeps_every_frame(pkg, engine):
@@ -2225,7 +2253,7 @@ def test_upload_reports_its_stages_and_restaging_is_exact(pkg, oracle):
 def test_bench_line_carries_the_depth_tested_and_boundary_legs(pkg):
     """the default bench line (a small config here): `depth_tested` -- plain / a cleared depth buffer / an opaque sphere, each checked bit for
     bit against a context that culls and classifies nothing -- and `boundary` -- the redraw through the nine verbs, and the re-stage loop"""
-    res, line = _run_bench(["--config", "C2", "--steps", "24", "--warmup", "6", "--no-cpu-baseline", "--no-other-configs"], {})
+    res, line = _run_bench(["--config", "C2", "--steps", "24", "--warmup", "6", "--no-cpu-baseline", "--no-other-configs", "--full"], {})
     assert res.returncode == 0, res.stderr[-2000:]
     dt = line["depth_tested"]
     for k in ("plain", "far_plane", "occluder"):

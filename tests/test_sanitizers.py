@@ -43,10 +43,15 @@ def _sanitized(kind: str):
     return lib, runtime
 
 
+def _preload(runtime: str) -> str:
+    """the sanitizer runtime first (it must come first), then whatever the environment already preloads"""
+    return ":".join(p for p in (runtime, os.environ.get("LD_PRELOAD", "")) if p)
+
+
 def _run(kind: str, pytest_args, extra_env=None, timeout=1500):
     lib, runtime = _sanitized(kind)
     env = dict(os.environ)
-    env.update({"LD_PRELOAD": runtime, "GSR_LIBRARY": lib, "GSR_EXPECT_SANITIZER": kind,
+    env.update({"LD_PRELOAD": _preload(runtime), "GSR_LIBRARY": lib, "GSR_EXPECT_SANITIZER": kind,
                 # leaks: python itself "leaks" at exit; everything else stops the run at the first report
                 "ASAN_OPTIONS": "detect_leaks=0:halt_on_error=1:abort_on_error=0:exitcode=87",
                 "UBSAN_OPTIONS": "print_stacktrace=1:halt_on_error=1:exitcode=88",
@@ -78,7 +83,7 @@ def test_the_sanitized_library_is_the_one_under_test():
             "assert 'libgsplat_hip_asan.so' in maps and 'houdini-gsplat-renderer_amd/libgsplat_hip.so' not in maps\n"
             "assert C.CDLL(None).__asan_init is not None\n"
             "print('ok')\n")
-    env = dict(os.environ, LD_PRELOAD=runtime, GSR_LIBRARY=lib, ASAN_OPTIONS="detect_leaks=0")
+    env = dict(os.environ, LD_PRELOAD=_preload(runtime), GSR_LIBRARY=lib, ASAN_OPTIONS="detect_leaks=0")
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
 

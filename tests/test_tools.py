@@ -109,3 +109,22 @@ def test_frame_kernels_keep_their_register_and_scratch_budgets():
     assert scratch <= 12 and vg <= 80, (vg, scratch)
     assert find("_Z7k_blendILb0E")[0] <= 72 and find("_Z7k_blendILb1E")[0] <= 80
     assert find("_Z7k_blendILb0E")[2] <= 20 * 1024 and find("_Z7k_blendILb1E")[2] <= 22 * 1024       # LDS: seven workgroups of either fit a CU's 160 KB
+
+
+def test_bench_dump_outputs_keeps_under_64_mb_and_samples_the_same_pixels(tmp_path):
+    """bench.py --dump-outputs: a 1080p frame is written whole; a 4K frame (C5) as the same seeded sample of its pixels every run"""
+    import torch
+    import bench
+    small = torch.rand((1080, 1920, 4), generator=torch.Generator().manual_seed(1))
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(np.load(tmp_path / "small" / "frame.npy"), small.numpy())
+    big = torch.rand((2160, 3840, 4), generator=torch.Generator().manual_seed(2))
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["frame_sample.npy", "frame_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_BYTES
+    px, idx = np.load(tmp_path / "a" / "frame_sample.npy"), np.load(tmp_path / "a" / "frame_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(np.unique(idx)) == len(idx) == len(px)
+    assert np.array_equal(px, big.numpy().reshape(-1, 4)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "frame_sample_index.npy"))

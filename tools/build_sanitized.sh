@@ -14,13 +14,13 @@ mkdir -p $V
 WHAT=${1:-all}
 CLANG_RT=$(dirname "$(/opt/rocm/lib/llvm/bin/clang++ -print-file-name=libclang_rt.asan-x86_64.so)")
 SRC="$P/csrc/gsr_api.hip $P/csrc/gsr_multi.cpp $P/csrc/GSplatRenderer.cpp $P/csrc/gsplat_ingest.cpp"
-COMMON="--offload-arch=gfx950 -O1 -g -fno-omit-frame-pointer -std=c++17 -ffp-contract=off -fPIC -shared -fno-gpu-sanitize -shared-libsan -Wno-unused-result"
+COMMON="--offload-arch=gfx950 -O1 -g -fno-omit-frame-pointer -std=c++17 -ffp-contract=off -fPIC -shared -shared-libsan -Wno-unused-result"
 if [ "$WHAT" = asan ] || [ "$WHAT" = all ]; then
-  hipcc $COMMON -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $V/libgsplat_hip_asan.so $SRC -ldl -pthread -Wl,-rpath,$CLANG_RT
+  hipcc $COMMON -fno-gpu-sanitize -fsanitize=address,undefined -fno-sanitize-recover=undefined -o $V/libgsplat_hip_asan.so $SRC -ldl -pthread -Wl,-rpath,$CLANG_RT
   echo "$CLANG_RT/libclang_rt.asan-x86_64.so" > $V/asan.preload
 fi
 if [ "$WHAT" = tsan ] || [ "$WHAT" = all ]; then
-  hipcc $COMMON -fsanitize=thread -o $V/libgsplat_hip_tsan.so $SRC -ldl -pthread -Wl,-rpath,$CLANG_RT
+  hipcc $COMMON -fno-gpu-sanitize -fsanitize=thread -o $V/libgsplat_hip_tsan.so $SRC -ldl -pthread -Wl,-rpath,$CLANG_RT
   echo "$CLANG_RT/libclang_rt.tsan-x86_64.so" > $V/tsan.preload
 fi
 ls -la $V/*san*

@@ -13,17 +13,17 @@ mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 echo "== $NG GPU(s) visible, running up to $MAXG"
 python -m pytest tests -q -m gpu -k "rccl or multi_gpu" 2>&1 | tail -3 | tee $OUT/pytest_rccl.txt
-python bench.py --gpus 1 --via-multi --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/c4_n1_via_multi.json 2> $OUT/c4_n1_via_multi.err
-python bench.py --gpus 1 --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/c4_n1.json 2> $OUT/c4_n1.err
+python bench.py --full --gpus 1 --via-multi --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/c4_n1_via_multi.json 2> $OUT/c4_n1_via_multi.err
+python bench.py --full --gpus 1 --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/c4_n1.json 2> $OUT/c4_n1.err
 for cfg in C4 C5; do
-  python bench.py --config $cfg --gpus 1 --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/${cfg}_n1_single.json 2>/dev/null
+  python bench.py --full --config $cfg --gpus 1 --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 > $OUT/${cfg}_n1_single.json 2>/dev/null
   for n in 2 4 8; do
     [ $n -gt $MAXG ] && continue
     for layout in 1 0; do
-      python bench.py --config $cfg --gpus $n --shard-layout $layout --no-cpu-baseline --steps 200 --warmup 20 \
+      python bench.py --full --config $cfg --gpus $n --shard-layout $layout --no-cpu-baseline --steps 200 --warmup 20 \
           > $OUT/${cfg}_n${n}_layout${layout}_one_process.json 2> $OUT/${cfg}_n${n}_layout${layout}_one_process.err
       python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n + 10 * layout)) \
-          bench.py --config $cfg --gpus $n --shard-layout $layout --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 \
+          bench.py --full --config $cfg --gpus $n --shard-layout $layout --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 \
           > $OUT/${cfg}_n${n}_layout${layout}_per_gpu.json 2> $OUT/${cfg}_n${n}_layout${layout}_per_gpu.err
     done
   done

@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 3000 "$OUT/bench.json"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$TAG -o trace -- python "$REPO/bench.py" --no-cpu-baseline --no-extra-legs "$@" > "$OUT/bench_profiled.json" 2> "$OUT/rocprof.err"
