@@ -836,6 +836,267 @@ int gso_render(const gso_splats* s, const gso_frame* f, float* rgba, int threads
 }
 
 /* ------------------------------------------------------------------------- */
+/* The product's frame and a per-pixel bound on how far a GPU frame may lie from it ("early-out").
+ *
+ * A GPU frame differs from gso_render's in exactly two ways: the blend kernel stops compositing a pixel once T < t_min
+ * (2^-14, k_blend.h GSR_T_MIN; T is tested before every fragment), and 2^x is v_exp_f32 there, gso_exp2f here.  Everything
+ * else -- the records, the depth order, the discard and depth decisions, the float32 blend operations -- is the same on both
+ * sides.  So one pass over the records fills
+ *   plain: the frame without early-out, bit-identical to gso_render / gso_render_depth;
+ *   eo:    the frame with the product's early-out;
+ *   bound: per pixel and channel, a bound on |GPU - eo| when every fragment's alpha may be off by a relative GSO_CONTRACT_ETA.
+ * The bound follows the compositing recurrence (w = T a, C += w c, T -= w) with an ABSOLUTE bound E on |T_gpu - T|:
+ *   |dw_k|  <= E_{k-1} a_k (1 + eta) + w_k eta + ulp(w_k)                       (a changed alpha, a changed T, w's rounding)
+ *   E_k     <= E_{k-1} (1 - a_k + a_k eta) + w_k eta + ulp(w_k) + ulp(T_k)
+ *   |dC_k|  <= |dC_{k-1}| + |dw_k| |c_k| + ulp(|C_k| + |dC_{k-1}|)              (the fma may round the other way)
+ *   |dA|    <= E_n + ulp(A)
+ * (first order in eta this is eta * sum_k w_k (|c_k| + max later |c|)).  A fragment with arg >= 0 has alpha = 1 exactly on
+ * both sides: eta = 0 and no rounding.  The stop is ambiguous at the first fragment where T - E < t_min <= T + E: from there
+ * on the two sides may composite different prefixes of the remaining fragments, so the pixel adds (T + E) * max |c| of the
+ * fragments from that one on (and T + E to alpha).  A pixel covered by a colour beyond 1e30 (the contract's +-3e38 stand-ins
+ * for inf) gets an infinite bound on every channel.
+ * seed != 0 (tests only): every fragment's alpha with arg < 0 is scaled by 1 + xi * eta, xi in [-1, 1] a hash of
+ * (seed, splat, pixel), never by more than eta * alpha -- a stand-in for another 2^x with which the bound is tested here.
+ * stats (nullable): [0] = pixels whose stop was ambiguous, [1] = pixels with an infinite bound.                         */
+typedef struct contract_px {
+    double E;      /* bound on |T_gpu - T| before the next fragment */
+    double B[3];   /* colour bound accumulated so far */
+    double X;      /* T + E at the fragment where the stop became ambiguous (0: not ambiguous) */
+    double M[3];   /* max |colour| of the fragments from that one on */
+    int amb, bad;
+} contract_px;
+
+typedef struct contract_args {
+    float t_min;
+    double eta;          /* perturbation amplitude (seed != 0) */
+    uint64_t seed;
+    const float* depth;  /* whole frame, or NULL */
+    int width, row_lo;
+    float* eo;           /* rows [row_lo, row_hi] only */
+    float* plain;
+    contract_px* st;
+} contract_args;
+
+static inline double ulp_of(double x)
+{
+    x = fabs(x);
+    if (!(x > 0.0)) return 0.0;
+    if (x < 1.1754943508222875e-38) return 1.401298464324817e-45;
+    int e;
+    frexp(x, &e);              /* x = m 2^e, m in [0.5, 1): a float there has ulp 2^(e-24) */
+    return ldexp(1.0, e - 24);
+}
+
+static inline double contract_xi(uint64_t seed, uint64_t splat, uint64_t pixel)
+{
+    uint64_t h = (seed * 0x9e3779b97f4a7c15ull) ^ (splat * 0xc2b2ae3d27d4eb4full) ^ (pixel * 0x165667b19e3779f9ull);
+    h ^= h >> 33; h *= 0xff51afd7ed558ccdull;
+    h ^= h >> 33; h *= 0xc4ceb9fe1a85ec53ull;
+    h ^= h >> 33;
+    return (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+
+/* alpha * (1 + xi eta), <= 1, and never further than eta * alpha from alpha */
+static inline float contract_perturb(float alpha, double xi, double eta)
+{
+    float a = (float)((double)alpha * (1.0 + xi * eta));
+    while (fabs((double)a - (double)alpha) > eta * (double)alpha) a = nextafterf(a, alpha);
+    return a > 1.0f ? 1.0f : a;
+}
+
+static void contract_splat_rows(const gso_record* o, int64_t si, int lo, int hi, const contract_args* A)
+{
+    const int width = A->width;
+    const float xlo = o->cx - o->hx - 0.5f, xhi = o->cx + o->hx - 0.5f;
+    const float ylo = o->cy - o->hy - 0.5f, yhi = o->cy + o->hy - 0.5f;
+    if (!(xhi >= 0.0f && xlo <= (float)(width - 1))) return;
+    if (!(yhi >= (float)lo && ylo <= (float)hi)) return;
+    const int i0 = (int)ceilf(fmaxf(xlo, 0.0f));
+    const int i1 = (int)floorf(fminf(xhi, (float)(width - 1)));
+    const int j0 = (int)ceilf(fmaxf(ylo, (float)lo));
+    const int j1 = (int)floorf(fminf(yhi, (float)hi));
+    const float col[3] = {o->r, o->g, o->b};
+    const double acol[3] = {fabs((double)o->r), fabs((double)o->g), fabs((double)o->b)};
+    const int bad = !(acol[0] <= 1e30 && acol[1] <= 1e30 && acol[2] <= 1e30);
+    for (int j = j0; j <= j1; ++j) {
+        const int tj = j & ~(GSO_TILE - 1);
+        const float d0y = ((float)tj + 0.5f) - o->cy;
+        const float ly = (float)(j - tj);
+        for (int i = i0; i <= i1; ++i) {
+            /* the fragment's fate: exactly as splat_rows_depth */
+            const int ti = i & ~(GSO_TILE - 1);
+            const float d0x = ((float)ti + 0.5f) - o->cx;
+            const float lx = (float)(i - ti);
+            const float c0 = fmaf(d0x, o->a1x, d0y * o->a1y);
+            const float c1 = fmaf(d0x, o->b1x, d0y * o->b1y);
+            const float q0 = fmaf(lx, o->a1x, fmaf(ly, o->a1y, c0));
+            const float q1 = fmaf(lx, o->b1x, fmaf(ly, o->b1y, c1));
+            if (!(fmaxf(fabsf(q0), fabsf(q1)) <= GSO_QLIM)) continue;
+            const float pw = fmaf(q0, q0, q1 * q1);
+            const float arg = o->la - pw;
+            if (!(arg >= -GSO_LOG2_255)) continue;
+            float alpha = arg >= 0.0f ? 1.0f : gso_exp2f(arg);
+            const size_t pix = (size_t)j * (size_t)width + (size_t)i;
+            if (A->depth && !(o->zwin <= A->depth[pix])) continue;
+            if (A->seed && arg < 0.0f) alpha = contract_perturb(alpha, contract_xi(A->seed, (uint64_t)si, (uint64_t)pix), A->eta);
+            const size_t p = (size_t)(j - A->row_lo) * (size_t)width + (size_t)i;
+            /* the frame without early-out (splat_rows_depth) */
+            float* pp = A->plain + 4 * p;
+            const float wp = pp[3] * alpha;
+            pp[0] = fmaf(wp, o->r, pp[0]);
+            pp[1] = fmaf(wp, o->g, pp[1]);
+            pp[2] = fmaf(wp, o->b, pp[2]);
+            pp[3] = pp[3] - wp;
+            /* the product's frame and its bound */
+            contract_px* s = A->st + p;
+            float* pe = A->eo + 4 * p;
+            const float T = pe[3];
+            s->bad |= bad;
+            if (s->amb) {
+                for (int k = 0; k < 3; ++k) s->M[k] = fmax(s->M[k], acol[k]);
+            } else if (A->t_min > 0.0f && (double)T - s->E < (double)A->t_min && (double)A->t_min <= (double)T + s->E) {
+                s->amb = 1;
+                s->X = (double)T + s->E;
+                for (int k = 0; k < 3; ++k) s->M[k] = acol[k];
+            }
+            if (!(T >= A->t_min)) continue;                          /* k_blend: weight 0 once T < t_min */
+            const float w = T * alpha;
+            pe[0] = fmaf(w, col[0], pe[0]);
+            pe[1] = fmaf(w, col[1], pe[1]);
+            pe[2] = fmaf(w, col[2], pe[2]);
+            pe[3] = T - w;
+            const double eta = arg >= 0.0f ? 0.0 : GSO_CONTRACT_ETA;  /* alpha = 1 exactly on both sides */
+            const double rw = arg >= 0.0f ? 0.0 : ulp_of((double)w * (1.0 + eta) + s->E);
+            const double dw = s->E * (double)alpha * (1.0 + eta) + (double)w * eta + rw;
+            for (int k = 0; k < 3; ++k) s->B[k] += dw * acol[k] + ulp_of(fabs((double)pe[k]) + s->B[k] + dw * acol[k]);
+            const double e1 = s->E * (1.0 - (double)alpha + (double)alpha * eta) + (double)w * eta + rw;
+            s->E = e1 + (arg >= 0.0f ? 0.0 : ulp_of((double)pe[3] + e1));
+        }
+    }
+}
+
+int gso_blend_contract_rows(const gso_record* rec, const int32_t* perm, int64_t n, int width, int height, const float* depth,
+                            int row_lo, int row_hi, float t_min, float eta, uint64_t seed, float* out_eo, float* out_plain,
+                            float* out_bound, int64_t* stats, int threads)
+{
+    if (!rec || !perm || !out_eo || !out_plain || !out_bound || width <= 0 || height <= 0) return -1;
+    if (row_lo < 0) row_lo = 0;
+    if (row_hi > height - 1) row_hi = height - 1;
+    if (row_hi < row_lo) return -1;
+    const size_t npx = (size_t)(row_hi - row_lo + 1) * (size_t)width;
+    contract_px* st = (contract_px*)calloc(npx + 1, sizeof(contract_px));
+    int rc = st ? 0 : -2;
+    const int nstrips = (height + GSO_STRIP - 1) / GSO_STRIP;
+    int64_t* start = NULL;
+    int32_t *slo = NULL, *shi = NULL, *list = NULL;
+    if (!rc) {
+        start = (int64_t*)calloc((size_t)nstrips + 1, sizeof(int64_t));
+        slo = (int32_t*)malloc((size_t)n * 4 + 4);
+        shi = (int32_t*)malloc((size_t)n * 4 + 4);
+        if (!start || !slo || !shi) rc = -2;
+    }
+    if (!rc) {
+        /* bin splat ranks to the strips of rows [row_lo, row_hi], in rank order (blend_parallel_rows) */
+        for (int64_t r = 0; r < n; ++r) {
+            const gso_record* o = &rec[perm[r]];
+            slo[r] = 1; shi[r] = 0;
+            if (!o->visible) continue;
+            const float ylo = o->cy - o->hy - 0.5f, yhi = o->cy + o->hy - 0.5f;
+            const float xlo = o->cx - o->hx - 0.5f, xhi = o->cx + o->hx - 0.5f;
+            if (!(yhi >= (float)row_lo && ylo <= (float)row_hi)) continue;
+            if (!(xhi >= 0.0f && xlo <= (float)(width - 1))) continue;
+            const int j0 = (int)ceilf(fmaxf(ylo, (float)row_lo));
+            const int j1 = (int)floorf(fminf(yhi, (float)row_hi));
+            if (j1 < j0) continue;
+            slo[r] = j0 / GSO_STRIP;
+            shi[r] = j1 / GSO_STRIP;
+        }
+        for (int64_t r = 0; r < n; ++r)
+            for (int k = slo[r]; k <= shi[r]; ++k) ++start[k + 1];
+        for (int k = 0; k < nstrips; ++k) start[k + 1] += start[k];
+        list = (int32_t*)malloc((size_t)start[nstrips] * 4 + 4);
+        if (!list) rc = -2;
+    }
+    if (!rc) {
+        int64_t* cur = (int64_t*)malloc(((size_t)nstrips + 1) * sizeof(int64_t));
+        if (!cur) rc = -2;
+        else {
+            memcpy(cur, start, ((size_t)nstrips + 1) * sizeof(int64_t));
+            for (int64_t r = 0; r < n; ++r)
+                for (int k = slo[r]; k <= shi[r]; ++k) list[cur[k]++] = perm[r];
+            free(cur);
+        }
+    }
+    if (!rc) {
+        for (size_t p = 0; p < npx; ++p) {
+            out_eo[4 * p] = out_eo[4 * p + 1] = out_eo[4 * p + 2] = 0.0f; out_eo[4 * p + 3] = 1.0f;
+            out_plain[4 * p] = out_plain[4 * p + 1] = out_plain[4 * p + 2] = 0.0f; out_plain[4 * p + 3] = 1.0f;
+        }
+        contract_args A = {t_min, (double)eta, seed, depth, width, row_lo, out_eo, out_plain, st};
+        const int nt = threads > 1 ? threads : 1;
+        (void)nt;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nt)
+        for (int k = 0; k < nstrips; ++k) {
+            int lo = k * GSO_STRIP;
+            int hi = (lo + GSO_STRIP - 1 < height - 1) ? lo + GSO_STRIP - 1 : height - 1;
+            if (lo < row_lo) lo = row_lo;
+            if (hi > row_hi) hi = row_hi;
+            if (hi < lo) continue;
+            for (int64_t q = start[k]; q < start[k + 1]; ++q) contract_splat_rows(&rec[list[q]], list[q], lo, hi, &A);
+        }
+        int64_t namb = 0, nbad = 0;
+        for (size_t p = 0; p < npx; ++p) {
+            const contract_px* c = st + p;
+            out_plain[4 * p + 3] = 1.0f - out_plain[4 * p + 3];
+            const float a = 1.0f - out_eo[4 * p + 3];
+            out_eo[4 * p + 3] = a;
+            double b[4] = {c->B[0], c->B[1], c->B[2], c->E + ulp_of((double)a + c->E)};
+            if (c->amb) {
+                for (int k = 0; k < 3; ++k) b[k] += c->X * c->M[k];
+                b[3] += c->X;
+                ++namb;
+            }
+            for (int k = 0; k < 4; ++k) {
+                float v = (float)b[k];
+                if ((double)v < b[k]) v = nextafterf(v, INFINITY);
+                out_bound[4 * p + k] = c->bad ? INFINITY : v;
+            }
+            nbad += c->bad;
+        }
+        if (stats) { stats[0] = namb; stats[1] = nbad; }
+    }
+    free(st); free(start); free(slo); free(shi); free(list);
+    return rc;
+}
+
+int gso_render_contract_rows(const gso_splats* s, const gso_frame* f, const float* depth, int row_lo, int row_hi,
+                             float t_min, float eta, uint64_t seed, float* out_eo, float* out_plain, float* out_bound,
+                             int64_t* stats, int threads)
+{
+    if (!s || !f) return -1;
+    gso_record* rec = (gso_record*)malloc((size_t)(s->n + 1) * sizeof(gso_record));
+    int32_t* perm = (int32_t*)malloc((size_t)(s->n + 1) * 4);
+    int rc = (!rec || !perm) ? -2 : gso_preprocess(s, f, rec);
+    if (!rc) rc = argsort_records(rec, s->P, s->n, perm);
+    if (!rc)
+        rc = gso_blend_contract_rows(rec, perm, s->n, f->width, f->height, depth, row_lo, row_hi, t_min, eta, seed, out_eo,
+                                     out_plain, out_bound, stats, threads);
+    free(rec);
+    free(perm);
+    return rc;
+}
+
+double gso_contract_eta(void) { return GSO_CONTRACT_ETA; }
+
+int gso_render_contract(const gso_splats* s, const gso_frame* f, const float* depth, float t_min, float eta, uint64_t seed,
+                        float* out_eo, float* out_plain, float* out_bound, int64_t* stats, int threads)
+{
+    if (!f) return -1;
+    return gso_render_contract_rows(s, f, depth, 0, f->height - 1, t_min, eta, seed, out_eo, out_plain, out_bound, stats,
+                                    threads);
+}
+
+/* ------------------------------------------------------------------------- */
 /* Wireframe overlay: shaders/GSplatShaderSource.h:22-110, geometry src/GR_GSplat.C:374-421.
  * Line rule = the contract's stand-in for GL's diamond-exit rule (see k_wire.h / DESIGN.md).          */
 static void wire_edge(float x0, float y0, float x1, float y1, int width, int height, uint64_t frag, uint64_t* zbuf)

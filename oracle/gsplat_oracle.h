@@ -156,6 +156,30 @@ int gso_render_rows(const gso_splats* s, const gso_frame* f, int row_lo, int row
 int gso_host_sort_only(const float* P, int64_t n, const float cam_pos[3], int32_t* perm);
 int gso_host_sort_from(const float* P, int64_t n, const float cam_pos[3], const int32_t* order0, int32_t* perm);
 
+/* The product's frame and a bound on a GPU frame's distance from it ("early-out"; the .c file derives it).
+ * One pass over the records and depth order of gso_render fills, per pixel of rows [row_lo, row_hi] (out_* hold those rows
+ * only, float[(row_hi - row_lo + 1) * width * 4], row 0 = row_lo):
+ *   out_plain  the frame without early-out: bit-identical to gso_render / gso_render_depth (depth nullable);
+ *   out_eo     the frame with the product's early-out: a fragment is composited only while T >= t_min (T tested before it);
+ *   out_bound  per channel, a bound on |GPU - out_eo| when each fragment's alpha may be off by a relative GSO_CONTRACT_ETA
+ *              (+inf on pixels covered by a colour beyond 1e30).
+ * seed != 0 (tests only): every alpha below 1 is scaled by 1 + xi * eta, xi in [-1, 1] a hash of (seed, splat, pixel).
+ * stats (nullable, int64[2]): pixels whose stop was ambiguous, pixels with an infinite bound.  threads <= 1: serial.     */
+#define GSO_CONTRACT_T_MIN 6.103515625e-05f   /* 2^-14: k_blend.h GSR_T_MIN */
+/* relative error allowed between two 2^x: gso_exp2f (<= 2.8 ulp) and v_exp_f32 (1 ulp), times a safety factor of 2;
+ * one ulp of a float y is at most 2^-23 y */
+#define GSO_CONTRACT_ETA (2.0 * (2.8 + 1.0) * 1.1920928955078125e-07)
+int gso_render_contract(const gso_splats* s, const gso_frame* f, const float* depth, float t_min, float eta, uint64_t seed,
+                        float* out_eo, float* out_plain, float* out_bound, int64_t* stats, int threads);
+int gso_render_contract_rows(const gso_splats* s, const gso_frame* f, const float* depth, int row_lo, int row_hi,
+                             float t_min, float eta, uint64_t seed, float* out_eo, float* out_plain, float* out_bound,
+                             int64_t* stats, int threads);
+/* the same from records and a depth order (perm may be any order: tests build mutant frames with it) */
+int gso_blend_contract_rows(const gso_record* rec, const int32_t* perm, int64_t n, int width, int height, const float* depth,
+                            int row_lo, int row_hi, float t_min, float eta, uint64_t seed, float* out_eo, float* out_plain,
+                            float* out_bound, int64_t* stats, int threads);
+double gso_contract_eta(void);
+
 /* number of OpenMP threads the parallel entry points would use */
 /* pixels where a rasteriser's coverage / discard / depth rule may decide differently from the analytic quad (see the .c file) */
 int gso_edge_mask(const gso_record* rec, int64_t n, int width, int height, float delta_px, float eps_log2,

@@ -104,6 +104,11 @@ def lib() -> C.CDLL:
         L.gso_storage_order.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
         L.gso_set_tie_order.argtypes = [C.c_int]
         L.gso_set_tie_order.restype = None
+        L.gso_render_contract_rows.argtypes = [C.POINTER(gso_splats), C.POINTER(gso_frame), C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                               C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.gso_blend_contract_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                              C.c_float, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.gso_contract_eta.restype = C.c_double
         _lib = L
     return _lib
 
@@ -219,6 +224,56 @@ def render_depth(splats, cam, depth, origin=(0, 0, 0)) -> np.ndarray:
     rc = lib().gso_render_depth(C.byref(pk.struct), C.byref(f), None if d is None else d.ctypes.data, out.ctypes.data)
     assert rc == 0
     return out
+
+
+T_MIN = float(np.float32(2.0 ** -14))             # GSO_CONTRACT_T_MIN: the product's per-pixel early-out (k_blend.h GSR_T_MIN)
+
+
+def contract_eta() -> float:
+    """GSO_CONTRACT_ETA: the relative error of a fragment's alpha the contract bound allows (two 2^x implementations)"""
+    return float(lib().gso_contract_eta())
+
+
+def _contract_outputs(width, lo, hi):
+    shape = (hi - lo, width, 4)
+    return tuple(np.zeros(shape, dtype=np.float32) for _ in range(3)) + (np.zeros(2, dtype=np.int64),)
+
+
+def _contract_result(eo, plain, bound, st):
+    return eo, plain, bound, {"ambiguous": int(st[0]), "infinite": int(st[1])}
+
+
+def render_contract(splats, cam, origin=(0, 0, 0), depth=None, t_min=T_MIN, eta=0.0, seed=0, threads=0, rows=None):
+    """One pass over the frame's records (gso_render_contract): returns (eo, plain, bound, stats).
+    plain = render() / render_depth() bit for bit; eo = the frame with the product's early-out (composite while T >= t_min);
+    bound = per pixel and channel, what a GPU frame may differ from eo by (+inf where a colour exceeds 1e30);
+    stats = {"ambiguous": pixels whose stop was ambiguous, "infinite": pixels with an infinite bound}.
+    seed != 0 (tests): every alpha below 1 is scaled by 1 + xi * eta, xi in [-1, 1] a hash of (seed, splat, pixel).
+    rows = (row_lo, row_hi): only rows [row_lo, row_hi), arrays [row_hi - row_lo, W, 4] (render_rows)."""
+    pk = _SplatPack(splats)
+    f = make_frame(cam, origin)
+    lo, hi = (0, f.height) if rows is None else (int(rows[0]), int(rows[1]))
+    eo, plain, bound, st = _contract_outputs(f.width, lo, hi)
+    d = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32).reshape(f.height, f.width)
+    rc = lib().gso_render_contract_rows(C.byref(pk.struct), C.byref(f), None if d is None else d.ctypes.data, lo, hi - 1,
+                                        float(t_min), float(eta), int(seed), eo.ctypes.data, plain.ctypes.data,
+                                        bound.ctypes.data, st.ctypes.data, int(threads) if threads else max_threads())
+    assert rc == 0
+    return _contract_result(eo, plain, bound, st)
+
+
+def blend_contract(rec, perm, width, height, depth=None, t_min=T_MIN, eta=0.0, seed=0, threads=0):
+    """render_contract from records and a depth order (any order: mutant frames in tests)"""
+    rec = np.ascontiguousarray(rec)
+    perm = np.ascontiguousarray(perm, dtype=np.int32)
+    eo, plain, bound, st = _contract_outputs(width, 0, height)
+    d = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32).reshape(height, width)
+    rc = lib().gso_blend_contract_rows(rec.ctypes.data, perm.ctypes.data, perm.shape[0], int(width), int(height),
+                                       None if d is None else d.ctypes.data, 0, int(height) - 1, float(t_min), float(eta),
+                                       int(seed), eo.ctypes.data, plain.ctypes.data, bound.ctypes.data, st.ctypes.data,
+                                       int(threads) if threads else max_threads())
+    assert rc == 0
+    return _contract_result(eo, plain, bound, st)
 
 
 def render_wire(splats, cam) -> np.ndarray:

@@ -141,3 +141,104 @@ class HipBuffers:
         for p in self.ptrs:
             self.hip.hipFree(p)
         self.ptrs = []
+
+
+# The blend contract ("early-out"): a GPU frame differs from the oracle's only by the per-pixel early-out (the
+# oracle restates it: out_eo) and by the last bits of 2^x (out_bound, per pixel and channel).  Every GPU-vs-oracle comparison
+# goes through check_contract; the north-star 1e-3 against the plain frame stays as well.
+CONTRACT_TOL = 1e-3
+
+
+def check_contract(img, oracle, splats, cam, origin=(0, 0, 0), depth=None, rows=None, threads=0, label="", ret_plain=False):
+    """assert |img - plain| <= 1e-3, |img - eo| <= bound on every pixel and channel, img finite; returns the worst err / bound
+    (printed as a CONTRACT line), and the oracle's plain frame too if ret_plain.  rows = (lo, hi): img holds rows [lo, hi) only."""
+    eo, plain, bound, _ = oracle.render_contract(splats, cam, origin=origin, depth=depth, rows=rows, threads=threads)
+    assert img.shape == plain.shape, (img.shape, plain.shape)
+    assert np.isfinite(img).all()
+    e_plain = np.abs(img - plain)
+    err = np.abs(img.astype(np.float64) - eo.astype(np.float64))
+    fin = np.isfinite(bound)
+    ratio = np.zeros(err.shape)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio[fin] = np.where(bound[fin] > 0, err[fin] / bound[fin], np.where(err[fin] > 0, np.inf, 0.0))
+    worst = float(ratio.max(initial=0.0))
+    print(f"CONTRACT {label or 'frame'} {img.shape[1]}x{img.shape[0]}: worst err/bound = {worst:.4f}, "
+          f"max|err| = {float(err[fin].max(initial=0.0)):.3e}, median bound = {float(np.median(bound[fin])) if fin.any() else 0.0:.3e}, "
+          f"max|img - plain| = {float(e_plain.max(initial=0.0)):.3e}")
+    assert e_plain.max(initial=0.0) <= CONTRACT_TOL, \
+        f"max err {e_plain.max()} at {np.unravel_index(e_plain.argmax(), e_plain.shape)}"
+    if not (worst <= 1.0):
+        over = fin & (err > bound)
+        y, x, ch = np.unravel_index(int(ratio.argmax()), ratio.shape)
+        raise AssertionError(f"{int(over.any(axis=2).sum())} pixels outside the contract bound; worst at (x, y, channel) = "
+                             f"({x}, {y}, {ch}): |img - eo| = {err[y, x, ch]:.4e}, bound = {bound[y, x, ch]:.4e}, "
+                             f"ratio = {worst:.3f}, img = {img[y, x].tolist()}, eo = {eo[y, x].tolist()}")
+    return (worst, plain) if ret_plain else worst
+
+
+def camera_axes(cam):
+    """(position, rows = camera x / y / z axes in world space) of a camera, float64"""
+    V = np.asarray(cam.view, np.float64).reshape(4, 4).T
+    R = V[:3, :3]
+    return -R.T @ V[:3, 3], R
+
+
+def unproject(cam, X, Y, D):
+    """float64 world points at GL window coordinates (X, Y) (y up, pixel centres at +0.5) and view distance D, for a
+    perspective camera whose projection has no off-centre terms"""
+    X, Y, D = (np.asarray(a, np.float64) for a in np.broadcast_arrays(X, Y, D))
+    Pm = np.asarray(cam.proj, np.float64).reshape(4, 4).T
+    pos, R = camera_axes(cam)
+    xc = (2.0 * X / cam.width - 1.0) * D / Pm[0, 0]
+    yc = (2.0 * Y / cam.height - 1.0) * D / Pm[1, 1]
+    return pos + xc[..., None] * R[0] + yc[..., None] * R[1] - D[..., None] * R[2]
+
+
+def world_sigma(cam, s_px, D):
+    """isotropic world scale whose projected axis s1 = sqrt(2 lambda) is about s_px pixels at view distance D"""
+    focal = cam.width * float(np.asarray(cam.proj, np.float64).reshape(4, 4).T[0, 0]) * 0.5
+    return np.asarray(s_px, np.float64) * np.asarray(D, np.float64) / (np.sqrt(2.0) * focal)
+
+
+def make_splats(pkg, P, sigma, opacity, Cd, orient=None, sh=None):
+    """a Splats from float64 arrays: P [n, 3], sigma [n] or [n, 3], opacity [n], Cd [n, 3]; orient (x, y, z, w) [n, 4]
+    (identity when None); sh = (shx, shy, shz) float [n, 15] each or None"""
+    P = np.asarray(P, np.float64).reshape(-1, 3)
+    n = P.shape[0]
+    sig = np.asarray(sigma, np.float64)
+    sig = np.broadcast_to(sig[:, None] if sig.ndim == 1 else sig, (n, 3))
+    if orient is None:
+        orient = np.tile([0.0, 0.0, 0.0, 1.0], (n, 1))
+    f16 = pkg.scenes.f16bits
+    shs = [None, None, None]
+    if sh is not None:
+        for k in range(3):
+            shs[k] = np.zeros((n, 16), np.uint16)
+            shs[k][:, :15] = f16(np.asarray(sh[k], np.float64).reshape(n, 15))
+    return pkg.scenes.Splats(np.ascontiguousarray(P, np.float32), f16(np.broadcast_to(np.asarray(Cd, np.float64), (n, 3))),
+                             np.ascontiguousarray(np.broadcast_to(np.asarray(opacity, np.float64), (n,)), np.float32),
+                             f16(sig), f16(np.asarray(orient, np.float64)), *shs)
+
+
+def veil_scene(pkg, cam, n=3000, seed=0, colours=(0.0, 1.0)):
+    """a veil: n splats of opacity 0.005-0.05 and 10-40 px, in a ball 0.3 across at the camera's pivot; stacks hundreds deep,
+    most pixels unsaturated"""
+    rng = np.random.default_rng(seed)
+    pos, R = camera_axes(cam)
+    D = float(np.linalg.norm(pos))
+    P = rng.normal(0.0, 0.15, (n, 3))
+    return make_splats(pkg, P, world_sigma(cam, rng.uniform(15.0, 50.0, n), D), rng.uniform(0.005, 0.05, n),
+                       rng.uniform(colours[0], colours[1], (n, 3)))
+
+
+def stop_scene(pkg, cam, n=500, seed=0):
+    """a deep stack of wide, faint splats along the view axis (distinct depths, lateral jitter): each pixel's T falls through
+    2^-14 after a few hundred fragments, and on many pixels it lands within the bound's error of 2^-14 -- the early-out's
+    decision is ambiguous there"""
+    rng = np.random.default_rng(seed)
+    D = np.linspace(2.0, 3.5, n) + rng.uniform(0.0, 1e-3, n)
+    X = cam.width * (0.5 + rng.uniform(-0.05, 0.05, n))
+    Y = cam.height * (0.5 + rng.uniform(-0.05, 0.05, n))
+    P = unproject(cam, X, Y, D)
+    return make_splats(pkg, P, world_sigma(cam, rng.uniform(0.4, 0.8, n) * max(cam.width, cam.height), D),
+                       rng.uniform(0.02, 0.04, n), rng.uniform(0.0, 1.0, (n, 3)))

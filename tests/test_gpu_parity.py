@@ -4,8 +4,12 @@ Tolerance: north_star asks for <= 1e-3 per channel.  Because the kernels impleme
 float32 op-order contract as the oracle, every per-splat record must match BIT FOR BIT and
 the image may differ only by the blend kernel's early-out (bound 2^-14 * max colour).
 """
+import os
+
 import numpy as np
 import pytest
+
+from helpers import check_contract
 
 pytestmark = pytest.mark.gpu
 
@@ -13,12 +17,10 @@ TOL = 1e-3
 REC_FIELDS = ("cx", "cy", "a1x", "a1y", "b1x", "b1y", "r", "g", "b", "la")
 
 
-def _check_image(img, ref, tol=TOL):
-    assert img.shape == ref.shape
-    err = np.abs(img - ref)
-    assert np.isfinite(img).all()
-    assert err.max() <= tol, f"max err {err.max()} at {np.unravel_index(err.argmax(), err.shape)}"
-    return float(err.max())
+def _check_contract(img, oracle, splats, cam, ret_plain=False, **kw):
+    """the blend contract (helpers.check_contract): |img - oracle| <= 1e-3 and |img - oracle's early-out frame| <= its bound"""
+    return check_contract(img, oracle, splats, cam, label=os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0],
+                          ret_plain=ret_plain, **kw)
 
 
 @pytest.mark.parametrize("n,w,h,sh,order,frame", [
@@ -36,8 +38,7 @@ def test_frame_matches_oracle(pkg, oracle, engine, n, w, h, sh, order, frame):
     engine.upload(splats)
     img = engine.render(cam)
     cam_o = pkg.camera.make_camera(w, h, sh_order=order if sh else 0, frame=frame)
-    ref = oracle.render(splats, cam_o)
-    _check_image(img, ref)
+    _check_contract(img, oracle, splats, cam_o)
 
 
 def test_records_bit_exact(pkg, oracle, engine):
@@ -193,9 +194,8 @@ def test_framebuffers_beyond_4096_pixels(pkg, oracle, engine, w, h, n, big):
     img = engine.render(cam)
     st = engine.stats()
     assert st["stiles_x"] * st["stiles_y"] <= 256
-    ref = oracle.render(splats, cam, threads=oracle.max_threads())
+    _, ref = _check_contract(img, oracle, splats, cam, ret_plain=True)
     assert ref[..., 3].max() > 0.5
-    _check_image(img, ref)
     # every list in depth order, and holding at least the splats whose exact tile rect reaches the super-tile
     ls, le, pv = engine.debug_tile_lists()
     dev = engine.debug_records(splats.n)
@@ -257,9 +257,8 @@ def test_the_largest_framebuffer(pkg, oracle, engine):
         for y0 in (0, 8000, h - 96):
             got = np.empty((96, w, 4), np.float32)
             assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), C.c_void_p(p.value + y0 * w * 16), C.c_size_t(got.nbytes), 2) == 0
-            ref = oracle.render_rows(splats, cam, y0, y0 + 96, threads=oracle.max_threads())
+            _, ref = _check_contract(got, oracle, splats, cam, rows=(y0, y0 + 96), ret_plain=True)
             assert ref[..., 3].max() > 0.2
-            _check_image(got, ref)
             del ref
         # the same frame with the heaviest-first tile order and occlusion culling forced on: bit-identical
         first = np.empty((256, w, 4), np.float32)
@@ -311,8 +310,7 @@ def test_edge_cases(pkg, oracle, engine):
     s.alpha[:] = 1.0
     engine.upload(s)
     img = engine.render(cam)
-    ref = oracle.render(s, cam)
-    _check_image(img, ref)
+    _check_contract(img, oracle, s, cam)
     assert img[..., 3].max() <= 1.0 + 1e-6
     _same_with_culling(pkg, engine, cam, img)
 
@@ -359,21 +357,23 @@ def test_renderer_shim_frame_protocol(pkg, oracle):
                               ("P", "Cd", "alpha", "scale", "orient", "shx", "shy", "shz")])
     origin = (a.barycenter() + b.barycenter()) / np.float32(2)
     assert np.array_equal(R.origin(), origin)
-    ref = oracle.render(cat, cam, origin=origin)
-    _check_image(img, ref)
+    # the shim derives the camera position itself (the inverse of the view matrix in double, src/GSplatRenderer.C:556-562): the SH
+    # view directions and sort keys of its frame follow that position, which may differ from numpy's in the last bit
+    cam.cam_pos = R.lastCameraPos()
+    _check_contract(img, oracle, cat, cam, origin=origin)
     # same active set -> no restaging; only A active -> restage
     R.frame(cam, [ida, idb])
     assert R.query(R.Q_STAGING_COUNT) == 1
     img_a = R.frame(cam, [ida])
     assert R.query(R.Q_STAGING_COUNT) == 2
-    _check_image(img_a, oracle.render(a, cam, origin=a.barycenter()))
+    _check_contract(img_a, oracle, a, cam, origin=a.barycenter())
     R.close()
 
 
 # ---------------------------------------------------------------------------------------------
 # golden fixtures: the reference's own GLSL on a software rasteriser (tests/golden/make_goldens.py)
 from helpers import (HipBuffers, check_against_golden, check_wire_against_golden, engine_render_golden, golden_names, golden_uncertainty,  # noqa: E402
-                     load_golden, oracle_render_golden)
+                     load_golden)
 
 
 @pytest.mark.parametrize("name", golden_names())
@@ -383,7 +383,7 @@ def test_golden_reference_glsl_images(pkg, oracle, engine, name):
     img = engine_render_golden(engine, d, c)                   # (g8: depth-tested against the fixture's depth buffer)
     # vs the reference GLSL: every pixel beyond the 1e-3 budget sits on a quad edge / at a discard threshold (helpers.py)
     check_against_golden(img, d["image_reference_glsl"], uncertainty=golden_uncertainty(oracle, d, s, c), extra_tol=2.0 ** -14)
-    _check_image(img, oracle_render_golden(oracle, d, s, c))   # vs the oracle: strict 1e-3 on every pixel
+    _check_contract(img, oracle, s, c, origin=d["origin"], depth=d["depth"] if "depth" in d.files else None)   # vs the oracle
     # vertex stage vs the captured reference vertex shader outputs
     dev = engine.debug_records(s.n)
     vs = d["vs_out"]
@@ -405,7 +405,7 @@ def test_baseline_config_c2_full_size(pkg, oracle, engine):
     cam = pkg.camera.make_camera(cfg["width"], cfg["height"], sh_order=cfg["sh_order"], frame=0)
     engine.upload(splats)
     img = engine.render(cam)
-    _check_image(img, oracle.render(splats, cam, threads=oracle.max_threads()))
+    _check_contract(img, oracle, splats, cam)
 
 
 def test_baseline_config_c3_through_the_scene_pipeline(pkg, oracle, engine, tmp_path):
@@ -421,14 +421,13 @@ def test_baseline_config_c3_through_the_scene_pipeline(pkg, oracle, engine, tmp_
     cam = pkg.camera.make_camera(cfg["width"], cfg["height"], sh_order=cfg["sh_order"], frame=0)
     engine.upload(splats, origin=splats.barycenter())
     img = engine.render(cam)
-    ref = oracle.render(splats, cam, origin=splats.barycenter(), threads=oracle.max_threads())
-    _check_image(img, ref)
+    _check_contract(img, oracle, splats, cam, origin=splats.barycenter())
     st = engine.stats()
     assert st["n_visible"] > 900_000 and img[..., 3].max() > 0.99
     # the synthetic stand-in bench.py uses for C3 (make_config) as well
     s2, _ = pkg.scenes.make_config("C3")
     engine.upload(s2)
-    _check_image(engine.render(cam), oracle.render(s2, cam, threads=oracle.max_threads()))
+    _check_contract(engine.render(cam), oracle, s2, cam)
 
 
 def test_baseline_config_c5_4k_eight_shards_device_stitch(pkg, oracle, engine):
@@ -441,9 +440,7 @@ def test_baseline_config_c5_4k_eight_shards_device_stitch(pkg, oracle, engine):
     cam = pkg.camera.make_camera(W, H, sh_order=3, frame=11)
     engine.upload(splats)
     full = engine.render(cam)
-    ref = oracle.render(splats, cam, threads=oracle.max_threads())
-    _check_image(full, ref)
-    del ref
+    _check_contract(full, oracle, splats, cam)
     G = 8
     hb = HipBuffers()
     try:
@@ -509,7 +506,7 @@ def test_sort_cache_and_rotation_only_camera(pkg, oracle, engine):
                              inv_object=cam.inv_object, view=np.ascontiguousarray(v2.T, np.float32).reshape(16),
                              proj=cam.proj, cam_pos=cam.cam_pos, width=cam.width, height=cam.height, sh_order=3)
     img = engine.render(cam2)
-    _check_image(img, oracle.render(splats, cam2))
+    _check_contract(img, oracle, splats, cam2)
     engine.set_option(pkg.engine.OPT_SORT_CACHE, 0)
     assert np.array_equal(img, engine.render(cam2))          # forced re-sort gives the same pixels
     engine.set_option(pkg.engine.OPT_SORT_CACHE, 1)
@@ -596,8 +593,7 @@ def test_baseline_config_c4_full_size_properties(pkg, oracle, engine):
             out[y0:y1] = band[lrow * 16: lrow * 16 + (y1 - y0)]
     engine.set_row_shard(0, 1)
     assert np.array_equal(out, full)
-    ref = oracle.render(splats, cam, threads=oracle.max_threads())
-    _check_image(full, ref)
+    _check_contract(full, oracle, splats, cam)
     # ... and against the reference's own GLSL program on this very scene: the band of tile rows held by the fixture
     import os
     from helpers import GOLDEN_DIR
@@ -659,8 +655,7 @@ def test_maximum_size_through_the_shim(pkg, oracle):
     # does, src/GSplatRenderer.C:556-562); with 8.4 M splats the sort has many near-ties, so the oracle
     # must be given exactly that position rather than numpy's last-ulp-different inverse
     cam.cam_pos = R.lastCameraPos()
-    ref = oracle.render(cat, cam, origin=origin, threads=oracle.max_threads())
-    _check_image(img, ref)
+    _check_contract(img, oracle, cat, cam, origin=origin)
     R.close()
 
 
@@ -677,8 +672,7 @@ def test_depth_tested_compositing(pkg, oracle, engine):
     depth[:20] = 0.0                                         # a strip that hides everything
     engine.upload(splats)
     img = engine.render_depth(cam, depth)
-    ref = oracle.render_depth(splats, cam, depth)
-    _check_image(img, ref)
+    _check_contract(img, oracle, splats, cam, depth=depth)
     assert np.count_nonzero(img[:20]) == 0
     free = engine.render(cam)
     assert np.array_equal(engine.render_depth(cam, np.ones_like(depth)), free)     # depth = far plane: nothing rejected
@@ -774,14 +768,14 @@ def test_list_buffer_regrows_behind_a_speculative_back_end(pkg, oracle):
             img = eng.render(cam)
             d1 = eng.stats()["pairs_total"]
             assert d1 > 4 * max(d0, 1)
-            _check_image(img, oracle.render(big, cam))
+            _check_contract(img, oracle, big, cam)
             assert np.array_equal(img, eng.render(cam))      # now non-speculative growth is over: same pixels
             huge = pkg.scenes.make_scene(300000, seed=7, sh=True)            # 5x the splats on 4.3x the pixels
             eng.upload(huge)
             cam2 = pkg.camera.make_camera(1920, 1080, sh_order=3, frame=2)
             img2 = eng.render(cam2)
             assert eng.stats()["pairs_total"] > 2 * d1
-            _check_image(img2, oracle.render(huge, cam2, threads=oracle.max_threads()))
+            _check_contract(img2, oracle, huge, cam2)
     finally:
         eng.close()
 
@@ -809,7 +803,7 @@ def test_random_frames_match_oracle(pkg, oracle, engine, seed):
         engine.set_option(pkg.engine.OPT_SUPER_TILE, 0)
         engine.set_option(pkg.engine.OPT_FRAMES_IN_FLIGHT, 2)
     cam_o = pkg.camera.make_camera(w, h, sh_order=order if sh else 0, frame=frame)   # (no SH data: the doSH gate forces order 0)
-    _check_image(img, oracle.render(splats, cam_o, threads=oracle.max_threads()))
+    _check_contract(img, oracle, splats, cam_o)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -849,7 +843,7 @@ def test_multi_gpu_in_library_matches_single_gpu(pkg, oracle, engine, ranks, lay
             hb.free()
         assert np.array_equal(got_d, engine.render_depth(cam, depth))
         assert np.array_equal(M.render(cam, depth), got_d)
-    _check_image(want, oracle.render(splats, cam))
+    _check_contract(want, oracle, splats, cam)
 
 
 @pytest.mark.parametrize("direct,items", [("2", "1"), ("-1", "2"), ("0", "4"), ("2", "4")])
@@ -922,7 +916,8 @@ def test_multi_gpu_behind_the_renderer_verbs(pkg, oracle):
         i2 = R2.registerUpdate(0x1, (1, 0, 0, 0), 0, a)
         img1, img2 = R1.frame(cam, [i1]), R2.frame(cam, [i2])
         assert R2.query(R2.Q_RENDER_COUNT) == 1 and np.array_equal(img1, img2)
-        _check_image(img2, oracle.render(a, cam, origin=a.barycenter()))
+        cam.cam_pos = R2.lastCameraPos()                          # the position the shim derived (test_renderer_shim_frame_protocol)
+        _check_contract(img2, oracle, a, cam, origin=a.barycenter())
     finally:
         R1.close(); R2.close()
 
@@ -1014,7 +1009,7 @@ def test_position_keyed_order_skips_the_sort_on_a_rotation(pkg, oracle, cull):
         assert eng.stats()["sorts_skipped"] == before                   # ... and a move sorts again
         assert np.array_equal(eng.render(pkg.camera.rotated_in_place(moved, 5)), ref.render(pkg.camera.rotated_in_place(moved, 5)))
         assert eng.stats()["sorts_skipped"] > before
-        _check_image(eng.render(turns[2]), oracle.render(splats, turns[2], threads=oracle.max_threads()))
+        _check_contract(eng.render(turns[2]), oracle, splats, turns[2])
     finally:
         eng.close(); ref.close()
 
@@ -1054,7 +1049,7 @@ def test_prim_ingest_renders_like_the_oracle(pkg, oracle, scheme):
         R.generateRenderGeometry(r); R.render(r, False); R.postRender()
         assert R.query(R.Q_RENDER_COUNT) == 1
         cam.cam_pos = R.lastCameraPos()
-        _check_image(out, oracle.render(ref_s, cam, origin=R.origin(), threads=oracle.max_threads()))
+        _check_contract(out, oracle, ref_s, cam, origin=R.origin())
         assert out[..., 3].max() > 0.5
     finally:
         P.close(); R.close()
@@ -1079,7 +1074,7 @@ def test_occlusion_culling_is_exact(pkg, oracle, shard):
         eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 0)
         want = [eng.render(c).copy() for c in cams]
         if count == 1:
-            _check_image(want[0], oracle.render(splats, cams[0], threads=oracle.max_threads()))
+            _check_contract(want[0], oracle, splats, cams[0])
         vis_full = eng.stats()["n_visible"]
         for fif in (1, 2):
             eng.set_option(pkg.engine.OPT_FRAMES_IN_FLIGHT, fif)
@@ -1195,10 +1190,10 @@ def test_cluster_culling_and_storage_order_are_invisible(pkg, oracle):
                 for c in cams:
                     want.append(ref.render(c).copy())
                     vis.append(ref.stats()["n_visible"])
-                _check_image(want[0], oracle.render(splats, cams[0], threads=oracle.max_threads()))
+                _check_contract(want[0], oracle, splats, cams[0])
                 if storage == 1:   # ... and the frames of the other projections are the oracle's frames
                     for k in range(n_plain, len(cams)):
-                        _check_image(want[k], oracle.render(splats, cams[k], threads=oracle.max_threads()))
+                        _check_contract(want[k], oracle, splats, cams[k])
             finally:
                 oracle.set_tie_order(False)
             for cull in (0, 2):
@@ -1245,7 +1240,7 @@ def test_occlusion_culling_on_scenes_with_sky_and_silhouettes(pkg, oracle, kind)
         ref.set_option(pkg.engine.OPT_CLUSTER_CULL, 0)
         ref.upload(splats); eng.upload(splats)
         want = [ref.render(c).copy() for c in cams]
-        _check_image(want[0], oracle.render(splats, cams[0], threads=oracle.max_threads()))
+        _check_contract(want[0], oracle, splats, cams[0])
         a = want[0][..., 3]
         assert (a < 0.01).mean() > 0.1 and (a > 0.99).mean() > 0.3        # empty sky AND opaque regions in one frame
         vis_full = ref.stats()["n_visible"]
@@ -1394,7 +1389,7 @@ def test_lazy_colour_is_exact_and_predicts(pkg, oracle):
         eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 0)      # (culled frames colour what K1 kept instead: their own test)
         eng.set_option(pkg.engine.OPT_LAZY_COLOUR, 0)
         want = [eng.render(c) for c in cams]
-        _check_image(want[0], oracle.render(splats, cams[0], threads=oracle.max_threads()))
+        _check_contract(want[0], oracle, splats, cams[0])
         eng.set_option(pkg.engine.OPT_LAZY_COLOUR, 2)         # always (1 = only when the kernels find that it pays)
         eng.upload(splats)                                    # forget the prediction
         eng.stats_reset()
@@ -1583,7 +1578,7 @@ def test_headline_regime_is_the_full_frame_at_full_size(pkg, oracle, config):
         assert st["frames_jumped"] == 1 and st["frames_slab"] >= 1, st
         assert st["frames_repaired"] <= 1, st
         c, img = checked
-        _check_image(img, oracle.render(splats, c, threads=oracle.max_threads()))
+        _check_contract(img, oracle, splats, c)
     finally:
         plain.close(); dflt.close()
 
@@ -1786,7 +1781,7 @@ def test_front_slab_frames_are_exact(pkg, oracle, shard):
         want_d = [plain.render_depth(c, depth).copy() for c in cams[:3]]
         vis_full = plain.stats()["n_visible"]
         if count == 1:
-            _check_image(want[0], oracle.render(splats, cams[0], threads=oracle.max_threads()))
+            _check_contract(want[0], oracle, splats, cams[0])
         eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 3)              # every frame a front-slab frame
         for k, (c, ref) in enumerate(zip(cams, want)):
             assert np.array_equal(eng.render(c), ref), f"front-slab frame {k} differs"
@@ -1938,8 +1933,8 @@ def test_randomised_frames_match_the_oracle(pkg, oracle):
             for k, c in enumerate(cams):
                 img = eng.render(c)
                 if k != 1:
-                    ref = oracle.render(splats, c, threads=oracle.max_threads())
-                    worst = max(worst, _check_image(img, ref))
+                    _, ref = _check_contract(img, oracle, splats, c, ret_plain=True)
+                    worst = max(worst, float(ref[..., 3].max()))
         finally:
             eng.close()
     assert worst > 0.0     # (something was drawn)
@@ -2175,8 +2170,8 @@ def test_depth_culling_and_quadrant_classification_are_invisible(pkg, oracle):
                 assert dut.stats()["n_visible"] * 4 < v_far, (dut.stats()["n_visible"], v_far)
             # against the oracle
             if n == 120000:
-                _check_image(dut.render_depth(cams[1], depths["sphere"]), oracle.render_depth(splats, cams[1], depths["sphere"]))
-                _check_image(dut.render_depth(cams[1], depths["blocks16"]), oracle.render_depth(splats, cams[1], depths["blocks16"]))
+                _check_contract(dut.render_depth(cams[1], depths["sphere"]), oracle, splats, cams[1], depth=depths["sphere"])
+                _check_contract(dut.render_depth(cams[1], depths["blocks16"]), oracle, splats, cams[1], depth=depths["blocks16"])
         finally:
             plain.close(); dut.close()
 
@@ -2208,7 +2203,7 @@ def test_depth_tested_headline_frame_at_full_size(pkg, oracle):
                     keep[name] = got.copy()
         st = dflt.stats()
         assert st["frames_culled"] >= 8, st
-        _check_image(keep["visible"], oracle.render_depth(splats, cams[6], vis))
+        _check_contract(keep["visible"], oracle, splats, cams[6], depth=vis)
         assert np.abs(keep["visible"] - keep["far"]).max() > 0.05           # (this one shows)
         # (the sphere sits 0.16 units under the cloud's surface: every pixel over it saturates in front of it -- the frame is the far-plane
         #  frame to within the kernel's 2^-14 early-out -- but nothing in the library may ASSUME that: the tiles over it end their lists there)
@@ -2245,7 +2240,7 @@ def test_upload_reports_its_stages_and_restaging_is_exact(pkg, oracle):
                 assert np.array_equal(eng.debug_storage_order(n), fresh.debug_storage_order(n))
             finally:
                 fresh.close()
-        _check_image(eng.render(cam), oracle.render(s, cam))
+        _check_contract(eng.render(cam), oracle, s, cam)
     finally:
         eng.close()
 
