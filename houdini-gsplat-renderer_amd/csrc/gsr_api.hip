@@ -40,8 +40,10 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #endif
 #include "k_sort.h"
 #include "k_wire.h"
-#include "gsr_policy.h"
+#include "gsr_frame_plan.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
+static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
+              GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
 
 #define GSR_VERSION_STR "gsplat_hip 0.1.0 (gfx950)"
 #define GSR_MAX_SLOTS 2
@@ -82,17 +84,26 @@ struct SortKey {
     }
 };
 
+// a render call's arguments: what a frame that is rendered again (frame_check, a front slab's phase 2) is rendered from
+struct FrameArgs {
+    gsr_camera cam{};
+    const float* depth = nullptr;      // the caller's depth buffer (host or device), or NULL
+    bool depth_is_device = false;
+    float* out = nullptr;              // the caller's image (host or device)
+    bool out_is_device = false;
+};
+
 // what a queued frame needs again when it is finished (or its back end re-queued)
 struct FrameJob {
+    FrameArgs args;
     bool open = false;
     GsrFrame f{};
     uint32_t n = 0;
     int local_tiles = 0, band_rows = 0, n_super = 0;
     size_t out_px = 0;
     float* target = nullptr;       // device buffer the blend kernel writes
-    float* user_out = nullptr;     // the caller's pointer (host or device)
-    const float* d_depth = nullptr;
-    bool out_is_device = false, timing = false, timing_all = false, use_map = false;
+    const float* d_depth = nullptr;   // the depth buffer on the device (args.depth, or the slot's copy of a host buffer)
+    bool timing = false, timing_all = false, use_map = false;
     bool speculative = false;      // the back end was queued before the pair count was known
     int bn_items = 4;              // splats per thread of the binning kernels (k_binning.h): 4, or fewer for a small frame
     uint32_t bn_grid = 0;          // ... and their grid (workgroups that stride over the blocks)
@@ -107,11 +118,8 @@ struct FrameJob {
     bool direct = false;           // the frame runs on the public stream itself
     uint32_t ticket = 0;           // stamps the frame's pair count in the host mailbox
     // front-slab frames: 0 = an ordinary frame; 1 = the front slab (splats up to the slab key), followed at frame_finish by
-    // 2 = the rest, culled against the tiles phase 1 left opaque.  The call's arguments are kept for queueing phase 2.
+    // 2 = the rest, culled against the tiles phase 1 left opaque
     int phase = 0;
-    gsr_camera cam_arg{};
-    const float* depth_arg = nullptr;
-    int depth_is_device_arg = 0;
     // depth-tested frames: K1 (and k_cluster_cull) drop what lies behind everything the opaque pass left under the tiles it reaches
     bool dcull = false;            // ... against the slot's tile-max depth pyramid, parity dpar
     int dpar = 0;
@@ -119,8 +127,6 @@ struct FrameJob {
     bool dblind = false;           // ... and k_cluster_cull ran without the depth pyramids (they were built beside it, for K1)
     bool dstat = false;            // ... and the depth pyramid pass masked the covered depths with the tiles' status (a culled frame with a valid status)
     bool blend_guess_plain = false;   // the plain blend kernel was launched, guarded by "no pixel is covered" (queue_back_end)
-    float* out_arg = nullptr;
-    int out_is_device_arg = 0;
 };
 
 // Everything one frame in flight owns: its HIP stream, the per-frame HBM arrays, the small
@@ -171,8 +177,6 @@ struct FrameSlot {
                                        // [2..5] the bucket ranges of the two phases' small-frame sorts (k_slab_pick)
     bool slab_dirty = false;           // a phase 1 filled the histogram and no phase 2 followed (its cull pass is what clears it): the
                                        // next front-slab frame clears it itself before it counts
-    uint32_t slab_kept = 0;            // splats phase 1 sent to the depth sort
-    uint32_t slab_kept1 = 0, slab_kept2 = 0;   // ... in this slot's LAST front-slab frame, per phase (0 = none yet): which sort a phase takes
     int32_t* redo = nullptr;           // lazy colour: tiles the plain blend kernel gave up (tile_cap entries)
     int32_t* order = nullptr;          // blockIdx -> tile, heaviest tiles first: written by k_tile_order at the end of a frame
     size_t order_cap = 0;              //   for this slot's next frame (valid while the tile geometry stays what it was)
@@ -201,10 +205,7 @@ struct FrameSlot {
     uint32_t* bkt_key = nullptr;       // small-frame sort (k_sort.h): the bucket regions, BK_BUCKETS x BK_CAP keys ...
     uint2* bkt_val = nullptr;          // ... and payloads
     uint32_t* bkt_cnt = nullptr;       // ... and the bucket counters, BK_STRIDE apart
-    uint32_t surv_hint = 0;            // surviving clusters of this slot's last frame (sizes K1's grid; 0 = unknown)
-    uint32_t kept_hint = 0;            // splats that reached the depth sort in this slot's last frame (picks the sort; 0 = unknown)
-    uint32_t kept_lo = 0, kept_hi = 0; // ... and the smallest / largest of their keys, as float bits of the distance^2 (0, 0 = unknown)
-    bool kept_culled = false;          // ... in a frame that was occlusion-culled (an unculled one keeps ten times as much: no prediction across)
+    GsrSlotHints hints;                // what the slot's last frame kept, from how many clusters, between which keys (gsr_frame_plan.h)
     GsrLocalSortPolicy local_pol;      // back-off of the small-frame sort (gsr_policy.h): a run of > 64 equal keys defeats it EVERY frame
     unsigned long long* h_end = nullptr;      // pinned + mapped: ticket << 32 | violation
     unsigned long long* h_end_dev = nullptr;
@@ -754,7 +755,7 @@ static void drop_geometry(gsr_context* c)
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
         FrameSlot& sl = c->slot[k];
         sl.sort_valid = false; sl.horizon_valid = false; sl.order_valid = false;
-        sl.surv_hint = 0; sl.kept_hint = 0; sl.kept_lo = sl.kept_hi = 0;
+        sl.hints.surv_hint = 0; sl.hints.kept_hint = 0; sl.hints.kept_lo = sl.hints.kept_hi = 0;
     }
 }
 
@@ -854,7 +855,11 @@ extern "C" int gsr_upload_end(gsr_context* c)
     c->prefix_valid = false;           // lazy colour: the first frame of a new cloud colours every list completely
     c->order_pays = false;
     c->cull_pol.on_upload(); c->slab_pol.on_upload();
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) { c->slot[k].surv_hint = 0; c->slot[k].kept_hint = 0; c->slot[k].kept_lo = c->slot[k].kept_hi = 0; c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload(); c->slot[k].slab_kept1 = c->slot[k].slab_kept2 = 0; }
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+        GsrSlotHints& h = c->slot[k].hints;
+        h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
+        c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
+    }
     c->lazy_pays = false;              // ... and in automatic mode the first frames are eager until the kernels say it pays
     // (the kernels' verdicts on the last frame of the PREVIOUS cloud must not reach the first frame of this one through the device word)
     if (c->lazy_hint && hipMemsetAsync(c->lazy_hint, 0, 4, c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "upload: could not reset the policy word");
@@ -1382,7 +1387,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
         // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
         // The launches walk the same tile table; a workgroup of another band's tile leaves at once (~3 us per extra launch).
         int nb = 1;
-        if (!j.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
+        if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
         if (nb > 1 && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; nb = 1; (void)hipGetLastError(); }
         for (int b = 0; b < nb && nb > 1; ++b)
             if (!sl.ev_band[b] && hipEventCreateWithFlags(&sl.ev_band[b], hipEventDisableTiming) != hipSuccess) { sl.ev_band[b] = nullptr; nb = 1; (void)hipGetLastError(); }
@@ -1537,7 +1542,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
         std::swap(sl.hpyr, sl.hpyr_next);      // (what the slot's next frame culls against)
         const int sig[7] = {j.f.width, j.f.height, j.f.shard_index, j.f.shard_count, j.f.shard_rpb, j.f.super_shift, (int)c->geo_gen};
         std::memcpy(sl.horizon_sig, sig, sizeof sig);
-        sl.horizon_cam = j.cam_arg;
+        sl.horizon_cam = j.args.cam;
     }
     if (order_now) {
         if (!fused_order) {
@@ -1555,7 +1560,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
                                                                            //  a front-slab frame's scan depths belong to two different lists)
     sl.last_lazy = j.lazy;
     if (j.timing) { sl.ev_pending = true; sl.ev_all = j.timing_all; }
-    if (!j.out_is_device) {
+    if (!j.args.out_is_device) {
         if (sl.bands > 1 && c->copy_stream) {
             // (band by band behind the blend launches' events, on a stream of their own: k_tile_pass and the frame end run beside the copies)
             for (int b = 0; b < sl.bands; ++b) {
@@ -1563,12 +1568,12 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
                 if (r1 <= r0) continue;
                 const size_t off = r0 * (size_t)j.f.width * 4;
                 HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.ev_band[b], 0));
-                HIP_TRY(hipMemcpyAsync(j.user_out + off, sl.fb + off, (r1 - r0) * (size_t)j.f.width * 16, hipMemcpyDeviceToHost, c->copy_stream));
+                HIP_TRY(hipMemcpyAsync(j.args.out + off, sl.fb + off, (r1 - r0) * (size_t)j.f.width * 16, hipMemcpyDeviceToHost, c->copy_stream));
             }
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
             HIP_TRY(hipStreamSynchronize(s));
         } else {
-            HIP_TRY(hipMemcpyAsync(j.user_out, sl.fb, j.out_px * 16, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb, j.out_px * 16, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
     }
@@ -1671,160 +1676,143 @@ static bool camera_jumped(const gsr_context* c, const gsr_camera& was, const gsr
     return false;
 }
 
-static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
-                       float* rgba_out, int out_is_device, FrameSlot** used, bool allow_cull, int phase_in = 0);
+static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, bool allow_cull, int phase_in = 0);
+static int frame_finish(gsr_context* c, FrameSlot& sl);
+
+// a slot buffer too small for this frame: drain what may still read the old one, then replace it (count elements; cap = the new capacity)
+template <typename T>
+static int regrow(hipStream_t s, T*& p, size_t& cap, size_t count, size_t new_cap)
+{
+    HIP_TRY(hipStreamSynchronize(s));
+    dev_free(p);
+    cap = 0;
+    const int rc = dev_alloc(&p, count);
+    if (rc) return rc;
+    cap = new_cap;
+    return GSR_OK;
+}
+
+// An attempt that is not handed over: its order is not cached, and the work sums its speculative back end added over its lists are
+// cleared (k_tile_order reads them).  redo: frame_check renders the frame again, as it is.
+static int abandon_attempt(FrameSlot& sl, bool redo)
+{
+    if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
+    sl.sort_valid = false;
+    sl.job.redo = redo;
+    sl.job.open = false;
+    return GSR_OK;
+}
+
+// the same frame again, in the same slot: frame_begin counts it once more, so the frame counters step back first
+static int render_again(gsr_context* c, const FrameArgs& a, int phase, FrameSlot** used)
+{
+    c->frame_no -= 1;
+    c->st.frames -= 1;
+    FrameSlot* sl = nullptr;
+    int rc = frame_begin(c, a, &sl, false, phase);
+    if (rc) return rc;
+    if ((rc = frame_finish(c, *sl))) return rc;
+    if (used) *used = sl;
+    return GSR_OK;
+}
 
 static int frame_finish(gsr_context* c, FrameSlot& sl)
 {
     if (!sl.job.open) return GSR_OK;
     FrameJob& j = sl.job;
     HIP_TRY(hipSetDevice(c->device));
-    uint32_t D = 0;
+    GsrMailbox mb;
     if (j.n > 0) {
         // The pair count arrives in mapped host memory, stamped with the frame's ticket, while the GPU carries on: the
         // host just watches the word -- no event in the stream (an event costs the GPU ~6 us of idle queue), no API call.
-        volatile unsigned long long* box = sl.h_total;
         unsigned long long v = 0;
-        const int wrc = wait_mailbox(sl, box, j.ticket, "pair count", &v);
+        const int wrc = wait_mailbox(sl, sl.h_total, j.ticket, "pair count", &v);
         if (wrc) return frame_abort(sl, wrc);
-        D = (uint32_t)v;
-        j.sort_failed = j.local_sort && (box[1] & 32ull) != 0ull;
-        if (j.sort_failed) {
-            // the small-frame sort gave a bucket up: this frame's order, lists and pair count mean nothing.  frame_check renders it
-            // again (three global passes); nothing of it is kept -- not the order (sort cache), not its bookkeeping (no frame end),
-            // not its say in the policies below -- and the work sums its speculative back end added over garbage lists are cleared
-            sl.sort_valid = false;
-            sl.kept_hint = 0; sl.kept_lo = sl.kept_hi = 0;
-            sl.last_pairs = 0;
-            if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
-            sl.local_pol.on_sort_result(true);       // (back-off: GsrLocalSortPolicy::begin_frame)
-            j.open = false;
-            return GSR_OK;
-        }
-        if (j.local_sort) sl.local_pol.on_sort_result(false);
-        if (j.dcull && j.dblind && j.cull && (box[1] & 64ull) != 0ull) {
-            // The frame was culled against horizons, its depth buffer turned out to hold opaque geometry, and k_cluster_cull did not know
-            // (the pyramids were built beside it: the previous depth buffer was clear).  Horizons speak for uncovered pixels only; the
-            // covered ones are served by the depth clause, which k_cluster_cull could not apply: clusters they need may be gone.  The
-            // frame again, with the pyramids in front (once, when opaque geometry first appears; frame_check).
-            c->depth_active = true;
-            c->st.frames_requeued += 1;
-            if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
-            sl.sort_valid = false;
-            j.redo = true;
-            j.open = false;
-            return GSR_OK;
-        }
-        if (j.dcull) {   // (the kernels' word on THIS frame's depth buffer: does it hold anything in front of the far plane?)
-            c->depth_active = (box[1] & 64ull) != 0ull;
-            if (j.sort_fresh) sl.sorted_dculled = c->depth_active;   // (conservatively "yes" until now)
-        }
-        if (j.phase != 2) {   // (the kernels' verdicts on the frame BEFORE: lazy colour / occlusion culling / list prefixes pay)
-            c->lazy_pays = (box[1] & 1ull) != 0ull;
-            c->cull_pol.on_kernel_verdict((box[1] & 4ull) != 0ull);
-            c->prefix_cheaper = (box[1] & 8ull) != 0ull;
-            c->order_pays = (box[1] & 2ull) != 0ull;
-        }
-        if (j.phase == 0) {
-        {   // occlusion culling earns its keep only if it drops a good part of what an unculled frame keeps
-            const uint32_t kept = (uint32_t)(box[1] >> 32);
-            c->cull_pol.on_kept(j.cull, kept, c->opt_cull);
-        }
-        sl.surv_hint = (uint32_t)box[2];           // clusters that survived k_cluster_cull: sizes the next frame's K1 grid
-        sl.kept_hint = (uint32_t)(box[1] >> 32);   // ... and how many splats reached the depth sort: picks the next frame's sort
-        sl.kept_culled = j.cull;
-        } else {
-            // a front-slab frame: its two phases say nothing about what an ordinary frame keeps (no say in the policies); the next
-            // frame -- usually one culled against this frame's horizons -- keeps about what both phases kept, from about as many clusters
-            const uint32_t kept = (uint32_t)(box[1] >> 32);
-            static const bool dbg = std::getenv("GSR_SLAB_DEBUG") != nullptr;
-            if (dbg) fprintf(stderr, "[slab] phase %d: clusters through K1 %u, splats kept %u, pairs %u\n", j.phase, (uint32_t)box[2], kept, D);
-            if (j.phase == 1) { sl.slab_kept = kept; sl.slab_kept1 = std::max(kept, 1u); }
-            else {
-                sl.slab_kept2 = std::max(kept, 1u);
-                sl.kept_hint = sl.slab_kept + kept;
-                // a slab behind which most of the frame still has to be drawn (a ball seen from afar: its near cap finishes few tiles;
-                // oblique ground; a wall) costs more than it saves
-                c->slab_pol.on_frame_done(sl.kept_hint, c->cull_pol.vis_unculled);
-                sl.surv_hint = std::min<uint32_t>((uint32_t)box[2], std::max<uint32_t>(16384u, 2u * div_up(sl.kept_hint, GSR_CLUSTER)));
-                sl.kept_culled = true;
-            }
-        }
-        if (sl.kept_hint > 0 && j.phase == 0) {    // ... between which keys (stored relative to THIS frame's key_min)
-            sl.kept_lo = (uint32_t)box[3] + j.f.key_min;
-            sl.kept_hi = (uint32_t)(box[3] >> 32) + j.f.key_min;
-        } else {
-            sl.kept_lo = sl.kept_hi = 0;
-        }
-        if (D == 0xffffffffu || (unsigned long long)D > (unsigned long long)GSR_MAX_PAIRS)
-            return frame_abort(sl, set_err(GSR_E_TOO_MANY_PAIRS, "gsr_render: the frame's super-tile pairs exceed the limit of %lld", GSR_MAX_PAIRS));
-        // (a slot that has never met a pair has no list buffer at all: the frame-end kernels read entry 0 of it unconditionally --
-        //  a rank whose rows see nothing, under forced culling or forced front-slab frames, faulted on the null pointer)
-        const bool short_buffer = D > sl.pair_cap || !sl.pvA;
-        if (short_buffer) {
-            (void)hipStreamSynchronize(sl.stream);   // a speculative (clamped) back end may still be reading the old buffer
-            const bool first_buffer = sl.pvA == nullptr;
-            dev_free(sl.pvA);
-            sl.pair_cap = 0;
-            // (a slot's first buffer may be sized by a frame -- or a front slab -- that shows next to nothing: at least two entries per splat
-            //  then, up to 32 MB, so that the frames behind it need not each regrow it)
-            const size_t floor_ = !first_buffer ? 0 : std::min<size_t>((size_t)2 * j.n + 4096, (size_t)1 << 22);
-            const size_t want = std::max<size_t>((size_t)D + D / 4 + 4096, std::max(floor_, c->pair_want));
-            int rc = dev_alloc(&sl.pvA, want + 4);   // (+4: the blend kernel scans in 4-entry steps)
-            if (rc) return frame_abort(sl, rc);
-            sl.pair_cap = want;
-            c->pair_want = std::max(c->pair_want, want);   // the other frame slot grows before its next frame
-        }
-        if (short_buffer && j.speculative && j.phase == 2) {
-            // Phase 2 of a front-slab frame CONTINUES from what phase 1 left in the target: the clamped back end that has run has
-            // composited on top of it, and a second run would composite the same splats again.  The whole frame again (frame_check),
-            // with the buffer that now fits; nothing of this attempt is kept.
-            c->st.frames_requeued += 1;
-            if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
-            sl.sort_valid = false;
-            j.redo = true;
-            j.open = false;
-            return GSR_OK;
-        }
-        if (j.deferred) {
-            // the frame was handed over before its pair count was known; if the lists were clamped it misses their tails
-            if (short_buffer) c->st.frames_truncated += 1;
-        } else if (short_buffer || !j.speculative) {
-            if (short_buffer && j.speculative) {
-                c->st.frames_requeued += 1;
-                // the first, clamped back end has already added its tiles' work to the sums k_tile_order reads
-                if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
-            }
-            int rc = queue_back_end(c, sl);
-            if (rc) return frame_abort(sl, rc);
-        }
+        mb = GsrMailbox::read(sl.h_total);
     }
-    sl.last_pairs = D;
-    if (j.n > 0 && j.blend_guess_plain && (sl.h_total[1] & 64ull) != 0ull) {
-        // the guarded plain kernel found covered pixels and did nothing: the depth-tested one draws the frame
-        j.blend_guess_plain = false;
-        int rc = queue_blend(c, sl, true, false);
+    GsrOutcomeIn in;
+    in.has_splats = j.n > 0; in.phase = j.phase; in.cull = j.cull; in.local_sort = j.local_sort; in.dcull = j.dcull; in.dblind = j.dblind;
+    in.speculative = j.speculative; in.deferred = j.deferred; in.blend_guess_plain = j.blend_guess_plain; in.key_min = j.f.key_min;
+    in.pair_cap = sl.pair_cap; in.has_list_buffer = sl.pvA != nullptr; in.max_pairs = (uint64_t)GSR_MAX_PAIRS;
+    in.mb_pairs = mb.pairs; in.mb_hints = mb.hints; in.mb_kept = mb.kept; in.mb_clusters = mb.clusters; in.mb_key_lo = mb.key_lo; in.mb_key_hi = mb.key_hi;
+    const GsrFrameOutcome o = gsr_frame_outcome(in, sl.hints);
+    const uint32_t D = mb.pairs;
+    if (o.local_result >= 0) sl.local_pol.on_sort_result(o.local_result != 0);   // (back-off: GsrLocalSortPolicy::begin_frame)
+    if (o.end == GSR_FE_SORT_GAVE_UP) {
+        // frame_check renders it again with the three global passes; nothing of it is kept, not its bookkeeping (no frame end) either
+        j.sort_failed = true;
+        sl.last_pairs = 0;
+        return abandon_attempt(sl, false);
+    }
+    if (o.end == GSR_FE_DEPTH_APPEARED) {   // (the frame again with the pyramids in front: frame_check)
+        c->depth_active = true;
+        c->st.frames_requeued += 1;
+        return abandon_attempt(sl, true);
+    }
+    if (o.depth_active >= 0) {
+        c->depth_active = o.depth_active != 0;
+        if (j.sort_fresh) sl.sorted_dculled = c->depth_active;   // (conservatively "yes" until now)
+    }
+    if (o.verdicts) {   // (the kernels' verdicts on the frame BEFORE: lazy colour / occlusion culling / list prefixes / tile order pay)
+        c->lazy_pays = mb.has(GSR_HINT_LAZY_PAYS);
+        c->cull_pol.on_kernel_verdict(mb.has(GSR_HINT_CULL_PAYS));
+        c->prefix_cheaper = mb.has(GSR_HINT_PREFIX_CHEAPER);
+        c->order_pays = mb.has(GSR_HINT_ORDER_PAYS);
+    }
+    // occlusion culling earns its keep only if it drops a good part of what an unculled frame keeps; a slab behind which most of the frame
+    // still has to be drawn (a ball seen from afar: its near cap finishes few tiles; oblique ground; a wall) costs more than it saves
+    if (o.kept_counts) c->cull_pol.on_kept(j.cull, mb.kept, c->opt_cull);
+    if (o.slab_done) c->slab_pol.on_frame_done(sl.hints.kept_hint, c->cull_pol.vis_unculled);
+    if (j.n > 0 && j.phase != 0) {
+        static const bool dbg = std::getenv("GSR_SLAB_DEBUG") != nullptr;
+        if (dbg) fprintf(stderr, "[slab] phase %d: clusters through K1 %u, splats kept %u, pairs %u\n", j.phase, mb.clusters, mb.kept, D);
+    }
+    if (o.end == GSR_FE_TOO_MANY_PAIRS)
+        return frame_abort(sl, set_err(GSR_E_TOO_MANY_PAIRS, "gsr_render: the frame's super-tile pairs exceed the limit of %lld", GSR_MAX_PAIRS));
+    // (a slot that has never met a pair has no list buffer at all: the frame-end kernels read entry 0 of it unconditionally --
+    //  a rank whose rows see nothing, under forced culling or forced front-slab frames, faulted on the null pointer)
+    if (o.grow) {
+        // (a slot's first buffer may be sized by a frame -- or a front slab -- that shows next to nothing: at least two entries per splat
+        //  then, up to 32 MB, so that the frames behind it need not each regrow it.  The sync: a clamped back end may still read the old one)
+        const size_t floor_ = sl.pvA ? 0 : std::min<size_t>((size_t)2 * j.n + 4096, (size_t)1 << 22);
+        const size_t want = std::max<size_t>((size_t)D + D / 4 + 4096, std::max(floor_, c->pair_want));
+        const int rc = regrow(sl.stream, sl.pvA, sl.pair_cap, want + 4, want);   // (+4: the blend kernel scans in 4-entry steps)
+        if (rc) return frame_abort(sl, rc);
+        c->pair_want = std::max(c->pair_want, want);   // the other frame slot grows before its next frame
+    }
+    if (o.end == GSR_FE_SLAB_OVERRUN) {
+        // Phase 2 of a front-slab frame CONTINUES from what phase 1 left in the target: the clamped back end that has run has composited on
+        // top of it, and a second run would composite the same splats again.  The whole frame again, with the buffer that now fits.
+        c->st.frames_requeued += 1;
+        return abandon_attempt(sl, true);
+    }
+    if (o.back_end == GSR_BE_TRUNCATED) c->st.frames_truncated += 1;   // (handed over before its count was known: the lists missed their tails)
+    if (o.back_end == GSR_BE_REQUEUED) {
+        c->st.frames_requeued += 1;
+        // the first, clamped back end has already added its tiles' work to the sums k_tile_order reads
+        if (sl.sup_work) (void)hipMemsetAsync(sl.sup_work + 256 * sl.sup_par, 0, 256 * sizeof(uint32_t), sl.stream);
+    }
+    if (o.back_end == GSR_BE_QUEUED || o.back_end == GSR_BE_REQUEUED) {
+        const int rc = queue_back_end(c, sl);
         if (rc) return frame_abort(sl, rc);
     }
-    if (j.phase == 1) {
+    sl.last_pairs = D;
+    if (o.guard_miss) {   // the guarded plain kernel found covered pixels and did nothing: the depth-tested one draws the frame
+        j.blend_guess_plain = false;
+        const int rc = queue_blend(c, sl, true, false);
+        if (rc) return frame_abort(sl, rc);
+    }
+    if (o.end == GSR_FE_PHASE_2) {
         // front slab composited: find the finished tiles, then the rest of the frame (same slot, same call arguments)
-        int rc = queue_slab_mid(c, sl);
+        const int rc = queue_slab_mid(c, sl);
         if (rc) return frame_abort(sl, rc);
         if (j.timing) { sl.ev_pending = true; sl.ev_all = false; }
         j.open = false;
-        const gsr_camera cam = j.cam_arg;
-        const float* depth = j.depth_arg;
-        const int ddev = j.depth_is_device_arg, odev = j.out_is_device_arg;
-        float* out = j.out_arg;
-        c->frame_no -= 1;          // (the same frame, in the same slot)
-        c->st.frames -= 1;
-        FrameSlot* sl2 = nullptr;
-        rc = frame_begin(c, &cam, depth, ddev, out, odev, &sl2, false, 2);
-        if (rc) return rc;
-        return frame_finish(c, *sl2);
+        const FrameArgs a = j.args;   // (frame_begin rewrites the job)
+        return render_again(c, a, 2, nullptr);
     }
     if (!j.deferred) {
-        int rc = queue_frame_end(c, sl);
+        const int rc = queue_frame_end(c, sl);
         if (rc) return frame_abort(sl, rc);
     }
     j.open = false;
@@ -1841,7 +1829,7 @@ static int frame_verdict(gsr_context* c, FrameSlot& sl, bool* broke)
     unsigned long long v = 0;
     const int wrc = wait_mailbox(sl, box, j.ticket, "culling verdict", &v);
     if (wrc) return wrc;
-    *broke = (v & 1ull) != 0ull;
+    *broke = (v & GSR_END_HORIZON_BROKE) != 0ull;
     return GSR_OK;
 }
 
@@ -1856,7 +1844,7 @@ static int finish_open_frames(gsr_context* c)
 }
 
 // the depth order of ALL splats for the camera position of frame f (k_sort.h): keys -> LSD passes -> c->pos_order
-static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f)
+static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f, int key_bits)
 {
     const uint32_t n = c->n;
     int rc;
@@ -1865,8 +1853,6 @@ static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f)
     if ((rc = dev_alloc(&kA, (size_t)n + 256)) || (rc = dev_alloc(&kB, (size_t)n + 256)) || (rc = dev_alloc(&vA, (size_t)n + 256)) ||
         (rc = dev_alloc(&vB, (size_t)n + 256))) { drop(); return rc; }
     hipStream_t s = sl.stream;
-    int key_bits = 1;
-    while (key_bits < 32 && ((f.key_max - f.key_min) >> key_bits) != 0u) ++key_bits;
     hipLaunchKernelGGL(k_pos_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->geoA, n, f.cam[0], f.cam[1], f.cam[2], f.key_min, f.key_max, kA, vA);
     rc = radix_sort(sl, kA, vA, kB, vB, n, key_bits, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(GSR_E_HIP, "position-keyed order: sort failed");
@@ -1881,10 +1867,9 @@ static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f)
     return GSR_OK;
 }
 
-static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
-                       float* rgba_out, int out_is_device, FrameSlot** used, bool allow_cull, int phase_in /* 2 = the second phase of a front-slab frame */)
+static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, bool allow_cull, int phase_in /* 2 = the second phase of a front-slab frame */)
 {
-    if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    const gsr_camera* cam = &a.cam;
     if (c->uploading) return set_err(GSR_E_INVALID, "gsr_render: upload in progress");
     if (cam->width <= 0 || cam->height <= 0 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM)
         return set_err(GSR_E_INVALID, "gsr_render: bad framebuffer size %dx%d (max %d)", cam->width, cam->height, GSR_MAX_DIM);
@@ -1910,15 +1895,12 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
     }
     hipStream_t s = sl.stream;
     if (sl.pair_cap > 0 && sl.pair_cap < c->pair_want) {   // the other slot met a frame that outgrew this size
-        HIP_TRY(hipStreamSynchronize(s));
-        dev_free(sl.pvA);
-        sl.pair_cap = 0;
-        if ((rc = dev_alloc(&sl.pvA, c->pair_want + 4))) return rc;
-        sl.pair_cap = c->pair_want;
+        if ((rc = regrow(s, sl.pvA, sl.pair_cap, c->pair_want + 4, c->pair_want))) return rc;
     }
 
     FrameJob& j = sl.job;
     j = FrameJob();
+    j.args = a;
     build_frame(c, cam, &j.f);
     const GsrFrame& f = j.f;
     const uint32_t n = c->n;
@@ -1927,54 +1909,40 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
     j.band_rows = (c->shard_count > 1) ? gsr_band_rows(cam->height, c->shard_index, c->shard_count) : cam->height;
     j.out_px = (size_t)j.band_rows * cam->width;
     j.n_super = f.stiles_x * f.stiles_y;
-    j.timing = c->opt_timing != 0 && (c->opt_timing >= 2 || c->frame_no % (uint64_t)c->opt_timing_every == 0);
-    j.timing_all = c->opt_timing >= 2;   // level 1 brackets only the blend kernel (events 5 and 6)
     j.use_map = c->opt_swizzle != 0;
-    j.user_out = rgba_out;
-    j.out_is_device = out_is_device != 0;
-    j.cam_arg = *cam; j.depth_arg = depth; j.depth_is_device_arg = depth_is_device; j.out_arg = rgba_out; j.out_is_device_arg = out_is_device;
-    j.deferred = c->opt_deferred && j.out_is_device && phase_in == 0;
-    // order 0: the colour is Cd itself, nothing to defer; mode 1 follows the kernels' own verdict on the previous frames
-    j.lazy = f.sh_order > 0 && (c->opt_lazy == 2 || (c->opt_lazy == 1 && c->lazy_pays));
-    {
-        const int sig[7] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift, (int)c->geo_gen};
-        j.cull = allow_cull && phase_in == 0 && c->opt_cull && !j.deferred && n > 0 && sl.horizon_valid && std::memcmp(sig, sl.horizon_sig, sizeof sig) == 0 &&
-                 !(c->opt_flags & GSR_FLAG_FULL_KEYS) && c->opt_cull != 3 && c->cull_pol.allows(c->opt_cull);
-        if (j.cull && c->opt_cull == 1 && camera_jumped(c, sl.horizon_cam, *cam)) { j.cull = false; c->st.frames_jumped += 1; }
-        if (allow_cull && phase_in == 0) c->cull_pol.tick();
-        j.f.cull_dilate = std::max(c->cull_pol.dilate - sl.hpyr_re, 0);   // (the rest of the radius is built into the slot's pyramid)
-        if (j.cull) {
-            c->st.frames_culled += 1;
-            // What K1 keeps is about what the frame composites: it evaluates the colours itself (eager: the SoA colour chunks of a
-            // cluster's 64 consecutive splats are coalesced reads) -- unless the frame keeps far more than its tiles look at
-            // (oblique ground, silhouettes: then list prefixes + fallback), or lazy colour is forced.  (Round 2 ran a separate pass
-            // over the sorted payloads, k_colour_kept: 16 us of scattered 128-byte rows against 9 us more in K1.)
-            if (f.sh_order > 0 && c->opt_lazy) j.lazy = c->opt_lazy >= 2 || (c->prefix_cheaper && c->prefix_valid);
-        }
-    }
-    // Front-slab frame?  A frame that cannot be culled against a previous frame's horizons (the first frames of a cloud, a jump, the
-    // re-render of a frame that broke a horizon, culling held off) is rendered in two phases where occlusion culling is known to pay:
-    // the nearest splats first, then -- behind the tiles that are still open only -- the rest (GSR_OPT_FRONT_SLAB; k_blend.h).
+
+    // the frame's regime (gsr_frame_plan.h: the policies' per-frame events happen in there)
     const SortKey key_now = {c->geo_gen, c->shard_index, c->shard_count, c->shard_layout, c->opt_flags, *cam};
-    {
-        const bool hit = c->opt_sort_cache && sl.sort_valid && sl.sort_key.same(key_now) && !j.cull && !sl.sorted_culled && !sl.sorted_dculled;   // (a static redraw)
-        const bool slab = phase_in == 0 && !j.cull && !j.deferred && n > 0 && c->opt_slab && c->opt_cull && c->opt_cluster && c->bbox_ok &&
-                          !(c->opt_flags & GSR_FLAG_FULL_KEYS) && c->opt_sort_cache < 2 && !hit &&
-                          // (where a frame is heavy enough for two phases' worth of launches to be repaid: C3's 0.8 M visible splats are not.
-                          //  Not tied to cull_weak: horizons of another view cull weakly whatever the scene; a slab that is weak holds ITSELF off)
-                          c->slab_pol.allows(c->opt_slab >= 2 || c->opt_cull == 3, c->cull_pol);
-        if (phase_in == 0) c->slab_pol.tick();
-        j.phase = phase_in == 2 ? 2 : (slab ? 1 : 0);
-        j.f.phase = j.phase;
-        if (j.phase) {   // (a phase keeps about what it composites: K1 shades on the spot; events only around phase 1's blend kernel)
-            j.lazy = false;
-            j.timing = j.phase == 1 && j.timing && c->opt_timing == 1;
-            j.timing_all = false;
-        }
-        if (j.phase == 2) j.f.cull_dilate = 0;                 // (this frame's own tiles: nothing moves)
-        if (j.phase == 1) c->st.frames_slab += 1;
-    }
-    if (j.lazy && n > 0 && phase_in == 0) c->st.frames_lazy += 1;
+    const int sig[7] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift, (int)c->geo_gen};
+    GsrPlanIn in;
+    in.phase_in = phase_in; in.allow_cull = allow_cull; in.out_is_device = a.out_is_device; in.has_depth = a.depth != nullptr;
+    in.n = n; in.nclus = c->nclus; in.sh_order = f.sh_order; in.key_min = f.key_min; in.key_max = f.key_max;
+    in.opt_deferred = c->opt_deferred; in.opt_lazy = c->opt_lazy; in.opt_cull = c->opt_cull; in.opt_slab = c->opt_slab; in.opt_cluster = c->opt_cluster;
+    in.opt_sort_cache = c->opt_sort_cache; in.opt_local_sort = c->opt_local_sort; in.opt_k1_scatter = c->opt_k1_scatter;
+    in.opt_scatter_direct = c->opt_scatter_direct; in.opt_mid_sort = c->opt_mid_sort; in.opt_bn_items = c->opt_bn_items;
+    in.full_keys = (c->opt_flags & GSR_FLAG_FULL_KEYS) != 0; in.shard_count = c->shard_count;
+    in.timing = c->opt_timing != 0 && (c->opt_timing >= 2 || c->frame_no % (uint64_t)c->opt_timing_every == 0);
+    in.timing_all = c->opt_timing >= 2;   // level 1 brackets only the blend kernel (events 5 and 6)
+    in.opt_timing = c->opt_timing;
+    in.lazy_pays = c->lazy_pays; in.prefix_cheaper = c->prefix_cheaper; in.prefix_valid = c->prefix_valid; in.bbox_ok = c->bbox_ok;
+    in.horizon_match = sl.horizon_valid && std::memcmp(sig, sl.horizon_sig, sizeof sig) == 0;
+    in.hpyr_re = sl.hpyr_re;
+    in.sort_match = sl.sort_valid && sl.sort_key.same(key_now);
+    in.sorted_culled = sl.sorted_culled; in.sorted_dculled = sl.sorted_dculled;
+    in.pos_match = c->pos_valid && c->pos_gen == c->geo_gen && std::memcmp(c->pos_cam, cam->cam_pos, sizeof c->pos_cam) == 0 &&
+                   c->pos_kmin == f.key_min && c->pos_kmax == f.key_max;
+    in.same_pos = c->last_cam_set && std::memcmp(c->last_cam, cam->cam_pos, sizeof c->last_cam) == 0;
+    in.hints = sl.hints;
+    const GsrFramePlan p = gsr_plan_frame(in, c->cull_pol, c->slab_pol, sl.local_pol, c->classic_once,
+                                          [&] { return camera_jumped(c, sl.horizon_cam, *cam); });
+    j.deferred = p.deferred; j.lazy = p.lazy; j.cull = p.cull; j.phase = p.phase; j.timing = p.timing; j.timing_all = p.timing_all;
+    j.dcull = p.dcull; j.local_sort = p.local || p.local_phase; j.bn_items = p.bn_items; j.bn_grid = p.bn_grid; j.k1_grid = p.k1_grid;
+    j.f.cull_dilate = p.cull_dilate;
+    j.f.phase = p.phase;
+    c->st.frames_jumped += p.jumped;
+    c->st.frames_culled += p.cull;
+    c->st.frames_slab += p.phase == 1;
+    c->st.frames_lazy += p.lazy && n > 0 && phase_in == 0;
     j.ticket = ++sl.ticket ? sl.ticket : ++sl.ticket;   // (never 0: the mailbox starts at 0)
     if (j.timing) harvest_slot(c, sl);
 
@@ -1992,41 +1960,25 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
             (rc = dev_alloc(&sl.send, (size_t)65536 + 1)) || (rc = dev_alloc(&sl.redo, (size_t)j.local_tiles + 1))) return rc;
         sl.tile_cap = (size_t)j.local_tiles + 1;
     }
-    if (j.phase == 1 && j.out_px > sl.tbuf_cap) {          // the transmittance a front slab leaves behind, per pixel of the band
-        HIP_TRY(hipStreamSynchronize(s));
-        dev_free(sl.tbuf);
-        sl.tbuf_cap = 0;
-        if ((rc = dev_alloc(&sl.tbuf, j.out_px))) return rc;
-        sl.tbuf_cap = j.out_px;
-    }
+    // (the transmittance a front slab leaves behind, per pixel of the band)
+    if (j.phase == 1 && j.out_px > sl.tbuf_cap && (rc = regrow(s, sl.tbuf, sl.tbuf_cap, j.out_px, j.out_px))) return rc;
     if (j.use_map && (rc = build_tile_map(c, f))) return rc;
-    j.d_depth = depth;
-    if (depth && !depth_is_device) {
+    j.d_depth = a.depth;
+    if (a.depth && !a.depth_is_device) {
         const size_t npx = (size_t)cam->width * cam->height;
-        if (npx > sl.depth_cap) {
-            HIP_TRY(hipStreamSynchronize(s));
-            dev_free(sl.depth_stage);
-            sl.depth_cap = 0;
-            if ((rc = dev_alloc(&sl.depth_stage, npx))) return rc;
-            sl.depth_cap = npx;
-        }
-        HIP_TRY(hipMemcpyAsync(sl.depth_stage, depth, npx * 4, hipMemcpyHostToDevice, s));
+        if (npx > sl.depth_cap && (rc = regrow(s, sl.depth_stage, sl.depth_cap, npx, npx))) return rc;
+        HIP_TRY(hipMemcpyAsync(sl.depth_stage, a.depth, npx * 4, hipMemcpyHostToDevice, s));
         j.d_depth = sl.depth_stage;
     }
     // Depth-tested frames: the tile-max pyramid of the opaque pass's depth (k_cluster.h), rebuilt every frame (the buffer's content is
     // the caller's), one per slot; the second phase of a front-slab frame uses the first one's.  GSR_OPT_OCCLUSION_CULL = 0 switches
     // it off like every other occlusion test (what is left is k_blend's own per-quadrant classification and per-fragment compare).
-    j.dcull = j.d_depth != nullptr && c->opt_cull != 0 && n > 0;
-    if (j.dcull) frame_depth_codes(c, cam, &j.f);
     if (j.dcull) {
+        frame_depth_codes(c, cam, &j.f);
         const size_t need = (size_t)f.pyr_off[GSR_PYR_LEVELS - 1] + (size_t)gsr_pyr_dim(f.tiles_x, GSR_PYR_LEVELS - 1) * gsr_pyr_dim(f.tiles_y, GSR_PYR_LEVELS - 1) + 16;
         if (need > sl.dpyr_cap || !sl.dactive) {
-            HIP_TRY(hipStreamSynchronize(s));
-            dev_free(sl.dpyr);
-            sl.dpyr_cap = 0;
-            if ((rc = dev_alloc(&sl.dpyr, 5 * need))) return rc;                   // (+ the per-tile "covered" array k_blend reads)
+            if ((rc = regrow(s, sl.dpyr, sl.dpyr_cap, 5 * need, need))) return rc;   // (+ the per-tile "covered" array k_blend reads)
             HIP_TRY(hipMemsetAsync(sl.dpyr, 0, 5 * need * sizeof(float), s));   // (levels 4 and 5 start cleared; afterwards every frame clears the next one's)
-            sl.dpyr_cap = need;
             if (!sl.dactive) {
                 if ((rc = dev_alloc(&sl.dactive, 2))) return rc;
                 HIP_TRY(hipMemsetAsync(sl.dactive, 0, 2 * sizeof(uint32_t), s));   // (on the frame's stream: a null-stream memset is not ordered against it)
@@ -2035,14 +1987,10 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
         if (phase_in != 2) sl.dpar ^= 1;
         j.dpar = sl.dpar;
     }
-    j.target = rgba_out;
-    if (!out_is_device) {
+    j.target = a.out;
+    if (!a.out_is_device) {
         if (j.out_px * 4 > sl.fb_cap) {
-            HIP_TRY(hipStreamSynchronize(s));
-            dev_free(sl.fb);
-            sl.fb_cap = 0;
-            if ((rc = dev_alloc(&sl.fb, j.out_px * 4))) return rc;
-            sl.fb_cap = j.out_px * 4;
+            if ((rc = regrow(s, sl.fb, sl.fb_cap, j.out_px * 4, j.out_px * 4))) return rc;
             std::memset(sl.fb_sig, 0xff, sizeof sl.fb_sig);
         }
         // A sharded context's band image is padded (gsr_band_rows): the pixel rows behind the rank's last image row are never
@@ -2057,54 +2005,16 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
 
     j.open = true;   // from here on kernels are queued: every error path drains them (frame_abort)
     if ((rc = mark(sl, 0))) return frame_abort(sl, rc);
-    // The depth order depends on the camera POSITION only (argsortByDistance re-sorts when the position moves,
-    // src/GSplatRenderer.C:165-186) -- but the sorted list holds just the splats visible to the frame that sorted, so
-    // it is reused as is only for an identical frame description (a static viewport redraw), per frame slot.
-    // (a culled frame's order holds only the splats in front of ITS horizons, and the horizons move: no reuse either way; the
-    //  two phases of a front-slab frame each sort what they keep)
-    // (nor the order of a frame that was culled against its depth buffer: the buffer's CONTENT is not part of the frame description)
-    const bool cache_hit = c->opt_sort_cache && sl.sort_valid && sl.sort_key.same(key_now) && !j.cull && !sl.sorted_culled && !sl.sorted_dculled && j.phase == 0;
-    // Position-keyed order (GSR_OPT_SORT_CACHE = 2; the reference's rule, src/GSplatRenderer.C:165-186): while the camera POSITION stands
-    // still -- a rotation about the eye, a change of lens -- the depth order of ALL splats is the one sorted when it last moved, K1 walks
-    // the splats in that order, and what a frame keeps leaves it sorted.  Built the second time a position is seen (a moving camera never
-    // pays for it).  Not for sharded, deferred or full-key frames.
-    bool ordered = false;
-    if (c->opt_sort_cache >= 2 && !cache_hit && n > 0 && c->shard_count == 1 && !j.deferred && !(c->opt_flags & GSR_FLAG_FULL_KEYS) && j.phase == 0) {
-        const bool same_pos = c->last_cam_set && std::memcmp(c->last_cam, cam->cam_pos, sizeof c->last_cam) == 0;
-        if (c->pos_valid && (c->pos_gen != c->geo_gen || std::memcmp(c->pos_cam, cam->cam_pos, sizeof c->pos_cam) != 0 ||
-                             c->pos_kmin != f.key_min || c->pos_kmax != f.key_max))
-            c->pos_valid = false;
-        if (!c->pos_valid && same_pos) {
-            if ((rc = build_pos_order(c, sl, f))) return frame_abort(sl, rc);
-        }
-        ordered = c->pos_valid;
+    // The position-keyed order (the reference's rule, src/GSplatRenderer.C:165-186): dropped when the position moved, built the second
+    // time a position is seen
+    if (p.want_pos && !in.pos_match) {
+        c->pos_valid = false;
+        if (p.ordered && (rc = build_pos_order(c, sl, f, p.key_bits))) return frame_abort(sl, rc);
     }
     std::memcpy(c->last_cam, cam->cam_pos, sizeof c->last_cam);
     c->last_cam_set = true;
-    // which depth sort: A frame that keeps few splats (occlusion culling; small clouds) is sorted by ONE bucket scatter + one local
-    // kernel (k_sort.h) instead of three global passes: 2 launches instead of 9.  Chosen from what the slot's previous frame kept
-    // (correct whatever it chooses).  Not for deferred frames: nobody could render them again; and no prediction from a culled
-    // frame for an unculled one.
-    int key_bits = 1;
-    while (key_bits < 32 && ((f.key_max - f.key_min) >> key_bits) != 0u) ++key_bits;
-    const uint32_t n_slots = n ? div_up(c->nclus, 4u) * (uint32_t)GSR_K1_THREADS : 0u;   // the slots K1 can fill at most
-    // (back-off: a geometry with a long run of coincident splats fails the small-frame sort's tie rule every frame; the re-render
-    //  refills the hints, so without this it would be rendered twice per frame for good)
-    const bool held = sl.local_pol.begin_frame(c->opt_local_sort, cache_hit);
-    const bool local = !cache_hit && !ordered && n_slots > 0 && key_bits > 9 && !(c->opt_flags & GSR_FLAG_FULL_KEYS) && sl.kept_hi > sl.kept_lo && !j.deferred &&
-                       !c->classic_once && !held && sl.kept_culled == j.cull && j.phase == 0 &&
-                       (c->opt_local_sort >= 2 || (c->opt_local_sort == 1 && sl.kept_hint > 0 && sl.kept_hint <= 500000u));
-    const bool classic_now = c->classic_once;
-    if (!cache_hit && j.phase != 1) c->classic_once = false;   // (the re-render of a front-slab frame: both phases)
-    // front-slab phases: the key range of a phase is k_slab_pick's (on the device); the small-frame sort is taken when the slot's
-    // last front-slab frame kept few enough in that phase (phase 1: the slab holds <= slab_max clusters; the first such frame: global passes)
-    const uint32_t kept_prev = j.phase == 1 ? sl.slab_kept1 : sl.slab_kept2;
-    const bool local_phase = j.phase != 0 && n_slots > 0 && key_bits > 9 && c->opt_local_sort && !classic_now && !held && kept_prev > 0 && kept_prev <= 900000u;
-    j.local_sort = local || local_phase;
+    const uint32_t n_slots = p.n_slots;
     GsrK1Scatter scat{};
-    uint32_t bk_lo = 0u;
-    int bk_shift = 0;
-    bool k1_scatters = false;
     if (n > 0) {
 #ifdef GSR_HOST_TIMING
         const double t_pre = now_us();
@@ -2118,8 +2028,8 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
         }
         // (front-slab frames: phase 1 leaves a histogram of the survivors' nearest keys and k_slab_pick takes the slab key from it;
         //  phase 2 culls against the tiles phase 1 finished)
-        const int hist_shift = key_bits > 10 ? key_bits - 10 : 0;
-        const float* pyr = j.phase == 2 ? sl.hpyr2 : ((j.cull && !ordered) ? sl.hpyr : (const float*)nullptr);
+        const int hist_shift = p.key_bits > 10 ? p.key_bits - 10 : 0;
+        const float* pyr = j.phase == 2 ? sl.hpyr2 : ((j.cull && !p.ordered) ? sl.hpyr : (const float*)nullptr);
         const GsrSlabPick pk{(uint32_t)c->slab_min, (uint32_t)c->slab_max, (uint32_t)c->slab_frac, f.key_max - f.key_min};
         // depth-tested frames: the opaque pass's tile-max depth pyramid -- where the previous depth-tested frame found opaque geometry in
         // its buffer, in a launch of its own in front of everything (k_cluster_cull and K1 cull against it); otherwise -- a buffer
@@ -2147,7 +2057,7 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
                     // (measured and rejected, round 6: the pass inside k_cluster_cull's launch here too, the cluster workgroups waiting on a
                     //  count of finished pyramid workgroups before their depth tests: 3650 fps against 4245 -- LAB_NOTES.md)
                     hipLaunchKernelGGL(k_depth_pyramid, dim3(nb8), dim3(1024), 0, s, dp);
-                    if (c->opt_cluster && !ordered) dc_clus = dc_k1;
+                    if (c->opt_cluster && !p.ordered) dc_clus = dc_k1;
                     sl.dpyr_built = true;
                 } else {
                     (void)nb8;
@@ -2174,44 +2084,28 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
             n_dp = 0;      // (looked at: not again in the pass below)
         }
         if (j.phase == 2) sl.slab_dirty = false;   // (mode 3 below clears the histogram for the slot's next front-slab frame)
-        hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(ngroups + n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, rounds, ordered ? 0 : c->opt_cluster,
+        hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(ngroups + n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, rounds, p.ordered ? 0 : c->opt_cluster,
                            pyr, sl.cseg, sl.ccnt,   // (ordered: slots, not clusters -- all of them)
                            j.phase == 1 ? 2 : (j.phase == 2 ? 3 : 0), sl.slab, hist_shift, sl.slab + GSR_SLAB_BINS, pk, (float*)nullptr, 0,
-                           (local || local_phase) ? sl.bkt_cnt : (uint32_t*)nullptr, sl.d_counts + 2, dp, n_dp, dc_clus);
-        // The small-frame sort's bucket pass runs inside K1 (a key's place in its bucket = one atomic): BK_BUCKETS buckets of equal width
-        // over the key range the previous frame kept, widened by a sixteenth on either side (the view moves), in this frame's key domain
-        // (keys are stored relative to key_min); front-slab phases: over the phase's own range, which k_slab_pick left on the device
-        if (local) {
-            const uint64_t span = (uint64_t)sl.kept_hi - sl.kept_lo, margin = span / 16 + 64;
-            const uint64_t lo_abs = sl.kept_lo > margin ? sl.kept_lo - margin : 0, hi_abs = (uint64_t)sl.kept_hi + margin;
-            bk_lo = lo_abs > f.key_min ? (uint32_t)(lo_abs - f.key_min) : 0u;
-            const uint64_t width = (hi_abs > f.key_min ? hi_abs - f.key_min : 0) - bk_lo + 1;
-            while (bk_shift < 31 && (width >> bk_shift) > (uint64_t)BK_BUCKETS) ++bk_shift;
-        }
-        k1_scatters = c->opt_k1_scatter != 0 && (local || local_phase) && c->opt_scatter_direct >= 0;
-        if (k1_scatters) {
+                           j.local_sort ? sl.bkt_cnt : (uint32_t*)nullptr, sl.d_counts + 2, dp, n_dp, dc_clus);
+        // The small-frame sort's bucket pass runs inside K1 (a key's place in its bucket = one atomic), over the plan's buckets; front-slab
+        // phases: over the phase's own range, which k_slab_pick left on the device
+        if (p.k1_scatters) {
             scat.key = sl.bkt_key; scat.val = sl.bkt_val; scat.cnt = sl.bkt_cnt; scat.failed = sl.d_counts + 2;
-            scat.range_dev = local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
-            scat.lo = bk_lo; scat.shift = bk_shift;
+            scat.range_dev = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
+            scat.lo = p.bk_lo; scat.shift = p.bk_shift;
         }
-        // K1 over the survivors, four clusters per workgroup-iteration; the grid follows the slot's previous frame (+25 %), and
-        // a frame that keeps more simply loops
-        const uint32_t all_iter = div_up(c->nclus, 4u);
-        uint32_t k1_grid = all_iter;
-        if (sl.surv_hint > 0 && !ordered) k1_grid = std::min<uint32_t>(all_iter, div_up(sl.surv_hint, 4u) * 5u / 4u + 64u);
-        if (j.phase) k1_grid = std::min<uint32_t>(all_iter, 8192u);   // (what a phase keeps is not known beforehand: a bounded grid that loops)
-        // on a cache hit (identical frame description) the sorted (keyA, valA) are kept and K1's key/payload
-        // output goes to the scratch buffers
-        j.k1_grid = k1_grid;
+        // K1 over the survivors (the plan's grid: a frame that keeps more loops); on a cache hit (identical frame description) the sorted
+        // (keyA, valA) are kept and K1's key/payload output goes to the scratch buffers
         // (two instantiations: the one that leaves the colours pending has no SH evaluation in it and runs at 8 waves per SIMD instead of 6)
-        hipLaunchKernelGGL(j.d_depth ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(k1_grid ? k1_grid : 1u), dim3(GSR_K1_THREADS), 0, s, n, c->cap, f, c->geoA, c->geoB, c->col,
-                           sl.rec, (cache_hit || ordered) ? sl.keyB : sl.keyA, (cache_hit || ordered) ? sl.valB : sl.valA,
+        hipLaunchKernelGGL(j.d_depth ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(j.k1_grid ? j.k1_grid : 1u), dim3(GSR_K1_THREADS), 0, s, n, c->cap, f, c->geoA, c->geoB, c->col,
+                           sl.rec, (p.cache_hit || p.ordered) ? sl.keyB : sl.keyA, (p.cache_hit || p.ordered) ? sl.valB : sl.valA,
                            j.d_depth ? sl.zwin : (float*)nullptr, j.phase == 2 ? sl.hpyr2 : (j.cull ? sl.hpyr : (const float*)nullptr), sl.blk_cnt,
                            sl.cseg, sl.ccnt, ngroups, (uint32_t)CC_THREADS * (uint32_t)rounds, sl.d_counts, scat,
                            // (the count of sorted splats starts at zero: a frame whose clusters are ALL culled runs no sort workgroup that
                            //  could say so, and the binning kernels would walk the previous frame's order; a static redraw keeps its order)
-                           cache_hit ? (uint32_t*)nullptr : sl.d_n,
-                           ordered ? c->pos_order : (const uint32_t*)nullptr, sl.slab + GSR_SLAB_BINS, dc_k1);
+                           p.cache_hit ? (uint32_t*)nullptr : sl.d_n,
+                           p.ordered ? c->pos_order : (const uint32_t*)nullptr, sl.slab + GSR_SLAB_BINS, dc_k1);
         hipError_t e = hipGetLastError();
 #ifdef GSR_HOST_TIMING
         if (g_t_verdict > 0) {
@@ -2226,9 +2120,9 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
         if (e != hipSuccess) return frame_abort(sl, set_err(GSR_E_HIP, "k_preprocess: %s", hipGetErrorString(e)));
     }
     if ((rc = mark(sl, 1))) return frame_abort(sl, rc);
-    if (cache_hit) {
+    if (p.cache_hit) {
         c->st.sorts_skipped += 1;
-    } else if (ordered) {
+    } else if (p.ordered) {
         // K1 walked the splats nearest first: the heads of its 256-slot blocks, one after the other, ARE the sorted frame
         const uint32_t m_max = n_slots / RS_SRC_BLOCK;
         if ((rc = ensure_u32(&c->blk_pre, &c->blk_pre_cap, (size_t)m_max + 8))) return frame_abort(sl, rc);
@@ -2241,27 +2135,23 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
         sl.sort_valid = false;       // (what the slot holds is this frame's kept set only)
         sl.sorted_culled = j.cull;
     } else {
-        if (local_phase) {
+        if (p.local_phase) {
             // K1's compacted slots -> bucket regions over the phase's key range (k_slab_pick left it on the device) -> sorted (keyA, valA)
             const uint32_t* range = sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4);
-            if (!k1_scatters)
+            if (!p.k1_scatters)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(std::max(1u, std::min(div_up(n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u))), dim3(256), 0, s, sl.keyA, sl.valA,
                                    n_slots / RS_SRC_BLOCK, sl.d_counts, 0, 0u, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2, range);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, 0, key_bits, 0u,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, 0, p.key_bits, 0u,
                                sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n, range);
             if (hipGetLastError() != hipSuccess) rc = set_err(GSR_E_HIP, "small-frame sort: launch failed");
-        } else if (local) {
-            // BK_BUCKETS buckets of equal width over the key range the previous frame kept, widened by a sixteenth on either side (the
-            // view moves); in this frame's key domain (keys are stored relative to key_min)
-            const uint32_t lo = bk_lo;
-            const int bshift = bk_shift;
+        } else if (p.local) {
+            const uint32_t lo = p.bk_lo;
+            const int bshift = p.bk_shift;
             const uint32_t nblk = div_up(n_slots, RS_TILE);
             // K1's compacted slots -> bucket regions (counters and *d_n were cleared by K1) -> sorted (keyA, valA)
-            // one global atomic per key pays up to ~150 k keys (fps direct / aggregated: C1 16 700 / 14 400, C2 8830 / 8560, C3 4650 / 4920, C4 3800 / 3950)
-            const bool direct = c->opt_scatter_direct == 2 || (c->opt_scatter_direct == 1 && sl.kept_hint <= 150000u);
-            if (k1_scatters) {
+            if (p.k1_scatters) {
                 // (K1 did it)
-            } else if (direct)
+            } else if (p.scatter_direct)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_direct<uint2>), dim3(n_slots / RS_SRC_BLOCK), dim3(RS_SRC_BLOCK), 0, s, sl.keyA, sl.valA,
                                    sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2);
             else if (c->opt_scatter_direct >= 0)
@@ -2271,15 +2161,12 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
             else   // (A/B: the general gathering scatter, 2048 slots per workgroup)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint2, true>), dim3(nblk), dim3(RS_THREADS), 0, s, sl.keyA, sl.valA, n_slots, sl.d_counts,
                                    bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, (uint32_t*)nullptr, sl.d_counts + 2);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, bshift, key_bits, lo,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, bshift, p.key_bits, lo,
                                sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n);
             if (hipGetLastError() != hipSuccess) rc = set_err(GSR_E_HIP, "small-frame sort: launch failed");
         } else {
-            // (keys per thread: by what the slot's previous frame kept -- any choice sorts correctly)
-            // (... from a frame of the same kind: an unculled frame keeps ten times what a culled one does)
-            const bool mid = c->opt_mid_sort && sl.kept_hint > 0 && sl.kept_hint <= 1500000u && n_slots <= 4000000u && sl.kept_culled == j.cull;
-            rc = radix_sort(sl, sl.keyA, sl.valA, sl.keyB, sl.valB, n_slots, key_bits,
-                            !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n, RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, mid);
+            rc = radix_sort(sl, sl.keyA, sl.valA, sl.keyB, sl.valB, n_slots, p.key_bits,
+                            !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n, RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, p.mid_sort);
         }
         if (rc) return frame_abort(sl, rc);
         sl.key_min = f.key_min;
@@ -2293,16 +2180,11 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
     hipError_t e = hipSuccess;
     if (n > 0) {
         // coarse binning as a counting sort (k_binning.h): count -> scan -> ranges -> [pair count to the host] -> place
-        // splats per binning workgroup: 1024 for frames that keep millions, fewer for the small ones (k_binning.h)
-        // (measured, fps with 4 / 2 / 1: C1 12 770 / 13 540 / 14 190, C2 7880 / 8270 / 8510, C3 4770 / 4900 / 4830, C4 3930 / 3950 / 3760)
-        j.bn_items = c->opt_bn_items > 0 ? c->opt_bn_items : (j.phase ? 2 : (!local ? 4 : (sl.kept_hint <= 150000u ? 1 : 2)));
         const uint32_t bn_tile = (uint32_t)BN_THREADS * (uint32_t)j.bn_items;
-        const uint32_t nblk = div_up(n, bn_tile);
+        const uint32_t nblk = p.bn_blocks;
         rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)BN_BINS * nblk + 8);
         if (rc) return frame_abort(sl, rc);
         const GsrShard shd{f.shard_index, f.shard_count, f.shard_rpb, f.rect_shift};
-        // the grids of the binning kernels: what the slot's previous frame kept, + 25 % (they loop if the frame keeps more)
-        j.bn_grid = (sl.kept_hint > 0 && j.phase == 0) ? std::min<uint32_t>(nblk, div_up(sl.kept_hint + sl.kept_hint / 4u, bn_tile) + 64u) : (j.phase ? std::min<uint32_t>(nblk, 4096u) : nblk);
         // (+ the extra work items of the blocks that are split by rows of super-tiles: k_binning.h, BN_SPLIT_TILES)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
 #define GSR_COUNT(I) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bin_count<I>), dim3(j.bn_grid + bn_extra), dim3(BN_THREADS), 0, s, sl.valA, sl.d_n, f.super_shift - f.rect_shift, \
@@ -2340,8 +2222,7 @@ static int frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth
 
 static FrameSlot* latest_slot(gsr_context* c);
 // a culled frame is handed over only once it has checked itself; one that broke a horizon is rendered again, complete
-static int frame_check(gsr_context* c, FrameSlot& first, const gsr_camera* cam, const float* depth, int depth_is_device,
-                       float* rgba_out, int out_is_device)
+static int frame_check(gsr_context* c, FrameSlot& first, const FrameArgs& a)
 {
     // A frame that is rendered again is checked again: the repair of a culled frame may itself meet a bucket its small-frame sort
     // gives up, or -- as a front-slab frame -- a list buffer its second phase overruns.  Every reason removes itself (the re-sort
@@ -2350,27 +2231,21 @@ static int frame_check(gsr_context* c, FrameSlot& first, const gsr_camera* cam, 
     FrameSlot* cur = &first;
     for (int round = 0; round < 8; ++round) {
         FrameSlot& slot = *cur;
+        int rc;
         if (slot.job.sort_failed || slot.job.redo) {
             // the small-frame sort met a bucket far beyond its prediction and left it unsorted: the frame again, with the global sort
-            // (and without culling: a prediction that far off means the view jumped, and the horizons with it) -- or the second phase
-            // of a front-slab frame ran off its list buffer (frame_finish): the frame again, as it was
+            // (and without culling: a prediction that far off means the view jumped, and the horizons with it) -- or the attempt was
+            // abandoned for a reason of its own (frame_finish): the frame again, as it was
             if (slot.job.sort_failed) {
                 c->st.frames_resorted += 1;
                 c->classic_once = true;
             }
-            c->frame_no -= 1;
-            c->st.frames -= 1;
-            FrameSlot* sl2 = nullptr;
-            int rc2 = frame_begin(c, cam, depth, depth_is_device, rgba_out, out_is_device, &sl2, false);
-            if (rc2) return rc2;
-            if ((rc2 = frame_finish(c, *sl2))) return rc2;
-            cur = sl2;
+            if ((rc = render_again(c, a, 0, &cur))) return rc;
             continue;
         }
         if (!slot.job.cull) return GSR_OK;
         bool broke = false;
-        int rc = frame_verdict(c, slot, &broke);
-        if (rc) return rc;
+        if ((rc = frame_verdict(c, slot, &broke))) return rc;
         if (!broke) {
             c->cull_pol.on_frame_held();
 #ifdef GSR_HOST_TIMING
@@ -2396,13 +2271,7 @@ static int frame_check(gsr_context* c, FrameSlot& first, const gsr_camera* cam, 
         // neighbourhood from now on (the repaired frame leaves fresh horizons, and the radius shrinks back while frames hold);
         // only when that is exhausted, leave culling alone for a while (8, 32, 128, 512, 1024 frames).
         c->cull_pol.on_horizon_broke();
-        c->frame_no -= 1;          // the same frame again, in the same slot
-        c->st.frames -= 1;
-        FrameSlot* sl = nullptr;
-        rc = frame_begin(c, cam, depth, depth_is_device, rgba_out, out_is_device, &sl, false);
-        if (rc) return rc;
-        if ((rc = frame_finish(c, *sl))) return rc;
-        cur = sl;
+        if ((rc = render_again(c, a, 0, &cur))) return rc;
     }
     return set_err(GSR_E_HIP, "gsr_render: the frame did not settle after eight attempts");
 }
@@ -2415,13 +2284,15 @@ extern "C" int gsr_render(gsr_context* c, const gsr_camera* cam, float* rgba_out
 extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
                                 float* rgba_out, int out_is_device)
 {
+    if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    const FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0};
     FrameSlot* sl = nullptr;
 #ifdef GSR_HOST_PHASES
     static double acc[4] = {0, 0, 0, 0}, t_last_exit = 0; static long cnt = 0;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
 #endif
-    int rc = frame_begin(c, cam, depth, depth_is_device, rgba_out, out_is_device, &sl, true);
+    int rc = frame_begin(c, a, &sl, true);
     if (rc) return rc;
     if (sl->job.deferred) return GSR_OK;   // GSR_OPT_DEFERRED_CHECK: the pair count is looked at by the next call that syncs
 #ifdef GSR_HOST_PHASES
@@ -2431,7 +2302,7 @@ extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const flo
 #ifdef GSR_HOST_PHASES
     const double t2 = now();
 #endif
-    rc = frame_check(c, *sl, cam, depth, depth_is_device, rgba_out, out_is_device);
+    rc = frame_check(c, *sl, a);
 #ifdef GSR_HOST_PHASES
     const double t3 = now();
     acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2; if (t_last_exit > 0) acc[3] += t0 - t_last_exit;
@@ -2445,7 +2316,8 @@ extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const flo
 __attribute__((visibility("hidden"))) int gsr_internal_frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth,
                                                                     int depth_is_device, float* out_dev)
 {
-    return frame_begin(c, cam, depth, depth_is_device, out_dev, 1, nullptr, true);
+    if (!c || !cam || !out_dev) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    return frame_begin(c, FrameArgs{*cam, depth, depth_is_device != 0, out_dev, true}, nullptr, true);
 }
 __attribute__((visibility("hidden"))) int gsr_internal_frame_finish(gsr_context* c) { return c ? finish_open_frames(c) : GSR_OK; }
 // third step of the split form: the newest frame's occlusion-culling verdict (and the repair, if it broke a horizon)
@@ -2453,7 +2325,9 @@ __attribute__((visibility("hidden"))) int gsr_internal_frame_check(gsr_context* 
                                                                     int depth_is_device, float* out_dev)
 {
     FrameSlot* sl = c ? latest_slot(c) : nullptr;
-    return sl ? frame_check(c, *sl, cam, depth, depth_is_device, out_dev, 1) : GSR_OK;
+    if (!sl) return GSR_OK;
+    if (!cam || !out_dev) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    return frame_check(c, *sl, FrameArgs{*cam, depth, depth_is_device != 0, out_dev, true});
 }
 __attribute__((visibility("hidden"))) void* gsr_internal_stream(gsr_context* c) { return c ? (void*)c->stream : nullptr; }
 __attribute__((visibility("hidden"))) int gsr_internal_device(gsr_context* c) { return c ? c->device : -1; }
@@ -2520,6 +2394,12 @@ extern "C" int gsr_debug_policy(int32_t* state16, int event, long long a, long l
     gsr_policy_apply(state16, event, a, b);
     return state16[11] < 0 ? set_err(GSR_E_INVALID, "gsr_debug_policy: unknown event %d", event) : GSR_OK;
 }
+// test door of the frame driver's decisions (gsr_frame_plan.h: the flat layouts): which = 0 the plan of a frame, 1 the outcome of an attempt
+extern "C" int gsr_debug_frame_plan(int which, const int32_t* in, int32_t* policy16, int32_t* out)
+{
+    if (!in || !out || (which == 0 && !policy16)) return set_err(GSR_E_INVALID, "gsr_debug_frame_plan: NULL argument");
+    return gsr_frame_plan_apply(which, in, policy16, out) ? set_err(GSR_E_INVALID, "gsr_debug_frame_plan: unknown selector %d", which) : GSR_OK;
+}
 // ... and the live policy state of a context, in the same layout ([12] = frames the slot's local-sort policy is for: slot 0)
 extern "C" int gsr_debug_policy_state(gsr_context* c, int32_t* state16)
 {
@@ -2576,7 +2456,7 @@ extern "C" int gsr_get_stats(gsr_context* c, gsr_stats* out)
         c->st.entries_scanned = (int64_t)sl.h_counters[3];
         c->st.pairs_total = sl.last_pairs;
         c->st.clusters_total = c->nclus;
-        c->st.clusters_kept = sl.surv_hint;
+        c->st.clusters_kept = sl.hints.surv_hint;
         c->st.policy_bits = (c->lazy_pays ? 1 : 0) | (c->order_pays ? 2 : 0) | (c->cull_pol.pays ? 4 : 0) | (c->cull_pol.weak ? 8 : 0) | (c->prefix_cheaper ? 16 : 0) | (c->depth_active ? 32 : 0);
         c->st.cull_dilate = c->cull_pol.dilate;
         c->st.cull_holdoff = c->cull_pol.holdoff;

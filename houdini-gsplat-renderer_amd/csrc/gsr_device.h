@@ -23,6 +23,7 @@ __device__ unsigned int g_kprof_blk[5][2][8192];   // per kernel and workgroup: 
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gsr_mailbox.h"
 
 #define GSR_TILE_PX 16
 #define GSR_WAVE 64

@@ -220,9 +220,10 @@ __device__ __forceinline__ uint32_t bn_ranges(const GsrRangeArgs& a, bool publis
         // word 3: the smallest and the largest key of the frame (predicts the next frame's sort buckets, k_sort.h)
         *a.redo_count = 0u;
         const uint32_t ns = *a.n_sorted;
-        // (bit 5 of the hints: the small-frame sort gave a bucket up -- the lists of this frame are not to be trusted)
-        a.host_total[1] = ((unsigned long long)ns << 32) | (unsigned long long)(*a.lazy_hint & 31u) | (a.k1_counts[2] ? 32ull : 0ull) |
-                          ((a.depth_active && *a.depth_active) ? 64ull : 0ull);
+        // (the words: gsr_mailbox.h)
+        a.host_total[1] = ((unsigned long long)ns << 32) | (unsigned long long)(*a.lazy_hint & GSR_HINT_VERDICTS) |
+                          (a.k1_counts[2] ? (unsigned long long)GSR_HINT_SORT_GAVE_UP : 0ull) |
+                          ((a.depth_active && *a.depth_active) ? (unsigned long long)GSR_HINT_DEPTH_COVERED : 0ull);
         a.host_total[2] = (unsigned long long)a.k1_counts[1];
         a.host_total[3] = ns ? ((unsigned long long)a.sorted_keys[ns - 1u] << 32) | (unsigned long long)a.sorted_keys[0] : 0ull;
     }
@@ -240,7 +241,7 @@ __device__ __forceinline__ uint32_t bn_ranges(const GsrRangeArgs& a, bool publis
             a.send[threadIdx.x] = too_many ? 0 : (int32_t)(ex + v);
         }
         // the host sizes the list buffer from it; it recognises THIS frame's count by the ticket in the upper half
-        if (threadIdx.x == 0) { *a.host_total = ((unsigned long long)a.ticket << 32) | (too_many ? 0xffffffffull : (unsigned long long)tot); __threadfence_system(); }
+        if (threadIdx.x == 0) { *a.host_total = ((unsigned long long)a.ticket << 32) | (too_many ? (unsigned long long)GSR_MB_TOO_MANY_PAIRS : (unsigned long long)tot); __threadfence_system(); }
     }
     return too_many ? 0u : ex;
 }

@@ -989,7 +989,7 @@ gsr_sum_work(const GsrTilePartial* __restrict__ partial, int nblocks, GsrSumArgs
     // first thing: the frame's verdict to the host, which is waiting for it before it hands the frame over and queues the next one
     if (hz.host_end && threadIdx.x == 0) {
         uint32_t v = s_viol;
-        *hz.host_end = ((unsigned long long)hz.ticket << 32) | (unsigned long long)(v ? 1u : 0u);
+        *hz.host_end = ((unsigned long long)hz.ticket << 32) | (unsigned long long)(v ? GSR_END_HORIZON_BROKE : 0u);
         __threadfence_system();   // out to the host NOW (without it the word left with the kernel's end: a 13 us bubble before the next frame)
     }
     if (sup_work_next) sup_work_next[threadIdx.x] = 0u;
@@ -1015,22 +1015,22 @@ gsr_sum_work(const GsrTilePartial* __restrict__ partial, int nblocks, GsrSumArgs
         // Lazy colour pays when the colour pass would evaluate well under half of what eager evaluation does (it gathers
         // rows at random, eager streams them) and (almost) no tile would need the on-demand fallback.  Small or sparse
         // clouds (BASELINE C2, C3) fail one of the two; the 6 M-splat scenes pass both.
-        // Bit 1: would a heaviest-first tile order pay (k_tile_order)?  When the heaviest tile alone is more than half of a
+        // (the bits: gsr_mailbox.h's GSR_HINT_*.)  ORDER_PAYS: would a heaviest-first tile order pay (k_tile_order)?  When the heaviest tile alone is more than half of a
         // workgroup slot's fair share of the frame (1536 slots: 6 workgroups on 256 CUs) raster order leaves a long, thin tail
         // (C3: heaviest tile = 0.85 of the share); when the tiles are all alike, no order helps (C4: 0.34) and the kernel is skipped.
         const unsigned long long wsum = s_sum[2] * 32ull + s_sum[1] * 8ull + (s_sum[0] >> 1);
         // ... and the frame must be long enough for the gain to beat the ordering kernel's ~10 us (C2: heaviest = 1.6 of the
         // share, but 37 us of work in all: 6 us gained)
-        const uint32_t order_pays = ((unsigned long long)s_wmax * 3072ull > wsum && wsum > 60000000ull) ? 2u : 0u;
+        const uint32_t order_pays = ((unsigned long long)s_wmax * 3072ull > wsum && wsum > 60000000ull) ? GSR_HINT_ORDER_PAYS : 0u;
         if (lazy_hint) *lazy_hint = ((prefix && (unsigned long long)s_est * 10ull < (unsigned long long)nvis * 4ull &&
-                                      s_unsat * 64u <= (uint32_t)g.n_tiles) ? 1u : 0u) | order_pays |
-                                    // bit 2: occlusion culling has something to work with: at least 30 % of the tiles that draw anything
+                                      s_unsat * 64u <= (uint32_t)g.n_tiles) ? GSR_HINT_LAZY_PAYS : 0u) | order_pays |
+                                    // CULL_PAYS: occlusion culling has something to work with: at least 30 % of the tiles that draw anything
                                     // went opaque in the first 70 % of their list (judged on unculled frames; a culled frame keeps the
                                     // verdict it was given)
-                                    // bit 3: in a frame like this one the list-prefix colour pass would evaluate fewer colours than one per
+                                    // PREFIX_CHEAPER: in a frame like this one the list-prefix colour pass would evaluate fewer colours than one per
                                     // kept splat (a culled frame that still keeps a lot: oblique ground, silhouettes)
-                                    ((prefix && (unsigned long long)s_est * 3ull < (unsigned long long)nvis * 2ull) ? 8u : 0u) |
-                                    ((hz.culled || ((unsigned long long)s_nfin * 10ull >= (unsigned long long)s_nused * 3ull && s_nused > 0u)) ? 4u : 0u);
+                                    ((prefix && (unsigned long long)s_est * 3ull < (unsigned long long)nvis * 2ull) ? GSR_HINT_PREFIX_CHEAPER : 0u) |
+                                    ((hz.culled || ((unsigned long long)s_nfin * 10ull >= (unsigned long long)s_nused * 3ull && s_nused > 0u)) ? GSR_HINT_CULL_PAYS : 0u);
         // running totals: plain read-modify-write (a slot's frames are serialised on its stream; nothing else touches them)
         const unsigned long long t2 = old2 + s_sum[1], t4 = old4 + s_sum[0], t5 = old5 + s_sum[2];
         counters[1] = s_sum[1]; counters[2] = t2; counters[3] = s_sum[0]; counters[4] = t4; counters[5] = t5;

@@ -101,7 +101,7 @@ C_ABI_SYMBOLS = [
     "gsr_device_count", "gsr_create", "gsr_destroy", "gsr_last_error", "gsr_version", "gsr_set_stream",
     "gsr_upload_begin", "gsr_upload_append", "gsr_upload_append_raw", "gsr_upload_end", "gsr_upload_abort", "gsr_upload", "gsr_set_row_shard", "gsr_band_rows",
     "gsr_stitch_bands", "gsr_render", "gsr_render_depth", "gsr_render_wire", "gsr_render_wire_over", "gsr_synchronize", "gsr_get_stats", "gsr_stats_reset", "gsr_set_option",
-    "gsr_debug_read_records", "gsr_debug_read_depth_order", "gsr_debug_read_storage_order", "gsr_debug_read_tile_lists", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_local", "gsr_debug_policy", "gsr_debug_policy_state",
+    "gsr_debug_read_records", "gsr_debug_read_depth_order", "gsr_debug_read_storage_order", "gsr_debug_read_tile_lists", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_local", "gsr_debug_policy", "gsr_debug_policy_state", "gsr_debug_frame_plan",
     "gsr_debug_read_tile_work", "gsr_debug_read_horizons",
     "gsr_multi_create", "gsr_multi_destroy", "gsr_multi_count", "gsr_multi_transport", "gsr_multi_context",
     "gsr_multi_set_stream", "gsr_multi_set_option", "gsr_multi_upload_begin", "gsr_multi_upload_append",
@@ -173,6 +173,7 @@ def load_library() -> C.CDLL:
     L.gsr_debug_sort_pairs_local.argtypes = [vp, vp, vp, i64, i32, C.c_uint32, i32]
     L.gsr_debug_policy.argtypes = [vp, i32, C.c_longlong, C.c_longlong]
     L.gsr_debug_policy_state.argtypes = [vp, vp]
+    L.gsr_debug_frame_plan.argtypes = [i32, vp, vp, vp]
     L.gsr_debug_read_tile_work.argtypes = [vp, vp, i64]
     L.gsr_debug_read_horizons.argtypes = [vp, vp, i64]
     # host shim wrappers
