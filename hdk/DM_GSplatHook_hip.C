@@ -59,6 +59,18 @@ static hipStream_t hookStream(GSplatRenderer& R)
     return theHookStream;
 }
 
+/* The frame is rendered in RGBA16F -- what a viewport's HDR beauty target is -- not RGBA32F: the blend kernel stores 8 bytes per pixel,
+ * the PBO is half the size, and GL converts nothing at the upload (GSR_TARGET_RGBA16F, gsplat_hip.h).  (GL headers older than 3.0
+ * lack the two names.) */
+#ifndef GL_RGBA16F
+#define GL_RGBA16F 0x881A
+#endif
+#ifndef GL_HALF_FLOAT
+#define GL_HALF_FLOAT 0x140B
+#endif
+static const int theTargetFormat = GSR_TARGET_RGBA16F;
+static const int theTargetPixelBytes = 8;
+
 namespace {
 
 /* the two pixel buffers of one viewport and the texture the result is drawn from */
@@ -73,7 +85,7 @@ struct ViewportBuffers {
         release();
         glGenBuffers(1, &rgbaPbo);
         glBindBuffer(GL_PIXEL_UNPACK_BUFFER, rgbaPbo);
-        glBufferData(GL_PIXEL_UNPACK_BUFFER, (GLsizeiptr)w * h * 16, nullptr, GL_STREAM_DRAW);
+        glBufferData(GL_PIXEL_UNPACK_BUFFER, (GLsizeiptr)w * h * theTargetPixelBytes, nullptr, GL_STREAM_DRAW);
         glBindBuffer(GL_PIXEL_UNPACK_BUFFER, 0);
         glGenBuffers(1, &depthPbo);
         glBindBuffer(GL_PIXEL_PACK_BUFFER, depthPbo);
@@ -81,7 +93,7 @@ struct ViewportBuffers {
         glBindBuffer(GL_PIXEL_PACK_BUFFER, 0);
         glGenTextures(1, &tex);
         glBindTexture(GL_TEXTURE_2D, tex);
-        glTexStorage2D(GL_TEXTURE_2D, 1, GL_RGBA32F, w, h);
+        glTexStorage2D(GL_TEXTURE_2D, 1, GL_RGBA16F, w, h);
         glTexParameteri(GL_TEXTURE_2D, GL_TEXTURE_MIN_FILTER, GL_NEAREST);
         glTexParameteri(GL_TEXTURE_2D, GL_TEXTURE_MAG_FILTER, GL_NEAREST);
         glBindTexture(GL_TEXTURE_2D, 0);
@@ -161,6 +173,7 @@ public:
          * public stream -- its own stream is hipStreamNonBlocking and would NOT be ordered against stream 0) and the unmaps, which
          * is what hands the finished frame back to GL.  It is the plugin's, not this viewport's (hookStream above). */
         hipStream_t stream = hookStream(R);
+        if (R.targetFormat() != theTargetFormat) (void)R.setTargetFormat(theTargetFormat);   /* (once: the singleton is shared by every viewport) */
         ctx.depth = static_cast<const float*>(myBuffers.depth.map(stream));
         ctx.depth_is_device = 1;
         ctx.target = static_cast<float*>(myBuffers.rgba.map(stream));
@@ -197,7 +210,7 @@ public:
         /* hand-back: PBO -> texture inside the GPU, then one triangle with the reference's blend state */
         glBindBuffer(GL_PIXEL_UNPACK_BUFFER, myBuffers.rgbaPbo);
         glBindTexture(GL_TEXTURE_2D, myBuffers.tex);
-        glTexSubImage2D(GL_TEXTURE_2D, 0, 0, 0, ctx.width, ctx.height, GL_RGBA, GL_FLOAT, nullptr);
+        glTexSubImage2D(GL_TEXTURE_2D, 0, 0, 0, ctx.width, ctx.height, GL_RGBA, GL_HALF_FLOAT, nullptr);
         glBindBuffer(GL_PIXEL_UNPACK_BUFFER, 0);
         r->pushBlendState();
         r->pushDepthState();

@@ -296,6 +296,16 @@ void GSplatRenderer::setExplicitCameraPos(const float p[3])
 
 void GSplatRenderer::setSphericalHarmonicsOrder(int order) { sh_order_ = order; }
 
+int GSplatRenderer::setTargetFormat(int format)
+{
+    if (gsr_target_pixel_bytes(format) < 0) return GSR_E_INVALID;
+    int rc = GSR_OK;
+    if (multi_) rc = gsr_multi_set_target_format(multi_, format);
+    else if (engine_) rc = gsr_set_target_format(engine_, format);
+    if (rc == GSR_OK) target_format_ = format;
+    return rc;
+}
+
 int64_t GSplatRenderer::query(int what, const std::string& id) const
 {
     switch (what) {
@@ -398,6 +408,8 @@ void gsplat_renderer_redraw(gsplat_renderer* h, const char* const* ids, int n, G
 void gsplat_renderer_set_rendering_enabled(gsplat_renderer* h, int enabled) { if (h) h->impl->setRenderingEnabled(enabled != 0); }
 void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos[3]) { if (h && pos) h->impl->setExplicitCameraPos(pos); }
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order) { if (h) h->impl->setSphericalHarmonicsOrder(order); }
+int gsplat_renderer_set_target_format(gsplat_renderer* h, int format) { return h ? h->impl->setTargetFormat(format) : GSR_E_INVALID; }
+int gsplat_renderer_get_target_format(gsplat_renderer* h) { return h ? h->impl->targetFormat() : GSR_E_INVALID; }
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id) { return h ? h->impl->query(what, id ? std::string(id) : std::string()) : -1; }
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]) { if (h && out) h->impl->origin(out); }
 void gsplat_renderer_get_last_camera_pos(gsplat_renderer* h, float out[3]) { if (h && out) h->impl->lastCameraPos(out); }

@@ -101,7 +101,8 @@ struct FrameJob {
     uint32_t n = 0;
     int local_tiles = 0, band_rows = 0, n_super = 0;
     size_t out_px = 0;
-    float* target = nullptr;       // device buffer the blend kernel writes
+    float* target = nullptr;       // device buffer the blend kernel writes (pixels of `format`)
+    int format = 0;                // the context's target format when the frame was begun (GSR_TARGET_*)
     const float* d_depth = nullptr;   // the depth buffer on the device (args.depth, or the slot's copy of a host buffer)
     bool timing = false, timing_all = false, use_map = false;
     bool speculative = false;      // the back end was queued before the pair count was known
@@ -216,9 +217,11 @@ struct FrameSlot {
     unsigned long long* lazy_ctr = nullptr;   // [0] low word: redo count of the frame, [1]: colours evaluated (running)
     uint32_t* colour_evals = nullptr;         // [256] colours evaluated per super-tile list (this frame; folded into lazy_ctr[1])
     bool last_lazy = false;            // the last frame of this slot left colours pending
-    float* fb = nullptr;               // staging for host-pointer output
+    float* fb = nullptr;               // staging for host-pointer output: pixels of the context's target format (fb_cap counts floats)
     size_t fb_cap = 0;
-    int fb_sig[5] = {-1, -1, -1, -1, -1};   // the band shape the staging buffer was last cleared for
+    int fb_sig[6] = {-1, -1, -1, -1, -1, -1};   // the band shape (and target format) the staging buffer was last cleared for
+    float* fb32 = nullptr;             // packed target formats, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
+    size_t fb32_cap = 0;
     // small device/host mailboxes
     unsigned long long* counters = nullptr;  // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
                                              // scanned, [5] wave-record evaluations (running)
@@ -302,6 +305,7 @@ struct gsr_context {
     int map_w = 0, map_h = 0, map_si = -1, map_sc = 0, map_rpb = -1, map_shift = -1, map_grid = 0;
 
     int shard_index = 0, shard_count = 1, shard_layout = 0;   // layout: 0 = interleaved rows, 1 = contiguous bands
+    int target_format = GSR_TARGET_RGBA32F;   // what a pixel of every target is (gsr_set_target_format)
     int opt_swizzle = 2, opt_timing = 1, opt_sort_cache = 1, opt_super = 0, opt_flags = 0, opt_deferred = 0, opt_lazy = 1, opt_cull = 1, opt_timing_every = 1;
     int opt_cluster = 1, opt_morton = 1, opt_local_sort = 1;
     int opt_slab = 1;                  // front-slab frames (GSR_OPT_FRONT_SLAB): 0 off, 1 where occlusion culling pays but has no horizons, 2 always
@@ -484,7 +488,7 @@ static void slot_destroy(FrameSlot& sl)
     slot_free_splat_arrays(sl);
     dev_free(sl.hist); dev_free(sl.totals);
     dev_free(sl.pvA);
-    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb);
+    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32);
     dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
     if (sl.h_end) (void)hipHostFree(sl.h_end); dev_free(sl.depth_stage); dev_free(sl.dpyr); dev_free(sl.dactive);
     dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
@@ -625,6 +629,59 @@ extern "C" int gsr_set_option(gsr_context* c, int option, int value)
         break;
     }
     default: return set_err(GSR_E_INVALID, "gsr_set_option: unknown option %d", option);
+    }
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// target format: what a pixel of every target (frames, band images, the wire overlay) is.  Not an option: it changes pixels.
+extern "C" int gsr_target_pixel_bytes(int format)
+{
+    const int b = gsr_format_pixel_bytes(format);
+    return b ? b : set_err(GSR_E_INVALID, "gsr_target_pixel_bytes: unknown target format %d", format);
+}
+
+extern "C" int gsr_set_target_format(gsr_context* c, int format)
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_set_target_format: ctx is NULL");
+    if (!gsr_format_pixel_bytes(format)) return set_err(GSR_E_INVALID, "gsr_set_target_format: unknown target format %d", format);
+    if (format == c->target_format) return GSR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);    // (finishes what is in flight -- a front-slab frame included -- in the format it was begun in)
+    if (rc) return rc;
+    rc = gsr_internal_comm_sync(c);
+    if (rc) return rc;
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {   // the staging images are laid out for the old pixel size
+        FrameSlot& sl = c->slot[k];
+        dev_free(sl.fb); sl.fb_cap = 0; std::memset(sl.fb_sig, 0xff, sizeof sl.fb_sig);
+        dev_free(sl.fb32); sl.fb32_cap = 0;
+    }
+    c->target_format = format;
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_target_format(gsr_context* c)
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_target_format: ctx is NULL");
+    return c->target_format;
+}
+
+// the same conversion on the host, through the same functions as the kernels' stores (gsr_device.h): for callers who keep f32 frames,
+// and the yardstick the GPU path is held to.  No context, no GPU.
+extern "C" int gsr_convert_pixels(const float* rgba32f, int64_t n_pixels, int format, void* out)
+{
+    if (!gsr_format_pixel_bytes(format)) return set_err(GSR_E_INVALID, "gsr_convert_pixels: unknown target format %d", format);
+    if (n_pixels < 0 || (n_pixels > 0 && (!rgba32f || !out))) return set_err(GSR_E_INVALID, "gsr_convert_pixels: bad argument");
+    if (format == GSR_TARGET_RGBA32F) { std::memcpy(out, rgba32f, (size_t)n_pixels * 16); return GSR_OK; }
+    for (int64_t i = 0; i < n_pixels; ++i) {
+        const float* p = rgba32f + 4 * i;
+        if (format == GSR_TARGET_RGBA16F) {
+            const uint2 v = gsr_pack_rgba16f(p[0], p[1], p[2], p[3]);
+            std::memcpy(static_cast<char*>(out) + 8 * i, &v, 8);
+        } else {
+            const uint32_t v = gsr_pack_rgba8(p[0], p[1], p[2], p[3]);
+            std::memcpy(static_cast<char*>(out) + 4 * i, &v, 4);
+        }
     }
     return GSR_OK;
 }
@@ -925,10 +982,14 @@ __attribute__((visibility("hidden"))) int gsr_internal_stitch(gsr_context* c, co
         return set_err(GSR_E_INVALID, "gsr_stitch_bands: bad argument");
     HIP_TRY(hipSetDevice(c->device));
     const size_t npx = (size_t)width * height;
-    hipLaunchKernelGGL(k_stitch_bands, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       reinterpret_cast<const float4*>(gathered), count,
-                       (c->shard_layout == 1 && count > 1) ? ((height + GSR_TILE - 1) / GSR_TILE + count - 1) / count : 0,
-                       gsr_band_rows(height, 0, count), width, height, reinterpret_cast<float4*>(out));
+    const int bpp = gsr_format_pixel_bytes(c->target_format);
+    if (((uintptr_t)gathered | (uintptr_t)out) % (uintptr_t)bpp) return set_err(GSR_E_INVALID, "gsr_stitch_bands: a buffer is not aligned to the %d-byte pixel", bpp);
+    const int rpb = (c->shard_layout == 1 && count > 1) ? ((height + GSR_TILE - 1) / GSR_TILE + count - 1) / count : 0;
+    // (pixels of the target format move as they are: a row copy, no conversion)
+#define GSR_STITCH(PIX) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_stitch_bands<PIX>), dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), \
+                                           reinterpret_cast<const PIX*>(gathered), count, rpb, gsr_band_rows(height, 0, count), width, height, reinterpret_cast<PIX*>(out))
+    if (bpp == 16) GSR_STITCH(float4); else if (bpp == 8) GSR_STITCH(uint2); else GSR_STITCH(uint32_t);
+#undef GSR_STITCH
     HIP_TRY(hipGetLastError());
     return GSR_OK;
 }
@@ -1381,7 +1442,9 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
         lz.f = f; lz.colrow = c->colrow;
         lz.redo = j.lazy ? sl.redo : nullptr;
         lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
-        float4* tgt = reinterpret_cast<float4*>(j.target);
+        // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
+        a.out_format = j.format; a.out_packed = j.format != GSR_TARGET_RGBA32F ? (void*)j.target : nullptr;
+        float4* tgt = reinterpret_cast<float4*>(j.format != GSR_TARGET_RGBA32F ? sl.fb32 : j.target);
         // Host-target frames (a caller without GL interop): the frame's LAST blend launch is issued band by band of tile rows, an event
         // behind each, and queue_frame_end copies a band's rows back on a second stream as soon as its event fires: all but the first
         // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
@@ -1561,19 +1624,20 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     sl.last_lazy = j.lazy;
     if (j.timing) { sl.ev_pending = true; sl.ev_all = j.timing_all; }
     if (!j.args.out_is_device) {
+        const size_t bpp = (size_t)gsr_format_pixel_bytes(j.format);
         if (sl.bands > 1 && c->copy_stream) {
             // (band by band behind the blend launches' events, on a stream of their own: k_tile_pass and the frame end run beside the copies)
             for (int b = 0; b < sl.bands; ++b) {
                 const size_t r0 = std::min<size_t>((size_t)sl.band_row[b] * GSR_TILE, (size_t)j.band_rows), r1 = std::min<size_t>((size_t)sl.band_row[b + 1] * GSR_TILE, (size_t)j.band_rows);
                 if (r1 <= r0) continue;
-                const size_t off = r0 * (size_t)j.f.width * 4;
+                const size_t off = r0 * (size_t)j.f.width * bpp;
                 HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.ev_band[b], 0));
-                HIP_TRY(hipMemcpyAsync(j.args.out + off, sl.fb + off, (r1 - r0) * (size_t)j.f.width * 16, hipMemcpyDeviceToHost, c->copy_stream));
+                HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, reinterpret_cast<const char*>(sl.fb) + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
             }
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
             HIP_TRY(hipStreamSynchronize(s));
         } else {
-            HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb, j.out_px * 16, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb, j.out_px * bpp, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
     }
@@ -1988,16 +2052,21 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         j.dpar = sl.dpar;
     }
     j.target = a.out;
+    j.format = c->target_format;
+    const size_t bpp = (size_t)gsr_format_pixel_bytes(j.format);
+    // (a packed target, front-slab frame: phase 2 continues from phase 1's f32 pixels, kept in a buffer of the slot's own)
+    if (j.format != GSR_TARGET_RGBA32F && j.phase == 1 && j.out_px * 4 > sl.fb32_cap && (rc = regrow(s, sl.fb32, sl.fb32_cap, j.out_px * 4, j.out_px * 4))) return rc;
     if (!a.out_is_device) {
-        if (j.out_px * 4 > sl.fb_cap) {
-            if ((rc = regrow(s, sl.fb, sl.fb_cap, j.out_px * 4, j.out_px * 4))) return rc;
+        const size_t fb_floats = j.out_px * bpp / 4;
+        if (fb_floats > sl.fb_cap) {
+            if ((rc = regrow(s, sl.fb, sl.fb_cap, fb_floats, fb_floats))) return rc;
             std::memset(sl.fb_sig, 0xff, sizeof sl.fb_sig);
         }
         // A sharded context's band image is padded (gsr_band_rows): the pixel rows behind the rank's last image row are never
         // written.  In the library's own staging buffer they read as zeros: it is cleared whenever the band's shape changes.
-        const int fsig[5] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb};
+        const int fsig[6] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, j.format};
         if (std::memcmp(fsig, sl.fb_sig, sizeof fsig) != 0) {
-            HIP_TRY(hipMemsetAsync(sl.fb, 0, j.out_px * 16, s));
+            HIP_TRY(hipMemsetAsync(sl.fb, 0, j.out_px * bpp, s));
             std::memcpy(sl.fb_sig, fsig, sizeof fsig);
         }
         j.target = sl.fb;
@@ -2276,6 +2345,8 @@ static int frame_check(gsr_context* c, FrameSlot& first, const FrameArgs& a)
     return set_err(GSR_E_HIP, "gsr_render: the frame did not settle after eight attempts");
 }
 
+static bool target_aligned(const gsr_context* c, const void* p) { return (uintptr_t)p % (uintptr_t)gsr_format_pixel_bytes(c->target_format) == 0; }
+
 extern "C" int gsr_render(gsr_context* c, const gsr_camera* cam, float* rgba_out, int out_is_device)
 {
     return gsr_render_depth(c, cam, nullptr, 0, rgba_out, out_is_device);
@@ -2285,6 +2356,7 @@ extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const flo
                                 float* rgba_out, int out_is_device)
 {
     if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    if (out_is_device && !target_aligned(c, rgba_out)) return set_err(GSR_E_INVALID, "gsr_render: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
     const FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0};
     FrameSlot* sl = nullptr;
 #ifdef GSR_HOST_PHASES
@@ -2317,6 +2389,7 @@ __attribute__((visibility("hidden"))) int gsr_internal_frame_begin(gsr_context* 
                                                                     int depth_is_device, float* out_dev)
 {
     if (!c || !cam || !out_dev) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
+    if (!target_aligned(c, out_dev)) return set_err(GSR_E_INVALID, "gsr_render: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
     return frame_begin(c, FrameArgs{*cam, depth, depth_is_device != 0, out_dev, true}, nullptr, true);
 }
 __attribute__((visibility("hidden"))) int gsr_internal_frame_finish(gsr_context* c) { return c ? finish_open_frames(c) : GSR_OK; }
@@ -2345,6 +2418,8 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
     if (cam->width <= 0 || cam->height <= 0 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM)
         return set_err(GSR_E_INVALID, "gsr_render_wire: bad framebuffer size %dx%d", cam->width, cam->height);
     if (!c->has_geometry) return set_err(GSR_E_NO_GEOMETRY, "gsr_render_wire: nothing uploaded");
+    if (out_is_device && !target_aligned(c, rgba_out)) return set_err(GSR_E_INVALID, "gsr_render_wire: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
+    const size_t bpp = (size_t)gsr_format_pixel_bytes(c->target_format);
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);
     if (rc) return rc;
@@ -2353,7 +2428,7 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
     build_frame(c, cam, &f);
     const size_t npix = (size_t)cam->width * cam->height;
     // the z-buffer (and the staging image for a host target) are kept between calls: an overlay redraw allocates nothing
-    if (npix > c->wire_cap) {
+    if (npix > c->wire_cap) {   // (the staging image holds 16 bytes per pixel: enough for every target format)
         dev_free(c->wire_zbuf); dev_free(c->wire_out);
         c->wire_cap = 0;
         if ((rc = dev_alloc(&c->wire_zbuf, npix)) || (rc = dev_alloc(&c->wire_out, npix * 4))) {
@@ -2374,14 +2449,14 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
     unsigned long long* zbuf = c->wire_zbuf;
     float* target = out_is_device ? rgba_out : c->wire_out;
     hipError_t e = hipMemsetAsync(zbuf, 0xff, npix * 8, s);
-    if (e == hipSuccess && over && !out_is_device) e = hipMemcpyAsync(c->wire_out, rgba_out, npix * 16, hipMemcpyHostToDevice, s);   // (the frame underneath)
+    if (e == hipSuccess && over && !out_is_device) e = hipMemcpyAsync(c->wire_out, rgba_out, npix * bpp, hipMemcpyHostToDevice, s);   // (the frame underneath)
     if (e == hipSuccess && c->n > 0)
         hipLaunchKernelGGL(k_wire_splats, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->n, f, c->geoA, c->geoB, zbuf, inv ? c->perm : (const uint32_t*)nullptr);
     if (e == hipSuccess)
         hipLaunchKernelGGL(k_wire_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, zbuf, npix, c->col,
-                           reinterpret_cast<float4*>(target), inv, over);
+                           target, c->target_format, inv, over);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess && !out_is_device) e = hipMemcpyAsync(rgba_out, c->wire_out, npix * 16, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !out_is_device) e = hipMemcpyAsync(rgba_out, c->wire_out, npix * bpp, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render_wire: %s", hipGetErrorString(e));
     return GSR_OK;

@@ -128,6 +128,48 @@ __device__ __forceinline__ float gsr_h2f(uint32_t bits16)
     return (float)h;  // v_cvt_f32_f16: exact
 }
 
+// ---- target formats (gsplat_hip.h: GSR_TARGET_*) ------------------------------
+// What a finished f32 pixel becomes in the context's target.  THE rule, in one place: the blend kernel's store, the wire overlay and
+// gsr_convert_pixels (the host yardstick the GPU path is held to) all go through these.
+#define GSR_FMT_RGBA32F 0
+#define GSR_FMT_RGBA16F 1
+#define GSR_FMT_RGBA8   2
+__host__ __device__ __forceinline__ int gsr_format_pixel_bytes(int format)
+{
+    return format == GSR_FMT_RGBA32F ? 16 : format == GSR_FMT_RGBA16F ? 8 : format == GSR_FMT_RGBA8 ? 4 : 0;
+}
+// binary16 of a channel: round to nearest even, overflow to infinity (v_cvt_f16_f32 on the device; what k_quantize_raw and
+// gsplat_quantize_half do to attributes)
+__host__ __device__ __forceinline__ uint32_t gsr_channel_half(float x)
+{
+    const _Float16 h = (_Float16)x;
+    return (uint32_t)__builtin_bit_cast(uint16_t, h);
+}
+// 8-bit unorm of a channel: clamp to [0, 1] (NaN -> 0), ONE rounding in the fma, then truncation.  Linear: no sRGB curve
+__host__ __device__ __forceinline__ uint32_t gsr_channel_unorm8(float x)
+{
+    float c = x > 0.0f ? x : 0.0f;
+    c = c < 1.0f ? c : 1.0f;
+    return (uint32_t)__builtin_fmaf(c, 255.0f, 0.5f);
+}
+__host__ __device__ __forceinline__ uint2 gsr_pack_rgba16f(float r, float g, float b, float a)
+{
+    uint2 o;
+    o.x = gsr_channel_half(r) | (gsr_channel_half(g) << 16);
+    o.y = gsr_channel_half(b) | (gsr_channel_half(a) << 16);
+    return o;
+}
+__host__ __device__ __forceinline__ uint32_t gsr_pack_rgba8(float r, float g, float b, float a)
+{
+    return gsr_channel_unorm8(r) | (gsr_channel_unorm8(g) << 8) | (gsr_channel_unorm8(b) << 16) | (gsr_channel_unorm8(a) << 24);
+}
+// one pixel into a target of either packed format (p = pixel index)
+__device__ __forceinline__ void gsr_store_packed(void* __restrict__ target, int format, size_t p, float r, float g, float b, float a)
+{
+    if (format == GSR_FMT_RGBA16F) reinterpret_cast<uint2*>(target)[p] = gsr_pack_rgba16f(r, g, b, a);
+    else reinterpret_cast<uint32_t*>(target)[p] = gsr_pack_rgba8(r, g, b, a);
+}
+
 // The contract's 2^x for x in [-2^22, 0]: identical operation sequence to the oracle's gso_exp2f
 // (round to the nearest-even integer with the 1.5*2^23 trick, EXACT remainder r = x - k, degree-5
 // polynomial for 2^r on [-0.5, 0.5], exponent add).  <= 2.8 ulp, exp2(0) == 1, never above 1.

@@ -142,7 +142,10 @@ struct DevBuf {
     }
 };
 
-size_t band_floats(int width, int height, int count) { return (size_t)gsr_band_rows(height, 0, count) * (size_t)width * 4; }
+// (buffers and offsets are counted in floats; a pixel of the target format is fpp = 4, 2 or 1 of them.  What crosses a link is counted
+//  in BYTES: the element type carries no meaning in a gather)
+size_t band_floats(int width, int height, int count, int fpp) { return (size_t)gsr_band_rows(height, 0, count) * (size_t)width * (size_t)fpp; }
+int floats_per_pixel(gsr_context* c) { return gsr_target_pixel_bytes(gsr_get_target_format(c)) / 4; }
 
 // band layout: the pixel rows of rank g's band that exist in the image, and the image row its band starts at
 int band_first_row(int height, int g, int count) { return g * gsr_band_rows(height, 0, count); }
@@ -237,7 +240,7 @@ struct gsr_multi {
     bool frame_rec[2] = {false, false};
     DevBuf final_fb;                     // staging of a host target
     uint64_t frame = 0;
-    int shape_sig[3] = {0, 0, -1};       // width, height, layout of the frames the buffers were sized for
+    int shape_sig[4] = {0, 0, -1, -1};   // width, height, layout, target format of the frames the buffers were sized for
     bool uploading = false;
     // gather timing (gsr_multi_gather_stats)
     bool time_gather = false;
@@ -489,6 +492,19 @@ extern "C" int gsr_multi_set_option(gsr_multi* m, int option, int value)
     return GSR_OK;
 }
 
+// every rank renders its band in the format, and the root stitches / receives pixels of it.  Frames in flight (the double-buffered
+// bands among them) are finished first: the buffers are laid out afresh by the next frame (shape_sig).
+extern "C" int gsr_multi_set_target_format(gsr_multi* m, int format)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_set_target_format: NULL");
+    if (gsr_target_pixel_bytes(format) < 0) return GSR_E_INVALID;
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    for (gsr_context* c : m->ctx)
+        if ((rc = gsr_set_target_format(c, format))) return rc;
+    return GSR_OK;
+}
+
 extern "C" int gsr_multi_gather_stats(gsr_multi* m, int enable, double* ms_total, int64_t* gathers)
 {
     if (!m) return fail(GSR_E_INVALID, "gsr_multi_gather_stats: NULL");
@@ -569,14 +585,16 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     if (cam->width <= 0 || cam->height <= 0 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM)
         return fail(GSR_E_INVALID, "gsr_multi_render: bad framebuffer size %dx%d", cam->width, cam->height);
     const int W = cam->width, H = cam->height;
-    const size_t bf = band_floats(W, H, G);
+    const int fpp = floats_per_pixel(m->ctx[0]);
+    const size_t bf = band_floats(W, H, G, fpp);
+    if (out_is_device && (uintptr_t)rgba_out % (uintptr_t)(fpp * 4)) return fail(GSR_E_INVALID, "gsr_multi_render: the device target is not aligned to its %d-byte pixel", fpp * 4);
     const size_t npx = (size_t)W * H;
     const int b = (int)(m->frame & 1u);
     const bool bands = gsr_internal_shard_layout(m->ctx[0]) == 1;
     int rc;
     harvest_gather_time(m, b);
     {   // a frame of another shape: buffers are about to be regrown, and frames in flight still use them
-        const int sig[3] = {W, H, bands ? 1 : 0};
+        const int sig[4] = {W, H, bands ? 1 : 0, fpp};
         if (std::memcmp(sig, m->shape_sig, sizeof sig) != 0) {
             if ((rc = gsr_multi_synchronize(m))) return rc;
             std::memcpy(m->shape_sig, sig, sizeof sig);
@@ -587,7 +605,7 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
         if ((rc = m->band[b][g].ensure(m->dev[g], bf))) return rc;
     float* target = rgba_out;
     if (!out_is_device) {
-        if ((rc = m->final_fb.ensure(m->dev[0], npx * 4))) return rc;
+        if ((rc = m->final_fb.ensure(m->dev[0], npx * fpp))) return rc;
         target = m->final_fb.p;
     }
     // the caller's stream position now: the target may still be read by what it queued before this call, and a depth image
@@ -631,8 +649,8 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     HIP_OK(hipSetDevice(m->dev[0]));
     HIP_OK(hipStreamWaitEvent(x0, m->ev_user, 0));
     if (m->time_gather) { HIP_OK(hipEventRecord(m->ev_t0[b], x0)); m->t0_rec[b] = true; }
-    auto dst_of = [&](int g) { return bands ? target + (size_t)band_first_row(H, g, G) * W * 4 : m->gathered[b].p + (size_t)g * bf; };
-    auto cnt_of = [&](int g) { return bands ? (size_t)band_live_rows(H, g, G) * W * 4 : bf; };
+    auto dst_of = [&](int g) { return bands ? target + (size_t)band_first_row(H, g, G) * W * fpp : m->gathered[b].p + (size_t)g * bf; };
+    auto cnt_of = [&](int g) { return bands ? (size_t)band_live_rows(H, g, G) * W * fpp : bf; };
     if (m->transport == GSR_TRANSPORT_RCCL) {
         for (int g = 1; g < G; ++g) {
             HIP_OK(hipSetDevice(m->dev[g]));
@@ -642,8 +660,8 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
         ncclResult_t r = ncclSuccess;
         for (int g = 1; g < G && r == ncclSuccess; ++g) {
             if (cnt_of(g) == 0) continue;
-            r = rccl().Recv(dst_of(g), cnt_of(g), ncclFloat, g, m->comm[0], x0);
-            if (r == ncclSuccess) r = rccl().Send(m->band[b][g].p, cnt_of(g), ncclFloat, 0, m->comm[g], m->xfer[g]);
+            r = rccl().Recv(dst_of(g), cnt_of(g) * 4, ncclUint8, g, m->comm[0], x0);
+            if (r == ncclSuccess) r = rccl().Send(m->band[b][g].p, cnt_of(g) * 4, ncclUint8, 0, m->comm[g], m->xfer[g]);
         }
         const ncclResult_t re = rccl().GroupEnd();
         if (r != ncclSuccess || re != ncclSuccess)
@@ -671,7 +689,7 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     m->frame_rec[b] = true;
     m->frame += 1;
     if (!out_is_device) {
-        HIP_OK(hipMemcpyAsync(rgba_out, target, npx * 16, hipMemcpyDeviceToHost, x0));
+        HIP_OK(hipMemcpyAsync(rgba_out, target, npx * fpp * 4, hipMemcpyDeviceToHost, x0));
         HIP_OK(hipStreamSynchronize(x0));
     }
     // the result is ordered on the caller's stream
@@ -697,7 +715,7 @@ struct CommState {
     hipEvent_t ev_band[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_user = nullptr;
     bool done_rec[2] = {false, false};
     uint64_t frame = 0;
-    int shape_sig[3] = {0, 0, -1};
+    int shape_sig[4] = {0, 0, -1, -1};
 };
 std::map<gsr_context*, CommState>& comm_table()
 {
@@ -846,13 +864,14 @@ extern "C" int gsr_comm_render(gsr_context* ctx, const gsr_camera* cam, const fl
     if (cam->width <= 0 || cam->height <= 0 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM)
         return fail(GSR_E_INVALID, "gsr_comm_render: bad framebuffer size %dx%d", cam->width, cam->height);
     const int W = cam->width, H = cam->height, G = st.world;
-    const size_t bf = band_floats(W, H, G);
+    const int fpp = floats_per_pixel(ctx);
+    const size_t bf = band_floats(W, H, G, fpp);
     const bool bands = gsr_internal_shard_layout(ctx) == 1;
     const int b = (int)(st.frame & 1u);
     int rc;
     HIP_OK(hipSetDevice(st.dev));
     {   // a frame of another shape: the buffers are about to be regrown, and frames in flight still use them
-        const int sig[3] = {W, H, bands ? 1 : 0};
+        const int sig[4] = {W, H, bands ? 1 : 0, fpp};
         if (std::memcmp(sig, st.shape_sig, sizeof sig) != 0) {
             HIP_OK(hipStreamSynchronize(st.exec));
             HIP_OK(hipStreamSynchronize(st.xfer));
@@ -867,15 +886,15 @@ extern "C" int gsr_comm_render(gsr_context* ctx, const gsr_camera* cam, const fl
     float* band = st.band[b].p;
     if ((rc = gsr_render_depth(ctx, cam, depth, depth_is_device, band, 1))) return rc;   // (on st.exec: the context's stream)
     HIP_OK(hipEventRecord(st.ev_band[b], st.exec));
-    auto cnt_of = [&](int g) { return bands ? (size_t)band_live_rows(H, g, G) * W * 4 : bf; };
+    auto cnt_of = [&](int g) { return bands ? (size_t)band_live_rows(H, g, G) * W * fpp : bf; };
     if (st.rank == 0) {
         HIP_OK(hipStreamWaitEvent(st.xfer, st.ev_user, 0));
         NCCL_OK(rccl().GroupStart());
         ncclResult_t r = ncclSuccess;
         for (int g = 1; g < G && r == ncclSuccess; ++g) {
             if (cnt_of(g) == 0) continue;
-            float* dst = bands ? rgba_out_device + (size_t)band_first_row(H, g, G) * W * 4 : st.band[b].p + (size_t)g * bf;
-            r = rccl().Recv(dst, cnt_of(g), ncclFloat, g, st.comm, st.xfer);
+            float* dst = bands ? rgba_out_device + (size_t)band_first_row(H, g, G) * W * fpp : st.band[b].p + (size_t)g * bf;
+            r = rccl().Recv(dst, cnt_of(g) * 4, ncclUint8, g, st.comm, st.xfer);
         }
         const ncclResult_t re = rccl().GroupEnd();
         if (r != ncclSuccess || re != ncclSuccess) return fail(GSR_E_COMM, "band gather (root): %s", rccl().GetErrorString(r != ncclSuccess ? r : re));
@@ -885,7 +904,7 @@ extern "C" int gsr_comm_render(gsr_context* ctx, const gsr_camera* cam, const fl
         } else if ((rc = gsr_internal_stitch(ctx, st.band[b].p, G, W, H, rgba_out_device, st.xfer))) return rc;
     } else {
         HIP_OK(hipStreamWaitEvent(st.xfer, st.ev_band[b], 0));
-        if (cnt_of(st.rank)) NCCL_OK(rccl().Send(band, cnt_of(st.rank), ncclFloat, 0, st.comm, st.xfer));
+        if (cnt_of(st.rank)) NCCL_OK(rccl().Send(band, cnt_of(st.rank) * 4, ncclUint8, 0, st.comm, st.xfer));
     }
     HIP_OK(hipEventRecord(st.ev_done[b], st.xfer));
     st.done_rec[b] = true;

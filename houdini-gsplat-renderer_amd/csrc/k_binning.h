@@ -352,9 +352,11 @@ k_bin_place(const uint2* __restrict__ sorted, const uint32_t* __restrict__ n_dev
 // root side of the multi-GPU path: gathered band images -> frame.
 // gathered = count bands of band_rows x width pixels; band g holds rank g's tile rows stacked bottom-up
 // (interleaved layout: rows g, g+count, ...; band layout, rpb > 0: rows g*rpb ...).
+// PIX = a pixel of the target format as one vector (float4 / uint2 / uint32_t): a stitch is a row copy, it never converts.
+template <typename PIX>
 __global__ void __launch_bounds__(256)
-k_stitch_bands(const float4* __restrict__ gathered, int count, int rpb, int band_rows, int width, int height,
-               float4* __restrict__ out)
+k_stitch_bands(const PIX* __restrict__ gathered, int count, int rpb, int band_rows, int width, int height,
+               PIX* __restrict__ out)
 {
     const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (p >= (size_t)width * height) return;

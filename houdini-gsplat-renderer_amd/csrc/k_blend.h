@@ -106,6 +106,11 @@ struct GsrBlendArgs {
     // rows back to the host on a second stream, so that all but the first band's compositing hides behind the link.  A workgroup whose
     // tile row (local) is outside [row_lo, row_hi) leaves at once.
     int32_t row_lo, row_hi;
+    // The target format (gsr_device.h: GSR_FMT_*).  RGBA32F: the pixel goes to `out` as ever.  A packed format: it goes, converted, to
+    // out_packed, and `out` is only used by front-slab frames -- phase 1 ALSO leaves the f32 pixel there (the slot's internal buffer), so
+    // that phase 2 continues from the exact colour; tiles phase 2 skips as finished hold their final packed pixel already.
+    int32_t out_format;
+    void* out_packed;
 };
 
 // Staging layout: one list PER QUADRANT (= per wave), holding the round's records that reach that
@@ -590,8 +595,11 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
         const int w2 = t2 >> 6, l2 = t2 & 63;
         const int brow = lty * GSR_TILE_PX + (w2 >> 1) * 8 + (l2 >> 3);
         const int bcol = tx * GSR_TILE_PX + (w2 & 1) * 8 + (l2 & 7);
-        out[(size_t)brow * a.width + bcol] = make_float4(C01.x, C01.y, C2, 1.0f - T);
-        if (a.slab == 1) a.tbuf[(size_t)brow * a.width + bcol] = T;
+        const size_t at = (size_t)brow * a.width + bcol;
+        // (a.out_format is wave-uniform: one scalar branch, outside every loop)
+        if (a.out_format == GSR_FMT_RGBA32F || a.slab == 1) out[at] = make_float4(C01.x, C01.y, C2, 1.0f - T);
+        if (a.out_format != GSR_FMT_RGBA32F) gsr_store_packed(a.out_packed, a.out_format, at, C01.x, C01.y, C2, 1.0f - T);
+        if (a.slab == 1) a.tbuf[at] = T;
     }
     BLP(8)
 #ifdef BL_PROFILE

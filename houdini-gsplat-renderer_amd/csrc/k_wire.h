@@ -81,7 +81,8 @@ k_wire_splats(uint32_t n, GsrFrame f, const float4* __restrict__ geoA, const uin
 
 __global__ void __launch_bounds__(256)
 k_wire_resolve(const unsigned long long* __restrict__ zbuf, size_t npix, const uint4* __restrict__ col0,
-               float4* __restrict__ out, const uint32_t* __restrict__ inv /* index in the upload -> storage slot, or NULL */,
+               void* __restrict__ out /* npix pixels of the target format */, int format,
+               const uint32_t* __restrict__ inv /* index in the upload -> storage slot, or NULL */,
                int over /* 1 = wire-over display: only the pixels an outline covers are written, the frame underneath stays */)
 {
     const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
@@ -94,7 +95,9 @@ k_wire_resolve(const unsigned long long* __restrict__ zbuf, size_t npix, const u
         const uint4 c = col0[inv ? inv[idx] : idx];               // chunk 0 starts with Cd.rgb (f16)
         o = make_float4(gsr_h2f(c.x & 0xffffu), gsr_h2f(c.x >> 16), gsr_h2f(c.y & 0xffffu), 1.0f);
     }
-    out[p] = o;
+    // (Cd is stored as halves: an RGBA16F target gets those bits back unchanged)
+    if (format == GSR_FMT_RGBA32F) reinterpret_cast<float4*>(out)[p] = o;
+    else gsr_store_packed(out, format, p, o.x, o.y, o.z, o.w);
 }
 
 // inv[perm[j]] = j

@@ -96,6 +96,12 @@ OPT_CULL_DILATE = 14
 OPT_LOCAL_SORT = 15
 OPT_FRONT_SLAB = 16
 
+# target formats (gsr_set_target_format): what one pixel of every target is
+TARGET_RGBA32F = 0
+TARGET_RGBA16F = 1
+TARGET_RGBA8 = 2
+TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
+
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
 C_ABI_SYMBOLS = [
     "gsr_device_count", "gsr_create", "gsr_destroy", "gsr_last_error", "gsr_version", "gsr_set_stream",
@@ -119,6 +125,8 @@ C_ABI_SYMBOLS = [
     "gsplat_renderer_query", "gsplat_renderer_get_origin", "gsplat_renderer_get_last_camera_pos",
     "gsplat_renderer_engine", "gsplat_closest_sqrt_power_of_2", "gsplat_quantize_half",
     "gsplat_pack_sh_from_vec3", "gsplat_pack_sh_from_frest", "gsplat_pack_sh_from_array",
+    "gsr_target_pixel_bytes", "gsr_set_target_format", "gsr_get_target_format", "gsr_multi_set_target_format", "gsr_convert_pixels",
+    "gsplat_renderer_set_target_format", "gsplat_renderer_get_target_format",
 ]
 
 
@@ -176,6 +184,13 @@ def load_library() -> C.CDLL:
     L.gsr_debug_frame_plan.argtypes = [i32, vp, vp, vp]
     L.gsr_debug_read_tile_work.argtypes = [vp, vp, i64]
     L.gsr_debug_read_horizons.argtypes = [vp, vp, i64]
+    L.gsr_target_pixel_bytes.argtypes = [i32]
+    L.gsr_set_target_format.argtypes = [vp, i32]
+    L.gsr_get_target_format.argtypes = [vp]
+    L.gsr_multi_set_target_format.argtypes = [vp, i32]
+    L.gsr_convert_pixels.argtypes = [vp, i64, i32, vp]
+    L.gsplat_renderer_set_target_format.argtypes = [vp, i32]
+    L.gsplat_renderer_get_target_format.argtypes = [vp]
     # host shim wrappers
     L.gsplat_renderer_create.restype = vp
     L.gsplat_renderer_create.argtypes = [i32]
@@ -281,6 +296,24 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
+def target_dtype(fmt: int) -> np.dtype:
+    """the numpy channel type of a target format (float32 / float16 / uint8)"""
+    if fmt not in TARGET_DTYPES:
+        raise GsrError(-1, f"unknown target format {fmt}")
+    return TARGET_DTYPES[fmt]
+
+
+def convert_pixels(rgba: np.ndarray, fmt: int) -> np.ndarray:
+    """gsr_convert_pixels: float32 [..., 4] pixels -> the same shape in the target format's channel type, on the host, by the
+    rule the kernels store with (RGBA16F: round to nearest even; RGBA8: clamp, one fma rounding, truncate)"""
+    a = np.ascontiguousarray(rgba, dtype=np.float32)
+    if a.ndim == 0 or a.shape[-1] != 4:
+        raise GsrError(-1, "convert_pixels: the last axis must hold the four channels")
+    out = np.empty(a.shape, dtype=target_dtype(fmt))
+    _check(load_library().gsr_convert_pixels(a.ctypes.data, a.size // 4, int(fmt), out.ctypes.data))
+    return out
+
+
 def camera_struct(cam) -> gsr_camera:
     s = gsr_camera()
     for name in ("obj_view", "object", "inv_object", "view", "proj"):
@@ -319,6 +352,7 @@ class Engine:
         self.h = h
         self.device = device
         self.shard = (0, 1)
+        self.target_format = TARGET_RGBA32F
 
     def close(self):
         if getattr(self, "h", None):
@@ -389,6 +423,12 @@ class Engine:
     def set_option(self, option: int, value: int):
         _check(self.L.gsr_set_option(self.h, option, value))
 
+    def set_target_format(self, fmt: int):
+        """what a pixel of every target is from the next frame on (TARGET_*): the host-returning render* methods return arrays of
+        target_dtype(fmt); the device-pointer methods write pixels of gsr_target_pixel_bytes(fmt) bytes"""
+        _check(self.L.gsr_set_target_format(self.h, int(fmt)))
+        self.target_format = int(fmt)
+
     def set_row_shard(self, index: int, count: int):
         _check(self.L.gsr_set_row_shard(self.h, index, count))
         self.shard = (index, count)
@@ -398,9 +438,9 @@ class Engine:
 
     # ---- per frame
     def render(self, cam) -> np.ndarray:
-        """synchronous render to a host array [rows, W, 4] float32 (row 0 = bottom)"""
+        """synchronous render to a host array [rows, W, 4] of the target format's channel type (float32 by default; row 0 = bottom)"""
         rows = self.band_rows(cam.height)
-        out = np.empty((rows, cam.width, 4), dtype=np.float32)
+        out = np.empty((rows, cam.width, 4), dtype=target_dtype(self.target_format))
         cs = camera_struct(cam)
         _check(self.L.gsr_render(self.h, C.byref(cs), out.ctypes.data, 0))
         return out
@@ -408,7 +448,7 @@ class Engine:
     def render_depth(self, cam, depth: np.ndarray) -> np.ndarray:
         """depth-tested frame; depth = float32 [H, W] window depth of the opaque pass (row 0 = bottom)"""
         rows = self.band_rows(cam.height)
-        out = np.empty((rows, cam.width, 4), dtype=np.float32)
+        out = np.empty((rows, cam.width, 4), dtype=target_dtype(self.target_format))
         d = np.ascontiguousarray(depth, dtype=np.float32).reshape(cam.height, cam.width)
         cs = camera_struct(cam)
         _check(self.L.gsr_render_depth(self.h, C.byref(cs), d.ctypes.data, 0, out.ctypes.data, 0))
@@ -421,15 +461,15 @@ class Engine:
         return dict(zip(POLICY_FIELDS, (int(x) for x in st[:11])))
 
     def render_wire(self, cam) -> np.ndarray:
-        """wireframe overlay (outlines of the +-2 quads, colour Cd), float32 [H, W, 4]"""
-        out = np.empty((cam.height, cam.width, 4), dtype=np.float32)
+        """wireframe overlay (outlines of the +-2 quads, colour Cd), [H, W, 4] in the target format"""
+        out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))
         cs = camera_struct(cam)
         _check(self.L.gsr_render_wire(self.h, C.byref(cs), out.ctypes.data, 0))
         return out
 
     def render_wire_over(self, cam, frame: np.ndarray) -> np.ndarray:
         """wire-over display: the outlines on top of `frame` (a finished beauty frame [H, W, 4]); returns the combined image"""
-        out = np.ascontiguousarray(frame, dtype=np.float32).reshape(cam.height, cam.width, 4).copy()
+        out = np.ascontiguousarray(frame, dtype=target_dtype(self.target_format)).reshape(cam.height, cam.width, 4).copy()
         cs = camera_struct(cam)
         _check(self.L.gsr_render_wire_over(self.h, C.byref(cs), out.ctypes.data, 0))
         return out
@@ -446,7 +486,7 @@ class Engine:
         _check(self.L.gsr_render(self.h, C.byref(cam_struct), C.c_void_p(device_ptr), 1))
 
     def render_struct_to_host(self, cam_struct: gsr_camera, host_ptr: int):
-        """gsr_render into a HOST buffer of height x width x 4 floats (what a caller without GL interop hands over)"""
+        """gsr_render into a HOST buffer of height x width pixels of the target format (what a caller without GL interop hands over)"""
         _check(self.L.gsr_render(self.h, C.byref(cam_struct), C.c_void_p(host_ptr), 0))
 
     def render_struct_depth_to_device(self, cam_struct: gsr_camera, depth_device_ptr: int, device_ptr: int):
@@ -641,6 +681,13 @@ class GSplatRenderer:
     def setSphericalHarmonicsOrder(self, order: int):
         self.L.gsplat_renderer_set_spherical_harmonics_order(self.h, int(order))
 
+    def setTargetFormat(self, fmt: int) -> int:
+        """what a pixel of GSplatRenderContext.target is (TARGET_*); 0, or a negative GSR_E_* code for an unknown format"""
+        return int(self.L.gsplat_renderer_set_target_format(self.h, int(fmt)))
+
+    def targetFormat(self) -> int:
+        return int(self.L.gsplat_renderer_get_target_format(self.h))
+
     def query(self, what: int, rid: str | None = None) -> int:
         return int(self.L.gsplat_renderer_query(self.h, what, rid.encode() if rid else None))
 
@@ -659,7 +706,7 @@ class GSplatRenderer:
         active, then the scene hook runs generate -> render -> postRender (src/DM_GSplatHook.C:30-39)"""
         for rid in rids:
             self.includeInRenderPass(rid)
-        out = np.zeros((cam.height, cam.width, 4), dtype=np.float32)
+        out = np.zeros((cam.height, cam.width, 4), dtype=target_dtype(self.targetFormat()))
         r = self.context(cam, out.ctypes.data, False)
         self.generateRenderGeometry(r)
         self.render(r, False)
@@ -684,6 +731,7 @@ class MultiEngine:
         _check(self.L.gsr_multi_create(arr, len(devices), int(transport), C.byref(h)))
         self.h = h
         self.count = len(devices)
+        self.target_format = TARGET_RGBA32F
 
     def close(self):
         if getattr(self, "h", None):
@@ -712,12 +760,17 @@ class MultiEngine:
     def set_option(self, option: int, value: int):
         _check(self.L.gsr_multi_set_option(self.h, option, value))
 
+    def set_target_format(self, fmt: int):
+        """every rank renders, and the gather moves, pixels of this format (TARGET_*) from the next frame on"""
+        _check(self.L.gsr_multi_set_target_format(self.h, int(fmt)))
+        self.target_format = int(fmt)
+
     def upload(self, splats, origin=(0.0, 0.0, 0.0)):
         a = _Arrays(splats)
         _check(self.L.gsr_multi_upload(self.h, a.n, *a.ptrs(), _f3(origin)))
 
     def render(self, cam, depth=None) -> np.ndarray:
-        out = np.empty((cam.height, cam.width, 4), dtype=np.float32)
+        out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))
         cs = camera_struct(cam)
         if depth is None:
             _check(self.L.gsr_multi_render(self.h, C.byref(cs), out.ctypes.data, 0))

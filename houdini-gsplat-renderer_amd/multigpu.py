@@ -57,8 +57,12 @@ class FrameGatherer:
     (already initialised: backend nccl == RCCL on ROCm, or gloo on CPU) or None for 1 rank."""
 
     def __init__(self, dist, rank: int, world: int, width: int, height: int, device, engine=None,
-                 via_host: bool = False, layout: int = 0):
+                 via_host: bool = False, layout: int = 0, dtype=None):
+        """dtype: the channel type of the band (torch.float32 by default; torch.float16 / torch.uint8 for an engine whose target
+        format is RGBA16F / RGBA8): packed bands are gathered as they are, at half or a quarter of the bytes"""
         import torch
+
+        dtype = torch.float32 if dtype is None else dtype
 
         self.layout = layout        # 0 = interleaved tile rows, 1 = contiguous bands (GSR_OPT_SHARD_LAYOUT)
         self.via_host = via_host    # functional-test mode: collective on host copies (backend without GPU support)
@@ -66,11 +70,11 @@ class FrameGatherer:
         self.width, self.height = width, height
         self.engine = engine
         self.rows = band_rows(height, world) if world > 1 else height
-        self.band = torch.zeros((self.rows, width, 4), dtype=torch.float32, device=device)
+        self.band = torch.zeros((self.rows, width, 4), dtype=dtype, device=device)
         self.gathered = self.final = None
         if world > 1 and rank == 0:
-            self.gathered = torch.zeros((world, self.rows, width, 4), dtype=torch.float32, device=device)
-            self.final = torch.zeros((height, width, 4), dtype=torch.float32, device=device)
+            self.gathered = torch.zeros((world, self.rows, width, 4), dtype=dtype, device=device)
+            self.final = torch.zeros((height, width, 4), dtype=dtype, device=device)
 
     def gather_and_stitch(self):
         """returns the full frame tensor on rank 0 (None elsewhere); 1 rank: the band itself"""

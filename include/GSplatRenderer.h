@@ -46,7 +46,8 @@ typedef struct GSplatRenderContext {
                              gives the camera position (src/GSplatRenderer.C:558-562) */
     float proj[16];       /* glH_ProjectMatrix   */
     int32_t width, height;/* glH_ScreenSize      */
-    float* target;        /* RGBA-f32 premultiplied, row 0 = bottom; height*width*4 floats */
+    float* target;        /* premultiplied RGBA, row 0 = bottom: height*width pixels of the renderer's target format
+                             (setTargetFormat; RGBA-f32 = height*width*4 floats by default) */
     int32_t target_is_device;
     const float* depth;   /* optional: window depth (0..1, row 0 = bottom) left by the opaque pass; the splats are
                              depth-tested against it with depth writes off (src/GSplatRenderer.C:595-610); NULL = none */
@@ -89,6 +90,10 @@ public:
     void setRenderingEnabled(bool isRenderEnabled);
     void setExplicitCameraPos(const float explicitCameraPos[3]);
     void setSphericalHarmonicsOrder(int shOrder);
+    /* what a pixel of GSplatRenderContext::target is: GSR_TARGET_RGBA32F (default) / _RGBA16F / _RGBA8 (gsplat_hip.h).  Takes effect
+     * with the next render(); GSR_OK, or GSR_E_INVALID for an unknown format (the format in use stays).  A dry instance remembers it. */
+    int setTargetFormat(int format);
+    int targetFormat() const { return target_format_; }
 
     /* introspection (no reference counterpart; used by tests and the C wrappers) */
     enum Query {
@@ -155,6 +160,7 @@ private:
     float eye_explicit_[3] = {0, 0, 0};
     float eye_[3] = {0, 0, 0};
     int sh_order_ = 3;
+    int target_format_ = 0;             /* GSR_TARGET_RGBA32F */
     int64_t stagings_ = 0, frames_ = 0;
     int status_ = 0;
     bool obj_notice_given_ = false;
@@ -190,6 +196,8 @@ void gsplat_renderer_redraw(gsplat_renderer* h, const char* const* ids, int n, G
 void gsplat_renderer_set_rendering_enabled(gsplat_renderer* h, int enabled);
 void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos[3]);
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order);
+int  gsplat_renderer_set_target_format(gsplat_renderer* h, int format);   /* GSplatRenderer::setTargetFormat */
+int  gsplat_renderer_get_target_format(gsplat_renderer* h);               /* the format in use; <0 for a NULL handle */
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id_or_null);
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]);
 void gsplat_renderer_get_last_camera_pos(gsplat_renderer* h, float out[3]);

@@ -126,6 +126,29 @@ const char* gsr_version(void);
  * stream); NULL restores the context's own stream. */
 int  gsr_set_stream(gsr_context* ctx, void* hip_stream);
 
+/* ---- target format ------------------------------------------------------ */
+/* What one pixel of every target of the context is: gsr_render* frames, the band images of a sharded context, what
+ * gsr_stitch_bands and the gsr_multi / gsr_comm gather move, and the wire overlay.  The f32 pixel is formed exactly as ever; the
+ * format only decides how the blend kernel STORES it (no conversion pass runs behind it):
+ *   RGBA32F  16 bytes  the f32 pixel itself (default; bit-identical to a context that never heard of formats)
+ *   RGBA16F   8 bytes  binary16 of every channel, round to nearest even, overflow to infinity (the rule of gsplat_quantize_half)
+ *   RGBA8     4 bytes  c = x clamped to [0, 1] (NaN -> 0); byte = (uint8_t)fmaf(c, 255, 0.5): one rounding, then truncation.
+ *                      Linear, premultiplied; no sRGB curve -- that belongs to whoever owns the display transform.
+ * A packed target holds the rounded FINAL pixel (the reference's GL blend into such a target rounds after every fragment).
+ * The float* rgba_out parameters below keep their C type and mean "rows*width pixels of the context's target format"; a DEVICE
+ * target must be aligned to the pixel size (GSR_E_INVALID otherwise).  This is not a GSR_OPT_* knob: those never change pixels. */
+#define GSR_TARGET_RGBA32F    0
+#define GSR_TARGET_RGBA16F    1
+#define GSR_TARGET_RGBA8      2
+int  gsr_target_pixel_bytes(int format);                  /* 16 / 8 / 4, GSR_E_INVALID for anything else; needs no context */
+/* Takes effect with the next frame.  Synchronises the context and drops what is laid out for the old pixel size (the staging
+ * images of host targets, a front-slab frame's intermediate buffer). */
+int  gsr_set_target_format(gsr_context* ctx, int format);
+int  gsr_get_target_format(gsr_context* ctx);
+/* The same conversion on the host (no context, no GPU): n_pixels RGBA-f32 pixels -> `format`, through the very functions the
+ * kernels store with.  For callers who keep f32 frames; also what the tests hold the GPU path to. */
+int  gsr_convert_pixels(const float* rgba32f, int64_t n_pixels, int format, void* out);
+
 /* ---- geometry staging (active set changed) ------------------------------ */
 /* Arrays are HOST pointers in the reference's registerUpdate() layout
  * (include/GSplatRenderer.h:34-47): P float[3n]; Cd half[3n]; alpha float[n];
@@ -174,14 +197,15 @@ int  gsr_upload(gsr_context* ctx, int64_t n,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
  * (layout 1, GSR_OPT_SHARD_LAYOUT: a rank keeps ~1/count of the splats, so its sort/binning/colour work shrinks too).
  * Its output is the compact band image: the owned tile rows stacked bottom-up, gsr_band_rows() pixel rows of `width`
- * RGBA-f32 pixels.  The stitched frame is bit-identical to the unsharded one in either layout.  The band is padded to the
+ * pixels of the context's target format.  The stitched frame is bit-identical to the unsharded one in either layout.  The band is padded to the
  * same height on every rank: pixel rows behind the rank's last image row (a last tile row the image does not fill, whole
  * tile rows of a rank that owns fewer than the others, all of it for a rank beyond the image) are NEVER written in a
  * device target -- clear it once if they are to read as zeros -- and read as zeros in a host target. */
 int  gsr_set_row_shard(gsr_context* ctx, int index, int count);
 int  gsr_band_rows(int height, int index, int count);      /* pixel rows in that band image */
 /* Root side: bands[count] gathered back to back (each padded to
- * gsr_band_rows(height, 0, count) rows) -> full image.  Device pointers. */
+ * gsr_band_rows(height, 0, count) rows) -> full image.  Device pointers; pixels of ctx's target format (set the format the
+ * ranks render in on the stitching context too): a row copy, never a conversion. */
 int  gsr_stitch_bands(gsr_context* ctx, const float* gathered, int count,
                       int width, int height, float* rgba_out);
 
@@ -207,6 +231,7 @@ gsr_context* gsr_multi_context(gsr_multi* m, int rank);      /* rank's context (
 int  gsr_multi_set_stream(gsr_multi* m, void* hip_stream);   /* the stream on devices[0] that frames are ORDERED on (the
                                                                  ranks' kernels and the gather run on streams of the library) */
 int  gsr_multi_set_option(gsr_multi* m, int option, int value);
+int  gsr_multi_set_target_format(gsr_multi* m, int format);   /* every rank and the root (gsr_set_target_format); synchronises */
 /* what RCCL itself reports: ranks_out[g] = ncclCommUserRank of rank g's communicator, *nranks_out = ncclCommCount of the
  * root's (-1 / 0 with the COPY transport) */
 int  gsr_multi_comm_info(gsr_multi* m, int* ranks_out, int* nranks_out);
@@ -224,7 +249,7 @@ int  gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const uint16_t* C
                       const uint16_t* scale, const uint16_t* orient,
                       const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, const float origin[3]);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
- * memory (synchronous) */
+ * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
 int  gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const float* depth, int depth_is_device,
                             float* rgba_out, int out_is_device);
@@ -233,7 +258,7 @@ int  gsr_multi_get_stats(gsr_multi* m, int rank, gsr_stats* out);
 
 /* ---- one process per GPU (torchrun-style launches): the same gather ----------- */
 /* The launcher hands every rank the 128-byte id rank 0 obtained (any side channel); after gsr_comm_init a frame is one
- * call per rank: the rank's band is rendered, sent (ncclSend) or received (root: straight into rgba_out_device with the
+ * call per rank: the rank's band is rendered (in the context's target format: set the same one on every rank), sent (ncclSend) or received (root: straight into rgba_out_device with the
  * band layout, stitched there with interleaved rows).  With world > 1 the context's kernels move to a stream of the
  * library and the collective to a second one (the gather of frame f overlaps frame f+1); the frame is ORDERED on the
  * context's public stream (gsr_set_stream, before or after gsr_comm_init).  rgba_out_device is the FULL frame on the root
@@ -248,8 +273,8 @@ int  gsr_comm_render(gsr_context* ctx, const gsr_camera* cam, const float* depth
                      float* rgba_out_device);
 
 /* ---- per frame ---------------------------------------------------------- */
-/* Renders the uploaded splats.  rgba_out: float[rows*width*4], premultiplied
- * RGBA, row 0 = BOTTOM row (GL window coordinates), cleared to 0 -- what the
+/* Renders the uploaded splats.  rgba_out: rows*width pixels of the context's target format
+ * (float[rows*width*4] by default), premultiplied RGBA, row 0 = BOTTOM row (GL window coordinates), cleared to 0 -- what the
  * reference's blend leaves in an initially transparent float target.  rows =
  * height, or gsr_band_rows() when sharded.  out_is_device: 0 = host pointer
  * (synchronous), 1 = device pointer: asynchronous, ordered on the context's public stream
@@ -267,12 +292,12 @@ int  gsr_render_depth(gsr_context* ctx, const gsr_camera* cam, const float* dept
 
 /* Wireframe overlay (the reference's wire program, shaders/GSplatShaderSource.h:22-110 drawn in
  * src/GR_GSplat.C:477-483): the outline of every splat's +-2 quad in colour Cd, alpha 1, nearest line wins,
- * background 0.  Whole image (ignores the row shard), synchronous.  Like the reference's wire program it uses
+ * background 0, in the context's target format (Cd is stored as halves: RGBA16F gets those bits).  Whole image (ignores the row shard), synchronous.  Like the reference's wire program it uses
  * P without the GSplatOrigin round trip and no object matrix in the covariance. */
 int  gsr_render_wire(gsr_context* ctx, const gsr_camera* cam, float* rgba_out, int out_is_device);
 /* Wire-OVER display: the reference draws the outlines and still includes the primitive in the splat pass
  * (src/GR_GSplat.C:471-486), so shaded + wire shows both.  The outlines are written on top of the frame that is
- * already in rgba_inout (a finished gsr_render / gsr_render_depth target of the same size); pixels no outline
+ * already in rgba_inout (a finished gsr_render / gsr_render_depth target of the same size and format); pixels no outline
  * covers keep their value. */
 int  gsr_render_wire_over(gsr_context* ctx, const gsr_camera* cam, float* rgba_inout, int is_device);
 

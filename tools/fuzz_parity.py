@@ -161,7 +161,11 @@ def execute(sc, dut, verbose=False):
     index, count, layout = sc["shard"]
     plain = E.Engine(0)
     frames = 0
+    # --formats: the context under test renders into a packed target; the expected image is gsr_convert_pixels of the plain f32 frame
+    fmt = sc.get("format", 0)
+    bpp, dt = 16 >> fmt, E.target_dtype(fmt)
     try:
+        dut.set_target_format(fmt)
         if multi:
             dut.set_option(E.OPT_SHARD_LAYOUT, layout)
         for e in ((plain,) if multi else (dut, plain)):
@@ -200,9 +204,11 @@ def execute(sc, dut, verbose=False):
                         e.set_row_shard(fl[1], fl[2])
                     count_now = fl[2]
             want = plain.render(c) if depth is None else plain.render_depth(c, depth)
+            if fmt:
+                want = E.convert_pixels(want, fmt)
             if sc.get("dev_target"):
                 rows_ = dut.band_rows(c.height) if count_now > 1 else c.height
-                nbytes = rows_ * c.width * 16
+                nbytes = rows_ * c.width * bpp
                 if devbuf[1] < nbytes:
                     if devbuf[0].value: HIP.hipFree(devbuf[0])
                     assert HIP.hipMalloc(C.byref(devbuf[0]), C.c_size_t(nbytes)) == 0
@@ -216,14 +222,14 @@ def execute(sc, dut, verbose=False):
                     assert HIP.hipMemsetAsync(devbuf[0], 0xff if k % 2 else 0, C.c_size_t(nbytes), ustream[0]) == 0      # (poison, then zeros: the
                     assert HIP.hipMemsetAsync(devbuf[0], 0, C.c_size_t(nbytes), ustream[0]) == 0                          #  frame must come after both)
                     dut.render_to_device(c, devbuf[0].value)
-                    got = np.empty((rows_, c.width, 4), np.float32)
+                    got = np.empty((rows_, c.width, 4), dt)
                     assert HIP.hipMemcpyAsync(C.c_void_p(got.ctypes.data), devbuf[0], C.c_size_t(nbytes), 2, ustream[0]) == 0
                     assert HIP.hipStreamSynchronize(ustream[0]) == 0
                 else:
                     assert HIP.hipMemset(devbuf[0], 0, C.c_size_t(nbytes)) == 0      # (band padding is never written in a device target)
                     dut.render_to_device(c, devbuf[0].value)
                     dut.synchronize()
-                    got = np.empty((rows_, c.width, 4), np.float32)
+                    got = np.empty((rows_, c.width, 4), dt)
                     assert HIP.hipMemcpy(C.c_void_p(got.ctypes.data), devbuf[0], C.c_size_t(nbytes), 2) == 0
             else:
                 got = (dut.render(c) if depth is None else (dut.render(c, depth) if multi else dut.render_depth(c, depth)))
@@ -235,8 +241,8 @@ def execute(sc, dut, verbose=False):
                 if tr != truncated_seen:
                     truncated_seen = tr
                     continue
-            if not np.array_equal(got, want, equal_nan=True):
-                d = np.nan_to_num(np.abs(got - want), nan=1.0)
+            if not (np.array_equal(got.view(np.uint8), want.view(np.uint8)) if fmt else np.array_equal(got, want, equal_nan=True)):
+                d = np.nan_to_num(np.abs(got.astype(np.float32) - want.astype(np.float32)), nan=1.0)
                 rows = np.nonzero(d.max(axis=(1, 2)))[0]
                 st = dut.stats()
                 return frames, (f"frame {k}: max |diff| {float(d.max())}, {int((d.max(axis=-1) > 0).sum())} pixels, rows {rows[0]}..{rows[-1]} | "
@@ -264,19 +270,27 @@ def fresh_dut(sc):
 
 
 def main():
-    iters = int(sys.argv[1]) if len(sys.argv) > 1 else 40
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    first = int(sys.argv[3]) if len(sys.argv) > 3 else 0        # (skip the iterations before this one: same random sequence)
-    mode = sys.argv[4] if len(sys.argv) > 4 else "0"
+    # --formats (off by default): every iteration also draws a target format (RGBA32F / RGBA16F / RGBA8) for the context under test,
+    # from a generator of its own -- the scripts themselves are the ones the same seed gives without the switch
+    formats = "--formats" in sys.argv
+    argv = [a for a in sys.argv if a != "--formats"]
+    iters = int(argv[1]) if len(argv) > 1 else 40
+    seed = int(argv[2]) if len(argv) > 2 else 1
+    first = int(argv[3]) if len(argv) > 3 else 0        # (skip the iterations before this one: same random sequence)
+    mode = argv[4] if len(argv) > 4 else "0"
     heavy, longlived = mode == "1", mode in ("2", "3")
     multi_ll = 3 if mode == "3" else 0         # mode 3: the long-lived context is a gsr_multi of three contexts on this GPU
     rng = np.random.default_rng(seed)
+    frng = np.random.default_rng([seed, 977])
     t_start = time.time()
     frames = 0
     keep_dut = None
     history = []
     for it in range(iters):
         sc = make_script(rng, it, heavy, longlived)
+        if formats:
+            sc["format"] = int(frng.integers(0, 3))
+            sc["desc"].update(format=sc["format"])
         if multi_ll:
             sc["multi"] = multi_ll; sc["shard"] = (0, 1, sc["shard"][2]); sc["cuts"] = None; sc["dev_target"] = False; sc["user_stream"] = False
             sc["opts"].pop(E.OPT_DEFERRED_CHECK, None)
