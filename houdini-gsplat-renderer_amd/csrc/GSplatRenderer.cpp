@@ -269,7 +269,7 @@ void GSplatRenderer::render(GSplatRenderContext& r, bool isObjectLevel)
     cam.height = r.height;
     cam.sh_order = (sh_order_ > 0 && resident_.sh) ? sh_order_ : 0;   // SH needs an order AND data
     status_ = multi_ ? gsr_multi_render_depth(multi_, &cam, r.depth, r.depth_is_device, r.target, r.target_is_device)
-                     : gsr_render_depth(engine_, &cam, r.depth, r.depth_is_device, r.target, r.target_is_device);
+                     : gsr_render_aov(engine_, &cam, r.depth, r.depth_is_device, r.target, r.target_is_device, aov_, aov_plane_);
     if (status_ != GSR_OK) { note("error", "frame failed: %s", gsr_last_error()); return; }
     ++frames_;
 }
@@ -304,6 +304,14 @@ int GSplatRenderer::setTargetFormat(int format)
     else if (engine_) rc = gsr_set_target_format(engine_, format);
     if (rc == GSR_OK) target_format_ = format;
     return rc;
+}
+
+int GSplatRenderer::setAovTarget(int aov, float* plane)
+{
+    if ((aov != 0 && aov != GSR_AOV_DEPTH) || (multi_ && aov != 0 && plane)) return GSR_E_INVALID;
+    aov_ = plane ? aov : 0;
+    aov_plane_ = aov_ ? plane : nullptr;
+    return GSR_OK;
 }
 
 int64_t GSplatRenderer::query(int what, const std::string& id) const
@@ -409,6 +417,7 @@ void gsplat_renderer_set_rendering_enabled(gsplat_renderer* h, int enabled) { if
 void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos[3]) { if (h && pos) h->impl->setExplicitCameraPos(pos); }
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order) { if (h) h->impl->setSphericalHarmonicsOrder(order); }
 int gsplat_renderer_set_target_format(gsplat_renderer* h, int format) { return h ? h->impl->setTargetFormat(format) : GSR_E_INVALID; }
+int gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane) { return h ? h->impl->setAovTarget(aov, plane) : GSR_E_INVALID; }
 int gsplat_renderer_get_target_format(gsplat_renderer* h) { return h ? h->impl->targetFormat() : GSR_E_INVALID; }
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id) { return h ? h->impl->query(what, id ? std::string(id) : std::string()) : -1; }
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]) { if (h && out) h->impl->origin(out); }

@@ -91,6 +91,8 @@ struct FrameArgs {
     bool depth_is_device = false;
     float* out = nullptr;              // the caller's image (host or device)
     bool out_is_device = false;
+    int aov = 0;                       // GSR_AOV_*: the plane rendered beside the image (0: none) ...
+    float* aov_out = nullptr;          // ... into the caller's buffer, where the image lives (host or device)
 };
 
 // what a queued frame needs again when it is finished (or its back end re-queued)
@@ -128,6 +130,7 @@ struct FrameJob {
     bool dblind = false;           // ... and k_cluster_cull ran without the depth pyramids (they were built beside it, for K1)
     bool dstat = false;            // ... and the depth pyramid pass masked the covered depths with the tiles' status (a culled frame with a valid status)
     bool blend_guess_plain = false;   // the plain blend kernel was launched, guarded by "no pixel is covered" (queue_back_end)
+    float2* aov_target = nullptr;  // depth AOV: the device plane the blend kernel writes ({zsum, cov} per band pixel); NULL = a frame without it
 };
 
 // Everything one frame in flight owns: its HIP stream, the per-frame HBM arrays, the small
@@ -220,6 +223,9 @@ struct FrameSlot {
     float* fb = nullptr;               // staging for host-pointer output: pixels of the context's target format (fb_cap counts floats)
     size_t fb_cap = 0;
     int fb_sig[6] = {-1, -1, -1, -1, -1, -1};   // the band shape (and target format) the staging buffer was last cleared for
+    float* aovb = nullptr;             // staging for a host-pointer AOV plane: two floats per band pixel (aovb_cap counts floats)
+    size_t aovb_cap = 0;
+    int aovb_sig[5] = {-1, -1, -1, -1, -1};     // the band shape the plane's staging buffer was last cleared for
     float* fb32 = nullptr;             // packed target formats, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
     size_t fb32_cap = 0;
     // small device/host mailboxes
@@ -488,7 +494,7 @@ static void slot_destroy(FrameSlot& sl)
     slot_free_splat_arrays(sl);
     dev_free(sl.hist); dev_free(sl.totals);
     dev_free(sl.pvA);
-    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32);
+    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32); dev_free(sl.aovb);
     dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
     if (sl.h_end) (void)hipHostFree(sl.h_end); dev_free(sl.depth_stage); dev_free(sl.dpyr); dev_free(sl.dactive);
     dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
@@ -1459,13 +1465,27 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
             a.row_lo = nb > 1 ? (int)((int64_t)f.local_tiles_y * b / nb) : 0;
             a.row_hi = nb > 1 ? (int)((int64_t)f.local_tiles_y * (b + 1) / nb) : 0x7fffffff;
             sl.band_row[b] = a.row_lo; sl.band_row[b + 1] = nb > 1 ? a.row_hi : f.local_tiles_y;
-            if (with_depth)
+            if (j.aov_target) {   // the depth AOV: the same walk, the plane behind the colour (k_blend.h: k_blend_aov)
+                if (with_depth)
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
+                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.aov_target);
+                else
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
+                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.aov_target);
+            } else if (with_depth)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
                                    sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz);
             else
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
                                    sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz);
-            if (j.lazy) {   // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
+            if (j.lazy && j.aov_target) {
+                if (with_depth)
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
+                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.aov_target);
+                else
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
+                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.aov_target);
+            } else if (j.lazy) {   // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
                 if (with_depth)
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
                                        sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz);
@@ -1515,7 +1535,8 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
     // Depth-tested frames: the plain kernel, guarded, while the slot's depth buffers have been clear (k_blend.h: GsrBlendArgs.guard);
     // not for a frame that is handed over before its mailbox is read (nobody could queue the other kernel in time)
     // (... nor over lists whose index words carry depth codes: only the depth-tested kernel masks them off)
-    sl.job.blend_guess_plain = j.d_depth != nullptr && j.dcull && !c->depth_active && !j.deferred && j.f.idx_mask == 0xffffffffu;
+    // (... nor for a frame with the depth AOV: a void launch would leave its plane unwritten, and the AOV kernels have no guarded form)
+    sl.job.blend_guess_plain = j.d_depth != nullptr && j.dcull && !c->depth_active && !j.deferred && j.f.idx_mask == 0xffffffffu && !j.aov_target;
     if ((rc = queue_blend(c, sl, j.d_depth != nullptr && !sl.job.blend_guess_plain, sl.job.blend_guess_plain))) return rc;
     return mark(sl, 6);
 }
@@ -1635,9 +1656,11 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
                 HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, reinterpret_cast<const char*>(sl.fb) + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
             }
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
+            if (j.aov_target) HIP_TRY(hipMemcpyAsync(j.args.aov_out, sl.aovb, j.out_px * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         } else {
             HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb, j.out_px * bpp, hipMemcpyDeviceToHost, s));
+            if (j.aov_target) HIP_TRY(hipMemcpyAsync(j.args.aov_out, sl.aovb, j.out_px * 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
     }
@@ -2071,6 +2094,23 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         }
         j.target = sl.fb;
     }
+    // The depth AOV's plane: the caller's device buffer, or -- a host buffer -- a staging plane of the slot's own, cleared like the
+    // staging image whenever the band's shape changes (the padding rows of a sharded context's band plane read as zeros)
+    if (a.aov != 0 && a.aov_out != nullptr) {
+        j.aov_target = reinterpret_cast<float2*>(a.aov_out);
+        if (!a.out_is_device) {
+            if (j.out_px * 2 > sl.aovb_cap) {
+                if ((rc = regrow(s, sl.aovb, sl.aovb_cap, j.out_px * 2, j.out_px * 2))) return rc;
+                std::memset(sl.aovb_sig, 0xff, sizeof sl.aovb_sig);
+            }
+            const int asig[5] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb};
+            if (std::memcmp(asig, sl.aovb_sig, sizeof asig) != 0) {
+                HIP_TRY(hipMemsetAsync(sl.aovb, 0, j.out_px * 8, s));
+                std::memcpy(sl.aovb_sig, asig, sizeof asig);
+            }
+            j.aov_target = reinterpret_cast<float2*>(sl.aovb);
+        }
+    }
 
     j.open = true;   // from here on kernels are queued: every error path drains them (frame_abort)
     if ((rc = mark(sl, 0))) return frame_abort(sl, rc);
@@ -2167,9 +2207,12 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         // K1 over the survivors (the plan's grid: a frame that keeps more loops); on a cache hit (identical frame description) the sorted
         // (keyA, valA) are kept and K1's key/payload output goes to the scratch buffers
         // (two instantiations: the one that leaves the colours pending has no SH evaluation in it and runs at 8 waves per SIMD instead of 6)
-        hipLaunchKernelGGL(j.d_depth ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(j.k1_grid ? j.k1_grid : 1u), dim3(GSR_K1_THREADS), 0, s, n, c->cap, f, c->geoA, c->geoB, c->col,
+        // (a frame with the depth AOV takes the depth-tested twins for the window depths they write; without a depth buffer it brings no
+        //  pyramids -- dc_k1 is empty -- so nothing is culled against a depth that is not there)
+        const bool k1_zwin = j.d_depth != nullptr || j.aov_target != nullptr;
+        hipLaunchKernelGGL(k1_zwin ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(j.k1_grid ? j.k1_grid : 1u), dim3(GSR_K1_THREADS), 0, s, n, c->cap, f, c->geoA, c->geoB, c->col,
                            sl.rec, (p.cache_hit || p.ordered) ? sl.keyB : sl.keyA, (p.cache_hit || p.ordered) ? sl.valB : sl.valA,
-                           j.d_depth ? sl.zwin : (float*)nullptr, j.phase == 2 ? sl.hpyr2 : (j.cull ? sl.hpyr : (const float*)nullptr), sl.blk_cnt,
+                           k1_zwin ? sl.zwin : (float*)nullptr, j.phase == 2 ? sl.hpyr2 : (j.cull ? sl.hpyr : (const float*)nullptr), sl.blk_cnt,
                            sl.cseg, sl.ccnt, ngroups, (uint32_t)CC_THREADS * (uint32_t)rounds, sl.d_counts, scat,
                            // (the count of sorted splats starts at zero: a frame whose clusters are ALL culled runs no sort workgroup that
                            //  could say so, and the binning kernels would walk the previous frame's order; a static redraw keeps its order)
@@ -2355,9 +2398,19 @@ extern "C" int gsr_render(gsr_context* c, const gsr_camera* cam, float* rgba_out
 extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
                                 float* rgba_out, int out_is_device)
 {
+    return gsr_render_aov(c, cam, depth, depth_is_device, rgba_out, out_is_device, 0, nullptr);
+}
+
+// gsr_render_depth + one AOV plane beside the image (aov = 0 or aov_out = NULL: gsr_render_depth itself)
+extern "C" int gsr_render_aov(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
+                              float* rgba_out, int out_is_device, int aov, float* aov_out)
+{
     if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
     if (out_is_device && !target_aligned(c, rgba_out)) return set_err(GSR_E_INVALID, "gsr_render: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
-    const FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0};
+    if (aov != 0 && aov != GSR_AOV_DEPTH) return set_err(GSR_E_INVALID, "gsr_render_aov: unknown AOV %d", aov);
+    if (aov_out == nullptr) aov = 0;
+    if (aov && out_is_device && (uintptr_t)aov_out % 8u != 0) return set_err(GSR_E_INVALID, "gsr_render_aov: the device plane is not aligned to its 8-byte pixel");
+    const FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0, aov, aov ? aov_out : nullptr};
     FrameSlot* sl = nullptr;
 #ifdef GSR_HOST_PHASES
     static double acc[4] = {0, 0, 0, 0}, t_last_exit = 0; static long cnt = 0;
@@ -2382,6 +2435,33 @@ extern "C" int gsr_render_depth(gsr_context* c, const gsr_camera* cam, const flo
     if (++cnt % 50 == 0) { fprintf(stderr, "[host phases] begin %.1f  finish(pair wait + frame end) %.1f  check(verdict wait) %.1f  outside gsr_render %.1f us\n", acc[0] / 50, acc[1] / 50, acc[2] / 50, acc[3] / 50); acc[0] = acc[1] = acc[2] = acc[3] = 0; }
 #endif
     return rc;
+}
+
+// ---- depth AOV -> window depth (gsr_device.h: gsr_resolve_depth_pixel) ----
+extern "C" int gsr_resolve_depth(const float* aov, int64_t n_pixels, float cov_min, float* depth_out)
+{
+    if (n_pixels < 0 || !aov || !depth_out) return set_err(GSR_E_INVALID, "gsr_resolve_depth: bad argument");
+    for (int64_t i = 0; i < n_pixels; ++i) depth_out[i] = gsr_resolve_depth_pixel(aov[2 * i], aov[2 * i + 1], cov_min);
+    return GSR_OK;
+}
+
+__global__ void __launch_bounds__(256)
+k_resolve_depth(const float2* __restrict__ aov, int64_t n, float cov_min, float* __restrict__ depth_out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { const float2 v = aov[i]; depth_out[i] = gsr_resolve_depth_pixel(v.x, v.y, cov_min); }
+}
+
+extern "C" int gsr_resolve_depth_device(gsr_context* c, const float* aov, int64_t n_pixels, float cov_min, float* depth_out)
+{
+    if (!c || n_pixels < 0 || !aov || !depth_out) return set_err(GSR_E_INVALID, "gsr_resolve_depth_device: bad argument");
+    if ((uintptr_t)aov % 8u != 0) return set_err(GSR_E_INVALID, "gsr_resolve_depth_device: the plane is not aligned to its 8-byte pixel");
+    if (n_pixels > (int64_t)GSR_MAX_DIM * GSR_MAX_DIM) return set_err(GSR_E_INVALID, "gsr_resolve_depth_device: more pixels than the largest frame");
+    if (n_pixels == 0) return GSR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_resolve_depth, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, c->stream, reinterpret_cast<const float2*>(aov), n_pixels, cov_min, depth_out);
+    HIP_TRY(hipGetLastError());
+    return GSR_OK;
 }
 
 // split form for callers that drive several contexts from one thread (gsr_multi.cpp)

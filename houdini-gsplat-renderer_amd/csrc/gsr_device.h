@@ -170,6 +170,15 @@ __device__ __forceinline__ void gsr_store_packed(void* __restrict__ target, int 
     else reinterpret_cast<uint32_t*>(target)[p] = gsr_pack_rgba8(r, g, b, a);
 }
 
+// ---- depth AOV (gsplat_hip.h: GSR_AOV_DEPTH) ----------------------------------
+// A pixel of the plane {zsum, cov} -> a window depth.  THE rule, in one place: gsr_resolve_depth (host) and the kernel of
+// gsr_resolve_depth_device both go through it.  One IEEE division (HIP's float `/` is correctly rounded), clamped to the far plane;
+// too little coverage, or none, is the far plane -- what a cleared depth buffer holds.
+__host__ __device__ __forceinline__ float gsr_resolve_depth_pixel(float zsum, float cov, float cov_min)
+{
+    return cov >= cov_min ? __builtin_fminf(zsum / cov, 1.0f) : 1.0f;
+}
+
 // The contract's 2^x for x in [-2^22, 0]: identical operation sequence to the oracle's gso_exp2f
 // (round to the nearest-even integer with the 1.5*2^23 trick, EXACT remainder r = x - k, degree-5
 // polynomial for 2^r on [-0.5, 0.5], exponent add).  <= 2.8 ulp, exp2(0) == 1, never above 1.

@@ -42,6 +42,9 @@
                               // C4 64 -> 0.195 ms, 128 -> 0.190, 256 -> 0.187.  Requesting the next sub-round's records ahead of
                               // the inner loop (12 more registers: 5 waves per SIMD) measured 0.196: latency is covered already
 #endif
+#ifndef BL_CHECK_AOVD
+#define BL_CHECK_AOVD 2       // ... in the plain loop of the depth-tested AOV kernel (k_blend_aov<true>), which has no register to spare
+#endif
 #define BL_QCAP 2048          // hit-queue ring capacity (>= BL_BATCH + the 1024 entries of a scan step)
 #define BL_PAIR_F4_MAX 6      // float4s per staged record PAIR: 5 (80 B), 6 with the depth test
 #define GSR_T_MIN 6.103515625e-05f  // 2^-14
@@ -136,19 +139,24 @@ struct GsrLazyArgs {
     int32_t* redo;             // tiles given up by the plain kernel
     uint32_t* redo_count;
 };
-template <bool HAS_DEPTH, bool LAZY>
+// AOV = true (the depth AOV, k_blend_aov below): the window depth of EVERY staged record travels in szl, the loop carries
+// Z = fma(w, zwin, Z) beside the colour -- the same w, the same fragments, the same order -- and the pixel's {Z, 1 - T} goes to `aov`
+// (float32 whatever the target format; indexed like the band image).  AOV = false compiles all of it out: the colour kernels are
+// instruction for instruction what they were.
+template <bool HAS_DEPTH, bool LAZY, bool AOV = false>
 __device__ __forceinline__ void
 gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
                const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
                const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
-               const float* __restrict__ zwin, const float* __restrict__ depth, const GsrLazyArgs& lz)
+               const float* __restrict__ zwin, const float* __restrict__ depth, const GsrLazyArgs& lz, float2* __restrict__ aov = nullptr)
 {
+    constexpr bool ZSTAGE = HAS_DEPTH || AOV;   // the staged records' window depths are kept
     constexpr int PF4 = 5;
     __shared__ float4 slist[4][(BL_ROUND / 2) * PF4];
     // depth-tested frames: the staged records' window depths, pair by pair, in an array of their OWN -- as a sixth vector of the pair
     // block they cost every tile of the launch (a 96-byte block stride puts the staging stores on 8 banks instead of 16, and the plain
     // loop of a tile the geometry does not touch skipped 16 of every 96 bytes): the depth-tested kernel under a clear buffer was 10 % slower
-    __shared__ float2 szl[HAS_DEPTH ? 4 : 1][HAS_DEPTH ? BL_ROUND / 2 : 1];
+    __shared__ float2 szl[ZSTAGE ? 4 : 1][ZSTAGE ? BL_ROUND / 2 : 1];
     __shared__ uint32_t q[BL_QCAP];   // hit queue: splat indices in list (= depth) order
     __shared__ __attribute__((aligned(16))) uint32_t scnt[2][4];   // hits of each wave in a scan step
     __shared__ uint32_t sdone[2][4];
@@ -230,6 +238,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
 
     gsr_v2f C01 = {0.0f, 0.0f};   // {C0, C1} as a register pair
     float C2 = 0.0f, T = 1.0f;    // blue, transmittance 1 - A
+    float Z = 0.0f;               // (AOV) the alpha-weighted sum of window depths
     bool wave_done = false;
     if (a.slab == 2) {
         // front-slab phase 2: finished tiles keep what they have; the others go on from the stored colour and transmittance
@@ -242,6 +251,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
             const size_t at = (size_t)(lty * GSR_TILE_PX + (wave >> 1) * 8 + (lane >> 3)) * a.width + (size_t)(tx * GSR_TILE_PX + (wave & 1) * 8 + (lane & 7));
             const float4 c = out[at];
             C01 = (gsr_v2f){c.x, c.y}; C2 = c.z; T = a.tbuf[at];
+            if constexpr (AOV) Z = aov[at].x;   // (phase 1 left its sum in the plane)
         }
         wave_done = __all(!pix_ok || T < GSR_T_MIN);
     }
@@ -388,7 +398,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                     const float4* p = reinterpret_cast<const float4*>(recs + ridx);
                     const float4 r0 = p[0];
                     r1 = p[1]; r2 = p[2];
-                    rz = (HAS_DEPTH && !d_triv) ? zwin[ridx] : 0.0f;
+                    rz = (AOV || (HAS_DEPTH && !d_triv)) ? zwin[ridx] : 0.0f;
                     // Can the splat touch this quadrant?  Separating-axis test of the oriented quad (shrunk to the radius
                     // where alpha can still reach 1/255) against the quadrant's box of pixel centres: the box axes (= bbox
                     // test) and the quad's own two axes.  Conservative.
@@ -434,7 +444,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                     blk[0 + h] = r1.x; blk[2 + h] = r1.y; blk[4 + h] = r1.z; blk[6 + h] = r1.w;
                     blk[8 + h] = c0; blk[10 + h] = c1;
                     reinterpret_cast<float4*>(blk)[3 + h] = r2;
-                    if (HAS_DEPTH) reinterpret_cast<float*>(&szl[wave][pos >> 1])[h] = rz;
+                    if (ZSTAGE) reinterpret_cast<float*>(&szl[wave][pos >> 1])[h] = rz;
                 }
                 if ((cnt & 1) && lane == 0) {   // odd list: pad with a record that cannot contribute (la = -inf: discarded everywhere)
                     float* blk = reinterpret_cast<float*>(&slist[wave][(cnt >> 1) * PF4]);
@@ -448,7 +458,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                         lds_vfloat* vb = (lds_vfloat*)blk;
                         vb[16] = 0.0f; vb[17] = 0.0f; vb[18] = 0.0f; vb[19] = -__builtin_inff();
                     }
-                    if (HAS_DEPTH) reinterpret_cast<float*>(&szl[wave][cnt >> 1])[1] = 0.0f;
+                    if (ZSTAGE) reinterpret_cast<float*>(&szl[wave][cnt >> 1])[1] = 0.0f;
                 }
                 // the list is written and read by this wave only: LDS operations of one wave execute in order
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -463,10 +473,10 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                 auto load_pair = [&](auto with_depth, int p) __attribute__((always_inline)) {
                     PairOps o;
                     o.v0 = L[p * PF4 + 0]; o.v1 = L[p * PF4 + 1]; o.v2 = L[p * PF4 + 2]; o.v3 = L[p * PF4 + 3]; o.v4 = L[p * PF4 + 4];
-                    if constexpr (decltype(with_depth)::value) o.z = szl[wave][p]; else o.z = make_float2(0.0f, 0.0f);
+                    if constexpr (decltype(with_depth)::value || AOV) o.z = szl[wave][p]; else o.z = make_float2(0.0f, 0.0f);
                     return o;
                 };
-                auto blend_ops = [&](auto with_depth, const PairOps& o, gsr_v2f& C01, float& C2, float& T) __attribute__((always_inline)) {
+                auto blend_ops = [&](auto with_depth, const PairOps& o, gsr_v2f& C01, float& C2, float& T, float& Z) __attribute__((always_inline)) {
                     const float4 v0 = o.v0, v1 = o.v1, v2 = o.v2, v3 = o.v3, v4 = o.v4;
                     // kappa * (quad-local coordinate) of this pixel for the two records
                     const gsr_v2f q0 = gsr_fma2(lx, (gsr_v2f){v0.x, v0.y}, gsr_fma2(ly, (gsr_v2f){v0.z, v0.w}, (gsr_v2f){v2.x, v2.y}));
@@ -502,16 +512,18 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                     const float wa = T * ((ina && T >= GSR_T_MIN) ? ala : 0.0f);
                     C01 = gsr_fma2((gsr_v2f)(wa), (gsr_v2f){v3.x, v3.y}, C01);
                     C2 = gsr_fma(wa, v3.z, C2);
+                    if constexpr (AOV) Z = gsr_fma(wa, o.z.x, Z);
                     T = T - wa;
                     const float wb = T * ((inb && T >= GSR_T_MIN) ? alb : 0.0f);
                     C01 = gsr_fma2((gsr_v2f)(wb), (gsr_v2f){v4.x, v4.y}, C01);
                     C2 = gsr_fma(wb, v4.z, C2);
+                    if constexpr (AOV) Z = gsr_fma(wb, o.z.y, Z);
                     T = T - wb;
                 };
                 typedef std::integral_constant<bool, false> no_depth_t;
                 typedef std::integral_constant<bool, true> depth_t;
-                auto blend_pair = [&](int p, gsr_v2f& C01, float& C2, float& T) __attribute__((always_inline)) { blend_ops(no_depth_t(), load_pair(no_depth_t(), p), C01, C2, T); };
-                auto blend_pair_d = [&](int p, gsr_v2f& C01, float& C2, float& T) __attribute__((always_inline)) { blend_ops(depth_t(), load_pair(depth_t(), p), C01, C2, T); };
+                auto blend_pair = [&](int p, gsr_v2f& C01, float& C2, float& T) __attribute__((always_inline)) { blend_ops(no_depth_t(), load_pair(no_depth_t(), p), C01, C2, T, Z); };
+                auto blend_pair_d = [&](int p, gsr_v2f& C01, float& C2, float& T) __attribute__((always_inline)) { blend_ops(depth_t(), load_pair(depth_t(), p), C01, C2, T, Z); };
 #ifdef BL_EXP_DOUBLE   // experiment: the inner loop a second time on shadow accumulators (its marginal cost = the time difference)
                 {
                     gsr_v2f sC01 = C01; float sC2 = C2, sT = T;
@@ -525,11 +537,13 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
                 // pair the compiler left four branches and twenty scalar instructions in every iteration), then the remainder
                 int p = 0;
                 if (!HAS_DEPTH || !dslow) {   // (no staged record needs the depth compare: the plain loop -- a weight-0 blend and a skipped one leave C, T bit-identical)
-                    const int nfull = npairs & ~(BL_CHECK - 1);
+                    // (the depth-tested AOV kernel: two pairs per trip -- with four, the four extra depth pairs in flight spill three registers)
+                    constexpr int CHK = (AOV && HAS_DEPTH) ? BL_CHECK_AOVD : BL_CHECK;
+                    const int nfull = npairs & ~(CHK - 1);
                     bool stop = false;
-                    for (; p < nfull && !stop; p += BL_CHECK) {
+                    for (; p < nfull && !stop; p += CHK) {
 #pragma unroll
-                        for (int u = 0; u < BL_CHECK; ++u) blend_pair(p + u, C01, C2, T);
+                        for (int u = 0; u < CHK; ++u) blend_pair(p + u, C01, C2, T);
                         stop = __all(!pix_ok || T < GSR_T_MIN);
                     }
                     if (!stop)
@@ -600,6 +614,7 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
         if (a.out_format == GSR_FMT_RGBA32F || a.slab == 1) out[at] = make_float4(C01.x, C01.y, C2, 1.0f - T);
         if (a.out_format != GSR_FMT_RGBA32F) gsr_store_packed(a.out_packed, a.out_format, at, C01.x, C01.y, C2, 1.0f - T);
         if (a.slab == 1) a.tbuf[at] = T;
+        if constexpr (AOV) aov[at] = make_float2(Z, 1.0f - T);
     }
     BLP(8)
 #ifdef BL_PROFILE
@@ -657,6 +672,28 @@ k_blend_lazy(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uint2* 
              const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz)
 {
     gsr_blend_tile<HAS_DEPTH, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz);
+}
+
+// The depth AOV's entry points (gsr_render_aov): the same tile walk with AOV = true, and the plane behind the kernel arguments of the
+// colour kernels -- GsrBlendArgs is untouched, so a frame without the AOV launches what it always did.  Same occupancy as the colour
+// kernels (six waves per SIMD); the lazy-colour fallback is left to the register allocator like its colour twin.
+template <bool HAS_DEPTH>
+__global__ void __launch_bounds__(256) BL_OCC
+k_blend_aov(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
+            const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
+            const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
+            const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz, float2* __restrict__ aov)
+{
+    gsr_blend_tile<HAS_DEPTH, false, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz, aov);
+}
+template <bool HAS_DEPTH>
+__global__ void __launch_bounds__(256)
+k_blend_aov_lazy(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
+                 const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
+                 const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
+                 const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz, float2* __restrict__ aov)
+{
+    gsr_blend_tile<HAS_DEPTH, true, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz, aov);
 }
 
 // The end of a frame, two small kernels.

@@ -100,6 +100,7 @@ OPT_FRONT_SLAB = 16
 TARGET_RGBA32F = 0
 TARGET_RGBA16F = 1
 TARGET_RGBA8 = 2
+AOV_DEPTH = 1          # gsr_render_aov: the plane {zsum, cov}, two float32 per pixel whatever the target format
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -127,6 +128,7 @@ C_ABI_SYMBOLS = [
     "gsplat_pack_sh_from_vec3", "gsplat_pack_sh_from_frest", "gsplat_pack_sh_from_array",
     "gsr_target_pixel_bytes", "gsr_set_target_format", "gsr_get_target_format", "gsr_multi_set_target_format", "gsr_convert_pixels",
     "gsplat_renderer_set_target_format", "gsplat_renderer_get_target_format",
+    "gsr_render_aov", "gsr_resolve_depth", "gsr_resolve_depth_device", "gsplat_renderer_set_aov_target",
 ]
 
 
@@ -167,6 +169,10 @@ def load_library() -> C.CDLL:
     L.gsr_stitch_bands.argtypes = [vp, vp, i32, i32, i32, vp]
     L.gsr_render.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_render_depth.argtypes = [vp, C.POINTER(gsr_camera), vp, i32, vp, i32]
+    L.gsr_render_aov.argtypes = [vp, C.POINTER(gsr_camera), vp, i32, vp, i32, i32, vp]
+    L.gsr_resolve_depth.argtypes = [vp, i64, C.c_float, vp]
+    L.gsr_resolve_depth_device.argtypes = [vp, vp, i64, C.c_float, vp]
+    L.gsplat_renderer_set_aov_target.argtypes = [vp, i32, vp]
     L.gsr_render_wire.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_render_wire_over.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_synchronize.argtypes = [vp]
@@ -314,6 +320,17 @@ def convert_pixels(rgba: np.ndarray, fmt: int) -> np.ndarray:
     return out
 
 
+def resolve_depth(aov: np.ndarray, cov_min: float = 0.5) -> np.ndarray:
+    """gsr_resolve_depth: a depth-AOV plane [..., 2] = {zsum, cov} -> float32 window depth [...], on the host:
+    cov >= cov_min ? min(zsum / cov, 1) : 1.  What gsr_render_depth (or GL) accepts as a depth buffer."""
+    a = np.ascontiguousarray(aov, dtype=np.float32)
+    if a.ndim == 0 or a.shape[-1] != 2:
+        raise GsrError(-1, "resolve_depth: the last axis must hold {zsum, cov}")
+    out = np.empty(a.shape[:-1], dtype=np.float32)
+    _check(load_library().gsr_resolve_depth(a.ctypes.data, a.size // 2, float(cov_min), out.ctypes.data))
+    return out
+
+
 def camera_struct(cam) -> gsr_camera:
     s = gsr_camera()
     for name in ("obj_view", "object", "inv_object", "view", "proj"):
@@ -453,6 +470,30 @@ class Engine:
         cs = camera_struct(cam)
         _check(self.L.gsr_render_depth(self.h, C.byref(cs), d.ctypes.data, 0, out.ctypes.data, 0))
         return out
+
+    def render_aov(self, cam, depth: np.ndarray | None = None, aov: int = AOV_DEPTH):
+        """the frame of render / render_depth plus the depth AOV: (rgba [rows, W, 4] in the target format, plane float32 [rows, W, 2] =
+        {zsum, cov}: the alpha-weighted sum of window depths and the coverage 1 - T, row 0 = bottom)"""
+        rows = self.band_rows(cam.height)
+        out = np.empty((rows, cam.width, 4), dtype=target_dtype(self.target_format))
+        plane = np.empty((rows, cam.width, 2), dtype=np.float32)
+        d = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32).reshape(cam.height, cam.width)
+        cs = camera_struct(cam)
+        _check(self.L.gsr_render_aov(self.h, C.byref(cs), _ptr(d), 0, out.ctypes.data, 0, int(aov), plane.ctypes.data))
+        return out, plane
+
+    def render_aov_struct_to_device(self, cam_struct: gsr_camera, device_ptr: int, aov_device_ptr: int, depth_device_ptr: int = 0, aov: int = AOV_DEPTH):
+        """gsr_render_aov with every buffer in device memory (the plane: 8 bytes per pixel, 8-byte aligned)"""
+        _check(self.L.gsr_render_aov(self.h, C.byref(cam_struct), C.c_void_p(depth_device_ptr or None), 1, C.c_void_p(device_ptr), 1, int(aov),
+                                     C.c_void_p(aov_device_ptr or None)))
+
+    def resolve_depth(self, aov: np.ndarray, cov_min: float = 0.5) -> np.ndarray:
+        """the module's resolve_depth (host, no GPU work): plane [..., 2] -> window depth [...]"""
+        return resolve_depth(aov, cov_min)
+
+    def resolve_depth_device(self, aov_device_ptr: int, n_pixels: int, cov_min: float, depth_device_ptr: int):
+        """gsr_resolve_depth_device: the same rule as one kernel on the context's public stream"""
+        _check(self.L.gsr_resolve_depth_device(self.h, C.c_void_p(aov_device_ptr), int(n_pixels), float(cov_min), C.c_void_p(depth_device_ptr)))
 
     def policy_state(self) -> dict:
         """the live state of the host-side policies (csrc/gsr_policy.h)"""
@@ -687,6 +728,11 @@ class GSplatRenderer:
 
     def targetFormat(self) -> int:
         return int(self.L.gsplat_renderer_get_target_format(self.h))
+
+    def setAovTarget(self, aov: int, plane_ptr: int | None) -> int:
+        """from the next render() on every frame also writes the depth AOV {zsum, cov} (height x width x 2 float32) to plane_ptr, which
+        lives where GSplatRenderContext.target lives and must stay alive; aov = 0 or no pointer switches it off.  0 or a GSR_E_* code"""
+        return int(self.L.gsplat_renderer_set_aov_target(self.h, int(aov), C.c_void_p(plane_ptr or None)))
 
     def query(self, what: int, rid: str | None = None) -> int:
         return int(self.L.gsplat_renderer_query(self.h, what, rid.encode() if rid else None))

@@ -94,6 +94,11 @@ public:
      * with the next render(); GSR_OK, or GSR_E_INVALID for an unknown format (the format in use stays).  A dry instance remembers it. */
     int setTargetFormat(int format);
     int targetFormat() const { return target_format_; }
+    /* depth AOV (gsplat_hip.h: gsr_render_aov): from the next render() on, every frame also writes the plane {zsum, cov} -- height*width
+     * pixels of two floats -- into `plane`, which lives where GSplatRenderContext::target lives and is BORROWED until it is replaced.
+     * aov = 0 or plane = NULL switches it off.  GSR_OK, or GSR_E_INVALID for an unknown aov or for a multi-GPU instance (gsr_multi_*
+     * has no AOV verb).  A dry instance remembers it. */
+    int setAovTarget(int aov, float* plane);
 
     /* introspection (no reference counterpart; used by tests and the C wrappers) */
     enum Query {
@@ -161,6 +166,8 @@ private:
     float eye_[3] = {0, 0, 0};
     int sh_order_ = 3;
     int target_format_ = 0;             /* GSR_TARGET_RGBA32F */
+    int aov_ = 0;                       /* GSR_AOV_*: 0 = none */
+    float* aov_plane_ = nullptr;        /* borrowed */
     int64_t stagings_ = 0, frames_ = 0;
     int status_ = 0;
     bool obj_notice_given_ = false;
@@ -197,6 +204,7 @@ void gsplat_renderer_set_rendering_enabled(gsplat_renderer* h, int enabled);
 void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos[3]);
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order);
 int  gsplat_renderer_set_target_format(gsplat_renderer* h, int format);   /* GSplatRenderer::setTargetFormat */
+int  gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane);   /* GSplatRenderer::setAovTarget */
 int  gsplat_renderer_get_target_format(gsplat_renderer* h);               /* the format in use; <0 for a NULL handle */
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id_or_null);
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]);

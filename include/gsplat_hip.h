@@ -290,6 +290,28 @@ int  gsr_render(gsr_context* ctx, const gsr_camera* cam, float* rgba_out, int ou
 int  gsr_render_depth(gsr_context* ctx, const gsr_camera* cam, const float* depth, int depth_is_device,
                       float* rgba_out, int out_is_device);
 
+/* ---- depth AOV ----------------------------------------------------------
+ * gsr_render_depth plus one plane beside the image.  GSR_AOV_DEPTH: per pixel two float32 {zsum, cov}, 8 bytes, ALWAYS float32
+ * whatever the context's target format; rows*width pixels, row 0 = bottom, like the image (a row-sharded context writes its band
+ * plane, gsr_band_rows() rows, padded like the band image).
+ *   zsum = sum of w_i * zwin_i over exactly the fragments the image composites, nearest first, with the same weights w = T*alpha
+ *          (same discard, same per-pixel early-out, same depth test), accumulated as Z = fma(w, zwin, Z);
+ *          zwin = the quad's window depth (ndc.z*0.5+0.5), the value the depth test compares;
+ *   cov  = 1 - T: the bits of the RGBA32F image's alpha.
+ * A pixel nothing covers holds {0, 0}.  The image is bit-identical to gsr_render_depth's.  aov_out lives where rgba_out lives
+ * (out_is_device); a device pointer must be 8-byte aligned.  aov = 0 or aov_out = NULL: gsr_render_depth itself; an unknown aov:
+ * GSR_E_INVALID.
+ * Not covered: gsr_multi_* and gsr_comm_* have no AOV verb (nothing is gathered); gsr_stitch_bands does not know the plane (a band
+ * plane stitches like a band image, by copying each rank's rows of tiles to where they belong); the wire overlay writes none. */
+#define GSR_AOV_DEPTH 1
+int  gsr_render_aov(gsr_context* ctx, const gsr_camera* cam, const float* depth, int depth_is_device,
+                    float* rgba_out, int out_is_device, int aov, float* aov_out);
+/* The plane -> a window-depth buffer gsr_render_depth (or GL) accepts: per pixel
+ *   cov >= cov_min ? min(zsum / cov, 1) : 1      (IEEE division; 1 = the far plane, what a cleared depth buffer holds)
+ * Host form: no context, no GPU.  Device form: one small kernel on the context's public stream, the same function. */
+int  gsr_resolve_depth(const float* aov, int64_t n_pixels, float cov_min, float* depth_out);
+int  gsr_resolve_depth_device(gsr_context* ctx, const float* aov, int64_t n_pixels, float cov_min, float* depth_out);
+
 /* Wireframe overlay (the reference's wire program, shaders/GSplatShaderSource.h:22-110 drawn in
  * src/GR_GSplat.C:477-483): the outline of every splat's +-2 quad in colour Cd, alpha 1, nearest line wins,
  * background 0, in the context's target format (Cd is stored as halves: RGBA16F gets those bits).  Whole image (ignores the row shard), synchronous.  Like the reference's wire program it uses
