@@ -269,6 +269,7 @@ void GSplatRenderer::render(GSplatRenderContext& r, bool isObjectLevel)
     cam.height = r.height;
     cam.sh_order = (sh_order_ > 0 && resident_.sh) ? sh_order_ : 0;   // SH needs an order AND data
     status_ = multi_ ? gsr_multi_render_depth(multi_, &cam, r.depth, r.depth_is_device, r.target, r.target_is_device)
+                     : bg_.kind != 0 ? gsr_render_over(engine_, &cam, r.depth, r.depth_is_device, &bg_, r.target, r.target_is_device)
                      : gsr_render_aov(engine_, &cam, r.depth, r.depth_is_device, r.target, r.target_is_device, aov_, aov_plane_);
     if (status_ != GSR_OK) { note("error", "frame failed: %s", gsr_last_error()); return; }
     ++frames_;
@@ -309,8 +310,19 @@ int GSplatRenderer::setTargetFormat(int format)
 int GSplatRenderer::setAovTarget(int aov, float* plane)
 {
     if ((aov != 0 && aov != GSR_AOV_DEPTH) || (multi_ && aov != 0 && plane)) return GSR_E_INVALID;
+    if (aov != 0 && plane && bg_.kind != 0) return GSR_E_INVALID;   // (no AOV + background verb)
     aov_ = plane ? aov : 0;
     aov_plane_ = aov_ ? plane : nullptr;
+    return GSR_OK;
+}
+
+int GSplatRenderer::setBackground(const gsr_background* bg)
+{
+    if (!bg || bg->kind == 0) { bg_ = gsr_background{}; return GSR_OK; }
+    if (bg->kind != GSR_BG_COLOUR && bg->kind != GSR_BG_IMAGE) return GSR_E_INVALID;
+    if (bg->kind == GSR_BG_IMAGE && (gsr_target_pixel_bytes(bg->format) < 0 || !bg->image)) return GSR_E_INVALID;
+    if (multi_ || aov_ != 0) return GSR_E_INVALID;
+    bg_ = *bg;
     return GSR_OK;
 }
 
@@ -418,6 +430,7 @@ void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order) { if (h) h->impl->setSphericalHarmonicsOrder(order); }
 int gsplat_renderer_set_target_format(gsplat_renderer* h, int format) { return h ? h->impl->setTargetFormat(format) : GSR_E_INVALID; }
 int gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane) { return h ? h->impl->setAovTarget(aov, plane) : GSR_E_INVALID; }
+int gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg) { return h ? h->impl->setBackground(bg) : GSR_E_INVALID; }
 int gsplat_renderer_get_target_format(gsplat_renderer* h) { return h ? h->impl->targetFormat() : GSR_E_INVALID; }
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id) { return h ? h->impl->query(what, id ? std::string(id) : std::string()) : -1; }
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]) { if (h && out) h->impl->origin(out); }

@@ -93,6 +93,7 @@ struct FrameArgs {
     bool out_is_device = false;
     int aov = 0;                       // GSR_AOV_*: the plane rendered beside the image (0: none) ...
     float* aov_out = nullptr;          // ... into the caller's buffer, where the image lives (host or device)
+    gsr_background bg{};               // gsr_render_over: what the frame is composited over (kind 0: nothing); the image is the caller's
 };
 
 // what a queued frame needs again when it is finished (or its back end re-queued)
@@ -131,6 +132,7 @@ struct FrameJob {
     bool dstat = false;            // ... and the depth pyramid pass masked the covered depths with the tiles' status (a culled frame with a valid status)
     bool blend_guess_plain = false;   // the plain blend kernel was launched, guarded by "no pixel is covered" (queue_back_end)
     float2* aov_target = nullptr;  // depth AOV: the device plane the blend kernel writes ({zsum, cov} per band pixel); NULL = a frame without it
+    GsrBgArgs bg{};                // a background (k_blend.h: k_blend_over): kind 0 = a frame without one; the image on the device
 };
 
 // Everything one frame in flight owns: its HIP stream, the per-frame HBM arrays, the small
@@ -226,8 +228,10 @@ struct FrameSlot {
     float* aovb = nullptr;             // staging for a host-pointer AOV plane: two floats per band pixel (aovb_cap counts floats)
     size_t aovb_cap = 0;
     int aovb_sig[5] = {-1, -1, -1, -1, -1};     // the band shape the plane's staging buffer was last cleared for
-    float* fb32 = nullptr;             // packed target formats, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
+    float* fb32 = nullptr;             // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
     size_t fb32_cap = 0;
+    unsigned char* bgb = nullptr;      // device copy of a host background image (bgb_cap bytes): per slot, staged anew by every attempt of a frame
+    size_t bgb_cap = 0;
     // small device/host mailboxes
     unsigned long long* counters = nullptr;  // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
                                              // scanned, [5] wave-record evaluations (running)
@@ -494,7 +498,7 @@ static void slot_destroy(FrameSlot& sl)
     slot_free_splat_arrays(sl);
     dev_free(sl.hist); dev_free(sl.totals);
     dev_free(sl.pvA);
-    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32); dev_free(sl.aovb);
+    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32); dev_free(sl.aovb); dev_free(sl.bgb);
     dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
     if (sl.h_end) (void)hipHostFree(sl.h_end); dev_free(sl.depth_stage); dev_free(sl.dpyr); dev_free(sl.dactive);
     dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
@@ -1449,8 +1453,11 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
         lz.redo = j.lazy ? sl.redo : nullptr;
         lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
         // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
-        a.out_format = j.format; a.out_packed = j.format != GSR_TARGET_RGBA32F ? (void*)j.target : nullptr;
-        float4* tgt = reinterpret_cast<float4*>(j.format != GSR_TARGET_RGBA32F ? sl.fb32 : j.target);
+        // (a frame over a background is laid out like a packed one whatever its format: the composited pixel goes to the target, the raw one
+        //  of a front slab's phase 1 to the slot's own buffer -- phase 2 must never continue from a composited pixel)
+        const bool over = j.bg.kind != 0;
+        a.out_format = j.format; a.out_packed = (j.format != GSR_TARGET_RGBA32F || over) ? (void*)j.target : nullptr;
+        float4* tgt = reinterpret_cast<float4*>((j.format != GSR_TARGET_RGBA32F || over) ? sl.fb32 : j.target);
         // Host-target frames (a caller without GL interop): the frame's LAST blend launch is issued band by band of tile rows, an event
         // behind each, and queue_frame_end copies a band's rows back on a second stream as soon as its event fires: all but the first
         // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
@@ -1472,6 +1479,13 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
                 else
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
                                        sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.aov_target);
+            } else if (over) {   // a background: the same walk, the composite in the epilogue (k_blend.h: k_blend_over)
+                if (with_depth)
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
+                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.bg);
+                else
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
+                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.bg);
             } else if (with_depth)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
                                    sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz);
@@ -1485,6 +1499,13 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
                 else
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
                                        sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.aov_target);
+            } else if (j.lazy && over) {
+                if (with_depth)
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
+                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.bg);
+                else
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
+                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.bg);
             } else if (j.lazy) {   // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
                 if (with_depth)
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
@@ -1536,7 +1557,8 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
     // not for a frame that is handed over before its mailbox is read (nobody could queue the other kernel in time)
     // (... nor over lists whose index words carry depth codes: only the depth-tested kernel masks them off)
     // (... nor for a frame with the depth AOV: a void launch would leave its plane unwritten, and the AOV kernels have no guarded form)
-    sl.job.blend_guess_plain = j.d_depth != nullptr && j.dcull && !c->depth_active && !j.deferred && j.f.idx_mask == 0xffffffffu && !j.aov_target;
+    // (... nor for a frame over a background: the over-kernels have no guarded form either)
+    sl.job.blend_guess_plain = j.d_depth != nullptr && j.dcull && !c->depth_active && !j.deferred && j.f.idx_mask == 0xffffffffu && !j.aov_target && j.bg.kind == 0;
     if ((rc = queue_blend(c, sl, j.d_depth != nullptr && !sl.job.blend_guess_plain, sl.job.blend_guess_plain))) return rc;
     return mark(sl, 6);
 }
@@ -2057,6 +2079,20 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         HIP_TRY(hipMemcpyAsync(sl.depth_stage, a.depth, npx * 4, hipMemcpyHostToDevice, s));
         j.d_depth = sl.depth_stage;
     }
+    // A background: the colour as it is; a device image read in place; a host image staged in the slot's own buffer like a host depth
+    // buffer -- by EVERY attempt of the frame (a repair, a re-queue, a front slab's phase 2 come through here again with the caller's
+    // arguments), so whatever is composited last read the original background
+    if (a.bg.kind != 0) {
+        j.bg.kind = a.bg.kind; j.bg.format = a.bg.format;
+        std::memcpy(j.bg.rgba, a.bg.rgba, sizeof j.bg.rgba);
+        j.bg.image = a.bg.kind == GSR_BG_IMAGE ? a.bg.image : nullptr;
+        if (a.bg.kind == GSR_BG_IMAGE && !a.bg.image_is_device) {
+            const size_t nbytes = (size_t)cam->width * cam->height * (size_t)gsr_format_pixel_bytes(a.bg.format);
+            if (nbytes > sl.bgb_cap && (rc = regrow(s, sl.bgb, sl.bgb_cap, nbytes, nbytes))) return rc;
+            HIP_TRY(hipMemcpyAsync(sl.bgb, a.bg.image, nbytes, hipMemcpyHostToDevice, s));
+            j.bg.image = sl.bgb;
+        }
+    }
     // Depth-tested frames: the tile-max pyramid of the opaque pass's depth (k_cluster.h), rebuilt every frame (the buffer's content is
     // the caller's), one per slot; the second phase of a front-slab frame uses the first one's.  GSR_OPT_OCCLUSION_CULL = 0 switches
     // it off like every other occlusion test (what is left is k_blend's own per-quadrant classification and per-fragment compare).
@@ -2078,7 +2114,8 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     j.format = c->target_format;
     const size_t bpp = (size_t)gsr_format_pixel_bytes(j.format);
     // (a packed target, front-slab frame: phase 2 continues from phase 1's f32 pixels, kept in a buffer of the slot's own)
-    if (j.format != GSR_TARGET_RGBA32F && j.phase == 1 && j.out_px * 4 > sl.fb32_cap && (rc = regrow(s, sl.fb32, sl.fb32_cap, j.out_px * 4, j.out_px * 4))) return rc;
+    // (... and so does a frame over a background in any format: the target holds composited pixels)
+    if ((j.format != GSR_TARGET_RGBA32F || a.bg.kind != 0) && j.phase == 1 && j.out_px * 4 > sl.fb32_cap && (rc = regrow(s, sl.fb32, sl.fb32_cap, j.out_px * 4, j.out_px * 4))) return rc;
     if (!a.out_is_device) {
         const size_t fb_floats = j.out_px * bpp / 4;
         if (fb_floats > sl.fb_cap) {
@@ -2390,6 +2427,8 @@ static int frame_check(gsr_context* c, FrameSlot& first, const FrameArgs& a)
 
 static bool target_aligned(const gsr_context* c, const void* p) { return (uintptr_t)p % (uintptr_t)gsr_format_pixel_bytes(c->target_format) == 0; }
 
+static int render_frame(gsr_context* c, const FrameArgs& a);
+
 extern "C" int gsr_render(gsr_context* c, const gsr_camera* cam, float* rgba_out, int out_is_device)
 {
     return gsr_render_depth(c, cam, nullptr, 0, rgba_out, out_is_device);
@@ -2410,7 +2449,12 @@ extern "C" int gsr_render_aov(gsr_context* c, const gsr_camera* cam, const float
     if (aov != 0 && aov != GSR_AOV_DEPTH) return set_err(GSR_E_INVALID, "gsr_render_aov: unknown AOV %d", aov);
     if (aov_out == nullptr) aov = 0;
     if (aov && out_is_device && (uintptr_t)aov_out % 8u != 0) return set_err(GSR_E_INVALID, "gsr_render_aov: the device plane is not aligned to its 8-byte pixel");
-    const FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0, aov, aov ? aov_out : nullptr};
+    return render_frame(c, FrameArgs{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0, aov, aov ? aov_out : nullptr});
+}
+
+// one frame from begin to hand-over (gsr_render_aov, gsr_render_over)
+static int render_frame(gsr_context* c, const FrameArgs& a)
+{
     FrameSlot* sl = nullptr;
 #ifdef GSR_HOST_PHASES
     static double acc[4] = {0, 0, 0, 0}, t_last_exit = 0; static long cnt = 0;
@@ -2435,6 +2479,67 @@ extern "C" int gsr_render_aov(gsr_context* c, const gsr_camera* cam, const float
     if (++cnt % 50 == 0) { fprintf(stderr, "[host phases] begin %.1f  finish(pair wait + frame end) %.1f  check(verdict wait) %.1f  outside gsr_render %.1f us\n", acc[0] / 50, acc[1] / 50, acc[2] / 50, acc[3] / 50); acc[0] = acc[1] = acc[2] = acc[3] = 0; }
 #endif
     return rc;
+}
+
+// ---- background (gsr_device.h: gsr_composite_over_pixel) ----
+static const char* background_error(const gsr_background* bg)
+{
+    if (bg->kind != GSR_BG_COLOUR && bg->kind != GSR_BG_IMAGE) return "unknown background kind";
+    if (bg->kind == GSR_BG_IMAGE) {
+        if (!gsr_format_pixel_bytes(bg->format)) return "unknown image format";
+        if (!bg->image) return "the image is NULL";
+    }
+    return nullptr;
+}
+
+// gsr_render_depth over a background (bg = NULL or kind 0: gsr_render_depth itself, the same launches)
+extern "C" int gsr_render_over(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device,
+                               const gsr_background* bg, float* rgba_out, int out_is_device)
+{
+    if (!bg || bg->kind == 0) return gsr_render_depth(c, cam, depth, depth_is_device, rgba_out, out_is_device);
+    if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render_over: NULL argument");
+    if (out_is_device && !target_aligned(c, rgba_out)) return set_err(GSR_E_INVALID, "gsr_render_over: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
+    if (const char* why = background_error(bg)) return set_err(GSR_E_INVALID, "gsr_render_over: %s", why);
+    if (bg->kind == GSR_BG_IMAGE && bg->image_is_device) {
+        const size_t ibpp = (size_t)gsr_format_pixel_bytes(bg->format);
+        if ((uintptr_t)bg->image % ibpp != 0) return set_err(GSR_E_INVALID, "gsr_render_over: the device image is not aligned to its %d-byte pixel", (int)ibpp);
+        if (out_is_device && cam->width > 0 && cam->height > 0 && cam->width <= GSR_MAX_DIM && cam->height <= GSR_MAX_DIM) {
+            // (no in-place form: an attempt that is composited again -- a repair, a re-queue -- must read the original background)
+            const int rows = c->shard_count > 1 ? gsr_band_rows(cam->height, c->shard_index, c->shard_count) : cam->height;
+            const uintptr_t i0 = (uintptr_t)bg->image, i1 = i0 + (size_t)cam->width * cam->height * ibpp;
+            const uintptr_t o0 = (uintptr_t)rgba_out, o1 = o0 + (size_t)cam->width * rows * (size_t)gsr_format_pixel_bytes(c->target_format);
+            if (i0 < o1 && o0 < i1) return set_err(GSR_E_INVALID, "gsr_render_over: the device image overlaps the device target (there is no in-place form)");
+        }
+    }
+    FrameArgs a{*cam, depth, depth_is_device != 0, rgba_out, out_is_device != 0, 0, nullptr};
+    a.bg = *bg;
+    return render_frame(c, a);
+}
+
+// the rule on the host, through the same functions as the kernel's epilogue: no context, no GPU
+extern "C" int gsr_composite_over(const float* rgba32f, int64_t n_pixels, const gsr_background* bg, int out_format, void* out)
+{
+    if (!gsr_format_pixel_bytes(out_format)) return set_err(GSR_E_INVALID, "gsr_composite_over: unknown output format %d", out_format);
+    if (!bg || n_pixels < 0 || (n_pixels > 0 && (!rgba32f || !out))) return set_err(GSR_E_INVALID, "gsr_composite_over: bad argument");
+    if (const char* why = background_error(bg)) return set_err(GSR_E_INVALID, "gsr_composite_over: %s", why);
+    if (bg->kind == GSR_BG_IMAGE && bg->image_is_device) return set_err(GSR_E_INVALID, "gsr_composite_over: the image must be in host memory");
+    for (int64_t i = 0; i < n_pixels; ++i) {
+        const float4 S = make_float4(rgba32f[4 * i], rgba32f[4 * i + 1], rgba32f[4 * i + 2], rgba32f[4 * i + 3]);
+        const float4 B = bg->kind == GSR_BG_IMAGE ? gsr_background_pixel(bg->image, bg->format, (size_t)i)
+                                                  : make_float4(bg->rgba[0], bg->rgba[1], bg->rgba[2], bg->rgba[3]);
+        const float4 o = gsr_composite_over_pixel(S, B);
+        if (out_format == GSR_TARGET_RGBA32F) {
+            const float v[4] = {o.x, o.y, o.z, o.w};
+            std::memcpy(static_cast<char*>(out) + 16 * i, v, 16);
+        } else if (out_format == GSR_TARGET_RGBA16F) {
+            const uint2 v = gsr_pack_rgba16f(o.x, o.y, o.z, o.w);
+            std::memcpy(static_cast<char*>(out) + 8 * i, &v, 8);
+        } else {
+            const uint32_t v = gsr_pack_rgba8(o.x, o.y, o.z, o.w);
+            std::memcpy(static_cast<char*>(out) + 4 * i, &v, 4);
+        }
+    }
+    return GSR_OK;
 }
 
 // ---- depth AOV -> window depth (gsr_device.h: gsr_resolve_depth_pixel) ----

@@ -179,6 +179,33 @@ __host__ __device__ __forceinline__ float gsr_resolve_depth_pixel(float zsum, fl
     return cov >= cov_min ? __builtin_fminf(zsum / cov, 1.0f) : 1.0f;
 }
 
+// ---- background (gsplat_hip.h: gsr_render_over) --------------------------------
+// The finished f32 pixel S = (C, 1 - T) over a background pixel B, both premultiplied: the reference's blend function
+// (ONE_MINUS_DST_ALPHA, ONE) applied ONCE, to the finished pixel.  THE rule, in one place: the epilogue of k_blend_over and
+// gsr_composite_over (host) both go through it.  One f32 subtraction and one explicit FMA per channel -- the translation units are
+// compiled with -ffp-contract=off, so neither side fuses or splits anything else.
+#define GSR_BGK_COLOUR 1
+#define GSR_BGK_IMAGE  2
+__host__ __device__ __forceinline__ float4 gsr_composite_over_pixel(float4 s, float4 b)
+{
+    const float k = 1.0f - b.w;
+    return make_float4(__builtin_fmaf(k, s.x, b.x), __builtin_fmaf(k, s.y, b.y), __builtin_fmaf(k, s.z, b.z), __builtin_fmaf(k, s.w, b.w));
+}
+// pixel p of a background image, decoded to f32.  RGBA32F: as is; RGBA16F: binary16 -> f32, exact; RGBA8: (float)byte / 255.0f, an
+// IEEE division (HIP's float `/` is correctly rounded) -- never a multiplication by a reciprocal, and never under -ffast-math, or
+// the two sides stop agreeing in the last bit.
+__host__ __device__ __forceinline__ float4 gsr_background_pixel(const void* __restrict__ image, int format, size_t p)
+{
+    if (format == GSR_FMT_RGBA32F) return reinterpret_cast<const float4*>(image)[p];
+    if (format == GSR_FMT_RGBA16F) {
+        const uint2 v = reinterpret_cast<const uint2*>(image)[p];
+        return make_float4((float)__builtin_bit_cast(_Float16, (uint16_t)(v.x & 0xffffu)), (float)__builtin_bit_cast(_Float16, (uint16_t)(v.x >> 16)),
+                           (float)__builtin_bit_cast(_Float16, (uint16_t)(v.y & 0xffffu)), (float)__builtin_bit_cast(_Float16, (uint16_t)(v.y >> 16)));
+    }
+    const uint32_t v = reinterpret_cast<const uint32_t*>(image)[p];
+    return make_float4((float)(v & 0xffu) / 255.0f, (float)((v >> 8) & 0xffu) / 255.0f, (float)((v >> 16) & 0xffu) / 255.0f, (float)(v >> 24) / 255.0f);
+}
+
 // The contract's 2^x for x in [-2^22, 0]: identical operation sequence to the oracle's gso_exp2f
 // (round to the nearest-even integer with the 1.5*2^23 trick, EXACT remainder r = x - k, degree-5
 // polynomial for 2^r on [-0.5, 0.5], exponent add).  <= 2.8 ulp, exp2(0) == 1, never above 1.

@@ -143,12 +143,24 @@ struct GsrLazyArgs {
 // Z = fma(w, zwin, Z) beside the colour -- the same w, the same fragments, the same order -- and the pixel's {Z, 1 - T} goes to `aov`
 // (float32 whatever the target format; indexed like the band image).  AOV = false compiles all of it out: the colour kernels are
 // instruction for instruction what they were.
-template <bool HAS_DEPTH, bool LAZY, bool AOV = false>
+// OVER = true (a background, k_blend_over below): the finished pixel (C, 1 - T) is composited over a background pixel in the epilogue
+// (gsr_device.h: gsr_composite_over_pixel) and THAT goes to the target.  The frame is laid out like a packed-format frame whatever
+// the target format: the target is a.out_packed, and `out` is the slot's internal f32 buffer, which only front-slab frames use --
+// phase 1 leaves the RAW pixel and T there and phase 2 continues from them, so a composited pixel is never fed back in.  The loop
+// is untouched; OVER = false compiles all of it out.
+struct GsrBgArgs {
+    int32_t kind;              // GSR_BGK_COLOUR / GSR_BGK_IMAGE
+    int32_t format;            // the image's pixel format (GSR_FMT_*), whatever the target's
+    float rgba[4];             // the colour, premultiplied
+    const void* image;         // height * width pixels of the FULL image (a sharded context's band reads its own rows of it)
+};
+template <bool HAS_DEPTH, bool LAZY, bool AOV = false, bool OVER = false>
 __device__ __forceinline__ void
 gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
                const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
                const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
-               const float* __restrict__ zwin, const float* __restrict__ depth, const GsrLazyArgs& lz, float2* __restrict__ aov = nullptr)
+               const float* __restrict__ zwin, const float* __restrict__ depth, const GsrLazyArgs& lz, float2* __restrict__ aov = nullptr,
+               const GsrBgArgs* __restrict__ bg = nullptr)
 {
     constexpr bool ZSTAGE = HAS_DEPTH || AOV;   // the staged records' window depths are kept
     constexpr int PF4 = 5;
@@ -610,10 +622,26 @@ gsr_blend_tile(const GsrBlendArgs& a, const int32_t* __restrict__ tile_map, cons
         const int brow = lty * GSR_TILE_PX + (w2 >> 1) * 8 + (l2 >> 3);
         const int bcol = tx * GSR_TILE_PX + (w2 & 1) * 8 + (l2 & 7);
         const size_t at = (size_t)brow * a.width + bcol;
-        // (a.out_format is wave-uniform: one scalar branch, outside every loop)
-        if (a.out_format == GSR_FMT_RGBA32F || a.slab == 1) out[at] = make_float4(C01.x, C01.y, C2, 1.0f - T);
-        if (a.out_format != GSR_FMT_RGBA32F) gsr_store_packed(a.out_packed, a.out_format, at, C01.x, C01.y, C2, 1.0f - T);
-        if (a.slab == 1) a.tbuf[at] = T;
+        if constexpr (OVER) {
+            // the background pixel: requested here, behind the loop -- nothing of it is live while the tile composites -- and first
+            // thing, so that the raw stores of a front slab go out beside it.  Indexed by the GLOBAL pixel row: the image is the full
+            // frame's also when this launch owns a band of it
+            float4 B = make_float4(bg->rgba[0], bg->rgba[1], bg->rgba[2], bg->rgba[3]);
+            if (bg->kind == GSR_BGK_IMAGE) {   // (uniform)
+                const int grow = gsr_shard_global_row(a.shard, lty) * GSR_TILE_PX + (w2 >> 1) * 8 + (l2 >> 3);
+                B = gsr_background_pixel(bg->image, bg->format, (size_t)grow * a.width + bcol);
+            }
+            const float4 S = make_float4(C01.x, C01.y, C2, 1.0f - T);
+            if (a.slab == 1) { out[at] = S; a.tbuf[at] = T; }   // (RAW: what phase 2 continues from)
+            const float4 o = gsr_composite_over_pixel(S, B);
+            if (a.out_format == GSR_FMT_RGBA32F) reinterpret_cast<float4*>(a.out_packed)[at] = o;
+            else gsr_store_packed(a.out_packed, a.out_format, at, o.x, o.y, o.z, o.w);
+        } else {
+            // (a.out_format is wave-uniform: one scalar branch, outside every loop)
+            if (a.out_format == GSR_FMT_RGBA32F || a.slab == 1) out[at] = make_float4(C01.x, C01.y, C2, 1.0f - T);
+            if (a.out_format != GSR_FMT_RGBA32F) gsr_store_packed(a.out_packed, a.out_format, at, C01.x, C01.y, C2, 1.0f - T);
+            if (a.slab == 1) a.tbuf[at] = T;
+        }
         if constexpr (AOV) aov[at] = make_float2(Z, 1.0f - T);
     }
     BLP(8)
@@ -694,6 +722,28 @@ k_blend_aov_lazy(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uin
                  const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz, float2* __restrict__ aov)
 {
     gsr_blend_tile<HAS_DEPTH, true, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz, aov);
+}
+
+// A background's entry points (gsr_render_over): the same tile walk with OVER = true, the background's operands behind the kernel
+// arguments of the colour kernels, as the AOV plane is -- GsrBlendArgs is untouched.  No guarded form (queue_back_end does not guess
+// for an over-frame) and no AOV beside it.
+template <bool HAS_DEPTH>
+__global__ void __launch_bounds__(256) BL_OCC
+k_blend_over(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
+             const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
+             const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
+             const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz, GsrBgArgs bg)
+{
+    gsr_blend_tile<HAS_DEPTH, false, false, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz, nullptr, &bg);
+}
+template <bool HAS_DEPTH>
+__global__ void __launch_bounds__(256)
+k_blend_over_lazy(GsrBlendArgs a, const int32_t* __restrict__ tile_map, const uint2* __restrict__ svals,
+                  const int32_t* __restrict__ sstart, const int32_t* __restrict__ send,
+                  const GsrRecord* __restrict__ recs, float4* __restrict__ out, uint4* __restrict__ tile_work,
+                  const float* __restrict__ zwin, const float* __restrict__ depth, GsrLazyArgs lz, GsrBgArgs bg)
+{
+    gsr_blend_tile<HAS_DEPTH, true, false, true>(a, tile_map, svals, sstart, send, recs, out, tile_work, zwin, depth, lz, nullptr, &bg);
 }
 
 // The end of a frame, two small kernels.

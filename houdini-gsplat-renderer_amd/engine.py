@@ -77,6 +77,12 @@ class gsr_raw_attrs(C.Structure):
                 ("sh_scheme", C.c_int32), ("sh_vec3_per_point", C.c_int32), ("sh_array", C.c_void_p), ("sh_ptr", C.POINTER(C.c_void_p))]
 
 
+class gsr_background(C.Structure):
+    """include/gsplat_hip.h: what gsr_render_over composites the frame over (premultiplied; kind 0 = nothing)"""
+    _fields_ = [("kind", C.c_int32), ("format", C.c_int32), ("rgba", C.c_float * 4), ("image", C.c_void_p),
+                ("image_is_device", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -101,6 +107,8 @@ TARGET_RGBA32F = 0
 TARGET_RGBA16F = 1
 TARGET_RGBA8 = 2
 AOV_DEPTH = 1          # gsr_render_aov: the plane {zsum, cov}, two float32 per pixel whatever the target format
+BG_COLOUR = 1          # gsr_background.kind
+BG_IMAGE = 2
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -129,6 +137,7 @@ C_ABI_SYMBOLS = [
     "gsr_target_pixel_bytes", "gsr_set_target_format", "gsr_get_target_format", "gsr_multi_set_target_format", "gsr_convert_pixels",
     "gsplat_renderer_set_target_format", "gsplat_renderer_get_target_format",
     "gsr_render_aov", "gsr_resolve_depth", "gsr_resolve_depth_device", "gsplat_renderer_set_aov_target",
+    "gsr_render_over", "gsr_composite_over", "gsplat_renderer_set_background",
 ]
 
 
@@ -173,6 +182,9 @@ def load_library() -> C.CDLL:
     L.gsr_resolve_depth.argtypes = [vp, i64, C.c_float, vp]
     L.gsr_resolve_depth_device.argtypes = [vp, vp, i64, C.c_float, vp]
     L.gsplat_renderer_set_aov_target.argtypes = [vp, i32, vp]
+    L.gsr_render_over.argtypes = [vp, C.POINTER(gsr_camera), vp, i32, C.POINTER(gsr_background), vp, i32]
+    L.gsr_composite_over.argtypes = [vp, i64, C.POINTER(gsr_background), i32, vp]
+    L.gsplat_renderer_set_background.argtypes = [vp, C.POINTER(gsr_background)]
     L.gsr_render_wire.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_render_wire_over.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_synchronize.argtypes = [vp]
@@ -317,6 +329,44 @@ def convert_pixels(rgba: np.ndarray, fmt: int) -> np.ndarray:
         raise GsrError(-1, "convert_pixels: the last axis must hold the four channels")
     out = np.empty(a.shape, dtype=target_dtype(fmt))
     _check(load_library().gsr_convert_pixels(a.ctypes.data, a.size // 4, int(fmt), out.ctypes.data))
+    return out
+
+
+def background_struct(bg, shape=None):
+    """a background as gsr_background: None (kind 0), a premultiplied colour (r, g, b, a), or an ndarray [..., 4] of float32 / float16 /
+    uint8 -- the image format is inferred from the dtype -- which must hold shape[0] x shape[1] pixels if `shape` is given.  Returns
+    (struct, the array the struct points into: keep it alive as long as the struct is used)"""
+    b = gsr_background()
+    if bg is None:
+        return b, None
+    if isinstance(bg, np.ndarray) and bg.ndim >= 2:
+        fmt = {np.dtype(np.float32): TARGET_RGBA32F, np.dtype(np.float16): TARGET_RGBA16F, np.dtype(np.uint8): TARGET_RGBA8}.get(bg.dtype)
+        if fmt is None or bg.shape[-1] != 4:
+            raise GsrError(-1, "a background image is float32, float16 or uint8 [..., 4]")
+        img = np.ascontiguousarray(bg)
+        if shape is not None and img.size != int(shape[0]) * int(shape[1]) * 4:
+            raise GsrError(-1, f"the background image must hold {shape[0]} x {shape[1]} pixels")
+        b.kind, b.format, b.image, b.image_is_device = BG_IMAGE, fmt, img.ctypes.data, 0
+        return b, img
+    col = [float(x) for x in np.asarray(bg, dtype=np.float32).reshape(-1)]
+    if len(col) != 4:
+        raise GsrError(-1, "a background colour is (r, g, b, a), premultiplied")
+    b.kind = BG_COLOUR
+    b.rgba[:] = col
+    return b, None
+
+
+def composite_over(rgba32f: np.ndarray, bg, fmt: int = TARGET_RGBA32F) -> np.ndarray:
+    """gsr_composite_over: float32 [..., 4] pixels over `bg` (a colour, or an image of as many pixels: background_struct) -> the same
+    shape in the channel type of `fmt`, on the host, by the rule k_blend_over composites and stores with"""
+    a = np.ascontiguousarray(rgba32f, dtype=np.float32)
+    if a.ndim == 0 or a.shape[-1] != 4:
+        raise GsrError(-1, "composite_over: the last axis must hold the four channels")
+    b, keep = background_struct(bg)
+    if keep is not None and keep.size != a.size:
+        raise GsrError(-1, "composite_over: the background image must hold as many pixels as the frame")
+    out = np.empty(a.shape, dtype=target_dtype(fmt))
+    _check(load_library().gsr_composite_over(a.ctypes.data, a.size // 4, C.byref(b), int(fmt), out.ctypes.data))
     return out
 
 
@@ -486,6 +536,24 @@ class Engine:
         """gsr_render_aov with every buffer in device memory (the plane: 8 bytes per pixel, 8-byte aligned)"""
         _check(self.L.gsr_render_aov(self.h, C.byref(cam_struct), C.c_void_p(depth_device_ptr or None), 1, C.c_void_p(device_ptr), 1, int(aov),
                                      C.c_void_p(aov_device_ptr or None)))
+
+    def render_over(self, cam, bg, depth: np.ndarray | None = None) -> np.ndarray:
+        """the frame of render / render_depth composited over `bg` inside the blend kernel: a premultiplied colour (r, g, b, a), or an
+        ndarray [H, W, 4] of float32 / float16 / uint8 (the FULL image also when row-sharded; the format is inferred from the dtype,
+        independent of the target format); None = the plain frame.  [rows, W, 4] in the target format, row 0 = bottom"""
+        rows = self.band_rows(cam.height)
+        out = np.empty((rows, cam.width, 4), dtype=target_dtype(self.target_format))
+        d = None if depth is None else np.ascontiguousarray(depth, dtype=np.float32).reshape(cam.height, cam.width)
+        b, keep = background_struct(bg, (cam.height, cam.width))
+        cs = camera_struct(cam)
+        _check(self.L.gsr_render_over(self.h, C.byref(cs), _ptr(d), 0, C.byref(b), out.ctypes.data, 0))
+        return out
+
+    def render_over_struct_to_device(self, cam_struct: gsr_camera, bg: gsr_background | None, device_ptr: int, depth_device_ptr: int = 0):
+        """gsr_render_over into a device target with a device depth buffer; bg: a gsr_background whose image may live on either side
+        (image_is_device) -- a device image must stay valid until the frame completes on the public stream"""
+        _check(self.L.gsr_render_over(self.h, C.byref(cam_struct), C.c_void_p(depth_device_ptr or None), 1,
+                                      C.byref(bg) if bg is not None else None, C.c_void_p(device_ptr), 1))
 
     def resolve_depth(self, aov: np.ndarray, cov_min: float = 0.5) -> np.ndarray:
         """the module's resolve_depth (host, no GPU work): plane [..., 2] -> window depth [...]"""
@@ -733,6 +801,11 @@ class GSplatRenderer:
         """from the next render() on every frame also writes the depth AOV {zsum, cov} (height x width x 2 float32) to plane_ptr, which
         lives where GSplatRenderContext.target lives and must stay alive; aov = 0 or no pointer switches it off.  0 or a GSR_E_* code"""
         return int(self.L.gsplat_renderer_set_aov_target(self.h, int(aov), C.c_void_p(plane_ptr or None)))
+
+    def setBackground(self, bg: gsr_background | None) -> int:
+        """from the next render() on every frame is composited over *bg (copied; an image it names is borrowed and must stay alive);
+        None or kind 0 clears it.  0 or a GSR_E_* code"""
+        return int(self.L.gsplat_renderer_set_background(self.h, C.byref(bg) if bg is not None else None))
 
     def query(self, what: int, rid: str | None = None) -> int:
         return int(self.L.gsplat_renderer_query(self.h, what, rid.encode() if rid else None))

@@ -99,6 +99,11 @@ public:
      * aov = 0 or plane = NULL switches it off.  GSR_OK, or GSR_E_INVALID for an unknown aov or for a multi-GPU instance (gsr_multi_*
      * has no AOV verb).  A dry instance remembers it. */
     int setAovTarget(int aov, float* plane);
+    /* background (gsplat_hip.h: gsr_render_over): from the next render() on every frame is composited over *bg -- copied here; an
+     * image it names is BORROWED -- until it is cleared with NULL or kind 0.  GSR_OK, or GSR_E_INVALID for an unknown kind or image
+     * format, a NULL image, a multi-GPU instance (gsr_multi_* takes no background), or while an AOV target is set (there is no AOV +
+     * background verb; setAovTarget refuses likewise while a background is set).  A dry instance remembers it. */
+    int setBackground(const gsr_background* bg);
 
     /* introspection (no reference counterpart; used by tests and the C wrappers) */
     enum Query {
@@ -168,6 +173,7 @@ private:
     int target_format_ = 0;             /* GSR_TARGET_RGBA32F */
     int aov_ = 0;                       /* GSR_AOV_*: 0 = none */
     float* aov_plane_ = nullptr;        /* borrowed */
+    gsr_background bg_ = {};            /* kind 0 = none; the image is borrowed */
     int64_t stagings_ = 0, frames_ = 0;
     int status_ = 0;
     bool obj_notice_given_ = false;
@@ -205,6 +211,7 @@ void gsplat_renderer_set_explicit_camera_pos(gsplat_renderer* h, const float pos
 void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order);
 int  gsplat_renderer_set_target_format(gsplat_renderer* h, int format);   /* GSplatRenderer::setTargetFormat */
 int  gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane);   /* GSplatRenderer::setAovTarget */
+int  gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg);   /* GSplatRenderer::setBackground */
 int  gsplat_renderer_get_target_format(gsplat_renderer* h);               /* the format in use; <0 for a NULL handle */
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id_or_null);
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]);

@@ -312,6 +312,43 @@ int  gsr_render_aov(gsr_context* ctx, const gsr_camera* cam, const float* depth,
 int  gsr_resolve_depth(const float* aov, int64_t n_pixels, float cov_min, float* depth_out);
 int  gsr_resolve_depth_device(gsr_context* ctx, const float* aov, int64_t n_pixels, float cov_min, float* depth_out);
 
+/* ---- background ----------------------------------------------------------
+ * gsr_render_depth composited over a premultiplied background -- a colour, or an image of the frame's size -- inside the blend
+ * kernel: the target holds the rounded FINAL picture (one rounding in a packed format, no full-frame pass behind the frame).
+ * With S = the f32 pixel of gsr_render_depth (S_a = 1 - T) and B = the background pixel decoded to f32:
+ *   k = 1.0f - B_a;   out_c = fmaf(k, S_c, B_c)   for c = r, g, b, a;   then the target format's store rule.
+ * That is the reference's blend function (ONE_MINUS_DST_ALPHA, ONE; src/GSplatRenderer.C:613-621) applied once to the finished
+ * pixel; the reference applies it per fragment into a target that is not empty -- algebraically the same, rounded differently.
+ * A pixel no splat covers, and a pixel under B_a == 1, get B exactly.  The background is the caller's data and is not sanitised
+ * (the 8-bit store maps NaN to 0).  Image pixels decode as: RGBA32F as is; RGBA16F binary16 -> f32 (exact); RGBA8 (float)byte / 255.0f
+ * (an IEEE division).  The image's format is independent of the context's target format.
+ * The image lives on either side whatever the target: a host image is copied when the call is made; a DEVICE image is read in
+ * place, must be aligned to its pixel size and must stay valid and unchanged until the frame completes on the public stream.
+ * There is NO in-place form (a device image whose bytes overlap a device rgba_out: GSR_E_INVALID): a frame can be composited more
+ * than once before it is final -- a repair after a broken horizon, a re-queue after the pair count outgrew the lists, a re-sort,
+ * a guard miss -- and every attempt must read the original background.
+ * bg = NULL or kind = 0: gsr_render_depth itself, bit for bit, the same launches.  GSR_E_INVALID: an unknown kind or image format,
+ * a NULL image, a misaligned or overlapping device image.
+ * Not covered: there is no AOV + background verb; gsr_multi_*, gsr_comm_* and the wire overlay take no background.  A row-sharded
+ * context composites its band over its own rows of the FULL image (padding rows as ever: never written in a device target, zero
+ * in a host target), so stitched bands are the unsharded over-frame. */
+#define GSR_BG_COLOUR 1
+#define GSR_BG_IMAGE  2
+typedef struct gsr_background {
+    int32_t kind;             /* 0 = none: the verb is gsr_render_depth itself */
+    int32_t format;           /* GSR_BG_IMAGE: GSR_TARGET_* of the image's pixels (independent of the context's target format) */
+    float   rgba[4];          /* GSR_BG_COLOUR: premultiplied */
+    const void* image;        /* GSR_BG_IMAGE: height*width pixels of the FULL image (also when row-sharded, like `depth`), row 0 = bottom */
+    int32_t image_is_device;
+    int32_t reserved_;
+} gsr_background;
+int  gsr_render_over(gsr_context* ctx, const gsr_camera* cam, const float* depth, int depth_is_device,
+                     const gsr_background* bg, float* rgba_out, int out_is_device);
+/* The rule on the host (no context, no GPU), through the very functions the kernel composites and stores with: n_pixels RGBA-f32
+ * pixels over bg (a HOST image of n_pixels pixels, or a colour) -> out_format.  What the tests hold the GPU path to. */
+int  gsr_composite_over(const float* rgba32f, int64_t n_pixels, const gsr_background* bg,
+                        int out_format, void* out);
+
 /* Wireframe overlay (the reference's wire program, shaders/GSplatShaderSource.h:22-110 drawn in
  * src/GR_GSplat.C:477-483): the outline of every splat's +-2 quad in colour Cd, alpha 1, nearest line wins,
  * background 0, in the context's target format (Cd is stored as halves: RGBA16F gets those bits).  Whole image (ignores the row shard), synchronous.  Like the reference's wire program it uses
