@@ -555,6 +555,11 @@ class Engine:
         _check(self.L.gsr_render_over(self.h, C.byref(cam_struct), C.c_void_p(depth_device_ptr or None), 1,
                                       C.byref(bg) if bg is not None else None, C.c_void_p(device_ptr), 1))
 
+    def render_over_struct_to_host(self, cam_struct: gsr_camera, bg: gsr_background | None, host_ptr: int):
+        """gsr_render_over into a HOST buffer of the band's pixels in the target format; bg as for render_over_struct_to_device (a
+        device image under a host target is the one route render_over cannot take)"""
+        _check(self.L.gsr_render_over(self.h, C.byref(cam_struct), None, 0, C.byref(bg) if bg is not None else None, C.c_void_p(host_ptr), 0))
+
     def resolve_depth(self, aov: np.ndarray, cov_min: float = 0.5) -> np.ndarray:
         """the module's resolve_depth (host, no GPU work): plane [..., 2] -> window depth [...]"""
         return resolve_depth(aov, cov_min)

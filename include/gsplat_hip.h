@@ -135,6 +135,9 @@ int  gsr_set_stream(gsr_context* ctx, void* hip_stream);
  *   RGBA8     4 bytes  c = x clamped to [0, 1] (NaN -> 0); byte = (uint8_t)fmaf(c, 255, 0.5): one rounding, then truncation.
  *                      Linear, premultiplied; no sRGB curve -- that belongs to whoever owns the display transform.
  * A packed target holds the rounded FINAL pixel (the reference's GL blend into such a target rounds after every fragment).
+ * NaN: a channel that is NaN in an RGBA32F or RGBA16F target is NaN in gsr_convert_pixels' result and vice versa, with sign and payload
+ * unspecified (x86 and gfx950 quiet and propagate NaNs differently); every other channel, infinities and signed zeros included, is
+ * bit-exact between the two, and RGBA8 is bit-exact throughout (NaN -> 0).
  * The float* rgba_out parameters below keep their C type and mean "rows*width pixels of the context's target format"; a DEVICE
  * target must be aligned to the pixel size (GSR_E_INVALID otherwise).  This is not a GSR_OPT_* knob: those never change pixels. */
 #define GSR_TARGET_RGBA32F    0
@@ -322,6 +325,8 @@ int  gsr_resolve_depth_device(gsr_context* ctx, const float* aov, int64_t n_pixe
  * A pixel no splat covers, and a pixel under B_a == 1, get B exactly.  The background is the caller's data and is not sanitised
  * (the 8-bit store maps NaN to 0).  Image pixels decode as: RGBA32F as is; RGBA16F binary16 -> f32 (exact); RGBA8 (float)byte / 255.0f
  * (an IEEE division).  The image's format is independent of the context's target format.
+ * NaN: where the rule yields NaN (a NaN operand, 0 * inf under an infinite B_a, inf - inf) the target's channel is NaN exactly where
+ * gsr_composite_over's is, with sign and payload unspecified; every other channel is bit-exact, and RGBA8 is bit-exact throughout.
  * The image lives on either side whatever the target: a host image is copied when the call is made; a DEVICE image is read in
  * place, must be aligned to its pixel size and must stay valid and unchanged until the frame completes on the public stream.
  * There is NO in-place form (a device image whose bytes overlap a device rgba_out: GSR_E_INVALID): a frame can be composited more

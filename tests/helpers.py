@@ -242,3 +242,63 @@ def stop_scene(pkg, cam, n=500, seed=0):
     P = unproject(cam, X, Y, D)
     return make_splats(pkg, P, world_sigma(cam, rng.uniform(0.4, 0.8, n) * max(cam.width, cam.height), D),
                        rng.uniform(0.02, 0.04, n), rng.uniform(0.0, 1.0, (n, 3)))
+
+
+# The NaN rule (include/gsplat_hip.h, "target format" and "background"): in an RGBA32F or RGBA16F target a channel that is NaN on
+# one side is NaN on the other, with sign and payload unspecified -- x86 and gfx950 quiet and propagate NaNs differently; every other
+# channel, infinities and signed zeros included, is bit-exact.  RGBA8 holds no NaN (the store maps it to 0): bit-exact throughout.
+# quiet and signalling NaNs of both signs with several payloads: what the edge tests feed wherever a NaN may arrive
+NAN_PATTERNS = np.array([0x7fc00000, 0xffc00000, 0x7f800001, 0xff800001, 0x7fffffff, 0xffffffff, 0x7fc12345, 0xff923456], np.uint32).view(np.float32)
+
+
+def _as_bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 2: np.uint16, 1: np.uint8}[a.dtype.itemsize])
+
+
+def pixels_differ(got, want):
+    """the boolean array of channels on which two images of one target format differ under the NaN rule"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (got.dtype, want.dtype, got.shape, want.shape)
+    diff = _as_bits(got) != _as_bits(want)
+    if got.dtype.kind == "f":
+        gn, wn = np.isnan(got), np.isnan(want)
+        diff = np.where(gn | wn, gn != wn, diff)
+    return diff
+
+
+def assert_same_pixels(got, want, label=""):
+    """got == want under the NaN rule; the message names the first channel that differs"""
+    diff = pixels_differ(got, want)
+    if diff.any():
+        at = tuple(int(v) for v in np.argwhere(diff)[0])
+        raise AssertionError(f"{label}: {int(diff.sum())} of {diff.size} channels differ; first at {at}: got {got[at]!r} "
+                             f"(bits {int(_as_bits(got)[at]):#x}), want {want[at]!r} (bits {int(_as_bits(want)[at]):#x})")
+
+
+def store_edge_classes(x):
+    """how many float32 values of x sit in each class the packed stores can get wrong:
+    ties            exactly halfway between two neighbouring binary16 values (round to nearest EVEN decides), below the overflow threshold
+    half_denormals  non-zero, below 2^-14 in magnitude: binary16 has no normal number for them (denormal, or rounds to zero)
+    overflow        finite, at least 65520 in magnitude: binary16 infinity
+    in_1_65504      in (1, 65504): beyond the 8-bit store's clamp, inside binary16's range
+    byte_edges      within one float32 step of a threshold (k + 0.5) / 255 between two bytes
+    and nan, inf, negatives (below zero, -inf included), neg_zero"""
+    x = np.ascontiguousarray(x, np.float32).ravel()
+    fin = np.isfinite(x)
+    a = np.abs(x[fin]).astype(np.float64)
+    a = a[a < 65520.0]
+    with np.errstate(over="ignore"):
+        h = a.astype(np.float16)
+    lo = np.nextafter(h, np.float16(-np.inf)).astype(np.float64)
+    hi = np.nextafter(h, np.float16(np.inf)).astype(np.float64)
+    h = h.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ties = (a != h) & ((a == (h + lo) / 2) | (a == (h + hi) / 2))
+    t = ((np.arange(255, dtype=np.float64) + 0.5) / 255.0).astype(np.float32)
+    near = np.concatenate([np.nextafter(t, np.float32(-np.inf)), t, np.nextafter(t, np.float32(np.inf))])
+    return {"ties": int(ties.sum()), "half_denormals": int(((a > 0) & (a < 2.0 ** -14)).sum()),
+            "overflow": int((fin & (np.abs(x) >= np.float32(65520.0))).sum()),
+            "in_1_65504": int(((x > 1) & (x < 65504)).sum()), "byte_edges": int(np.isin(x, near).sum()),
+            "nan": int(np.isnan(x).sum()), "inf": int(np.isinf(x).sum()), "negatives": int((x < 0).sum()),
+            "neg_zero": int(((x == 0) & np.signbit(x)).sum())}

@@ -145,6 +145,85 @@ def test_composite_over_is_the_rule(pkg, fmt, bg):
     assert np.array_equal(store(S, fmt).view(np.uint8), E.convert_pixels(S, fmt).view(np.uint8))
 
 
+def test_fma_restatement_is_nan_exactly_where_ieee_fma_is():
+    """IEEE 754 fma(a, b, c) is NaN iff an operand is NaN, the product is inf * 0, or the product is infinite and c the opposite
+    infinity; an overflowing finite sum is an infinity, not NaN.  Known answers first, then the predicate over every combination of
+    the special values (the round-to-odd step of fma32 must not touch a sum that is not finite)"""
+    inf, nan, big = f32(np.inf), f32(np.nan), f32(3.0e38)
+    table = [(inf, 0, 1, nan), (0, -inf, 1, nan), (inf, 1, -inf, nan), (-inf, 1, inf, nan), (inf, -1, inf, nan), (1, 1, nan, nan),
+             (nan, 0, 0, nan), (0, nan, 0, nan), (inf, 1, inf, inf), (inf, -2, -inf, -inf), (inf, 1, 5, inf), (2, 3, -inf, -inf),
+             (big, big, -inf, -inf), (big, big, 0, inf), (big, -2, -big, -inf), (big, 2, -big, big), (1, 0, -0.0, 0.0), (1, -0.0, -0.0, -0.0)]
+    a, b, c, want = (np.array([row[k] for row in table], np.float32) for k in range(4))
+    with np.errstate(all="ignore"):
+        got = fma32(a, b, c)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), got
+    ok = ~np.isnan(want)
+    assert np.array_equal(got[ok].view(np.uint32), want[ok].view(np.uint32)), (got, want)
+    v = np.array([0.0, -0.0, 1.0, -1.0, 0.4, 3.0e38, -3.0e38, 1.0e-45, np.inf, -np.inf, np.nan], np.float32)
+    a, b, c = (g.ravel() for g in np.meshgrid(v, v, v, indexing="ij"))
+    with np.errstate(all="ignore"):
+        got = fma32(a, b, c)
+        p_inf = (np.isinf(a) | np.isinf(b)) & ~np.isnan(a) & ~np.isnan(b)
+        invalid = (np.isinf(a) & (b == 0)) | ((a == 0) & np.isinf(b))
+        p_sign = np.signbit(a) != np.signbit(b)
+        want_nan = np.isnan(a) | np.isnan(b) | np.isnan(c) | invalid | (p_inf & ~invalid & np.isinf(c) & (p_sign != np.signbit(c)))
+    assert np.array_equal(np.isnan(got), want_nan)
+    assert want_nan.sum() > 300 and (~want_nan).sum() > 300 and np.isinf(got).sum() > 100
+
+
+EDGE_ALPHAS = (0.0, 0.4, 1.0, 1.5, -0.5, np.inf, np.nan)
+
+
+def _edge_frame():
+    """S and B [n, 4] float32, both drawn from the stores' own edge inputs (test_target_format._inputs: every byte threshold +- 1 ulp,
+    binary16 ties and denormals, 65504 / 65519.996 / 65520, infinities, -0) plus NaNs of both signs; B_a cycles through EDGE_ALPHAS,
+    so k = 1 - B_a is 1, 0.6, 0, negative, above 1, -inf and NaN.  S is the input set (its alpha whatever falls there: the rule does
+    not know what a channel means); B_c is a shuffle of it, so that every edge value meets every k and operands of every other kind"""
+    from helpers import NAN_PATTERNS
+    from test_target_format import _inputs
+    x = _inputs().ravel()
+    x = np.concatenate([x, np.tile(NAN_PATTERNS, 7)])
+    assert x.size % 4 == 0
+    S = x.reshape(-1, 4).copy()
+    B = np.random.default_rng(77).permutation(x).reshape(-1, 4).copy()
+    B[:, 3] = np.resize(np.array(EDGE_ALPHAS, np.float32), len(B))
+    # ... and the pixels where the frame's edge value goes through alone: S over an empty background, an edge-valued B under S = 0
+    keep = np.arange(len(S)) % 5
+    B[keep == 0] = 0
+    S[keep == 1] = 0
+    return S, B
+
+
+@pytest.mark.parametrize("fmt", [0, 1, 2])
+@pytest.mark.parametrize("bg", ["f32", "f16"])
+def test_composite_over_is_the_rule_at_the_edges(pkg, fmt, bg):
+    """gsr_composite_over against the numpy rule on non-finite, out-of-range and boundary operands, under the NaN rule
+    (helpers.assert_same_pixels): the reference the GPU is held to in test_store_edges_gpu.py, validated at the edges first"""
+    from helpers import assert_same_pixels, store_edge_classes
+    E = pkg.engine
+    S, B = _edge_frame()
+    with np.errstate(all="ignore"):
+        Bi = B if bg == "f32" else B.astype(np.float16)
+        Bf = decode(Bi)
+        for a in decode(np.array(EDGE_ALPHAS, Bi.dtype)):
+            assert (np.isnan(Bf[:, 3]) if np.isnan(a) else Bf[:, 3] == a).sum() > 5000, a
+        want = rule(S, Bf, fmt)
+        out32 = rule(S, Bf, 0)
+        want_store = store(out32, fmt)
+    got = E.composite_over(S, Bi, fmt)
+    assert got.dtype == want.dtype == E.target_dtype(fmt)
+    assert_same_pixels(got, want, f"format {fmt} over an {bg} image")
+    # teeth: what reaches the store holds every class of edge, and NaN exactly where IEEE says (inf * 0 under B_a = -inf ... )
+    cls = store_edge_classes(out32)
+    print(f"composite_over edges, format {fmt}, {bg} image: {cls}")
+    assert min(v for k, v in cls.items() if k != "neg_zero") > 0, cls      # (a sum is -0 only if both of its terms are)
+    assert cls["nan"] > np.isnan(S).sum() + np.isnan(Bf).sum() and cls["byte_edges"] > 300 and cls["negatives"] > 10000
+    if fmt == 2:
+        assert (got[np.isnan(out32)] == 0).all() and got.min() == 0 and got.max() == 255
+    # the numpy store is the library's on this set too
+    assert_same_pixels(E.convert_pixels(out32, fmt), want_store, f"convert_pixels, format {fmt}")
+
+
 def test_composite_over_rejects_bad_arguments(pkg):
     E = pkg.engine
     L = pkg.load_library()
