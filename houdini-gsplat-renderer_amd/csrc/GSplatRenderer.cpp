@@ -164,6 +164,54 @@ void GSplatRenderer::flushEntriesForMatchingDetail(const std::string& id)
     }
 }
 
+int GSplatRenderer::updateAttributes(const std::string& id, const uint16_t* splatColors, const float* splatAlphas,
+                                     const uint16_t* splatScales, const uint16_t* splatOrients, const uint16_t* splatShxs,
+                                     const uint16_t* splatShys, const uint16_t* splatShzs, int64_t* first_out, int64_t* n_out)
+{
+    if (first_out) *first_out = 0;
+    if (n_out) *n_out = 0;
+    const auto hit = table_.find(id);
+    if (hit == table_.end()) return GSR_E_INVALID;
+    Row& row = hit->second;
+    // where the row sits in what is resident: the splats taken from the parts before it, and how many were taken from it
+    int64_t first = 0, take = -1;
+    if (resident_ok_)
+        for (const Plan::Part& part : resident_.parts) {
+            if (part.id == id) { take = part.take; break; }
+            first += part.take;
+        }
+    const int nsh = (splatShxs ? 1 : 0) + (splatShys ? 1 : 0) + (splatShzs ? 1 : 0);
+    if (nsh != 0 && (nsh != 3 || row.sh_count < (take >= 0 ? take : row.count))) return GSR_E_INVALID;
+    if (splatColors) row.Cd = splatColors;
+    if (splatAlphas) row.alpha = splatAlphas;
+    if (splatScales) row.scale = splatScales;
+    if (splatOrients) row.orient = splatOrients;
+    if (nsh) { row.shx = splatShxs; row.shy = splatShys; row.shz = splatShzs; }
+    if (take < 0) return 0;
+    if (first_out) *first_out = first;
+    if (n_out) *n_out = take;
+    if (dry_) return 1;
+    gsr_attr_update u{};
+    u.Cd = splatColors; u.alpha = splatAlphas; u.scale = splatScales; u.orient = splatOrients;
+    if (nsh && resident_.sh) { u.shx = splatShxs; u.shy = splatShys; u.shz = splatShzs; }
+    status_ = multi_ ? gsr_multi_update(multi_, first, take, &u) : engine_ ? gsr_update(engine_, first, take, &u) : GSR_E_NO_DEVICE;
+    if (status_ != GSR_OK) {
+        note("error", "updating %" PRId64 " splats in place failed: %s", take, gsr_last_error());
+        resident_ok_ = false;   // the next redraw stages the edited arrays
+        return status_;
+    }
+    return 1;
+}
+
+const void* GSplatRenderer::rowArray(const std::string& id, int what) const
+{
+    const auto hit = table_.find(id);
+    if (hit == table_.end()) return nullptr;
+    const Row& r = hit->second;
+    const void* const a[8] = {r.P, r.Cd, r.alpha, r.scale, r.orient, r.shx, r.shy, r.shz};
+    return what >= 0 && what < 8 ? a[what] : nullptr;
+}
+
 void GSplatRenderer::includeInRenderPass(const std::string& id)
 {
     const auto hit = table_.find(id);
@@ -431,6 +479,13 @@ void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order
 int gsplat_renderer_set_target_format(gsplat_renderer* h, int format) { return h ? h->impl->setTargetFormat(format) : GSR_E_INVALID; }
 int gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane) { return h ? h->impl->setAovTarget(aov, plane) : GSR_E_INVALID; }
 int gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg) { return h ? h->impl->setBackground(bg) : GSR_E_INVALID; }
+int gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
+                                      const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
+                                      int64_t* first_out, int64_t* n_out)
+{
+    return h && id ? h->impl->updateAttributes(id, Cd, alpha, scale, orient, shx, shy, shz, first_out, n_out) : GSR_E_INVALID;
+}
+const void* gsplat_renderer_row_array(gsplat_renderer* h, const char* id, int what) { return h && id ? h->impl->rowArray(id, what) : nullptr; }
 int gsplat_renderer_get_target_format(gsplat_renderer* h) { return h ? h->impl->targetFormat() : GSR_E_INVALID; }
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id) { return h ? h->impl->query(what, id ? std::string(id) : std::string()) : -1; }
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]) { if (h && out) h->impl->origin(out); }

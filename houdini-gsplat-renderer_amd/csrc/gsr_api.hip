@@ -338,7 +338,7 @@ struct gsr_context {
     bool order_pays = false;           // k_sum_work's other verdict: the tiles differ enough in work for k_tile_order to pay
     unsigned long long* wire_zbuf = nullptr;   // wireframe overlay: (depth bits, splat index) per pixel ...
     float* wire_out = nullptr;                 // ... and the image staged for a host target
-    uint32_t* wire_inv = nullptr;              // ... and, with spatially ordered storage, upload index -> storage slot (built on first use per geometry)
+    uint32_t* wire_inv = nullptr;              // ... and, with spatially ordered storage, upload index -> storage slot (built on first use per geometry; gsr_update scatters through it too)
     uint64_t wire_inv_gen = 0;
     size_t wire_cap = 0;                       // pixels both hold
     // An upload in progress.  The registerUpdate()-layout arrays of ALL its entries sit in one device arena (sized at gsr_upload_begin,
@@ -1163,6 +1163,132 @@ static int order_and_pack(gsr_context* c)
     if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[1] = ms;
     if (hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess) c->st.upload_ms[2] = ms;
     return GSR_OK;
+}
+
+// upload index -> storage slot: the inverse of the storage permutation, built once per geometry on slot 0's own stream and shared by
+// the wire overlay (k_wire.h) and gsr_update.  Only an upload changes the permutation (and the generation the inverse is stamped with).
+static int ensure_inverse_perm(gsr_context* c)
+{
+    if (!c->perm || c->n == 0 || (c->wire_inv && c->wire_inv_gen == c->geo_gen)) return GSR_OK;
+    dev_free(c->wire_inv);
+    int rc = dev_alloc(&c->wire_inv, (size_t)c->n);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_invert_perm, dim3(div_up(c->n, 256)), dim3(256), 0, c->slot[0].own, c->perm, c->n, c->wire_inv);
+    c->wire_inv_gen = c->geo_gen;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Attributes of resident splats rewritten in place ("Attribute updates").  No position: the storage order, the bounding
+// box, the Morton scratch and the cluster boxes' xyz depend on P alone and stay as they are.
+extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u)
+{
+    if (!c || !u) return set_err(GSR_E_INVALID, "gsr_update: NULL argument");
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_update: upload in progress");
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_update: no geometry: nothing uploaded");
+    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
+        return set_err(GSR_E_INVALID, "gsr_update: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
+    const int nsh = (u->shx ? 1 : 0) + (u->shy ? 1 : 0) + (u->shz ? 1 : 0);
+    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_update: the three SH arrays come together or not at all");
+    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_update: SH arrays for a cloud uploaded without SH");
+    if (n64 == 0 || !(u->Cd || u->alpha || u->scale || u->orient || nsh)) return GSR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);      // no in-place write under a frame in flight (two frames in flight, deferred-check frames included)
+    if (rc) return rc;
+    const uint32_t n = (uint32_t)n64;
+    hipStream_t us = c->slot[0].own;
+    // the given arrays, rows [0, n), in the upload arena (kept between uploads and updates; grown only when too small)
+    const size_t al = 256;
+    size_t off = 0;
+    auto place = [&](const void* given, size_t bytes) { const size_t at = off; if (given) off += (bytes + al - 1) / al * al; return at; };
+    const size_t oA = place(u->alpha, (size_t)n * 4), oC = place(u->Cd, (size_t)n * 6), oS = place(u->scale, (size_t)n * 6), oO = place(u->orient, (size_t)n * 8);
+    const size_t oX = place(u->shx, (size_t)n * 32), oY = place(u->shy, (size_t)n * 32), oZ = place(u->shz, (size_t)n * 32);
+    if (off > c->stage_cap) {
+        dev_free(c->stage);
+        c->stage_cap = 0;
+        if ((rc = dev_alloc(&c->stage, off + 256))) return rc;
+        c->stage_cap = off + 256;
+    }
+    if ((rc = ensure_inverse_perm(c))) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
+    const double t0 = up_now_ms();
+    char* const base = c->stage;
+    hipError_t e = hipSuccess;
+    auto h2d = [&](size_t at, const void* h, size_t bytes) { if (h && e == hipSuccess) e = hipMemcpyAsync(base + at, h, bytes, hipMemcpyHostToDevice, us); };
+    h2d(oA, u->alpha, (size_t)n * 4); h2d(oC, u->Cd, (size_t)n * 6); h2d(oS, u->scale, (size_t)n * 6); h2d(oO, u->orient, (size_t)n * 8);
+    h2d(oX, u->shx, (size_t)n * 32); h2d(oY, u->shy, (size_t)n * 32); h2d(oZ, u->shz, (size_t)n * 32);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be freed on return
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_update: %s", hipGetErrorString(e));
+    const double h2d_ms = up_now_ms() - t0;
+    auto dev = [&](const void* given, size_t at) { return given ? base + at : (char*)nullptr; };
+    GsrUpdateSrc src;
+    src.alpha = reinterpret_cast<const float*>(dev(u->alpha, oA));
+    src.Cd = reinterpret_cast<const uint16_t*>(dev(u->Cd, oC)); src.scale = reinterpret_cast<const uint16_t*>(dev(u->scale, oS));
+    src.orient = reinterpret_cast<const uint16_t*>(dev(u->orient, oO)); src.shx = reinterpret_cast<const uint16_t*>(dev(u->shx, oX));
+    src.shy = reinterpret_cast<const uint16_t*>(dev(u->shy, oY)); src.shz = reinterpret_cast<const uint16_t*>(dev(u->shz, oZ));
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    const bool extents = u->scale || u->orient;
+    e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        if (c->has_sh)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update<true>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update<false>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+        // (the bounds of ALL clusters: a Morton-ordered store scatters the range over them, and the pass reads 32 bytes per splat)
+        if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    // What the resident cloud's frames may keep (the invalidation table).  The cached depth orders go in every case: their
+    // records hold the colours.  Colours change neither visibility, order nor opacity: horizons, prefixes, hints and policies survive
+    // a Cd / SH update; anything else is treated like a new cloud at the same positions.
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
+    if (u->alpha || extents) {
+        c->prefix_valid = false;
+        c->order_pays = false;
+        c->cull_pol.on_upload(); c->slab_pol.on_upload();
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+            GsrSlotHints& h = c->slot[k].hints;
+            h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
+            c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
+        }
+        c->lazy_pays = false;
+        if (e == hipSuccess && c->lazy_hint) e = hipMemsetAsync(c->lazy_hint, 0, 4, us);
+        if (e == hipSuccess && c->lazy_hint) e = hipStreamSynchronize(us);
+    }
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_update: %s", hipGetErrorString(e));
+    float ms = 0.0f;
+    c->st.upload_ms[4] = h2d_ms;
+    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
+    return GSR_OK;
+}
+
+// the resident geometry as it is stored (tests hold gsr_update to a fresh upload with it)
+extern "C" int gsr_debug_read_resident(gsr_context* c, int which, void* out, int64_t bytes)
+{
+    if (!c || which < 0 || which > 5) return set_err(GSR_E_INVALID, "gsr_debug_read_resident: bad argument");
+    if (c->uploading || !c->has_geometry) return set_err(GSR_E_INVALID, "gsr_debug_read_resident: no geometry");
+    if (which == 3 && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_debug_read_resident: a cloud without SH has no colour rows");
+    const void* src = nullptr;
+    size_t size = 0;
+    switch (which) {
+    case 0: src = c->geoA; size = (size_t)c->n * 16; break;
+    case 1: src = c->geoB; size = (size_t)c->n * 16; break;
+    case 2: src = c->col; size = (size_t)c->col_chunks * c->cap * 16; break;   // (chunk k starts k * cap splats in)
+    case 3: src = c->colrow; size = (size_t)c->n * 128; break;
+    case 4: src = c->clusA; size = (size_t)c->nclus * 16; break;
+    default: src = c->clusB; size = (size_t)c->nclus * 16; break;
+    }
+    if (size > (size_t)0x7fffffff) return set_err(GSR_E_INVALID, "gsr_debug_read_resident: the plane is too large for this door");
+    if (!out) return (int)size;
+    if (bytes < (int64_t)size) return set_err(GSR_E_INVALID, "gsr_debug_read_resident: %lld bytes given, %zu needed", (long long)bytes, size);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    if (size) HIP_TRY(hipMemcpy(out, src, size, hipMemcpyDeviceToHost));
+    return (int)size;
 }
 
 // ---------------------------------------------------------------------------
@@ -2623,13 +2749,8 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
         c->wire_cap = npix;
     }
     // outlines at the same depth are drawn in UPLOAD order (k_wire.h): with spatially ordered storage the resolve pass goes back
-    // from the winner's upload index to its slot through the inverse of the storage permutation, built once per geometry
-    if (c->perm && c->n > 0 && (!c->wire_inv || c->wire_inv_gen != c->geo_gen)) {
-        dev_free(c->wire_inv);
-        if ((rc = dev_alloc(&c->wire_inv, (size_t)c->n))) return rc;
-        hipLaunchKernelGGL(k_invert_perm, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->perm, c->n, c->wire_inv);
-        c->wire_inv_gen = c->geo_gen;
-    }
+    // from the winner's upload index to its slot through the inverse of the storage permutation, built once per geometry (gsr_update shares it)
+    if ((rc = ensure_inverse_perm(c))) return rc;
     const uint32_t* const inv = (c->perm && c->n > 0) ? c->wire_inv : (const uint32_t*)nullptr;
     unsigned long long* zbuf = c->wire_zbuf;
     float* target = out_is_device ? rgba_out : c->wire_out;

@@ -570,6 +570,16 @@ extern "C" int gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const u
     return rc;
 }
 
+// the resident cloud edited in place on every rank (it is replicated)
+extern "C" int gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_update* u)
+{
+    if (!m || !u) return fail(GSR_E_INVALID, "gsr_multi_update: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_update: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return for_each_rank(m, [=](int g) { return gsr_update(m->ctx[g], first, n, u); });
+}
+
 // ---- per frame ---------------------------------------------------------------------------------
 extern "C" int gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device)
 {

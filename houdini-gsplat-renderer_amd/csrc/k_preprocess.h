@@ -29,6 +29,38 @@
 // splat, its rows of the source arrays (96 + 36 bytes; a gather when perm is a permutation).  Before round 6 this was three passes:
 // k_repack (one thread per splat, 2-byte loads at a 32-byte stride, 16-byte stores at a 128-byte stride: 1.5 x write amplification,
 // 0.19 of HBM), then k_permute_geo + k_permute_rows over a second copy of the geometry, then k_cluster_bounds.
+// eighth half of geoB: an upper bound of |diag(scale) R(orient)^T|_F, the only thing K1's cheap extent bound needs of the
+// scale and the (unnormalised) quaternion -- so the bound costs a dozen instructions per splat instead of ninety.
+// One function for k_pack and k_update: an updated splat's bound is bit for bit what a fresh upload gives it.
+__device__ __forceinline__ uint16_t gsr_extent_half(uint16_t s0, uint16_t s1, uint16_t s2, uint16_t o0, uint16_t o1, uint16_t o2, uint16_t o3)
+{
+    const float sx = gsr_h2f(s0), sy = gsr_h2f(s1), sz = gsr_h2f(s2);
+    const float qi = gsr_h2f(o0), qj = gsr_h2f(o1), qk = gsr_h2f(o2), qr = gsr_h2f(o3);
+    const float r00 = 1.0f - 2.0f * gsr_fma(qj, qj, qk * qk), r01 = 2.0f * gsr_fma(qi, qj, -(qr * qk)), r02 = 2.0f * gsr_fma(qi, qk, qr * qj);
+    const float r10 = 2.0f * gsr_fma(qi, qj, qr * qk), r11 = 1.0f - 2.0f * gsr_fma(qi, qi, qk * qk), r12 = 2.0f * gsr_fma(qj, qk, -(qr * qi));
+    const float r20 = 2.0f * gsr_fma(qi, qk, -(qr * qj)), r21 = 2.0f * gsr_fma(qj, qk, qr * qi), r22 = 1.0f - 2.0f * gsr_fma(qi, qi, qj * qj);
+    const float mf2 = sx * sx * (r00 * r00 + r10 * r10 + r20 * r20) + sy * sy * (r01 * r01 + r11 * r11 + r21 * r21) +
+                      sz * sz * (r02 * r02 + r12 * r12 + r22 * r22);
+    const float mfv = __builtin_sqrtf(mf2) * 1.001f;
+    const _Float16 hh = (_Float16)mfv;              // rounded up (to nearest, then one step if that fell short): mf >= 0
+    uint16_t mf_h = __builtin_bit_cast(uint16_t, hh);
+    if ((float)hh < mfv) mf_h += 1;                 // (0x7bff + 1 = inf; inf / NaN stay what they are: K1 then takes the full path)
+    return mf_h;
+}
+// chunk c (eight halves) of a splat's 48 colour halves from its LDS row x[16] y[16] z[16] Cd[3]: the 16 x 3 -> 3 x 16 transpose
+template <bool SH>
+__device__ __forceinline__ uint4 gsr_colour_chunk(const uint16_t* row, int c)
+{
+    uint16_t h[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int hh = 8 * c + k, co = hh / 3, chn = hh - 3 * co;     // coefficient (0 = Cd), channel
+        // coefficient co of the reference's row-major 4x4 sits at flat index co - 1 of the x / y / z rows (co = 1..15)
+        h[k] = co == 0 ? row[48 + chn] : (SH ? row[16 * chn + (co - 1)] : (uint16_t)0);
+    }
+    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
+    return make_uint4(pk(h[0], h[1]), pk(h[2], h[3]), pk(h[4], h[5]), pk(h[6], h[7]));
+}
 struct GsrPackSrc {
     const float* P; const float* alpha;
     const uint16_t *Cd, *scale, *orient, *shx, *shy, *shz;
@@ -63,22 +95,7 @@ k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ pe
             const uint16_t* s = src.scale + 3 * (size_t)i;
             const uint16_t* o = src.orient + 4 * (size_t)i;
             const uint16_t s0 = s[0], s1 = s[1], s2 = s[2], o0 = o[0], o1 = o[1], o2 = o[2], o3 = o[3];
-            // eighth half of geoB: an upper bound of |diag(scale) R(orient)^T|_F, the only thing K1's cheap extent bound needs of the
-            // scale and the (unnormalised) quaternion -- so the bound costs a dozen instructions per splat instead of ninety
-            uint16_t mf_h;
-            {
-                const float sx = gsr_h2f(s0), sy = gsr_h2f(s1), sz = gsr_h2f(s2);
-                const float qi = gsr_h2f(o0), qj = gsr_h2f(o1), qk = gsr_h2f(o2), qr = gsr_h2f(o3);
-                const float r00 = 1.0f - 2.0f * gsr_fma(qj, qj, qk * qk), r01 = 2.0f * gsr_fma(qi, qj, -(qr * qk)), r02 = 2.0f * gsr_fma(qi, qk, qr * qj);
-                const float r10 = 2.0f * gsr_fma(qi, qj, qr * qk), r11 = 1.0f - 2.0f * gsr_fma(qi, qi, qk * qk), r12 = 2.0f * gsr_fma(qj, qk, -(qr * qi));
-                const float r20 = 2.0f * gsr_fma(qi, qk, -(qr * qj)), r21 = 2.0f * gsr_fma(qj, qk, qr * qi), r22 = 1.0f - 2.0f * gsr_fma(qi, qi, qj * qj);
-                const float mf2 = sx * sx * (r00 * r00 + r10 * r10 + r20 * r20) + sy * sy * (r01 * r01 + r11 * r11 + r21 * r21) +
-                                  sz * sz * (r02 * r02 + r12 * r12 + r22 * r22);
-                const float mfv = __builtin_sqrtf(mf2) * 1.001f;
-                const _Float16 hh = (_Float16)mfv;              // rounded up (to nearest, then one step if that fell short): mf >= 0
-                mf_h = __builtin_bit_cast(uint16_t, hh);
-                if ((float)hh < mfv) mf_h += 1;                 // (0x7bff + 1 = inf; inf / NaN stay what they are: K1 then takes the full path)
-            }
+            const uint16_t mf_h = gsr_extent_half(s0, s1, s2, o0, o1, o2, o3);
             geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, mf_h));
             mf = gsr_h2f(mf_h);
             bad = !(mf < 6.0e4f);
@@ -95,14 +112,7 @@ k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ pe
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (live && q >= 1 && (SH ? q <= 6 : q == 1)) {
         const int c = q - 1;
-        uint16_t h[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int hh = 8 * c + k, co = hh / 3, chn = hh - 3 * co;     // coefficient (0 = Cd), channel
-            // coefficient co of the reference's row-major 4x4 sits at flat index co - 1 of the x / y / z rows (co = 1..15)
-            h[k] = co == 0 ? s_h[sp][48 + chn] : (SH ? s_h[sp][16 * chn + (co - 1)] : (uint16_t)0);
-        }
-        const uint4 v = make_uint4(pk(h[0], h[1]), pk(h[2], h[3]), pk(h[4], h[5]), pk(h[6], h[7]));
+        const uint4 v = gsr_colour_chunk<SH>(s_h[sp], c);
         col[(size_t)c * cap + j] = v;                  // SoA chunks: coalesced for a pass over ALL splats (eager colour)
         rowpiece = v;
     }
@@ -133,6 +143,117 @@ k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ pe
         }
         clusA[blockIdx.x] = make_float4(l0, l1, l2, m);
         clusB[blockIdx.x] = make_float4(h0, h1, h2, b != 0.0f ? 1.0f : 0.0f);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K0u: attributes of RESIDENT splats rewritten in place (gsr_update): k_pack mirrored.  The source arrays (the staging arena, upload
+// order, rows [0, cnt) = splats [first, first + cnt) of the upload) are read coalesced and scattered into the storage slots
+//   j = inv[first + t]     (inv: upload index -> storage slot, the inverse of perm; NULL: upload order, j = first + t)
+// One workgroup = 64 splats, eight lanes per splat with k_pack's roles; an array that is NULL is left as it is in HBM:
+//   q = 0      alpha -> geoA[j].w and colrow[j][0].w (4-byte stores; the position stays); Cd (or, SH without Cd, the resident Cd) -> LDS
+//   q = 1..6   SH rows -> LDS, then chunk q - 1 -> col[q - 1][j] and colrow[j][q]; Cd alone: lane 1 rewrites halves 0..2 of chunk 0
+//              (an SH context: read-modify-write, sh1.rgb and sh2.rg survive; no SH: Cd + zero halves, and there is no colrow)
+//   q = 7      scale and / or orient (the other from the resident geoB[j]) -> geoB[j] with its extent bound
+// Pieces of a splat's 128-byte colrow line that do not change are not written.  The cluster bounds follow in k_cluster_extents.
+struct GsrUpdateSrc {
+    const float* alpha;
+    const uint16_t *Cd, *scale, *orient, *shx, *shy, *shz;
+};
+template <bool SH>
+__global__ void __launch_bounds__(GSR_PACK_THREADS)
+k_update(uint32_t first, uint32_t cnt, uint32_t cap, GsrUpdateSrc src, const uint32_t* __restrict__ inv,
+         float4* __restrict__ geoA, uint4* __restrict__ geoB, uint4* __restrict__ col, uint4* __restrict__ colrow)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad), as in k_pack
+    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
+    const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
+    const bool live = t < cnt;
+    const uint32_t j = live ? (inv ? inv[first + t] : first + t) : 0u;
+    const bool sh = SH && src.shx;                     // (all three or none: the host checks)
+    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
+    if (live) {
+        if (q == 0) {
+            if (src.alpha) {
+                const float op = src.alpha[t];
+                reinterpret_cast<float*>(geoA + j)[3] = op;
+                if (SH) reinterpret_cast<float*>(colrow + (size_t)j * 8)[3] = op;
+            }
+            if (src.Cd) {
+                s_h[sp][48] = src.Cd[3 * (size_t)t]; s_h[sp][49] = src.Cd[3 * (size_t)t + 1]; s_h[sp][50] = src.Cd[3 * (size_t)t + 2];
+            } else if (sh) {                           // new SH under the resident Cd: halves 0..2 of chunk 0
+                const uint2 w = *reinterpret_cast<const uint2*>(col + j);
+                s_h[sp][48] = (uint16_t)(w.x & 0xffffu); s_h[sp][49] = (uint16_t)(w.x >> 16); s_h[sp][50] = (uint16_t)(w.y & 0xffffu);
+            }
+        } else if (q == 7) {
+            if (src.scale || src.orient) {
+                uint4 b = make_uint4(0u, 0u, 0u, 0u);
+                if (!src.scale || !src.orient) b = geoB[j];
+                uint16_t s0 = (uint16_t)(b.x & 0xffffu), s1 = (uint16_t)(b.x >> 16), s2 = (uint16_t)(b.y & 0xffffu);
+                uint16_t o0 = (uint16_t)(b.y >> 16), o1 = (uint16_t)(b.z & 0xffffu), o2 = (uint16_t)(b.z >> 16), o3 = (uint16_t)(b.w & 0xffffu);
+                if (src.scale) { const uint16_t* s = src.scale + 3 * (size_t)t; s0 = s[0]; s1 = s[1]; s2 = s[2]; }
+                if (src.orient) { const uint16_t* o = src.orient + 4 * (size_t)t; o0 = o[0]; o1 = o[1]; o2 = o[2]; o3 = o[3]; }
+                geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, gsr_extent_half(s0, s1, s2, o0, o1, o2, o3)));
+            }
+        } else if (sh) {
+            const int ch = (q - 1) >> 1, part = (q - 1) & 1;
+            const uint16_t* row = (ch == 0 ? src.shx : (ch == 1 ? src.shy : src.shz)) + 16 * (size_t)t + 8 * part;
+            *reinterpret_cast<uint4*>(&s_h[sp][16 * ch + 8 * part]) = *reinterpret_cast<const uint4*>(row);
+        }
+    }
+    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!live) return;
+    if (sh) {
+        if (q >= 1 && q <= 6) {
+            const uint4 v = gsr_colour_chunk<true>(s_h[sp], q - 1);
+            col[(size_t)(q - 1) * cap + j] = v;
+            colrow[(size_t)j * 8 + q] = v;
+        }
+    } else if (q == 1 && src.Cd) {
+        const uint32_t w0 = pk(s_h[sp][48], s_h[sp][49]), c2 = s_h[sp][50];
+        if (SH) {
+            uint4 v = col[j];
+            v.x = w0; v.y = (v.y & 0xffff0000u) | c2;
+            col[j] = v;
+            colrow[(size_t)j * 8 + 1] = v;
+        } else {
+            col[j] = make_uint4(w0, c2, 0u, 0u);
+        }
+    }
+}
+
+// ... and the w fields of the cluster bounds after scale / orient changed: clusA[c].w = the largest extent bound of the cluster's live
+// slots, clusB[c].w = the "never cull" flag (a non-finite position or !(mf < 6e4) anywhere in it) -- from the resident geoA / geoB, by
+// k_pack's rule, so a bound is neither stale-large after a shrink nor stale-small after a growth.  lo.xyz / hi.xyz depend on the
+// positions alone and are not touched.  One wave per cluster, 32 bytes read per splat.
+__global__ void __launch_bounds__(256)
+k_cluster_extents(uint32_t n, uint32_t nclus, const float4* __restrict__ geoA, const uint4* __restrict__ geoB,
+                  float4* __restrict__ clusA, float4* __restrict__ clusB)
+{
+    static_assert(GSR_CLUSTER == 64, "one wave = one cluster");
+    const int lane = threadIdx.x & 63;
+    const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (c >= nclus) return;                            // (wave-uniform)
+    const uint32_t j = c * (uint32_t)GSR_CLUSTER + (uint32_t)lane;
+    float mf = 0.0f;
+    bool bad = false;
+    if (j < n) {
+        const float4 a = geoA[j];
+        mf = gsr_h2f(geoB[j].w >> 16);
+        bad = !(mf < 6.0e4f) || !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) mf = __builtin_fmaxf(mf, __shfl_xor(mf, d, 64));
+    // (k_pack folds the same values with fmaxf, which drops a NaN operand, so the order of the fold does not matter; its last fold
+    //  starts from 0, which turns a cluster whose bounds are ALL NaN into 0: so does this one)
+    mf = __builtin_fmaxf(0.0f, mf);
+    if (lane == 0) {
+        reinterpret_cast<float*>(clusA + c)[3] = mf;
+        reinterpret_cast<float*>(clusB + c)[3] = any_bad ? 1.0f : 0.0f;
     }
 }
 

@@ -83,6 +83,12 @@ class gsr_background(C.Structure):
                 ("image_is_device", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_attr_update(C.Structure):
+    """include/gsplat_hip.h: the arrays gsr_update rewrites in place (NULL = leave as is)"""
+    _fields_ = [("Cd", C.c_void_p), ("alpha", C.c_void_p), ("scale", C.c_void_p), ("orient", C.c_void_p),
+                ("shx", C.c_void_p), ("shy", C.c_void_p), ("shz", C.c_void_p)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -138,6 +144,7 @@ C_ABI_SYMBOLS = [
     "gsplat_renderer_set_target_format", "gsplat_renderer_get_target_format",
     "gsr_render_aov", "gsr_resolve_depth", "gsr_resolve_depth_device", "gsplat_renderer_set_aov_target",
     "gsr_render_over", "gsr_composite_over", "gsplat_renderer_set_background",
+    "gsr_update", "gsr_multi_update", "gsr_debug_read_resident", "gsplat_renderer_update_attributes", "gsplat_renderer_row_array",
 ]
 
 
@@ -171,6 +178,12 @@ def load_library() -> C.CDLL:
     L.gsr_upload_append.argtypes = [vp, i64] + [vp] * 8
     L.gsr_upload_append_raw.argtypes = [vp, i64, C.POINTER(gsr_raw_attrs)]
     L.gsr_upload_end.argtypes = [vp]
+    L.gsr_update.argtypes = [vp, i64, i64, C.POINTER(gsr_attr_update)]
+    L.gsr_multi_update.argtypes = [vp, i64, i64, C.POINTER(gsr_attr_update)]
+    L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
+    L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
+    L.gsplat_renderer_row_array.restype = vp
     L.gsr_upload_abort.argtypes = [vp]
     L.gsr_upload.argtypes = [vp, i64] + [vp] * 8 + [f32p]
     L.gsr_set_row_shard.argtypes = [vp, i32, i32]
@@ -390,6 +403,30 @@ def camera_struct(cam) -> gsr_camera:
     return s
 
 
+UPDATE_ATTRS = (("Cd", np.uint16, 3), ("alpha", np.float32, 1), ("scale", np.uint16, 3), ("orient", np.uint16, 4),
+                ("shx", np.uint16, 16), ("shy", np.uint16, 16), ("shz", np.uint16, 16))
+RESIDENT_GEOA, RESIDENT_GEOB, RESIDENT_COL, RESIDENT_COLROW, RESIDENT_CLUSA, RESIDENT_CLUSB = range(6)
+
+
+def attr_update_struct(**arrays):
+    """gsr_attr_update from keyword arrays (Cd, alpha, scale, orient, shx, shy, shz; None = leave as is) -> (struct, n, the typed
+    contiguous arrays it points into: keep them alive during the call).  n comes from the arrays; mismatched lengths raise."""
+    u, keep, n = gsr_attr_update(), [], None
+    for name, dtype, width in UPDATE_ATTRS:
+        a = arrays.get(name)
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size % width:
+            raise GsrError(-1, f"update_attrs: {name} holds {a.size} values, not a multiple of {width}")
+        if n is not None and a.size // width != n:
+            raise GsrError(-1, f"update_attrs: {name} holds {a.size // width} splats, the arrays before it {n}")
+        n = a.size // width
+        keep.append(a)
+        setattr(u, name, a.ctypes.data)
+    return u, (n or 0), keep
+
+
 class _Arrays:
     """contiguous, correctly typed views of a Splats-like object (kept alive during the call)"""
 
@@ -482,6 +519,24 @@ class Engine:
             self.L.gsr_upload_abort(self.h)
             raise
         return n
+
+    def update_attrs(self, first: int, Cd=None, alpha=None, scale=None, orient=None, shx=None, shy=None, shz=None) -> int:
+        """gsr_update: new attribute values for the resident splats [first, first + n) (upload order) written in place, no re-upload;
+        arrays in the registerUpdate() layout (halves as uint16 bits), None = leave as is, n from the arrays.  No P: that is an upload."""
+        u, n, keep = attr_update_struct(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
+        _check(self.L.gsr_update(self.h, int(first), n, C.byref(u)))
+        return n
+
+    def debug_resident(self, which: int) -> np.ndarray:
+        """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
+        size = self.L.gsr_debug_read_resident(self.h, int(which), None, 0)
+        if size < 0:
+            _check(size)
+        out = np.zeros(size, np.uint8)
+        rc = self.L.gsr_debug_read_resident(self.h, int(which), out.ctypes.data, size)
+        if rc < 0:
+            _check(rc)
+        return out
 
     # ---- configuration
     def set_stream(self, hip_stream: int | None):
@@ -721,6 +776,7 @@ class GSplatRenderer:
         if not self.h:
             raise GsrError(-3, self.L.gsr_last_error().decode("utf-8", "replace") or "gsplat_renderer_create failed")
         self._keep = {}
+        self._updates = {}      # rid -> {attribute: the array updateAttributes gave the row last}
 
     def close(self):
         if getattr(self, "h", None):
@@ -745,13 +801,43 @@ class GSplatRenderer:
             raise GsrError(n, "registerUpdate failed")
         rid = buf.value.decode()
         self._keep[rid] = a  # the shim BORROWS the arrays, as the reference does
+        # the new registration replaced every pointer of the row, and retired the rows of older versions of its detail
+        detail = rid.split("__", 1)[0] + "__"
+        for k in [k for k in self._updates if k == rid or (k.startswith(detail) and k.rsplit("__", 1)[-1] != rid.rsplit("__", 1)[-1])]:
+            del self._updates[k]
         return rid
+
+    def updateAttributes(self, rid: str, Cd=None, alpha=None, scale=None, orient=None, shx=None, shy=None, shz=None):
+        """GSplatRenderer::updateAttributes: new arrays for a registered primitive whose positions did not change -> (rc, first, n):
+        rc 1 = its resident splats [first, first + n) were edited in place, 0 = not resident (staged when next shown), < 0 = GSR_E_*.
+        The shim BORROWS the arrays: each is kept alive here, one per attribute of the row, in place of the one it replaces."""
+        given = dict(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
+        u, n, keep = attr_update_struct(**given)
+        first, cnt = C.c_int64(0), C.c_int64(0)
+        rc = int(self.L.gsplat_renderer_update_attributes(self.h, rid.encode(), u.Cd, u.alpha, u.scale, u.orient, u.shx, u.shy, u.shz,
+                                                          C.byref(first), C.byref(cnt)))
+        # keep what the row holds NOW: a refused call may or may not have replaced its pointers (an unknown id or bad SH arrays: not;
+        # an engine's refusal: yes), so ask the row
+        what = {"Cd": 1, "alpha": 2, "scale": 3, "orient": 4, "shx": 5, "shy": 6, "shz": 7}
+        names = [k for k, _, _ in UPDATE_ATTRS if given[k] is not None]
+        for k, a in zip(names, keep):
+            if self.rowArray(rid, what[k]) == a.ctypes.data:
+                self._updates.setdefault(rid, {})[k] = a
+        return rc, first.value, cnt.value
+
+    def rowArray(self, rid: str, what: int) -> int:
+        """address of the array a registered row holds now (0 P, 1 Cd, 2 alpha, 3 scale, 4 orient, 5..7 shx / shy / shz); 0 = none"""
+        return int(self.L.gsplat_renderer_row_array(self.h, rid.encode(), int(what)) or 0)
 
     def includeInRenderPass(self, rid: str):
         self.L.gsplat_renderer_include_in_render_pass(self.h, rid.encode())
 
     def flushEntriesForMatchingDetail(self, rid: str):
         self.L.gsplat_renderer_flush_entries_for_matching_detail(self.h, rid.encode())
+        # the rows of that detail are gone: ids are "<detail>__<vertex offset>__<version>"
+        detail = rid.split("__", 1)[0] + "__"
+        for k in [k for k in self._updates if k.startswith(detail)]:
+            del self._updates[k]
 
     @staticmethod
     def context(cam, target=None, target_is_device=False) -> GSplatRenderContext:
@@ -892,6 +978,12 @@ class MultiEngine:
     def upload(self, splats, origin=(0.0, 0.0, 0.0)):
         a = _Arrays(splats)
         _check(self.L.gsr_multi_upload(self.h, a.n, *a.ptrs(), _f3(origin)))
+
+    def update_attrs(self, first: int, Cd=None, alpha=None, scale=None, orient=None, shx=None, shy=None, shz=None) -> int:
+        """gsr_multi_update: Engine.update_attrs on every rank"""
+        u, n, keep = attr_update_struct(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
+        _check(self.L.gsr_multi_update(self.h, int(first), n, C.byref(u)))
+        return n
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

@@ -105,7 +105,23 @@ public:
      * background verb; setAovTarget refuses likewise while a background is set).  A dry instance remembers it. */
     int setBackground(const gsr_background* bg);
 
+    /* New attribute arrays (registerUpdate() layout, BORROWED like the ones they replace; NULL = that attribute stays) for a registered
+     * primitive whose positions did not change -- no reference counterpart; GR_Primitive::update would call it when the update reason
+     * carries no P change.  The row's pointers are replaced, so a later re-stage uploads the edited arrays.  If the
+     * row is a part of the plan that is resident, its splats are edited in place (gsr_update / gsr_multi_update: no re-upload): they
+     * are the upload-order range [*first_out, *first_out + *n_out) -- the splats taken from the parts before it, and as many as were
+     * taken from it (a budget-truncated part updates only what is resident).  Returns 1: updated in place; 0: not resident, the next
+     * generateRenderGeometry() that shows it stages it (*first_out = *n_out = 0); GSR_E_INVALID: unknown id, one or two of the three
+     * SH arrays, or SH arrays for a row that registered fewer SH elements than splats; another GSR_E_* code: the engine refused (the
+     * next redraw re-stages).  SH arrays do not reach the GPU while the resident pass carries no SH.  A dry instance does the same
+     * bookkeeping without a GPU.  first_out / n_out may be NULL. */
+    int updateAttributes(const std::string& id, const uint16_t* splatColors, const float* splatAlphas, const uint16_t* splatScales,
+                         const uint16_t* splatOrients, const uint16_t* splatShxs, const uint16_t* splatShys, const uint16_t* splatShzs,
+                         int64_t* first_out, int64_t* n_out);
     /* introspection (no reference counterpart; used by tests and the C wrappers) */
+    /* debug door: the (borrowed) array a row holds now, i.e. what the next re-stage uploads: what = 0 P, 1 Cd, 2 alpha, 3 scale,
+     * 4 orient, 5 shx, 6 shy, 7 shz; NULL for an unknown id */
+    const void* rowArray(const std::string& id, int what) const;
     enum Query {
         Q_REGISTRY_SIZE = 0, Q_ACTIVE_STAGED = 1, Q_SPLAT_COUNT = 2, Q_CAN_RENDER = 3,
         Q_STAGING_COUNT = 4,   /* how many times geometry was (re)staged */
@@ -212,6 +228,12 @@ void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order
 int  gsplat_renderer_set_target_format(gsplat_renderer* h, int format);   /* GSplatRenderer::setTargetFormat */
 int  gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane);   /* GSplatRenderer::setAovTarget */
 int  gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg);   /* GSplatRenderer::setBackground */
+/* GSplatRenderer::updateAttributes; gsplat_renderer_row_array below is the debug door GSplatRenderer::rowArray (tests only) */
+int  gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const uint16_t* Cd, const float* alpha,
+                                       const uint16_t* scale, const uint16_t* orient,
+                                       const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
+                                       int64_t* first_out, int64_t* n_out);
+const void* gsplat_renderer_row_array(gsplat_renderer* h, const char* id, int what);
 int  gsplat_renderer_get_target_format(gsplat_renderer* h);               /* the format in use; <0 for a NULL handle */
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id_or_null);
 void gsplat_renderer_get_origin(gsplat_renderer* h, float out[3]);

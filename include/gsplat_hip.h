@@ -110,7 +110,8 @@ typedef struct gsr_stats {
     int64_t uploads;                       /* complete uploads (gsr_upload_end) since gsr_create / gsr_stats_reset */
     double upload_ms[6];                   /* the LAST upload: [0] host -> device copies (wall clock spent inside gsr_upload_append*, quantisation of raw
                                               attributes included), [1] bounding box + Morton codes + their sort (HIP events), [2] k_pack: the arrays into
-                                              storage order + cluster bounds (HIP events), [3] wall clock gsr_upload_begin .. gsr_upload_end, [4], [5] reserved */
+                                              storage order + cluster bounds (HIP events), [3] wall clock gsr_upload_begin .. gsr_upload_end; the LAST gsr_update: [4] its host ->
+                                              device copies (wall clock), [5] its kernels (k_update + the cluster bounds, HIP events); 0 before the first one */
 } gsr_stats;
 
 /* ---- lifetime ----------------------------------------------------------- */
@@ -195,6 +196,30 @@ int  gsr_upload(gsr_context* ctx, int64_t n,
                 const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
                 const float origin[3]);
 
+/* ---- attribute update (the resident splats edited in place) --------------- */
+/* New values for attributes of splats that are already resident, without a re-upload: what a colour grade, an opacity mask, a
+ * rescale or an SH swap costs is the bytes of the arrays given, not the cloud.  Arrays are HOST pointers in the registerUpdate()
+ * layout above, holding rows for the splats [first, first + n) only; first counts in UPLOAD order across all the entries that were
+ * appended (so a caller who concatenated several entries addresses one of them by the running sum of their sizes).  NULL = that
+ * attribute stays as it is.  shx / shy / shz come all three or not at all, and only for a cloud uploaded with SH.
+ * There is NO P: a position decides the storage order, the bounding box and the cluster boxes -- moving a point is a re-upload.
+ * Also not covered: raw float32 sources (gsr_raw_attrs: quantise on the host, or re-upload) and device-pointer sources.
+ * Synchronous like gsr_upload_append (the arrays may be freed on return); it first waits for every frame of the context that is
+ * still in flight, so no frame ever reads a half-written splat.
+ * CONTRACT: after GSR_OK the resident geometry is bit for bit what a fresh context holds after gsr_upload of the edited arrays
+ * (same P, origin, GSR_OPT_STORAGE_ORDER and SH presence), and so is every later frame, in every option mode.
+ * GSR_E_INVALID, with the context untouched: NULL ctx or u; no geometry resident; an upload in progress; first < 0, n < 0 or
+ * first + n beyond the resident count; one or two of the three SH arrays; SH arrays for a cloud without SH.
+ * n == 0, or all seven pointers NULL: GSR_OK, nothing happens.  gsr_stats.uploads does not count updates; upload_ms[4], [5] time the last one. */
+typedef struct gsr_attr_update {
+    const uint16_t* Cd;               /* half[3n]  */
+    const float*    alpha;            /* float[n]  */
+    const uint16_t* scale;            /* half[3n]  */
+    const uint16_t* orient;           /* half[4n] (x, y, z, w) */
+    const uint16_t *shx, *shy, *shz;  /* half[16n] each */
+} gsr_attr_update;
+int  gsr_update(gsr_context* ctx, int64_t first, int64_t n, const gsr_attr_update* u);
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -251,6 +276,8 @@ int  gsr_multi_upload_abort(gsr_multi* m);
 int  gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const uint16_t* Cd, const float* alpha,
                       const uint16_t* scale, const uint16_t* orient,
                       const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, const float origin[3]);
+/* gsr_update on every rank (the cloud is replicated); synchronises the frames and the gather in flight first */
+int  gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_update* u);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
@@ -457,6 +484,12 @@ int  gsr_debug_read_depth_order(gsr_context* ctx, int32_t* perm, int64_t cap, in
 /* the storage order of the uploaded splats: perm[j] = upload index of the splat in storage slot j (n = uploaded count).
  * Equal sort keys leave the depth sort in this order. */
 int  gsr_debug_read_storage_order(gsr_context* ctx, int32_t* perm, int64_t n);
+/* the resident geometry as stored, bytes as they sit in HBM: which = 0 geoA (n x 16: P.xyz, opacity), 1 geoB (n x 16: scale, orient, extent
+ * half), 2 col (the colour chunks, 16 bytes per splat each: 6 with SH, 1 without, chunk k starting k * CAPACITY splats in -- the capacity is
+ * the largest count the context has been uploaded with since its chunk count last changed, so the plane is size / (16 * chunks) splats
+ * per chunk, of which the first n are live), 3 colrow (n x 128; GSR_E_INVALID for a cloud without SH), 4 clusA, 5 clusB (clusters x 16).
+ * out = NULL: returns the plane's size in bytes; otherwise copies it (bytes = room in out) and returns the size.  Storage order. */
+int  gsr_debug_read_resident(gsr_context* ctx, int which, void* out, int64_t bytes);
 /* per-SUPER-tile [start,end) into the sorted pair list + the list itself (splat indices);
  * n_lists = stiles_x*stiles_y, n_pairs = pairs_total of the last frame */
 int  gsr_debug_read_tile_lists(gsr_context* ctx, int32_t* list_start, int32_t* list_end, int64_t n_lists,
