@@ -19,7 +19,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
@@ -41,6 +40,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_sort.h"
 #include "k_wire.h"
 #include "gsr_frame_plan.h"
+#include "gsr_host_buffers.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -52,25 +52,6 @@ static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN
 #ifndef GSR_SPIN_US
 #define GSR_SPIN_US 2000         // how long a host wait for a mailbox word spins before it blocks in the runtime
 #endif
-
-static thread_local char g_err[512] = "";
-
-static int set_err(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_err(e_ == hipErrorOutOfMemory ? GSR_E_OOM : GSR_E_HIP, "%s failed: %s (%s:%d)", #expr, \
-                           hipGetErrorString(e_), __FILE__, __LINE__);                             \
-    } while (0)
 
 // what identifies a depth order: the geometry generation, the shard (a rank sorts only the splats it owns) and the camera
 struct SortKey {
@@ -156,8 +137,7 @@ struct FrameSlot {
     uint2 *valA = nullptr, *valB = nullptr;      // depth-sort payload: (splat index, packed tile rect)
     uint32_t* d_n = nullptr;           // splats that survived culling = items after the first sort pass
     float* zwin = nullptr;             // per-splat window depth (depth-tested frames)
-    float* depth_stage = nullptr;      // device copy of a host depth buffer
-    size_t depth_cap = 0;
+    StageBuf depth_stage;              // device copy of a host depth buffer
     float* dpyr = nullptr;             // depth-tested frames: the two tile-max pyramids of the opaque pass's depth (k_cluster.h), by
     size_t dpyr_cap = 0;               // frame parity: [par][which], dpyr_cap floats each
     uint32_t* dactive = nullptr;       // [2] by parity: "some tile's largest depth is below 1" (something can be culled)
@@ -222,16 +202,11 @@ struct FrameSlot {
     unsigned long long* lazy_ctr = nullptr;   // [0] low word: redo count of the frame, [1]: colours evaluated (running)
     uint32_t* colour_evals = nullptr;         // [256] colours evaluated per super-tile list (this frame; folded into lazy_ctr[1])
     bool last_lazy = false;            // the last frame of this slot left colours pending
-    float* fb = nullptr;               // staging for host-pointer output: pixels of the context's target format (fb_cap counts floats)
-    size_t fb_cap = 0;
-    int fb_sig[6] = {-1, -1, -1, -1, -1, -1};   // the band shape (and target format) the staging buffer was last cleared for
-    float* aovb = nullptr;             // staging for a host-pointer AOV plane: two floats per band pixel (aovb_cap counts floats)
-    size_t aovb_cap = 0;
-    int aovb_sig[5] = {-1, -1, -1, -1, -1};     // the band shape the plane's staging buffer was last cleared for
+    StageBuf fb;                       // staging for host-pointer output: pixels of the context's target format; cleared per band shape and format
+    StageBuf aovb;                     // staging for a host-pointer AOV plane: two floats per band pixel; cleared per band shape
     float* fb32 = nullptr;             // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
     size_t fb32_cap = 0;
-    unsigned char* bgb = nullptr;      // device copy of a host background image (bgb_cap bytes): per slot, staged anew by every attempt of a frame
-    size_t bgb_cap = 0;
+    StageBuf bgb;                      // device copy of a host background image: per slot, staged anew by every attempt of a frame
     // small device/host mailboxes
     unsigned long long* counters = nullptr;  // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
                                              // scanned, [5] wave-record evaluations (running)
@@ -353,21 +328,6 @@ struct gsr_context {
     hipEvent_t up_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double up_t_begin = 0.0, up_h2d_ms = 0.0, up_quant_ms = 0.0;
 };
-
-template <typename T>
-static int dev_alloc(T** p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)));
-    return GSR_OK;
-}
-template <typename T>
-static void dev_free(T*& p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
@@ -498,9 +458,9 @@ static void slot_destroy(FrameSlot& sl)
     slot_free_splat_arrays(sl);
     dev_free(sl.hist); dev_free(sl.totals);
     dev_free(sl.pvA);
-    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); dev_free(sl.fb); dev_free(sl.fb32); dev_free(sl.aovb); dev_free(sl.bgb);
+    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); sl.fb.release(); dev_free(sl.fb32); sl.aovb.release(); sl.bgb.release();
     dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
-    if (sl.h_end) (void)hipHostFree(sl.h_end); dev_free(sl.depth_stage); dev_free(sl.dpyr); dev_free(sl.dactive);
+    if (sl.h_end) (void)hipHostFree(sl.h_end); sl.depth_stage.release(); dev_free(sl.dpyr); dev_free(sl.dactive);
     dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
     dev_free(sl.counters); dev_free(sl.d_n);
     if (sl.h_total) (void)hipHostFree(sl.h_total);
@@ -663,7 +623,7 @@ extern "C" int gsr_set_target_format(gsr_context* c, int format)
     if (rc) return rc;
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) {   // the staging images are laid out for the old pixel size
         FrameSlot& sl = c->slot[k];
-        dev_free(sl.fb); sl.fb_cap = 0; std::memset(sl.fb_sig, 0xff, sizeof sl.fb_sig);
+        sl.fb.release();
         dev_free(sl.fb32); sl.fb32_cap = 0;
     }
     c->target_format = format;
@@ -1544,106 +1504,107 @@ static GsrRangeArgs range_args(gsr_context* c, FrameSlot& sl)
     return a;
 }
 
+// what the frame driver's caches are keyed by: the tile geometry of a frame (the horizons': this, and the geometry generation behind it)
+static inline void tile_sig(const GsrFrame& f, int* sig /* [6] */)
+{
+    const int now[6] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift};
+    std::memcpy(sig, now, sizeof now);
+}
+
+static inline int32_t list_cap(const FrameSlot& sl) { return (int32_t)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff); }
+
+static GsrSumArgs sum_args(const FrameJob& j)
+{
+    GsrSumArgs g;
+    g.n_tiles = j.local_tiles; g.tiles_x = j.f.tiles_x; g.tiles_y = j.f.tiles_y; g.shard = GsrShard{j.f.shard_index, j.f.shard_count, j.f.shard_rpb};
+    g.super_shift = j.f.super_shift; g.stiles_x = j.f.stiles_x; g.n_super = j.n_super;
+    return g;
+}
+
+// what every kernel that forms horizons needs of the frame (k_tile_pass, k_slab_mid): its lists, the positions, the camera, the pyramid's layout
+static GsrHorizonArgs horizon_args(const gsr_context* c, const FrameSlot& sl)
+{
+    const GsrFrame& f = sl.job.f;
+    GsrHorizonArgs hz{};
+    hz.list_cap = list_cap(sl); hz.lists = sl.pvA; hz.geoA = c->geoA; hz.idx_mask = f.idx_mask;
+    for (int l = 0; l < GSR_PYR_LEVELS; ++l) hz.pyr_off[l] = f.pyr_off[l];
+    hz.cam[0] = f.cam[0]; hz.cam[1] = f.cam[1]; hz.cam[2] = f.cam[2];
+    return hz;
+}
+
 // the compositing launch (+ the lazy-colour fallback behind it)
 static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guarded)
 {
     const FrameJob& j = sl.job;
     const GsrFrame& f = j.f;
     hipStream_t s = sl.stream;
-    if (j.local_tiles > 0) {
-        if (!j.direct) HIP_TRY(hipStreamWaitEvent(s, sl.ev_user, 0));
-        GsrBlendArgs a;
-        a.guard = guarded ? sl.dactive + j.dpar : (const uint32_t*)nullptr; a.guard_want = 0u;
-        {   // (a perspective projection -- clip w = -view z, clip z = a z + b: window depth = (1 - a) / 2 - beta / view depth)
-            const bool persp = f.pr[8] == 0.0f && f.pr[9] == 0.0f && f.pr[12] == 0.0f && f.pr[13] == 0.0f && f.pr[14] == -1.0f && f.pr[15] == 0.0f;
-            a.near_alpha = persp ? 0.5f * (1.0f - f.pr[10]) : 0.0f;
-            a.near_scale = persp ? 1.12f : 0.0f;
-        }
-        a.tile_cov = (with_depth && j.dcull && !j.dblind) ? sl.dpyr + 4 * sl.dpyr_cap : (const float*)nullptr;
-        a.idx_mask = f.idx_mask; a.zq0 = f.zq0; a.zqs = f.zqs;
-        a.tile_dmax = (with_depth && j.dcull && !j.dblind && f.idx_mask != 0xffffffffu) ? sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap + f.pyr_off[0] : (const float*)nullptr;
-        a.width = f.width; a.height = f.height; a.tiles_x = f.tiles_x; a.local_tiles = j.local_tiles;
-        a.shard = GsrShard{f.shard_index, f.shard_count, f.shard_rpb}; a.band_rows = j.band_rows;
-        a.super_shift = f.super_shift; a.rect_shift = f.rect_shift; a.stiles_x = f.stiles_x; a.use_map = j.use_map ? 1 : 0; a.flags = f.flags;
-        a.list_cap = (int32_t)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff);
-        a.sup_work = (a.use_map && c->opt_swizzle >= 2 && sl.sup_work) ? sl.sup_work + 256 * sl.sup_par : nullptr;
-        a.slab = j.phase; a.tbuf = sl.tbuf; a.tile_work_a = sl.tile_work_a;
-        uint4* const tw = j.phase == 1 ? sl.tile_work_a : sl.tile_work;   // (phase 1's bookkeeping is kept for phase 2 and the frame end)
-        // heaviest-first table of this slot's previous frame, if that frame had the same tiles
-        const int sig[6] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift};
-        const bool ordered = a.use_map && c->opt_swizzle >= 2 && sl.order_valid && std::memcmp(sig, sl.order_sig, sizeof sig) == 0;
-        const int32_t* tmap = ordered ? sl.order : c->tile_map;
-        const unsigned grid = ordered ? (unsigned)(8 * sl.order_per_xcd) : a.use_map ? (unsigned)c->map_grid : (unsigned)j.local_tiles;
-        GsrLazyArgs lz;
-        lz.f = f; lz.colrow = c->colrow;
-        lz.redo = j.lazy ? sl.redo : nullptr;
-        lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
-        // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
-        // (a frame over a background is laid out like a packed one whatever its format: the composited pixel goes to the target, the raw one
-        //  of a front slab's phase 1 to the slot's own buffer -- phase 2 must never continue from a composited pixel)
-        const bool over = j.bg.kind != 0;
-        a.out_format = j.format; a.out_packed = (j.format != GSR_TARGET_RGBA32F || over) ? (void*)j.target : nullptr;
-        float4* tgt = reinterpret_cast<float4*>((j.format != GSR_TARGET_RGBA32F || over) ? sl.fb32 : j.target);
-        // Host-target frames (a caller without GL interop): the frame's LAST blend launch is issued band by band of tile rows, an event
-        // behind each, and queue_frame_end copies a band's rows back on a second stream as soon as its event fires: all but the first
-        // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
-        // The launches walk the same tile table; a workgroup of another band's tile leaves at once (~3 us per extra launch).
-        int nb = 1;
-        if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
-        if (nb > 1 && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; nb = 1; (void)hipGetLastError(); }
-        for (int b = 0; b < nb && nb > 1; ++b)
-            if (!sl.ev_band[b] && hipEventCreateWithFlags(&sl.ev_band[b], hipEventDisableTiming) != hipSuccess) { sl.ev_band[b] = nullptr; nb = 1; (void)hipGetLastError(); }
-        sl.bands = nb;
-        for (int b = 0; b < nb; ++b) {
-            a.row_lo = nb > 1 ? (int)((int64_t)f.local_tiles_y * b / nb) : 0;
-            a.row_hi = nb > 1 ? (int)((int64_t)f.local_tiles_y * (b + 1) / nb) : 0x7fffffff;
-            sl.band_row[b] = a.row_lo; sl.band_row[b + 1] = nb > 1 ? a.row_hi : f.local_tiles_y;
-            if (j.aov_target) {   // the depth AOV: the same walk, the plane behind the colour (k_blend.h: k_blend_aov)
-                if (with_depth)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.aov_target);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.aov_target);
-            } else if (over) {   // a background: the same walk, the composite in the epilogue (k_blend.h: k_blend_over)
-                if (with_depth)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.bg);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                       sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz, j.bg);
-            } else if (with_depth)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend<true>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                   sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend<false>), dim3(grid), dim3(256), 0, s, a, tmap, sl.pvA, sl.sstart,
-                                   sl.send, sl.rec, tgt, tw, sl.zwin, j.d_depth, lz);
-            if (j.lazy && j.aov_target) {
-                if (with_depth)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.aov_target);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_aov_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.aov_target);
-            } else if (j.lazy && over) {
-                if (with_depth)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.bg);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_over_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz, j.bg);
-            } else if (j.lazy) {   // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
-                if (with_depth)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_lazy<true>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_blend_lazy<false>), dim3((unsigned)j.local_tiles), dim3(256), 0, s, a, c->tile_map,
-                                       sl.pvA, sl.sstart, sl.send, sl.rec, tgt, sl.tile_work, sl.zwin, j.d_depth, lz);
-            }
-            if (nb > 1) HIP_TRY(hipEventRecord(sl.ev_band[b], s));
-        }
-        HIP_TRY(hipGetLastError());
+    if (j.local_tiles <= 0) return GSR_OK;
+    if (!j.direct) HIP_TRY(hipStreamWaitEvent(s, sl.ev_user, 0));
+    GsrBlendArgs a;
+    a.guard = guarded ? sl.dactive + j.dpar : (const uint32_t*)nullptr; a.guard_want = 0u;
+    {   // (a perspective projection -- clip w = -view z, clip z = a z + b: window depth = (1 - a) / 2 - beta / view depth)
+        const bool persp = f.pr[8] == 0.0f && f.pr[9] == 0.0f && f.pr[12] == 0.0f && f.pr[13] == 0.0f && f.pr[14] == -1.0f && f.pr[15] == 0.0f;
+        a.near_alpha = persp ? 0.5f * (1.0f - f.pr[10]) : 0.0f;
+        a.near_scale = persp ? 1.12f : 0.0f;
     }
+    a.tile_cov = (with_depth && j.dcull && !j.dblind) ? sl.dpyr + 4 * sl.dpyr_cap : (const float*)nullptr;
+    a.idx_mask = f.idx_mask; a.zq0 = f.zq0; a.zqs = f.zqs;
+    a.tile_dmax = (with_depth && j.dcull && !j.dblind && f.idx_mask != 0xffffffffu) ? sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap + f.pyr_off[0] : (const float*)nullptr;
+    a.width = f.width; a.height = f.height; a.tiles_x = f.tiles_x; a.local_tiles = j.local_tiles;
+    a.shard = GsrShard{f.shard_index, f.shard_count, f.shard_rpb}; a.band_rows = j.band_rows;
+    a.super_shift = f.super_shift; a.rect_shift = f.rect_shift; a.stiles_x = f.stiles_x; a.use_map = j.use_map ? 1 : 0; a.flags = f.flags;
+    a.list_cap = list_cap(sl);
+    a.sup_work = (a.use_map && c->opt_swizzle >= 2 && sl.sup_work) ? sl.sup_work + 256 * sl.sup_par : nullptr;
+    a.slab = j.phase; a.tbuf = sl.tbuf; a.tile_work_a = sl.tile_work_a;
+    uint4* const tw = j.phase == 1 ? sl.tile_work_a : sl.tile_work;   // (phase 1's bookkeeping is kept for phase 2 and the frame end)
+    // heaviest-first table of this slot's previous frame, if that frame had the same tiles
+    int sig[6];
+    tile_sig(f, sig);
+    const bool ordered = a.use_map && c->opt_swizzle >= 2 && sl.order_valid && std::memcmp(sig, sl.order_sig, sizeof sig) == 0;
+    const int32_t* tmap = ordered ? sl.order : c->tile_map;
+    const unsigned grid = ordered ? (unsigned)(8 * sl.order_per_xcd) : a.use_map ? (unsigned)c->map_grid : (unsigned)j.local_tiles;
+    GsrLazyArgs lz;
+    lz.f = f; lz.colrow = c->colrow;
+    lz.redo = j.lazy ? sl.redo : nullptr;
+    lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
+    // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
+    // (a frame over a background is laid out like a packed one whatever its format: the composited pixel goes to the target, the raw one
+    //  of a front slab's phase 1 to the slot's own buffer -- phase 2 must never continue from a composited pixel)
+    const bool over = j.bg.kind != 0;
+    a.out_format = j.format; a.out_packed = (j.format != GSR_TARGET_RGBA32F || over) ? (void*)j.target : nullptr;
+    float4* tgt = reinterpret_cast<float4*>((j.format != GSR_TARGET_RGBA32F || over) ? sl.fb32 : j.target);
+    // One launch of the blend family: every member takes the same arguments up to the lazy-colour block; the AOV kernels take the
+    // plane behind them (k_blend.h: k_blend_aov), the background kernels what the frame is composited over (k_blend_over)
+    auto launch = [&](auto kernel, unsigned g, const int32_t* map, uint4* work, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, a, map, sl.pvA, sl.sstart, sl.send, sl.rec, tgt, work, sl.zwin, j.d_depth, lz, tail...);
+    };
+    auto launch_verb = [&](auto plain, auto aov, auto bg, unsigned g, const int32_t* map, uint4* work) {
+        if (j.aov_target) launch(aov, g, map, work, j.aov_target);
+        else if (over) launch(bg, g, map, work, j.bg);
+        else launch(plain, g, map, work);
+    };
+    // Host-target frames (a caller without GL interop): the frame's LAST blend launch is issued band by band of tile rows, an event
+    // behind each, and queue_frame_end copies a band's rows back on a second stream as soon as its event fires: all but the first
+    // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
+    // The launches walk the same tile table; a workgroup of another band's tile leaves at once (~3 us per extra launch).
+    int nb = 1;
+    if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
+    if (nb > 1 && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; nb = 1; (void)hipGetLastError(); }
+    for (int b = 0; b < nb && nb > 1; ++b)
+        if (!sl.ev_band[b] && hipEventCreateWithFlags(&sl.ev_band[b], hipEventDisableTiming) != hipSuccess) { sl.ev_band[b] = nullptr; nb = 1; (void)hipGetLastError(); }
+    sl.bands = nb;
+    for (int b = 0; b < nb; ++b) {
+        a.row_lo = nb > 1 ? (int)((int64_t)f.local_tiles_y * b / nb) : 0;
+        a.row_hi = nb > 1 ? (int)((int64_t)f.local_tiles_y * (b + 1) / nb) : 0x7fffffff;
+        sl.band_row[b] = a.row_lo; sl.band_row[b + 1] = nb > 1 ? a.row_hi : f.local_tiles_y;
+        if (with_depth) launch_verb(k_blend<true>, k_blend_aov<true>, k_blend_over<true>, grid, tmap, tw);
+        else launch_verb(k_blend<false>, k_blend_aov<false>, k_blend_over<false>, grid, tmap, tw);
+        // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
+        if (j.lazy && with_depth) launch_verb(k_blend_lazy<true>, k_blend_aov_lazy<true>, k_blend_over_lazy<true>, (unsigned)j.local_tiles, c->tile_map, sl.tile_work);
+        else if (j.lazy) launch_verb(k_blend_lazy<false>, k_blend_aov_lazy<false>, k_blend_over_lazy<false>, (unsigned)j.local_tiles, c->tile_map, sl.tile_work);
+        if (nb > 1) HIP_TRY(hipEventRecord(sl.ev_band[b], s));
+    }
+    HIP_TRY(hipGetLastError());
     return GSR_OK;
 }
 
@@ -1675,7 +1636,7 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
         const bool predict = c->prefix_valid && !(f.flags & GSR_FLAG_LAZY_NO_PREFIX);
         hipLaunchKernelGGL(k_colour_prefix, dim3((unsigned)(j.n_super * CL_BLOCKS_PER_LIST)), dim3(CL_THREADS), 0, s, f, sl.pvA,
                            sl.sstart, sl.send, (f.flags & GSR_FLAG_LAZY_NO_PREFIX) ? c->prefix_none : (predict ? c->prefix : c->prefix_all),
-                           (int)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff), c->colrow, sl.rec, sl.colour_evals);
+                           (int)list_cap(sl), c->colrow, sl.rec, sl.colour_evals);
         HIP_TRY(hipGetLastError());
     }
     if ((rc = mark(sl, 5))) return rc;
@@ -1694,25 +1655,21 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
 {
     const FrameJob& j = sl.job;
     hipStream_t s = sl.stream;
-    GsrSumArgs g;
-    g.n_tiles = j.local_tiles; g.tiles_x = j.f.tiles_x; g.tiles_y = j.f.tiles_y; g.shard = GsrShard{j.f.shard_index, j.f.shard_count, j.f.shard_rpb};
-    g.super_shift = j.f.super_shift; g.stiles_x = j.f.stiles_x; g.n_super = j.n_super;
+    const GsrSumArgs g = sum_args(j);
     GsrHorizonArgs hz{};
-    hz.list_cap = (int32_t)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff);
+    hz.list_cap = list_cap(sl);
     // (below a few hundred thousand splats in the sort the frame is bound by launch floors: nothing for culling to win)
     // ... and while culling is held off nobody needs horizons: they are prepared again two frames before it may resume.
     // A deferred frame (handed over before its pair count was known) never culls and may have clamped lists: no horizons from it.
     if (c->opt_cull && c->opt_cull != 3 && j.n > 0 && !j.deferred && (c->opt_cull >= 2 || j.cull || j.phase == 2 || (c->cull_pol.vis_unculled >= 300000u && c->cull_pol.holdoff <= 2))) {
-        hz.raw = sl.hraw; hz.pyr_in = sl.hpyr; hz.pyr_out = sl.hpyr_next; hz.dilate = j.f.cull_dilate; hz.culled = j.cull ? 1 : 0; hz.lists = sl.pvA; hz.geoA = c->geoA;
-        for (int l = 0; l < GSR_PYR_LEVELS; ++l) hz.pyr_off[l] = j.f.pyr_off[l];
-        hz.cam[0] = j.f.cam[0]; hz.cam[1] = j.f.cam[1]; hz.cam[2] = j.f.cam[2];
+        hz = horizon_args(c, sl);
+        hz.raw = sl.hraw; hz.pyr_in = sl.hpyr; hz.pyr_out = sl.hpyr_next; hz.dilate = j.f.cull_dilate; hz.culled = j.cull ? 1 : 0;
         hz.host_end = j.cull ? sl.h_end_dev : nullptr; hz.ticket = j.ticket;
         // (depth-tested frames leave, and culled ones check, the tiles' status: k_blend.h.  A frame without a depth buffer leaves every
         //  tile classic: the sign bits of its raw horizons are clear)
         hz.stat = sl.hstat;
         hz.stat_in_use = (j.cull && j.dcull && j.dstat) ? 1 : 0;
         hz.depth_culled = (j.dcull && !j.dblind) ? 1 : 0;
-        hz.idx_mask = j.f.idx_mask;
         static const bool dbgv = std::getenv("GSR_DEBUG_VIOL") != nullptr;
         if (dbgv) {
             if (!sl.dbg_viol && hipMalloc(reinterpret_cast<void**>(&sl.dbg_viol), 80 * 4) != hipSuccess) sl.dbg_viol = nullptr;
@@ -1731,7 +1688,8 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     // The heaviest-first table is rebuilt every frame where the tiles differ a lot (k_sum_work's verdict); where they do not it is
     // still worth a few microseconds of k_blend's tail (C4: 0.142 -> 0.139 ms), but not the 10 us of k_tile_order every frame:
     // then a table stands for GSR_ORDER_KEEP frames of the same shape.
-    const int osig[6] = {j.f.width, j.f.height, j.f.shard_index, j.f.shard_count, j.f.shard_rpb, j.f.super_shift};
+    int osig[6];
+    tile_sig(j.f, osig);
     const bool order_due = c->opt_swizzle >= 3 || (c->opt_swizzle == 2 && c->order_pays);
     const bool order_kept = !order_due && c->opt_swizzle == 2 && c->opt_order_keep > 0 && sl.order_valid && sl.order_age < c->opt_order_keep &&
                             std::memcmp(osig, sl.order_sig, sizeof osig) == 0;
@@ -1739,16 +1697,9 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     if (order_kept) sl.order_age += 1; else sl.order_valid = false;
     const bool order_now = j.use_map && (order_due || order_refresh) && j.local_tiles > 0 && j.n_super <= 256 && sl.sup_work;
     const int per_xcd = 2 * ((j.n_super + 15) / 16) << (2 * j.f.super_shift);
-    if (order_now) {
-        const size_t want = (size_t)8 * per_xcd;
-        if (want > sl.order_cap) {
-            HIP_TRY(hipStreamSynchronize(s));
-            dev_free(sl.order);
-            sl.order_cap = 0;
-            int rc = dev_alloc(&sl.order, want);
-            if (rc) return rc;
-            sl.order_cap = want;
-        }
+    if (order_now && (size_t)8 * per_xcd > sl.order_cap) {
+        const int rc = regrow(s, sl.order, sl.order_cap, (size_t)8 * per_xcd, (size_t)8 * per_xcd);
+        if (rc) return rc;
     }
     // the next frame's tile order is built BESIDE the frame's sums (and the horizon dilation), in the same launch (k_blend.h: k_frame_end_order)
     const bool fused_order = order_now && c->opt_fuse_order != 0;
@@ -1772,8 +1723,8 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     }
     if (sl.horizon_valid) {
         std::swap(sl.hpyr, sl.hpyr_next);      // (what the slot's next frame culls against)
-        const int sig[7] = {j.f.width, j.f.height, j.f.shard_index, j.f.shard_count, j.f.shard_rpb, j.f.super_shift, (int)c->geo_gen};
-        std::memcpy(sl.horizon_sig, sig, sizeof sig);
+        tile_sig(j.f, sl.horizon_sig);
+        sl.horizon_sig[6] = (int)c->geo_gen;
         sl.horizon_cam = j.args.cam;
     }
     if (order_now) {
@@ -1801,16 +1752,14 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
                 if (r1 <= r0) continue;
                 const size_t off = r0 * (size_t)j.f.width * bpp;
                 HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.ev_band[b], 0));
-                HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, reinterpret_cast<const char*>(sl.fb) + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
+                HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, static_cast<const char*>(sl.fb.p) + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
             }
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
-            if (j.aov_target) HIP_TRY(hipMemcpyAsync(j.args.aov_out, sl.aovb, j.out_px * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
         } else {
-            HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb, j.out_px * bpp, hipMemcpyDeviceToHost, s));
-            if (j.aov_target) HIP_TRY(hipMemcpyAsync(j.args.aov_out, sl.aovb, j.out_px * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(hipMemcpyAsync(j.args.out, sl.fb.p, j.out_px * bpp, hipMemcpyDeviceToHost, s));
         }
+        if (j.aov_target) HIP_TRY(hipMemcpyAsync(j.args.aov_out, sl.aovb.p, j.out_px * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
     }
     // results are ordered on the public stream: anything the caller queues there next sees this frame
     if (!j.direct) {
@@ -1826,15 +1775,9 @@ static int queue_slab_mid(gsr_context* c, FrameSlot& sl)
 {
     const FrameJob& j = sl.job;
     hipStream_t s = sl.stream;
-    GsrSumArgs g;
-    g.n_tiles = j.local_tiles; g.tiles_x = j.f.tiles_x; g.tiles_y = j.f.tiles_y; g.shard = GsrShard{j.f.shard_index, j.f.shard_count, j.f.shard_rpb};
-    g.super_shift = j.f.super_shift; g.stiles_x = j.f.stiles_x; g.n_super = j.n_super;
-    GsrHorizonArgs hz{};
-    hz.list_cap = (int32_t)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff);
+    const GsrSumArgs g = sum_args(j);
+    GsrHorizonArgs hz = horizon_args(c, sl);
     hz.raw = (c->opt_cull && c->opt_cull != 3) ? sl.hraw : nullptr;          // the finished tiles' horizons for the slot's NEXT frame
-    hz.lists = sl.pvA; hz.geoA = c->geoA; hz.idx_mask = j.f.idx_mask;
-    for (int l = 0; l < GSR_PYR_LEVELS; ++l) hz.pyr_off[l] = j.f.pyr_off[l];
-    hz.cam[0] = j.f.cam[0]; hz.cam[1] = j.f.cam[1]; hz.cam[2] = j.f.cam[2];
     const int nblocks8 = ((j.f.tiles_x + 7) >> 3) * ((j.f.tiles_y + 7) >> 3);
     hipLaunchKernelGGL(k_slab_mid, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tile_work_a, g, sl.sstart, sl.send, hz, sl.hpyr2,
                        sl.slab + GSR_SLAB_BINS, j.f.key_min);
@@ -1890,7 +1833,6 @@ static bool camera_jumped(const gsr_context* c, const gsr_camera& was, const gsr
     const double near2 = diag2 / 16.0;                              // reference points closer than a quarter of the diagonal say nothing
     const double focal_px = 0.5 * std::fabs((double)now.proj[0]) * now.width;
     const double max_px = 24.0 * GSR_TILE_PX;
-    int used = 0;
     for (int k = 0; k < 9; ++k) {
         double p[3], va[3], vb[3], da2 = 0.0, db2 = 0.0;
         for (int a = 0; a < 3; ++a) p[a] = k < 8 ? (((k >> a) & 1) ? c->bb_hi[a] : c->bb_lo[a]) : 0.5 * ((double)c->bb_lo[a] + c->bb_hi[a]);
@@ -1900,32 +1842,17 @@ static bool camera_jumped(const gsr_context* c, const gsr_camera& was, const gsr
             da2 += va[r] * va[r]; db2 += vb[r] * vb[r];
         }
         if (!(da2 > near2) || !(db2 > near2) || !std::isfinite(da2) || !std::isfinite(db2)) continue;
-        ++used;
         const double ratio2 = db2 / da2;
         if (ratio2 > 1.25 * 1.25 || ratio2 < 0.8 * 0.8) return true;
         const double cosang = (va[0] * vb[0] + va[1] * vb[1] + va[2] * vb[2]) / std::sqrt(da2 * db2);
         const double ang = std::acos(std::min(1.0, std::max(-1.0, cosang)));
         if (ang * focal_px > max_px) return true;
     }
-    (void)used;
     return false;
 }
 
 static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, bool allow_cull, int phase_in = 0);
 static int frame_finish(gsr_context* c, FrameSlot& sl);
-
-// a slot buffer too small for this frame: drain what may still read the old one, then replace it (count elements; cap = the new capacity)
-template <typename T>
-static int regrow(hipStream_t s, T*& p, size_t& cap, size_t count, size_t new_cap)
-{
-    HIP_TRY(hipStreamSynchronize(s));
-    dev_free(p);
-    cap = 0;
-    const int rc = dev_alloc(&p, count);
-    if (rc) return rc;
-    cap = new_cap;
-    return GSR_OK;
-}
 
 // An attempt that is not handed over: its order is not cached, and the work sums its speculative back end added over its lists are
 // cleared (k_tile_order reads them).  redo: frame_check renders the frame again, as it is.
@@ -2102,23 +2029,35 @@ static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f, int
     return GSR_OK;
 }
 
-static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, bool allow_cull, int phase_in /* 2 = the second phase of a front-slab frame */)
+// ---- frame_begin, stage by stage ----
+// What crosses the stage boundaries: the frame's plan and the launch arguments more than one stage needs.  Lives on frame_begin's stack.
+struct FrontEnd {
+    GsrFramePlan p;
+    bool pos_match = false;            // the position-keyed order is this frame's (plan_frame; queue_pos_order drops or builds it otherwise)
+    SortKey key_now;                   // what this frame's depth order is cached under (queue_sort)
+    int rounds = 0; uint32_t ngroups = 0;   // the cull grid: rounds per workgroup and workgroups of k_cluster_cull, whose segments K1 walks
+    int hist_shift = 0;                // front-slab frames: key bits dropped by the slab histogram
+    GsrDepthPyrArgs dp{};              // depth-tested frames: the pyramid pass ...
+    uint32_t n_dp = 0;                 // ... its detection workgroups in front of k_cluster_cull's (0: none in this launch)
+    GsrDepthCull dc_clus{nullptr, nullptr, nullptr}, dc_k1{nullptr, nullptr, nullptr};   // ... and what the cluster pass and K1 cull against
+    GsrK1Scatter scat{};               // the small-frame sort's bucket pass inside K1
+};
+
+// argument checks, the slot and its stream, the slot's previous frame finished, the job and its derived sizes
+static int frame_open(gsr_context* c, const FrameArgs& a, FrameSlot*& slot)
 {
     const gsr_camera* cam = &a.cam;
     if (c->uploading) return set_err(GSR_E_INVALID, "gsr_render: upload in progress");
     if (cam->width <= 0 || cam->height <= 0 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM)
         return set_err(GSR_E_INVALID, "gsr_render: bad framebuffer size %dx%d (max %d)", cam->width, cam->height, GSR_MAX_DIM);
     if (!c->has_geometry) return set_err(GSR_E_NO_GEOMETRY, "gsr_render: nothing uploaded");
-#ifdef GSR_HOST_TIMING
-    const double t_enter = now_us();
-#endif
     HIP_TRY(hipSetDevice(c->device));
 
     // Frames alternate between the slots.  Everything up to the blend kernel touches only the slot's
     // private arrays (plus the read-only geometry), so it may run while the previous frame -- and
     // whatever the caller queued on the public stream -- is still executing.
     FrameSlot& sl = c->slot[c->frame_no % (uint64_t)c->nslots];
-    if (used) *used = &sl;
+    slot = &sl;
     int rc = frame_finish(c, sl);   // a deferred frame of this slot: look at its pair count now
     if (rc) return rc;
     // strictly serial frames run on the public stream itself: nothing to hand over, no events; with two frames in flight a
@@ -2128,30 +2067,35 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         HIP_TRY(hipStreamSynchronize(sl.stream));
         sl.stream = want;
     }
-    hipStream_t s = sl.stream;
-    if (sl.pair_cap > 0 && sl.pair_cap < c->pair_want) {   // the other slot met a frame that outgrew this size
-        if ((rc = regrow(s, sl.pvA, sl.pair_cap, c->pair_want + 4, c->pair_want))) return rc;
-    }
+    // (the other slot met a frame that outgrew this slot's list buffer)
+    if (sl.pair_cap > 0 && sl.pair_cap < c->pair_want && (rc = regrow(sl.stream, sl.pvA, sl.pair_cap, c->pair_want + 4, c->pair_want))) return rc;
 
     FrameJob& j = sl.job;
     j = FrameJob();
     j.args = a;
     build_frame(c, cam, &j.f);
-    const GsrFrame& f = j.f;
-    const uint32_t n = c->n;
-    j.n = n;
-    j.local_tiles = f.tiles_x * f.local_tiles_y;
+    j.n = c->n;
+    j.local_tiles = j.f.tiles_x * j.f.local_tiles_y;
     j.band_rows = (c->shard_count > 1) ? gsr_band_rows(cam->height, c->shard_index, c->shard_count) : cam->height;
     j.out_px = (size_t)j.band_rows * cam->width;
-    j.n_super = f.stiles_x * f.stiles_y;
+    j.n_super = j.f.stiles_x * j.f.stiles_y;
     j.use_map = c->opt_swizzle != 0;
+    return GSR_OK;
+}
 
-    // the frame's regime (gsr_frame_plan.h: the policies' per-frame events happen in there)
-    const SortKey key_now = {c->geo_gen, c->shard_index, c->shard_count, c->shard_layout, c->opt_flags, *cam};
-    const int sig[7] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift, (int)c->geo_gen};
+// the frame's regime (gsr_frame_plan.h: the policies' per-frame events happen in there), the frame counters, the ticket
+static void plan_frame(gsr_context* c, FrameSlot& sl, FrontEnd& fe, bool allow_cull, int phase_in)
+{
+    FrameJob& j = sl.job;
+    const FrameArgs& a = j.args;
+    const gsr_camera* cam = &a.cam;
+    const GsrFrame& f = j.f;
+    fe.key_now = SortKey{c->geo_gen, c->shard_index, c->shard_count, c->shard_layout, c->opt_flags, *cam};
+    int sig[7] = {0, 0, 0, 0, 0, 0, (int)c->geo_gen};
+    tile_sig(f, sig);
     GsrPlanIn in;
     in.phase_in = phase_in; in.allow_cull = allow_cull; in.out_is_device = a.out_is_device; in.has_depth = a.depth != nullptr;
-    in.n = n; in.nclus = c->nclus; in.sh_order = f.sh_order; in.key_min = f.key_min; in.key_max = f.key_max;
+    in.n = j.n; in.nclus = c->nclus; in.sh_order = f.sh_order; in.key_min = f.key_min; in.key_max = f.key_max;
     in.opt_deferred = c->opt_deferred; in.opt_lazy = c->opt_lazy; in.opt_cull = c->opt_cull; in.opt_slab = c->opt_slab; in.opt_cluster = c->opt_cluster;
     in.opt_sort_cache = c->opt_sort_cache; in.opt_local_sort = c->opt_local_sort; in.opt_k1_scatter = c->opt_k1_scatter;
     in.opt_scatter_direct = c->opt_scatter_direct; in.opt_mid_sort = c->opt_mid_sort; in.opt_bn_items = c->opt_bn_items;
@@ -2162,14 +2106,15 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     in.lazy_pays = c->lazy_pays; in.prefix_cheaper = c->prefix_cheaper; in.prefix_valid = c->prefix_valid; in.bbox_ok = c->bbox_ok;
     in.horizon_match = sl.horizon_valid && std::memcmp(sig, sl.horizon_sig, sizeof sig) == 0;
     in.hpyr_re = sl.hpyr_re;
-    in.sort_match = sl.sort_valid && sl.sort_key.same(key_now);
+    in.sort_match = sl.sort_valid && sl.sort_key.same(fe.key_now);
     in.sorted_culled = sl.sorted_culled; in.sorted_dculled = sl.sorted_dculled;
     in.pos_match = c->pos_valid && c->pos_gen == c->geo_gen && std::memcmp(c->pos_cam, cam->cam_pos, sizeof c->pos_cam) == 0 &&
                    c->pos_kmin == f.key_min && c->pos_kmax == f.key_max;
     in.same_pos = c->last_cam_set && std::memcmp(c->last_cam, cam->cam_pos, sizeof c->last_cam) == 0;
     in.hints = sl.hints;
-    const GsrFramePlan p = gsr_plan_frame(in, c->cull_pol, c->slab_pol, sl.local_pol, c->classic_once,
-                                          [&] { return camera_jumped(c, sl.horizon_cam, *cam); });
+    fe.pos_match = in.pos_match;
+    fe.p = gsr_plan_frame(in, c->cull_pol, c->slab_pol, sl.local_pol, c->classic_once, [&] { return camera_jumped(c, sl.horizon_cam, *cam); });
+    const GsrFramePlan& p = fe.p;
     j.deferred = p.deferred; j.lazy = p.lazy; j.cull = p.cull; j.phase = p.phase; j.timing = p.timing; j.timing_all = p.timing_all;
     j.dcull = p.dcull; j.local_sort = p.local || p.local_phase; j.bn_items = p.bn_items; j.bn_grid = p.bn_grid; j.k1_grid = p.k1_grid;
     j.f.cull_dilate = p.cull_dilate;
@@ -2177,10 +2122,21 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     c->st.frames_jumped += p.jumped;
     c->st.frames_culled += p.cull;
     c->st.frames_slab += p.phase == 1;
-    c->st.frames_lazy += p.lazy && n > 0 && phase_in == 0;
+    c->st.frames_lazy += p.lazy && j.n > 0 && phase_in == 0;
     j.ticket = ++sl.ticket ? sl.ticket : ++sl.ticket;   // (never 0: the mailbox starts at 0)
     if (j.timing) harvest_slot(c, sl);
+}
 
+// Everything the frame's kernels need in place before any of them is queued: the slot's arrays sized for the frame, the caller's
+// host buffers staged (StageBuf), the targets chosen.  Errors return directly: nothing of the frame is in the stream yet.
+static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
+{
+    FrameJob& j = sl.job;
+    const FrameArgs& a = j.args;
+    const gsr_camera* cam = &a.cam;
+    const GsrFrame& f = j.f;
+    hipStream_t s = sl.stream;
+    int rc;
     // the caller's stream position now: the blend kernel (the only writer of caller-visible memory)
     // waits for it, so an output buffer that earlier work on the public stream still reads is safe
     j.direct = sl.stream == c->stream;
@@ -2200,10 +2156,8 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     if (j.use_map && (rc = build_tile_map(c, f))) return rc;
     j.d_depth = a.depth;
     if (a.depth && !a.depth_is_device) {
-        const size_t npx = (size_t)cam->width * cam->height;
-        if (npx > sl.depth_cap && (rc = regrow(s, sl.depth_stage, sl.depth_cap, npx, npx))) return rc;
-        HIP_TRY(hipMemcpyAsync(sl.depth_stage, a.depth, npx * 4, hipMemcpyHostToDevice, s));
-        j.d_depth = sl.depth_stage;
+        if ((rc = sl.depth_stage.upload(s, a.depth, (size_t)cam->width * cam->height * sizeof(float)))) return rc;
+        j.d_depth = static_cast<const float*>(sl.depth_stage.p);
     }
     // A background: the colour as it is; a device image read in place; a host image staged in the slot's own buffer like a host depth
     // buffer -- by EVERY attempt of the frame (a repair, a re-queue, a front slab's phase 2 come through here again with the caller's
@@ -2213,10 +2167,8 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         std::memcpy(j.bg.rgba, a.bg.rgba, sizeof j.bg.rgba);
         j.bg.image = a.bg.kind == GSR_BG_IMAGE ? a.bg.image : nullptr;
         if (a.bg.kind == GSR_BG_IMAGE && !a.bg.image_is_device) {
-            const size_t nbytes = (size_t)cam->width * cam->height * (size_t)gsr_format_pixel_bytes(a.bg.format);
-            if (nbytes > sl.bgb_cap && (rc = regrow(s, sl.bgb, sl.bgb_cap, nbytes, nbytes))) return rc;
-            HIP_TRY(hipMemcpyAsync(sl.bgb, a.bg.image, nbytes, hipMemcpyHostToDevice, s));
-            j.bg.image = sl.bgb;
+            if ((rc = sl.bgb.upload(s, a.bg.image, (size_t)cam->width * cam->height * (size_t)gsr_format_pixel_bytes(a.bg.format)))) return rc;
+            j.bg.image = sl.bgb.p;
         }
     }
     // Depth-tested frames: the tile-max pyramid of the opaque pass's depth (k_cluster.h), rebuilt every frame (the buffer's content is
@@ -2233,7 +2185,7 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
                 HIP_TRY(hipMemsetAsync(sl.dactive, 0, 2 * sizeof(uint32_t), s));   // (on the frame's stream: a null-stream memset is not ordered against it)
             }
         }
-        if (phase_in != 2) sl.dpar ^= 1;
+        if (j.phase != 2) sl.dpar ^= 1;
         j.dpar = sl.dpar;
     }
     j.target = a.out;
@@ -2242,223 +2194,224 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     // (a packed target, front-slab frame: phase 2 continues from phase 1's f32 pixels, kept in a buffer of the slot's own)
     // (... and so does a frame over a background in any format: the target holds composited pixels)
     if ((j.format != GSR_TARGET_RGBA32F || a.bg.kind != 0) && j.phase == 1 && j.out_px * 4 > sl.fb32_cap && (rc = regrow(s, sl.fb32, sl.fb32_cap, j.out_px * 4, j.out_px * 4))) return rc;
+    // Host targets: the band is composited into the slot's staging image -- and plane, with the depth AOV -- and copied back by
+    // queue_frame_end.  Padding rows read as zeros (StageBuf): the image is cleared per band shape and format, the plane per band shape.
+    int band[6];
+    tile_sig(f, band);
     if (!a.out_is_device) {
-        const size_t fb_floats = j.out_px * bpp / 4;
-        if (fb_floats > sl.fb_cap) {
-            if ((rc = regrow(s, sl.fb, sl.fb_cap, fb_floats, fb_floats))) return rc;
-            std::memset(sl.fb_sig, 0xff, sizeof sl.fb_sig);
-        }
-        // A sharded context's band image is padded (gsr_band_rows): the pixel rows behind the rank's last image row are never
-        // written.  In the library's own staging buffer they read as zeros: it is cleared whenever the band's shape changes.
-        const int fsig[6] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, j.format};
-        if (std::memcmp(fsig, sl.fb_sig, sizeof fsig) != 0) {
-            HIP_TRY(hipMemsetAsync(sl.fb, 0, j.out_px * bpp, s));
-            std::memcpy(sl.fb_sig, fsig, sizeof fsig);
-        }
-        j.target = sl.fb;
+        band[5] = j.format;
+        if ((rc = sl.fb.ensure(s, j.out_px * bpp)) || (rc = sl.fb.clear_if_reshaped(s, band, j.out_px * bpp))) return rc;
+        j.target = static_cast<float*>(sl.fb.p);
     }
-    // The depth AOV's plane: the caller's device buffer, or -- a host buffer -- a staging plane of the slot's own, cleared like the
-    // staging image whenever the band's shape changes (the padding rows of a sharded context's band plane read as zeros)
     if (a.aov != 0 && a.aov_out != nullptr) {
         j.aov_target = reinterpret_cast<float2*>(a.aov_out);
         if (!a.out_is_device) {
-            if (j.out_px * 2 > sl.aovb_cap) {
-                if ((rc = regrow(s, sl.aovb, sl.aovb_cap, j.out_px * 2, j.out_px * 2))) return rc;
-                std::memset(sl.aovb_sig, 0xff, sizeof sl.aovb_sig);
-            }
-            const int asig[5] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb};
-            if (std::memcmp(asig, sl.aovb_sig, sizeof asig) != 0) {
-                HIP_TRY(hipMemsetAsync(sl.aovb, 0, j.out_px * 8, s));
-                std::memcpy(sl.aovb_sig, asig, sizeof asig);
-            }
-            j.aov_target = reinterpret_cast<float2*>(sl.aovb);
+            band[5] = 0;
+            if ((rc = sl.aovb.ensure(s, j.out_px * sizeof(float2))) || (rc = sl.aovb.clear_if_reshaped(s, band, j.out_px * sizeof(float2)))) return rc;
+            j.aov_target = static_cast<float2*>(sl.aovb.p);
         }
     }
+    return GSR_OK;
+}
 
-    j.open = true;   // from here on kernels are queued: every error path drains them (frame_abort)
-    if ((rc = mark(sl, 0))) return frame_abort(sl, rc);
-    // The position-keyed order (the reference's rule, src/GSplatRenderer.C:165-186): dropped when the position moved, built the second
-    // time a position is seen
-    if (p.want_pos && !in.pos_match) {
+// The position-keyed order (the reference's rule, src/GSplatRenderer.C:165-186): dropped when the position moved, built the second
+// time a position is seen
+static int queue_pos_order(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
+{
+    if (fe.p.want_pos && !fe.pos_match) {
         c->pos_valid = false;
-        if (p.ordered && (rc = build_pos_order(c, sl, f, p.key_bits))) return frame_abort(sl, rc);
+        if (const int rc = fe.p.ordered ? build_pos_order(c, sl, sl.job.f, fe.p.key_bits) : GSR_OK) return rc;
     }
-    std::memcpy(c->last_cam, cam->cam_pos, sizeof c->last_cam);
+    std::memcpy(c->last_cam, sl.job.args.cam.cam_pos, sizeof c->last_cam);
     c->last_cam_set = true;
-    const uint32_t n_slots = p.n_slots;
-    GsrK1Scatter scat{};
-    if (n > 0) {
-#ifdef GSR_HOST_TIMING
-        const double t_pre = now_us();
-#endif
-        // cluster culling (k_cluster.h): which clusters of 64 storage-ordered splats can draw anything in this frame
-        int rounds; uint32_t ngroups;
-        cluster_grid(c->nclus, &rounds, &ngroups);
-        if ((c->opt_flags & GSR_FLAG_CULL_ROUNDS) && c->nclus > 0) {   // (test hook: the several-rounds-per-workgroup form clouds beyond 33 M splats take)
-            rounds = std::max(rounds, 3);
-            ngroups = div_up(c->nclus, (uint32_t)CC_THREADS * (uint32_t)rounds);
-        }
-        // (front-slab frames: phase 1 leaves a histogram of the survivors' nearest keys and k_slab_pick takes the slab key from it;
-        //  phase 2 culls against the tiles phase 1 finished)
-        const int hist_shift = p.key_bits > 10 ? p.key_bits - 10 : 0;
-        const float* pyr = j.phase == 2 ? sl.hpyr2 : ((j.cull && !p.ordered) ? sl.hpyr : (const float*)nullptr);
-        const GsrSlabPick pk{(uint32_t)c->slab_min, (uint32_t)c->slab_max, (uint32_t)c->slab_frac, f.key_max - f.key_min};
-        // depth-tested frames: the opaque pass's tile-max depth pyramid -- where the previous depth-tested frame found opaque geometry in
-        // its buffer, in a launch of its own in front of everything (k_cluster_cull and K1 cull against it); otherwise -- a buffer
-        // cleared to the far plane, the common case -- NO pyramid: the first workgroups of k_cluster_cull's launch only look whether a
-        // pixel is covered at all (k_cluster.h: gsr_depth_detect_block), and a frame in which geometry appears goes without depth culling.
-        // Whatever the guess, the pixels are the same: the tests are conservative and k_blend compares every fragment.
-        GsrDepthPyrArgs dp{};
-        uint32_t n_dp = 0;
-        GsrDepthCull dc_clus{nullptr, nullptr, nullptr}, dc_k1{nullptr, nullptr, nullptr};
-        if (j.dcull) {
-            float* const dp0 = sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap;
-            float* const dq0 = sl.dpyr + (size_t)(2 * (j.dpar ^ 1)) * sl.dpyr_cap;
-            dc_k1 = GsrDepthCull{dp0, j.phase == 2 ? (const float*)nullptr : dp0 + sl.dpyr_cap, sl.dactive + j.dpar};
-            if (j.phase == 2 && !sl.dpyr_built) { dc_k1 = GsrDepthCull{nullptr, nullptr, nullptr}; j.dblind = true; }   // (phase 1 built none)
-            if (j.phase != 2) {
-                dp.depth = j.d_depth; dp.pyr = dp0; dp.pyrc = dp0 + sl.dpyr_cap; dp.pyr_next = dq0; dp.pyrc_next = dq0 + sl.dpyr_cap; dp.active = sl.dactive; dp.par = j.dpar;
-                dp.tcov = sl.dpyr + 4 * sl.dpyr_cap;
-                // (a culled frame: the tiles that were classic when the horizons were left get no depth clause)
-                dp.stat = (j.cull && sl.hstat_valid) ? sl.hstat : (const float*)nullptr;
-                j.dstat = dp.stat != nullptr;
-                dp.width = f.width; dp.height = f.height; dp.tiles_x = f.tiles_x; dp.tiles_y = f.tiles_y;
-                for (int l = 0; l < GSR_PYR_LEVELS; ++l) dp.off[l] = f.pyr_off[l];
-                const uint32_t nb8 = (uint32_t)gsr_depth_pyramid_blocks(f.tiles_x, f.tiles_y);
-                if (c->depth_active) {
-                    // (measured and rejected, round 6: the pass inside k_cluster_cull's launch here too, the cluster workgroups waiting on a
-                    //  count of finished pyramid workgroups before their depth tests: 3650 fps against 4245 -- LAB_NOTES.md)
-                    hipLaunchKernelGGL(k_depth_pyramid, dim3(nb8), dim3(1024), 0, s, dp);
-                    if (c->opt_cluster && !p.ordered) dc_clus = dc_k1;
-                    sl.dpyr_built = true;
-                } else {
-                    (void)nb8;
-                    n_dp = (uint32_t)gsr_depth_detect_blocks(f.width, f.height);
-                    j.dblind = true;
-                    j.dstat = false;
-                    sl.dpyr_built = false;
-                    dc_k1 = GsrDepthCull{nullptr, nullptr, nullptr};
-                }
-            } else if (c->opt_cluster && sl.dpyr_built) {
-                dc_clus = dc_k1;       // (phase 1 built it)
-            }
-        }
-        if (j.phase == 1) {   // a first pass for the histogram alone (the pass below takes the slab key from it and keeps the slab's clusters only)
-            // (the histogram is cleared by phase 2's cull pass; a phase 1 that never got its phase 2 -- its small-frame sort gave a bucket
-            //  up, an error in between -- left its counts behind: they would skew this frame's slab key, never its pixels)
-            if (sl.slab_dirty && hipMemsetAsync(sl.slab, 0, (size_t)GSR_SLAB_BINS * sizeof(uint32_t), s) != hipSuccess)
-                return frame_abort(sl, set_err(GSR_E_HIP, "gsr_render: clearing the slab histogram failed"));
-            sl.slab_dirty = true;
-            const int n45 = gsr_pyr_dim(f.tiles_x, 4) * gsr_pyr_dim(f.tiles_y, 4) + gsr_pyr_dim(f.tiles_x, 5) * gsr_pyr_dim(f.tiles_y, 5);
-            hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(ngroups + n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, rounds, c->opt_cluster,
-                               (const float*)nullptr, sl.cseg, sl.ccnt, 1, sl.slab, hist_shift, sl.slab + GSR_SLAB_BINS, pk, sl.hpyr2 + f.pyr_off[4], n45,
-                               (uint32_t*)nullptr, (uint32_t*)nullptr, dp, n_dp, dc_clus);
-            n_dp = 0;      // (looked at: not again in the pass below)
-        }
-        if (j.phase == 2) sl.slab_dirty = false;   // (mode 3 below clears the histogram for the slot's next front-slab frame)
-        hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(ngroups + n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, rounds, p.ordered ? 0 : c->opt_cluster,
-                           pyr, sl.cseg, sl.ccnt,   // (ordered: slots, not clusters -- all of them)
-                           j.phase == 1 ? 2 : (j.phase == 2 ? 3 : 0), sl.slab, hist_shift, sl.slab + GSR_SLAB_BINS, pk, (float*)nullptr, 0,
-                           j.local_sort ? sl.bkt_cnt : (uint32_t*)nullptr, sl.d_counts + 2, dp, n_dp, dc_clus);
-        // The small-frame sort's bucket pass runs inside K1 (a key's place in its bucket = one atomic), over the plan's buckets; front-slab
-        // phases: over the phase's own range, which k_slab_pick left on the device
-        if (p.k1_scatters) {
-            scat.key = sl.bkt_key; scat.val = sl.bkt_val; scat.cnt = sl.bkt_cnt; scat.failed = sl.d_counts + 2;
-            scat.range_dev = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
-            scat.lo = p.bk_lo; scat.shift = p.bk_shift;
-        }
-        // K1 over the survivors (the plan's grid: a frame that keeps more loops); on a cache hit (identical frame description) the sorted
-        // (keyA, valA) are kept and K1's key/payload output goes to the scratch buffers
-        // (two instantiations: the one that leaves the colours pending has no SH evaluation in it and runs at 8 waves per SIMD instead of 6)
-        // (a frame with the depth AOV takes the depth-tested twins for the window depths they write; without a depth buffer it brings no
-        //  pyramids -- dc_k1 is empty -- so nothing is culled against a depth that is not there)
-        const bool k1_zwin = j.d_depth != nullptr || j.aov_target != nullptr;
-        hipLaunchKernelGGL(k1_zwin ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(j.k1_grid ? j.k1_grid : 1u), dim3(GSR_K1_THREADS), 0, s, n, c->cap, f, c->geoA, c->geoB, c->col,
-                           sl.rec, (p.cache_hit || p.ordered) ? sl.keyB : sl.keyA, (p.cache_hit || p.ordered) ? sl.valB : sl.valA,
-                           k1_zwin ? sl.zwin : (float*)nullptr, j.phase == 2 ? sl.hpyr2 : (j.cull ? sl.hpyr : (const float*)nullptr), sl.blk_cnt,
-                           sl.cseg, sl.ccnt, ngroups, (uint32_t)CC_THREADS * (uint32_t)rounds, sl.d_counts, scat,
-                           // (the count of sorted splats starts at zero: a frame whose clusters are ALL culled runs no sort workgroup that
-                           //  could say so, and the binning kernels would walk the previous frame's order; a static redraw keeps its order)
-                           p.cache_hit ? (uint32_t*)nullptr : sl.d_n,
-                           p.ordered ? c->pos_order : (const uint32_t*)nullptr, sl.slab + GSR_SLAB_BINS, dc_k1);
-        hipError_t e = hipGetLastError();
-#ifdef GSR_HOST_TIMING
-        if (g_t_verdict > 0) {
-            const double t_l = now_us();
-            g_acc_py += t_enter - g_t_verdict; g_acc_pre += t_pre - t_enter; g_acc_launch += t_l - t_pre; ++g_acc_n;
-            if (g_acc_n % 100 == 0)
-                fprintf(stderr, "[host timing] verdict -> gsr_render %.1f us, frame_begin before K1 %.1f us, K1 launch %.1f us (avg of %ld)\n",
-                        g_acc_py / g_acc_n, g_acc_pre / g_acc_n, g_acc_launch / g_acc_n, g_acc_n);
-            g_t_verdict = 0;
-        }
-#endif
-        if (e != hipSuccess) return frame_abort(sl, set_err(GSR_E_HIP, "k_preprocess: %s", hipGetErrorString(e)));
+    return GSR_OK;
+}
+
+// cluster culling (k_cluster.h): which clusters of 64 storage-ordered splats can draw anything in this frame
+static int queue_cull(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
+{
+    FrameJob& j = sl.job;
+    const GsrFrame& f = j.f;
+    const GsrFramePlan& p = fe.p;
+    hipStream_t s = sl.stream;
+    if (j.n == 0) return GSR_OK;
+    cluster_grid(c->nclus, &fe.rounds, &fe.ngroups);
+    if ((c->opt_flags & GSR_FLAG_CULL_ROUNDS) && c->nclus > 0) {   // (test hook: the several-rounds-per-workgroup form clouds beyond 33 M splats take)
+        fe.rounds = std::max(fe.rounds, 3);
+        fe.ngroups = div_up(c->nclus, (uint32_t)CC_THREADS * (uint32_t)fe.rounds);
     }
-    if ((rc = mark(sl, 1))) return frame_abort(sl, rc);
+    // (front-slab frames: phase 1 leaves a histogram of the survivors' nearest keys and k_slab_pick takes the slab key from it;
+    //  phase 2 culls against the tiles phase 1 finished)
+    fe.hist_shift = p.key_bits > 10 ? p.key_bits - 10 : 0;
+    const float* pyr = j.phase == 2 ? sl.hpyr2 : ((j.cull && !p.ordered) ? sl.hpyr : (const float*)nullptr);
+    const GsrSlabPick pk{(uint32_t)c->slab_min, (uint32_t)c->slab_max, (uint32_t)c->slab_frac, f.key_max - f.key_min};
+    // depth-tested frames: the opaque pass's tile-max depth pyramid -- where the previous depth-tested frame found opaque geometry in
+    // its buffer, in a launch of its own in front of everything (k_cluster_cull and K1 cull against it); otherwise -- a buffer
+    // cleared to the far plane, the common case -- NO pyramid: the first workgroups of k_cluster_cull's launch only look whether a
+    // pixel is covered at all (k_cluster.h: gsr_depth_detect_block), and a frame in which geometry appears goes without depth culling.
+    // Whatever the guess, the pixels are the same: the tests are conservative and k_blend compares every fragment.
+    GsrDepthPyrArgs& dp = fe.dp;
+    if (j.dcull) {
+        float* const dp0 = sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap;
+        float* const dq0 = sl.dpyr + (size_t)(2 * (j.dpar ^ 1)) * sl.dpyr_cap;
+        fe.dc_k1 = GsrDepthCull{dp0, j.phase == 2 ? (const float*)nullptr : dp0 + sl.dpyr_cap, sl.dactive + j.dpar};
+        if (j.phase == 2 && !sl.dpyr_built) { fe.dc_k1 = GsrDepthCull{nullptr, nullptr, nullptr}; j.dblind = true; }   // (phase 1 built none)
+        if (j.phase != 2) {
+            dp.depth = j.d_depth; dp.pyr = dp0; dp.pyrc = dp0 + sl.dpyr_cap; dp.pyr_next = dq0; dp.pyrc_next = dq0 + sl.dpyr_cap; dp.active = sl.dactive; dp.par = j.dpar;
+            dp.tcov = sl.dpyr + 4 * sl.dpyr_cap;
+            // (a culled frame: the tiles that were classic when the horizons were left get no depth clause)
+            dp.stat = (j.cull && sl.hstat_valid) ? sl.hstat : (const float*)nullptr;
+            j.dstat = dp.stat != nullptr;
+            dp.width = f.width; dp.height = f.height; dp.tiles_x = f.tiles_x; dp.tiles_y = f.tiles_y;
+            for (int l = 0; l < GSR_PYR_LEVELS; ++l) dp.off[l] = f.pyr_off[l];
+            if (c->depth_active) {
+                // (measured and rejected, round 6: the pass inside k_cluster_cull's launch here too, the cluster workgroups waiting on a
+                //  count of finished pyramid workgroups before their depth tests: 3650 fps against 4245 -- LAB_NOTES.md)
+                hipLaunchKernelGGL(k_depth_pyramid, dim3((uint32_t)gsr_depth_pyramid_blocks(f.tiles_x, f.tiles_y)), dim3(1024), 0, s, dp);
+                if (c->opt_cluster && !p.ordered) fe.dc_clus = fe.dc_k1;
+                sl.dpyr_built = true;
+            } else {
+                fe.n_dp = (uint32_t)gsr_depth_detect_blocks(f.width, f.height);
+                j.dblind = true;
+                j.dstat = false;
+                sl.dpyr_built = false;
+                fe.dc_k1 = GsrDepthCull{nullptr, nullptr, nullptr};
+            }
+        } else if (c->opt_cluster && sl.dpyr_built) {
+            fe.dc_clus = fe.dc_k1;       // (phase 1 built it)
+        }
+    }
+    if (j.phase == 1) {   // a first pass for the histogram alone (the pass below takes the slab key from it and keeps the slab's clusters only)
+        // (the histogram is cleared by phase 2's cull pass; a phase 1 that never got its phase 2 -- its small-frame sort gave a bucket
+        //  up, an error in between -- left its counts behind: they would skew this frame's slab key, never its pixels)
+        if (sl.slab_dirty && hipMemsetAsync(sl.slab, 0, (size_t)GSR_SLAB_BINS * sizeof(uint32_t), s) != hipSuccess)
+            return set_err(GSR_E_HIP, "gsr_render: clearing the slab histogram failed");
+        sl.slab_dirty = true;
+        const int n45 = gsr_pyr_dim(f.tiles_x, 4) * gsr_pyr_dim(f.tiles_y, 4) + gsr_pyr_dim(f.tiles_x, 5) * gsr_pyr_dim(f.tiles_y, 5);
+        hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(fe.ngroups + fe.n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, fe.rounds, c->opt_cluster,
+                           (const float*)nullptr, sl.cseg, sl.ccnt, 1, sl.slab, fe.hist_shift, sl.slab + GSR_SLAB_BINS, pk, sl.hpyr2 + f.pyr_off[4], n45,
+                           (uint32_t*)nullptr, (uint32_t*)nullptr, dp, fe.n_dp, fe.dc_clus);
+        fe.n_dp = 0;      // (looked at: not again in the pass below)
+    }
+    if (j.phase == 2) sl.slab_dirty = false;   // (mode 3 below clears the histogram for the slot's next front-slab frame)
+    hipLaunchKernelGGL(j.dcull ? k_cluster_cull<true> : k_cluster_cull<false>, dim3(fe.ngroups + fe.n_dp), dim3(CC_THREADS), 0, s, f, c->clusA, c->clusB, c->nclus, fe.rounds, p.ordered ? 0 : c->opt_cluster,
+                       pyr, sl.cseg, sl.ccnt,   // (ordered: slots, not clusters -- all of them)
+                       j.phase == 1 ? 2 : (j.phase == 2 ? 3 : 0), sl.slab, fe.hist_shift, sl.slab + GSR_SLAB_BINS, pk, (float*)nullptr, 0,
+                       j.local_sort ? sl.bkt_cnt : (uint32_t*)nullptr, sl.d_counts + 2, dp, fe.n_dp, fe.dc_clus);
+    return GSR_OK;
+}
+
+// K1 over the survivors (the plan's grid: a frame that keeps more loops); on a cache hit (identical frame description) the sorted
+// (keyA, valA) are kept and K1's key/payload output goes to the scratch buffers
+static int queue_preprocess(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
+{
+    const FrameJob& j = sl.job;
+    const GsrFrame& f = j.f;
+    const GsrFramePlan& p = fe.p;
+    if (j.n == 0) return GSR_OK;
+    // The small-frame sort's bucket pass runs inside K1 (a key's place in its bucket = one atomic), over the plan's buckets; front-slab
+    // phases: over the phase's own range, which k_slab_pick left on the device
+    GsrK1Scatter& scat = fe.scat;
+    if (p.k1_scatters) {
+        scat.key = sl.bkt_key; scat.val = sl.bkt_val; scat.cnt = sl.bkt_cnt; scat.failed = sl.d_counts + 2;
+        scat.range_dev = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
+        scat.lo = p.bk_lo; scat.shift = p.bk_shift;
+    }
+    // (two instantiations: the one that leaves the colours pending has no SH evaluation in it and runs at 8 waves per SIMD instead of 6)
+    // (a frame with the depth AOV takes the depth-tested twins for the window depths they write; without a depth buffer it brings no
+    //  pyramids -- dc_k1 is empty -- so nothing is culled against a depth that is not there)
+    const bool k1_zwin = j.d_depth != nullptr || j.aov_target != nullptr;
+    hipLaunchKernelGGL(k1_zwin ? (j.lazy ? k_preprocess_lazy_depth : k_preprocess_depth) : (j.lazy ? k_preprocess_lazy : k_preprocess), dim3(j.k1_grid ? j.k1_grid : 1u), dim3(GSR_K1_THREADS), 0, sl.stream, j.n, c->cap, f, c->geoA, c->geoB, c->col,
+                       sl.rec, (p.cache_hit || p.ordered) ? sl.keyB : sl.keyA, (p.cache_hit || p.ordered) ? sl.valB : sl.valA,
+                       k1_zwin ? sl.zwin : (float*)nullptr, j.phase == 2 ? sl.hpyr2 : (j.cull ? sl.hpyr : (const float*)nullptr), sl.blk_cnt,
+                       sl.cseg, sl.ccnt, fe.ngroups, (uint32_t)CC_THREADS * (uint32_t)fe.rounds, sl.d_counts, scat,
+                       // (the count of sorted splats starts at zero: a frame whose clusters are ALL culled runs no sort workgroup that
+                       //  could say so, and the binning kernels would walk the previous frame's order; a static redraw keeps its order)
+                       p.cache_hit ? (uint32_t*)nullptr : sl.d_n,
+                       p.ordered ? c->pos_order : (const uint32_t*)nullptr, sl.slab + GSR_SLAB_BINS, fe.dc_k1);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "k_preprocess: %s", hipGetErrorString(e));
+}
+
+// the small-frame sort (k_sort.h): K1's compacted slots -> bucket regions (counters and *d_n were cleared by K1) -> sorted (keyA, valA),
+// over the plan's buckets; a front-slab phase: over the phase's own key range, which k_slab_pick left on the device
+static int queue_local_sort(gsr_context* c, FrameSlot& sl, const FrontEnd& fe)
+{
+    const FrameJob& j = sl.job;
+    const GsrFramePlan& p = fe.p;
+    hipStream_t s = sl.stream;
+    const uint32_t* range = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
+    const uint32_t lo = p.local_phase ? 0u : p.bk_lo;
+    const int bshift = p.local_phase ? 0 : p.bk_shift;
+    const uint32_t n_slots = p.n_slots;
+    if (p.k1_scatters) {
+        // (K1 did it)
+    } else if (p.scatter_direct && !p.local_phase)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_direct<uint2>), dim3(n_slots / RS_SRC_BLOCK), dim3(RS_SRC_BLOCK), 0, s, sl.keyA, sl.valA,
+                           sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2);
+    else if (c->opt_scatter_direct >= 0 || p.local_phase)
+        // (grid: K1's own estimate of its workgroup-iterations, four per workgroup here)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(std::max(1u, std::min(div_up(n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u))), dim3(256), 0, s, sl.keyA, sl.valA,
+                           n_slots / RS_SRC_BLOCK, sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2, range);
+    else   // (A/B: the general gathering scatter, 2048 slots per workgroup)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint2, true>), dim3(div_up(n_slots, RS_TILE)), dim3(RS_THREADS), 0, s, sl.keyA, sl.valA, n_slots, sl.d_counts,
+                           bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, (uint32_t*)nullptr, sl.d_counts + 2);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, bshift, p.key_bits, lo,
+                       sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n, range);
+    return hipGetLastError() == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "small-frame sort: launch failed");
+}
+
+// the frame's depth order in (keyA, valA): kept (a static redraw), compacted from K1's blocks (the position-keyed order), or sorted
+static int queue_sort(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
+{
+    FrameJob& j = sl.job;
+    const GsrFramePlan& p = fe.p;
+    hipStream_t s = sl.stream;
+    int rc;
     if (p.cache_hit) {
         c->st.sorts_skipped += 1;
-    } else if (p.ordered) {
+        return GSR_OK;
+    }
+    if (p.ordered) {
         // K1 walked the splats nearest first: the heads of its 256-slot blocks, one after the other, ARE the sorted frame
-        const uint32_t m_max = n_slots / RS_SRC_BLOCK;
-        if ((rc = ensure_u32(&c->blk_pre, &c->blk_pre_cap, (size_t)m_max + 8))) return frame_abort(sl, rc);
+        const uint32_t m_max = p.n_slots / RS_SRC_BLOCK;
+        if ((rc = ensure_u32(&c->blk_pre, &c->blk_pre_cap, (size_t)m_max + 8))) return rc;
         hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, sl.blk_cnt, sl.d_counts, c->blk_pre, sl.d_n);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compact_blocks<uint2>), dim3(m_max), dim3(RS_SRC_BLOCK), 0, s, sl.keyB, sl.valB, sl.blk_cnt, c->blk_pre,
                            sl.d_counts, sl.keyA, sl.valA);
-        if (hipGetLastError() != hipSuccess) return frame_abort(sl, set_err(GSR_E_HIP, "position-keyed order: launch failed"));
+        if (hipGetLastError() != hipSuccess) return set_err(GSR_E_HIP, "position-keyed order: launch failed");
         c->st.sorts_skipped += 1;
-        sl.key_min = f.key_min;
+        sl.key_min = j.f.key_min;
         sl.sort_valid = false;       // (what the slot holds is this frame's kept set only)
         sl.sorted_culled = j.cull;
-    } else {
-        if (p.local_phase) {
-            // K1's compacted slots -> bucket regions over the phase's key range (k_slab_pick left it on the device) -> sorted (keyA, valA)
-            const uint32_t* range = sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4);
-            if (!p.k1_scatters)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(std::max(1u, std::min(div_up(n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u))), dim3(256), 0, s, sl.keyA, sl.valA,
-                                   n_slots / RS_SRC_BLOCK, sl.d_counts, 0, 0u, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2, range);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, 0, p.key_bits, 0u,
-                               sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n, range);
-            if (hipGetLastError() != hipSuccess) rc = set_err(GSR_E_HIP, "small-frame sort: launch failed");
-        } else if (p.local) {
-            const uint32_t lo = p.bk_lo;
-            const int bshift = p.bk_shift;
-            const uint32_t nblk = div_up(n_slots, RS_TILE);
-            // K1's compacted slots -> bucket regions (counters and *d_n were cleared by K1) -> sorted (keyA, valA)
-            if (p.k1_scatters) {
-                // (K1 did it)
-            } else if (p.scatter_direct)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_direct<uint2>), dim3(n_slots / RS_SRC_BLOCK), dim3(RS_SRC_BLOCK), 0, s, sl.keyA, sl.valA,
-                                   sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2);
-            else if (c->opt_scatter_direct >= 0)
-                // (grid: K1's own estimate of its workgroup-iterations, four per workgroup here)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(std::max(1u, std::min(div_up(n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u))), dim3(256), 0, s, sl.keyA, sl.valA,
-                                   n_slots / RS_SRC_BLOCK, sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2);
-            else   // (A/B: the general gathering scatter, 2048 slots per workgroup)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint2, true>), dim3(nblk), dim3(RS_THREADS), 0, s, sl.keyA, sl.valA, n_slots, sl.d_counts,
-                                   bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, (uint32_t*)nullptr, sl.d_counts + 2);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, bshift, p.key_bits, lo,
-                               sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n);
-            if (hipGetLastError() != hipSuccess) rc = set_err(GSR_E_HIP, "small-frame sort: launch failed");
-        } else {
-            rc = radix_sort(sl, sl.keyA, sl.valA, sl.keyB, sl.valB, n_slots, p.key_bits,
-                            !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n, RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, p.mid_sort);
-        }
-        if (rc) return frame_abort(sl, rc);
-        sl.key_min = f.key_min;
-        sl.sort_valid = j.phase == 0;    // (a phase's order holds a part of the frame only)
-        sl.sort_key = key_now;
-        sl.sorted_culled = j.cull;
-        sl.sorted_dculled = j.dcull;     // (until the frame's mailbox says that its depth buffer culled nothing: frame_finish)
-        j.sort_fresh = true;
+        return GSR_OK;
     }
-    if ((rc = mark(sl, 2))) return frame_abort(sl, rc);
+    rc = (p.local_phase || p.local) ? queue_local_sort(c, sl, fe)
+                                    : radix_sort(sl, sl.keyA, sl.valA, sl.keyB, sl.valB, p.n_slots, p.key_bits, !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n,
+                                                 RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, p.mid_sort);
+    if (rc) return rc;
+    sl.key_min = j.f.key_min;
+    sl.sort_valid = j.phase == 0;    // (a phase's order holds a part of the frame only)
+    sl.sort_key = fe.key_now;
+    sl.sorted_culled = j.cull;
+    sl.sorted_dculled = j.dcull;     // (until the frame's mailbox says that its depth buffer culled nothing: frame_finish)
+    j.sort_fresh = true;
+    return GSR_OK;
+}
+
+// coarse binning as a counting sort (k_binning.h): count -> scan -> ranges -> [pair count to the host] -> place; then the back end,
+// speculatively where a list buffer exists, and a deferred frame's end
+static int queue_binning(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
+{
+    FrameJob& j = sl.job;
+    const GsrFrame& f = j.f;
+    hipStream_t s = sl.stream;
+    int rc;
     hipError_t e = hipSuccess;
-    if (n > 0) {
-        // coarse binning as a counting sort (k_binning.h): count -> scan -> ranges -> [pair count to the host] -> place
+    if (j.n > 0) {
         const uint32_t bn_tile = (uint32_t)BN_THREADS * (uint32_t)j.bn_items;
-        const uint32_t nblk = p.bn_blocks;
-        rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)BN_BINS * nblk + 8);
-        if (rc) return frame_abort(sl, rc);
+        const uint32_t nblk = fe.p.bn_blocks;
+        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)BN_BINS * nblk + 8))) return rc;
         const GsrShard shd{f.shard_index, f.shard_count, f.shard_rpb, f.rect_shift};
         // (+ the extra work items of the blocks that are split by rows of super-tiles: k_binning.h, BN_SPLIT_TILES)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
@@ -2466,7 +2419,7 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
                                         shd, f.stiles_x, f.stiles_y, sl.hist, nblk)
         if (j.bn_items == 1) GSR_COUNT(1); else if (j.bn_items == 2) GSR_COUNT(2); else GSR_COUNT(4);
 #undef GSR_COUNT
-        hipLaunchKernelGGL(k_scan_rows, dim3(BN_BINS), dim3(SC_THREADS), 0, s, sl.hist, nblk, sl.totals, sl.d_n, n, bn_tile);
+        hipLaunchKernelGGL(k_scan_rows, dim3(BN_BINS), dim3(SC_THREADS), 0, s, sl.hist, nblk, sl.totals, sl.d_n, j.n, bn_tile);
         // the list ranges and the pair count: formed by k_bin_place itself (queue_back_end) when the back end is queued
         // speculatively; a frame without a list buffer needs the count first
         if (!(sl.pair_cap > 0)) hipLaunchKernelGGL(k_bin_ranges, dim3(1), dim3(BN_BINS), 0, s, range_args(c, sl));
@@ -2475,15 +2428,15 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
         e = hipMemsetAsync(sl.sstart, 0, ((size_t)j.n_super + 1) * 4, s);
         if (e == hipSuccess) e = hipMemsetAsync(sl.send, 0, ((size_t)j.n_super + 1) * 4, s);
     }
-    if (e != hipSuccess) return frame_abort(sl, set_err(GSR_E_HIP, "gsr_render: binning: %s", hipGetErrorString(e)));
-    j.speculative = n > 0 && sl.pair_cap > 0;
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render: binning: %s", hipGetErrorString(e));
+    j.speculative = j.n > 0 && sl.pair_cap > 0;
     j.ranges_folded = j.speculative;
-    if (j.speculative || n == 0) {
-        if ((rc = queue_back_end(c, sl))) return frame_abort(sl, rc);
+    if (j.speculative || j.n == 0) {
+        if ((rc = queue_back_end(c, sl))) return rc;
     } else {
         j.deferred = false;   // no list buffer yet (first frame): the host has to size it before anything is composited
     }
-    if (j.deferred && (rc = queue_frame_end(c, sl))) return frame_abort(sl, rc);
+    if (j.deferred && (rc = queue_frame_end(c, sl))) return rc;
     sl.last_supers = j.n_super;
     sl.last_tiles_x = f.tiles_x;
     sl.last_local_ty = f.local_tiles_y;
@@ -2493,6 +2446,53 @@ static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, boo
     sl.frame_id = c->frame_no;
     // (the frame's counters are written to the host mirror by k_sum_work; they are read in gsr_get_stats)
     return GSR_OK;
+}
+
+#ifdef GSR_HOST_TIMING
+// the host's share of a frame, from the previous frame's verdict (frame_check) to K1's launch, averaged over 100 frames
+static void host_timing_note(double t_enter, double t_pre)
+{
+    if (!(g_t_verdict > 0)) return;
+    g_acc_py += t_enter - g_t_verdict; g_acc_pre += t_pre - t_enter; g_acc_launch += now_us() - t_pre; ++g_acc_n;
+    if (g_acc_n % 100 == 0)
+        fprintf(stderr, "[host timing] verdict -> gsr_render %.1f us, frame_begin before K1 %.1f us, K1 launch %.1f us (avg of %ld)\n",
+                g_acc_py / g_acc_n, g_acc_pre / g_acc_n, g_acc_launch / g_acc_n, g_acc_n);
+    g_t_verdict = 0;
+}
+#endif
+
+static int frame_begin(gsr_context* c, const FrameArgs& a, FrameSlot** used, bool allow_cull, int phase_in /* 2 = the second phase of a front-slab frame */)
+{
+#ifdef GSR_HOST_TIMING
+    const double t_enter = now_us();
+#endif
+    FrameSlot* slot = nullptr;
+    FrontEnd fe;
+    int rc = frame_open(c, a, slot);
+    if (used && slot) *used = slot;
+    if (rc) return rc;
+    FrameSlot& sl = *slot;
+    plan_frame(c, sl, fe, allow_cull, phase_in);
+    if ((rc = stage_frame_buffers(c, sl))) return rc;
+
+    // THE BOUNDARY.  Up to here nothing of the frame is in the stream and a stage's error is returned as it is.  From here on kernels
+    // are queued, some of which write the caller's buffers: the stages below return their error and frame_abort drains the stream.
+    sl.job.open = true;
+    rc = mark(sl, 0);
+    if (!rc) rc = queue_pos_order(c, sl, fe);
+#ifdef GSR_HOST_TIMING
+    const double t_pre = now_us();
+#endif
+    if (!rc) rc = queue_cull(c, sl, fe);
+    if (!rc) rc = queue_preprocess(c, sl, fe);
+#ifdef GSR_HOST_TIMING
+    if (sl.job.n > 0) host_timing_note(t_enter, t_pre);
+#endif
+    if (!rc) rc = mark(sl, 1);
+    if (!rc) rc = queue_sort(c, sl, fe);
+    if (!rc) rc = mark(sl, 2);
+    if (!rc) rc = queue_binning(c, sl, fe);
+    return rc ? frame_abort(sl, rc) : GSR_OK;
 }
 
 static FrameSlot* latest_slot(gsr_context* c);
