@@ -168,6 +168,28 @@ int GSplatRenderer::updateAttributes(const std::string& id, const uint16_t* spla
                                      const uint16_t* splatScales, const uint16_t* splatOrients, const uint16_t* splatShxs,
                                      const uint16_t* splatShys, const uint16_t* splatShzs, int64_t* first_out, int64_t* n_out)
 {
+    return editRow(id, nullptr, nullptr, splatColors, splatAlphas, splatScales, splatOrients, splatShxs, splatShys, splatShzs, first_out, n_out);
+}
+
+int GSplatRenderer::moveSplats(const std::string& id, const float* splatPts, const float* splatOrigin, const uint16_t* splatColors,
+                               const float* splatAlphas, const uint16_t* splatScales, const uint16_t* splatOrients,
+                               const uint16_t* splatShxs, const uint16_t* splatShys, const uint16_t* splatShzs, int64_t* first_out,
+                               int64_t* n_out)
+{
+    if (!splatPts) {
+        if (first_out) *first_out = 0;
+        if (n_out) *n_out = 0;
+        return GSR_E_INVALID;
+    }
+    return editRow(id, splatPts, splatOrigin, splatColors, splatAlphas, splatScales, splatOrients, splatShxs, splatShys, splatShzs, first_out, n_out);
+}
+
+// updateAttributes (splatPts == NULL) and moveSplats: one row's new arrays, and its resident splats edited without a re-stage
+int GSplatRenderer::editRow(const std::string& id, const float* splatPts, const float* splatOrigin, const uint16_t* splatColors,
+                            const float* splatAlphas, const uint16_t* splatScales, const uint16_t* splatOrients,
+                            const uint16_t* splatShxs, const uint16_t* splatShys, const uint16_t* splatShzs, int64_t* first_out,
+                            int64_t* n_out)
+{
     if (first_out) *first_out = 0;
     if (n_out) *n_out = 0;
     const auto hit = table_.find(id);
@@ -182,6 +204,16 @@ int GSplatRenderer::updateAttributes(const std::string& id, const uint16_t* spla
         }
     const int nsh = (splatShxs ? 1 : 0) + (splatShys ? 1 : 0) + (splatShzs ? 1 : 0);
     if (nsh != 0 && (nsh != 3 || row.sh_count < (take >= 0 ? take : row.count))) return GSR_E_INVALID;
+    // registerUpdate() may have retired another resident row since the plan was recorded: what is resident is then due for a
+    // re-stage, which takes this row as it is now -- nothing is moved on the GPU, and no origin is formed over rows that are gone
+    if (splatPts && take >= 0)
+        for (const Plan::Part& part : resident_.parts)
+            if (table_.find(part.id) == table_.end()) { resident_ok_ = false; take = -1; break; }
+    if (splatPts) row.P = splatPts;
+    if (splatPts && splatOrigin) {
+        std::copy(splatOrigin, splatOrigin + 3, row.origin);
+        if (take >= 0) planOrigin(resident_);   // the resident pass's origin, by the rule a re-stage forms it with
+    }
     if (splatColors) row.Cd = splatColors;
     if (splatAlphas) row.alpha = splatAlphas;
     if (splatScales) row.scale = splatScales;
@@ -194,9 +226,14 @@ int GSplatRenderer::updateAttributes(const std::string& id, const uint16_t* spla
     gsr_attr_update u{};
     u.Cd = splatColors; u.alpha = splatAlphas; u.scale = splatScales; u.orient = splatOrients;
     if (nsh && resident_.sh) { u.shx = splatShxs; u.shy = splatShys; u.shz = splatShzs; }
-    status_ = multi_ ? gsr_multi_update(multi_, first, take, &u) : engine_ ? gsr_update(engine_, first, take, &u) : GSR_E_NO_DEVICE;
+    if (splatPts) {
+        const float* const org = splatOrigin ? resident_.origin : nullptr;
+        status_ = multi_ ? gsr_multi_move(multi_, first, take, splatPts, org, &u) : engine_ ? gsr_move(engine_, first, take, splatPts, org, &u) : GSR_E_NO_DEVICE;
+    } else {
+        status_ = multi_ ? gsr_multi_update(multi_, first, take, &u) : engine_ ? gsr_update(engine_, first, take, &u) : GSR_E_NO_DEVICE;
+    }
     if (status_ != GSR_OK) {
-        note("error", "updating %" PRId64 " splats in place failed: %s", take, gsr_last_error());
+        note("error", "%s %" PRId64 " splats in place failed: %s", splatPts ? "moving" : "updating", take, gsr_last_error());
         resident_ok_ = false;   // the next redraw stages the edited arrays
         return status_;
     }
@@ -220,11 +257,21 @@ void GSplatRenderer::includeInRenderPass(const std::string& id)
 
 // What this redraw would put on the GPU.  Rows are visited in id order; a row joins while the budget is not
 // yet used up, and the row that crosses the budget is truncated.
+// The origin of a pass: the mean of its rows' origins, summed in packing order (src/GSplatRenderer.C:403-418).  The ONE place the
+// rule lives: planFrame() and moveSplats() must give the same plan the same bits.
+void GSplatRenderer::planOrigin(Plan& p) const
+{
+    if (p.parts.empty()) return;
+    float sum[3] = {0.0f, 0.0f, 0.0f};
+    for (const Plan::Part& part : p.parts)
+        for (int k = 0; k < 3; ++k) sum[k] += table_.at(part.id).origin[k];
+    for (int k = 0; k < 3; ++k) p.origin[k] = sum[k] / static_cast<float>(p.parts.size());
+}
+
 GSplatRenderer::Plan GSplatRenderer::planFrame() const
 {
     const int64_t budget = GSPLAT_COUNT_MAX - 1;
     Plan p;
-    float sum[3] = {0.0f, 0.0f, 0.0f};
     for (const auto& kv : table_) {
         const Row& r = kv.second;
         p.registered += r.count;
@@ -234,10 +281,8 @@ GSplatRenderer::Plan GSplatRenderer::planFrame() const
         p.total += take;
         p.wanted += r.count;
         p.sh = r.sh_count > 0;   // the row joined last decides
-        for (int k = 0; k < 3; ++k) sum[k] += r.origin[k];
     }
-    if (!p.parts.empty())
-        for (int k = 0; k < 3; ++k) p.origin[k] = sum[k] / static_cast<float>(p.parts.size());
+    planOrigin(p);
     return p;
 }
 
@@ -484,6 +529,12 @@ int gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const 
                                       int64_t* first_out, int64_t* n_out)
 {
     return h && id ? h->impl->updateAttributes(id, Cd, alpha, scale, orient, shx, shy, shz, first_out, n_out) : GSR_E_INVALID;
+}
+int gsplat_renderer_move_splats(gsplat_renderer* h, const char* id, const float* P, const float* origin, const uint16_t* Cd, const float* alpha,
+                                const uint16_t* scale, const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
+                                int64_t* first_out, int64_t* n_out)
+{
+    return h && id ? h->impl->moveSplats(id, P, origin, Cd, alpha, scale, orient, shx, shy, shz, first_out, n_out) : GSR_E_INVALID;
 }
 const void* gsplat_renderer_row_array(gsplat_renderer* h, const char* id, int what) { return h && id ? h->impl->rowArray(id, what) : nullptr; }
 int gsplat_renderer_get_target_format(gsplat_renderer* h) { return h ? h->impl->targetFormat() : GSR_E_INVALID; }

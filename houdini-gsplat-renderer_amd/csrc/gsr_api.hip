@@ -248,6 +248,12 @@ struct gsr_context {
     uint4* col = nullptr;              // colour halves as SoA chunks (eager colour in K1)
     uint4* colrow = nullptr;           // ... and as one contiguous row per splat (lazy colour gathers by index)
     int col_chunks = 0;
+    // gsr_move: the SPARE copy of the planes (at the capacity c->cap) that k_repack writes the new storage order into; the two sets are
+    // then swapped by pointer.  Allocated at the first move that re-orders, kept until the geometry is freed; the spare cluster bounds
+    // (nclus entries) go whenever an upload gives the live ones up.
+    float4* geoA2 = nullptr;
+    uint4 *geoB2 = nullptr, *col2 = nullptr, *colrow2 = nullptr;
+    float4 *clusA2 = nullptr, *clusB2 = nullptr;
     // spatially ordered storage (k_cluster.h): storage slot j holds the perm[j]-th splat of the upload; clusters of 64 slots
     uint32_t* perm = nullptr;          // NULL = upload order
     std::vector<int32_t> h_perm;       // host copy (debug read-backs un-permute through it), fetched on demand
@@ -525,6 +531,7 @@ static void free_geometry(gsr_context* c)
 {
     dev_free(c->geoA); dev_free(c->geoB); dev_free(c->col); dev_free(c->colrow);
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->nclus = 0; c->h_perm.clear();
+    dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(c->clusA2); dev_free(c->clusB2);
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_free_splat_arrays(c->slot[k]);
     c->cap = 0; c->n = 0;
 }
@@ -733,6 +740,7 @@ extern "C" int gsr_upload_begin(gsr_context* c, int64_t total, int has_sh, const
     for (int k = 0; k < 3; ++k) c->origin[k] = origin ? origin[k] : 0.0f;
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB);   // (the arrays are filled in upload order again)
+    dev_free(c->clusA2); dev_free(c->clusB2);
     c->nclus = 0; c->h_perm.clear();
     return GSR_OK;
 }
@@ -775,6 +783,7 @@ static void drop_geometry(gsr_context* c)
 {
     c->n = 0; c->nclus = 0; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->h_perm.clear();
+    dev_free(c->clusA2); dev_free(c->clusB2);
     c->has_geometry = false;           // gsr_render: GSR_E_NO_GEOMETRY (the generation is NOT rewound: stamps of the lost cloud stay stale)
     c->geo_gen++;
     dev_free(c->wire_inv); c->wire_inv_gen = 0;
@@ -858,6 +867,28 @@ extern "C" int gsr_upload_append_raw(gsr_context* c, int64_t n64, const gsr_raw_
     return GSR_OK;
 }
 
+// A new cloud is resident (the end of an upload, or of a move: the same splats at other positions are a new cloud to everything a
+// frame keeps): a new generation, and nothing the frames of the cloud before learned survives.
+static int new_cloud_state(gsr_context* c, const char* who)
+{
+    c->geo_gen++;
+    c->has_geometry = true;
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
+    c->prefix_valid = false;           // lazy colour: the first frame of a new cloud colours every list completely
+    c->order_pays = false;
+    c->cull_pol.on_upload(); c->slab_pol.on_upload();
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+        GsrSlotHints& h = c->slot[k].hints;
+        h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
+        c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
+    }
+    c->lazy_pays = false;              // ... and in automatic mode the first frames are eager until the kernels say it pays
+    // (the kernels' verdicts on the last frame of the PREVIOUS cloud must not reach the first frame of this one through the device word)
+    if (c->lazy_hint && hipMemsetAsync(c->lazy_hint, 0, 4, c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "%s: could not reset the policy word", who);
+    if (c->lazy_hint && hipStreamSynchronize(c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "%s: could not reset the policy word", who);
+    return GSR_OK;
+}
+
 extern "C" int gsr_upload_end(gsr_context* c)
 {
     if (!c || !c->uploading) return set_err(GSR_E_INVALID, "gsr_upload_end: no upload in progress");
@@ -876,21 +907,8 @@ extern "C" int gsr_upload_end(gsr_context* c)
             return rc;
         }
     }
-    c->geo_gen++;
-    c->has_geometry = true;
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
-    c->prefix_valid = false;           // lazy colour: the first frame of a new cloud colours every list completely
-    c->order_pays = false;
-    c->cull_pol.on_upload(); c->slab_pol.on_upload();
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
-        GsrSlotHints& h = c->slot[k].hints;
-        h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
-        c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
-    }
-    c->lazy_pays = false;              // ... and in automatic mode the first frames are eager until the kernels say it pays
-    // (the kernels' verdicts on the last frame of the PREVIOUS cloud must not reach the first frame of this one through the device word)
-    if (c->lazy_hint && hipMemsetAsync(c->lazy_hint, 0, 4, c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "upload: could not reset the policy word");
-    if (c->lazy_hint && hipStreamSynchronize(c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "upload: could not reset the policy word");
+    int rc = new_cloud_state(c, "upload");
+    if (rc) return rc;
     c->st.n_splats = c->n;
     c->st.uploads += 1;
     c->st.upload_ms[0] = c->up_h2d_ms;
@@ -1041,6 +1059,65 @@ static void cluster_grid(uint32_t nclus, int* rounds, uint32_t* ngroups)
     *ngroups = nclus ? div_up(nclus, (uint32_t)CC_THREADS * (uint32_t)r) : 0u;
 }
 
+// The ordering of a cloud, in the steps an upload and a move (gsr_move) share -- so both give the same storage order to the same
+// positions.  P: every position, upload order, device memory.
+// (1) the bounding box: bounds distance^2 to any camera, i.e. the sort-key range per frame -- and the Morton grid
+static int position_box(gsr_context* c, const float* P, uint32_t n, hipStream_t us, const char* who)
+{
+    const int grid = 512;
+    int rc = GSR_OK;
+    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)grid * 6))) return rc;
+    hipLaunchKernelGGL(k_bbox_partials, dim3(grid), dim3(256), 0, us, P, n, c->up_part);
+    std::vector<float> hp((size_t)grid * 6);
+    hipError_t e = hipMemcpyAsync(hp.data(), c->up_part, hp.size() * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) { c->bb_lo[k] = 3.0e38; c->bb_hi[k] = -3.0e38; }
+    for (int b = 0; b < grid; ++b)
+        for (int k = 0; k < 3; ++k) {
+            const float lo = hp[(size_t)b * 6 + k], hi = hp[(size_t)b * 6 + 3 + k];
+            ok = ok && std::isfinite(lo) && std::isfinite(hi);
+            c->bb_lo[k] = std::min(c->bb_lo[k], (double)lo);
+            c->bb_hi[k] = std::max(c->bb_hi[k], (double)hi);
+        }
+    c->bbox_ok = ok;
+    return GSR_OK;
+}
+// (2) the scratch of the sort: Morton codes / upload indices, ping-pong (kept between uploads and moves)
+static bool ensure_order_scratch(gsr_context* c, uint32_t n)
+{
+    if ((size_t)n <= c->up_sort_cap) return true;
+    dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
+    c->up_sort_cap = 0;
+    const size_t want = (size_t)n + n / 8 + 1024;
+    if (dev_alloc(&c->up_kA, want) || dev_alloc(&c->up_kB, want) || dev_alloc(&c->up_vA, want) || dev_alloc(&c->up_vB, want)) {
+        dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
+        (void)hipGetLastError();
+        return false;
+    }
+    c->up_sort_cap = want;
+    return true;
+}
+// (3) 30-bit Morton codes in the box of (1), sorted stably with the upload index as the value: perm[j] = upload index of the splat
+// in slot j (perm: n entries; the scratch of (2) is there)
+static int morton_order(gsr_context* c, const float* P, uint32_t n, uint32_t* perm, const char* who)
+{
+    FrameSlot& sl = c->slot[0];
+    float lo[3], sc[3];
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = (float)c->bb_lo[k];
+        const double ext = c->bb_hi[k] - c->bb_lo[k];
+        sc[k] = ext > 0.0 ? (float)(1023.999 / ext) : 0.0f;
+        if (!std::isfinite(sc[k])) sc[k] = 0.0f;
+    }
+    uint32_t *kA = c->up_kA, *kB = c->up_kB, *vA = c->up_vA, *vB = c->up_vB;
+    hipLaunchKernelGGL(k_morton_codes, dim3(div_up(n, 256)), dim3(256), 0, sl.stream, P, n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], kA, vA);
+    int rc = radix_sort(sl, kA, vA, kB, vB, n, 30, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);   // (leaves the result in what kA / vA name now)
+    if (!rc && hipMemcpyAsync(perm, vA, (size_t)n * 4, hipMemcpyDeviceToDevice, sl.stream) != hipSuccess) rc = set_err(GSR_E_HIP, "%s: storage order", who);
+    return rc;
+}
+
 static int order_and_pack(gsr_context* c)
 {
     const uint32_t n = c->n;
@@ -1051,55 +1128,15 @@ static int order_and_pack(gsr_context* c)
     for (int k = 0; k < 4; ++k)
         if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
     HIP_TRY(hipEventRecord(c->up_ev[0], us));
-    // bounding box of the positions: bounds distance^2 to any camera, i.e. the sort-key range per frame -- and the Morton grid
-    {
-        const int grid = 512;
-        if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)grid * 6))) return rc;
-        hipLaunchKernelGGL(k_bbox_partials, dim3(grid), dim3(256), 0, us, A.P, n, c->up_part);
-        std::vector<float> hp((size_t)grid * 6);
-        hipError_t e = hipMemcpyAsync(hp.data(), c->up_part, hp.size() * 4, hipMemcpyDeviceToHost, us);
-        if (e == hipSuccess) e = hipStreamSynchronize(us);
-        if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_end: %s", hipGetErrorString(e));
-        bool ok = true;
-        for (int k = 0; k < 3; ++k) { c->bb_lo[k] = 3.0e38; c->bb_hi[k] = -3.0e38; }
-        for (int b = 0; b < grid; ++b)
-            for (int k = 0; k < 3; ++k) {
-                const float lo = hp[(size_t)b * 6 + k], hi = hp[(size_t)b * 6 + 3 + k];
-                ok = ok && std::isfinite(lo) && std::isfinite(hi);
-                c->bb_lo[k] = std::min(c->bb_lo[k], (double)lo);
-                c->bb_hi[k] = std::max(c->bb_hi[k], (double)hi);
-            }
-        c->bbox_ok = ok;
-    }
+    if ((rc = position_box(c, A.P, n, us, "gsr_upload_end"))) return rc;
     // the storage order: perm[j] = upload index of the splat in slot j (NULL: upload order)
     dev_free(c->perm);
     if (c->opt_morton && c->bbox_ok && n > 1) {
-        bool have = true;
-        if ((size_t)n > c->up_sort_cap) {
-            dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
-            c->up_sort_cap = 0;
-            const size_t want = (size_t)n + n / 8 + 1024;
-            have = !(dev_alloc(&c->up_kA, want) || dev_alloc(&c->up_kB, want) || dev_alloc(&c->up_vA, want) || dev_alloc(&c->up_vB, want));
-            if (have) c->up_sort_cap = want;
-            else {
-                // without the scratch the splats simply stay in upload order (perm = NULL: ties then break by upload index, the
-                // documented meaning of an unordered store) and get their clusters
-                dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
-                (void)hipGetLastError();
-            }
-        }
+        // without the scratch the splats simply stay in upload order (perm = NULL: ties then break by upload index, the
+        // documented meaning of an unordered store) and get their clusters
+        const bool have = ensure_order_scratch(c, n);
         if (have && !(rc = dev_alloc(&c->perm, (size_t)n))) {
-            float lo[3], sc[3];
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = (float)c->bb_lo[k];
-                const double ext = c->bb_hi[k] - c->bb_lo[k];
-                sc[k] = ext > 0.0 ? (float)(1023.999 / ext) : 0.0f;
-                if (!std::isfinite(sc[k])) sc[k] = 0.0f;
-            }
-            uint32_t *kA = c->up_kA, *kB = c->up_kB, *vA = c->up_vA, *vB = c->up_vB;
-            hipLaunchKernelGGL(k_morton_codes, dim3(div_up(n, 256)), dim3(256), 0, us, A.P, n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], kA, vA);
-            rc = radix_sort(sl, kA, vA, kB, vB, n, 30, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);   // (leaves the result in what kA / vA name now)
-            if (!rc && hipMemcpyAsync(c->perm, vA, (size_t)n * 4, hipMemcpyDeviceToDevice, us) != hipSuccess) rc = set_err(GSR_E_HIP, "gsr_upload_end: storage order");
+            rc = morton_order(c, A.P, n, c->perm, "gsr_upload_end");
             if (rc) { dev_free(c->perm); return rc; }
         } else if (have) {
             (void)hipGetLastError();
@@ -1126,7 +1163,7 @@ static int order_and_pack(gsr_context* c)
 }
 
 // upload index -> storage slot: the inverse of the storage permutation, built once per geometry on slot 0's own stream and shared by
-// the wire overlay (k_wire.h) and gsr_update.  Only an upload changes the permutation (and the generation the inverse is stamped with).
+// the wire overlay (k_wire.h) and gsr_update.  Only an upload or a move (gsr_move) changes the permutation, and both count the generation the inverse is stamped with up.
 static int ensure_inverse_perm(gsr_context* c)
 {
     if (!c->perm || c->n == 0 || (c->wire_inv && c->wire_inv_gen == c->geo_gen)) return GSR_OK;
@@ -1222,6 +1259,138 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
     float ms = 0.0f;
     c->st.upload_ms[4] = h2d_ms;
     if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// New positions for resident splats ("Position updates").  Only the P rows cross the link; the ordering of an upload runs
+// over all positions (formed on the device in upload order), and k_repack carries the resident planes into the new storage order,
+// into a spare copy that is then swapped in.  Everything is allocated before the first write to resident memory.
+extern "C" int gsr_move(gsr_context* c, int64_t first, int64_t n64, const float* P, const float origin[3], const gsr_attr_update* u)
+{
+    if (!c || !P) return set_err(GSR_E_INVALID, "gsr_move: NULL argument");
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_move: upload in progress");
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_move: no geometry: nothing uploaded");
+    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
+        return set_err(GSR_E_INVALID, "gsr_move: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
+    const int nsh = u ? (u->shx ? 1 : 0) + (u->shy ? 1 : 0) + (u->shz ? 1 : 0) : 0;
+    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_move: the three SH arrays come together or not at all");
+    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_move: SH arrays for a cloud uploaded without SH");
+    if (n64 == 0) return GSR_OK;
+    const bool attrs = u && (u->Cd || u->alpha || u->scale || u->orient || nsh);
+    HIP_TRY(hipSetDevice(c->device));
+    const double t_begin = up_now_ms();
+    int rc = sync_all(c);      // no write under a frame in flight
+    if (rc) return rc;
+    const uint32_t n = c->n, cnt = (uint32_t)n64;
+    FrameSlot& sl = c->slot[0];
+    hipStream_t us = sl.stream;
+    // ---- everything the call needs, before the first write: an allocation failure leaves the context as it was
+    // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
+    const bool may_order = c->opt_morton && n > 1;
+    const size_t al = 256;
+    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
+    size_t upd_bytes = 0;      // what gsr_update stages of u (its own layout), so that it does not grow the arena behind this call's back
+    if (attrs)
+        upd_bytes = (u->alpha ? pad((size_t)cnt * 4) : 0) + (u->Cd ? pad((size_t)cnt * 6) : 0) + (u->scale ? pad((size_t)cnt * 6) : 0) +
+                    (u->orient ? pad((size_t)cnt * 8) : 0) + (nsh ? 3 * pad((size_t)cnt * 32) : 0);
+    const size_t oNew = 0, oAll = pad((size_t)cnt * 12), need = std::max(oAll + pad((size_t)n * 12), upd_bytes);
+    if (need > c->stage_cap) {
+        dev_free(c->stage);
+        c->stage_cap = 0;
+        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
+        c->stage_cap = need + 256;
+    }
+    uint32_t* perm_new = nullptr;
+    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
+    if (may_order) {
+        if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "gsr_move: no room for the sort of the storage order");
+        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+        if ((rc = dev_alloc(&perm_new, (size_t)n))) return rc;
+    }
+    if (may_order || c->perm) {
+        const size_t cap = c->cap;
+        if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
+                          (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
+            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(perm_new);
+            return rc;
+        }
+        if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
+            dev_free(c->clusA2); dev_free(c->clusB2); dev_free(perm_new);
+            return rc;
+        }
+    }
+    if ((rc = ensure_inverse_perm(c))) { dev_free(perm_new); return rc; }      // (the OLD order's inverse; built on slot 0's own stream)
+    for (int k = 0; k < 3; ++k)
+        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "gsr_move: no event"); }
+    if (hipStreamSynchronize(sl.own) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "gsr_move: the inverse of the storage order"); }
+    // ---- from here on a failure leaves no geometry (as a failed gsr_upload_end does)
+    auto lost = [&](int code) { dev_free(perm_new); drop_geometry(c); return code; };
+    double h2d_ms = 0.0;
+    // 1. the attributes of the same rows, through the old inverse: gsr_update as it is (it refuses nothing here that was not refused above)
+    if (attrs) {
+        rc = gsr_update(c, first, n64, u);
+        // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
+        //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
+        if (rc == GSR_E_HIP) return lost(rc);
+        if (rc) { dev_free(perm_new); return rc; }     // (refused before its first write)
+        h2d_ms = c->st.upload_ms[4];
+    }
+    // 2. the new rows where the splats sit now, and every position in upload order
+    const double t0 = up_now_ms();
+    float* const Pnew = reinterpret_cast<float*>(c->stage + oNew);
+    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
+    hipError_t e = hipMemcpyAsync(Pnew, P, (size_t)cnt * 12, hipMemcpyHostToDevice, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's array may be freed on return
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
+    h2d_ms += up_now_ms() - t0;
+    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, us, (uint32_t)first, cnt, n, Pnew, inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
+    // 3. the ordering of an upload
+    if ((rc = position_box(c, Pall, n, us, "gsr_move"))) return lost(rc);
+    const bool ordered = may_order && c->bbox_ok;
+    if (ordered && (rc = morton_order(c, Pall, n, perm_new, "gsr_move"))) return lost(rc);
+    if (!ordered) dev_free(perm_new);
+    e = hipEventRecord(c->up_ev[1], us);
+    // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
+    if (e == hipSuccess) {
+        if (perm_new || c->perm) {
+            if (c->has_sh)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
+                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
+                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+        } else {
+            hipLaunchKernelGGL(k_cluster_bounds, dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->geoA, c->geoB, c->clusA, c->clusB);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
+    // 5. the swap: nothing is in flight, and every frame takes the planes from the context
+    if (perm_new || c->perm) {
+        std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
+        std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
+        dev_free(c->perm);
+        c->perm = perm_new;
+        perm_new = nullptr;
+    }
+    c->h_perm.clear();
+    if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
+    if ((rc = new_cloud_state(c, "gsr_move"))) { drop_geometry(c); return rc; }   // (the policy word could not be reset: a HIP failure like any other)
+    c->st.moves += 1;
+    float ms = 0.0f;
+    c->st.move_ms[0] = h2d_ms;
+    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.move_ms[1] = ms;
+    if (hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess) c->st.move_ms[2] = ms;
+    c->st.move_ms[3] = up_now_ms() - t_begin;
     return GSR_OK;
 }
 
@@ -2887,12 +3056,14 @@ extern "C" int gsr_stats_reset(gsr_context* c)
             if (c->slot[k].lazy_ctr && hipMemcpy(&v, c->slot[k].lazy_ctr + 1, 8, hipMemcpyDeviceToHost) == hipSuccess) tot += v;
         c->lazy_base = (int64_t)tot;
     }
-    const int64_t ups = c->st.uploads;
-    double upm[6];
+    const int64_t ups = c->st.uploads, mvs = c->st.moves;
+    double upm[6], mvm[4];
     std::memcpy(upm, c->st.upload_ms, sizeof upm);      // (the last upload's figures describe the resident cloud: they outlive a reset)
+    std::memcpy(mvm, c->st.move_ms, sizeof mvm);        // (... and so do the moves': both are treated alike)
     c->st = gsr_stats{};
-    c->st.uploads = ups;
+    c->st.uploads = ups; c->st.moves = mvs;
     std::memcpy(c->st.upload_ms, upm, sizeof upm);
+    std::memcpy(c->st.move_ms, mvm, sizeof mvm);
     c->st.n_splats = ns;
     c->st.record_bytes = (int32_t)sizeof(GsrRecord);
     c->st.pair_bytes = 8;

@@ -580,6 +580,16 @@ extern "C" int gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gs
     return for_each_rank(m, [=](int g) { return gsr_update(m->ctx[g], first, n, u); });
 }
 
+// ... and moved on every rank: each orders and repacks its own replica
+extern "C" int gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u)
+{
+    if (!m || !P) return fail(GSR_E_INVALID, "gsr_multi_move: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_move: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return for_each_rank(m, [=](int g) { return gsr_move(m->ctx[g], first, n, P, origin, u); });
+}
+
 // ---- per frame ---------------------------------------------------------------------------------
 extern "C" int gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device)
 {

@@ -61,11 +61,45 @@ __device__ __forceinline__ uint4 gsr_colour_chunk(const uint16_t* row, int c)
     auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
     return make_uint4(pk(h[0], h[1]), pk(h[2], h[3]), pk(h[4], h[5]), pk(h[6], h[7]));
 }
+// The bounds of ONE cluster (k_cluster.h: clusA = lo.xyz of the positions + the largest extent bound, clusB = hi.xyz + "never cull"
+// flag), folded by a workgroup of GSR_PACK_THREADS in k_pack's shape: of a splat's eight lanes, lane 0 brings its position in lo = hi
+// (and bad = a non-finite coordinate), lane 7 its extent bound in mf (and bad = !(mf < 6e4)); every other lane, and every lane of a
+// slot behind n, brings the neutral values.  One function for k_pack, k_repack and k_cluster_bounds: the same operands meet in the
+// same order, so a cluster's bounds after gsr_move are bit for bit what a fresh upload gives it.
+#define GSR_PACK_THREADS 512
+__device__ __forceinline__ void gsr_cluster_fold(float (&lo)[3], float (&hi)[3], float mf, bool bad, float (&s_red)[8][8],
+                                                 float4* __restrict__ clusA, float4* __restrict__ clusB)
+{
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const bool any_bad = __ballot(bad) != 0ull;
+#pragma unroll
+    for (int d = 8; d < 64; d <<= 1) {     // (the position lanes are q = 0, the extent lanes q = 7: strides of eight)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = __builtin_fminf(lo[k], __shfl_xor(lo[k], d, 64));
+            hi[k] = __builtin_fmaxf(hi[k], __shfl_xor(hi[k], d, 64));
+        }
+        mf = __builtin_fmaxf(mf, __shfl_xor(mf, d, 64));
+    }
+    const int lane = tid & 63;
+    if (lane == 0) { s_red[wave][0] = lo[0]; s_red[wave][1] = lo[1]; s_red[wave][2] = lo[2]; s_red[wave][3] = hi[0]; s_red[wave][4] = hi[1]; s_red[wave][5] = hi[2]; s_red[wave][7] = any_bad ? 1.0f : 0.0f; }
+    if (lane == 7) s_red[wave][6] = mf;
+    __syncthreads();
+    if (tid == 0) {
+        float l0 = 3.0e38f, l1 = 3.0e38f, l2 = 3.0e38f, h0 = -3.0e38f, h1 = -3.0e38f, h2 = -3.0e38f, m = 0.0f, b = 0.0f;
+        for (int w = 0; w < 8; ++w) {
+            l0 = __builtin_fminf(l0, s_red[w][0]); l1 = __builtin_fminf(l1, s_red[w][1]); l2 = __builtin_fminf(l2, s_red[w][2]);
+            h0 = __builtin_fmaxf(h0, s_red[w][3]); h1 = __builtin_fmaxf(h1, s_red[w][4]); h2 = __builtin_fmaxf(h2, s_red[w][5]);
+            m = __builtin_fmaxf(m, s_red[w][6]); b = __builtin_fmaxf(b, s_red[w][7]);
+        }
+        clusA[blockIdx.x] = make_float4(l0, l1, l2, m);
+        clusB[blockIdx.x] = make_float4(h0, h1, h2, b != 0.0f ? 1.0f : 0.0f);
+    }
+}
 struct GsrPackSrc {
     const float* P; const float* alpha;
     const uint16_t *Cd, *scale, *orient, *shx, *shy, *shz;
 };
-#define GSR_PACK_THREADS 512
 template <bool SH>
 __global__ void __launch_bounds__(GSR_PACK_THREADS)
 k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ perm,
@@ -75,7 +109,7 @@ k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ pe
     static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = one cluster");
     __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad: 112 B rows)
     __shared__ float s_red[8][8];                                           // per wave: lo.xyz hi.xyz mf bad
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3, wave = tid >> 6;
+    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
     const uint32_t j = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
     const bool live = j < n;
     const uint32_t i = live ? (perm ? perm[j] : j) : 0u;
@@ -119,31 +153,7 @@ k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ pe
     // ... and as ONE 128-byte row per splat, gathered by index (lazy colour): piece q from lane q, the eight pieces of a row in ONE store
     // instruction (as three -- position, colours, padding -- a quarter of the rows went out as partial lines: PMC 1.16 x the output)
     if (SH && live) colrow[(size_t)j * 8 + q] = rowpiece;
-    // the cluster's bounds (k_cluster.h: clusA = lo.xyz of the positions + the largest extent bound, clusB = hi.xyz + "never cull" flag)
-    const bool any_bad = __ballot(bad) != 0ull;
-#pragma unroll
-    for (int d = 8; d < 64; d <<= 1) {     // (the position lanes are q = 0, the extent lanes q = 7: strides of eight)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = __builtin_fminf(lo[k], __shfl_xor(lo[k], d, 64));
-            hi[k] = __builtin_fmaxf(hi[k], __shfl_xor(hi[k], d, 64));
-        }
-        mf = __builtin_fmaxf(mf, __shfl_xor(mf, d, 64));
-    }
-    const int lane = tid & 63;
-    if (lane == 0) { s_red[wave][0] = lo[0]; s_red[wave][1] = lo[1]; s_red[wave][2] = lo[2]; s_red[wave][3] = hi[0]; s_red[wave][4] = hi[1]; s_red[wave][5] = hi[2]; s_red[wave][7] = any_bad ? 1.0f : 0.0f; }
-    if (lane == 7) s_red[wave][6] = mf;
-    __syncthreads();
-    if (tid == 0) {
-        float l0 = 3.0e38f, l1 = 3.0e38f, l2 = 3.0e38f, h0 = -3.0e38f, h1 = -3.0e38f, h2 = -3.0e38f, m = 0.0f, b = 0.0f;
-        for (int w = 0; w < 8; ++w) {
-            l0 = __builtin_fminf(l0, s_red[w][0]); l1 = __builtin_fminf(l1, s_red[w][1]); l2 = __builtin_fminf(l2, s_red[w][2]);
-            h0 = __builtin_fmaxf(h0, s_red[w][3]); h1 = __builtin_fmaxf(h1, s_red[w][4]); h2 = __builtin_fmaxf(h2, s_red[w][5]);
-            m = __builtin_fmaxf(m, s_red[w][6]); b = __builtin_fmaxf(b, s_red[w][7]);
-        }
-        clusA[blockIdx.x] = make_float4(l0, l1, l2, m);
-        clusB[blockIdx.x] = make_float4(h0, h1, h2, b != 0.0f ? 1.0f : 0.0f);
-    }
+    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA, clusB);
 }
 
 // ---------------------------------------------------------------------------
@@ -255,6 +265,107 @@ k_cluster_extents(uint32_t n, uint32_t nclus, const float4* __restrict__ geoA, c
         reinterpret_cast<float*>(clusA + c)[3] = mf;
         reinterpret_cast<float*>(clusB + c)[3] = any_bad ? 1.0f : 0.0f;
     }
+}
+
+// ---------------------------------------------------------------------------
+// K0m: new POSITIONS for resident splats (gsr_move).  A position decides the storage order, so a move is: the new rows written where
+// the splats sit now (k_move_positions), the ordering of an upload over ALL positions in upload order (k_bbox_partials,
+// k_morton_codes, the radix sort), and the resident planes carried from the old order into the new one (k_repack) -- nothing but
+// the new P rows crosses the link.
+// k_move_positions: one thread per resident splat i (upload order), old slot j = inv[i] (inv: the inverse of the storage permutation
+// in force; NULL: j = i).  Splats [first, first + cnt) take row i - first of Pnew into geoA[j].xyz and, with SH, into piece 0 of
+// their colour row (three 4-byte stores each; .w, the opacity, stays); the others keep what geoA holds, which is the raw P bits of
+// their upload.  Either way the position goes to Pup[3 i ..]: the whole cloud's positions in upload order, what the ordering reads.
+__global__ void __launch_bounds__(256)
+k_move_positions(uint32_t first, uint32_t cnt, uint32_t n, const float* __restrict__ Pnew, const uint32_t* __restrict__ inv,
+                 float4* __restrict__ geoA, uint4* __restrict__ colrow /* NULL: no SH */, float* __restrict__ Pup)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = inv ? inv[i] : i;
+    float px, py, pz;
+    if (i - first < cnt) {                             // (unsigned: also false for i < first)
+        const float* p = Pnew + 3 * (size_t)(i - first);
+        px = p[0]; py = p[1]; pz = p[2];
+        float* a = reinterpret_cast<float*>(geoA + j);
+        a[0] = px; a[1] = py; a[2] = pz;
+        if (colrow) {
+            float* r = reinterpret_cast<float*>(colrow + (size_t)j * 8);
+            r[0] = px; r[1] = py; r[2] = pz;
+        }
+    } else {
+        const float4 a = geoA[j];
+        px = a.x; py = a.y; pz = a.z;
+    }
+    float* o = Pup + 3 * (size_t)i;
+    o[0] = px; o[1] = py; o[2] = pz;
+}
+
+// k_repack: the resident planes from the old storage order into the new one, into the SPARE copy of the planes (the host swaps the
+// two sets afterwards).  One workgroup = one destination cluster of 64 slots, eight lanes per splat -- k_pack's shape:
+//   slot j' <- the splat i = perm_new[j'] (NULL: i = j'), which sits in slot j = inv_old[i] (NULL: j = i)
+// and lane q of the eight carries 16-byte pieces, one vector load and one vector store each:
+//   q = 0      geoA[j] -> geoA'[j'] (and the position into the cluster's box)
+//   q = 1..6   col[q - 1][j] -> col'[q - 1][j'] (chunks strided by the capacity; without SH there is only chunk 0)
+//   q = 7      geoB[j] -> geoB'[j'] (and its extent half into the cluster's bound)
+//   every q    colrow[j][q] -> colrow'[j'][q] (SH only): whole 128-byte lines in and out
+// Slots behind n in the last cluster are not written, as k_pack leaves them.  The cluster bounds come from gsr_cluster_fold.
+template <bool SH>
+__global__ void __launch_bounds__(GSR_PACK_THREADS)
+k_repack(uint32_t n, uint32_t cap, const uint32_t* __restrict__ perm_new, const uint32_t* __restrict__ inv_old,
+         const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col, const uint4* __restrict__ colrow,
+         float4* __restrict__ geoA2, uint4* __restrict__ geoB2, uint4* __restrict__ col2, uint4* __restrict__ colrow2,
+         float4* __restrict__ clusA2, float4* __restrict__ clusB2)
+{
+    static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = one cluster");
+    __shared__ float s_red[8][8];
+    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
+    const uint32_t jn = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
+    const bool live = jn < n;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mf = 0.0f;
+    bool bad = false;
+    if (live) {
+        const uint32_t i = perm_new ? perm_new[jn] : jn;
+        const uint32_t j = inv_old ? inv_old[i] : i;
+        if (SH) colrow2[(size_t)jn * 8 + q] = colrow[(size_t)j * 8 + q];
+        if (q == 0) {
+            const float4 a = geoA[j];
+            geoA2[jn] = a;
+            bad = !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
+            lo[0] = hi[0] = a.x; lo[1] = hi[1] = a.y; lo[2] = hi[2] = a.z;
+        } else if (q == 7) {
+            const uint4 b = geoB[j];
+            geoB2[jn] = b;
+            mf = gsr_h2f((uint16_t)(b.w >> 16));
+            bad = !(mf < 6.0e4f);
+        } else if (SH || q == 1) {
+            col2[(size_t)(q - 1) * cap + jn] = col[(size_t)(q - 1) * cap + j];
+        }
+    }
+    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA2, clusB2);
+}
+
+// ... and where no permutation is in force before or after the move (upload order kept): the splats stay where they are and only the
+// cluster bounds are formed again, in place, from the resident geoA / geoB -- k_repack without the copies.
+__global__ void __launch_bounds__(GSR_PACK_THREADS)
+k_cluster_bounds(uint32_t n, const float4* __restrict__ geoA, const uint4* __restrict__ geoB, float4* __restrict__ clusA, float4* __restrict__ clusB)
+{
+    __shared__ float s_red[8][8];
+    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
+    const uint32_t j = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mf = 0.0f;
+    bool bad = false;
+    if (j < n) {
+        if (q == 0) {
+            const float4 a = geoA[j];
+            bad = !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
+            lo[0] = hi[0] = a.x; lo[1] = hi[1] = a.y; lo[2] = hi[2] = a.z;
+        } else if (q == 7) {
+            mf = gsr_h2f((uint16_t)(geoB[j].w >> 16));
+            bad = !(mf < 6.0e4f);
+        }
+    }
+    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA, clusB);
 }
 
 // ---------------------------------------------------------------------------

@@ -45,12 +45,14 @@ class gsr_stats(C.Structure):
                 ("clusters_total", C.c_int64), ("clusters_kept", C.c_int64),
                 ("policy_bits", C.c_int32), ("cull_dilate", C.c_int32), ("cull_holdoff", C.c_int32), ("reserved2_", C.c_int32),
                 ("frames_resorted", C.c_int64), ("frames_slab", C.c_int64), ("frames_jumped", C.c_int64), ("frames_lazy", C.c_int64),
-                ("uploads", C.c_int64), ("upload_ms", C.c_double * 6)]
+                ("uploads", C.c_int64), ("upload_ms", C.c_double * 6),
+                ("moves", C.c_int64), ("move_ms", C.c_double * 4)]
 
     def as_dict(self) -> dict:
         d = {n: getattr(self, n) for n, _ in self._fields_}
         d["stage_ms_total"] = list(self.stage_ms_total)
         d["upload_ms"] = list(self.upload_ms)
+        d["move_ms"] = list(self.move_ms)
         return d
 
 
@@ -145,6 +147,7 @@ C_ABI_SYMBOLS = [
     "gsr_render_aov", "gsr_resolve_depth", "gsr_resolve_depth_device", "gsplat_renderer_set_aov_target",
     "gsr_render_over", "gsr_composite_over", "gsplat_renderer_set_background",
     "gsr_update", "gsr_multi_update", "gsr_debug_read_resident", "gsplat_renderer_update_attributes", "gsplat_renderer_row_array",
+    "gsr_move", "gsr_multi_move", "gsplat_renderer_move_splats",
 ]
 
 
@@ -180,6 +183,9 @@ def load_library() -> C.CDLL:
     L.gsr_upload_end.argtypes = [vp]
     L.gsr_update.argtypes = [vp, i64, i64, C.POINTER(gsr_attr_update)]
     L.gsr_multi_update.argtypes = [vp, i64, i64, C.POINTER(gsr_attr_update)]
+    L.gsr_move.argtypes = [vp, i64, i64, vp, f32p, C.POINTER(gsr_attr_update)]
+    L.gsr_multi_move.argtypes = [vp, i64, i64, vp, f32p, C.POINTER(gsr_attr_update)]
+    L.gsplat_renderer_move_splats.argtypes = [vp, C.c_char_p, vp, f32p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
@@ -427,6 +433,19 @@ def attr_update_struct(**arrays):
     return u, (n or 0), keep
 
 
+def move_arrays(P, **attrs):
+    """the arguments of gsr_move from P (float32, (n, 3)) and update_attrs' keyword arrays -> (P, n, gsr_attr_update, the arrays to keep
+    alive during the call); the attribute arrays must hold n rows"""
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    if P.size % 3:
+        raise GsrError(-1, f"move: P holds {P.size} values, not a multiple of 3")
+    n = P.size // 3
+    u, nu, keep = attr_update_struct(**attrs)
+    if keep and nu != n:
+        raise GsrError(-1, f"move: the attribute arrays hold {nu} splats, P {n}")
+    return P, n, u, keep
+
+
 class _Arrays:
     """contiguous, correctly typed views of a Splats-like object (kept alive during the call)"""
 
@@ -525,6 +544,14 @@ class Engine:
         arrays in the registerUpdate() layout (halves as uint16 bits), None = leave as is, n from the arrays.  No P: that is an upload."""
         u, n, keep = attr_update_struct(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
         _check(self.L.gsr_update(self.h, int(first), n, C.byref(u)))
+        return n
+
+    def move(self, first: int, P, origin=None, **attrs) -> int:
+        """gsr_move: new positions P (float32, (n, 3)) for the resident splats [first, first + n) (upload order), re-ordered on the GPU
+        with no re-upload; origin = the new GSplatOrigin (None: it stays); attrs = update_attrs' arrays for the same rows, applied in
+        the same call.  The context keeps a second copy of the resident planes from the first move on (include/gsplat_hip.h)."""
+        P, n, u, keep = move_arrays(P, **attrs)
+        _check(self.L.gsr_move(self.h, int(first), n, P.ctypes.data, None if origin is None else _f3(origin), C.byref(u)))
         return n
 
     def debug_resident(self, which: int) -> np.ndarray:
@@ -825,6 +852,22 @@ class GSplatRenderer:
                 self._updates.setdefault(rid, {})[k] = a
         return rc, first.value, cnt.value
 
+    def moveSplats(self, rid: str, P, origin=None, Cd=None, alpha=None, scale=None, orient=None, shx=None, shy=None, shz=None):
+        """GSplatRenderer::moveSplats: new positions (and optionally a new origin and new attribute arrays) for a registered primitive
+        whose point count did not change -> (rc, first, n) as updateAttributes returns them.  The arrays are BORROWED and kept alive
+        here, P included, in place of the ones they replace."""
+        given = dict(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
+        P, n, u, keep = move_arrays(P, **given)
+        first, cnt = C.c_int64(0), C.c_int64(0)
+        rc = int(self.L.gsplat_renderer_move_splats(self.h, rid.encode(), P.ctypes.data, None if origin is None else _f3(origin),
+                                                    u.Cd, u.alpha, u.scale, u.orient, u.shx, u.shy, u.shz, C.byref(first), C.byref(cnt)))
+        what = {"P": 0, "Cd": 1, "alpha": 2, "scale": 3, "orient": 4, "shx": 5, "shy": 6, "shz": 7}
+        names = ["P"] + [k for k, _, _ in UPDATE_ATTRS if given[k] is not None]
+        for k, a in zip(names, [P] + keep):
+            if self.rowArray(rid, what[k]) == a.ctypes.data:
+                self._updates.setdefault(rid, {})[k] = a
+        return rc, first.value, cnt.value
+
     def rowArray(self, rid: str, what: int) -> int:
         """address of the array a registered row holds now (0 P, 1 Cd, 2 alpha, 3 scale, 4 orient, 5..7 shx / shy / shz); 0 = none"""
         return int(self.L.gsplat_renderer_row_array(self.h, rid.encode(), int(what)) or 0)
@@ -983,6 +1026,12 @@ class MultiEngine:
         """gsr_multi_update: Engine.update_attrs on every rank"""
         u, n, keep = attr_update_struct(Cd=Cd, alpha=alpha, scale=scale, orient=orient, shx=shx, shy=shy, shz=shz)
         _check(self.L.gsr_multi_update(self.h, int(first), n, C.byref(u)))
+        return n
+
+    def move(self, first: int, P, origin=None, **attrs) -> int:
+        """gsr_multi_move: Engine.move on every rank"""
+        P, n, u, keep = move_arrays(P, **attrs)
+        _check(self.L.gsr_multi_move(self.h, int(first), n, P.ctypes.data, None if origin is None else _f3(origin), C.byref(u)))
         return n
 
     def render(self, cam, depth=None) -> np.ndarray:

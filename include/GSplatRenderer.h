@@ -118,6 +118,18 @@ public:
     int updateAttributes(const std::string& id, const uint16_t* splatColors, const float* splatAlphas, const uint16_t* splatScales,
                          const uint16_t* splatOrients, const uint16_t* splatShxs, const uint16_t* splatShys, const uint16_t* splatShzs,
                          int64_t* first_out, int64_t* n_out);
+    /* New POSITIONS (float[3 * count], BORROWED like the array they replace) for a registered primitive whose point count and topology
+     * did not change, with a new GSplatOrigin for the row (or NULL: it stays) and optionally new attribute arrays, as updateAttributes
+     * takes them, in the same call -- no reference counterpart; GR_Primitive::update would call it when P's data id changed and the
+     * point count did not.  Which splats those are, what is returned, and what happens to a row that is not resident
+     * are exactly as updateAttributes has it; the resident splats are moved by gsr_move / gsr_multi_move (re-ordered on the GPU, no
+     * re-upload; the engine then keeps a second copy of the resident planes: gsplat_hip.h).  The row keeps splatPts, so a later
+     * re-stage uploads the moved cloud.  With a new origin the resident pass's origin becomes the mean over its rows, as a re-stage
+     * would form it.  If registerUpdate() has retired another row of the resident plan since it was staged, the plan is stale: the row
+     * counts as not resident (0), and the next generateRenderGeometry() re-stages.  GSR_E_INVALID also for NULL splatPts. */
+    int moveSplats(const std::string& id, const float* splatPts, const float* splatOrigin, const uint16_t* splatColors,
+                   const float* splatAlphas, const uint16_t* splatScales, const uint16_t* splatOrients, const uint16_t* splatShxs,
+                   const uint16_t* splatShys, const uint16_t* splatShzs, int64_t* first_out, int64_t* n_out);
     /* introspection (no reference counterpart; used by tests and the C wrappers) */
     /* debug door: the (borrowed) array a row holds now, i.e. what the next re-stage uploads: what = 0 P, 1 Cd, 2 alpha, 3 scale,
      * 4 orient, 5 shx, 6 shy, 7 shz; NULL for an unknown id */
@@ -172,6 +184,10 @@ private:
         }
     };
     Plan planFrame() const;
+    void planOrigin(Plan& p) const;     /* p.origin = the mean of its rows' origins */
+    int editRow(const std::string& id, const float* splatPts, const float* splatOrigin, const uint16_t* splatColors, const float* splatAlphas,
+                const uint16_t* splatScales, const uint16_t* splatOrients, const uint16_t* splatShxs, const uint16_t* splatShys,
+                const uint16_t* splatShzs, int64_t* first_out, int64_t* n_out);
     bool upload(const Plan& p);
 
     std::map<std::string, Row> table_;
@@ -233,6 +249,11 @@ int  gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const
                                        const uint16_t* scale, const uint16_t* orient,
                                        const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
                                        int64_t* first_out, int64_t* n_out);
+/* GSplatRenderer::moveSplats */
+int  gsplat_renderer_move_splats(gsplat_renderer* h, const char* id, const float* P, const float* origin, const uint16_t* Cd,
+                                 const float* alpha, const uint16_t* scale, const uint16_t* orient,
+                                 const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
+                                 int64_t* first_out, int64_t* n_out);
 const void* gsplat_renderer_row_array(gsplat_renderer* h, const char* id, int what);
 int  gsplat_renderer_get_target_format(gsplat_renderer* h);               /* the format in use; <0 for a NULL handle */
 int64_t gsplat_renderer_query(gsplat_renderer* h, int what, const char* id_or_null);

@@ -112,6 +112,10 @@ typedef struct gsr_stats {
                                               attributes included), [1] bounding box + Morton codes + their sort (HIP events), [2] k_pack: the arrays into
                                               storage order + cluster bounds (HIP events), [3] wall clock gsr_upload_begin .. gsr_upload_end; the LAST gsr_update: [4] its host ->
                                               device copies (wall clock), [5] its kernels (k_update + the cluster bounds, HIP events); 0 before the first one */
+    int64_t moves;                         /* gsr_move calls that moved splats (uploads does not count them); kept by gsr_stats_reset as uploads is */
+    double move_ms[4];                     /* the LAST gsr_move: [0] host -> device copies (the P rows, and the arrays of u; wall clock), [1] the new rows into
+                                              place + every position in upload order + bounding box + Morton codes + their sort (HIP events), [2] k_repack:
+                                              the planes into the new storage order + cluster bounds (HIP events), [3] wall clock of the call */
 } gsr_stats;
 
 /* ---- lifetime ----------------------------------------------------------- */
@@ -202,8 +206,8 @@ int  gsr_upload(gsr_context* ctx, int64_t n,
  * layout above, holding rows for the splats [first, first + n) only; first counts in UPLOAD order across all the entries that were
  * appended (so a caller who concatenated several entries addresses one of them by the running sum of their sizes).  NULL = that
  * attribute stays as it is.  shx / shy / shz come all three or not at all, and only for a cloud uploaded with SH.
- * There is NO P: a position decides the storage order, the bounding box and the cluster boxes -- moving a point is a re-upload.
- * Also not covered: raw float32 sources (gsr_raw_attrs: quantise on the host, or re-upload) and device-pointer sources.
+ * There is NO P: a position decides the storage order, the bounding box and the cluster boxes -- moving a point is gsr_move below.
+ * Not covered: raw float32 sources (gsr_raw_attrs: quantise on the host, or re-upload) and device-pointer sources.
  * Synchronous like gsr_upload_append (the arrays may be freed on return); it first waits for every frame of the context that is
  * still in flight, so no frame ever reads a half-written splat.
  * CONTRACT: after GSR_OK the resident geometry is bit for bit what a fresh context holds after gsr_upload of the edited arrays
@@ -219,6 +223,29 @@ typedef struct gsr_attr_update {
     const uint16_t *shx, *shy, *shz;  /* half[16n] each */
 } gsr_attr_update;
 int  gsr_update(gsr_context* ctx, int64_t first, int64_t n, const gsr_attr_update* u);
+
+/* ---- position update (resident splats moved, and re-ordered on the GPU) ----- */
+/* New positions for the resident splats [first, first + n) (UPLOAD order, as gsr_update counts), and optionally new attributes for the
+ * same rows in the same call.  P: float[3n] HOST pointer, required.  origin: float[3] = the new GSplatOrigin, or NULL = it stays.
+ * u: as gsr_update takes it (rows for the same range), or NULL.  Synchronous like gsr_update; waits for every frame in flight first.
+ * Only P (and the arrays of u) cross the link: 12 bytes per moved splat.  On the device the attributes are applied first (gsr_update
+ * as it is), the new rows are written where the splats sit, all positions are put in upload order and go through the ordering of an
+ * upload (bounding box, Morton codes, sort), and the resident planes are carried into the new storage order.
+ * CONTRACT: after GSR_OK the resident geometry -- geoA, geoB, every colour chunk, the colour rows, the cluster bounds and the storage
+ * order -- is bit for bit what a fresh context holds after gsr_upload of the edited arrays (same GSR_OPT_STORAGE_ORDER, same SH
+ * presence, the origin now in force), and so is every later frame, in every option mode.  Whatever a frame of the cloud before left
+ * (cached orders, horizons, hints, policies) is dropped as an upload drops it.
+ * MEMORY: a context that moves splats under GSR_OPT_STORAGE_ORDER = 1 keeps a SECOND copy of the resident planes (the re-ordered
+ * planes are written there and the two sets swapped): 16 + 16 + 16 x chunks (+ 128 with SH) bytes per splat of capacity -- about
+ * 1.5 GB at 6 M splats with SH -- from the first move until the capacity changes or the context is destroyed.  With
+ * GSR_OPT_STORAGE_ORDER = 0 the splats stay where they are; only the cluster bounds are formed again, and there is no second copy.
+ * GSR_E_INVALID, with the context untouched: NULL ctx or P; no geometry resident; an upload in progress; a bad range; the gsr_update
+ * rules for u.  n == 0: GSR_OK, nothing happens.  Everything is allocated before the first write: GSR_E_OOM leaves the context
+ * untouched.  A HIP failure after that leaves NO geometry (gsr_render: GSR_E_NO_GEOMETRY until the next complete upload); with
+ * attributes in u that includes ANY HIP failure of the gsr_update step, also one before its own first write.
+ * gsr_stats.uploads does not count a move; moves and move_ms[] do.  Not covered: raw float32 and device-pointer sources; a change of
+ * the splat count (that is an upload). */
+int  gsr_move(gsr_context* ctx, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
 
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
@@ -278,6 +305,8 @@ int  gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const uint16_t* C
                       const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, const float origin[3]);
 /* gsr_update on every rank (the cloud is replicated); synchronises the frames and the gather in flight first */
 int  gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_update* u);
+/* gsr_move on every rank, after the same synchronisation (every rank then keeps its own second copy of the planes) */
+int  gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
