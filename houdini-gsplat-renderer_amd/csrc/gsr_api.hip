@@ -1175,6 +1175,29 @@ static int ensure_inverse_perm(gsr_context* c)
     return GSR_OK;
 }
 
+// What the resident cloud's frames may keep after an attribute update (the invalidation table).  The cached depth orders go
+// in every case: their records hold the colours.  Colours change neither visibility, order nor opacity: horizons, prefixes, hints and
+// policies survive a Cd / SH update; anything else (`shape`: alpha, scale or orient changed) is treated like a new cloud at the same
+// positions.  e: the state of the call so far; the first failure is what comes back.
+static hipError_t after_update(gsr_context* c, bool shape, hipStream_t us, hipError_t e)
+{
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
+    if (shape) {
+        c->prefix_valid = false;
+        c->order_pays = false;
+        c->cull_pol.on_upload(); c->slab_pol.on_upload();
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+            GsrSlotHints& h = c->slot[k].hints;
+            h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
+            c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
+        }
+        c->lazy_pays = false;
+        if (e == hipSuccess && c->lazy_hint) e = hipMemsetAsync(c->lazy_hint, 0, 4, us);
+        if (e == hipSuccess && c->lazy_hint) e = hipStreamSynchronize(us);
+    }
+    return e;
+}
+
 // ---------------------------------------------------------------------------
 // Attributes of resident splats rewritten in place ("Attribute updates").  No position: the storage order, the bounding
 // box, the Morton scratch and the cluster boxes' xyz depend on P alone and stay as they are.
@@ -1238,27 +1261,129 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
     }
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);
-    // What the resident cloud's frames may keep (the invalidation table).  The cached depth orders go in every case: their
-    // records hold the colours.  Colours change neither visibility, order nor opacity: horizons, prefixes, hints and policies survive
-    // a Cd / SH update; anything else is treated like a new cloud at the same positions.
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
-    if (u->alpha || extents) {
-        c->prefix_valid = false;
-        c->order_pays = false;
-        c->cull_pol.on_upload(); c->slab_pol.on_upload();
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
-            GsrSlotHints& h = c->slot[k].hints;
-            h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
-            c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
-        }
-        c->lazy_pays = false;
-        if (e == hipSuccess && c->lazy_hint) e = hipMemsetAsync(c->lazy_hint, 0, 4, us);
-        if (e == hipSuccess && c->lazy_hint) e = hipStreamSynchronize(us);
-    }
+    e = after_update(c, u->alpha || extents, us, e);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_update: %s", hipGetErrorString(e));
     float ms = 0.0f;
     c->st.upload_ms[4] = h2d_ms;
     if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The body of gsr_move and gsr_move_device, behind their refusals.  new_bytes: what the new rows take at the head of the arena (0: they
+// stay in the caller's device memory); upd_bytes: what the attribute step stages there; attr_step(): the update verb for the same rows
+// (attrs: whether there is one; it leaves its link time in upload_ms[4]); new_rows(arena, stream, &Pnew, &h2d_ms): the device pointer
+// of the new rows, after whatever copy brings them there.
+template <class AttrStep, class NewRows>
+static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64, const float origin[3], size_t new_bytes, size_t upd_bytes,
+                     bool attrs, AttrStep&& attr_step, NewRows&& new_rows)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    const double t_begin = up_now_ms();
+    int rc = sync_all(c);      // no write under a frame in flight
+    if (rc) return rc;
+    const uint32_t n = c->n, cnt = (uint32_t)n64;
+    FrameSlot& sl = c->slot[0];
+    hipStream_t us = sl.stream;
+    // ---- everything the call needs, before the first write: an allocation failure leaves the context as it was
+    // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
+    const bool may_order = c->opt_morton && n > 1;
+    const size_t al = 256;
+    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t oNew = 0, oAll = pad(new_bytes), need = std::max(oAll + pad((size_t)n * 12), upd_bytes);
+    if (need > c->stage_cap) {
+        dev_free(c->stage);
+        c->stage_cap = 0;
+        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
+        c->stage_cap = need + 256;
+    }
+    uint32_t* perm_new = nullptr;
+    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
+    if (may_order) {
+        if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
+        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+        if ((rc = dev_alloc(&perm_new, (size_t)n))) return rc;
+    }
+    if (may_order || c->perm) {
+        const size_t cap = c->cap;
+        if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
+                          (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
+            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(perm_new);
+            return rc;
+        }
+        if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
+            dev_free(c->clusA2); dev_free(c->clusB2); dev_free(perm_new);
+            return rc;
+        }
+    }
+    if ((rc = ensure_inverse_perm(c))) { dev_free(perm_new); return rc; }      // (the OLD order's inverse; built on slot 0's own stream)
+    for (int k = 0; k < 3; ++k)
+        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "%s: no event", who); }
+    if (hipStreamSynchronize(sl.own) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "%s: the inverse of the storage order", who); }
+    // ---- from here on a failure leaves no geometry (as a failed gsr_upload_end does)
+    auto lost = [&](int code) { dev_free(perm_new); drop_geometry(c); return code; };
+    double h2d_ms = 0.0;
+    // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
+    if (attrs) {
+        rc = attr_step();
+        // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
+        //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
+        if (rc == GSR_E_HIP) return lost(rc);
+        if (rc) { dev_free(perm_new); return rc; }     // (refused before its first write)
+        h2d_ms = c->st.upload_ms[4];
+    }
+    // 2. the new rows where the splats sit now, and every position in upload order
+    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
+    const float* Pnew = nullptr;       // the new rows, in device memory
+    hipError_t e = new_rows(reinterpret_cast<float*>(c->stage + oNew), us, &Pnew, &h2d_ms);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, us, (uint32_t)first, cnt, n, Pnew, inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    // 3. the ordering of an upload
+    if ((rc = position_box(c, Pall, n, us, who))) return lost(rc);
+    const bool ordered = may_order && c->bbox_ok;
+    if (ordered && (rc = morton_order(c, Pall, n, perm_new, who))) return lost(rc);
+    if (!ordered) dev_free(perm_new);
+    e = hipEventRecord(c->up_ev[1], us);
+    // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
+    if (e == hipSuccess) {
+        if (perm_new || c->perm) {
+            if (c->has_sh)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
+                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
+                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+        } else {
+            hipLaunchKernelGGL(k_cluster_bounds, dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->geoA, c->geoB, c->clusA, c->clusB);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    // 5. the swap: nothing is in flight, and every frame takes the planes from the context
+    if (perm_new || c->perm) {
+        std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
+        std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
+        dev_free(c->perm);
+        c->perm = perm_new;
+        perm_new = nullptr;
+    }
+    c->h_perm.clear();
+    if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
+    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }   // (the policy word could not be reset: a HIP failure like any other)
+    c->st.moves += 1;
+    float ms = 0.0f;
+    c->st.move_ms[0] = h2d_ms;
+    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.move_ms[1] = ms;
+    if (hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess) c->st.move_ms[2] = ms;
+    c->st.move_ms[3] = up_now_ms() - t_begin;
     return GSR_OK;
 }
 
@@ -1278,120 +1403,188 @@ extern "C" int gsr_move(gsr_context* c, int64_t first, int64_t n64, const float*
     if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_move: SH arrays for a cloud uploaded without SH");
     if (n64 == 0) return GSR_OK;
     const bool attrs = u && (u->Cd || u->alpha || u->scale || u->orient || nsh);
-    HIP_TRY(hipSetDevice(c->device));
-    const double t_begin = up_now_ms();
-    int rc = sync_all(c);      // no write under a frame in flight
-    if (rc) return rc;
-    const uint32_t n = c->n, cnt = (uint32_t)n64;
-    FrameSlot& sl = c->slot[0];
-    hipStream_t us = sl.stream;
-    // ---- everything the call needs, before the first write: an allocation failure leaves the context as it was
-    // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
-    const bool may_order = c->opt_morton && n > 1;
     const size_t al = 256;
     auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t cnt = (size_t)n64;
     size_t upd_bytes = 0;      // what gsr_update stages of u (its own layout), so that it does not grow the arena behind this call's back
     if (attrs)
-        upd_bytes = (u->alpha ? pad((size_t)cnt * 4) : 0) + (u->Cd ? pad((size_t)cnt * 6) : 0) + (u->scale ? pad((size_t)cnt * 6) : 0) +
-                    (u->orient ? pad((size_t)cnt * 8) : 0) + (nsh ? 3 * pad((size_t)cnt * 32) : 0);
-    const size_t oNew = 0, oAll = pad((size_t)cnt * 12), need = std::max(oAll + pad((size_t)n * 12), upd_bytes);
-    if (need > c->stage_cap) {
-        dev_free(c->stage);
-        c->stage_cap = 0;
-        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
-        c->stage_cap = need + 256;
+        upd_bytes = (u->alpha ? pad(cnt * 4) : 0) + (u->Cd ? pad(cnt * 6) : 0) + (u->scale ? pad(cnt * 6) : 0) +
+                    (u->orient ? pad(cnt * 8) : 0) + (nsh ? 3 * pad(cnt * 32) : 0);
+    return move_body(c, "gsr_move", first, n64, origin, cnt * 12, upd_bytes, attrs,
+                     [&]() { return gsr_update(c, first, n64, u); },
+                     [&](float* arena, hipStream_t us, const float** Pnew, double* h2d_ms) {
+                         const double t0 = up_now_ms();
+                         hipError_t e = hipMemcpyAsync(arena, P, cnt * 12, hipMemcpyHostToDevice, us);
+                         if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's array may be freed on return
+                         *h2d_ms += up_now_ms() - t0;
+                         *Pnew = arena;
+                         return e;
+                     });
+}
+
+// ---------------------------------------------------------------------------
+// Device sources ("Device sources"): upload, update and move from float32 arrays that already sit in device memory.
+// What the three verbs ask of a source pointer, before anything is written or launched -- a wrong pointer must never be found out by
+// a kernel: 4-byte aligned; device memory of the context's device, or pinned host memory; and, where the runtime reports the
+// allocation's range, every byte inside it.  Pageable host memory fails the attribute query or comes back "unregistered", depending
+// on the ROCm version: both are refused, and the runtime's sticky error is cleared.
+static int check_device_source(gsr_context* c, const void* p, size_t bytes, const char* who, const char* name)
+{
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return set_err(GSR_E_INVALID, "%s: %s is not 4-byte aligned", who, name);
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_INVALID, "%s: %s is not device memory (the runtime does not know the pointer)", who, name);
     }
-    uint32_t* perm_new = nullptr;
-    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
-    if (may_order) {
-        if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "gsr_move: no room for the sort of the storage order");
-        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
-        if ((rc = dev_alloc(&perm_new, (size_t)n))) return rc;
+    if (at.type == hipMemoryTypeDevice) {
+        if (at.device != c->device) return set_err(GSR_E_INVALID, "%s: %s is memory of device %d, the context renders on device %d", who, name, at.device, c->device);
+    } else if (at.type != hipMemoryTypeHost) {      // (host = pinned: hipHostMalloc, hipHostRegister)
+        return set_err(GSR_E_INVALID, "%s: %s is neither device memory nor pinned host memory (memory type %d)", who, name, (int)at.type);
     }
-    if (may_order || c->perm) {
-        const size_t cap = c->cap;
-        if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
-                          (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
-            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(perm_new);
-            return rc;
-        }
-        if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
-            dev_free(c->clusA2); dev_free(c->clusB2); dev_free(perm_new);
-            return rc;
-        }
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, reinterpret_cast<hipDeviceptr_t>(const_cast<void*>(p))) != hipSuccess) {
+        (void)hipGetLastError();                     // (no range on record: the type is what there is to go by)
+        return GSR_OK;
     }
-    if ((rc = ensure_inverse_perm(c))) { dev_free(perm_new); return rc; }      // (the OLD order's inverse; built on slot 0's own stream)
-    for (int k = 0; k < 3; ++k)
-        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "gsr_move: no event"); }
-    if (hipStreamSynchronize(sl.own) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "gsr_move: the inverse of the storage order"); }
-    // ---- from here on a failure leaves no geometry (as a failed gsr_upload_end does)
-    auto lost = [&](int code) { dev_free(perm_new); drop_geometry(c); return code; };
-    double h2d_ms = 0.0;
-    // 1. the attributes of the same rows, through the old inverse: gsr_update as it is (it refuses nothing here that was not refused above)
-    if (attrs) {
-        rc = gsr_update(c, first, n64, u);
-        // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
-        //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
-        if (rc == GSR_E_HIP) return lost(rc);
-        if (rc) { dev_free(perm_new); return rc; }     // (refused before its first write)
-        h2d_ms = c->st.upload_ms[4];
-    }
-    // 2. the new rows where the splats sit now, and every position in upload order
-    const double t0 = up_now_ms();
-    float* const Pnew = reinterpret_cast<float*>(c->stage + oNew);
-    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
-    hipError_t e = hipMemcpyAsync(Pnew, P, (size_t)cnt * 12, hipMemcpyHostToDevice, us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's array may be freed on return
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
-    h2d_ms += up_now_ms() - t0;
-    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, us, (uint32_t)first, cnt, n, Pnew, inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
-    // 3. the ordering of an upload
-    if ((rc = position_box(c, Pall, n, us, "gsr_move"))) return lost(rc);
-    const bool ordered = may_order && c->bbox_ok;
-    if (ordered && (rc = morton_order(c, Pall, n, perm_new, "gsr_move"))) return lost(rc);
-    if (!ordered) dev_free(perm_new);
-    e = hipEventRecord(c->up_ev[1], us);
-    // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
-    if (e == hipSuccess) {
-        if (perm_new || c->perm) {
-            if (c->has_sh)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
-                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
-                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-        } else {
-            hipLaunchKernelGGL(k_cluster_bounds, dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->geoA, c->geoB, c->clusA, c->clusB);
-        }
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "gsr_move: %s", hipGetErrorString(e)));
-    // 5. the swap: nothing is in flight, and every frame takes the planes from the context
-    if (perm_new || c->perm) {
-        std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
-        std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
-        dev_free(c->perm);
-        c->perm = perm_new;
-        perm_new = nullptr;
-    }
-    c->h_perm.clear();
-    if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
-    if ((rc = new_cloud_state(c, "gsr_move"))) { drop_geometry(c); return rc; }   // (the policy word could not be reset: a HIP failure like any other)
-    c->st.moves += 1;
-    float ms = 0.0f;
-    c->st.move_ms[0] = h2d_ms;
-    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.move_ms[1] = ms;
-    if (hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess) c->st.move_ms[2] = ms;
-    c->st.move_ms[3] = up_now_ms() - t_begin;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_p = reinterpret_cast<uintptr_t>(p);
+    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo))
+        return set_err(GSR_E_INVALID, "%s: %s: %zu bytes from the pointer reach past the end of its allocation (%zu bytes left)", who, name, bytes,
+                       at_p >= lo && at_p - lo <= size ? size - (at_p - lo) : (size_t)0);
     return GSR_OK;
+}
+
+extern "C" int gsr_debug_check_device_source(gsr_context* c, const void* p, int64_t bytes)
+{
+    if (!c || !p || bytes < 0) return set_err(GSR_E_INVALID, "gsr_debug_check_device_source: bad argument");
+    return check_device_source(c, p, (size_t)bytes, "gsr_debug_check_device_source", "the pointer");
+}
+
+// every non-NULL array of a, for n rows (sh_vec3_per_point is in range when sh is given: the callers looked)
+static int check_device_attrs(gsr_context* c, const gsr_device_attrs* a, size_t n, const char* who)
+{
+    int rc = GSR_OK;
+    auto look = [&](const float* p, size_t floats_per_row, const char* name) {
+        if (p && !rc) rc = check_device_source(c, p, n * floats_per_row * 4, who, name);
+    };
+    look(a->P, 3, "P"); look(a->Cd, 3, "Cd"); look(a->alpha, 1, "alpha"); look(a->scale, 3, "scale"); look(a->orient, 4, "orient");
+    look(a->sh, a->sh ? (size_t)a->sh_vec3_per_point * 3 : 0, "sh");
+    return rc;
+}
+
+extern "C" int gsr_upload_append_device(gsr_context* c, int64_t n64, const gsr_device_attrs* a)
+{
+    if (!c || !c->uploading) return set_err(GSR_E_INVALID, "gsr_upload_append_device: no upload in progress");
+    if (!a) return set_err(GSR_E_INVALID, "gsr_upload_append_device: attrs is NULL");
+    if (n64 < 0 || (uint64_t)n64 + c->up_filled > c->up_total)
+        return set_err(GSR_E_INVALID, "gsr_upload_append_device: %lld splats exceed the %u announced", (long long)n64, c->up_total);
+    if (n64 == 0) return GSR_OK;
+    if (!a->P) return set_err(GSR_E_INVALID, "gsr_upload_append_device: P is NULL");
+    if (c->has_sh != (a->sh != nullptr)) return set_err(GSR_E_INVALID, "gsr_upload_append_device: SH presence differs from gsr_upload_begin");
+    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
+        return set_err(GSR_E_INVALID, "gsr_upload_append_device: sh_vec3_per_point = %d is not within 1..16", a->sh_vec3_per_point);
+    const uint32_t n = (uint32_t)n64;
+    int rc = check_device_attrs(c, a, n, "gsr_upload_append_device");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));          // a producer queued on the public stream has finished
+    const size_t at = c->up_filled;
+    hipStream_t us = c->slot[0].own;
+    const UpArena A = up_arena(c->stage, c->up_total, c->has_sh);
+    // P and alpha as they are, behind the entries before this one (the runtime picks the direction: a source may be pinned host memory);
+    // the rest is quantised straight from the caller's arrays
+    hipError_t e = hipMemcpyAsync(A.P + 3 * at, a->P, (size_t)n * 12, hipMemcpyDefault, us);
+    if (e == hipSuccess)
+        e = a->alpha ? hipMemcpyAsync(A.alpha + at, a->alpha, (size_t)n * 4, hipMemcpyDefault, us)
+                     : hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(A.alpha + at), 0x3f800000, n, us);      // missing opacity: opaque
+    if (e == hipSuccess) {
+        GsrRawSh sh{};
+        sh.scheme = a->sh ? 1 : 0;
+        sh.vec3_per_point = a->sh_vec3_per_point;
+        sh.array = a->sh;
+        hipLaunchKernelGGL(k_quantize_raw, dim3(div_up(n, 256)), dim3(256), 0, us, n, a->Cd, a->scale, a->orient, sh, A.Cd + 3 * at, A.scale + 3 * at, A.orient + 4 * at,
+                           c->has_sh ? A.shx + 16 * at : (uint16_t*)nullptr, c->has_sh ? A.shy + 16 * at : (uint16_t*)nullptr, c->has_sh ? A.shz + 16 * at : (uint16_t*)nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_append_device: %s", hipGetErrorString(e));
+    c->up_filled += n;
+    return GSR_OK;
+}
+
+// what gsr_update_device and gsr_move_device refuse of a before they look at its pointers (the range is the caller's to check first)
+static int refuse_device_update(gsr_context* c, const gsr_device_attrs* a, const char* who)
+{
+    if (a->sh && !c->has_sh) return set_err(GSR_E_INVALID, "%s: sh for a cloud uploaded without SH", who);
+    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
+        return set_err(GSR_E_INVALID, "%s: sh_vec3_per_point = %d is not within 1..16", who, a->sh_vec3_per_point);
+    return GSR_OK;
+}
+
+// gsr_update_device behind its refusals: gsr_update without the staging -- k_update_f32 reads the caller's rows where they are
+static int update_device_rows(gsr_context* c, int64_t first, uint32_t n, const gsr_device_attrs* a, const char* who)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);      // the public stream (a producer queued there has finished), and no in-place write under a frame in flight
+    if (rc) return rc;
+    hipStream_t us = c->slot[0].own;
+    if ((rc = ensure_inverse_perm(c))) return rc;
+    for (int k = 0; k < 2; ++k)
+        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
+    const GsrUpdateSrcF32 src{a->alpha, a->Cd, a->scale, a->orient, a->sh, a->sh ? a->sh_vec3_per_point : 0};
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    const bool extents = a->scale || a->orient;
+    hipError_t e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        if (c->has_sh)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<true>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<false>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+        if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
+    e = after_update(c, a->alpha || extents, us, e);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    float ms = 0.0f;
+    c->st.upload_ms[4] = 0.0;  // nothing crossed the link
+    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
+    return GSR_OK;
+}
+
+extern "C" int gsr_update_device(gsr_context* c, int64_t first, int64_t n64, const gsr_device_attrs* a)
+{
+    if (!c || !a) return set_err(GSR_E_INVALID, "gsr_update_device: NULL argument");
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_update_device: upload in progress");
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_update_device: no geometry: nothing uploaded");
+    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
+        return set_err(GSR_E_INVALID, "gsr_update_device: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
+    if (a->P) return set_err(GSR_E_INVALID, "gsr_update_device: P is given: a position is gsr_move_device");
+    int rc = refuse_device_update(c, a, "gsr_update_device");
+    if (rc) return rc;
+    if (n64 == 0 || !(a->Cd || a->alpha || a->scale || a->orient || a->sh)) return GSR_OK;
+    if ((rc = check_device_attrs(c, a, (size_t)n64, "gsr_update_device"))) return rc;
+    return update_device_rows(c, first, (uint32_t)n64, a, "gsr_update_device");
+}
+
+extern "C" int gsr_move_device(gsr_context* c, int64_t first, int64_t n64, const float origin[3], const gsr_device_attrs* a)
+{
+    if (!c || !a) return set_err(GSR_E_INVALID, "gsr_move_device: NULL argument");
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_move_device: upload in progress");
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_move_device: no geometry: nothing uploaded");
+    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
+        return set_err(GSR_E_INVALID, "gsr_move_device: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
+    if (!a->P) return set_err(GSR_E_INVALID, "gsr_move_device: P is NULL");
+    int rc = refuse_device_update(c, a, "gsr_move_device");
+    if (rc) return rc;
+    if (n64 == 0) return GSR_OK;
+    if ((rc = check_device_attrs(c, a, (size_t)n64, "gsr_move_device"))) return rc;
+    const bool attrs = a->Cd || a->alpha || a->scale || a->orient || a->sh;
+    // (k_move_positions reads the caller's P where it is, and the attribute step stages nothing: the arena holds the positions in upload order only)
+    return move_body(c, "gsr_move_device", first, n64, origin, 0, 0, attrs,
+                     [&]() { return update_device_rows(c, first, (uint32_t)n64, a, "gsr_move_device"); },
+                     [&](float*, hipStream_t, const float** Pnew, double*) { *Pnew = a->P; return hipSuccess; });
 }
 
 // the resident geometry as it is stored (tests hold gsr_update to a fresh upload with it)

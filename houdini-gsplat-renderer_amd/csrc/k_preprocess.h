@@ -420,6 +420,94 @@ k_quantize_raw(uint32_t n, const float* __restrict__ Cd, const float* __restrict
 }
 
 // ---------------------------------------------------------------------------
+// K0u': k_update for float32 sources in DEVICE memory (gsr_update_device): the caller's rows are read once, quantised in registers
+// (gsr_f2h) and scattered to j = inv[first + t] -- no staging copy of the halves, and nothing crosses the link.  One workgroup = 64
+// splats, eight lanes per splat with k_update's roles; an array that is NULL is left as it is in HBM:
+//   q = 0      alpha -> geoA[j].w and colrow[j][0].w; Cd (three floats; or, SH without Cd, the resident Cd) -> LDS halves 48..50
+//   q = 1..6   floats [8 (q - 1), 8 (q - 1) + 8) of the splat's 3 * vpp SH floats (coefficient j, channel ch at float 3 j + ch) -> LDS
+//              half 16 ch + j: the x / y / z rows k_update loads; a slot j >= vpp is a zero half.  Then chunk q - 1 -> col[q - 1][j]
+//              and colrow[j][q]; Cd alone: lane 1 rewrites halves 0..2 of chunk 0 as k_update does
+//   q = 7      scale (three floats) and / or orient (four), the other from the resident geoB[j] -> geoB[j] with its extent bound
+// Every source value is ONE 4-byte load inside its array (rows are not 16-byte aligned: 15 vec3 are 180 bytes), and only rows
+// t < cnt are touched.  Per splat: 4 + 12 + 12 + 16 + 12 vpp bytes read of what is given (224 with everything at vpp = 15) against
+// k_update's 122 of halves; the bytes written are k_update's (16 + 16 + 96 + 128 with everything, 4 + 4 + 16 + 16 for Cd + alpha
+// with SH).  The extent bound and the colour chunks come from gsr_extent_half / gsr_colour_chunk, the functions of k_pack.
+struct GsrUpdateSrcF32 {
+    const float *alpha, *Cd, *scale, *orient, *sh;
+    int32_t vpp;                 // vec3 per point of sh: 1..16
+};
+template <bool SH>
+__global__ void __launch_bounds__(GSR_PACK_THREADS)
+k_update_f32(uint32_t first, uint32_t cnt, uint32_t cap, GsrUpdateSrcF32 src, const uint32_t* __restrict__ inv,
+             float4* __restrict__ geoA, uint4* __restrict__ geoB, uint4* __restrict__ col, uint4* __restrict__ colrow)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad), as in k_pack
+    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
+    const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
+    const bool live = t < cnt;
+    const uint32_t j = live ? (inv ? inv[first + t] : first + t) : 0u;
+    const bool sh = SH && src.sh;
+    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
+    if (live) {
+        if (q == 0) {
+            if (src.alpha) {
+                const float op = src.alpha[t];
+                reinterpret_cast<float*>(geoA + j)[3] = op;
+                if (SH) reinterpret_cast<float*>(colrow + (size_t)j * 8)[3] = op;
+            }
+            if (src.Cd) {
+                const float* cd = src.Cd + 3 * (size_t)t;
+                s_h[sp][48] = gsr_f2h(cd[0]); s_h[sp][49] = gsr_f2h(cd[1]); s_h[sp][50] = gsr_f2h(cd[2]);
+            } else if (sh) {                           // new SH under the resident Cd: halves 0..2 of chunk 0
+                const uint2 w = *reinterpret_cast<const uint2*>(col + j);
+                s_h[sp][48] = (uint16_t)(w.x & 0xffffu); s_h[sp][49] = (uint16_t)(w.x >> 16); s_h[sp][50] = (uint16_t)(w.y & 0xffffu);
+            }
+        } else if (q == 7) {
+            if (src.scale || src.orient) {
+                uint4 b = make_uint4(0u, 0u, 0u, 0u);
+                if (!src.scale || !src.orient) b = geoB[j];
+                uint16_t s0 = (uint16_t)(b.x & 0xffffu), s1 = (uint16_t)(b.x >> 16), s2 = (uint16_t)(b.y & 0xffffu);
+                uint16_t o0 = (uint16_t)(b.y >> 16), o1 = (uint16_t)(b.z & 0xffffu), o2 = (uint16_t)(b.z >> 16), o3 = (uint16_t)(b.w & 0xffffu);
+                if (src.scale) { const float* s = src.scale + 3 * (size_t)t; s0 = gsr_f2h(s[0]); s1 = gsr_f2h(s[1]); s2 = gsr_f2h(s[2]); }
+                if (src.orient) { const float* o = src.orient + 4 * (size_t)t; o0 = gsr_f2h(o[0]); o1 = gsr_f2h(o[1]); o2 = gsr_f2h(o[2]); o3 = gsr_f2h(o[3]); }
+                geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, gsr_extent_half(s0, s1, s2, o0, o1, o2, o3)));
+            }
+        } else if (sh) {
+            const int nf = 3 * src.vpp;                // floats of a splat's row (<= 48)
+            const float* row = src.sh + (size_t)t * (size_t)nf;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int f = 8 * (q - 1) + k, co = f / 3, chn = f - 3 * co;
+                // (a slot without data is a zero HALF, as k_quantize_raw leaves it)
+                s_h[sp][16 * chn + co] = f < nf ? gsr_f2h(row[f]) : (uint16_t)0;
+            }
+        }
+    }
+    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!live) return;
+    if (sh) {
+        if (q >= 1 && q <= 6) {
+            const uint4 v = gsr_colour_chunk<true>(s_h[sp], q - 1);
+            col[(size_t)(q - 1) * cap + j] = v;
+            colrow[(size_t)j * 8 + q] = v;
+        }
+    } else if (q == 1 && src.Cd) {
+        const uint32_t w0 = pk(s_h[sp][48], s_h[sp][49]), c2 = s_h[sp][50];
+        if (SH) {
+            uint4 v = col[j];
+            v.x = w0; v.y = (v.y & 0xffff0000u) | c2;
+            col[j] = v;
+            colrow[(size_t)j * 8 + 1] = v;
+        } else {
+            col[j] = make_uint4(w0, c2, 0u, 0u);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // SH evaluation for one channel; expressions are written and associated exactly
 // as in the oracle (and in shaders/GSplatShaderCoreLib.h:146-175).
 __device__ __forceinline__ float gsr_shade_sh(float base, const float* sh, float x, float y, float z, int order)

@@ -91,6 +91,12 @@ class gsr_attr_update(C.Structure):
                 ("shx", C.c_void_p), ("shy", C.c_void_p), ("shz", C.c_void_p)]
 
 
+class gsr_device_attrs(C.Structure):
+    """include/gsplat_hip.h: float32 point attributes in DEVICE memory (NULL has the meaning the verb gives it)"""
+    _fields_ = [("P", C.c_void_p), ("Cd", C.c_void_p), ("alpha", C.c_void_p), ("scale", C.c_void_p), ("orient", C.c_void_p),
+                ("sh", C.c_void_p), ("sh_vec3_per_point", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -148,6 +154,7 @@ C_ABI_SYMBOLS = [
     "gsr_render_over", "gsr_composite_over", "gsplat_renderer_set_background",
     "gsr_update", "gsr_multi_update", "gsr_debug_read_resident", "gsplat_renderer_update_attributes", "gsplat_renderer_row_array",
     "gsr_move", "gsr_multi_move", "gsplat_renderer_move_splats",
+    "gsr_upload_append_device", "gsr_update_device", "gsr_move_device", "gsr_debug_check_device_source",
 ]
 
 
@@ -186,6 +193,10 @@ def load_library() -> C.CDLL:
     L.gsr_move.argtypes = [vp, i64, i64, vp, f32p, C.POINTER(gsr_attr_update)]
     L.gsr_multi_move.argtypes = [vp, i64, i64, vp, f32p, C.POINTER(gsr_attr_update)]
     L.gsplat_renderer_move_splats.argtypes = [vp, C.c_char_p, vp, f32p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_upload_append_device.argtypes = [vp, i64, C.POINTER(gsr_device_attrs)]
+    L.gsr_update_device.argtypes = [vp, i64, i64, C.POINTER(gsr_device_attrs)]
+    L.gsr_move_device.argtypes = [vp, i64, i64, f32p, C.POINTER(gsr_device_attrs)]
+    L.gsr_debug_check_device_source.argtypes = [vp, vp, i64]
     L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
@@ -446,6 +457,59 @@ def move_arrays(P, **attrs):
     return P, n, u, keep
 
 
+DEVICE_ATTRS = (("P", 3), ("Cd", 3), ("alpha", 1), ("scale", 3), ("orient", 4), ("sh", None))     # (name, float32 values per splat)
+
+
+def device_attrs_struct(n=None, sh_vec3_per_point=None, **arrays):
+    """gsr_device_attrs from keyword arrays in DEVICE memory (P, Cd, alpha, scale, orient, sh; None = NULL) -> (struct, n, the objects it
+    points into: keep them alive during the call).  An array is an int -- a device pointer; then n must be given, and sh_vec3_per_point
+    with sh -- or an object with data_ptr() (a torch tensor): float32, contiguous, on a GPU, its first axis the splats; n and
+    sh_vec3_per_point come from the shapes and are cross-checked.  Nothing is copied and nothing is synchronised."""
+    unknown = set(arrays) - {name for name, _ in DEVICE_ATTRS}
+    if unknown:
+        raise GsrError(-1, f"device_attrs_struct: unknown attribute(s) {sorted(unknown)}")
+    a, keep = gsr_device_attrs(), []
+    n = None if n is None else int(n)
+    vpp = None if sh_vec3_per_point is None else int(sh_vec3_per_point)
+    for name, width in DEVICE_ATTRS:
+        v = arrays.get(name)
+        if v is None:
+            continue
+        if isinstance(v, (int, np.integer)):
+            if n is None:
+                raise GsrError(-1, f"device_attrs_struct: {name} is a raw device pointer: n must be given")
+            setattr(a, name, int(v))
+            continue
+        if not hasattr(v, "data_ptr"):
+            raise GsrError(-1, f"device_attrs_struct: {name} is neither a device pointer (int) nor an object with data_ptr()")
+        if not str(v.dtype).endswith("float32"):
+            raise GsrError(-1, f"device_attrs_struct: {name} is {v.dtype}, not float32")
+        if not v.is_contiguous():
+            raise GsrError(-1, f"device_attrs_struct: {name} is not contiguous")
+        if not getattr(v, "is_cuda", False):
+            raise GsrError(-1, f"device_attrs_struct: {name} lives on {getattr(v, 'device', 'the host')}, not on a GPU")
+        shape = tuple(int(x) for x in v.shape)
+        if not shape:
+            raise GsrError(-1, f"device_attrs_struct: {name} has no splat axis")
+        rows, per = shape[0], int(np.prod(shape[1:], dtype=np.int64))
+        if n is not None and rows != n:
+            raise GsrError(-1, f"device_attrs_struct: {name} holds {rows} splats, not {n}")
+        n = rows
+        if width is None:                           # sh: (n, vpp, 3)
+            if per % 3 or (len(shape) > 2 and shape[-1] != 3) or (vpp is not None and per != 3 * vpp):
+                raise GsrError(-1, f"device_attrs_struct: sh holds {per} values per splat, not {'3 x vec3 per point' if vpp is None else 3 * vpp}")
+            vpp = per // 3
+        elif per != width:
+            raise GsrError(-1, f"device_attrs_struct: {name} holds {per} values per splat, not {width}")
+        keep.append(v)
+        setattr(a, name, int(v.data_ptr()))
+    if a.sh:
+        if vpp is None:
+            raise GsrError(-1, "device_attrs_struct: sh is a raw device pointer: sh_vec3_per_point must be given")
+        a.sh_vec3_per_point = vpp
+    return a, (n or 0), keep
+
+
 class _Arrays:
     """contiguous, correctly typed views of a Splats-like object (kept alive during the call)"""
 
@@ -553,6 +617,40 @@ class Engine:
         P, n, u, keep = move_arrays(P, **attrs)
         _check(self.L.gsr_move(self.h, int(first), n, P.ctypes.data, None if origin is None else _f3(origin), C.byref(u)))
         return n
+
+    # ---- device sources: float32 arrays that already sit in device memory (device_attrs_struct says what an array may be)
+    def upload_device(self, attrs: dict, origin=(0.0, 0.0, 0.0), n=None, sh_vec3_per_point=None):
+        """gsr_upload_append_device as a whole upload: attrs = {P, and optionally Cd, alpha, scale, orient, sh}, quantised and packed on
+        the GPU with nothing crossing the link; missing arrays take upload_raw's defaults, and the cloud has SH exactly when sh is given"""
+        a, n, keep = device_attrs_struct(n, sh_vec3_per_point, **attrs)
+        _check(self.L.gsr_upload_begin(self.h, n, int(bool(a.sh)), _f3(origin)))
+        try:
+            _check(self.L.gsr_upload_append_device(self.h, n, C.byref(a)))
+            _check(self.L.gsr_upload_end(self.h))
+        except GsrError:
+            self.L.gsr_upload_abort(self.h)
+            raise
+        return n
+
+    def update_attrs_device(self, first: int, n=None, sh_vec3_per_point=None, **attrs) -> int:
+        """gsr_update_device: update_attrs from float32 arrays in device memory (Cd, alpha, scale, orient, sh; no P), quantised on the GPU.
+        Waits for the work queued on the stream given to set_stream, then for the frames in flight; synchronous."""
+        a, n, keep = device_attrs_struct(n, sh_vec3_per_point, **attrs)
+        _check(self.L.gsr_update_device(self.h, int(first), n, C.byref(a)))
+        return n
+
+    def move_device(self, first: int, P, origin=None, n=None, sh_vec3_per_point=None, **attrs) -> int:
+        """gsr_move_device: move from a float32 P (n, 3) in device memory, with update_attrs_device's arrays for the same rows"""
+        a, n, keep = device_attrs_struct(n, sh_vec3_per_point, P=P, **attrs)
+        _check(self.L.gsr_move_device(self.h, int(first), n, None if origin is None else _f3(origin), C.byref(a)))
+        return n
+
+    def check_device_source(self, ptr: int, nbytes: int) -> bool:
+        """gsr_debug_check_device_source: would the device-source verbs take [ptr, ptr + nbytes) as a source array?  A pure query."""
+        rc = self.L.gsr_debug_check_device_source(self.h, C.c_void_p(int(ptr)), int(nbytes))
+        if rc not in (0, -1):
+            _check(rc)
+        return rc == 0
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""

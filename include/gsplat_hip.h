@@ -207,7 +207,8 @@ int  gsr_upload(gsr_context* ctx, int64_t n,
  * appended (so a caller who concatenated several entries addresses one of them by the running sum of their sizes).  NULL = that
  * attribute stays as it is.  shx / shy / shz come all three or not at all, and only for a cloud uploaded with SH.
  * There is NO P: a position decides the storage order, the bounding box and the cluster boxes -- moving a point is gsr_move below.
- * Not covered: raw float32 sources (gsr_raw_attrs: quantise on the host, or re-upload) and device-pointer sources.
+ * float32 sources in DEVICE memory, quantised on the GPU: gsr_update_device below.  Raw float32 HOST sources (gsr_raw_attrs) are
+ * not covered: quantise on the host (gsplat_quantize_half), or re-upload.
  * Synchronous like gsr_upload_append (the arrays may be freed on return); it first waits for every frame of the context that is
  * still in flight, so no frame ever reads a half-written splat.
  * CONTRACT: after GSR_OK the resident geometry is bit for bit what a fresh context holds after gsr_upload of the edited arrays
@@ -243,9 +244,58 @@ int  gsr_update(gsr_context* ctx, int64_t first, int64_t n, const gsr_attr_updat
  * rules for u.  n == 0: GSR_OK, nothing happens.  Everything is allocated before the first write: GSR_E_OOM leaves the context
  * untouched.  A HIP failure after that leaves NO geometry (gsr_render: GSR_E_NO_GEOMETRY until the next complete upload); with
  * attributes in u that includes ANY HIP failure of the gsr_update step, also one before its own first write.
- * gsr_stats.uploads does not count a move; moves and move_ms[] do.  Not covered: raw float32 and device-pointer sources; a change of
- * the splat count (that is an upload). */
+ * gsr_stats.uploads does not count a move; moves and move_ms[] do.  float32 sources in DEVICE memory: gsr_move_device below.  Not
+ * covered: raw float32 HOST sources for u; a change of the splat count (that is an upload). */
 int  gsr_move(gsr_context* ctx, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
+
+/* ---- device sources (upload, update and move from float32 arrays in DEVICE memory) ------------------------------------------ */
+/* For a caller whose splats already live on the GPU of the context, in the same process (a trainer's live view, a deformation
+ * network, a simulation, a torch expression): the three verbs above from float32 arrays in device memory.  Nothing crosses the
+ * link; Cd, scale, orient and sh are quantised on the GPU by the rule of gsplat_quantize_half (round to nearest even, overflow to
+ * infinity), P and alpha stay float32, and SH slot j >= sh_vec3_per_point of a splat's 16 is a zero half.  Activations (0.5 + C0 dc,
+ * sigmoid, exp) stay with the caller, as with gsr_raw_attrs.
+ * NULL arrays.  gsr_upload_append_device: P is required; the others take the defaults of gsr_upload_append_raw (Cd 0, alpha 1,
+ * scale 1, orient (0, 0, 0, 1)); sh is present exactly when the upload announced SH.  gsr_update_device: NULL = the attribute stays;
+ * P must be NULL (a position is gsr_move_device); sh only for a cloud with SH.  gsr_move_device: P is required, everything else as
+ * for gsr_update_device, applied in the same call; origin as in gsr_move.
+ * CONTRACT: that of gsr_update / gsr_move.  After GSR_OK the resident geometry -- geoA, geoB, every colour chunk, the colour rows,
+ * the cluster bounds and the storage order -- is bit for bit what a fresh context holds after gsr_upload of the same arrays
+ * quantised on the host with gsplat_quantize_half, and so is every later frame, in every option mode; what the frames of the cloud
+ * before may keep is decided as the host verbs decide it (a colour-only edit keeps horizons and policies; anything else is a new
+ * cloud).  An attribute value that is NaN becomes a NaN half with unspecified sign and payload (the exception of the target
+ * formats above); every other value is bit-exact.  Host-source and device-source entries may be mixed inside one gsr_upload_begin /
+ * gsr_upload_end.
+ * ORDERING: each verb first waits for the work queued on the context's public stream (gsr_set_stream) -- a producer kernel queued
+ * there has finished; a producer on any other stream is the caller's to synchronise -- and for the context's frames in flight, as the
+ * host verbs do.  The verbs are synchronous: on return the source arrays may be overwritten.
+ * SOURCE POINTERS: every non-NULL array is checked before anything is written or launched.  It passes when it is 4-byte aligned,
+ * the runtime calls it device memory of the context's device or pinned host memory (hipPointerGetAttributes), and, where the runtime
+ * reports the allocation's range (hipMemGetAddressRange), all its bytes lie inside the allocation.  Pageable host memory, another
+ * device's memory, managed memory and a range past the allocation's end are GSR_E_INVALID with the context untouched.
+ * gsr_debug_check_device_source is that check as a pure query (no kernel, no copy, nothing written): GSR_OK or GSR_E_INVALID.
+ * The other refusals are those of the host verbs (NULL ctx or struct, a bad range, an upload in progress or none, no geometry, SH
+ * for a cloud without SH), plus P in an update and sh_vec3_per_point outside 1..16.  n == 0, or an update with nothing given:
+ * GSR_OK, nothing happens.
+ * gsr_stats: upload_ms[4] after gsr_update_device and move_ms[0] after gsr_move_device are 0.0 (nothing crossed the link), and
+ * gsr_upload_append_device adds nothing to upload_ms[0]; the kernel and wall-clock entries, moves and uploads are the host verbs'.
+ * Out of scope: gsr_multi_* (the cloud is replicated per GPU, a device pointer lives on one of them); the GSplatRenderer shim and
+ * the HDK glue (their rows are borrowed host arrays that a re-stage uploads again: a device edit would be lost by it); the SH
+ * naming schemes 2 and 3 of gsr_raw_attrs; asynchronous forms; half sources in device memory. */
+typedef struct gsr_device_attrs {
+    const float* P;        /* float[3n] */
+    const float* Cd;       /* float[3n] */
+    const float* alpha;    /* float[n]  */
+    const float* scale;    /* float[3n] */
+    const float* orient;   /* float[4n] (x, y, z, w) */
+    const float* sh;       /* float[n * sh_vec3_per_point * 3]: coefficient j of point i at sh[(i * vpp + j) * 3 ..]
+                              (gsr_raw_attrs' scheme 1; with vpp = 15 it is a trainer's features_rest (N, 15, 3)) */
+    int32_t sh_vec3_per_point;   /* 1..16 when sh is given */
+    int32_t reserved_;           /* 0 */
+} gsr_device_attrs;
+int  gsr_upload_append_device(gsr_context* ctx, int64_t n, const gsr_device_attrs* a);   /* between gsr_upload_begin and _end */
+int  gsr_update_device(gsr_context* ctx, int64_t first, int64_t n, const gsr_device_attrs* a);
+int  gsr_move_device(gsr_context* ctx, int64_t first, int64_t n, const float origin[3], const gsr_device_attrs* a);
+int  gsr_debug_check_device_source(gsr_context* ctx, const void* p, int64_t bytes);
 
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
