@@ -222,6 +222,7 @@ struct FrameSlot {
     FrameJob job;                      // the frame queued in this slot (open until frame_finish)
     // last frame rendered in this slot
     int last_tiles_x = 0, last_local_ty = 0, last_supers = 0;
+    uint32_t last_cc_groups = 0, last_cc_per = 0;   // the grid of the slot's last k_cluster_cull (0: none, or slots in cached order instead of clusters)
     uint32_t last_pairs = 0;
     int super_tile = 0, stiles_x = 0, stiles_y = 0;
     uint64_t frame_id = 0;             // 1-based id of that frame, 0 = never used
@@ -2660,6 +2661,8 @@ static int queue_cull(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
                        pyr, sl.cseg, sl.ccnt,   // (ordered: slots, not clusters -- all of them)
                        j.phase == 1 ? 2 : (j.phase == 2 ? 3 : 0), sl.slab, fe.hist_shift, sl.slab + GSR_SLAB_BINS, pk, (float*)nullptr, 0,
                        j.local_sort ? sl.bkt_cnt : (uint32_t*)nullptr, sl.d_counts + 2, dp, fe.n_dp, fe.dc_clus);
+    sl.last_cc_groups = p.ordered ? 0u : fe.ngroups;
+    sl.last_cc_per = (uint32_t)CC_THREADS * (uint32_t)fe.rounds;
     return GSR_OK;
 }
 
@@ -3344,6 +3347,40 @@ extern "C" int gsr_debug_read_records(gsr_context* c, gsr_debug_record* out, int
     }
     delete[] hr; delete[] hk; delete[] hv;
     return rc;
+}
+
+extern "C" int gsr_debug_read_cull(gsr_context* c, uint32_t* rect, int64_t n, uint32_t* clusters, int64_t cap, int64_t* n_clusters)
+{
+    if (!c || !rect || n < 0 || (uint64_t)n > c->n || cap < 0 || (cap > 0 && !clusters) || !n_clusters) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    FrameSlot* sl = latest_slot(c);
+    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: no frame rendered yet");
+    if (!sl->last_cc_groups) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: the last frame ran no cluster pass over clusters");
+    if ((rc = host_perm(c))) return rc;
+    // rects live in depth order beside the storage slots of the splats that stayed (gsr_debug_read_records)
+    const uint32_t ns = sorted_count(sl);
+    std::vector<uint2> hv(ns ? ns : 1);
+    if (ns) HIP_TRY(hipMemcpy(hv.data(), sl->valA, (size_t)ns * 8, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) rect[i] = 0xffffffffu;
+    for (uint32_t r = 0; r < ns; ++r) {
+        const uint32_t slot = hv[r].x;
+        if ((uint64_t)slot >= c->n) continue;
+        const uint32_t i = to_upload_index(c, slot);
+        if ((int64_t)i < n) rect[i] = hv[r].y;
+    }
+    // the survivors: workgroup g left cnt[g] of them, in cluster order, at seg[g * per ...]
+    const uint32_t ng = sl->last_cc_groups, per = sl->last_cc_per;
+    std::vector<uint32_t> cnt(ng), seg((size_t)ng * per);
+    HIP_TRY(hipMemcpy(cnt.data(), sl->ccnt, (size_t)ng * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(seg.data(), sl->cseg, (size_t)ng * per * 4, hipMemcpyDeviceToHost));
+    int64_t m = 0;
+    for (uint32_t g = 0; g < ng; ++g)
+        for (uint32_t k = 0; k < cnt[g] && k < per; ++k, ++m)
+            if (m < cap) clusters[m] = seg[(size_t)g * per + k];
+    *n_clusters = m;
+    return GSR_OK;
 }
 
 extern "C" int gsr_debug_read_depth_order(gsr_context* c, int32_t* perm, int64_t cap, int64_t* n_sorted)

@@ -92,6 +92,26 @@ struct GsrFrame {
     uint32_t idx_mask;
     float zq0, zqs;                    // code = clamp(floor((zwin - zq0) * zqs), 0, 511)
 };
+// The frame of a kernel that takes it BY VALUE, as it lies in the kernel's argument segment (constant address space; kernarg_off = the
+// byte offset of the parameter there).  K1 and k_cluster_cull read it through gsr_frame_fetch(): each PHASE of the kernel fetches the
+// frame anew -- scalar loads through the scalar cache, of the fields that phase uses alone (the others' loads are dead and go) -- so
+// no field is live outside its phase.  Read as a plain by-value parameter the whole frame (about a hundred scalars) is loaded at entry
+// and stays live throughout; beside the kernel's two dozen pointers it does not fit the scalar register file, and the compiler parks
+// it in the lanes of VGPRs: 370-420 v_readlane / v_writelane in each K1, a quarter of its vector instructions (LAB_NOTES).  The empty asm
+// makes the address opaque, so the loads behind it can be neither hoisted to the entry block nor merged with another phase's.
+typedef const GsrFrame __attribute__((address_space(4)))* GsrFrameArg;
+__device__ __forceinline__ GsrFrameArg gsr_frame_arg(unsigned kernarg_off)
+{
+    static_assert(alignof(GsrFrame) == 4 && sizeof(GsrFrame) % 4 == 0, "the frame is a run of dwords");
+    return (GsrFrameArg)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + kernarg_off);
+}
+__device__ __forceinline__ GsrFrame gsr_frame_fetch(GsrFrameArg p)
+{
+    asm volatile("" : "+s"(p));
+    GsrFrame f;
+    __builtin_memcpy(&f, p, sizeof(GsrFrame));
+    return f;
+}
 #define GSR_ZQ_SHIFT 23
 #define GSR_ZQ_MAX 511.0f
 #define GSR_SLAB_BINS 1024             // k_cluster_cull's histogram of the surviving clusters' nearest keys (k_slab_pick reads it)

@@ -69,7 +69,10 @@ __host__ __device__ __forceinline__ int gsr_pyr_dim(int tiles, int level) { retu
 // MONOTONE: a rect that contains another never gets a smaller value (its cells are unions of the other's), which is what lets
 // k_tile_pass check a tile against the value of the tile itself -- every splat that touches the tile was compared with at
 // least that.
-__device__ __forceinline__ float gsr_pyr_max(const float* __restrict__ pyr, const int32_t* pyr_off, int tiles_x, int x0, int y0, int x1, int y1)
+// (OffP: the level offsets, `const int32_t*` or the frame's own array in the kernel's argument segment, GsrFrameArg->pyr_off: indexed by
+//  a per-lane level, they are read where they lie and not copied into registers)
+template <class OffP>
+__device__ __forceinline__ float gsr_pyr_max(const float* __restrict__ pyr, OffP pyr_off, int tiles_x, int x0, int y0, int x1, int y1)
 {
     const int span = max(x1 - x0, y1 - y0);
     int L = 31 - __builtin_clz((uint32_t)span | 1u);
@@ -127,7 +130,8 @@ struct GsrDepthPyrArgs {
 // largest value over the tile rect [x0, x1] x [y0, y1] of a depth pyramid (levels 0 .. GSR_DPYR_LEVELS - 1); +inf -- "unknown": nothing
 // is culled on its account -- for a rect that spans more than 2 x 2 cells of the top level (more than 512 pixels)
 #define GSR_DPYR_LEVELS 5
-__device__ __forceinline__ float gsr_dpyr_max(const float* __restrict__ pyr, const int32_t* pyr_off, int tiles_x, int x0, int y0, int x1, int y1)
+template <class OffP>
+__device__ __forceinline__ float gsr_dpyr_max(const float* __restrict__ pyr, OffP pyr_off, int tiles_x, int x0, int y0, int x1, int y1)
 {
     const int span = max(x1 - x0, y1 - y0);
     int L = 31 - __builtin_clz((uint32_t)span | 1u);
@@ -355,6 +359,8 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
                GsrDepthCull dc /* ... or the pyramid exists already (k_depth_pyramid ran in front): clusters are tested against it */)
 {
     static_assert(CC_THREADS == 256, "the folded depth pyramid workgroups are gsr_depth_pyramid_block<256>");
+    // (the frame is the first parameter; it is read from the argument segment phase by phase: gsr_device.h, gsr_frame_fetch)
+    const GsrFrameArg fp = gsr_frame_arg(0u);
     if (DEPTH && blockIdx.x < n_dp) { gsr_depth_detect_block(dp, (int)blockIdx.x); return; }
     const uint32_t bid = DEPTH ? blockIdx.x - n_dp : blockIdx.x, nbid = DEPTH ? gridDim.x - n_dp : gridDim.x;
     const bool dact = DEPTH && dc.pyr != nullptr && *dc.active != 0u;     // (uniform)
@@ -388,6 +394,7 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
         if (keep && enabled) {
             const float4 A = clusA[cl], B = clusB[cl];
             if (B.w == 0.0f) {
+                const GsrFrame f = gsr_frame_fetch(fp);                // (origin, ov, pr, the third row of vw, W / H)
                 // the box, widened by what the GSplatOrigin round trip (fl32(P - origin) + origin) can move a position
                 const float plo[3] = {A.x, A.y, A.z}, phi[3] = {B.x, B.y, B.z};
                 float lo[3] = {A.x, A.y, A.z}, hi[3] = {B.x, B.y, B.z};
@@ -429,6 +436,7 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
                 if (wmax < -eps || zpw_max < -eps || wmz_max < -eps) {
                     keep = false;                                       // w <= 0, or z outside [-w, w], for every splat
                 } else if (wmin > eps && (tz_max < -1.0e-6f * mag || tz_min > 1.0e-6f * mag) && mag < 1.0e15f) {
+                    const GsrFrame f = gsr_frame_fetch(fp);            // (focal, the limits, sigma_vo2, width / height)
                     // wholly in front of the eye: the screen positions of its splats lie inside the hull of the projected
                     // corners, and every quad inside its centre +- hb: the cheap extent bound of gsr_k1_front, taken at the
                     // largest |diag(scale) R^T|_F and the smallest |view z| of the cluster
@@ -448,13 +456,14 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
                         if (xhi < 0.0f || xlo > wm1 || yhi < 0.0f || ylo > hm1) {
                             keep = false;                               // off screen
                         } else {
+                            const GsrFrame f = gsr_frame_fetch(fp);    // (the tile grid, the dilation, the shard, cam, the key range)
                             const int tx0 = (int)__builtin_fmaxf(xlo, 0.0f) >> 4, tx1 = (int)__builtin_fminf(xhi, wm1) >> 4;
                             const int ty0 = (int)__builtin_fmaxf(ylo, 0.0f) >> 4, ty1 = (int)__builtin_fminf(yhi, hm1) >> 4;
                             bool behind = false, covered_need = false;
                             float hcl = __builtin_inff();         // the horizon over the tiles the cluster can reach (+inf: none)
                             if (hpyr) {
                                 const int r_ = f.cull_dilate;
-                                hcl = gsr_pyr_max(hpyr, f.pyr_off, f.tiles_x, max(tx0 - r_, 0), max(ty0 - r_, 0), min(tx1 + r_, f.tiles_x - 1), min(ty1 + r_, f.tiles_y - 1));
+                                hcl = gsr_pyr_max(hpyr, fp->pyr_off, f.tiles_x, max(tx0 - r_, 0), max(ty0 - r_, 0), min(tx1 + r_, f.tiles_x - 1), min(ty1 + r_, f.tiles_y - 1));
                             }
                             if (dact) {
                                 // depth-tested frames: does every splat of the cluster lie behind everything the opaque pass left under the
@@ -463,11 +472,11 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
                                 const float zerr = 1.05f * eps * (1.0f + __builtin_fabsf(znmin)) / (wmin - eps) + 2.0e-7f;
                                 const float zlo = gsr_fma(znmin - zerr, 0.5f, 0.5f) - 2.0e-7f;
                                 // (only where no finite horizon applies: k_preprocess.h says why)
-                                behind = !(hcl < 3.0e38f) && zlo > gsr_dpyr_max(dc.pyr, f.pyr_off, f.tiles_x, tx0, ty0, tx1, ty1);
+                                behind = !(hcl < 3.0e38f) && zlo > gsr_dpyr_max(dc.pyr, fp->pyr_off, f.tiles_x, tx0, ty0, tx1, ty1);
                                 // ... or may a COVERED pixel there need one of them (k_preprocess.h: the depth clause of gsr_k1_back)?
                                 if (dc.pyrc) {
                                     const int r_ = f.cull_dilate;
-                                    covered_need = !(zlo > gsr_dpyr_max(dc.pyrc, f.pyr_off, f.tiles_x, max(tx0 - r_, 0), max(ty0 - r_, 0), min(tx1 + r_, f.tiles_x - 1), min(ty1 + r_, f.tiles_y - 1)));
+                                    covered_need = !(zlo > gsr_dpyr_max(dc.pyrc, fp->pyr_off, f.tiles_x, max(tx0 - r_, 0), max(ty0 - r_, 0), min(tx1 + r_, f.tiles_x - 1), min(ty1 + r_, f.tiles_y - 1)));
                                 }
                             }
                             if (gsr_owned_rows(ty0, ty1, GsrShard{f.shard_index, f.shard_count, f.shard_rpb}) == 0) {

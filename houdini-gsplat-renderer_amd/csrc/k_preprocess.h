@@ -6,7 +6,7 @@
 // splat instead of once per quad corner -- and the CPU distance loop of
 // argsortByDistance (src/GSplatRenderer.C:194-204).  One wavefront per cluster that survived k_cluster_cull (k_cluster.h):
 // 32 B read per splat of it, 56 B (record, key, payload) written per splat that stays, + its 96 B of colour halves when the
-// frame shades in K1 (occlusion-culled frames; unculled ones leave the colours to k_colour.h).  Bound by FP32 issue -- the
+// frame shades in K1 (occlusion-culled frames; unculled ones leave the colours to k_colour.h).  Bound by vector issue -- the
 // ~1000-instruction covariance chain with its eleven IEEE divisions and four square roots -- not by HBM.
 #pragma once
 #include "gsr_device.h"
@@ -791,11 +791,12 @@ gsr_k1_front(const GsrFrame& f, const float4 a, const uint4 b, float* __restrict
 
 // returns the packed tile rect (GSR_RECT_EMPTY: the splat draws nothing here); writes the record of a splat that draws
 __device__ __forceinline__ uint32_t
-gsr_k1_back(const GsrFrame& f, uint32_t i, uint32_t cap, const GsrK1Front& o, const uint4 b, const uint4* __restrict__ col,
+gsr_k1_back(GsrFrameArg fp, uint32_t i, uint32_t cap, const GsrK1Front& o, const uint4 b, const uint4* __restrict__ col,
             GsrRecord* __restrict__ rec, int lazy, const float* __restrict__ hpyr, const float* __restrict__ dpyr /* NULL: no depth culling */,
             const float* __restrict__ dpyrc)
 {
     uint32_t out_rect = GSR_RECT_EMPTY;
+    const GsrFrame f = gsr_frame_fetch(fp);            // (vw, ob, focal, the limits, the rect, shard and pyramid fields)
     const float x = o.x, y = o.y, z = o.z, cx = o.cx, cy = o.cy, opacity = o.opacity;
     const float sx = gsr_h2f(b.x & 0xffffu), sy = gsr_h2f(b.x >> 16), sz = gsr_h2f(b.y & 0xffffu);
     const float qi = gsr_h2f(b.y >> 16), qj = gsr_h2f(b.z & 0xffffu), qk = gsr_h2f(b.z >> 16);
@@ -836,7 +837,7 @@ gsr_k1_back(const GsrFrame& f, uint32_t i, uint32_t cap, const GsrK1Front& o, co
         const int x0 = (int)(out_rect & 255u) << g, y0 = (int)((out_rect >> 8) & 255u) << g;
         const int x1 = (((int)((out_rect >> 16) & 255u) + 1) << g) - 1, y1 = (((int)(out_rect >> 24) + 1) << g) - 1;
         const int r = f.cull_dilate;
-        const float h = gsr_pyr_max(hpyr, f.pyr_off, f.tiles_x, max(x0 - r, 0), max(y0 - r, 0), min(x1 + r, f.tiles_x - 1), min(y1 + r, f.tiles_y - 1));
+        const float h = gsr_pyr_max(hpyr, fp->pyr_off, f.tiles_x, max(x0 - r, 0), max(y0 - r, 0), min(x1 + r, f.tiles_x - 1), min(y1 + r, f.tiles_y - 1));
         beyond = o.kb > gsr_horizon_key(h, f.key_min, f.key_max);
         no_horizon = !(h < 3.0e38f);
         if (beyond && !dpyr) out_rect = GSR_RECT_EMPTY;
@@ -857,13 +858,13 @@ gsr_k1_back(const GsrFrame& f, uint32_t i, uint32_t cap, const GsrK1Front& o, co
         // (the first rule only where no finite horizon applies: INSIDE a horizon nothing is dropped by depth -- k_tile_pass places the next
         //  horizon a quarter + 1024 entries down the list, a list cut at the geometry is "too short" for that, and its fallback pushes the
         //  horizon out by 5 % per frame for good: measured, 13 k surviving clusters became 45 k)
-        if (no_horizon) { if (o.zw > gsr_dpyr_max(dpyr, f.pyr_off, f.tiles_x, x0, y0, x1, y1)) out_rect = GSR_RECT_EMPTY; }
+        if (no_horizon) { if (o.zw > gsr_dpyr_max(dpyr, fp->pyr_off, f.tiles_x, x0, y0, x1, y1)) out_rect = GSR_RECT_EMPTY; }
         // (the covered depths of the tiles that were NOT classic in the frame that left the horizons, looked up over the rect widened like
         //  the horizon look-up: a tile's status is as old as its horizon.  No pyrc: no depth clause at all -- phase 2 of a front-slab
         //  frame, whose "horizons" are 0 for the tiles phase 1 FINISHED and +inf for the others)
         else if (beyond) {
             const int r = f.cull_dilate;
-            if (!dpyrc || o.zw > gsr_dpyr_max(dpyrc, f.pyr_off, f.tiles_x, max(x0 - r, 0), max(y0 - r, 0), min(x1 + r, f.tiles_x - 1), min(y1 + r, f.tiles_y - 1)))
+            if (!dpyrc || o.zw > gsr_dpyr_max(dpyrc, fp->pyr_off, f.tiles_x, max(x0 - r, 0), max(y0 - r, 0), min(x1 + r, f.tiles_x - 1), min(y1 + r, f.tiles_y - 1)))
                 out_rect = GSR_RECT_EMPTY;
         }
     }
@@ -873,15 +874,17 @@ gsr_k1_back(const GsrFrame& f, uint32_t i, uint32_t cap, const GsrK1Front& o, co
         if (lazy) {
             cr = __builtin_bit_cast(float, GSR_COLOUR_PENDING); cg = 0.0f; cbl = 0.0f;
         } else {
+            const GsrFrame fc = gsr_frame_fetch(fp);   // (io, cam, sh_order)
+            asm volatile("" : "+s"(cap));              // (the chunk strides c * cap are formed here, not kept in registers from the entry block on)
             uint4 cw[6];
             cw[0] = col[i];
-            const int nchunk = f.sh_order == 0 ? 1 : (f.sh_order == 1 ? 2 : (f.sh_order == 2 ? 4 : 6));
+            const int nchunk = fc.sh_order == 0 ? 1 : (fc.sh_order == 1 ? 2 : (fc.sh_order == 2 ? 4 : 6));
 #pragma unroll
             for (int c = 1; c < 6; ++c) {
                 cw[c] = make_uint4(0, 0, 0, 0);
                 if (c < nchunk) cw[c] = col[(size_t)c * cap + i];
             }
-            gsr_splat_colour(f, cw, x, y, z, cr, cg, cbl);
+            gsr_splat_colour(fc, cw, x, y, z, cr, cg, cbl);
         }
         // contract v2: the quad-local coordinate as two affine forms scaled by kappa = sqrt(log2 e)
         const float k1 = (1.0f / s1) * GSR_KAPPA, k2 = (1.0f / s2) * GSR_KAPPA;
@@ -906,13 +909,16 @@ struct GsrK1Scatter {
 // One wavefront per surviving cluster (k_cluster.h): workgroup-iteration k takes the clusters of rank 4k .. 4k+3 of
 // k_cluster_cull's ordered list, so its 256 slots are in storage order like the list itself.  The grid is sized from the
 // previous frame's survivor count (gsr_api.hip); a frame that keeps more simply loops.
-// (6 waves per SIMD = 80 VGPRs: with the colours evaluated here, 7 waves (72 VGPRs) spill 12 dwords: 38.2 -> 34.5 us on a culled C4 frame)
+// (6 waves per SIMD = 80 VGPRs.  The frame constants are read from the argument segment phase by phase (gsr_device.h: gsr_frame_fetch):
+//  held in registers from the entry block on they overflowed the scalar file into VGPR lanes -- 375 v_readlane / v_writelane of 1599 vector
+//  instructions, and 12 bytes of scratch; now 18 of 1240 and no scratch, and a culled C4 launch went from 39.5 to 34.2 us with 23 % fewer vector
+//  instructions executed: K1 pays for what it issues (LAB_NOTES.md, "Frame constants out of the VGPR lanes").  7 waves (72 VGPRs) still spill
+//  12 bytes with the colours evaluated here and were no faster: 4333 against 4356 fps, alternated on one box.)
 #ifndef GSR_K1_WAVES_PER_EU
 #define GSR_K1_WAVES_PER_EU 6
 #endif
 // The LAZY instantiation (colours left pending: unculled frames of scenes with depth complexity) has no SH evaluation in it and needs
-// 52 VGPRs instead of 80: it runs at 8 waves per SIMD.  K1 is bound by resident workgroups x the ~10 us a workgroup lives (12.7
-// generations of 1536 workgroups x 10.4 us = the 133 us of an unculled C4 frame, tools/kprof.py), so occupancy is its lever.
+// 43 VGPRs instead of 79: it runs at 8 waves per SIMD (12.7 generations of 1536 resident workgroups in an unculled C4 frame, tools/kprof.py).
 #ifndef GSR_K1_WAVES_PER_EU_LAZY
 #define GSR_K1_WAVES_PER_EU_LAZY 8
 #endif
@@ -920,7 +926,7 @@ struct GsrK1Scatter {
 //  run-time pointer test: the plain shading instantiation is the headline frame's K1, and its 80 registers have no room for the extra state)
 template <bool LAZY, bool DEPTH>
 __device__ __forceinline__ void
-gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
+gsr_k1_body(uint32_t n, uint32_t cap, GsrFrameArg fp,
              const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col,
              GsrRecord* __restrict__ rec, uint32_t* __restrict__ key, uint2* __restrict__ val,
              float* __restrict__ zwin /* NULL unless the frame is depth-tested */,
@@ -940,7 +946,7 @@ gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
     __shared__ uint32_t s_inc[CC_MAX_GROUPS];
     __shared__ uint32_t s_wcnt[2][GSR_K1_THREADS / 64];
     __shared__ uint32_t s_scan[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform: `w < wave` is a scalar compare, not four lane masks)
     KPROFB(4, 0, gridDim.x / 2)
     KPROF_BLK_BEGIN
     const uint32_t nsurv = cc_prefix_to_lds(ccnt, ngroups, s_inc, s_scan);
@@ -953,7 +959,7 @@ gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
     uint32_t sc_lo = sc.lo;
     int sc_shift = sc.shift;
     if (sc.key && sc.range_dev) { sc_lo = sc.range_dev[0]; sc_shift = (int)sc.range_dev[1]; }
-    const uint32_t slab_key = (f.phase != 0 && slab) ? slab[0] : 0xffffffffu;
+    const uint32_t slab_key = (gsr_frame_fetch(fp).phase != 0 && slab) ? slab[0] : 0xffffffffu;
     const float* const dpyr = (DEPTH && dc.pyr && *dc.active != 0u) ? dc.pyr : (const float*)nullptr;   // (uniform: nothing changes under a cleared depth buffer)
     int par = 0;
     for (uint32_t k = blockIdx.x; k < niter; k += gridDim.x, par ^= 1) {
@@ -972,8 +978,9 @@ gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
 #ifdef GSR_KPROF
                 if (k == blockIdx.x && blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); g_kprof[4][2] = wall_clock64(); }
 #endif
-                const GsrK1Front o = gsr_k1_front(f, a, b, (DEPTH && zwin) ? zwin + i : nullptr, slab_key);
-                if (o.keep && !o.far) out_rect = gsr_k1_back(f, i, cap, o, b, col, rec, LAZY ? 1 : 0, hpyr, DEPTH ? dpyr : (const float*)nullptr, DEPTH ? dc.pyrc : (const float*)nullptr);
+                const GsrFrame ff = gsr_frame_fetch(fp);       // (ov, pr, cam, origin, the key range, W / H, the band)
+                const GsrK1Front o = gsr_k1_front(ff, a, b, (DEPTH && zwin) ? zwin + i : nullptr, slab_key);
+                if (o.keep && !o.far) out_rect = gsr_k1_back(fp, i, cap, o, b, col, rec, LAZY ? 1 : 0, hpyr, DEPTH ? dpyr : (const float*)nullptr, DEPTH ? dc.pyrc : (const float*)nullptr);
                 kb = o.kb;
             }
         }
@@ -1000,8 +1007,10 @@ gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
         if (lane == 0) s_wcnt[par][wave] = (uint32_t)__builtin_popcountll(bal);
         __syncthreads();
         uint32_t before = 0, total = 0;
+        int wv = wave;
+        asm volatile("" : "+s"(wv));                   // (the four `w < wave` are scalar compares made here: as lane masks from the entry block they were parked in a VGPR)
 #pragma unroll
-        for (int w = 0; w < GSR_K1_THREADS / 64; ++w) { const uint32_t c = s_wcnt[par][w]; before += w < wave ? c : 0u; total += c; }
+        for (int w = 0; w < GSR_K1_THREADS / 64; ++w) { const uint32_t c = s_wcnt[par][w]; before += w < wv ? c : 0u; total += c; }
         if (stays) {
             const uint32_t pos = k * (uint32_t)GSR_K1_THREADS + before + (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
             key[pos] = kb;
@@ -1013,12 +1022,14 @@ gsr_k1_body(uint32_t n, uint32_t cap, const GsrFrame& f,
     KPROF_BLK_END(4, (blockIdx.x < niter ? 1u : 0u) + (niter > blockIdx.x ? (niter - 1u - blockIdx.x) / gridDim.x : 0u))
 }
 
+// (the frame sits behind the two leading dwords of the argument segment; the bodies read it from there: gsr_device.h, gsr_frame_fetch)
+#define GSR_K1_FRAME_OFF 8u
 #define GSR_K1_PARAMS uint32_t n, uint32_t cap, GsrFrame f, const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col, \
                       GsrRecord* __restrict__ rec, uint32_t* __restrict__ key, uint2* __restrict__ val, float* __restrict__ zwin, const float* __restrict__ hpyr, \
                       uint32_t* __restrict__ blk_cnt, const uint32_t* __restrict__ cseg, const uint32_t* __restrict__ ccnt, uint32_t ngroups, uint32_t cper, \
                       uint32_t* __restrict__ d_counts, GsrK1Scatter sc, uint32_t* __restrict__ zero_n, const uint32_t* __restrict__ order, const uint32_t* __restrict__ slab, \
                       GsrDepthCull dc
-#define GSR_K1_ARGS n, cap, f, geoA, geoB, col, rec, key, val, zwin, hpyr, blk_cnt, cseg, ccnt, ngroups, cper, d_counts, sc, zero_n, order, slab, dc
+#define GSR_K1_ARGS n, cap, gsr_frame_arg(GSR_K1_FRAME_OFF), geoA, geoB, col, rec, key, val, zwin, hpyr, blk_cnt, cseg, ccnt, ngroups, cper, d_counts, sc, zero_n, order, slab, dc
 // the two entry points: colours evaluated here (eager: 80 VGPRs, 6 waves per SIMD) or left pending (52 VGPRs, 8 waves per SIMD)
 __global__ void __launch_bounds__(GSR_K1_THREADS) __attribute__((amdgpu_waves_per_eu(GSR_K1_WAVES_PER_EU)))
 k_preprocess(GSR_K1_PARAMS) { gsr_k1_body<false, false>(GSR_K1_ARGS); }

@@ -131,7 +131,7 @@ C_ABI_SYMBOLS = [
     "gsr_upload_begin", "gsr_upload_append", "gsr_upload_append_raw", "gsr_upload_end", "gsr_upload_abort", "gsr_upload", "gsr_set_row_shard", "gsr_band_rows",
     "gsr_stitch_bands", "gsr_render", "gsr_render_depth", "gsr_render_wire", "gsr_render_wire_over", "gsr_synchronize", "gsr_get_stats", "gsr_stats_reset", "gsr_set_option",
     "gsr_debug_read_records", "gsr_debug_read_depth_order", "gsr_debug_read_storage_order", "gsr_debug_read_tile_lists", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_local", "gsr_debug_policy", "gsr_debug_policy_state", "gsr_debug_frame_plan",
-    "gsr_debug_read_tile_work", "gsr_debug_read_horizons",
+    "gsr_debug_read_tile_work", "gsr_debug_read_horizons", "gsr_debug_read_cull",
     "gsr_multi_create", "gsr_multi_destroy", "gsr_multi_count", "gsr_multi_transport", "gsr_multi_context",
     "gsr_multi_set_stream", "gsr_multi_set_option", "gsr_multi_upload_begin", "gsr_multi_upload_append",
     "gsr_multi_upload_end", "gsr_multi_upload_abort", "gsr_multi_upload", "gsr_multi_render", "gsr_multi_render_depth",
@@ -223,6 +223,7 @@ def load_library() -> C.CDLL:
     L.gsr_set_option.argtypes = [vp, i32, i32]
     L.gsr_debug_read_records.argtypes = [vp, vp, i64]
     L.gsr_debug_read_depth_order.argtypes = [vp, vp, i64, C.POINTER(C.c_int64)]
+    L.gsr_debug_read_cull.argtypes = [vp, vp, i64, vp, i64, C.POINTER(C.c_int64)]
     L.gsr_debug_read_tile_lists.argtypes = [vp, vp, vp, i64, vp, i64]
     L.gsr_debug_read_storage_order.argtypes = [vp, vp, i64]
     L.gsr_debug_sort_pairs.argtypes = [vp, vp, vp, i64, i32]
@@ -829,6 +830,17 @@ class Engine:
         out = np.zeros(n, dtype=DEBUG_RECORD_DTYPE)
         _check(self.L.gsr_debug_read_records(self.h, out.ctypes.data, n))
         return out
+
+    def debug_cull(self, n: int):
+        """(rect[n] uint32: the packed tile rect K1 gave each splat, by upload index, 0xffffffff = it left no sort entry; the ordered list
+        of the clusters k_cluster_cull kept, cluster k = storage slots [64 k, 64 k + 64)) of the last frame"""
+        rect = np.zeros(n, dtype=np.uint32)
+        nclus = (n + 63) // 64
+        clus = np.zeros(max(nclus, 1), dtype=np.uint32)
+        cnt = C.c_int64()
+        _check(self.L.gsr_debug_read_cull(self.h, rect.ctypes.data, n, clus.ctypes.data, nclus, C.byref(cnt)))
+        assert cnt.value <= nclus
+        return rect, clus[:cnt.value]
 
     def debug_depth_order(self, n: int) -> np.ndarray:
         """indices of the splats that survived culling, nearest first"""

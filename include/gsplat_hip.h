@@ -557,6 +557,12 @@ typedef struct gsr_debug_record {
     int32_t visible;   /* 0 = culled */
 } gsr_debug_record;
 int  gsr_debug_read_records(gsr_context* ctx, gsr_debug_record* out, int64_t n);
+/* what the two cull stages of the last frame left.  rect[i], i < n: the packed tile rect K1 gave the splat of upload index i
+ * (x0 | y0 << 8 | x1 << 16 | y1 << 24, in units of 1, 2 or 4 tiles: frames of up to 4096, 8192, 16384 pixels a side), 0xffffffff = the
+ * splat left no sort entry.  clusters: the ordered list of the clusters k_cluster_cull kept (cluster k = storage slots [64 k, 64 k + 64):
+ * gsr_debug_read_storage_order); writes min(cap, count) of them and the count.  After a front-slab frame: its second phase's.
+ * GSR_E_INVALID after a frame that walked the splats in a cached order (no clusters). */
+int  gsr_debug_read_cull(gsr_context* ctx, uint32_t* rect, int64_t n, uint32_t* clusters, int64_t cap, int64_t* n_clusters);
 /* depth order (nearest first) of the splats that survived culling in the last frame; writes min(cap, count)
  * indices and the count */
 int  gsr_debug_read_depth_order(gsr_context* ctx, int32_t* perm, int64_t cap, int64_t* n_sorted);
