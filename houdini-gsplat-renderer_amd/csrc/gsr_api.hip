@@ -57,10 +57,12 @@ static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN
 struct SortKey {
     uint64_t gen = 0;
     int shard_index = 0, shard_count = 1, shard_layout = 0, flags = 0;
+    int band_first = 0, band_tile_rows = -1;   // an explicit band (gsr_set_row_band), -1 rows: none
     gsr_camera cam{};
     bool same(const SortKey& o) const
     {
         return gen == o.gen && shard_index == o.shard_index && shard_count == o.shard_count && shard_layout == o.shard_layout && flags == o.flags &&
+               band_first == o.band_first && band_tile_rows == o.band_tile_rows &&
                std::memcmp(&cam, &o.cam, sizeof(gsr_camera)) == 0;
     }
 };
@@ -194,6 +196,12 @@ struct FrameSlot {
     GsrSlotHints hints;                // what the slot's last frame kept, from how many clusters, between which keys (gsr_frame_plan.h)
     GsrLocalSortPolicy local_pol;      // back-off of the small-frame sort (gsr_policy.h): a run of > 64 equal keys defeats it EVERY frame
     unsigned long long* h_end = nullptr;      // pinned + mapped: ticket << 32 | violation
+    // GSR_OPT_ROW_WORK: per global tile row, ticket << 32 | blend work of the row (k_blend.h: k_row_work), pinned + mapped + coherent,
+    // GSR_MAX_TILES_SIDE words; allocated when the option is switched on
+    unsigned long long* h_rows = nullptr;
+    unsigned long long* h_rows_dev = nullptr;
+    uint32_t rows_ticket = 0;          // ticket of the attempt whose frame end queued the slot's last k_row_work (0: none yet)
+    int rows_tiles_y = 0;              // ... and the tile rows of its image
     unsigned long long* h_end_dev = nullptr;
     bool horizon_valid = false;
     int horizon_sig[7] = {0, 0, 0, 0, 0, 0, 0};   // tile geometry + geometry generation the horizons belong to
@@ -294,9 +302,11 @@ struct gsr_context {
 
     int32_t* tile_map = nullptr;       // blockIdx -> tile (XCD-aware order), -1 = idle block
     size_t map_cap = 0;
-    int map_w = 0, map_h = 0, map_si = -1, map_sc = 0, map_rpb = -1, map_shift = -1, map_grid = 0;
+    int map_w = 0, map_h = 0, map_si = -1, map_sc = 0, map_rpb = -1, map_first = -1, map_shift = -1, map_grid = 0;
 
     int shard_index = 0, shard_count = 1, shard_layout = 0;   // layout: 0 = interleaved rows, 1 = contiguous bands
+    int band_first = 0, band_tile_rows = -1;   // gsr_set_row_band: the explicit band [band_first, band_first + band_tile_rows) of tile rows; -1 rows: none
+    int opt_row_work = 0;              // GSR_OPT_ROW_WORK: every frame ends with k_row_work
     int target_format = GSR_TARGET_RGBA32F;   // what a pixel of every target is (gsr_set_target_format)
     int opt_swizzle = 2, opt_timing = 1, opt_sort_cache = 1, opt_super = 0, opt_flags = 0, opt_deferred = 0, opt_lazy = 1, opt_cull = 1, opt_timing_every = 1;
     int opt_cluster = 1, opt_morton = 1, opt_local_sort = 1;
@@ -467,7 +477,7 @@ static void slot_destroy(FrameSlot& sl)
     dev_free(sl.pvA);
     dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); sl.fb.release(); dev_free(sl.fb32); sl.aovb.release(); sl.bgb.release();
     dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
-    if (sl.h_end) (void)hipHostFree(sl.h_end); sl.depth_stage.release(); dev_free(sl.dpyr); dev_free(sl.dactive);
+    if (sl.h_end) (void)hipHostFree(sl.h_end); if (sl.h_rows) (void)hipHostFree(sl.h_rows); sl.depth_stage.release(); dev_free(sl.dpyr); dev_free(sl.dactive);
     dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
     dev_free(sl.counters); dev_free(sl.d_n);
     if (sl.h_total) (void)hipHostFree(sl.h_total);
@@ -586,7 +596,21 @@ extern "C" int gsr_set_option(gsr_context* c, int option, int value)
     case GSR_OPT_TIMING_EVERY: c->opt_timing_every = value < 1 ? 1 : (value > 1024 ? 1024 : value); break;
     case GSR_OPT_OCCLUSION_CULL: c->opt_cull = value < 0 ? 0 : (value > 3 ? 3 : value); break;
     case GSR_OPT_LAZY_COLOUR: c->opt_lazy = value < 0 ? 0 : (value > 2 ? 2 : value); break;
-    case GSR_OPT_SHARD_LAYOUT: c->shard_layout = value ? 1 : 0; break;
+    case GSR_OPT_SHARD_LAYOUT: c->shard_layout = value ? 1 : 0; break;   // (2, gsr_multi's balanced bands: bands, to a context)
+    case GSR_OPT_ROW_WORK: {
+        if (value) {   // the rows' mailboxes, once
+            HIP_TRY(hipSetDevice(c->device));
+            for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+                FrameSlot& sl = c->slot[k];
+                if (sl.h_rows) continue;
+                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_rows), GSR_MAX_TILES_SIDE * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+                std::memset(sl.h_rows, 0, GSR_MAX_TILES_SIDE * sizeof(unsigned long long));
+                HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.h_rows_dev), sl.h_rows, 0));
+            }
+        }
+        c->opt_row_work = value ? 1 : 0;
+        break;
+    }
     case GSR_OPT_CLUSTER_CULL: c->opt_cluster = value ? 1 : 0; break;
     case GSR_OPT_LOCAL_SORT: c->opt_local_sort = value < 0 ? 0 : (value > 2 ? 2 : value); break;
     case GSR_OPT_FRONT_SLAB: c->opt_slab = value < 0 ? 0 : (value > 2 ? 2 : value); break;
@@ -946,7 +970,26 @@ extern "C" int gsr_set_row_shard(gsr_context* c, int index, int count)
     if (count < 1 || index < 0 || index >= count) return set_err(GSR_E_INVALID, "gsr_set_row_shard: bad shard %d/%d", index, count);
     c->shard_index = index;
     c->shard_count = count;
+    c->band_first = 0; c->band_tile_rows = -1;   // (cancels an explicit band)
     return GSR_OK;
+}
+
+bool gsr_internal_comm_has(gsr_context* c);
+extern "C" int gsr_set_row_band(gsr_context* c, int first_tile_row, int tile_rows)
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_set_row_band: ctx is NULL");
+    if (first_tile_row < 0 || tile_rows < 0 || (int64_t)first_tile_row + tile_rows > GSR_MAX_DIM / GSR_TILE)
+        return set_err(GSR_E_INVALID, "gsr_set_row_band: bad band [%d, %d + %d) (at most %d tile rows)", first_tile_row, first_tile_row, tile_rows, GSR_MAX_DIM / GSR_TILE);
+    if (gsr_internal_comm_has(c)) return set_err(GSR_E_INVALID, "gsr_set_row_band: the context holds a communicator (gsr_comm_init sets its shard)");
+    c->shard_index = 0; c->shard_count = 1;      // (cancels a row shard)
+    c->band_first = first_tile_row; c->band_tile_rows = tile_rows;
+    return GSR_OK;
+}
+// pixel rows of the context's band image of a frame `height` pixels high
+static inline int ctx_band_rows(const gsr_context* c, int height)
+{
+    if (c->band_tile_rows >= 0) return c->band_tile_rows * GSR_TILE;
+    return c->shard_count > 1 ? gsr_band_rows(height, c->shard_index, c->shard_count) : height;
 }
 
 extern "C" int gsr_band_rows(int height, int index, int count)
@@ -1709,8 +1752,14 @@ static void build_frame(const gsr_context* c, const gsr_camera* cam, GsrFrame* f
     f->shard_index = c->shard_index;
     f->shard_count = c->shard_count;
     f->shard_rpb = (c->shard_layout == 1 && c->shard_count > 1) ? (f->tiles_y + c->shard_count - 1) / c->shard_count : 0;
+    f->shard_first = c->shard_index * f->shard_rpb;
+    if (c->band_tile_rows >= 0) {
+        // an explicit band: a band layout of its own extent (an empty one owns one row beyond every image: rpb = 0 means interleaved rows)
+        f->shard_rpb = c->band_tile_rows > 0 ? c->band_tile_rows : 1;
+        f->shard_first = c->band_tile_rows > 0 ? c->band_first : GSR_MAX_DIM / GSR_TILE;
+    }
     if (f->shard_rpb > 0) {
-        const int lo = c->shard_index * f->shard_rpb, hi = std::min(lo + f->shard_rpb, f->tiles_y);
+        const int lo = f->shard_first, hi = std::min(lo + f->shard_rpb, f->tiles_y);
         f->local_tiles_y = hi > lo ? hi - lo : 0;
     } else {
         f->local_tiles_y = (f->tiles_y > c->shard_index) ? (f->tiles_y - c->shard_index + c->shard_count - 1) / c->shard_count : 0;
@@ -1768,7 +1817,7 @@ static void build_frame(const gsr_context* c, const gsr_camera* cam, GsrFrame* f
 static int build_tile_map(gsr_context* c, const GsrFrame& f)
 {
     if (c->map_w == f.width && c->map_h == f.height && c->map_si == c->shard_index && c->map_sc == c->shard_count &&
-        c->map_rpb == f.shard_rpb && c->map_shift == f.super_shift && c->tile_map)
+        c->map_rpb == f.shard_rpb && c->map_first == f.shard_first && c->map_shift == f.super_shift && c->tile_map)
         return GSR_OK;
     int rc = sync_all(c);   // a frame in flight may still be reading the old table
     if (rc) return rc;
@@ -1778,9 +1827,9 @@ static int build_tile_map(gsr_context* c, const GsrFrame& f)
         std::vector<int32_t>& v = per_xcd[st & 7];
         const int sx = st % f.stiles_x, sy = st / f.stiles_x;
         for (int gty = sy << f.super_shift; gty < ((sy + 1) << f.super_shift) && gty < f.tiles_y; ++gty) {
-            const GsrShard sh{f.shard_index, f.shard_count, f.shard_rpb};
+            const GsrShard sh = gsr_frame_shard(f, 0);
             if (!gsr_shard_owns(sh, gty)) continue;
-            const int lty = f.shard_rpb > 0 ? gty - f.shard_index * f.shard_rpb : gty / c->shard_count;
+            const int lty = gsr_shard_local_row(sh, gty);
             for (int tx = sx << f.super_shift; tx < ((sx + 1) << f.super_shift) && tx < f.tiles_x; ++tx)
                 v.push_back(lty * f.tiles_x + tx);
         }
@@ -1799,7 +1848,7 @@ static int build_tile_map(gsr_context* c, const GsrFrame& f)
     }
     HIP_TRY(hipMemcpy(c->tile_map, map.data(), map.size() * 4, hipMemcpyHostToDevice));
     c->map_grid = (int)(chunk * 8);
-    c->map_w = f.width; c->map_h = f.height; c->map_si = c->shard_index; c->map_sc = c->shard_count; c->map_rpb = f.shard_rpb;
+    c->map_w = f.width; c->map_h = f.height; c->map_si = c->shard_index; c->map_sc = c->shard_count; c->map_rpb = f.shard_rpb; c->map_first = f.shard_first;
     c->map_shift = f.super_shift;
     return GSR_OK;
 }
@@ -1870,7 +1919,7 @@ static GsrRangeArgs range_args(gsr_context* c, FrameSlot& sl)
 // what the frame driver's caches are keyed by: the tile geometry of a frame (the horizons': this, and the geometry generation behind it)
 static inline void tile_sig(const GsrFrame& f, int* sig /* [6] */)
 {
-    const int now[6] = {f.width, f.height, f.shard_index, f.shard_count, f.shard_rpb, f.super_shift};
+    const int now[6] = {f.width, f.height, f.shard_rpb > 0 ? f.shard_first : f.shard_index, f.shard_count, f.shard_rpb, f.super_shift};   // (a band: where it begins, how many rows)
     std::memcpy(sig, now, sizeof now);
 }
 
@@ -1879,7 +1928,7 @@ static inline int32_t list_cap(const FrameSlot& sl) { return (int32_t)std::min<s
 static GsrSumArgs sum_args(const FrameJob& j)
 {
     GsrSumArgs g;
-    g.n_tiles = j.local_tiles; g.tiles_x = j.f.tiles_x; g.tiles_y = j.f.tiles_y; g.shard = GsrShard{j.f.shard_index, j.f.shard_count, j.f.shard_rpb};
+    g.n_tiles = j.local_tiles; g.tiles_x = j.f.tiles_x; g.tiles_y = j.f.tiles_y; g.shard = gsr_frame_shard(j.f, 0);
     g.super_shift = j.f.super_shift; g.stiles_x = j.f.stiles_x; g.n_super = j.n_super;
     return g;
 }
@@ -1914,7 +1963,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     a.idx_mask = f.idx_mask; a.zq0 = f.zq0; a.zqs = f.zqs;
     a.tile_dmax = (with_depth && j.dcull && !j.dblind && f.idx_mask != 0xffffffffu) ? sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap + f.pyr_off[0] : (const float*)nullptr;
     a.width = f.width; a.height = f.height; a.tiles_x = f.tiles_x; a.local_tiles = j.local_tiles;
-    a.shard = GsrShard{f.shard_index, f.shard_count, f.shard_rpb}; a.band_rows = j.band_rows;
+    a.shard = gsr_frame_shard(f, 0); a.band_rows = j.band_rows;
     a.super_shift = f.super_shift; a.rect_shift = f.rect_shift; a.stiles_x = f.stiles_x; a.use_map = j.use_map ? 1 : 0; a.flags = f.flags;
     a.list_cap = list_cap(sl);
     a.sup_work = (a.use_map && c->opt_swizzle >= 2 && sl.sup_work) ? sl.sup_work + 256 * sl.sup_par : nullptr;
@@ -1951,7 +2000,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     // band's compositing hides behind the link, which is what bounds such a frame (33 MB at ~55 GB/s = 0.6 ms per 1080p frame).
     // The launches walk the same tile table; a workgroup of another band's tile leaves at once (~3 us per extra launch).
     int nb = 1;
-    if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
+    if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && c->band_tile_rows < 0 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
     if (nb > 1 && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; nb = 1; (void)hipGetLastError(); }
     for (int b = 0; b < nb && nb > 1; ++b)
         if (!sl.ev_band[b] && hipEventCreateWithFlags(&sl.ev_band[b], hipEventDisableTiming) != hipSuccess) { sl.ev_band[b] = nullptr; nb = 1; (void)hipGetLastError(); }
@@ -1981,7 +2030,7 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
     if (j.n > 0) {
         const uint32_t nblk = div_up(j.n, (uint32_t)BN_THREADS * (uint32_t)j.bn_items);
         const size_t lds = (size_t)4 * j.bn_items * j.n_super * (8 + 4);   // lane masks (u64) + first list position (u32) per (group of 64 splats, super-tile)
-        const GsrShard shd{f.shard_index, f.shard_count, f.shard_rpb, f.rect_shift};
+        const GsrShard shd = gsr_frame_shard(f, f.rect_shift);
         const GsrRangeArgs ra = j.ranges_folded ? range_args(c, sl) : GsrRangeArgs{};
         // (+ the extra work items of the blocks that are split by rows of super-tiles, k_binning.h; +1: the publishing workgroup)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
@@ -2100,6 +2149,13 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
         sl.order_per_xcd = per_xcd;
         sl.order_valid = true;
         sl.order_age = 0;
+    }
+    if (c->opt_row_work && sl.h_rows_dev) {
+        // the tile rows' work, into the slot's mapped words (one launch more; nothing waits for it)
+        hipLaunchKernelGGL(k_row_work, dim3((unsigned)((j.f.tiles_y + RW_THREADS / 64 - 1) / (RW_THREADS / 64))), dim3(RW_THREADS), 0, s, sl.tile_work,
+                           j.phase == 2 ? sl.tile_work_a : (const uint4*)nullptr, g, sl.h_rows_dev, j.ticket);
+        HIP_TRY(hipGetLastError());
+        sl.rows_ticket = j.ticket; sl.rows_tiles_y = j.f.tiles_y;
     }
     sl.sup_par ^= 1;
     if (j.f.sh_order > 0 && c->opt_lazy) c->prefix_valid = j.phase == 0;   // (eager frames keep the scan depths too: the switch to lazy starts predicted;
@@ -2439,7 +2495,7 @@ static int frame_open(gsr_context* c, const FrameArgs& a, FrameSlot*& slot)
     build_frame(c, cam, &j.f);
     j.n = c->n;
     j.local_tiles = j.f.tiles_x * j.f.local_tiles_y;
-    j.band_rows = (c->shard_count > 1) ? gsr_band_rows(cam->height, c->shard_index, c->shard_count) : cam->height;
+    j.band_rows = ctx_band_rows(c, cam->height);
     j.out_px = (size_t)j.band_rows * cam->width;
     j.n_super = j.f.stiles_x * j.f.stiles_y;
     j.use_map = c->opt_swizzle != 0;
@@ -2453,7 +2509,7 @@ static void plan_frame(gsr_context* c, FrameSlot& sl, FrontEnd& fe, bool allow_c
     const FrameArgs& a = j.args;
     const gsr_camera* cam = &a.cam;
     const GsrFrame& f = j.f;
-    fe.key_now = SortKey{c->geo_gen, c->shard_index, c->shard_count, c->shard_layout, c->opt_flags, *cam};
+    fe.key_now = SortKey{c->geo_gen, c->shard_index, c->shard_count, c->shard_layout, c->opt_flags, c->band_first, c->band_tile_rows, *cam};
     int sig[7] = {0, 0, 0, 0, 0, 0, (int)c->geo_gen};
     tile_sig(f, sig);
     GsrPlanIn in;
@@ -2777,7 +2833,7 @@ static int queue_binning(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
         const uint32_t bn_tile = (uint32_t)BN_THREADS * (uint32_t)j.bn_items;
         const uint32_t nblk = fe.p.bn_blocks;
         if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)BN_BINS * nblk + 8))) return rc;
-        const GsrShard shd{f.shard_index, f.shard_count, f.shard_rpb, f.rect_shift};
+        const GsrShard shd = gsr_frame_shard(f, f.rect_shift);
         // (+ the extra work items of the blocks that are split by rows of super-tiles: k_binning.h, BN_SPLIT_TILES)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
 #define GSR_COUNT(I) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bin_count<I>), dim3(j.bn_grid + bn_extra), dim3(BN_THREADS), 0, s, sl.valA, sl.d_n, f.super_shift - f.rect_shift, \
@@ -2947,6 +3003,7 @@ extern "C" int gsr_render_aov(gsr_context* c, const gsr_camera* cam, const float
 static int render_frame(gsr_context* c, const FrameArgs& a)
 {
     FrameSlot* sl = nullptr;
+    if (c->band_tile_rows == 0) return GSR_OK;   // (gsr_set_row_band: a rank that owns nothing -- no frame, nothing written)
 #ifdef GSR_HOST_PHASES
     static double acc[4] = {0, 0, 0, 0}, t_last_exit = 0; static long cnt = 0;
     auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -2996,7 +3053,7 @@ extern "C" int gsr_render_over(gsr_context* c, const gsr_camera* cam, const floa
         if ((uintptr_t)bg->image % ibpp != 0) return set_err(GSR_E_INVALID, "gsr_render_over: the device image is not aligned to its %d-byte pixel", (int)ibpp);
         if (out_is_device && cam->width > 0 && cam->height > 0 && cam->width <= GSR_MAX_DIM && cam->height <= GSR_MAX_DIM) {
             // (no in-place form: an attempt that is composited again -- a repair, a re-queue -- must read the original background)
-            const int rows = c->shard_count > 1 ? gsr_band_rows(cam->height, c->shard_index, c->shard_count) : cam->height;
+            const int rows = ctx_band_rows(c, cam->height);
             const uintptr_t i0 = (uintptr_t)bg->image, i1 = i0 + (size_t)cam->width * cam->height * ibpp;
             const uintptr_t o0 = (uintptr_t)rgba_out, o1 = o0 + (size_t)cam->width * rows * (size_t)gsr_format_pixel_bytes(c->target_format);
             if (i0 < o1 && o0 < i1) return set_err(GSR_E_INVALID, "gsr_render_over: the device image overlaps the device target (there is no in-place form)");
@@ -3066,6 +3123,7 @@ __attribute__((visibility("hidden"))) int gsr_internal_frame_begin(gsr_context* 
 {
     if (!c || !cam || !out_dev) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
     if (!target_aligned(c, out_dev)) return set_err(GSR_E_INVALID, "gsr_render: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
+    if (c->band_tile_rows == 0) return GSR_OK;   // (an empty explicit band: no frame)
     return frame_begin(c, FrameArgs{*cam, depth, depth_is_device != 0, out_dev, true}, nullptr, true);
 }
 __attribute__((visibility("hidden"))) int gsr_internal_frame_finish(gsr_context* c) { return c ? finish_open_frames(c) : GSR_OK; }
@@ -3074,7 +3132,7 @@ __attribute__((visibility("hidden"))) int gsr_internal_frame_check(gsr_context* 
                                                                     int depth_is_device, float* out_dev)
 {
     FrameSlot* sl = c ? latest_slot(c) : nullptr;
-    if (!sl) return GSR_OK;
+    if (!sl || c->band_tile_rows == 0) return GSR_OK;
     if (!cam || !out_dev) return set_err(GSR_E_INVALID, "gsr_render: NULL argument");
     return frame_check(c, *sl, FrameArgs{*cam, depth, depth_is_device != 0, out_dev, true});
 }
@@ -3230,6 +3288,50 @@ extern "C" int gsr_get_stats(gsr_context* c, gsr_stats* out)
         }
     }
     *out = c->st;
+    return GSR_OK;
+}
+
+// the newest complete set of row sums among the slots' mailboxes (no synchronisation: a set that is being written, or torn, is skipped).
+// A slot's words belong to its last frame when they carry the ticket of the slot's last attempt (rows_ticket == ticket).  -> 0, or 1: none
+static int peek_row_work(gsr_context* c, uint32_t* out, int n_rows, int64_t* frame_out)
+{
+    int order[GSR_MAX_SLOTS];
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) order[k] = k;
+    std::sort(order, order + GSR_MAX_SLOTS, [&](int a, int b) { return c->slot[a].frame_id > c->slot[b].frame_id; });
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
+        const FrameSlot& sl = c->slot[order[k]];
+        if (!sl.h_rows || !sl.frame_id || !sl.rows_ticket || sl.rows_ticket != sl.ticket || sl.rows_tiles_y != n_rows) continue;
+        const volatile unsigned long long* box = sl.h_rows;
+        bool whole = true;
+        for (int r = 0; r < n_rows && whole; ++r) {
+            const unsigned long long v = box[r];
+            whole = (uint32_t)(v >> 32) == sl.rows_ticket;
+            out[r] = (uint32_t)v;
+        }
+        if (!whole) continue;
+        if (frame_out) *frame_out = (int64_t)sl.frame_id;
+        return 0;
+    }
+    return 1;
+}
+// gsr_multi's balancer: whatever set is complete now, without a wait (1: none)
+__attribute__((visibility("hidden"))) int gsr_internal_peek_row_work(gsr_context* c, uint32_t* out, int n_rows, int64_t* frame_out)
+{
+    if (!c || !out || !c->opt_row_work || n_rows < 1 || n_rows > GSR_MAX_TILES_SIDE) return 1;
+    return peek_row_work(c, out, n_rows, frame_out);
+}
+
+extern "C" int gsr_read_row_work(gsr_context* c, uint32_t* out, int n_rows, int64_t* frame_out)
+{
+    if (!c || !out) return set_err(GSR_E_INVALID, "gsr_read_row_work: NULL argument");
+    if (!c->opt_row_work) return set_err(GSR_E_INVALID, "gsr_read_row_work: GSR_OPT_ROW_WORK is off");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    FrameSlot* sl = latest_slot(c);
+    if (!sl || !sl->rows_ticket) return set_err(GSR_E_INVALID, "gsr_read_row_work: no frame has run with GSR_OPT_ROW_WORK on");
+    if (n_rows != sl->rows_tiles_y) return set_err(GSR_E_INVALID, "gsr_read_row_work: expected %d tile rows", sl->rows_tiles_y);
+    if (peek_row_work(c, out, n_rows, frame_out)) return set_err(GSR_E_HIP, "gsr_read_row_work: the frame finished without delivering its row sums");
     return GSR_OK;
 }
 

@@ -71,7 +71,8 @@ struct GsrFrame {
     int32_t tiles_x;   // ceil(width/16)
     int32_t tiles_y;   // ceil(height/16) (whole image)
     int32_t shard_index, shard_count;  // which tile rows are ours: see GsrShard
-    int32_t shard_rpb;                 // 0 = interleaved rows (r % count == index); > 0 = contiguous bands of rpb tile rows
+    int32_t shard_rpb;                 // 0 = interleaved rows (r % count == index); > 0 = a contiguous band of rpb tile rows ...
+    int32_t shard_first;               // ... that begins at this tile row (layout 1: index * rpb; gsr_set_row_band: the caller's)
     int32_t local_tiles_y;             // rows owned by this shard
     int32_t super;                     // super-tile edge in tiles (power of two)
     int32_t super_shift;               // log2(super)
@@ -339,26 +340,38 @@ __device__ __forceinline__ uint32_t gsr_pack_rect(int x0, int y0, int x1, int y1
 // Tile-row ownership of a rank.  Two layouts:
 //   interleaved (rpb == 0): row r belongs to rank r % count -- balances any scene, but almost every splat reaches a row of
 //                           almost every rank once count is small against the splat's height in rows;
-//   bands       (rpb  > 0): rank g owns rows [g*rpb, (g+1)*rpb) -- a rank keeps ~1/count of the splats (plus a boundary
+//   bands       (rpb  > 0): the rank owns rows [first, first + rpb) -- a rank keeps ~1/count of the splats (plus a boundary
 //                           strip), and a splat's centre row alone usually tells whether it is ours (early-out in K1).
+//                           Layout 1 is first = index * rpb; an explicit band (gsr_set_row_band) begins wherever it is told.
 struct GsrShard {
     int32_t index, count, rpb;
     int32_t g;                         // GsrFrame.rect_shift (rects -> tile rows), 0 where no rect is involved
+    int32_t first;                     // bands: the band's first tile row
 };
+// the shard of a frame (g: the frame's rect_shift where rects are involved, else 0)
+__host__ __device__ __forceinline__ GsrShard gsr_frame_shard(const GsrFrame& f, int g)
+{
+    return GsrShard{f.shard_index, f.shard_count, f.shard_rpb, g, f.shard_first};
+}
 __host__ __device__ __forceinline__ bool gsr_shard_owns(const GsrShard& sh, int r)
 {
-    return sh.rpb > 0 ? (r / sh.rpb == sh.index) : (r % sh.count == sh.index);
+    return sh.rpb > 0 ? (r >= sh.first && r - sh.first < sh.rpb) : (r % sh.count == sh.index);
 }
 // global tile row of the rank's local row l
 __host__ __device__ __forceinline__ int gsr_shard_global_row(const GsrShard& sh, int l)
 {
-    return sh.rpb > 0 ? sh.index * sh.rpb + l : l * sh.count + sh.index;
+    return sh.rpb > 0 ? sh.first + l : l * sh.count + sh.index;
+}
+// local row of a global tile row the rank owns
+__host__ __device__ __forceinline__ int gsr_shard_local_row(const GsrShard& sh, int r)
+{
+    return sh.rpb > 0 ? r - sh.first : r / sh.count;
 }
 // number of tile rows in [y0,y1] owned by the shard
 __host__ __device__ __forceinline__ int gsr_owned_rows(int y0, int y1, const GsrShard& sh)
 {
     if (sh.rpb > 0) {
-        const int lo = sh.index * sh.rpb, hi = lo + sh.rpb - 1;
+        const int lo = sh.first, hi = lo + sh.rpb - 1;
         const int a = y0 > lo ? y0 : lo, b = y1 < hi ? y1 : hi;
         return b >= a ? b - a + 1 : 0;
     }

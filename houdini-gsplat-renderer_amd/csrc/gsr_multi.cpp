@@ -17,6 +17,10 @@
 // contiguous block of rows of the final image -- the peers' bands are received straight into the caller's framebuffer
 // (zero copy, no stitch kernel); only the root's own band is copied there.  Interleaved layout: bands are received back to
 // back and de-interleaved by k_stitch_bands on the transfer stream.
+// Balanced bands (GSR_OPT_SHARD_LAYOUT = 2): the band layout with boundaries that follow the blend work -- every rank renders an
+// explicit band (gsr_set_row_band) and leaves per-row work sums (GSR_OPT_ROW_WORK); every few frames the sums are merged and
+// gsr_balance.h proposes new boundaries (balance_bands below).  The gather takes every rank's first row and row count from the
+// boundaries of the frame it gathers.
 // RCCL is loaded at run time (dlopen) the first time a communicator is needed, so single-GPU users never map it.
 // Transport COPY (hipMemcpyPeerAsync / device-to-device copies ordered by events) exists so that the whole path -- shard,
 // render, gather, stitch -- also runs with several contexts on ONE GPU (the 1-GPU test box), where RCCL refuses duplicate
@@ -25,6 +29,7 @@
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -42,6 +47,7 @@
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
+#include "gsr_balance.h"
 
 // hooks into gsr_api.hip (hidden symbols of the same library)
 int gsr_internal_frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device, float* out_dev);
@@ -52,6 +58,7 @@ int gsr_internal_device(gsr_context* c);
 int gsr_internal_shard_layout(gsr_context* c);
 int gsr_internal_set_error(int code, const char* text);
 int gsr_internal_stitch(gsr_context* c, const float* gathered, int count, int width, int height, float* out, void* stream);
+int gsr_internal_peek_row_work(gsr_context* c, uint32_t* out, int n_rows, int64_t* frame_out);
 
 namespace {
 
@@ -240,8 +247,17 @@ struct gsr_multi {
     bool frame_rec[2] = {false, false};
     DevBuf final_fb;                     // staging of a host target
     uint64_t frame = 0;
-    int shape_sig[4] = {0, 0, -1, -1};   // width, height, layout, target format of the frames the buffers were sized for
+    int shape_sig[5] = {0, 0, -1, -1, 0};   // width, height, layout, target format, generation of the balanced boundaries of the frames the buffers were sized for
     bool uploading = false;
+    // balanced bands (GSR_OPT_SHARD_LAYOUT = 2)
+    int layout = 1;                      // 0 interleaved rows, 1 equal bands, 2 balanced bands
+    std::vector<int32_t> first;          // [G + 1] boundaries in tile rows that the ranks' explicit bands are set to (empty: none set)
+    int first_tiles_y = 0;               // ... of an image this many tile rows high
+    std::vector<int32_t> last_first;     // the boundaries of the last frame (gsr_multi_get_bands)
+    std::vector<int> row0[2], rows[2];   // per double-buffer slot: every rank's first pixel row and live pixel rows in the frame gathered from it
+    int64_t rebalances = 0;
+    int since_eval = 0;                  // frames since the boundaries were last set or evaluated
+    int period = GSR_MULTI_BALANCE_PERIOD, gain = GSR_MULTI_BALANCE_GAIN;   // (A/B hooks: GSR_BALANCE_PERIOD, GSR_BALANCE_GAIN in the environment)
     // gather timing (gsr_multi_gather_stats)
     bool time_gather = false;
     bool t0_rec[2] = {false, false};
@@ -371,6 +387,8 @@ extern "C" int gsr_multi_create(const int* devices, int count, int transport, gs
     gsr_multi* m = new (std::nothrow) gsr_multi();
     if (!m) return fail(GSR_E_OOM, "gsr_multi_create: host allocation failed");
     m->transport = transport;
+    if (const char* e = std::getenv("GSR_BALANCE_PERIOD")) { const int v = std::atoi(e); if (v >= 2) m->period = v; }                // (A/B hook)
+    if (const char* e = std::getenv("GSR_BALANCE_GAIN")) { const int v = std::atoi(e); if (v >= 0 && v <= 1000) m->gain = v; }       // (A/B hook)
     m->dev.assign(devices, devices + count);
     m->ctx.assign(count, nullptr);
     m->comm.assign(count, nullptr);
@@ -382,6 +400,8 @@ extern "C" int gsr_multi_create(const int* devices, int count, int transport, gs
         m->ev_band[b].assign(count, nullptr);
         m->ev_sent[b].assign(count, nullptr);
         m->sent_rec[b].assign(count, 0);
+        m->row0[b].assign(count, 0);
+        m->rows[b].assign(count, 0);
     }
     int rc = GSR_OK;
     for (int g = 0; g < count && !rc; ++g) {
@@ -484,6 +504,15 @@ extern "C" int gsr_multi_set_option(gsr_multi* m, int option, int value)
     if (option == GSR_OPT_SHARD_LAYOUT) {   // frames in flight were rendered in the old layout
         int rc = gsr_multi_synchronize(m);
         if (rc) return rc;
+        // balanced bands: every rank leaves its rows' work; the first frame sets the equal split.  Any other layout: the ranks' row
+        // shards again (which cancels their explicit bands)
+        const int G = (int)m->ctx.size();
+        m->layout = value == 2 ? 2 : (value ? 1 : 0);
+        m->first.clear(); m->first_tiles_y = 0; m->since_eval = 0;
+        for (int g = 0; g < G; ++g) {
+            if ((rc = gsr_set_row_shard(m->ctx[g], g, G))) return rc;
+            if (G > 1 && (rc = gsr_set_option(m->ctx[g], GSR_OPT_ROW_WORK, value == 2 ? 1 : 0))) return rc;
+        }
     }
     for (gsr_context* c : m->ctx) {
         int rc = gsr_set_option(c, option, value);
@@ -590,6 +619,68 @@ extern "C" int gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const floa
     return for_each_rank(m, [=](int g) { return gsr_move(m->ctx[g], first, n, P, origin, u); });
 }
 
+// ---- balanced bands ------------------------------------------------------------------------------
+extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
+                                      int32_t* out_first)
+{
+    const int r = gsr_balance_rows(row_work, tiles_y, count, cur_first, min_gain_permille, out_first);
+    if (r < 0) return fail(GSR_E_INVALID, "gsr_debug_balance_rows: bad argument");
+    return r;
+}
+
+extern "C" int gsr_multi_get_bands(gsr_multi* m, int32_t* first, int64_t* rebalances)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_get_bands: NULL");
+    const size_t G = m->ctx.size();
+    if (m->layout == 0 || m->last_first.size() != G + 1) return fail(GSR_E_INVALID, "gsr_multi_get_bands: no frame has run in a band layout");
+    if (first) std::memcpy(first, m->last_first.data(), (G + 1) * sizeof(int32_t));
+    if (rebalances) *rebalances = m->rebalances;
+    return GSR_OK;
+}
+
+// every rank's explicit band from m->first; callers have synchronised
+static int apply_bands(gsr_multi* m)
+{
+    for (size_t g = 0; g < m->ctx.size(); ++g) {
+        const int rc = gsr_set_row_band(m->ctx[g], m->first[g], m->first[g + 1] - m->first[g]);
+        if (rc) return rc;
+    }
+    return GSR_OK;
+}
+
+// Layout 2, in front of a frame `height` pixels high.  An image of another height (the first frame among them): the equal split.
+// Otherwise, once per period: the ranks' newest row sums (mapped host memory, no wait; a rank whose set is still on its way puts
+// the evaluation off by a frame), each contributing the rows it owns, and the balancer's verdict.  New boundaries cost a
+// synchronisation, every rank's tile table and its depth horizons: the period and the gain keep that rare.
+static int balance_bands(gsr_multi* m, int height)
+{
+    const int G = (int)m->ctx.size(), tiles_y = (height + GSR_TILE - 1) / GSR_TILE;
+    int rc;
+    if (m->first_tiles_y != tiles_y || m->first.size() != (size_t)G + 1) {
+        if ((rc = gsr_multi_synchronize(m))) return rc;
+        m->first.assign((size_t)G + 1, 0);
+        gsr_equal_split(tiles_y, G, m->first.data());
+        m->first_tiles_y = tiles_y;
+        m->since_eval = 0;
+        return apply_bands(m);
+    }
+    if (m->since_eval < m->period) return GSR_OK;
+    std::vector<uint32_t> work((size_t)tiles_y, 0u), mine((size_t)tiles_y);
+    for (int g = 0; g < G; ++g) {
+        if (m->first[g + 1] <= m->first[g]) continue;                       // (an empty band: no frames, no sums)
+        if (gsr_internal_peek_row_work(m->ctx[g], mine.data(), tiles_y, nullptr)) return GSR_OK;   // not there yet: next frame
+        for (int r = m->first[g]; r < m->first[g + 1]; ++r) work[r] = mine[r];
+    }
+    m->since_eval = 0;
+    std::vector<int32_t> next((size_t)G + 1);
+    const int verdict = gsr_balance_rows(work.data(), tiles_y, G, m->first.data(), m->gain, next.data());
+    if (verdict != 1) return GSR_OK;
+    if ((rc = gsr_multi_synchronize(m))) return rc;
+    m->first = next;
+    m->rebalances += 1;
+    return apply_bands(m);
+}
+
 // ---- per frame ---------------------------------------------------------------------------------
 extern "C" int gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device)
 {
@@ -606,23 +697,46 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
         return fail(GSR_E_INVALID, "gsr_multi_render: bad framebuffer size %dx%d", cam->width, cam->height);
     const int W = cam->width, H = cam->height;
     const int fpp = floats_per_pixel(m->ctx[0]);
-    const size_t bf = band_floats(W, H, G, fpp);
     if (out_is_device && (uintptr_t)rgba_out % (uintptr_t)(fpp * 4)) return fail(GSR_E_INVALID, "gsr_multi_render: the device target is not aligned to its %d-byte pixel", fpp * 4);
     const size_t npx = (size_t)W * H;
     const int b = (int)(m->frame & 1u);
     const bool bands = gsr_internal_shard_layout(m->ctx[0]) == 1;
+    const bool balanced = bands && m->layout == 2;
     int rc;
     harvest_gather_time(m, b);
-    {   // a frame of another shape: buffers are about to be regrown, and frames in flight still use them
-        const int sig[4] = {W, H, bands ? 1 : 0, fpp};
+    if (balanced && (rc = balance_bands(m, H))) return rc;
+    {   // a frame of another shape: buffers are about to be regrown, and frames in flight still use them (new boundaries: balance_bands
+        // has synchronised already; the generation keeps the rule in one place)
+        const int sig[5] = {W, H, bands ? m->layout : 0, fpp, balanced ? (int)m->rebalances : 0};
         if (std::memcmp(sig, m->shape_sig, sizeof sig) != 0) {
             if ((rc = gsr_multi_synchronize(m))) return rc;
             std::memcpy(m->shape_sig, sig, sizeof sig);
         }
     }
+    // this frame's bands: every rank's first pixel row and live pixel rows in the image, per double-buffer slot (the next frame may
+    // run under other boundaries while this one is gathered), and the floats of its band image
+    std::vector<int>& row0 = m->row0[b];
+    std::vector<int>& rows = m->rows[b];
+    std::vector<size_t> bfs((size_t)G, band_floats(W, H, G, fpp));
+    for (int g = 0; g < G && bands; ++g) {
+        if (balanced) {
+            row0[g] = m->first[g] * GSR_TILE;
+            rows[g] = std::max(std::min(m->first[g + 1] * GSR_TILE, H) - row0[g], 0);
+            bfs[g] = (size_t)(m->first[g + 1] - m->first[g]) * GSR_TILE * (size_t)W * (size_t)fpp;
+        } else {
+            row0[g] = band_first_row(H, g, G);
+            rows[g] = band_live_rows(H, g, G);
+        }
+    }
+    if (bands) {
+        if (balanced) m->last_first = m->first;
+        else { m->last_first.resize((size_t)G + 1); gsr_equal_split((H + GSR_TILE - 1) / GSR_TILE, G, m->last_first.data()); }
+    }
+    const size_t bf = bfs[0];
+    // (balanced: a buffer grows to the largest band its rank has held -- DevBuf::ensure never shrinks)
     if ((rc = m->gathered[b].ensure(m->dev[0], bands ? bf : bf * G))) return rc;
     for (int g = 1; g < G; ++g)
-        if ((rc = m->band[b][g].ensure(m->dev[g], bf))) return rc;
+        if ((rc = m->band[b][g].ensure(m->dev[g], bfs[g]))) return rc;
     float* target = rgba_out;
     if (!out_is_device) {
         if ((rc = m->final_fb.ensure(m->dev[0], npx * fpp))) return rc;
@@ -669,8 +783,8 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     HIP_OK(hipSetDevice(m->dev[0]));
     HIP_OK(hipStreamWaitEvent(x0, m->ev_user, 0));
     if (m->time_gather) { HIP_OK(hipEventRecord(m->ev_t0[b], x0)); m->t0_rec[b] = true; }
-    auto dst_of = [&](int g) { return bands ? target + (size_t)band_first_row(H, g, G) * W * fpp : m->gathered[b].p + (size_t)g * bf; };
-    auto cnt_of = [&](int g) { return bands ? (size_t)band_live_rows(H, g, G) * W * fpp : bf; };
+    auto dst_of = [&](int g) { return bands ? target + (size_t)row0[g] * W * fpp : m->gathered[b].p + (size_t)g * bf; };
+    auto cnt_of = [&](int g) { return bands ? (size_t)rows[g] * W * fpp : bf; };
     if (m->transport == GSR_TRANSPORT_RCCL) {
         for (int g = 1; g < G; ++g) {
             HIP_OK(hipSetDevice(m->dev[g]));
@@ -708,6 +822,7 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     HIP_OK(hipEventRecord(m->ev_frame[b], x0));
     m->frame_rec[b] = true;
     m->frame += 1;
+    m->since_eval += 1;
     if (!out_is_device) {
         HIP_OK(hipMemcpyAsync(rgba_out, target, npx * fpp * 4, hipMemcpyDeviceToHost, x0));
         HIP_OK(hipStreamSynchronize(x0));
@@ -870,6 +985,8 @@ extern "C" int gsr_comm_destroy(gsr_context* ctx)
     return GSR_OK;
 }
 
+// gsr_set_row_band refuses a context whose shard belongs to a communicator
+__attribute__((visibility("hidden"))) bool gsr_internal_comm_has(gsr_context* ctx) { return comm_find(ctx) != nullptr; }
 // called by gsr_destroy
 __attribute__((visibility("hidden"))) void gsr_internal_comm_release(gsr_context* ctx) { comm_erase(ctx, false); }
 

@@ -58,7 +58,7 @@ __device__ __forceinline__ void bn_for_each_super(uint32_t rc, int shift, const 
     if (x1 < x0 || y1 < y0) return;
     const int sx0 = x0 >> shift, sx1 = x1 >> shift;
     for (int sy = max(y0 >> shift, row_lo); sy <= min(y1 >> shift, row_hi); ++sy) {
-        if (sh.count > 1) {
+        if (sh.count > 1 || sh.rpb > 0) {   // (a shard, or an explicit band of a context on its own)
             const int lo = max(y0, sy << shift), hi = min(y1, ((sy + 1) << shift) - 1);
             if (gsr_owned_rect_rows(lo, hi, sh) == 0) continue;
         }
@@ -125,7 +125,7 @@ __device__ __forceinline__ void bn_group_pairs(uint2 v, int shift, const GsrShar
         const int w = (X1 >> shift) - sx0 + 1, h = min(Y1 >> shift, row_hi) - sy0 + 1;
         auto cell = [&](int ry, int cx) __attribute__((always_inline)) {
             const int sy = sy0 + ry, sx = sx0 + cx;
-            if (sh.count > 1) {
+            if (sh.count > 1 || sh.rpb > 0) {   // (a shard, or an explicit band of a context on its own)
                 const int lo = max(Y0, sy << shift), hi = min(Y1, ((sy + 1) << shift) - 1);
                 if (gsr_owned_rect_rows(lo, hi, sh) == 0) return;
             }

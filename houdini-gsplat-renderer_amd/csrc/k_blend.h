@@ -836,7 +836,7 @@ k_tile_pass(const uint4* __restrict__ tile_work, GsrSumArgs g, const int32_t* __
     bool own = false;
     int ti = 0, st = 0;
     if (inside && gsr_shard_owns(g.shard, gty)) {
-        const int lty = g.shard.rpb > 0 ? gty - g.shard.index * g.shard.rpb : gty / g.shard.count;
+        const int lty = gsr_shard_local_row(g.shard, gty);
         const int i = lty * g.tiles_x + tx;
         if (i < g.n_tiles) { own = true; ti = i; st = (gty >> g.super_shift) * g.stiles_x + (tx >> g.super_shift); }
     }
@@ -986,7 +986,7 @@ k_slab_mid(const uint4* __restrict__ tile_work_a, GsrSumArgs g, const int32_t* _
     bool own = false;
     int ti = 0, st = 0;
     if (inside && gsr_shard_owns(g.shard, gty)) {
-        const int lty = g.shard.rpb > 0 ? gty - g.shard.index * g.shard.rpb : gty / g.shard.count;
+        const int lty = gsr_shard_local_row(g.shard, gty);
         const int i = lty * g.tiles_x + tx;
         if (i < g.n_tiles) { own = true; ti = i; st = (gty >> g.super_shift) * g.stiles_x + (tx >> g.super_shift); }
     }
@@ -1261,7 +1261,7 @@ gsr_tile_order(const uint4* __restrict__ tile_work, const GsrSumArgs& g, int til
         const int tx = (sx << g.super_shift) + (j & emask), gty = (sy << g.super_shift) + (j >> g.super_shift);
         w = 0u;
         if (tx >= g.tiles_x || gty >= tiles_y || !gsr_shard_owns(g.shard, gty)) return -1;
-        const int lty = g.shard.rpb > 0 ? gty - g.shard.index * g.shard.rpb : gty / g.shard.count;
+        const int lty = gsr_shard_local_row(g.shard, gty);
         const int i = lty * g.tiles_x + tx;
         if (i >= g.n_tiles) return -1;
         w = gsr_tile_weight(tile_work[i]);
@@ -1358,4 +1358,35 @@ k_frame_end_order(const GsrTilePartial* __restrict__ partial, int nblocks, int n
     const int blk = (b - 9) * (TO_THREADS / 64) + (int)(threadIdx.x >> 6);
     if (blk >= ndilate) return;
     gsr_horizon_dilate(hz.raw, g.tiles_x, g.tiles_y, dilate_r, hz, hz.pyr_out, blk, (int)(threadIdx.x & 63u));
+}
+
+// GSR_OPT_ROW_WORK: the blend work of every GLOBAL tile row, for whoever balances bands of tile rows between ranks (gsr_multi's layout
+// 2).  One wavefront per tile row of the image: the row's tiles are contiguous in the local tile array, so a row is one strided read
+// and one wave reduction -- no atomics.  A front-slab frame's figure is both phases' (work_a: phase 1's bookkeeping, NULL otherwise),
+// as in k_tile_pass.  The sum saturates at 2^32 - 1; a row this context does not own gets 0.  Every row's word goes to mapped host
+// memory as ONE 8-byte vector store, ticket << 32 | sum (gsr_mailbox.h): a set whose words all carry the frame's ticket is complete.
+#define RW_THREADS 256
+__global__ void __launch_bounds__(RW_THREADS)
+k_row_work(const uint4* __restrict__ tile_work, const uint4* __restrict__ work_a, GsrSumArgs g, unsigned long long* __restrict__ rows, uint32_t ticket)
+{
+    const int gty = (int)blockIdx.x * (RW_THREADS / 64) + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    if (gty >= g.tiles_y) return;                                  // (whole wavefronts; no barrier below)
+    unsigned long long sum = 0ull;
+    if (gsr_shard_owns(g.shard, gty)) {
+        const int base = gsr_shard_local_row(g.shard, gty) * g.tiles_x;
+        for (int tx = lane; tx < g.tiles_x; tx += 64) {
+            const int i = base + tx;
+            if (i >= g.n_tiles) break;
+            uint4 w = tile_work[i];
+            if (work_a) {
+                const uint4 wa = work_a[i];
+                if (wa.w & 1u) w = make_uint4(0u, 0u, 0u, 0u);     // (finished inside the front slab: phase 2 spent nothing on it)
+                sum += gsr_tile_weight(wa);
+            }
+            sum += gsr_tile_weight(w);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (lane == 0) rows[gty] = ((unsigned long long)ticket << 32) | (sum > 0xffffffffull ? 0xffffffffull : sum);
 }

@@ -479,7 +479,7 @@ k_cluster_cull(GsrFrame f, const float4* __restrict__ clusA, const float4* __res
                                     covered_need = !(zlo > gsr_dpyr_max(dc.pyrc, fp->pyr_off, f.tiles_x, max(tx0 - r_, 0), max(ty0 - r_, 0), min(tx1 + r_, f.tiles_x - 1), min(ty1 + r_, f.tiles_y - 1)));
                                 }
                             }
-                            if (gsr_owned_rows(ty0, ty1, GsrShard{f.shard_index, f.shard_count, f.shard_rpb}) == 0) {
+                            if (gsr_owned_rows(ty0, ty1, gsr_frame_shard(f, 0)) == 0) {
                                 keep = false;                           // none of its tile rows is ours
                             } else if (behind) {
                                 keep = false;                           // wholly behind the opaque geometry

@@ -779,7 +779,7 @@ gsr_k1_front(const GsrFrame& f, const float4 a, const uint4 b, float* __restrict
             if (hb < 1.0e9f) {   // (false for NaN / inf: those take the full path and its finite-covariance rule)
                 const float lo_px = cy - hb - 0.5f, hi_px = cy + hb - 0.5f;
                 if (f.shard_rpb > 0) {
-                    const int band_lo = f.shard_index * f.shard_rpb * GSR_TILE_PX;
+                    const int band_lo = f.shard_first * GSR_TILE_PX;
                     const int band_hi = band_lo + f.shard_rpb * GSR_TILE_PX - 1;
                     if (hi_px < (float)band_lo || lo_px > (float)band_hi) o.far = true;
                 }
@@ -822,7 +822,7 @@ gsr_k1_back(GsrFrameArg fp, uint32_t i, uint32_t cap, const GsrK1Front& o, const
     }
     // a splat none of whose tiles belong to this context's row shard is dropped here: it costs no
     // colour fetch, no record and (sentinel key) no sorting
-    if (out_rect != GSR_RECT_EMPTY && gsr_rect_tiles(out_rect, GsrShard{f.shard_index, f.shard_count, f.shard_rpb, f.rect_shift}) == 0)
+    if (out_rect != GSR_RECT_EMPTY && gsr_rect_tiles(out_rect, gsr_frame_shard(f, f.rect_shift)) == 0)
         out_rect = GSR_RECT_EMPTY;
     // Occlusion culling against the previous frame's depth horizons (k_blend.h, k_sum_work): a tile that went opaque at some
     // depth needs nothing behind it.  A splat whose key lies beyond the horizon of EVERY tile its rect reaches (widened by the

@@ -115,6 +115,8 @@ OPT_STORAGE_ORDER = 13
 OPT_CULL_DILATE = 14
 OPT_LOCAL_SORT = 15
 OPT_FRONT_SLAB = 16
+OPT_ROW_WORK = 17
+TILE = 16               # GSR_TILE
 
 # target formats (gsr_set_target_format): what one pixel of every target is
 TARGET_RGBA32F = 0
@@ -155,7 +157,23 @@ C_ABI_SYMBOLS = [
     "gsr_update", "gsr_multi_update", "gsr_debug_read_resident", "gsplat_renderer_update_attributes", "gsplat_renderer_row_array",
     "gsr_move", "gsr_multi_move", "gsplat_renderer_move_splats",
     "gsr_upload_append_device", "gsr_update_device", "gsr_move_device", "gsr_debug_check_device_source",
+    "gsr_set_row_band", "gsr_read_row_work", "gsr_debug_balance_rows", "gsr_multi_get_bands",
 ]
+
+
+def balance_rows(row_work, count: int, cur_first=None, min_gain_permille: int = 0):
+    """gsr_debug_balance_rows (host only, no GPU): uint32 row_work[tiles_y] -> (changed: bool, int32 boundaries[count + 1]) of the
+    contiguous partition into `count` bands with the smallest largest band sum; with cur_first the proposal is adopted only if it cuts
+    the largest sum by min_gain_permille.  Raises GsrError on a bad argument"""
+    L = load_library()
+    w = np.ascontiguousarray(row_work, dtype=np.uint32).reshape(-1)
+    cur = None if cur_first is None else np.ascontiguousarray(cur_first, dtype=np.int32).reshape(-1)
+    if cur is not None and cur.size != count + 1:
+        raise ValueError("cur_first holds count + 1 boundaries")
+    out = np.zeros(max(int(count), 0) + 1, np.int32)
+    rc = L.gsr_debug_balance_rows(_ptr(w) if w.size else None, int(w.size), int(count), _ptr(cur), int(min_gain_permille), out.ctypes.data)
+    _check(rc if rc < 0 else 0)
+    return bool(rc), out
 
 
 POLICY_FIELDS = ("cull_pays", "cull_weak", "vis_unculled", "cull_holdoff", "cull_backoff", "cull_streak", "cull_dilate", "opt_dilate",
@@ -304,6 +322,10 @@ def load_library() -> C.CDLL:
     L.gsr_multi_synchronize.argtypes = [vp]
     L.gsr_multi_get_stats.argtypes = [vp, i32, C.POINTER(gsr_stats)]
     L.gsr_multi_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.gsr_set_row_band.argtypes = [vp, i32, i32]
+    L.gsr_read_row_work.argtypes = [vp, vp, i32, C.POINTER(C.c_int64)]
+    L.gsr_debug_balance_rows.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.gsr_multi_get_bands.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.gsr_multi_gather_stats.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.gsr_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.gsr_comm_get_unique_id.argtypes = [vp]
@@ -680,9 +702,28 @@ class Engine:
     def set_row_shard(self, index: int, count: int):
         _check(self.L.gsr_set_row_shard(self.h, index, count))
         self.shard = (index, count)
+        self.band = None
+
+    def set_row_band(self, first_tile_row: int, tile_rows: int):
+        """gsr_set_row_band: render only the tile rows [first_tile_row, first_tile_row + tile_rows); the render* methods then return
+        the band image, tile_rows * 16 pixel rows (row 0 = the bottom pixel row of tile row first_tile_row)"""
+        _check(self.L.gsr_set_row_band(self.h, int(first_tile_row), int(tile_rows)))
+        self.shard = (0, 1)
+        self.band = (int(first_tile_row), int(tile_rows))
 
     def band_rows(self, height: int) -> int:
+        if getattr(self, "band", None) is not None:
+            return self.band[1] * TILE
         return height if self.shard[1] == 1 else int(self.L.gsr_band_rows(height, self.shard[0], self.shard[1]))
+
+    def read_row_work(self, height: int):
+        """gsr_read_row_work (OPT_ROW_WORK = 1): (uint32 [ceil(height / 16)] blend work per GLOBAL tile row of the newest frame, 0 for
+        rows this context does not own; the frame's ordinal).  Synchronises"""
+        n = (int(height) + TILE - 1) // TILE
+        out = np.zeros(n, np.uint32)
+        frame = C.c_int64(0)
+        _check(self.L.gsr_read_row_work(self.h, out.ctypes.data, n, C.byref(frame)))
+        return out, frame.value
 
     # ---- per frame
     def render(self, cam) -> np.ndarray:
@@ -1178,6 +1219,13 @@ class MultiEngine:
         st = gsr_stats()
         _check(self.L.gsr_multi_get_stats(self.h, rank, C.byref(st)))
         return st.as_dict()
+
+    def get_bands(self):
+        """gsr_multi_get_bands: ([count + 1] boundaries of the last frame's bands in tile rows, how often they have changed)"""
+        first = np.zeros(self.count + 1, np.int32)
+        n = C.c_int64(0)
+        _check(self.L.gsr_multi_get_bands(self.h, first.ctypes.data, C.byref(n)))
+        return first, n.value
 
 
 class GSplatPrim:

@@ -22,20 +22,24 @@ def band_rows(height: int, count: int) -> int:
     return ((tiles_y(height) + count - 1) // count) * TILE
 
 
-def owned_tile_rows(height: int, index: int, count: int, layout: int = 0) -> list[int]:
-    """layout 0: interleaved rows index, index+count, ...; layout 1: the contiguous band [index*rpb, (index+1)*rpb)"""
+def owned_tile_rows(height: int, index: int = 0, count: int = 1, layout: int = 0, band=None) -> list[int]:
+    """layout 0: interleaved rows index, index+count, ...; layout 1: the contiguous band [index*rpb, (index+1)*rpb);
+    band = (first, rows): the explicit band of gsr_set_row_band (its rows inside the image)"""
     ty = tiles_y(height)
+    if band is not None:
+        return list(range(min(band[0], ty), min(band[0] + band[1], ty)))
     if layout == 1 and count > 1:
         rpb = (ty + count - 1) // count
         return list(range(index * rpb, min((index + 1) * rpb, ty)))
     return list(range(index, ty, count))
 
 
-def extract_band(full: np.ndarray, index: int, count: int, layout: int = 0) -> np.ndarray:
-    """what rank `index` would render: its owned tile rows of `full` stacked bottom-up"""
+def extract_band(full: np.ndarray, index: int = 0, count: int = 1, layout: int = 0, band=None) -> np.ndarray:
+    """what rank `index` would render: its owned tile rows of `full` stacked bottom-up (band = (first, rows): what a context with that
+    explicit band renders -- rows * 16 pixel rows, zero where the band reaches beyond the image)"""
     h, w = full.shape[0], full.shape[1]
-    out = np.zeros((band_rows(h, count), w) + full.shape[2:], dtype=full.dtype)
-    for lrow, trow in enumerate(owned_tile_rows(h, index, count, layout)):
+    out = np.zeros((band_rows(h, count) if band is None else band[1] * TILE, w) + full.shape[2:], dtype=full.dtype)
+    for lrow, trow in enumerate(owned_tile_rows(h, index, count, layout, band)):
         y0, y1 = trow * TILE, min(trow * TILE + TILE, h)
         out[lrow * TILE: lrow * TILE + (y1 - y0)] = full[y0:y1]
     return out

@@ -308,6 +308,44 @@ int  gsr_debug_check_device_source(gsr_context* ctx, const void* p, int64_t byte
  * device target -- clear it once if they are to read as zeros -- and read as zeros in a host target. */
 int  gsr_set_row_shard(gsr_context* ctx, int index, int count);
 int  gsr_band_rows(int height, int index, int count);      /* pixel rows in that band image */
+/* An EXPLICIT band: this context renders only the tile rows [first_tile_row, first_tile_row + tile_rows) of the image -- a
+ * contiguous band of any extent, wherever it begins (layout 1's bands are the special case first = index * rpb).  Rows beyond
+ * the image are owned but empty; tile_rows = 0 is a rank that owns nothing: its frame is GSR_OK, runs nothing and writes
+ * nothing.  The band image is tile_rows * GSR_TILE pixel rows of `width` pixels of the target format; row 0 is the bottom
+ * pixel row of tile row first_tile_row.  Padding as above: pixel rows beyond the image are never written in a device target
+ * and read as zeros in a host target.  Every frame verb works in a band (gsr_render, _depth, _aov, _over: the depth buffer and
+ * the background image are the FULL image, the outputs are the band, as for a row-sharded context), in every target format
+ * and option mode.  The band may change between frames: it is a new tile geometry, so the tile table is rebuilt (which
+ * synchronises) and depth horizons, tile orders and cached depth orders of the old band are dropped.  gsr_set_row_shard cancels
+ * an explicit band, gsr_set_row_band cancels a row shard.  gsr_band_rows and gsr_stitch_bands do not know explicit bands: a
+ * band is a block of image rows, so placing it is a row copy.
+ * GSR_E_INVALID, context untouched: NULL ctx, a negative argument, first_tile_row + tile_rows > GSR_MAX_DIM / GSR_TILE, a
+ * context that holds a communicator (gsr_comm_init: out of scope -- one process per GPU would need an all-gather of the row
+ * sums per evaluation). */
+int  gsr_set_row_band(gsr_context* ctx, int first_tile_row, int tile_rows);
+/* GSR_OPT_ROW_WORK: the newest complete set of per-tile-row work sums and the ordinal of the frame it belongs to (1-based, as
+ * the context counts the frames it rendered; frame_out may be NULL).  out[r], r < n_rows = ceil(height / GSR_TILE) of that
+ * frame, is the saturating sum over the tiles of GLOBAL tile row r of the blend kernel's per-tile work (wave-record
+ * evaluations * 32 + records gathered * 8 + list entries scanned / 2; both phases of a front-slab frame; of a repaired or
+ * re-queued frame, the attempt that produced the pixels); 0 for rows the context does not own.  Blend work only: a rank's
+ * front-end floor is not in it.  Synchronises like gsr_get_stats (the frames themselves never wait for the sums: they arrive
+ * in mapped host memory, every word stamped with the frame's ticket).  GSR_E_INVALID: the option is off, no frame has run with
+ * it, or n_rows is not that frame's. */
+int  gsr_read_row_work(gsr_context* ctx, uint32_t* out, int n_rows, int64_t* frame_out);
+/* The balancer behind GSR_OPT_SHARD_LAYOUT = 2, a pure host function (no context, no GPU).  row_work[tiles_y] -> the
+ * boundaries out_first[count + 1] (band g = tile rows [out_first[g], out_first[g + 1]); out_first[0] = 0, out_first[count] =
+ * tiles_y) of the contiguous partition into `count` bands whose LARGEST band sum (64-bit) is smallest; every band gets at
+ * least one row while tiles_y >= count (with count > tiles_y the trailing bands are empty).  Among the optimal partitions the
+ * one whose interior boundaries are closest to layout 1's equal split e[g] = min(g * ceil(tiles_y / count), tiles_y) is
+ * chosen, boundary by boundary from the first: smallest |out_first[g] - e[g]|, the smaller boundary on a tie.  All-zero work
+ * gives e (made feasible: at least one row per band) itself.
+ * Hysteresis: with cur_first (a valid partition) the proposal is adopted only if its largest band sum is at most
+ * (1000 - min_gain_permille) / 1000 of cur_first's under the same row_work; otherwise out_first = cur_first.
+ * Returns 1 = out_first differs from cur_first (always 1 without cur_first), 0 = kept, negative (GSR_E_INVALID) = bad
+ * argument: NULL row_work / out_first, tiles_y < 1 or > GSR_MAX_DIM / GSR_TILE, count < 1 or > 64, min_gain_permille outside
+ * 0..1000, a cur_first that is not a monotone cover of [0, tiles_y). */
+int  gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first,
+                            int min_gain_permille, int32_t* out_first);
 /* Root side: bands[count] gathered back to back (each padded to
  * gsr_band_rows(height, 0, count) rows) -> full image.  Device pointers; pixels of ctx's target format (set the format the
  * ranks render in on the stitching context too): a row copy, never a conversion. */
@@ -364,6 +402,22 @@ int  gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const float* de
                             float* rgba_out, int out_is_device);
 int  gsr_multi_synchronize(gsr_multi* m);
 int  gsr_multi_get_stats(gsr_multi* m, int rank, gsr_stats* out);
+/* BALANCED BANDS, gsr_multi_set_option(m, GSR_OPT_SHARD_LAYOUT, 2): contiguous bands like layout 1, but their boundaries follow
+ * the blend work.  Every rank runs with GSR_OPT_ROW_WORK; the frames start from the equal split; every GSR_MULTI_BALANCE_PERIOD
+ * frames the ranks' newest row sums are merged (each rank contributes the rows it owns; nothing waits: a rank whose set has not
+ * arrived leaves the evaluation to the next period), gsr_debug_balance_rows proposes a partition, and if it cuts the heaviest
+ * band by at least GSR_MULTI_BALANCE_GAIN permille every rank gets its new band with gsr_set_row_band.  A rebalance costs a
+ * synchronisation, a tile-table rebuild and every rank's depth horizons -- hence the period and the gain.  The gather follows the
+ * bands of the frame it gathers (per-rank rows and counts).  Pixels are the 1-GPU frame's, bit for bit.
+ * gsr_multi_get_bands: first[count + 1] = the boundaries of the last frame in tile rows (layout 1: the equal split; layout 0:
+ * GSR_E_INVALID), *rebalances = how often they have changed (either may be NULL).
+ * Out of scope: gsr_comm_* (one process per GPU); balancing by anything but blend work (the per-rank front-end floor is not in the
+ * tile weights); the GSplatRenderer shim and the HDK glue keep gsr_multi's default layout 1; there is no stitch kernel for
+ * unequal bands (none is needed: a band is a block of rows). */
+#define GSR_MULTI_BALANCE_PERIOD 24     /* frames between two evaluations (LAB_NOTES.md, "Balanced bands": a rebalance costs 1.3 frame
+                                           times once the buffers exist, 5 the first time, and wins ~5 % of T1's heaviest band) */
+#define GSR_MULTI_BALANCE_GAIN   150    /* permille by which a proposal must cut the heaviest band's work sum (T1 at 4 ranks: 250) */
+int  gsr_multi_get_bands(gsr_multi* m, int32_t* first, int64_t* rebalances);
 
 /* ---- one process per GPU (torchrun-style launches): the same gather ----------- */
 /* The launcher hands every rank the 128-byte id rank 0 obtained (any side channel); after gsr_comm_init a frame is one
@@ -507,7 +561,11 @@ int  gsr_stats_reset(gsr_context* ctx);
                                        earlier frames (+25 % headroom); a frame whose pair count outgrows it is composited
                                        from clamped lists and counted in gsr_stats.frames_truncated (the buffer is regrown
                                        for the next frame).  The first frame after a buffer-less start is never deferred. */
-#define GSR_OPT_SHARD_LAYOUT     9   /* 0 (default) = interleaved tile rows, 1 = contiguous bands; set on every rank AND on the
+#define GSR_OPT_ROW_WORK        17   /* 0 (default) / 1: every frame ends with one more launch (k_row_work) that reduces the blend kernel's
+                                       per-tile work to one sum per GLOBAL tile row, in mapped host memory: gsr_read_row_work.  Off: the
+                                       frame's launches are exactly what they were */
+#define GSR_OPT_SHARD_LAYOUT     9   /* (2 = gsr_multi's balanced bands, see gsr_multi_get_bands; a plain context takes 2 as 1)
+                                       0 (default) = interleaved tile rows, 1 = contiguous bands; set on every rank AND on the
                                        context that stitches */
 #define GSR_OPT_TIMING_EVERY    11   /* timing level 1 brackets the blend kernel of every N-th frame only (default 1): a pair of events in
                                        the stream costs the GPU ~12 us of idle queue, and an average wants a sample, not a census */

@@ -4,6 +4,8 @@
 # (1080p) and C5 (4K) in both shard layouts, through ONE process (gsr_multi_*: a worker thread per rank, grouped ncclSend / ncclRecv) and
 # through one process per GPU (torch.distributed.run, gsr_comm_*).  Every bench line checks its last stitched frame bit for bit against the
 # unsharded frame and refuses a value when the communicator does not span the N ranks.  Output: gpurun_out/multi/*.json + one table.
+# Balanced bands (layout 2) run beside them through tools/multi_layout_probe.py: bench.py knows layouts 0 and 1 only, so the three layouts
+# are timed by one small driver over gsr_multi on the same GPUs, T1 (the unbalanced scene) and C4, each checked against the 1-GPU frame.
 set -u
 MAXG=${1:-8}
 NG=$(python -c "import torch; print(torch.cuda.device_count())")
@@ -26,6 +28,13 @@ for cfg in C4 C5; do
           bench.py --full --config $cfg --gpus $n --shard-layout $layout --no-cpu-baseline --no-extra-legs --steps 200 --warmup 20 \
           > $OUT/${cfg}_n${n}_layout${layout}_per_gpu.json 2> $OUT/${cfg}_n${n}_layout${layout}_per_gpu.err
     done
+  done
+done
+for cfg in T1 C4; do
+  for n in 2 4 8; do
+    [ $n -gt $MAXG ] && continue
+    python tools/multi_layout_probe.py $cfg --gpus $n --layouts 1,0,2 > $OUT/${cfg}_n${n}_layouts_0_1_2.txt 2>&1
+    tail -4 $OUT/${cfg}_n${n}_layouts_0_1_2.txt
   done
 done
 python - $OUT <<'PY'
