@@ -419,6 +419,18 @@ int GSplatRenderer::setBackground(const gsr_background* bg)
     return GSR_OK;
 }
 
+int GSplatRenderer::setVisibility(const gsr_visibility* v)
+{
+    if (v && v->mask) return GSR_E_INVALID;            // (a mask belongs to one upload: the next re-stage would lose it)
+    // the struct is checked by the one function that knows the rule: an evaluation over no splats
+    if (gsr_visibility_eval(v, nullptr, 0, 0, nullptr) != GSR_OK) return GSR_E_INVALID;
+    int rc = GSR_OK;
+    if (multi_) rc = gsr_multi_set_visibility(multi_, v);
+    else if (engine_) rc = gsr_set_visibility(engine_, v);
+    status_ = rc;
+    return rc;
+}
+
 int64_t GSplatRenderer::query(int what, const std::string& id) const
 {
     switch (what) {
@@ -524,6 +536,7 @@ void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order
 int gsplat_renderer_set_target_format(gsplat_renderer* h, int format) { return h ? h->impl->setTargetFormat(format) : GSR_E_INVALID; }
 int gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane) { return h ? h->impl->setAovTarget(aov, plane) : GSR_E_INVALID; }
 int gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg) { return h ? h->impl->setBackground(bg) : GSR_E_INVALID; }
+int gsplat_renderer_set_visibility(gsplat_renderer* h, const gsr_visibility* v) { return h ? h->impl->setVisibility(v) : GSR_E_INVALID; }
 int gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
                                       const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz,
                                       int64_t* first_out, int64_t* n_out)

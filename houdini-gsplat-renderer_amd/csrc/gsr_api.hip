@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
@@ -41,6 +42,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_wire.h"
 #include "gsr_frame_plan.h"
 #include "gsr_host_buffers.h"
+#include "k_visibility.h"   // (last: the kernels of the frame keep their places in the code object)
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -344,6 +346,16 @@ struct gsr_context {
     float* up_part = nullptr;                  // bounding-box partials
     hipEvent_t up_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     double up_t_begin = 0.0, up_h2d_ms = 0.0, up_quant_ms = 0.0;
+    // gsr_set_visibility (k_visibility.h): the rule in force, the TRUE alphas in upload order (one float per splat of capacity, valid
+    // while vis_on: geoA holds +0.0f for the hidden splats), the mask of the resident cloud, and the counter slots of k_visibility.
+    // (Behind everything a frame reads: the fields above lie where they lay before there was a visibility.)
+    bool vis_on = false;               // volumes or a mask are in force: the hooks of upload / update / move run
+    GsrVisRule vis{};
+    float* alpha0 = nullptr;
+    uint32_t* vis_mask = nullptr;      // ceil(n / 32) words, NULL: no mask
+    unsigned long long* vis_counters = nullptr;   // k_visibility's counter slots ...
+    unsigned long long* vis_h_counters = nullptr; // ... and where they are read back: pinned host memory, like the slots' read-backs
+    int64_t vis_hidden = 0;            // what the last application hid
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -538,11 +550,20 @@ extern "C" int gsr_create(int device, gsr_context** out)
     return GSR_OK;
 }
 
+// the mask belongs to a cloud: gone with it (a visibility that was a mask alone is then no visibility)
+static void vis_drop_mask(gsr_context* c)
+{
+    dev_free(c->vis_mask);
+    if (c->vis.n_volumes == 0) { c->vis_on = false; c->vis_hidden = 0; }
+}
+
 static void free_geometry(gsr_context* c)
 {
     dev_free(c->geoA); dev_free(c->geoB); dev_free(c->col); dev_free(c->colrow);
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->nclus = 0; c->h_perm.clear();
     dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(c->clusA2); dev_free(c->clusB2);
+    dev_free(c->alpha0);               // (sized by the capacity; the volumes stay in force, the next complete upload captures again)
+    vis_drop_mask(c);
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_free_splat_arrays(c->slot[k]);
     c->cap = 0; c->n = 0;
 }
@@ -560,7 +581,8 @@ extern "C" void gsr_destroy(gsr_context* c)
     dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB); dev_free(c->up_part);
     for (int k = 0; k < 4; ++k) if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]);
     dev_free(c->prefix); dev_free(c->prefix_all); dev_free(c->prefix_none); dev_free(c->lazy_hint);
-    dev_free(c->pos_order); dev_free(c->blk_pre);
+    dev_free(c->pos_order); dev_free(c->blk_pre); dev_free(c->vis_counters);
+    if (c->vis_h_counters) (void)hipHostFree(c->vis_h_counters);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
@@ -802,6 +824,10 @@ extern "C" int gsr_upload_append(gsr_context* c, int64_t n64, const float* P, co
 }
 
 static int order_and_pack(gsr_context* c);
+// visibility (the verb and its hooks are at the end of the file)
+static int vis_after_upload(gsr_context* c);
+static hipError_t vis_apply(gsr_context* c, hipStream_t us, uint32_t cap_first, uint32_t cap_cnt, bool apply, const GsrVisRule& rule,
+                            const uint32_t* mask, bool* changed);
 
 // an upload that failed after the arrays were filled: the context goes back to "nothing uploaded"
 static void drop_geometry(gsr_context* c)
@@ -809,6 +835,7 @@ static void drop_geometry(gsr_context* c)
     c->n = 0; c->nclus = 0; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->h_perm.clear();
     dev_free(c->clusA2); dev_free(c->clusB2);
+    vis_drop_mask(c);
     c->has_geometry = false;           // gsr_render: GSR_E_NO_GEOMETRY (the generation is NOT rewound: stamps of the lost cloud stay stale)
     c->geo_gen++;
     dev_free(c->wire_inv); c->wire_inv_gen = 0;
@@ -934,6 +961,7 @@ extern "C" int gsr_upload_end(gsr_context* c)
     }
     int rc = new_cloud_state(c, "upload");
     if (rc) return rc;
+    if ((rc = vis_after_upload(c))) { drop_geometry(c); return rc; }   // (the volumes in force hide their share of the new cloud; its mask is gone)
     c->st.n_splats = c->n;
     c->st.uploads += 1;
     c->st.upload_ms[0] = c->up_h2d_ms;
@@ -1245,7 +1273,9 @@ static hipError_t after_update(gsr_context* c, bool shape, hipStream_t us, hipEr
 // ---------------------------------------------------------------------------
 // Attributes of resident splats rewritten in place ("Attribute updates").  No position: the storage order, the bounding
 // box, the Morton scratch and the cluster boxes' xyz depend on P alone and stay as they are.
-extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u)
+// vis_rule: with a visibility in force and new alphas, put them aside AND apply the rule (gsr_update); false: put them aside only (the
+// attribute step of a move, which applies the rule itself once the splats sit at their new positions, in the new order)
+static int update_rows(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u, bool vis_rule)
 {
     if (!c || !u) return set_err(GSR_E_INVALID, "gsr_update: NULL argument");
     if (c->uploading) return set_err(GSR_E_INVALID, "gsr_update: upload in progress");
@@ -1302,6 +1332,8 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
         // (the bounds of ALL clusters: a Morton-ordered store scatters the range over them, and the pass reads 32 bytes per splat)
         if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
         e = hipGetLastError();
+        // a visibility in force: the new alphas are put aside, and the hidden ones among them go back to +0.0f (a move does that itself)
+        if (e == hipSuccess && c->vis_on && u->alpha) e = vis_apply(c, us, (uint32_t)first, n, vis_rule, c->vis, c->vis_mask, nullptr);
     }
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);
@@ -1311,6 +1343,11 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
     c->st.upload_ms[4] = h2d_ms;
     if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
     return GSR_OK;
+}
+
+extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u)
+{
+    return update_rows(c, first, n64, u, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -1369,7 +1406,7 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     double h2d_ms = 0.0;
     // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
     if (attrs) {
-        rc = attr_step();
+        rc = attr_step();              // (a visibility in force: the step puts new alphas aside; the rule is applied below, at the new positions)
         // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
         //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
         if (rc == GSR_E_HIP) return lost(rc);
@@ -1421,6 +1458,9 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     }
     c->h_perm.clear();
     if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
+    // 6. a visibility in force: the volumes against the positions the splats have now, in the order they sit in now
+    if (c->vis_on && (e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess)
+        return lost(set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e)));
     if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }   // (the policy word could not be reset: a HIP failure like any other)
     c->st.moves += 1;
     float ms = 0.0f;
@@ -1455,7 +1495,7 @@ extern "C" int gsr_move(gsr_context* c, int64_t first, int64_t n64, const float*
         upd_bytes = (u->alpha ? pad(cnt * 4) : 0) + (u->Cd ? pad(cnt * 6) : 0) + (u->scale ? pad(cnt * 6) : 0) +
                     (u->orient ? pad(cnt * 8) : 0) + (nsh ? 3 * pad(cnt * 32) : 0);
     return move_body(c, "gsr_move", first, n64, origin, cnt * 12, upd_bytes, attrs,
-                     [&]() { return gsr_update(c, first, n64, u); },
+                     [&]() { return update_rows(c, first, n64, u, false); },
                      [&](float* arena, hipStream_t us, const float** Pnew, double* h2d_ms) {
                          const double t0 = up_now_ms();
                          hipError_t e = hipMemcpyAsync(arena, P, cnt * 12, hipMemcpyHostToDevice, us);
@@ -1566,7 +1606,7 @@ static int refuse_device_update(gsr_context* c, const gsr_device_attrs* a, const
 }
 
 // gsr_update_device behind its refusals: gsr_update without the staging -- k_update_f32 reads the caller's rows where they are
-static int update_device_rows(gsr_context* c, int64_t first, uint32_t n, const gsr_device_attrs* a, const char* who)
+static int update_device_rows(gsr_context* c, int64_t first, uint32_t n, const gsr_device_attrs* a, const char* who, bool vis_rule /* as update_rows takes it */)
 {
     HIP_TRY(hipSetDevice(c->device));
     int rc = sync_all(c);      // the public stream (a producer queued there has finished), and no in-place write under a frame in flight
@@ -1586,6 +1626,7 @@ static int update_device_rows(gsr_context* c, int64_t first, uint32_t n, const g
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<false>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
         if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
         e = hipGetLastError();
+        if (e == hipSuccess && c->vis_on && a->alpha) e = vis_apply(c, us, (uint32_t)first, n, vis_rule, c->vis, c->vis_mask, nullptr);   // (as in update_rows)
     }
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
@@ -1609,7 +1650,7 @@ extern "C" int gsr_update_device(gsr_context* c, int64_t first, int64_t n64, con
     if (rc) return rc;
     if (n64 == 0 || !(a->Cd || a->alpha || a->scale || a->orient || a->sh)) return GSR_OK;
     if ((rc = check_device_attrs(c, a, (size_t)n64, "gsr_update_device"))) return rc;
-    return update_device_rows(c, first, (uint32_t)n64, a, "gsr_update_device");
+    return update_device_rows(c, first, (uint32_t)n64, a, "gsr_update_device", true);
 }
 
 extern "C" int gsr_move_device(gsr_context* c, int64_t first, int64_t n64, const float origin[3], const gsr_device_attrs* a)
@@ -1627,7 +1668,7 @@ extern "C" int gsr_move_device(gsr_context* c, int64_t first, int64_t n64, const
     const bool attrs = a->Cd || a->alpha || a->scale || a->orient || a->sh;
     // (k_move_positions reads the caller's P where it is, and the attribute step stages nothing: the arena holds the positions in upload order only)
     return move_body(c, "gsr_move_device", first, n64, origin, 0, 0, attrs,
-                     [&]() { return update_device_rows(c, first, (uint32_t)n64, a, "gsr_move_device"); },
+                     [&]() { return update_device_rows(c, first, (uint32_t)n64, a, "gsr_move_device", false); },
                      [&](float*, hipStream_t, const float** Pnew, double*) { *Pnew = a->P; return hipSuccess; });
 }
 
@@ -3613,4 +3654,172 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
     dev_free(kA); dev_free(kB); dev_free(vA); dev_free(vB);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_debug_sort_pairs: %s", hipGetErrorString(e));
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Visibility (k_visibility.h): resident splats hidden by crop volumes or a mask.  The verb and three hooks -- behind a
+// complete upload, behind an alpha update, behind a move -- that run only while a visibility is in force.
+static_assert(sizeof(gsr_crop_volume) == sizeof(GsrVisVolume) && offsetof(gsr_visibility, mask) == sizeof(GsrVisRule) &&
+              offsetof(gsr_visibility, volume) == offsetof(GsrVisRule, vol) && GSR_VIS_MAX_VOLUMES == GSR_VIS_VOLUMES &&
+              GSR_VOL_BOX == GSR_VISK_BOX && GSR_VOL_ELLIPSOID == GSR_VISK_ELLIPSOID, "gsr_visibility begins with the kernel's rule");
+
+// what is wrong with the caller's struct (NULL: nothing; v == NULL is "everything visible")
+static const char* visibility_error(const gsr_visibility* v)
+{
+    if (!v) return nullptr;
+    if (v->n_volumes < 0 || v->n_volumes > GSR_VIS_MAX_VOLUMES) return "n_volumes is not within 0..GSR_VIS_MAX_VOLUMES";
+    if (v->reserved_ != 0) return "reserved_ is not 0";
+    for (int k = 0; k < v->n_volumes; ++k) {
+        if (v->volume[k].kind != GSR_VOL_BOX && v->volume[k].kind != GSR_VOL_ELLIPSOID) return "unknown volume kind";
+        if (v->volume[k].invert != 0 && v->volume[k].invert != 1) return "invert is neither 0 nor 1";
+    }
+    return nullptr;
+}
+// the rule of v as the kernel takes it (volumes beyond n_volumes zeroed)
+static GsrVisRule visibility_rule(const gsr_visibility* v)
+{
+    GsrVisRule r{};
+    if (v) {
+        r.n_volumes = v->n_volumes;
+        std::memcpy(r.vol, v->volume, sizeof(GsrVisVolume) * (size_t)v->n_volumes);
+    }
+    return r;
+}
+
+extern "C" int gsr_visibility_eval(const gsr_visibility* v, const float* P, int64_t first, int64_t n, uint8_t* visible_out)
+{
+    const char* bad = visibility_error(v);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_visibility_eval: %s", bad);
+    if (first < 0 || n < 0 || (n > 0 && (!P || !visible_out))) return set_err(GSR_E_INVALID, "gsr_visibility_eval: bad argument");
+    const uint32_t* const mask = v ? v->mask : nullptr;
+    if (mask && (v->mask_splats < 0 || first > v->mask_splats || n > v->mask_splats - first))
+        return set_err(GSR_E_INVALID, "gsr_visibility_eval: splats [%lld, %lld + %lld) are not within the %lld of the mask", (long long)first, (long long)first,
+                       (long long)n, (long long)v->mask_splats);
+    const GsrVisRule rule = visibility_rule(v);
+    for (int64_t k = 0; k < n; ++k) {
+        const uint64_t i = (uint64_t)(first + k);
+        visible_out[k] = gsr_splat_visible(rule, P[3 * k], P[3 * k + 1], P[3 * k + 2], mask ? mask[i >> 5] : 0u, (uint32_t)(i & 31u)) ? 1 : 0;
+    }
+    return GSR_OK;
+}
+
+// room for the true alphas and the counters: before the first write of whoever applies the rule
+static int vis_ensure_buffers(gsr_context* c)
+{
+    int rc = GSR_OK;
+    if (!c->alpha0 && (rc = dev_alloc(&c->alpha0, (size_t)c->cap))) return rc;
+    const size_t words = (size_t)GSR_VIS_COUNTER_SLOTS * GSR_VIS_COUNTER_STRIDE;
+    if (!c->vis_counters && (rc = dev_alloc(&c->vis_counters, words))) return rc;
+    if (!c->vis_h_counters && hipHostMalloc(reinterpret_cast<void**>(&c->vis_h_counters), words * 8, 0) != hipSuccess) {
+        c->vis_h_counters = nullptr;
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "no pinned host memory for the visibility counters");
+    }
+    return GSR_OK;
+}
+
+// On `us`: the true alphas of the splats [cap_first, cap_first + cap_cnt) (upload order; geoA holds them; 0: none) into alpha0 -- through
+// the inverse of the storage order, which the caller has ensured -- then, with `apply`, the rule over every storage slot.  Waits for
+// the counters: *changed = a resident bit changed, c->vis_hidden = what is hidden now.
+static hipError_t vis_apply(gsr_context* c, hipStream_t us, uint32_t cap_first, uint32_t cap_cnt, bool apply, const GsrVisRule& rule,
+                            const uint32_t* mask, bool* changed)
+{
+    const uint32_t n = c->n;
+    if (changed) *changed = false;
+    if (n == 0) { c->vis_hidden = 0; return hipSuccess; }
+    if (!c->alpha0 || !c->vis_counters || !c->vis_h_counters) return hipErrorInvalidValue;       // (the callers allocate before their first write)
+    if (cap_cnt) hipLaunchKernelGGL(k_alpha_capture, dim3(div_up(cap_cnt, 256)), dim3(256), 0, us, cap_first, cap_cnt,
+                                    c->perm ? c->wire_inv : (const uint32_t*)nullptr, c->geoA, c->alpha0);
+    if (!apply) return hipGetLastError();
+    const size_t words = (size_t)GSR_VIS_COUNTER_SLOTS * GSR_VIS_COUNTER_STRIDE;
+    hipError_t e = hipMemsetAsync(c->vis_counters, 0, words * 8, us);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_visibility, dim3(div_up(n, 256)), dim3(256), 0, us, n, c->perm, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, c->alpha0,
+                       mask, rule, c->vis_counters);
+    e = hipGetLastError();
+    const unsigned long long* const h = c->vis_h_counters;
+    if (e == hipSuccess) e = hipMemcpyAsync(c->vis_h_counters, c->vis_counters, words * 8, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return e;
+    unsigned long long n_hidden = 0, n_changed = 0;        // (a slot's words cannot carry: each counts at most n <= 2^31 splats)
+    for (size_t k = 0; k < words; k += GSR_VIS_COUNTER_STRIDE) { n_hidden += h[k] & 0xffffffffull; n_changed += h[k] >> 32; }
+    c->vis_hidden = (int64_t)n_hidden;
+    if (changed) *changed = n_changed != 0;
+    return hipSuccess;
+}
+
+// behind a complete upload (the generation is the new cloud's): its mask is gone; the volumes in force hide their share of it
+static int vis_after_upload(gsr_context* c)
+{
+    vis_drop_mask(c);
+    c->vis_hidden = 0;
+    if (!c->vis_on || c->n == 0) return GSR_OK;
+    int rc = vis_ensure_buffers(c);
+    if (!rc) rc = ensure_inverse_perm(c);
+    if (rc) return rc;
+    const hipError_t e = vis_apply(c, c->slot[0].own, 0u, c->n, true, c->vis, nullptr, nullptr);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_end: applying the visibility: %s", hipGetErrorString(e));
+    return GSR_OK;
+}
+
+extern "C" int gsr_set_visibility(gsr_context* c, const gsr_visibility* v)
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_set_visibility: ctx is NULL");
+    const char* bad = visibility_error(v);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_set_visibility: %s", bad);
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_set_visibility: upload in progress");
+    const bool has_mask = v && v->mask;
+    if (has_mask && !c->has_geometry) return set_err(GSR_E_INVALID, "gsr_set_visibility: a mask belongs to a cloud, and none is resident");
+    if (has_mask && v->mask_splats != (int64_t)c->n)
+        return set_err(GSR_E_INVALID, "gsr_set_visibility: the mask covers %lld splats, %u are resident", (long long)v->mask_splats, c->n);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);      // no in-place write under a frame in flight
+    if (rc) return rc;
+    const GsrVisRule rule = visibility_rule(v);
+    if (!c->has_geometry || c->n == 0) {               // nothing to hide yet: the volumes wait for gsr_upload_end
+        dev_free(c->vis_mask);
+        c->vis = rule; c->vis_on = rule.n_volumes > 0; c->vis_hidden = 0;
+        return GSR_OK;
+    }
+    const bool on = rule.n_volumes > 0 || has_mask;
+    if (!on && !c->vis_on) return GSR_OK;              // everything is visible already
+    // ---- everything the call needs, before the first write
+    if ((rc = vis_ensure_buffers(c))) return rc;
+    const size_t words = ((size_t)c->n + 31) / 32;
+    uint32_t* mask_new = nullptr;
+    if (has_mask && (rc = dev_alloc(&mask_new, words))) return rc;
+    // (geoA holds every true alpha exactly while no visibility is in force: that is when they are put aside)
+    const bool capture = !c->vis_on;
+    if (capture && (rc = ensure_inverse_perm(c))) { dev_free(mask_new); return rc; }
+    hipStream_t us = c->slot[0].own;
+    hipError_t e = has_mask ? hipMemcpyAsync(mask_new, v->mask, words * 4, hipMemcpyHostToDevice, us) : hipSuccess;
+    if (e != hipSuccess) { dev_free(mask_new); return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e)); }
+    // ---- from here on a failure leaves no geometry (as a failed gsr_move does), and no visibility
+    bool changed = false;
+    e = vis_apply(c, us, 0u, capture ? c->n : 0u, true, rule, mask_new, &changed);
+    // a change of the hidden set is a shape edit, like new alphas: horizons, prefixes, hints and policies of the cloud's frames go
+    if (e == hipSuccess && changed) e = after_update(c, true, us, e);
+    if (e != hipSuccess) {
+        dev_free(mask_new);
+        c->vis = GsrVisRule{}; c->vis_on = false;
+        drop_geometry(c);
+        return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e));
+    }
+    dev_free(c->vis_mask);
+    c->vis_mask = mask_new;
+    c->vis = rule;
+    c->vis_on = on;
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_visibility(gsr_context* c, gsr_visibility* out, int64_t* hidden)
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_visibility: ctx is NULL");
+    if (out) {
+        std::memset(out, 0, sizeof(*out));
+        std::memcpy(out, &c->vis, sizeof(GsrVisRule));
+        out->mask_splats = c->vis_mask ? (int64_t)c->n : 0;
+    }
+    if (hidden) *hidden = c->vis_hidden;
+    return GSR_OK;
 }

@@ -227,6 +227,39 @@ __host__ __device__ __forceinline__ float4 gsr_background_pixel(const void* __re
     return make_float4((float)(v & 0xffu) / 255.0f, (float)((v >> 8) & 0xffu) / 255.0f, (float)((v >> 16) & 0xffu) / 255.0f, (float)(v >> 24) / 255.0f);
 }
 
+// ---- visibility (gsplat_hip.h: gsr_set_visibility) -------------------------------
+// Is a splat at the upload-space position (x, y, z) -- the raw P bits, what geoA holds -- visible under up to four crop volumes and
+// its mask bit?  THE rule, in one place: k_visibility and gsr_visibility_eval (host) both go through it.  Per axis one chain of three
+// explicit FMAs, innermost first (the translation units are compiled with -ffp-contract=off, so neither side fuses or splits anything
+// else); the comparisons are written so that a NaN anywhere means "not inside".  GsrVisVolume is gsr_crop_volume's layout.
+#define GSR_VISK_BOX       1
+#define GSR_VISK_ELLIPSOID 2
+#define GSR_VIS_VOLUMES    4
+struct GsrVisVolume {
+    int32_t kind, invert;
+    float m[12];                       // rows of the 3x4 affine map: m[r*4+c]
+};
+struct GsrVisRule {
+    int32_t n_volumes, reserved_;
+    GsrVisVolume vol[GSR_VIS_VOLUMES];
+};
+__host__ __device__ __forceinline__ bool gsr_volume_inside(const GsrVisVolume& v, float x, float y, float z)
+{
+    const float qx = __builtin_fmaf(v.m[0], x, __builtin_fmaf(v.m[1], y, __builtin_fmaf(v.m[2], z, v.m[3])));
+    const float qy = __builtin_fmaf(v.m[4], x, __builtin_fmaf(v.m[5], y, __builtin_fmaf(v.m[6], z, v.m[7])));
+    const float qz = __builtin_fmaf(v.m[8], x, __builtin_fmaf(v.m[9], y, __builtin_fmaf(v.m[10], z, v.m[11])));
+    if (v.kind == GSR_VISK_BOX)        // max(|q.x|, |q.y|, |q.z|) <= 1, as three comparisons: fmaxf would drop a NaN operand
+        return __builtin_fabsf(qx) <= 1.0f && __builtin_fabsf(qy) <= 1.0f && __builtin_fabsf(qz) <= 1.0f;
+    return __builtin_fmaf(qx, qx, __builtin_fmaf(qy, qy, qz * qz)) <= 1.0f;
+}
+// every volume must pass (inside, or NOT inside for an inverted one); mask_word: the word of the splat's mask bit (0 without a mask)
+__host__ __device__ __forceinline__ bool gsr_splat_visible(const GsrVisRule& r, float x, float y, float z, uint32_t mask_word, uint32_t bit)
+{
+    bool vis = ((mask_word >> (bit & 31u)) & 1u) == 0u;
+    for (int k = 0; k < r.n_volumes; ++k) vis = vis && (gsr_volume_inside(r.vol[k], x, y, z) != (r.vol[k].invert != 0));
+    return vis;
+}
+
 // The contract's 2^x for x in [-2^22, 0]: identical operation sequence to the oracle's gso_exp2f
 // (round to the nearest-even integer with the 1.5*2^23 trick, EXACT remainder r = x - k, degree-5
 // polynomial for 2^r on [-0.5, 0.5], exponent add).  <= 2.8 ulp, exp2(0) == 1, never above 1.

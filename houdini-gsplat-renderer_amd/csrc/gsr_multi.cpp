@@ -619,6 +619,16 @@ extern "C" int gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const floa
     return for_each_rank(m, [=](int g) { return gsr_move(m->ctx[g], first, n, P, origin, u); });
 }
 
+// ... and hidden on every rank: each applies the rule to its own replica
+extern "C" int gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_set_visibility: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_set_visibility: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return for_each_rank(m, [=](int g) { return gsr_set_visibility(m->ctx[g], v); });
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

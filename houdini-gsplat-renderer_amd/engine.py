@@ -97,6 +97,17 @@ class gsr_device_attrs(C.Structure):
                 ("sh", C.c_void_p), ("sh_vec3_per_point", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_crop_volume(C.Structure):
+    """include/gsplat_hip.h: one crop volume -- a 3x4 affine map (rows) from upload space onto the unit box / unit ball"""
+    _fields_ = [("kind", C.c_int32), ("invert", C.c_int32), ("to_unit", C.c_float * 12)]
+
+
+class gsr_visibility(C.Structure):
+    """include/gsplat_hip.h: what gsr_set_visibility hides by -- up to four volumes (a splat must pass every one) and a HOST bit mask"""
+    _fields_ = [("n_volumes", C.c_int32), ("reserved_", C.c_int32), ("volume", gsr_crop_volume * 4),
+                ("mask", C.c_void_p), ("mask_splats", C.c_int64)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -125,6 +136,9 @@ TARGET_RGBA8 = 2
 AOV_DEPTH = 1          # gsr_render_aov: the plane {zsum, cov}, two float32 per pixel whatever the target format
 BG_COLOUR = 1          # gsr_background.kind
 BG_IMAGE = 2
+VIS_MAX_VOLUMES = 4    # GSR_VIS_MAX_VOLUMES
+VOL_BOX = 1            # gsr_crop_volume.kind: inside iff max(|q|) <= 1
+VOL_ELLIPSOID = 2      # ... iff |q|^2 <= 1
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -158,6 +172,7 @@ C_ABI_SYMBOLS = [
     "gsr_move", "gsr_multi_move", "gsplat_renderer_move_splats",
     "gsr_upload_append_device", "gsr_update_device", "gsr_move_device", "gsr_debug_check_device_source",
     "gsr_set_row_band", "gsr_read_row_work", "gsr_debug_balance_rows", "gsr_multi_get_bands",
+    "gsr_set_visibility", "gsr_get_visibility", "gsr_visibility_eval", "gsr_multi_set_visibility", "gsplat_renderer_set_visibility",
 ]
 
 
@@ -216,6 +231,11 @@ def load_library() -> C.CDLL:
     L.gsr_move_device.argtypes = [vp, i64, i64, f32p, C.POINTER(gsr_device_attrs)]
     L.gsr_debug_check_device_source.argtypes = [vp, vp, i64]
     L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
+    L.gsr_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
+    L.gsr_get_visibility.argtypes = [vp, C.POINTER(gsr_visibility), C.POINTER(C.c_int64)]
+    L.gsr_visibility_eval.argtypes = [C.POINTER(gsr_visibility), vp, i64, i64, vp]
+    L.gsr_multi_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
+    L.gsplat_renderer_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -432,6 +452,65 @@ def resolve_depth(aov: np.ndarray, cov_min: float = 0.5) -> np.ndarray:
     out = np.empty(a.shape[:-1], dtype=np.float32)
     _check(load_library().gsr_resolve_depth(a.ctypes.data, a.size // 2, float(cov_min), out.ctypes.data))
     return out
+
+
+def _crop_to_unit(centre, half_extents, rotation3x3):
+    """to_unit[12] (rows of a 3x4 map, float32) of a volume with the given centre, half extents and orientation (the columns of
+    rotation3x3 are the volume's axes in upload space; None = axis-aligned): q = diag(1 / h) R^T (P - centre), formed in float64 and
+    rounded once.  Dyadic extents and an axis-aligned volume give dyadic entries, so centre +- h lands on +-1 exactly."""
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    h = np.asarray(half_extents, dtype=np.float64).reshape(-1)
+    h = np.repeat(h, 3) if h.size == 1 else h.reshape(3)
+    R = np.eye(3) if rotation3x3 is None else np.asarray(rotation3x3, dtype=np.float64).reshape(3, 3)
+    A = R.T / h[:, None]
+    return np.concatenate([A, -(A @ c)[:, None]], axis=1).astype(np.float32).reshape(12)
+
+
+def crop_box(centre, half_extents, rotation3x3=None, invert: bool = False):
+    """a box volume (kind, invert, to_unit12) for visibility_struct: centre + R diag(half_extents) [-1, 1]^3"""
+    return (VOL_BOX, int(bool(invert)), _crop_to_unit(centre, half_extents, rotation3x3))
+
+
+def crop_ellipsoid(centre, half_extents, rotation3x3=None, invert: bool = False):
+    """an ellipsoid volume (kind, invert, to_unit12) for visibility_struct: semi-axes half_extents along the columns of rotation3x3"""
+    return (VOL_ELLIPSOID, int(bool(invert)), _crop_to_unit(centre, half_extents, rotation3x3))
+
+
+def pack_mask(hidden) -> np.ndarray:
+    """a boolean array (True = hidden, upload order) -> the uint32 words gsr_visibility.mask takes: bit (i & 31) of word (i >> 5)"""
+    h = np.asarray(hidden, dtype=bool).reshape(-1)
+    bits = np.zeros((h.size + 31) // 32 * 32, np.uint8)
+    bits[:h.size] = h
+    return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def visibility_struct(volumes=(), mask=None):
+    """gsr_visibility from volumes = [(kind, invert, to_unit12), ...] (crop_box / crop_ellipsoid build them) and mask = a boolean array,
+    True = hidden, one entry per resident splat in upload order (or None) -> (struct, the words it points into: keep them alive
+    during the call).  The counts and kinds are the library's to refuse."""
+    v, keep = gsr_visibility(), None
+    volumes = list(volumes)
+    v.n_volumes = len(volumes)
+    for k, (kind, invert, to_unit) in enumerate(volumes[:VIS_MAX_VOLUMES]):
+        v.volume[k].kind, v.volume[k].invert = int(kind), int(invert)
+        v.volume[k].to_unit[:] = np.asarray(to_unit, dtype=np.float32).reshape(12).tolist()
+    if mask is not None:
+        m = np.asarray(mask).reshape(-1)
+        keep = pack_mask(m)
+        if keep.size == 0:
+            keep = np.zeros(1, np.uint32)
+        v.mask, v.mask_splats = keep.ctypes.data, m.size
+    return v, keep
+
+
+def visibility_eval(vis, P, first: int = 0) -> np.ndarray:
+    """gsr_visibility_eval: the rule of gsr_set_visibility on the host, through the function the kernel evaluates.  vis: a gsr_visibility
+    (visibility_struct) or None; P: float32 (n, 3) = the splats [first, first + n) as far as a mask is concerned -> bool (n,), True = visible"""
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros(P.shape[0], np.uint8)
+    _check(load_library().gsr_visibility_eval(C.byref(vis) if vis is not None else None, P.ctypes.data if P.size else None, int(first),
+                                              P.shape[0], out.ctypes.data if P.size else None))
+    return out.astype(bool)
 
 
 def camera_struct(cam) -> gsr_camera:
@@ -674,6 +753,21 @@ class Engine:
         if rc not in (0, -1):
             _check(rc)
         return rc == 0
+
+    def set_visibility(self, vis=None, volumes=None, mask=None):
+        """gsr_set_visibility: hide the resident splats that fail the volumes or whose mask entry is True, with no re-upload.  Either a
+        gsr_visibility (its mask words must stay alive during the call), or volumes / mask as visibility_struct takes them; nothing
+        given = everything visible again.  Volumes persist across updates, moves and uploads; the mask is dropped by an upload."""
+        keep = None
+        if vis is None and (volumes is not None or mask is not None):
+            vis, keep = visibility_struct(volumes or (), mask)
+        _check(self.L.gsr_set_visibility(self.h, C.byref(vis) if vis is not None else None))
+
+    def get_visibility(self):
+        """gsr_get_visibility -> (the gsr_visibility in force, mask pointer always NULL; how many splats the last application hid)"""
+        v, hidden = gsr_visibility(), C.c_int64(0)
+        _check(self.L.gsr_get_visibility(self.h, C.byref(v), C.byref(hidden)))
+        return v, hidden.value
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
@@ -1092,6 +1186,11 @@ class GSplatRenderer:
         None or kind 0 clears it.  0 or a GSR_E_* code"""
         return int(self.L.gsplat_renderer_set_background(self.h, C.byref(bg) if bg is not None else None))
 
+    def setVisibility(self, vis: gsr_visibility | None) -> int:
+        """crop volumes (visibility_struct; no mask: the shim refuses one) that hide resident splats from the next render() on and
+        through every re-stage; None or no volume clears them.  0 or a GSR_E_* code"""
+        return int(self.L.gsplat_renderer_set_visibility(self.h, C.byref(vis) if vis is not None else None))
+
     def query(self, what: int, rid: str | None = None) -> int:
         return int(self.L.gsplat_renderer_query(self.h, what, rid.encode() if rid else None))
 
@@ -1184,6 +1283,13 @@ class MultiEngine:
         P, n, u, keep = move_arrays(P, **attrs)
         _check(self.L.gsr_multi_move(self.h, int(first), n, P.ctypes.data, None if origin is None else _f3(origin), C.byref(u)))
         return n
+
+    def set_visibility(self, vis=None, volumes=None, mask=None):
+        """gsr_multi_set_visibility: Engine.set_visibility on every rank"""
+        keep = None
+        if vis is None and (volumes is not None or mask is not None):
+            vis, keep = visibility_struct(volumes or (), mask)
+        _check(self.L.gsr_multi_set_visibility(self.h, C.byref(vis) if vis is not None else None))
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

@@ -104,6 +104,11 @@ public:
      * format, a NULL image, a multi-GPU instance (gsr_multi_* takes no background), or while an AOV target is set (there is no AOV +
      * background verb; setAovTarget refuses likewise while a background is set).  A dry instance remembers it. */
     int setBackground(const gsr_background* bg);
+    /* visibility (gsplat_hip.h: gsr_set_visibility): crop volumes in upload space that hide the resident splats failing them, from the
+     * next render() on, until cleared with NULL or n_volumes 0.  The engine keeps volumes across uploads, so every re-stage is cropped
+     * too.  Volumes only: a mask belongs to one upload and every re-stage would lose it -- GSR_E_INVALID for v->mask != NULL, as for
+     * whatever gsr_set_visibility refuses of the volumes.  A dry instance checks the struct and does nothing else. */
+    int setVisibility(const gsr_visibility* v);
 
     /* New attribute arrays (registerUpdate() layout, BORROWED like the ones they replace; NULL = that attribute stays) for a registered
      * primitive whose positions did not change -- no reference counterpart; GR_Primitive::update would call it when the update reason
@@ -244,6 +249,7 @@ void gsplat_renderer_set_spherical_harmonics_order(gsplat_renderer* h, int order
 int  gsplat_renderer_set_target_format(gsplat_renderer* h, int format);   /* GSplatRenderer::setTargetFormat */
 int  gsplat_renderer_set_aov_target(gsplat_renderer* h, int aov, float* plane);   /* GSplatRenderer::setAovTarget */
 int  gsplat_renderer_set_background(gsplat_renderer* h, const gsr_background* bg);   /* GSplatRenderer::setBackground */
+int  gsplat_renderer_set_visibility(gsplat_renderer* h, const gsr_visibility* v);   /* GSplatRenderer::setVisibility */
 /* GSplatRenderer::updateAttributes; gsplat_renderer_row_array below is the debug door GSplatRenderer::rowArray (tests only) */
 int  gsplat_renderer_update_attributes(gsplat_renderer* h, const char* id, const uint16_t* Cd, const float* alpha,
                                        const uint16_t* scale, const uint16_t* orient,

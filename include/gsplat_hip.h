@@ -297,6 +297,62 @@ int  gsr_update_device(gsr_context* ctx, int64_t first, int64_t n, const gsr_dev
 int  gsr_move_device(gsr_context* ctx, int64_t first, int64_t n, const float origin[3], const gsr_device_attrs* a);
 int  gsr_debug_check_device_source(gsr_context* ctx, const void* p, int64_t bytes);
 
+/* ---- visibility (resident splats hidden by crop volumes or a mask, without a re-upload) ---------------------------------------- */
+/* Isolating an object, cutting floaters away with a box, hiding a group: the resident splats that fail the rule below get the
+ * resident opacity +0.0f -- K1 drops such a splat before its covariance chain and the fragment test discards on the same value, so it
+ * contributes nothing, exactly -- and the others keep their own alpha.  Nothing but the struct (and a mask's n / 8 bytes) crosses the
+ * link; one streaming kernel evaluates the volumes on the GPU and rewrites the opacities that change.  No frame kernel knows about it,
+ * and a context that never calls gsr_set_visibility runs exactly the launches it ran before.
+ * THE RULE.  With (x, y, z) = the raw P bits of splat i as uploaded (upload space: before the GSplatOrigin round trip and the object
+ * matrix) and m = to_unit of a volume, per axis r
+ *     q.r = fmaf(m[4r], x, fmaf(m[4r+1], y, fmaf(m[4r+2], z, m[4r+3])))          (float32, exactly these three fused operations)
+ * the splat is INSIDE the volume iff the comparison beside its kind holds (a NaN anywhere: not inside), it PASSES the volume iff
+ * inside != invert, and it is VISIBLE iff it passes every volume and its mask bit is clear.  gsr_visibility_eval is this rule on the
+ * host (no context, no GPU), through the very function the kernel evaluates: rows [0, n) of P are the splats [first, first + n) as far
+ * as the mask is concerned; visible_out[k] = 1 / 0.
+ * THE EFFECT, while a visibility is in force: the resident opacity of a hidden splat is +0.0f, that of a visible one its own alpha bit
+ * for bit (alphas below 1/255, NaN and -0 included).
+ * CONTRACT: after GSR_OK the resident geometry -- geoA, geoB, every colour chunk, the colour rows, the cluster bounds and the storage
+ * order -- is bit for bit what a fresh context holds after gsr_upload of the same arrays with alpha[i] replaced by
+ * visible(i) ? alpha[i] : +0.0f (same options, origin and SH presence), and so is every later frame, in every option mode, target
+ * format, frame verb and band.  NULL, or no volume and no mask, makes everything visible again: the planes of a plain upload, exactly.
+ * PERSISTENCE.  The volumes stay in force across gsr_update*, gsr_move* and complete uploads: an alpha update of a hidden splat is
+ * remembered and shows when the splat becomes visible, a move evaluates the volumes at the new positions, gsr_upload_end applies them
+ * to the new cloud.  The mask belongs to a cloud: it is copied when the call is made, kept by updates and moves, and dropped by every
+ * complete upload.  Volumes without a mask may be set before any upload.
+ * Synchronous like gsr_update: it first waits for every frame of the context that is still in flight.  What the frames of the cloud
+ * may keep afterwards is decided as for an alpha update (horizons, hints and policies go) -- unless no resident bit changed.
+ * MEMORY: from the first call the context keeps the true alphas aside, one float per splat of capacity (4 bytes: 24 MB at 6 M
+ * splats), and with a mask ceil(n / 32) words, until the capacity changes or the context is destroyed.
+ * GSR_E_INVALID, with the context untouched: NULL ctx; n_volumes outside 0..GSR_VIS_MAX_VOLUMES; an unknown kind; invert not 0 or 1;
+ * reserved_ not 0; a mask with no geometry resident or with mask_splats != the resident count; an upload in progress.  Non-finite
+ * matrix entries are the caller's data and follow the rule.  Everything is allocated before the first write: GSR_E_OOM leaves the
+ * resident geometry and the visibility in force untouched (a buffer the call had already allocated by then stays with the context and
+ * is used by the next call).  A HIP failure after the first write leaves NO geometry, as gsr_move documents, and no visibility.
+ * gsr_get_visibility: the volumes in force (out->mask is always NULL; mask_splats = the splats a mask in force covers, else 0) and
+ * how many resident splats the last application hid; either pointer may be NULL.
+ * Out of scope: skipping wholly hidden clusters in k_cluster_cull (K1 still loads the 16 bytes of every hidden splat); the wire
+ * overlay, which outlines every resident splat as before; a mask in device memory; a mask through the GSplatRenderer shim or the HDK
+ * glue; gsr_comm_* (each rank is a plain context and sets its own visibility); picking. */
+#define GSR_VIS_MAX_VOLUMES 4
+#define GSR_VOL_BOX         1   /* inside iff max(|q.x|, |q.y|, |q.z|) <= 1 */
+#define GSR_VOL_ELLIPSOID   2   /* inside iff fmaf(q.x, q.x, fmaf(q.y, q.y, q.z * q.z)) <= 1 */
+typedef struct gsr_crop_volume {
+    int32_t kind;          /* GSR_VOL_* */
+    int32_t invert;        /* 0: the splat passes iff inside; 1: iff NOT inside */
+    float   to_unit[12];   /* rows of a 3x4 affine map, to_unit[r*4+c]: upload-space P -> the unit volume */
+} gsr_crop_volume;
+typedef struct gsr_visibility {
+    int32_t n_volumes;     /* 0..GSR_VIS_MAX_VOLUMES; a splat must pass EVERY volume */
+    int32_t reserved_;     /* 0 */
+    gsr_crop_volume volume[GSR_VIS_MAX_VOLUMES];
+    const uint32_t* mask;  /* HOST pointer or NULL: bit (i & 31) of word (i >> 5) set = splat i (UPLOAD order) is hidden */
+    int64_t mask_splats;   /* must equal the resident count when mask is given */
+} gsr_visibility;
+int  gsr_set_visibility(gsr_context* ctx, const gsr_visibility* v);   /* NULL, or no volume and no mask: everything visible again */
+int  gsr_get_visibility(gsr_context* ctx, gsr_visibility* out, int64_t* hidden);  /* out->mask is always NULL; either may be NULL */
+int  gsr_visibility_eval(const gsr_visibility* v, const float* P, int64_t first, int64_t n, uint8_t* visible_out); /* host, no context, no GPU */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -395,6 +451,8 @@ int  gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const uint16_t* C
 int  gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_update* u);
 /* gsr_move on every rank, after the same synchronisation (every rank then keeps its own second copy of the planes) */
 int  gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
+/* gsr_set_visibility on every rank, after the same synchronisation (every rank keeps its own copy of the alphas and of a mask) */
+int  gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
