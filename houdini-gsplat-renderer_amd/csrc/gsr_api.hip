@@ -43,6 +43,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "gsr_frame_plan.h"
 #include "gsr_host_buffers.h"
 #include "k_visibility.h"   // (last: the kernels of the frame keep their places in the code object)
+#include "k_remove.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -356,6 +357,12 @@ struct gsr_context {
     unsigned long long* vis_counters = nullptr;   // k_visibility's counter slots ...
     unsigned long long* vis_h_counters = nullptr; // ... and where they are read back: pinned host memory, like the slots' read-backs
     int64_t vis_hidden = 0;            // what the last application hid
+    // gsr_remove (k_remove.h): the SECOND array of true alphas the compaction writes (swapped with alpha0 like the planes; only with a
+    // visibility in force), the pinned words the survivor count arrives in, and what gsr_get_removal reports
+    float* alpha0_2 = nullptr;
+    uint32_t* rm_h_total = nullptr;
+    int64_t rm_calls = 0, rm_last = 0;
+    double rm_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -563,6 +570,7 @@ static void free_geometry(gsr_context* c)
     dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->nclus = 0; c->h_perm.clear();
     dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(c->clusA2); dev_free(c->clusB2);
     dev_free(c->alpha0);               // (sized by the capacity; the volumes stay in force, the next complete upload captures again)
+    dev_free(c->alpha0_2);
     vis_drop_mask(c);
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_free_splat_arrays(c->slot[k]);
     c->cap = 0; c->n = 0;
@@ -583,6 +591,7 @@ extern "C" void gsr_destroy(gsr_context* c)
     dev_free(c->prefix); dev_free(c->prefix_all); dev_free(c->prefix_none); dev_free(c->lazy_hint);
     dev_free(c->pos_order); dev_free(c->blk_pre); dev_free(c->vis_counters);
     if (c->vis_h_counters) (void)hipHostFree(c->vis_h_counters);
+    if (c->rm_h_total) (void)hipHostFree(c->rm_h_total);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
@@ -1351,6 +1360,59 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
 }
 
 // ---------------------------------------------------------------------------
+// What gsr_move and gsr_remove share around k_repack.  The SPARE copy of the planes (at the capacity) and of the cluster bounds (at the
+// cluster count in force: a removal only ever needs fewer): allocated at the first call that writes a new storage order, kept until the
+// geometry is freed.  A failure leaves no half of a set behind.
+static int ensure_spare_planes(gsr_context* c)
+{
+    int rc = GSR_OK;
+    const size_t cap = c->cap;
+    if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
+                      (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
+        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+        return rc;
+    }
+    if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
+        dev_free(c->clusA2); dev_free(c->clusB2);
+        return rc;
+    }
+    return GSR_OK;
+}
+// The sort of a new storage order over n splats, provided for before the first write: the Morton scratch, slot 0's histogram, and the
+// new permutation (*perm_new: the caller's, freed by it on every later failure)
+static int ensure_order_buffers(gsr_context* c, uint32_t n, uint32_t** perm_new, const char* who)
+{
+    FrameSlot& sl = c->slot[0];
+    int rc = GSR_OK;
+    if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
+    if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+    return dev_alloc(perm_new, (size_t)n);
+}
+// k_repack on `us`: the n splats of the new order perm_new (NULL: upload order) from the slots old_slot names (upload index -> resident
+// slot; NULL: upload order) into the spare planes, with the bounds of their clusters
+static hipError_t queue_repack(gsr_context* c, hipStream_t us, uint32_t n, const uint32_t* perm_new, const uint32_t* old_slot)
+{
+    const dim3 grid(div_up(n, GSR_CLUSTER)), block(GSR_PACK_THREADS);
+    if (c->has_sh)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), grid, block, 0, us, n, c->cap, perm_new, old_slot, c->geoA, c->geoB, c->col, c->colrow,
+                           c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), grid, block, 0, us, n, c->cap, perm_new, old_slot, c->geoA, c->geoB, c->col, c->colrow,
+                           c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+    return hipGetLastError();
+}
+// ... and the swap behind it: the spare set becomes the resident one, under the storage order perm_new (taken over; NULL: upload order).
+// Nothing is in flight, and every frame takes the planes from the context.
+static void swap_planes(gsr_context* c, uint32_t*& perm_new)
+{
+    std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
+    std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
+    dev_free(c->perm);
+    c->perm = perm_new;
+    perm_new = nullptr;
+}
+
+// ---------------------------------------------------------------------------
 // The body of gsr_move and gsr_move_device, behind their refusals.  new_bytes: what the new rows take at the head of the arena (0: they
 // stay in the caller's device memory); upd_bytes: what the attribute step stages there; attr_step(): the update verb for the same rows
 // (attrs: whether there is one; it leaves its link time in upload_ms[4]); new_rows(arena, stream, &Pnew, &h2d_ms): the device pointer
@@ -1380,23 +1442,8 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     }
     uint32_t* perm_new = nullptr;
     if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
-    if (may_order) {
-        if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
-        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
-        if ((rc = dev_alloc(&perm_new, (size_t)n))) return rc;
-    }
-    if (may_order || c->perm) {
-        const size_t cap = c->cap;
-        if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
-                          (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
-            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(perm_new);
-            return rc;
-        }
-        if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
-            dev_free(c->clusA2); dev_free(c->clusB2); dev_free(perm_new);
-            return rc;
-        }
-    }
+    if (may_order && (rc = ensure_order_buffers(c, n, &perm_new, who))) return rc;
+    if ((may_order || c->perm) && (rc = ensure_spare_planes(c))) { dev_free(perm_new); return rc; }
     if ((rc = ensure_inverse_perm(c))) { dev_free(perm_new); return rc; }      // (the OLD order's inverse; built on slot 0's own stream)
     for (int k = 0; k < 3; ++k)
         if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "%s: no event", who); }
@@ -1434,28 +1481,17 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
     if (e == hipSuccess) {
         if (perm_new || c->perm) {
-            if (c->has_sh)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
-                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, inv_old, c->geoA, c->geoB, c->col, c->colrow,
-                                   c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+            e = queue_repack(c, us, n, perm_new, inv_old);
         } else {
             hipLaunchKernelGGL(k_cluster_bounds, dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->geoA, c->geoB, c->clusA, c->clusB);
+            e = hipGetLastError();
         }
-        e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);
     if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
     // 5. the swap: nothing is in flight, and every frame takes the planes from the context
-    if (perm_new || c->perm) {
-        std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
-        std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
-        dev_free(c->perm);
-        c->perm = perm_new;
-        perm_new = nullptr;
-    }
+    if (perm_new || c->perm) swap_planes(c, perm_new);
     c->h_perm.clear();
     if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
     // 6. a visibility in force: the volumes against the positions the splats have now, in the order they sit in now
@@ -3821,5 +3857,185 @@ extern "C" int gsr_get_visibility(gsr_context* c, gsr_visibility* out, int64_t* 
         out->mask_splats = c->vis_mask ? (int64_t)c->n : 0;
     }
     if (hidden) *hidden = c->vis_hidden;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Removal (k_remove.h): resident splats deleted on the GPU.  A move whose source is a subset: mark, scan and compact in
+// upload order, then the ordering of an upload over the survivors' positions, k_repack into the spare planes, the swap.
+extern "C" int gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_index, int64_t* n_left)
+{
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && !mask)) return set_err(GSR_E_INVALID, "gsr_remove_map: bad argument");
+    int64_t left = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const bool gone = ((mask[i >> 5] >> (i & 31)) & 1u) != 0u;
+        if (new_index) new_index[i] = gone ? -1 : (int32_t)left;
+        if (!gone) ++left;
+    }
+    if (n_left) *n_left = left;
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_removal(gsr_context* c, int64_t* removals, int64_t* removed_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_removal: ctx is NULL");
+    if (removals) *removals = c->rm_calls;
+    if (removed_last) *removed_last = c->rm_last;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->rm_ms[k];
+    return GSR_OK;
+}
+
+// gsr_multi_remove: ranks that disagree keep nothing
+__attribute__((visibility("hidden"))) void gsr_internal_drop_geometry(gsr_context* c) { if (c) drop_geometry(c); }
+
+extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_device, int flags, int64_t* n_left)
+{
+    const char* const who = "gsr_remove";
+    if (!c) return set_err(GSR_E_INVALID, "gsr_remove: ctx is NULL");
+    if (flags & ~GSR_REMOVE_HIDDEN) return set_err(GSR_E_INVALID, "gsr_remove: unknown flag bits %#x", flags & ~GSR_REMOVE_HIDDEN);
+    if (!mask && !(flags & GSR_REMOVE_HIDDEN)) return set_err(GSR_E_INVALID, "gsr_remove: mask is NULL and GSR_REMOVE_HIDDEN is not set");
+    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_remove: upload in progress");
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_remove: no geometry: nothing uploaded");
+    const uint32_t n = c->n;
+    const size_t words = ((size_t)n + 31) / 32;
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = GSR_OK;
+    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    const double t_begin = up_now_ms();
+    if ((rc = sync_all(c))) return rc;   // the public stream (a producer of a device mask queued there has finished), and no write under a frame in flight
+    const bool hidden = (flags & GSR_REMOVE_HIDDEN) && c->vis_on;
+    if (n == 0 || (!mask && !hidden)) {                // nothing can go
+        if (n_left) *n_left = (int64_t)n;
+        return GSR_OK;
+    }
+    FrameSlot& sl = c->slot[0];
+    hipStream_t us = sl.stream;
+    // ---- the scratch of mark, scan and compaction, in the staging arena (kept between uploads and edits; grown only when too small)
+    const uint32_t nblocks = div_up(n, (uint32_t)GSR_REMOVE_BLOCK);
+    const size_t al = 256;
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t at = off; off += (bytes + al - 1) / al * al; return at; };
+    const size_t oMask = place(mask && !mask_is_device ? words * 4 : 0), oKeep = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8), oCnt = place((size_t)nblocks * 4),
+                 oOff = place(((size_t)nblocks + 1) * 4), oP = place((size_t)n * 12), oSlot = place((size_t)n * 4);
+    if (off > c->stage_cap) {
+        dev_free(c->stage);
+        c->stage_cap = 0;
+        if ((rc = dev_alloc(&c->stage, off + 256))) return rc;
+        c->stage_cap = off + 256;
+    }
+    if (!c->rm_h_total && hipHostMalloc(reinterpret_cast<void**>(&c->rm_h_total), 2 * sizeof(uint32_t), 0) != hipSuccess) {
+        c->rm_h_total = nullptr;
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "gsr_remove: no pinned host memory for the survivor count");
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
+    if ((rc = ensure_inverse_perm(c))) return rc;      // (the OLD order's inverse; built on slot 0's own stream)
+    HIP_TRY(hipStreamSynchronize(sl.own));
+    unsigned long long* const keep = reinterpret_cast<unsigned long long*>(c->stage + oKeep);
+    uint32_t* const counts = reinterpret_cast<uint32_t*>(c->stage + oCnt);
+    uint32_t* const offsets = reinterpret_cast<uint32_t*>(c->stage + oOff);
+    float* const Pup = reinterpret_cast<float*>(c->stage + oP);
+    uint32_t* const src_slot = reinterpret_cast<uint32_t*>(c->stage + oSlot);
+    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    // ---- 1, 2. which splats stay, and how many: nothing resident is written yet
+    const uint32_t* dmask = mask;
+    double h2d_ms = 0.0;
+    if (mask && !mask_is_device) {
+        const double t0 = up_now_ms();
+        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
+        HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
+        HIP_TRY(hipStreamSynchronize(us));             // the caller's mask may be freed on return
+        h2d_ms = up_now_ms() - t0;
+        dmask = staged;
+    }
+    HIP_TRY(hipEventRecord(c->up_ev[0], us));
+    if (hidden)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<true>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, c->vis_mask, c->vis, keep, counts);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<false>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, (const uint32_t*)nullptr, GsrVisRule{}, keep, counts);
+    hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, counts, offsets);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->rm_h_total, offsets + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us));
+    HIP_TRY(hipStreamSynchronize(us));
+    const uint32_t n1 = c->rm_h_total[0];
+    if (n1 > n) return set_err(GSR_E_HIP, "gsr_remove: the scan counted %u survivors of %u splats", n1, n);
+    if (n1 == n) {                                     // nothing goes: no resident bit changes, nothing is invalidated
+        if (n_left) *n_left = (int64_t)n;
+        return GSR_OK;
+    }
+    // ---- everything the rest needs, before the first write to resident memory or to the visibility's state
+    const bool may_order = c->opt_morton && n1 > 1;
+    const bool vis = c->vis_on;
+    uint32_t *perm_new = nullptr, *mask_new = nullptr;
+    if (n1 > 0) {
+        if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
+        if (may_order && (rc = ensure_order_buffers(c, n1, &perm_new, who))) return rc;
+        if ((rc = ensure_spare_planes(c))) { dev_free(perm_new); return rc; }
+        if (vis) {
+            if (!(rc = vis_ensure_buffers(c)) && !c->alpha0_2) rc = dev_alloc(&c->alpha0_2, (size_t)c->cap);
+            if (!rc && c->vis_mask) rc = dev_alloc(&mask_new, words);
+            if (rc) { dev_free(perm_new); dev_free(mask_new); return rc; }
+        }
+    }
+    // ---- from here on a failure leaves no geometry (as a failed gsr_move does)
+    auto lost = [&](int code) { dev_free(perm_new); dev_free(mask_new); drop_geometry(c); return code; };
+    hipError_t e = hipSuccess;
+    if (n1 == 0) {
+        // the empty cloud, as gsr_upload of 0 splats leaves it: no order, no clusters, no mask
+        dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); dev_free(c->clusA2); dev_free(c->clusB2);
+        c->n = 0; c->nclus = 0; c->h_perm.clear(); c->bbox_ok = false; c->up_total = c->up_filled = 0;
+        vis_drop_mask(c);
+        c->vis_hidden = 0;
+        e = hipEventRecord(c->up_ev[1], us);
+        if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+        if (e == hipSuccess) e = hipStreamSynchronize(us);
+        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    } else {
+        // 3. the survivors' positions, old slots, true alphas and mask bits at their new upload indices
+        if (mask_new) e = hipMemsetAsync(mask_new, 0, words * 4, us);
+        if (e == hipSuccess) {
+            if (vis)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_compact<true>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, keep, offsets, inv_old, c->geoA, Pup, src_slot,
+                                   c->alpha0, c->alpha0_2, c->vis_mask, mask_new);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_compact<false>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, keep, offsets, inv_old, c->geoA, Pup, src_slot,
+                                   (const float*)nullptr, (float*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+        // 4. the ordering of an upload over the survivors, and their planes into the spare set: k_repack as a move runs it, with the
+        // survivors' old slots in the place of the old order's inverse
+        if ((rc = position_box(c, Pup, n1, us, who))) return lost(rc);
+        const bool ordered = may_order && c->bbox_ok;
+        if (ordered && (rc = morton_order(c, Pup, n1, perm_new, who))) return lost(rc);
+        if (!ordered) dev_free(perm_new);
+        e = hipEventRecord(c->up_ev[1], us);
+        if (e == hipSuccess) e = queue_repack(c, us, n1, perm_new, src_slot);
+        if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+        if (e == hipSuccess) e = hipStreamSynchronize(us);
+        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+        // 5. the swap, and the upload-ordered state of the visibility with it
+        swap_planes(c, perm_new);
+        c->h_perm.clear();
+        c->n = n1; c->nclus = div_up(n1, GSR_CLUSTER); c->up_total = c->up_filled = n1;
+        if (vis) {
+            std::swap(c->alpha0, c->alpha0_2);
+            if (c->vis_mask) { dev_free(c->vis_mask); c->vis_mask = mask_new; mask_new = nullptr; }
+            // 6. the volumes against the survivors, in the order they sit in now (as a move's step 6)
+            if ((e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess)
+                return lost(set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e)));
+        }
+    }
+    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }
+    c->st.n_splats = c->n;
+    c->rm_calls += 1;
+    c->rm_last = (int64_t)n - (int64_t)n1;
+    float ms = 0.0f;
+    c->rm_ms[0] = h2d_ms;
+    c->rm_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? ms : 0.0;
+    c->rm_ms[2] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? ms : 0.0;
+    c->rm_ms[3] = up_now_ms() - t_begin;
+    if (n_left) *n_left = (int64_t)n1;
     return GSR_OK;
 }

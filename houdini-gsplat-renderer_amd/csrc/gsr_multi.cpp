@@ -59,6 +59,7 @@ int gsr_internal_shard_layout(gsr_context* c);
 int gsr_internal_set_error(int code, const char* text);
 int gsr_internal_stitch(gsr_context* c, const float* gathered, int count, int width, int height, float* out, void* stream);
 int gsr_internal_peek_row_work(gsr_context* c, uint32_t* out, int n_rows, int64_t* frame_out);
+void gsr_internal_drop_geometry(gsr_context* c);
 
 namespace {
 
@@ -627,6 +628,31 @@ extern "C" int gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v)
     int rc = gsr_multi_synchronize(m);
     if (rc) return rc;
     return for_each_rank(m, [=](int g) { return gsr_set_visibility(m->ctx[g], v); });
+}
+
+// ... and removed on every rank: each compacts, orders and repacks its own replica.  The replicas must stay replicas: ranks that do
+// not agree on the splats left (or of which one failed behind its first write, and so holds nothing) all give their geometry up.
+// Balanced bands: as after an upload, the boundaries stay, and the next evaluation reads the row sums of the survivors' frames.
+extern "C" int gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int flags, int64_t* n_left)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_remove: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_remove: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> left((size_t)G, -1);
+    int64_t* const lp = left.data();
+    rc = for_each_rank(m, [=](int g) { return gsr_remove(m->ctx[g], mask_host, 0, flags, lp + g); });
+    bool any_done = false, same = rc == GSR_OK;
+    for (int g = 0; g < G; ++g) any_done = any_done || left[(size_t)g] >= 0;
+    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
+    for (int g = 1; g < G && same; ++g) same = left[(size_t)g] == left[0];
+    if (!same) {
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_remove: the ranks do not agree on the splats left: the geometry is dropped on all of them");
+    }
+    if (n_left) *n_left = left[0];
+    return GSR_OK;
 }
 
 // ---- balanced bands ------------------------------------------------------------------------------

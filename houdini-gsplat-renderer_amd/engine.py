@@ -139,6 +139,8 @@ BG_IMAGE = 2
 VIS_MAX_VOLUMES = 4    # GSR_VIS_MAX_VOLUMES
 VOL_BOX = 1            # gsr_crop_volume.kind: inside iff max(|q|) <= 1
 VOL_ELLIPSOID = 2      # ... iff |q|^2 <= 1
+REMOVE_HIDDEN = 1      # GSR_REMOVE_HIDDEN: gsr_remove also removes what the visibility in force hides
+REMOVE_BLOCK = 4096    # GSR_REMOVE_BLOCK: upload indices one workgroup of the compaction kernels spans
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -173,6 +175,7 @@ C_ABI_SYMBOLS = [
     "gsr_upload_append_device", "gsr_update_device", "gsr_move_device", "gsr_debug_check_device_source",
     "gsr_set_row_band", "gsr_read_row_work", "gsr_debug_balance_rows", "gsr_multi_get_bands",
     "gsr_set_visibility", "gsr_get_visibility", "gsr_visibility_eval", "gsr_multi_set_visibility", "gsplat_renderer_set_visibility",
+    "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
 ]
 
 
@@ -236,6 +239,10 @@ def load_library() -> C.CDLL:
     L.gsr_visibility_eval.argtypes = [C.POINTER(gsr_visibility), vp, i64, i64, vp]
     L.gsr_multi_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
     L.gsplat_renderer_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
+    L.gsr_remove.argtypes = [vp, vp, i32, i32, C.POINTER(C.c_int64)]
+    L.gsr_remove_map.argtypes = [vp, i64, vp, C.POINTER(C.c_int64)]
+    L.gsr_get_removal.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_remove.argtypes = [vp, vp, i32, C.POINTER(C.c_int64)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -513,6 +520,49 @@ def visibility_eval(vis, P, first: int = 0) -> np.ndarray:
     return out.astype(bool)
 
 
+def removal_mask(mask) -> np.ndarray:
+    """what gsr_remove takes from a caller's mask: a boolean array (True = the splat goes, upload order) is packed with pack_mask; an
+    array of uint32 is taken as the packed words it already is.  Never empty (a cloud of no splats still hands a word over)."""
+    m = np.asarray(mask)
+    if m.dtype == np.uint32:
+        words = np.ascontiguousarray(m).reshape(-1)
+    elif m.dtype == np.bool_:
+        words = pack_mask(m)
+    else:
+        raise GsrError(-1, f"remove: the mask is {m.dtype}, neither bool (one entry per splat) nor uint32 (packed words)")
+    return words if words.size else np.zeros(1, np.uint32)
+
+
+def removal_words(mask, n: int):
+    """removal_mask for a cloud of n resident splats: a boolean mask must hold n entries and packed words must cover n bits -- the
+    library reads ceil(n / 32) words and cannot know how many the caller has"""
+    m = None if mask is None else np.asarray(mask)
+    if m is None:
+        return None
+    if m.dtype == np.bool_ and m.size != int(n):
+        raise GsrError(-1, f"remove: the mask holds {m.size} entries, {int(n)} splats are resident")
+    words = removal_mask(m)
+    if words.size * 32 < int(n):
+        raise GsrError(-1, f"remove: {words.size} mask words do not cover the {int(n)} resident splats")
+    return words
+
+
+def remove_map(mask, n=None):
+    """gsr_remove_map (host only, no GPU): where gsr_remove puts the survivors.  mask as removal_mask takes it; n = the splat count
+    (from a boolean mask's length when None) -> (int32 new_index[n]: the new upload index, -1 for a removed splat; the splats left)"""
+    m = np.asarray(mask)
+    if n is None:
+        if m.dtype != np.bool_:
+            raise GsrError(-1, "remove_map: packed words do not say how many splats they cover: n must be given")
+        n = m.size
+    words = removal_mask(m)
+    if words.size * 32 < int(n):
+        raise GsrError(-1, f"remove_map: {words.size} words do not cover {int(n)} splats")
+    out, left = np.zeros(max(int(n), 0), np.int32), C.c_int64(0)
+    _check(load_library().gsr_remove_map(words.ctypes.data, int(n), out.ctypes.data if out.size else None, C.byref(left)))
+    return out, left.value
+
+
 def camera_struct(cam) -> gsr_camera:
     s = gsr_camera()
     for name in ("obj_view", "object", "inv_object", "view", "proj"):
@@ -768,6 +818,41 @@ class Engine:
         v, hidden = gsr_visibility(), C.c_int64(0)
         _check(self.L.gsr_get_visibility(self.h, C.byref(v), C.byref(hidden)))
         return v, hidden.value
+
+    def remove(self, mask=None, hidden: bool = False) -> int:
+        """gsr_remove: the resident splats whose mask entry is True (a boolean array over the resident splats in upload order, or the
+        packed uint32 words) leave the cloud, compacted and re-ordered on the GPU with no re-upload; hidden = also everything the
+        visibility in force hides (mask may then be None).  The survivors keep their relative upload order (remove_map) -> the splats
+        left.  The context keeps a second copy of the resident planes from the first removal on (include/gsplat_hip.h)."""
+        words = removal_words(mask, self.stats()["n_splats"])
+        left = C.c_int64(0)
+        _check(self.L.gsr_remove(self.h, None if words is None else words.ctypes.data, 0, REMOVE_HIDDEN if hidden else 0, C.byref(left)))
+        return left.value
+
+    def remove_device(self, mask, hidden: bool = False) -> int:
+        """gsr_remove from packed uint32 mask words in DEVICE memory: an int (a device pointer) or an object with data_ptr() (a torch
+        tensor of 32-bit integers, contiguous, on the context's GPU), ceil(n / 32) words.  Waits for the work queued on the stream
+        given to set_stream first -> the splats left"""
+        if isinstance(mask, (int, np.integer)):
+            ptr = int(mask)
+        elif hasattr(mask, "data_ptr"):
+            if not str(mask.dtype).endswith(("int32", "uint32")):
+                raise GsrError(-1, f"remove_device: the mask is {mask.dtype}, not packed 32-bit words")
+            if not mask.is_contiguous() or not getattr(mask, "is_cuda", False):
+                raise GsrError(-1, "remove_device: the mask is not a contiguous tensor on a GPU")
+            ptr = int(mask.data_ptr())
+        else:
+            raise GsrError(-1, "remove_device: the mask is neither a device pointer (int) nor an object with data_ptr()")
+        left = C.c_int64(0)
+        _check(self.L.gsr_remove(self.h, C.c_void_p(ptr), 1, REMOVE_HIDDEN if hidden else 0, C.byref(left)))
+        return left.value
+
+    def get_removal(self) -> dict:
+        """gsr_get_removal -> {removals: calls that removed something, removed_last, ms: the last call's stage clock
+        [mask copy, mark .. sort, repack, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_removal(self.h, C.byref(calls), C.byref(last), ms))
+        return {"removals": calls.value, "removed_last": last.value, "ms": [float(x) for x in ms]}
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
@@ -1290,6 +1375,13 @@ class MultiEngine:
         if vis is None and (volumes is not None or mask is not None):
             vis, keep = visibility_struct(volumes or (), mask)
         _check(self.L.gsr_multi_set_visibility(self.h, C.byref(vis) if vis is not None else None))
+
+    def remove(self, mask=None, hidden: bool = False) -> int:
+        """gsr_multi_remove: Engine.remove on every rank, from a host mask -> the splats left (the ranks agree, or none keeps geometry)"""
+        words = removal_words(mask, self.stats(0)["n_splats"])
+        left = C.c_int64(0)
+        _check(self.L.gsr_multi_remove(self.h, None if words is None else words.ctypes.data, REMOVE_HIDDEN if hidden else 0, C.byref(left)))
+        return left.value
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

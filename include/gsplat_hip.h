@@ -245,7 +245,7 @@ int  gsr_update(gsr_context* ctx, int64_t first, int64_t n, const gsr_attr_updat
  * untouched.  A HIP failure after that leaves NO geometry (gsr_render: GSR_E_NO_GEOMETRY until the next complete upload); with
  * attributes in u that includes ANY HIP failure of the gsr_update step, also one before its own first write.
  * gsr_stats.uploads does not count a move; moves and move_ms[] do.  float32 sources in DEVICE memory: gsr_move_device below.  Not
- * covered: raw float32 HOST sources for u; a change of the splat count (that is an upload). */
+ * covered: raw float32 HOST sources for u.  A change of the splat count: fewer splats is gsr_remove below, more is an upload. */
 int  gsr_move(gsr_context* ctx, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
 
 /* ---- device sources (upload, update and move from float32 arrays in DEVICE memory) ------------------------------------------ */
@@ -353,6 +353,53 @@ int  gsr_set_visibility(gsr_context* ctx, const gsr_visibility* v);   /* NULL, o
 int  gsr_get_visibility(gsr_context* ctx, gsr_visibility* out, int64_t* hidden);  /* out->mask is always NULL; either may be NULL */
 int  gsr_visibility_eval(const gsr_visibility* v, const float* P, int64_t first, int64_t n, uint8_t* visible_out); /* host, no context, no GPU */
 
+/* ---- removal (resident splats deleted on the GPU, without a re-upload) ---------------------------------------------------------- */
+/* A Delete SOP, a trainer's pruning step, "delete what I cropped away": the splats named by a mask leave the resident cloud and the
+ * survivors close ranks.  Nothing but the mask (n / 8 bytes; nothing at all for a device mask or GSR_REMOVE_HIDDEN alone) crosses the
+ * link: the survivors are compacted on the GPU, go through the ordering of an upload, and their planes are carried into the new
+ * storage order as gsr_move carries them.
+ * THE MASK: bit (i & 31) of word (i >> 5) set = splat i (UPLOAD order, as gsr_update counts) goes -- the sense and layout of
+ * gsr_visibility.mask -- in ceil(n / 32) words for the n resident splats; bits at and behind n in the last word are ignored.  A HOST
+ * pointer, or with mask_is_device != 0 device memory of the context's device or pinned host memory, checked like the sources of the
+ * device verbs above (4-byte aligned, the memory type, every byte inside its allocation) before anything is launched; the verb then
+ * waits for the work queued on the context's public stream, as they do.  NULL only with GSR_REMOVE_HIDDEN.
+ * flags: GSR_REMOVE_HIDDEN = also remove every splat the visibility in force hides: splat i goes iff its bit of `mask` is set or the
+ * rule of gsr_set_visibility (volumes and visibility mask in force, on the raw P bits) calls it hidden.  Without a visibility in force
+ * the flag removes nothing extra.
+ * THE SURVIVORS keep their relative upload order: survivor i becomes upload index i' = the number of survivors before it, and every
+ * later gsr_update / gsr_move / gsr_set_visibility counts in that index space.  gsr_remove_map is the rule on the host (no context, no
+ * GPU): new_index[i] = i', or -1 for a removed splat, for i < n; *n_left = the survivors (either out pointer may be NULL).
+ * CONTRACT: after GSR_OK the resident geometry -- geoA, geoB, every colour chunk, the colour rows, the cluster bounds and the storage
+ * order -- is bit for bit what a fresh context holds after gsr_upload of the survivors' arrays in that order (same
+ * GSR_OPT_STORAGE_ORDER, SH presence and origin), and so is every later frame, in every option mode, target format, frame verb and
+ * band.  Whatever a frame of the cloud before left is dropped as an upload drops it.  *n_left (may be NULL) = the splats left.
+ * With a visibility in force the volumes stay in force, the survivors' true alphas and their bits of a visibility mask in force are
+ * carried into the new upload order (a hidden survivor stays hidden), and the contract is gsr_set_visibility's over the survivors.
+ * After GSR_REMOVE_HIDDEN gsr_get_visibility reports 0 hidden.
+ * Nothing removed: GSR_OK, *n_left = n, no resident bit changes and nothing is invalidated.  Everything removed: the context holds the
+ * empty cloud, as after gsr_upload of 0 splats.
+ * Synchronous; waits for every frame in flight first.  gsr_stats does not grow and its uploads, moves, upload_ms and move_ms are left
+ * alone; gsr_get_removal reports the calls that removed something, the splats the last one removed, and its stage clock ms[4]:
+ *   [0] host -> device wall clock of the mask copy (0.0 for a device mask)   [1] marking, scan, compaction, bounding box, Morton
+ *   codes and sort (HIP events)   [2] k_repack and the cluster bounds (HIP events)   [3] wall clock of the call.
+ * MEMORY: a removal ALWAYS writes the survivors into the spare planes, also under GSR_OPT_STORAGE_ORDER = 0 (the slots change even
+ * when the order does not): a context that uses the verb keeps the second copy of the resident planes that gsr_move documents, and
+ * with a visibility in force a second array of true alphas (4 bytes per splat of capacity).  The capacity and every buffer sized by
+ * it stay: nothing is freed or shrunk.
+ * GSR_E_INVALID, with the context untouched: NULL ctx; a NULL mask without GSR_REMOVE_HIDDEN; unknown flag bits; no geometry
+ * resident; an upload in progress; a device mask that fails the pointer check.  Everything is allocated before the first write to
+ * resident memory or to the visibility's state: GSR_E_OOM leaves the context untouched.  A HIP failure after that leaves NO
+ * geometry, as a failed gsr_move does.
+ * Out of scope: the GSplatRenderer shim and the HDK glue (their rows are borrowed host arrays, and Houdini hands a changed point
+ * count over as new arrays without saying which points went: that is a re-stage); gsr_comm_* (each rank is a plain context and
+ * calls gsr_remove itself); adding splats to a resident cloud; giving memory back (shrinking the capacity, freeing the spare planes);
+ * an asynchronous form. */
+#define GSR_REMOVE_HIDDEN 1     /* flags: also remove every splat the visibility in force hides */
+#define GSR_REMOVE_BLOCK  4096  /* upload indices one workgroup of the compaction kernels spans (k_remove.h) */
+int  gsr_remove(gsr_context* ctx, const uint32_t* mask, int mask_is_device, int flags, int64_t* n_left);
+int  gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_index, int64_t* n_left);   /* host, no context, no GPU */
+int  gsr_get_removal(gsr_context* ctx, int64_t* removals, int64_t* removed_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -453,6 +500,10 @@ int  gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_upd
 int  gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
 /* gsr_set_visibility on every rank, after the same synchronisation (every rank keeps its own copy of the alphas and of a mask) */
 int  gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v);
+/* gsr_remove on every rank, after the same synchronisation, from a HOST mask (NULL with GSR_REMOVE_HIDDEN alone).  The ranks must
+ * agree on the splats left: if they do not, or a rank fails after its first write, the verb fails and NO rank keeps geometry.  The
+ * boundaries of balanced bands stay as after an upload: the next evaluation reads the survivors' row sums. */
+int  gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int flags, int64_t* n_left);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
