@@ -44,6 +44,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "gsr_host_buffers.h"
 #include "k_visibility.h"   // (last: the kernels of the frame keep their places in the code object)
 #include "k_remove.h"
+#include "k_add.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -261,8 +262,9 @@ struct gsr_context {
     uint4* colrow = nullptr;           // ... and as one contiguous row per splat (lazy colour gathers by index)
     int col_chunks = 0;
     // gsr_move: the SPARE copy of the planes (at the capacity c->cap) that k_repack writes the new storage order into; the two sets are
-    // then swapped by pointer.  Allocated at the first move that re-orders, kept until the geometry is freed; the spare cluster bounds
-    // (nclus entries) go whenever an upload gives the live ones up.
+    // then swapped by pointer.  Allocated at the first move that re-orders, kept until the geometry is freed or an add grows the
+    // capacity (gsr_add: the set it leaves as the spare one is at the old capacity and is freed); the spare cluster bounds (nclus
+    // entries) go whenever an upload gives the live ones up, and after every add (they are the smaller cloud's).
     float4* geoA2 = nullptr;
     uint4 *geoB2 = nullptr, *col2 = nullptr, *colrow2 = nullptr;
     float4 *clusA2 = nullptr, *clusB2 = nullptr;
@@ -363,6 +365,9 @@ struct gsr_context {
     uint32_t* rm_h_total = nullptr;
     int64_t rm_calls = 0, rm_last = 0;
     double rm_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // gsr_add (k_add.h): what gsr_get_add reports (the capacity in force is c->cap)
+    int64_t add_calls = 0, add_last = 0, add_grows = 0;
+    double add_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -487,6 +492,34 @@ static void slot_free_splat_arrays(FrameSlot& sl)
     dev_free(sl.rec); dev_free(sl.keyA); dev_free(sl.keyB); dev_free(sl.valA); dev_free(sl.valB); dev_free(sl.blk_cnt);
     dev_free(sl.zwin); dev_free(sl.cseg);
     sl.sort_valid = false;
+}
+
+// A frame slot's arrays that are sized by the capacity, as a set of their own: gsr_upload_begin allocates them for a new capacity, and
+// gsr_add allocates the larger set before its first write and hands it over once nothing can fail for lack of memory any more.
+struct SlotSplatArrays {
+    GsrRecord* rec = nullptr;
+    uint32_t *keyA = nullptr, *keyB = nullptr, *blk_cnt = nullptr, *cseg = nullptr;
+    uint2 *valA = nullptr, *valB = nullptr;
+    float* zwin = nullptr;
+    void release() { dev_free(rec); dev_free(keyA); dev_free(keyB); dev_free(valA); dev_free(valB); dev_free(blk_cnt); dev_free(zwin); dev_free(cseg); }
+};
+static int alloc_splat_arrays(SlotSplatArrays& a, size_t cap)
+{
+    int rc = GSR_OK;
+    // (+256: K1 writes what it keeps at the head of its workgroup's 256 slots)
+    if ((rc = dev_alloc(&a.rec, cap)) || (rc = dev_alloc(&a.keyA, cap + 256)) || (rc = dev_alloc(&a.keyB, cap + 256)) ||
+        (rc = dev_alloc(&a.valA, cap + 256)) || (rc = dev_alloc(&a.valB, cap + 256)) ||
+        (rc = dev_alloc(&a.zwin, cap)) || (rc = dev_alloc(&a.blk_cnt, cap / 256 + 16)) ||
+        (rc = dev_alloc(&a.cseg, cap / GSR_CLUSTER + (size_t)CC_THREADS * 64 + 16)))
+        a.release();
+    return rc;
+}
+// (nothing of the slot is in flight)
+static void slot_take_splat_arrays(FrameSlot& sl, SlotSplatArrays& a)
+{
+    slot_free_splat_arrays(sl);
+    sl.rec = a.rec; sl.keyA = a.keyA; sl.keyB = a.keyB; sl.valA = a.valA; sl.valB = a.valB; sl.blk_cnt = a.blk_cnt; sl.zwin = a.zwin; sl.cseg = a.cseg;
+    a = SlotSplatArrays{};
 }
 
 static void slot_destroy(FrameSlot& sl)
@@ -764,15 +797,12 @@ extern "C" int gsr_upload_begin(gsr_context* c, int64_t total, int has_sh, const
             return rc;
         }
         for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
-            FrameSlot& sl = c->slot[k];
-            // (+256: K1 writes what it keeps at the head of its workgroup's 256 slots)
-            if ((rc = dev_alloc(&sl.rec, cap)) || (rc = dev_alloc(&sl.keyA, cap + 256)) || (rc = dev_alloc(&sl.keyB, cap + 256)) ||
-                (rc = dev_alloc(&sl.valA, cap + 256)) || (rc = dev_alloc(&sl.valB, cap + 256)) ||
-                (rc = dev_alloc(&sl.zwin, cap)) || (rc = dev_alloc(&sl.blk_cnt, cap / 256 + 16)) ||
-                (rc = dev_alloc(&sl.cseg, cap / GSR_CLUSTER + (size_t)CC_THREADS * 64 + 16))) {
+            SlotSplatArrays a;
+            if ((rc = alloc_splat_arrays(a, cap))) {
                 free_geometry(c);
                 return rc;
             }
+            slot_take_splat_arrays(c->slot[k], a);
         }
         c->cap = (uint32_t)cap;
         c->col_chunks = chunks;
@@ -4038,4 +4068,267 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     c->rm_ms[3] = up_now_ms() - t_begin;
     if (n_left) *n_left = (int64_t)n1;
     return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Adding (k_add.h): splats appended to the resident cloud on the GPU.  gsr_remove the other way round: the new rows are
+// staged, every position goes through the ordering of an upload, k_add_pack writes the spare planes from the resident planes (old
+// splats) and the staged rows (new ones), the swap.  The one verb that can need MORE room than the context has: the capacity policy.
+extern "C" int64_t gsr_add_capacity(int64_t capacity, int64_t n_needed)
+{
+    if (capacity < 0 || n_needed < 0 || n_needed > 0x7fffffffll)
+        return (int64_t)set_err(GSR_E_INVALID, "gsr_add_capacity: bad argument (%lld, %lld)", (long long)capacity, (long long)n_needed);
+    if (n_needed <= capacity) return capacity;
+    return std::min<int64_t>(n_needed + n_needed / 4, 0x7fffffffll);     // (the 25 % headroom the list buffers take)
+}
+
+extern "C" int gsr_get_add(gsr_context* c, int64_t* adds, int64_t* added_last, int64_t* capacity, int64_t* grows, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_add: ctx is NULL");
+    if (adds) *adds = c->add_calls;
+    if (added_last) *added_last = c->add_last;
+    if (capacity) *capacity = (int64_t)c->cap;
+    if (grows) *grows = c->add_grows;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->add_ms[k];
+    return GSR_OK;
+}
+
+// what both forms refuse before they look at their arrays; *done: m == 0, there is nothing to do
+static int add_refuse(gsr_context* c, int64_t m, int64_t* n_total, const char* who, bool* done)
+{
+    *done = false;
+    if (!c) return set_err(GSR_E_INVALID, "%s: ctx is NULL", who);
+    if (m < 0) return set_err(GSR_E_INVALID, "%s: bad splat count %lld", who, (long long)m);
+    if (c->uploading) return set_err(GSR_E_INVALID, "%s: upload in progress", who);
+    if (!c->has_geometry) return set_err(GSR_E_INVALID, "%s: no geometry: nothing uploaded", who);
+    if ((int64_t)c->n + m > 0x7fffffffll) return set_err(GSR_E_INVALID, "%s: %u + %lld splats are more than a context holds", who, c->n, (long long)m);
+    if (m == 0) {                                      // nothing changes, nothing is invalidated
+        if (n_total) *n_total = (int64_t)c->n;
+        *done = true;
+    }
+    return GSR_OK;
+}
+
+// The body of gsr_add and gsr_add_device, behind their refusals.  stage_rows(arena of m rows, stream, &link_ms): the new rows into the
+// arena in gsr_upload_append's layout, complete when it returns.
+template <class StageRows>
+static int add_body(gsr_context* c, const char* who, uint32_t m, StageRows&& stage_rows, int64_t* n_total)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    const double t_begin = up_now_ms();
+    int rc = sync_all(c);      // the public stream (a producer of a device source queued there has finished), and no write under a frame in flight
+    if (rc) return rc;
+    const uint32_t n0 = c->n, n1 = n0 + m, nclus1 = div_up(n1, GSR_CLUSTER);
+    FrameSlot& sl = c->slot[0];
+    hipStream_t us = sl.stream;
+    const uint32_t cap0 = c->cap, cap1 = (uint32_t)gsr_add_capacity((int64_t)cap0, (int64_t)n1);
+    const bool grow = cap1 != cap0;
+    const bool vis = c->vis_on;
+    // ---- everything the call needs, before the first write to resident memory or to the visibility's state
+    const size_t al = 256;
+    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
+    const size_t oAll = pad(up_arena(nullptr, m, c->has_sh).bytes), need = oAll + pad((size_t)n1 * 12);
+    if (need > c->stage_cap) {
+        dev_free(c->stage);
+        c->stage_cap = 0;
+        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
+        c->stage_cap = need + 256;
+    }
+    const bool may_order = c->opt_morton && n1 > 1;
+    uint32_t *perm_new = nullptr, *mask_new = nullptr;
+    float4 *clusA_new = nullptr, *clusB_new = nullptr;
+    float* alpha0_new = nullptr;
+    SlotSplatArrays slot_new[GSR_MAX_SLOTS];
+    auto give_up = [&](int code) {
+        dev_free(perm_new); dev_free(mask_new); dev_free(clusA_new); dev_free(clusB_new); dev_free(alpha0_new);
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_new[k].release();
+        return code;
+    };
+    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
+    if (may_order && (rc = ensure_order_buffers(c, n1, &perm_new, who))) return give_up(rc);
+    if (grow) {
+        // the spare set is at the old capacity: it goes first (nothing reads it), and the destination set comes at the new one
+        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+        const size_t cap = cap1;
+        if ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
+            (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8)))) {
+            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+            return give_up(rc);
+        }
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k)
+            if ((rc = alloc_splat_arrays(slot_new[k], cap))) {
+                dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+                return give_up(rc);
+            }
+    } else if ((rc = ensure_spare_planes(c))) {
+        return give_up(rc);
+    }
+    // (ensure_spare_planes sizes the spare cluster bounds for a removal, which only ever needs fewer: an add brings its own)
+    if ((rc = dev_alloc(&clusA_new, nclus1)) || (rc = dev_alloc(&clusB_new, nclus1))) return give_up(rc);
+    if (vis) {
+        if ((rc = vis_ensure_buffers(c))) return give_up(rc);
+        if (grow && (rc = dev_alloc(&alpha0_new, (size_t)cap1))) return give_up(rc);
+        if (c->vis_mask && (rc = dev_alloc(&mask_new, ((size_t)n1 + 31) / 32))) return give_up(rc);
+    }
+    for (int k = 0; k < 3; ++k)
+        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) return give_up(set_err(GSR_E_HIP, "%s: no event", who));
+    if ((rc = ensure_inverse_perm(c))) return give_up(rc);      // (the OLD order's inverse; built on slot 0's own stream)
+    if (hipStreamSynchronize(sl.own) != hipSuccess) return give_up(set_err(GSR_E_HIP, "%s: the inverse of the storage order", who));
+    // nothing can fail for lack of memory any more: the larger buffers take their places (none of them holds anything a frame keeps)
+    dev_free(c->clusA2); dev_free(c->clusB2);
+    c->clusA2 = clusA_new; c->clusB2 = clusB_new; clusA_new = clusB_new = nullptr;
+    if (grow) {
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], slot_new[k]);
+        dev_free(c->alpha0_2);
+        if (!vis) dev_free(c->alpha0);                 // (at the old capacity, and valid only while a visibility is in force)
+    }
+    // ---- from here on a failure leaves no geometry (as a failed gsr_move does)
+    auto lost = [&](int code) {
+        give_up(code);
+        if (grow) {                                    // (the planes that stay are at the old capacity)
+            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+        }
+        drop_geometry(c);
+        return code;
+    };
+    // 1. the new rows, staged
+    const UpArena A = up_arena(c->stage, m, c->has_sh);
+    double link_ms = 0.0;
+    hipError_t e = stage_rows(A, us, &link_ms);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: staging the new rows: %s", who, hipGetErrorString(e)));
+    // 2. every position in upload order: the resident ones from geoA through the old order's inverse, the new ones behind them
+    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
+    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess && n0) {
+        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n0, 256)), dim3(256), 0, us, 0u, 0u, n0, (const float*)nullptr, inv_old, c->geoA, (uint4*)nullptr, Pall);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(Pall + 3 * (size_t)n0, A.P, (size_t)m * 12, hipMemcpyDeviceToDevice, us);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    // 3. the ordering of an upload over all of them
+    if ((rc = position_box(c, Pall, n1, us, who))) return lost(rc);
+    const bool ordered = may_order && c->bbox_ok;
+    if (ordered && (rc = morton_order(c, Pall, n1, perm_new, who))) return lost(rc);
+    if (!ordered) dev_free(perm_new);
+    e = hipEventRecord(c->up_ev[1], us);
+    // 4. the planes of the larger cloud into the spare set: resident splats from the planes, new ones from the staged rows
+    if (e == hipSuccess) {
+        const GsrPackSrc src{A.P, A.alpha, A.Cd, A.scale, A.orient, A.shx, A.shy, A.shz};
+        if (c->has_sh)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_add_pack<true>), dim3(nclus1), dim3(GSR_PACK_THREADS), 0, us, n1, n0, cap0, cap1, src, perm_new, inv_old,
+                               c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_add_pack<false>), dim3(nclus1), dim3(GSR_PACK_THREADS), 0, us, n1, n0, cap0, cap1, src, perm_new, inv_old,
+                               c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+    // ... and the upload-ordered state of a visibility in force: the true alphas of the new rows behind the old ones, the mask extended
+    // by clear bits
+    if (e == hipSuccess && vis) {
+        float* const a0 = grow ? alpha0_new : c->alpha0;
+        if (grow && n0) e = hipMemcpyAsync(a0, c->alpha0, (size_t)n0 * 4, hipMemcpyDeviceToDevice, us);
+        if (e == hipSuccess) e = hipMemcpyAsync(a0 + n0, A.alpha, (size_t)m * 4, hipMemcpyDeviceToDevice, us);
+        if (e == hipSuccess && mask_new) {
+            const uint32_t words1 = (uint32_t)(((size_t)n1 + 31) / 32);
+            hipLaunchKernelGGL(k_add_mask_extend, dim3(div_up(words1, 256)), dim3(256), 0, us, n0, words1, c->vis_mask, mask_new);
+            e = hipGetLastError();
+        }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
+    // 5. the swap.  What becomes the spare set is the cloud before: its cluster bounds are too few for the next edit of this one, and
+    // after a growth its planes are at the wrong capacity -- both go, and the next edit that needs spare planes allocates them again
+    swap_planes(c, perm_new);
+    c->h_perm.clear();
+    dev_free(c->clusA2); dev_free(c->clusB2);
+    if (grow) {
+        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
+        c->cap = cap1;
+        if (vis) { dev_free(c->alpha0); c->alpha0 = alpha0_new; alpha0_new = nullptr; }
+    }
+    c->n = n1; c->nclus = nclus1; c->up_total = c->up_filled = n1;
+    c->st.n_splats = n1;
+    if (mask_new) { dev_free(c->vis_mask); c->vis_mask = mask_new; mask_new = nullptr; }
+    // 6. a visibility in force: the rule over the whole cloud, in the order it sits in now (as a move's step 6)
+    if (vis && (e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess) {
+        drop_geometry(c);
+        return set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e));
+    }
+    // 7. a new cloud to everything a frame keeps
+    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }
+    c->add_calls += 1;
+    c->add_last = (int64_t)m;
+    if (grow) c->add_grows += 1;
+    float ms = 0.0f;
+    c->add_ms[0] = link_ms;
+    c->add_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? ms : 0.0;
+    c->add_ms[2] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? ms : 0.0;
+    c->add_ms[3] = up_now_ms() - t_begin;
+    if (n_total) *n_total = (int64_t)n1;
+    return GSR_OK;
+}
+
+extern "C" int gsr_add(gsr_context* c, int64_t m64, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
+                       const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total)
+{
+    const char* const who = "gsr_add";
+    bool done = false;
+    int rc = add_refuse(c, m64, n_total, who, &done);
+    if (rc || done) return rc;
+    if (!P || !Cd || !alpha || !scale || !orient) return set_err(GSR_E_INVALID, "gsr_add: NULL attribute array");
+    const int nsh = (shx ? 1 : 0) + (shy ? 1 : 0) + (shz ? 1 : 0);
+    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_add: SH arrays for a cloud uploaded without SH");
+    if (c->has_sh && nsh != 3) return set_err(GSR_E_INVALID, "gsr_add: the cloud has SH and the three SH arrays are not all given");
+    const uint32_t m = (uint32_t)m64;
+    const bool has_sh = c->has_sh;
+    return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double* link_ms) {
+        // host -> device, nothing else (as gsr_upload_append)
+        const double t0 = up_now_ms();
+        hipError_t e = hipSuccess;
+        auto h2d = [&](void* d, const void* h, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, us); };
+        h2d(A.P, P, (size_t)m * 12); h2d(A.alpha, alpha, (size_t)m * 4); h2d(A.Cd, Cd, (size_t)m * 6);
+        h2d(A.scale, scale, (size_t)m * 6); h2d(A.orient, orient, (size_t)m * 8);
+        if (has_sh) { h2d(A.shx, shx, (size_t)m * 32); h2d(A.shy, shy, (size_t)m * 32); h2d(A.shz, shz, (size_t)m * 32); }
+        if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be freed on return
+        *link_ms = up_now_ms() - t0;
+        return e;
+    }, n_total);
+}
+
+extern "C" int gsr_add_device(gsr_context* c, int64_t m64, const gsr_device_attrs* a, int64_t* n_total)
+{
+    const char* const who = "gsr_add_device";
+    bool done = false;
+    int rc = add_refuse(c, m64, n_total, who, &done);
+    if (rc || done) return rc;
+    if (!a) return set_err(GSR_E_INVALID, "gsr_add_device: attrs is NULL");
+    if (!a->P) return set_err(GSR_E_INVALID, "gsr_add_device: P is NULL");
+    if (c->has_sh != (a->sh != nullptr)) return set_err(GSR_E_INVALID, "gsr_add_device: SH presence differs from the resident cloud's");
+    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
+        return set_err(GSR_E_INVALID, "gsr_add_device: sh_vec3_per_point = %d is not within 1..16", a->sh_vec3_per_point);
+    const uint32_t m = (uint32_t)m64;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = check_device_attrs(c, a, m, who))) return rc;
+    const bool has_sh = c->has_sh;
+    return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double*) {
+        // P and alpha as they are (the runtime picks the direction: a source may be pinned host memory); the rest is quantised straight
+        // from the caller's arrays (as gsr_upload_append_device)
+        hipError_t e = hipMemcpyAsync(A.P, a->P, (size_t)m * 12, hipMemcpyDefault, us);
+        if (e == hipSuccess)
+            e = a->alpha ? hipMemcpyAsync(A.alpha, a->alpha, (size_t)m * 4, hipMemcpyDefault, us)
+                         : hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(A.alpha), 0x3f800000, m, us);      // missing opacity: opaque
+        if (e == hipSuccess) {
+            GsrRawSh sh{};
+            sh.scheme = a->sh ? 1 : 0;
+            sh.vec3_per_point = a->sh_vec3_per_point;
+            sh.array = a->sh;
+            hipLaunchKernelGGL(k_quantize_raw, dim3(div_up(m, 256)), dim3(256), 0, us, m, a->Cd, a->scale, a->orient, sh, A.Cd, A.scale, A.orient,
+                               has_sh ? A.shx : (uint16_t*)nullptr, has_sh ? A.shy : (uint16_t*)nullptr, has_sh ? A.shz : (uint16_t*)nullptr);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
+        return e;
+    }, n_total);
 }

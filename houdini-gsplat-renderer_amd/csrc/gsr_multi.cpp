@@ -655,6 +655,30 @@ extern "C" int gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int fla
     return GSR_OK;
 }
 
+// ... and added to on every rank: each stages the new rows, orders and packs its own replica.  gsr_multi_remove's agreement rule.
+extern "C" int gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
+                             const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_add: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_add: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> total((size_t)G, -1);
+    int64_t* const tp = total.data();
+    rc = for_each_rank(m, [=](int g) { return gsr_add(m->ctx[g], n_new, P, Cd, alpha, scale, orient, shx, shy, shz, tp + g); });
+    bool any_done = false, same = rc == GSR_OK;
+    for (int g = 0; g < G; ++g) any_done = any_done || total[(size_t)g] >= 0;
+    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
+    for (int g = 1; g < G && same; ++g) same = total[(size_t)g] == total[0];
+    if (!same) {
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_add: the ranks do not agree on the splat count: the geometry is dropped on all of them");
+    }
+    if (n_total) *n_total = total[0];
+    return GSR_OK;
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

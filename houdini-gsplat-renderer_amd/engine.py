@@ -176,6 +176,7 @@ C_ABI_SYMBOLS = [
     "gsr_set_row_band", "gsr_read_row_work", "gsr_debug_balance_rows", "gsr_multi_get_bands",
     "gsr_set_visibility", "gsr_get_visibility", "gsr_visibility_eval", "gsr_multi_set_visibility", "gsplat_renderer_set_visibility",
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
+    "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
 ]
 
 
@@ -243,6 +244,12 @@ def load_library() -> C.CDLL:
     L.gsr_remove_map.argtypes = [vp, i64, vp, C.POINTER(C.c_int64)]
     L.gsr_get_removal.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_remove.argtypes = [vp, vp, i32, C.POINTER(C.c_int64)]
+    L.gsr_add.argtypes = [vp, i64] + [vp] * 8 + [C.POINTER(C.c_int64)]
+    L.gsr_add_device.argtypes = [vp, i64, C.POINTER(gsr_device_attrs), C.POINTER(C.c_int64)]
+    L.gsr_add_capacity.argtypes = [i64, i64]
+    L.gsr_add_capacity.restype = i64
+    L.gsr_get_add.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_double)]
+    L.gsr_multi_add.argtypes = [vp, i64] + [vp] * 8 + [C.POINTER(C.c_int64)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -563,6 +570,30 @@ def remove_map(mask, n=None):
     return out, left.value
 
 
+def add_capacity(cap: int, need: int) -> int:
+    """gsr_add_capacity (host only, no GPU): the capacity a context of capacity cap has after an add that brings it to need splats --
+    cap while need fits, else need + need // 4, clamped to 0x7fffffff"""
+    cap, need = int(cap), int(need)
+    if not (-2 ** 63 <= cap < 2 ** 63 and -2 ** 63 <= need < 2 ** 63):
+        raise GsrError(-1, f"add_capacity: ({cap}, {need}) are not 64-bit counts")
+    out = load_library().gsr_add_capacity(cap, need)
+    if out < 0:
+        _check(int(out))
+    return int(out)
+
+
+def add_arrays(splats, has_sh=None):
+    """the arrays of gsr_add from a Splats-like object -> _Arrays; has_sh (None: not known here) = whether the resident cloud has SH,
+    which the new rows must match"""
+    for name in ("P", "Cd", "alpha", "scale", "orient"):
+        if getattr(splats, name, None) is None:
+            raise GsrError(-1, f"add: the new splats have no {name}")
+    a = _Arrays(splats)
+    if has_sh is not None and bool(has_sh) != (a.shx is not None) and a.n:
+        raise GsrError(-1, "add: the new splats " + ("have no SH and the resident cloud has" if has_sh else "have SH and the resident cloud has none"))
+    return a
+
+
 def camera_struct(cam) -> gsr_camera:
     s = gsr_camera()
     for name in ("obj_view", "object", "inv_object", "view", "proj"):
@@ -853,6 +884,34 @@ class Engine:
         calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
         _check(self.L.gsr_get_removal(self.h, C.byref(calls), C.byref(last), ms))
         return {"removals": calls.value, "removed_last": last.value, "ms": [float(x) for x in ms]}
+
+    def add(self, splats) -> int:
+        """gsr_add: the splats (a Splats-like object, arrays in upload's layout) join the resident cloud behind its last upload index,
+        ordered and packed on the GPU with no re-upload; with SH exactly when the resident cloud has SH -> the splats resident now.
+        An add that does not fit grows the context (add_capacity; include/gsplat_hip.h)."""
+        a = add_arrays(splats)
+        total = C.c_int64(0)
+        _check(self.L.gsr_add(self.h, a.n, *a.ptrs(), C.byref(total)))
+        return total.value
+
+    def add_device(self, attrs: dict, n=None, sh_vec3_per_point=None) -> int:
+        """gsr_add_device: add from float32 arrays in device memory, attrs = {P, and optionally Cd, alpha, scale, orient, sh} as
+        upload_device takes them; sh exactly when the resident cloud has SH -> the splats resident now"""
+        if not isinstance(attrs, dict):
+            raise GsrError(-1, "add_device: attrs is not a dict of device arrays")
+        if attrs.get("P") is None:
+            raise GsrError(-1, "add_device: P is missing")
+        a, n, keep = device_attrs_struct(n, sh_vec3_per_point, **attrs)
+        total = C.c_int64(0)
+        _check(self.L.gsr_add_device(self.h, n, C.byref(a), C.byref(total)))
+        return total.value
+
+    def get_add(self) -> dict:
+        """gsr_get_add -> {adds: calls that added something, added_last, capacity: splats the context has room for, grows: adds that
+        grew it, ms: the last call's stage clock [new rows over the link, positions .. sort, pack, wall]}"""
+        calls, last, cap, grows, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_add(self.h, C.byref(calls), C.byref(last), C.byref(cap), C.byref(grows), ms))
+        return {"adds": calls.value, "added_last": last.value, "capacity": cap.value, "grows": grows.value, "ms": [float(x) for x in ms]}
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
@@ -1382,6 +1441,13 @@ class MultiEngine:
         left = C.c_int64(0)
         _check(self.L.gsr_multi_remove(self.h, None if words is None else words.ctypes.data, REMOVE_HIDDEN if hidden else 0, C.byref(left)))
         return left.value
+
+    def add(self, splats) -> int:
+        """gsr_multi_add: Engine.add on every rank, from host arrays -> the splats resident now (the ranks agree, or none keeps geometry)"""
+        a = add_arrays(splats)
+        total = C.c_int64(0)
+        _check(self.L.gsr_multi_add(self.h, a.n, *a.ptrs(), C.byref(total)))
+        return total.value
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

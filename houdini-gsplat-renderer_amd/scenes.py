@@ -43,6 +43,14 @@ class Splats:
         g = lambda a: None if a is None else np.ascontiguousarray(a[sl])
         return Splats(g(self.P), g(self.Cd), g(self.alpha), g(self.scale), g(self.orient), g(self.shx), g(self.shy), g(self.shz))
 
+    def concat(self, other: "Splats") -> "Splats":
+        """this cloud's splats, then other's (upload order): both with SH or both without"""
+        if self.has_sh != other.has_sh:
+            raise ValueError("concat: one cloud has SH and the other has none")
+        g = lambda a, b: None if a is None else np.ascontiguousarray(np.concatenate([a, b], axis=0))
+        return Splats(g(self.P, other.P), g(self.Cd, other.Cd), g(self.alpha, other.alpha), g(self.scale, other.scale),
+                      g(self.orient, other.orient), g(self.shx, other.shx), g(self.shy, other.shy), g(self.shz, other.shz))
+
 
 def f16bits(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32).astype(np.float16).view(np.uint16)

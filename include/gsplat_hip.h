@@ -245,7 +245,7 @@ int  gsr_update(gsr_context* ctx, int64_t first, int64_t n, const gsr_attr_updat
  * untouched.  A HIP failure after that leaves NO geometry (gsr_render: GSR_E_NO_GEOMETRY until the next complete upload); with
  * attributes in u that includes ANY HIP failure of the gsr_update step, also one before its own first write.
  * gsr_stats.uploads does not count a move; moves and move_ms[] do.  float32 sources in DEVICE memory: gsr_move_device below.  Not
- * covered: raw float32 HOST sources for u.  A change of the splat count: fewer splats is gsr_remove below, more is an upload. */
+ * covered: raw float32 HOST sources for u.  A change of the splat count: fewer splats is gsr_remove below, more is gsr_add below. */
 int  gsr_move(gsr_context* ctx, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u);
 
 /* ---- device sources (upload, update and move from float32 arrays in DEVICE memory) ------------------------------------------ */
@@ -392,13 +392,64 @@ int  gsr_visibility_eval(const gsr_visibility* v, const float* P, int64_t first,
  * geometry, as a failed gsr_move does.
  * Out of scope: the GSplatRenderer shim and the HDK glue (their rows are borrowed host arrays, and Houdini hands a changed point
  * count over as new arrays without saying which points went: that is a re-stage); gsr_comm_* (each rank is a plain context and
- * calls gsr_remove itself); adding splats to a resident cloud; giving memory back (shrinking the capacity, freeing the spare planes);
+ * calls gsr_remove itself); giving memory back (shrinking the capacity, freeing the spare planes);
  * an asynchronous form. */
 #define GSR_REMOVE_HIDDEN 1     /* flags: also remove every splat the visibility in force hides */
 #define GSR_REMOVE_BLOCK  4096  /* upload indices one workgroup of the compaction kernels spans (k_remove.h) */
 int  gsr_remove(gsr_context* ctx, const uint32_t* mask, int mask_is_device, int flags, int64_t* n_left);
 int  gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_index, int64_t* n_left);   /* host, no context, no GPU */
 int  gsr_get_removal(gsr_context* ctx, int64_t* removals, int64_t* removed_last, double ms[4]);   /* any pointer may be NULL */
+
+/* ---- adding (splats appended to the resident cloud on the GPU, without a re-upload) ---------------------------------------------- */
+/* A trainer's densification step, a merge of two captures, a simulation that emits splats: m new splats join the n resident ones.
+ * Only the m new rows cross the link (nothing at all for device sources): every position goes through the ordering of an upload on
+ * the GPU, and the planes of the larger cloud are written in the new storage order from the resident planes (old splats) and the
+ * staged rows (new ones) by one kernel (k_add.h).
+ * gsr_add: host arrays in gsr_upload_append's layout, m rows; all required for m > 0, the three SH arrays exactly when the resident
+ * cloud has SH.  gsr_add_device: float32 arrays in device memory under gsr_upload_append_device's rules -- P required, the NULL
+ * defaults (Cd 0, alpha 1, scale 1, orient identity), sh given exactly when the cloud has SH with sh_vec3_per_point in 1..16, every
+ * pointer checked before anything is launched, the work queued on the context's public stream waited for first, the attributes
+ * quantised on the GPU; its NaN exception is gsr_upload_append_device's.
+ * INDEX SPACE: the new splats get the upload indices [n, n + m) in the order given; every resident splat keeps its index, and every
+ * later gsr_update / gsr_move / gsr_set_visibility / gsr_remove counts in the new space.  *n_total (may be NULL) = n + m.
+ * CONTRACT: after GSR_OK the resident geometry -- geoA, geoB, every colour chunk, the colour rows, the cluster bounds and the storage
+ * order -- is bit for bit what a fresh context holds after gsr_upload of the concatenation (the resident arrays as edited so far,
+ * then the new rows; same GSR_OPT_STORAGE_ORDER, SH presence and the origin in force: there is no origin parameter), and so is every
+ * later frame, in every option mode, target format, frame verb and band.  Whatever a frame of the cloud before left is dropped as an
+ * upload drops it.
+ * With a visibility in force the volumes apply to the new splats at their positions, a mask in force is carried and extended with
+ * clear bits, the true alphas of the new rows are put aside behind the old ones, and the contract is gsr_set_visibility's over the
+ * concatenation with the mask extended by zeros; gsr_get_visibility reports the new hidden count and mask_splats = n + m.
+ * m == 0: GSR_OK, nothing changes and nothing is invalidated.  Adding to the EMPTY cloud (after gsr_upload of 0 splats, or a removal
+ * of everything) leaves what gsr_upload of the rows leaves.
+ * CAPACITY: the one edit that can need more room than the context has.  gsr_add_capacity(capacity, n_needed) is the policy, a pure
+ * host function (no context, no GPU): n_needed <= capacity gives capacity; otherwise min(n_needed + n_needed / 4, 0x7fffffff) -- the
+ * 25 % headroom the list buffers take; a negative argument or n_needed > 0x7fffffff gives GSR_E_INVALID.  When n + m exceeds the
+ * capacity in force the add GROWS the context to that value: the planes are written at the new capacity and the old set is freed,
+ * and every per-splat buffer of the frame slots and of the visibility follows, all of it allocated before the first write.  A later
+ * gsr_upload of a smaller cloud keeps the larger capacity.  A run of small adds therefore grows now and then, not every time.
+ * MEMORY: an add ALWAYS writes the larger cloud into a second set of planes, also under GSR_OPT_STORAGE_ORDER = 0; without growth
+ * that is the spare copy gsr_move documents, which stays.  After a growth there is no spare copy: the next edit that needs one
+ * allocates it again, at the new capacity.
+ * Synchronous; waits for every frame in flight first.  gsr_stats.uploads, moves, upload_ms and move_ms are left alone; gsr_get_add
+ * reports the calls that added something, the rows the last one added, the capacity in force, how often an add grew it, and the
+ * last call's stage clock ms[4]:
+ *   [0] host -> device wall clock of the new rows (0.0 for device sources)   [1] positions in upload order, bounding box, Morton
+ *   codes and sort (HIP events)   [2] k_add_pack and the cluster bounds (HIP events)   [3] wall clock of the call.
+ * GSR_E_INVALID, with the context untouched: NULL ctx; m < 0; n + m > 0x7fffffff; a NULL required array with m > 0; SH arrays for a
+ * cloud without SH, or a cloud with SH and not all three arrays (device form: sh absent or present against the cloud, or
+ * sh_vec3_per_point outside 1..16); no geometry ever uploaded; an upload in progress; a device source that fails the pointer check.
+ * Everything is allocated before the first write to resident memory or to the visibility's state: GSR_E_OOM leaves the context
+ * untouched.  A HIP failure after that leaves NO geometry, as a failed gsr_move does.
+ * Out of scope: the GSplatRenderer shim and the HDK glue (Houdini hands a changed point count over as new arrays: that is a
+ * re-stage); gsr_comm_* (each rank is a plain context and calls gsr_add itself); raw float32 HOST sources; inserting at an index
+ * other than the end; an in-place tail append under GSR_OPT_STORAGE_ORDER = 0; giving memory back; a gsr_reserve; an asynchronous
+ * form. */
+int  gsr_add(gsr_context* ctx, int64_t m, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
+             const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total);
+int  gsr_add_device(gsr_context* ctx, int64_t m, const gsr_device_attrs* a, int64_t* n_total);
+int64_t gsr_add_capacity(int64_t capacity, int64_t n_needed);   /* host, no context, no GPU */
+int  gsr_get_add(gsr_context* ctx, int64_t* adds, int64_t* added_last, int64_t* capacity, int64_t* grows, double ms[4]);   /* any pointer may be NULL */
 
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
@@ -504,6 +555,11 @@ int  gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v);
  * agree on the splats left: if they do not, or a rank fails after its first write, the verb fails and NO rank keeps geometry.  The
  * boundaries of balanced bands stay as after an upload: the next evaluation reads the survivors' row sums. */
 int  gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int flags, int64_t* n_left);
+/* gsr_add on every rank, after the same synchronisation, from HOST arrays.  The ranks must agree on the total: if they do not, or a
+ * rank fails after its first write, the verb fails and NO rank keeps geometry.  The boundaries of balanced bands stay as after an
+ * upload. */
+int  gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
+                   const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
