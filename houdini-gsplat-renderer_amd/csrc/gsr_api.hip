@@ -1,5 +1,6 @@
 // gsr_api.hip -- host side of libgsplat_hip.so: context, HBM buffers, the
 // per-frame kernel pipeline and the C ABI declared in include/gsplat_hip.h.
+// (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end.)
 //
 // Pipeline per gsr_render (all on one HIP stream):
 //   k_cluster_cull         clusters of 64 Morton-ordered splats vs clip planes / screen / band / depth horizons (k_cluster.h)
@@ -25,6 +26,7 @@
 #include <chrono>
 #include <algorithm>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gsplat_hip.h"
@@ -752,6 +754,7 @@ extern "C" int gsr_convert_pixels(const float* rgba32f, int64_t n_pixels, int fo
     return GSR_OK;
 }
 
+static inline size_t pad256(size_t b) { return (b + 255) / 256 * 256; }
 // the arena's arrays for `total` splats (256-byte aligned sections)
 struct UpArena {
     float *P, *alpha;
@@ -760,11 +763,9 @@ struct UpArena {
 };
 static UpArena up_arena(char* base, size_t total, bool has_sh)
 {
-    const size_t al = 256;
-    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
     UpArena a{};
     size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += pad(bytes); return p; };
+    auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += pad256(bytes); return p; };
     a.P = reinterpret_cast<float*>(take(total * 12)); a.alpha = reinterpret_cast<float*>(take(total * 4));
     a.Cd = reinterpret_cast<uint16_t*>(take(total * 6)); a.scale = reinterpret_cast<uint16_t*>(take(total * 6));
     a.orient = reinterpret_cast<uint16_t*>(take(total * 8));
@@ -776,6 +777,50 @@ static UpArena up_arena(char* base, size_t total, bool has_sh)
     return a;
 }
 static double up_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The arena holds `bytes` (kept between uploads and edits; only ever grown, and what it held does not survive a growth).
+static int ensure_stage(gsr_context* c, size_t bytes)
+{
+    if (bytes <= c->stage_cap) return GSR_OK;
+    dev_free(c->stage);
+    c->stage_cap = 0;
+    const int rc = dev_alloc(&c->stage, bytes + 256);
+    if (rc) return rc;
+    c->stage_cap = bytes + 256;
+    return GSR_OK;
+}
+// The first `count` events of the upload / edit clock.  oom_code: hipErrorOutOfMemory comes back as GSR_E_OOM (upload, update, remove)
+// or, like every other failure, as GSR_E_HIP (move, add): the verbs differ there, and each keeps its code.
+static int ensure_up_events(gsr_context* c, int count, const char* who, bool oom_code)
+{
+    for (int k = 0; k < count; ++k) {
+        if (c->up_ev[k]) continue;
+        const hipError_t e = hipEventCreate(&c->up_ev[k]);
+        if (e != hipSuccess) return set_err(oom_code && e == hipErrorOutOfMemory ? GSR_E_OOM : GSR_E_HIP, "%s: no event: %s", who, hipGetErrorString(e));
+    }
+    return GSR_OK;
+}
+// n rows of host arrays (rows: HOST pointers here) into the arena behind its first `at` rows, on `us`; complete on return, so the caller's
+// arrays may be freed.  Host -> device, nothing else.  (Pageable memory: the runtime stages it through its own pinned buffers at the
+// link's rate -- 56 GB/s measured on this box, the same as from pinned memory: tools/ubench_h2d.hip.)
+static hipError_t stage_host_rows(const UpArena& A, size_t at, uint32_t n, const GsrPackSrc& rows, bool has_sh, hipStream_t us)
+{
+    hipError_t e = hipSuccess;
+    auto h2d = [&](void* d, const void* h, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, us); };
+    h2d(A.P + 3 * at, rows.P, (size_t)n * 12); h2d(A.alpha + at, rows.alpha, (size_t)n * 4); h2d(A.Cd + 3 * at, rows.Cd, (size_t)n * 6);
+    h2d(A.scale + 3 * at, rows.scale, (size_t)n * 6); h2d(A.orient + 4 * at, rows.orient, (size_t)n * 8);
+    if (has_sh) { h2d(A.shx + 16 * at, rows.shx, (size_t)n * 32); h2d(A.shy + 16 * at, rows.shy, (size_t)n * 32); h2d(A.shz + 16 * at, rows.shz, (size_t)n * 32); }
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    return e;
+}
+// One launch for a kernel template's two <SH> forms: launch(std::true_type / std::false_type).  (A kernel template takes its place in
+// the code object where it is first used: the launches of k_pack, k_update, k_repack and k_update_f32 stay in this file, in that order.)
+template <class Launch>
+static void launch_sh(bool has_sh, Launch&& launch)
+{
+    if (has_sh) launch(std::true_type{});
+    else launch(std::false_type{});
+}
 
 // ---------------------------------------------------------------------------
 // geometry staging
@@ -808,15 +853,7 @@ extern "C" int gsr_upload_begin(gsr_context* c, int64_t total, int has_sh, const
         c->col_chunks = chunks;
     }
     // the staging arena of the whole upload (kept between uploads; only ever grown)
-    {
-        const UpArena A = up_arena(nullptr, n, has_sh != 0);
-        if (A.bytes > c->stage_cap) {
-            dev_free(c->stage);
-            c->stage_cap = 0;
-            if ((rc = dev_alloc(&c->stage, A.bytes + 256))) return rc;
-            c->stage_cap = A.bytes + 256;
-        }
-    }
+    if ((rc = ensure_stage(c, up_arena(nullptr, n, has_sh != 0).bytes))) return rc;
     c->up_t_begin = up_now_ms(); c->up_h2d_ms = 0.0; c->up_quant_ms = 0.0;
     c->n = 0;
     c->has_sh = has_sh != 0;
@@ -847,15 +884,9 @@ extern "C" int gsr_upload_append(gsr_context* c, int64_t n64, const float* P, co
     const size_t at = c->up_filled;
     hipStream_t us = c->slot[0].own;
     const UpArena A = up_arena(c->stage, c->up_total, c->has_sh);
-    // Host -> device, nothing else: the entry lands behind the ones before it, in upload order.  (Pageable memory: the runtime stages
-    // it through its own pinned buffers at the link's rate -- 56 GB/s measured on this box, the same as from pinned memory:
-    // tools/ubench_h2d.hip.  Ordering, packing and the cluster bounds happen once, over the whole upload, in gsr_upload_end.)
-    hipError_t e = hipSuccess;
-    auto h2d = [&](void* d, const void* h, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, us); };
-    h2d(A.P + 3 * at, P, (size_t)n * 12); h2d(A.alpha + at, alpha, (size_t)n * 4); h2d(A.Cd + 3 * at, Cd, (size_t)n * 6);
-    h2d(A.scale + 3 * at, scale, (size_t)n * 6); h2d(A.orient + 4 * at, orient, (size_t)n * 8);
-    if (c->has_sh) { h2d(A.shx + 16 * at, shx, (size_t)n * 32); h2d(A.shy + 16 * at, shy, (size_t)n * 32); h2d(A.shz + 16 * at, shz, (size_t)n * 32); }
-    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be freed on return
+    // The entry lands behind the ones before it, in upload order.  (Ordering, packing and the cluster bounds happen once, over the whole
+    // upload, in gsr_upload_end.)
+    const hipError_t e = stage_host_rows(A, at, n, GsrPackSrc{P, alpha, Cd, scale, orient, shx, shy, shz}, c->has_sh, us);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_append: %s", hipGetErrorString(e));
     c->up_filled += n;
     c->up_h2d_ms += up_now_ms() - t0;
@@ -885,6 +916,8 @@ static void drop_geometry(gsr_context* c)
         sl.hints.surv_hint = 0; sl.hints.kept_hint = 0; sl.hints.kept_lo = sl.hints.kept_hi = 0;
     }
 }
+// gsr_multi_remove: ranks that disagree keep nothing
+__attribute__((visibility("hidden"))) void gsr_internal_drop_geometry(gsr_context* c) { if (c) drop_geometry(c); }
 
 extern "C" int gsr_upload_append_raw(gsr_context* c, int64_t n64, const gsr_raw_attrs* a)
 {
@@ -903,24 +936,16 @@ extern "C" int gsr_upload_append_raw(gsr_context* c, int64_t n64, const gsr_raw_
     const size_t at = c->up_filled;
     hipStream_t us = c->slot[0].own;
     const UpArena A = up_arena(c->stage, c->up_total, c->has_sh);
-    const size_t al = 256;
-    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
     // the raw float arrays of THIS entry: their own scratch (kept between calls), quantised into the arena behind the entries before it
     const int nsh = a->sh_scheme == 2 ? 15 : (a->sh_scheme == 3 ? 45 : 0);
     int sh_live = 0;                 // schemes 2 / 3: the arrays before the first gap
     if (nsh) while (sh_live < nsh && a->sh_ptr[sh_live]) ++sh_live;
-    const size_t rC = a->Cd ? pad((size_t)n * 12) : 0, rS = a->scale ? pad((size_t)n * 12) : 0, rO = a->orient ? pad((size_t)n * 16) : 0;
-    const size_t rArr = a->sh_scheme == 1 ? pad((size_t)n * std::min(a->sh_vec3_per_point, 16) * 12) : 0;
-    const size_t rEach = a->sh_scheme == 2 ? pad((size_t)n * 12) : (a->sh_scheme == 3 ? pad((size_t)n * 4) : 0);
-    const size_t need = rC + rS + rO + rArr + rEach * sh_live + al;
-    if (need > c->stage_raw_cap) {
-        HIP_TRY(hipStreamSynchronize(us));
-        dev_free(c->stage_raw);
-        c->stage_raw_cap = 0;
-        int rc = dev_alloc(&c->stage_raw, need);
-        if (rc) return rc;
-        c->stage_raw_cap = need;
-    }
+    const size_t rC = a->Cd ? pad256((size_t)n * 12) : 0, rS = a->scale ? pad256((size_t)n * 12) : 0, rO = a->orient ? pad256((size_t)n * 16) : 0;
+    const size_t rArr = a->sh_scheme == 1 ? pad256((size_t)n * std::min(a->sh_vec3_per_point, 16) * 12) : 0;
+    const size_t rEach = a->sh_scheme == 2 ? pad256((size_t)n * 12) : (a->sh_scheme == 3 ? pad256((size_t)n * 4) : 0);
+    const size_t need = rC + rS + rO + rArr + rEach * sh_live + 256;
+    int rc = GSR_OK;
+    if (need > c->stage_raw_cap && (rc = regrow(us, c->stage_raw, c->stage_raw_cap, need, need))) return rc;
     char* base = c->stage_raw;
     auto take = [&](size_t bytes) { char* p = base; base += bytes; return p; };
     hipError_t e = hipSuccess;
@@ -958,13 +983,11 @@ extern "C" int gsr_upload_append_raw(gsr_context* c, int64_t n64, const gsr_raw_
     return GSR_OK;
 }
 
-// A new cloud is resident (the end of an upload, or of a move: the same splats at other positions are a new cloud to everything a
-// frame keeps): a new generation, and nothing the frames of the cloud before learned survives.
-static int new_cloud_state(gsr_context* c, const char* who)
+// What the frames of a cloud learned about it -- prefixes, the tile order's verdict, policies, hints, horizons -- goes: behind a new
+// cloud, and behind an edit that changes the shape of the resident one (after_update).  e: the state of the call so far -- the device
+// word is reset (on `us`, and waited for) only behind a success, and the first failure is what comes back.
+static hipError_t forget_frame_learning(gsr_context* c, hipStream_t us, hipError_t e)
 {
-    c->geo_gen++;
-    c->has_geometry = true;
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
     c->prefix_valid = false;           // lazy colour: the first frame of a new cloud colours every list completely
     c->order_pays = false;
     c->cull_pol.on_upload(); c->slab_pol.on_upload();
@@ -975,8 +998,18 @@ static int new_cloud_state(gsr_context* c, const char* who)
     }
     c->lazy_pays = false;              // ... and in automatic mode the first frames are eager until the kernels say it pays
     // (the kernels' verdicts on the last frame of the PREVIOUS cloud must not reach the first frame of this one through the device word)
-    if (c->lazy_hint && hipMemsetAsync(c->lazy_hint, 0, 4, c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "%s: could not reset the policy word", who);
-    if (c->lazy_hint && hipStreamSynchronize(c->slot[0].own) != hipSuccess) return set_err(GSR_E_HIP, "%s: could not reset the policy word", who);
+    if (e == hipSuccess && c->lazy_hint) e = hipMemsetAsync(c->lazy_hint, 0, 4, us);
+    if (e == hipSuccess && c->lazy_hint) e = hipStreamSynchronize(us);
+    return e;
+}
+// A new cloud is resident (the end of an upload, or of a move: the same splats at other positions are a new cloud to everything a
+// frame keeps): a new generation, and nothing the frames of the cloud before learned survives.
+static int new_cloud_state(gsr_context* c, const char* who)
+{
+    c->geo_gen++;
+    c->has_geometry = true;
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
+    if (forget_frame_learning(c, c->slot[0].own, hipSuccess) != hipSuccess) return set_err(GSR_E_HIP, "%s: could not reset the policy word", who);
     return GSR_OK;
 }
 
@@ -1236,8 +1269,7 @@ static int order_and_pack(gsr_context* c)
     hipStream_t us = sl.stream;
     int rc = GSR_OK;
     const UpArena A = up_arena(c->stage, c->up_total, c->has_sh);
-    for (int k = 0; k < 4; ++k)
-        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
+    if ((rc = ensure_up_events(c, 4, "gsr_upload_end", true))) return rc;
     HIP_TRY(hipEventRecord(c->up_ev[0], us));
     if ((rc = position_box(c, A.P, n, us, "gsr_upload_end"))) return rc;
     // the storage order: perm[j] = upload index of the splat in slot j (NULL: upload order)
@@ -1259,10 +1291,9 @@ static int order_and_pack(gsr_context* c)
     dev_free(c->clusA); dev_free(c->clusB);
     if ((rc = dev_alloc(&c->clusA, c->nclus)) || (rc = dev_alloc(&c->clusB, c->nclus))) return rc;
     const GsrPackSrc src{A.P, A.alpha, A.Cd, A.scale, A.orient, A.shx, A.shy, A.shz};
-    if (c->has_sh)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<true>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, src, c->perm, c->geoA, c->geoB, c->col, c->colrow, c->clusA, c->clusB);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<false>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, src, c->perm, c->geoA, c->geoB, c->col, c->colrow, c->clusA, c->clusB);
+    launch_sh(c->has_sh, [&](auto sh) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<decltype(sh)::value>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, src, c->perm, c->geoA, c->geoB, c->col, c->colrow, c->clusA, c->clusB);
+    });
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);
@@ -1286,456 +1317,30 @@ static int ensure_inverse_perm(gsr_context* c)
     return GSR_OK;
 }
 
-// What the resident cloud's frames may keep after an attribute update (the invalidation table).  The cached depth orders go
-// in every case: their records hold the colours.  Colours change neither visibility, order nor opacity: horizons, prefixes, hints and
-// policies survive a Cd / SH update; anything else (`shape`: alpha, scale or orient changed) is treated like a new cloud at the same
-// positions.  e: the state of the call so far; the first failure is what comes back.
-static hipError_t after_update(gsr_context* c, bool shape, hipStream_t us, hipError_t e)
+// The kernels that rewrite resident planes in place or into the spare set, behind the <SH> dispatch; the verbs that launch them are in
+// gsr_resident_edit.h.  k_update / k_update_f32 on `us`: rows [first, first + n) from src, through the storage order's inverse (NULL:
+// upload order)
+static void launch_update(gsr_context* c, hipStream_t us, uint32_t first, uint32_t n, const GsrUpdateSrc& src, const uint32_t* inv)
 {
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
-    if (shape) {
-        c->prefix_valid = false;
-        c->order_pays = false;
-        c->cull_pol.on_upload(); c->slab_pol.on_upload();
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
-            GsrSlotHints& h = c->slot[k].hints;
-            h.surv_hint = 0; h.kept_hint = 0; h.kept_lo = h.kept_hi = 0; h.slab_kept1 = h.slab_kept2 = 0;
-            c->slot[k].horizon_valid = false; c->slot[k].local_pol.on_upload();
-        }
-        c->lazy_pays = false;
-        if (e == hipSuccess && c->lazy_hint) e = hipMemsetAsync(c->lazy_hint, 0, 4, us);
-        if (e == hipSuccess && c->lazy_hint) e = hipStreamSynchronize(us);
-    }
-    return e;
-}
-
-// ---------------------------------------------------------------------------
-// Attributes of resident splats rewritten in place ("Attribute updates").  No position: the storage order, the bounding
-// box, the Morton scratch and the cluster boxes' xyz depend on P alone and stay as they are.
-// vis_rule: with a visibility in force and new alphas, put them aside AND apply the rule (gsr_update); false: put them aside only (the
-// attribute step of a move, which applies the rule itself once the splats sit at their new positions, in the new order)
-static int update_rows(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u, bool vis_rule)
-{
-    if (!c || !u) return set_err(GSR_E_INVALID, "gsr_update: NULL argument");
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_update: upload in progress");
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_update: no geometry: nothing uploaded");
-    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
-        return set_err(GSR_E_INVALID, "gsr_update: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
-    const int nsh = (u->shx ? 1 : 0) + (u->shy ? 1 : 0) + (u->shz ? 1 : 0);
-    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_update: the three SH arrays come together or not at all");
-    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_update: SH arrays for a cloud uploaded without SH");
-    if (n64 == 0 || !(u->Cd || u->alpha || u->scale || u->orient || nsh)) return GSR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);      // no in-place write under a frame in flight (two frames in flight, deferred-check frames included)
-    if (rc) return rc;
-    const uint32_t n = (uint32_t)n64;
-    hipStream_t us = c->slot[0].own;
-    // the given arrays, rows [0, n), in the upload arena (kept between uploads and updates; grown only when too small)
-    const size_t al = 256;
-    size_t off = 0;
-    auto place = [&](const void* given, size_t bytes) { const size_t at = off; if (given) off += (bytes + al - 1) / al * al; return at; };
-    const size_t oA = place(u->alpha, (size_t)n * 4), oC = place(u->Cd, (size_t)n * 6), oS = place(u->scale, (size_t)n * 6), oO = place(u->orient, (size_t)n * 8);
-    const size_t oX = place(u->shx, (size_t)n * 32), oY = place(u->shy, (size_t)n * 32), oZ = place(u->shz, (size_t)n * 32);
-    if (off > c->stage_cap) {
-        dev_free(c->stage);
-        c->stage_cap = 0;
-        if ((rc = dev_alloc(&c->stage, off + 256))) return rc;
-        c->stage_cap = off + 256;
-    }
-    if ((rc = ensure_inverse_perm(c))) return rc;
-    for (int k = 0; k < 2; ++k)
-        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
-    const double t0 = up_now_ms();
-    char* const base = c->stage;
-    hipError_t e = hipSuccess;
-    auto h2d = [&](size_t at, const void* h, size_t bytes) { if (h && e == hipSuccess) e = hipMemcpyAsync(base + at, h, bytes, hipMemcpyHostToDevice, us); };
-    h2d(oA, u->alpha, (size_t)n * 4); h2d(oC, u->Cd, (size_t)n * 6); h2d(oS, u->scale, (size_t)n * 6); h2d(oO, u->orient, (size_t)n * 8);
-    h2d(oX, u->shx, (size_t)n * 32); h2d(oY, u->shy, (size_t)n * 32); h2d(oZ, u->shz, (size_t)n * 32);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be freed on return
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_update: %s", hipGetErrorString(e));
-    const double h2d_ms = up_now_ms() - t0;
-    auto dev = [&](const void* given, size_t at) { return given ? base + at : (char*)nullptr; };
-    GsrUpdateSrc src;
-    src.alpha = reinterpret_cast<const float*>(dev(u->alpha, oA));
-    src.Cd = reinterpret_cast<const uint16_t*>(dev(u->Cd, oC)); src.scale = reinterpret_cast<const uint16_t*>(dev(u->scale, oS));
-    src.orient = reinterpret_cast<const uint16_t*>(dev(u->orient, oO)); src.shx = reinterpret_cast<const uint16_t*>(dev(u->shx, oX));
-    src.shy = reinterpret_cast<const uint16_t*>(dev(u->shy, oY)); src.shz = reinterpret_cast<const uint16_t*>(dev(u->shz, oZ));
-    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    const bool extents = u->scale || u->orient;
-    e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess) {
-        if (c->has_sh)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update<true>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update<false>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
-        // (the bounds of ALL clusters: a Morton-ordered store scatters the range over them, and the pass reads 32 bytes per splat)
-        if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
-        e = hipGetLastError();
-        // a visibility in force: the new alphas are put aside, and the hidden ones among them go back to +0.0f (a move does that itself)
-        if (e == hipSuccess && c->vis_on && u->alpha) e = vis_apply(c, us, (uint32_t)first, n, vis_rule, c->vis, c->vis_mask, nullptr);
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);
-    e = after_update(c, u->alpha || extents, us, e);
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_update: %s", hipGetErrorString(e));
-    float ms = 0.0f;
-    c->st.upload_ms[4] = h2d_ms;
-    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
-    return GSR_OK;
-}
-
-extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_attr_update* u)
-{
-    return update_rows(c, first, n64, u, true);
-}
-
-// ---------------------------------------------------------------------------
-// What gsr_move and gsr_remove share around k_repack.  The SPARE copy of the planes (at the capacity) and of the cluster bounds (at the
-// cluster count in force: a removal only ever needs fewer): allocated at the first call that writes a new storage order, kept until the
-// geometry is freed.  A failure leaves no half of a set behind.
-static int ensure_spare_planes(gsr_context* c)
-{
-    int rc = GSR_OK;
-    const size_t cap = c->cap;
-    if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
-                      (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
-        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-        return rc;
-    }
-    if (!c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
-        dev_free(c->clusA2); dev_free(c->clusB2);
-        return rc;
-    }
-    return GSR_OK;
-}
-// The sort of a new storage order over n splats, provided for before the first write: the Morton scratch, slot 0's histogram, and the
-// new permutation (*perm_new: the caller's, freed by it on every later failure)
-static int ensure_order_buffers(gsr_context* c, uint32_t n, uint32_t** perm_new, const char* who)
-{
-    FrameSlot& sl = c->slot[0];
-    int rc = GSR_OK;
-    if (!ensure_order_scratch(c, n)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
-    if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
-    return dev_alloc(perm_new, (size_t)n);
+    launch_sh(c->has_sh, [&](auto sh) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+    });
 }
 // k_repack on `us`: the n splats of the new order perm_new (NULL: upload order) from the slots old_slot names (upload index -> resident
 // slot; NULL: upload order) into the spare planes, with the bounds of their clusters
 static hipError_t queue_repack(gsr_context* c, hipStream_t us, uint32_t n, const uint32_t* perm_new, const uint32_t* old_slot)
 {
-    const dim3 grid(div_up(n, GSR_CLUSTER)), block(GSR_PACK_THREADS);
-    if (c->has_sh)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<true>), grid, block, 0, us, n, c->cap, perm_new, old_slot, c->geoA, c->geoB, c->col, c->colrow,
-                           c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<false>), grid, block, 0, us, n, c->cap, perm_new, old_slot, c->geoA, c->geoB, c->col, c->colrow,
-                           c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+    launch_sh(c->has_sh, [&](auto sh) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, old_slot,
+                           c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
+    });
     return hipGetLastError();
 }
-// ... and the swap behind it: the spare set becomes the resident one, under the storage order perm_new (taken over; NULL: upload order).
-// Nothing is in flight, and every frame takes the planes from the context.
-static void swap_planes(gsr_context* c, uint32_t*& perm_new)
+static void launch_update(gsr_context* c, hipStream_t us, uint32_t first, uint32_t n, const GsrUpdateSrcF32& src, const uint32_t* inv)
 {
-    std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
-    std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
-    dev_free(c->perm);
-    c->perm = perm_new;
-    perm_new = nullptr;
-}
-
-// ---------------------------------------------------------------------------
-// The body of gsr_move and gsr_move_device, behind their refusals.  new_bytes: what the new rows take at the head of the arena (0: they
-// stay in the caller's device memory); upd_bytes: what the attribute step stages there; attr_step(): the update verb for the same rows
-// (attrs: whether there is one; it leaves its link time in upload_ms[4]); new_rows(arena, stream, &Pnew, &h2d_ms): the device pointer
-// of the new rows, after whatever copy brings them there.
-template <class AttrStep, class NewRows>
-static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64, const float origin[3], size_t new_bytes, size_t upd_bytes,
-                     bool attrs, AttrStep&& attr_step, NewRows&& new_rows)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    const double t_begin = up_now_ms();
-    int rc = sync_all(c);      // no write under a frame in flight
-    if (rc) return rc;
-    const uint32_t n = c->n, cnt = (uint32_t)n64;
-    FrameSlot& sl = c->slot[0];
-    hipStream_t us = sl.stream;
-    // ---- everything the call needs, before the first write: an allocation failure leaves the context as it was
-    // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
-    const bool may_order = c->opt_morton && n > 1;
-    const size_t al = 256;
-    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
-    const size_t oNew = 0, oAll = pad(new_bytes), need = std::max(oAll + pad((size_t)n * 12), upd_bytes);
-    if (need > c->stage_cap) {
-        dev_free(c->stage);
-        c->stage_cap = 0;
-        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
-        c->stage_cap = need + 256;
-    }
-    uint32_t* perm_new = nullptr;
-    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
-    if (may_order && (rc = ensure_order_buffers(c, n, &perm_new, who))) return rc;
-    if ((may_order || c->perm) && (rc = ensure_spare_planes(c))) { dev_free(perm_new); return rc; }
-    if ((rc = ensure_inverse_perm(c))) { dev_free(perm_new); return rc; }      // (the OLD order's inverse; built on slot 0's own stream)
-    for (int k = 0; k < 3; ++k)
-        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "%s: no event", who); }
-    if (hipStreamSynchronize(sl.own) != hipSuccess) { dev_free(perm_new); return set_err(GSR_E_HIP, "%s: the inverse of the storage order", who); }
-    // ---- from here on a failure leaves no geometry (as a failed gsr_upload_end does)
-    auto lost = [&](int code) { dev_free(perm_new); drop_geometry(c); return code; };
-    double h2d_ms = 0.0;
-    // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
-    if (attrs) {
-        rc = attr_step();              // (a visibility in force: the step puts new alphas aside; the rule is applied below, at the new positions)
-        // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
-        //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
-        if (rc == GSR_E_HIP) return lost(rc);
-        if (rc) { dev_free(perm_new); return rc; }     // (refused before its first write)
-        h2d_ms = c->st.upload_ms[4];
-    }
-    // 2. the new rows where the splats sit now, and every position in upload order
-    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
-    const float* Pnew = nullptr;       // the new rows, in device memory
-    hipError_t e = new_rows(reinterpret_cast<float*>(c->stage + oNew), us, &Pnew, &h2d_ms);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, us, (uint32_t)first, cnt, n, Pnew, inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    // 3. the ordering of an upload
-    if ((rc = position_box(c, Pall, n, us, who))) return lost(rc);
-    const bool ordered = may_order && c->bbox_ok;
-    if (ordered && (rc = morton_order(c, Pall, n, perm_new, who))) return lost(rc);
-    if (!ordered) dev_free(perm_new);
-    e = hipEventRecord(c->up_ev[1], us);
-    // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
-    if (e == hipSuccess) {
-        if (perm_new || c->perm) {
-            e = queue_repack(c, us, n, perm_new, inv_old);
-        } else {
-            hipLaunchKernelGGL(k_cluster_bounds, dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->geoA, c->geoB, c->clusA, c->clusB);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    // 5. the swap: nothing is in flight, and every frame takes the planes from the context
-    if (perm_new || c->perm) swap_planes(c, perm_new);
-    c->h_perm.clear();
-    if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
-    // 6. a visibility in force: the volumes against the positions the splats have now, in the order they sit in now
-    if (c->vis_on && (e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess)
-        return lost(set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e)));
-    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }   // (the policy word could not be reset: a HIP failure like any other)
-    c->st.moves += 1;
-    float ms = 0.0f;
-    c->st.move_ms[0] = h2d_ms;
-    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.move_ms[1] = ms;
-    if (hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess) c->st.move_ms[2] = ms;
-    c->st.move_ms[3] = up_now_ms() - t_begin;
-    return GSR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// New positions for resident splats ("Position updates").  Only the P rows cross the link; the ordering of an upload runs
-// over all positions (formed on the device in upload order), and k_repack carries the resident planes into the new storage order,
-// into a spare copy that is then swapped in.  Everything is allocated before the first write to resident memory.
-extern "C" int gsr_move(gsr_context* c, int64_t first, int64_t n64, const float* P, const float origin[3], const gsr_attr_update* u)
-{
-    if (!c || !P) return set_err(GSR_E_INVALID, "gsr_move: NULL argument");
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_move: upload in progress");
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_move: no geometry: nothing uploaded");
-    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
-        return set_err(GSR_E_INVALID, "gsr_move: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
-    const int nsh = u ? (u->shx ? 1 : 0) + (u->shy ? 1 : 0) + (u->shz ? 1 : 0) : 0;
-    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_move: the three SH arrays come together or not at all");
-    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_move: SH arrays for a cloud uploaded without SH");
-    if (n64 == 0) return GSR_OK;
-    const bool attrs = u && (u->Cd || u->alpha || u->scale || u->orient || nsh);
-    const size_t al = 256;
-    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
-    const size_t cnt = (size_t)n64;
-    size_t upd_bytes = 0;      // what gsr_update stages of u (its own layout), so that it does not grow the arena behind this call's back
-    if (attrs)
-        upd_bytes = (u->alpha ? pad(cnt * 4) : 0) + (u->Cd ? pad(cnt * 6) : 0) + (u->scale ? pad(cnt * 6) : 0) +
-                    (u->orient ? pad(cnt * 8) : 0) + (nsh ? 3 * pad(cnt * 32) : 0);
-    return move_body(c, "gsr_move", first, n64, origin, cnt * 12, upd_bytes, attrs,
-                     [&]() { return update_rows(c, first, n64, u, false); },
-                     [&](float* arena, hipStream_t us, const float** Pnew, double* h2d_ms) {
-                         const double t0 = up_now_ms();
-                         hipError_t e = hipMemcpyAsync(arena, P, cnt * 12, hipMemcpyHostToDevice, us);
-                         if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's array may be freed on return
-                         *h2d_ms += up_now_ms() - t0;
-                         *Pnew = arena;
-                         return e;
-                     });
-}
-
-// ---------------------------------------------------------------------------
-// Device sources ("Device sources"): upload, update and move from float32 arrays that already sit in device memory.
-// What the three verbs ask of a source pointer, before anything is written or launched -- a wrong pointer must never be found out by
-// a kernel: 4-byte aligned; device memory of the context's device, or pinned host memory; and, where the runtime reports the
-// allocation's range, every byte inside it.  Pageable host memory fails the attribute query or comes back "unregistered", depending
-// on the ROCm version: both are refused, and the runtime's sticky error is cleared.
-static int check_device_source(gsr_context* c, const void* p, size_t bytes, const char* who, const char* name)
-{
-    if (reinterpret_cast<uintptr_t>(p) & 3u) return set_err(GSR_E_INVALID, "%s: %s is not 4-byte aligned", who, name);
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return set_err(GSR_E_INVALID, "%s: %s is not device memory (the runtime does not know the pointer)", who, name);
-    }
-    if (at.type == hipMemoryTypeDevice) {
-        if (at.device != c->device) return set_err(GSR_E_INVALID, "%s: %s is memory of device %d, the context renders on device %d", who, name, at.device, c->device);
-    } else if (at.type != hipMemoryTypeHost) {      // (host = pinned: hipHostMalloc, hipHostRegister)
-        return set_err(GSR_E_INVALID, "%s: %s is neither device memory nor pinned host memory (memory type %d)", who, name, (int)at.type);
-    }
-    void* base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(reinterpret_cast<hipDeviceptr_t*>(&base), &size, reinterpret_cast<hipDeviceptr_t>(const_cast<void*>(p))) != hipSuccess) {
-        (void)hipGetLastError();                     // (no range on record: the type is what there is to go by)
-        return GSR_OK;
-    }
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), at_p = reinterpret_cast<uintptr_t>(p);
-    if (at_p < lo || at_p - lo > size || bytes > size - (at_p - lo))
-        return set_err(GSR_E_INVALID, "%s: %s: %zu bytes from the pointer reach past the end of its allocation (%zu bytes left)", who, name, bytes,
-                       at_p >= lo && at_p - lo <= size ? size - (at_p - lo) : (size_t)0);
-    return GSR_OK;
-}
-
-extern "C" int gsr_debug_check_device_source(gsr_context* c, const void* p, int64_t bytes)
-{
-    if (!c || !p || bytes < 0) return set_err(GSR_E_INVALID, "gsr_debug_check_device_source: bad argument");
-    return check_device_source(c, p, (size_t)bytes, "gsr_debug_check_device_source", "the pointer");
-}
-
-// every non-NULL array of a, for n rows (sh_vec3_per_point is in range when sh is given: the callers looked)
-static int check_device_attrs(gsr_context* c, const gsr_device_attrs* a, size_t n, const char* who)
-{
-    int rc = GSR_OK;
-    auto look = [&](const float* p, size_t floats_per_row, const char* name) {
-        if (p && !rc) rc = check_device_source(c, p, n * floats_per_row * 4, who, name);
-    };
-    look(a->P, 3, "P"); look(a->Cd, 3, "Cd"); look(a->alpha, 1, "alpha"); look(a->scale, 3, "scale"); look(a->orient, 4, "orient");
-    look(a->sh, a->sh ? (size_t)a->sh_vec3_per_point * 3 : 0, "sh");
-    return rc;
-}
-
-extern "C" int gsr_upload_append_device(gsr_context* c, int64_t n64, const gsr_device_attrs* a)
-{
-    if (!c || !c->uploading) return set_err(GSR_E_INVALID, "gsr_upload_append_device: no upload in progress");
-    if (!a) return set_err(GSR_E_INVALID, "gsr_upload_append_device: attrs is NULL");
-    if (n64 < 0 || (uint64_t)n64 + c->up_filled > c->up_total)
-        return set_err(GSR_E_INVALID, "gsr_upload_append_device: %lld splats exceed the %u announced", (long long)n64, c->up_total);
-    if (n64 == 0) return GSR_OK;
-    if (!a->P) return set_err(GSR_E_INVALID, "gsr_upload_append_device: P is NULL");
-    if (c->has_sh != (a->sh != nullptr)) return set_err(GSR_E_INVALID, "gsr_upload_append_device: SH presence differs from gsr_upload_begin");
-    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
-        return set_err(GSR_E_INVALID, "gsr_upload_append_device: sh_vec3_per_point = %d is not within 1..16", a->sh_vec3_per_point);
-    const uint32_t n = (uint32_t)n64;
-    int rc = check_device_attrs(c, a, n, "gsr_upload_append_device");
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));          // a producer queued on the public stream has finished
-    const size_t at = c->up_filled;
-    hipStream_t us = c->slot[0].own;
-    const UpArena A = up_arena(c->stage, c->up_total, c->has_sh);
-    // P and alpha as they are, behind the entries before this one (the runtime picks the direction: a source may be pinned host memory);
-    // the rest is quantised straight from the caller's arrays
-    hipError_t e = hipMemcpyAsync(A.P + 3 * at, a->P, (size_t)n * 12, hipMemcpyDefault, us);
-    if (e == hipSuccess)
-        e = a->alpha ? hipMemcpyAsync(A.alpha + at, a->alpha, (size_t)n * 4, hipMemcpyDefault, us)
-                     : hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(A.alpha + at), 0x3f800000, n, us);      // missing opacity: opaque
-    if (e == hipSuccess) {
-        GsrRawSh sh{};
-        sh.scheme = a->sh ? 1 : 0;
-        sh.vec3_per_point = a->sh_vec3_per_point;
-        sh.array = a->sh;
-        hipLaunchKernelGGL(k_quantize_raw, dim3(div_up(n, 256)), dim3(256), 0, us, n, a->Cd, a->scale, a->orient, sh, A.Cd + 3 * at, A.scale + 3 * at, A.orient + 4 * at,
-                           c->has_sh ? A.shx + 16 * at : (uint16_t*)nullptr, c->has_sh ? A.shy + 16 * at : (uint16_t*)nullptr, c->has_sh ? A.shz + 16 * at : (uint16_t*)nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_append_device: %s", hipGetErrorString(e));
-    c->up_filled += n;
-    return GSR_OK;
-}
-
-// what gsr_update_device and gsr_move_device refuse of a before they look at its pointers (the range is the caller's to check first)
-static int refuse_device_update(gsr_context* c, const gsr_device_attrs* a, const char* who)
-{
-    if (a->sh && !c->has_sh) return set_err(GSR_E_INVALID, "%s: sh for a cloud uploaded without SH", who);
-    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
-        return set_err(GSR_E_INVALID, "%s: sh_vec3_per_point = %d is not within 1..16", who, a->sh_vec3_per_point);
-    return GSR_OK;
-}
-
-// gsr_update_device behind its refusals: gsr_update without the staging -- k_update_f32 reads the caller's rows where they are
-static int update_device_rows(gsr_context* c, int64_t first, uint32_t n, const gsr_device_attrs* a, const char* who, bool vis_rule /* as update_rows takes it */)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);      // the public stream (a producer queued there has finished), and no in-place write under a frame in flight
-    if (rc) return rc;
-    hipStream_t us = c->slot[0].own;
-    if ((rc = ensure_inverse_perm(c))) return rc;
-    for (int k = 0; k < 2; ++k)
-        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
-    const GsrUpdateSrcF32 src{a->alpha, a->Cd, a->scale, a->orient, a->sh, a->sh ? a->sh_vec3_per_point : 0};
-    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    const bool extents = a->scale || a->orient;
-    hipError_t e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess) {
-        if (c->has_sh)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<true>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<false>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, (uint32_t)first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
-        if (extents) hipLaunchKernelGGL(k_cluster_extents, dim3(div_up(c->nclus, 4)), dim3(256), 0, us, c->n, c->nclus, c->geoA, c->geoB, c->clusA, c->clusB);
-        e = hipGetLastError();
-        if (e == hipSuccess && c->vis_on && a->alpha) e = vis_apply(c, us, (uint32_t)first, n, vis_rule, c->vis, c->vis_mask, nullptr);   // (as in update_rows)
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
-    e = after_update(c, a->alpha || extents, us, e);
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    float ms = 0.0f;
-    c->st.upload_ms[4] = 0.0;  // nothing crossed the link
-    if (hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess) c->st.upload_ms[5] = ms;
-    return GSR_OK;
-}
-
-extern "C" int gsr_update_device(gsr_context* c, int64_t first, int64_t n64, const gsr_device_attrs* a)
-{
-    if (!c || !a) return set_err(GSR_E_INVALID, "gsr_update_device: NULL argument");
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_update_device: upload in progress");
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_update_device: no geometry: nothing uploaded");
-    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
-        return set_err(GSR_E_INVALID, "gsr_update_device: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
-    if (a->P) return set_err(GSR_E_INVALID, "gsr_update_device: P is given: a position is gsr_move_device");
-    int rc = refuse_device_update(c, a, "gsr_update_device");
-    if (rc) return rc;
-    if (n64 == 0 || !(a->Cd || a->alpha || a->scale || a->orient || a->sh)) return GSR_OK;
-    if ((rc = check_device_attrs(c, a, (size_t)n64, "gsr_update_device"))) return rc;
-    return update_device_rows(c, first, (uint32_t)n64, a, "gsr_update_device", true);
-}
-
-extern "C" int gsr_move_device(gsr_context* c, int64_t first, int64_t n64, const float origin[3], const gsr_device_attrs* a)
-{
-    if (!c || !a) return set_err(GSR_E_INVALID, "gsr_move_device: NULL argument");
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_move_device: upload in progress");
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_move_device: no geometry: nothing uploaded");
-    if (first < 0 || n64 < 0 || first > (int64_t)c->n || n64 > (int64_t)c->n - first)
-        return set_err(GSR_E_INVALID, "gsr_move_device: splats [%lld, %lld + %lld) are not within the %u resident", (long long)first, (long long)first, (long long)n64, c->n);
-    if (!a->P) return set_err(GSR_E_INVALID, "gsr_move_device: P is NULL");
-    int rc = refuse_device_update(c, a, "gsr_move_device");
-    if (rc) return rc;
-    if (n64 == 0) return GSR_OK;
-    if ((rc = check_device_attrs(c, a, (size_t)n64, "gsr_move_device"))) return rc;
-    const bool attrs = a->Cd || a->alpha || a->scale || a->orient || a->sh;
-    // (k_move_positions reads the caller's P where it is, and the attribute step stages nothing: the arena holds the positions in upload order only)
-    return move_body(c, "gsr_move_device", first, n64, origin, 0, 0, attrs,
-                     [&]() { return update_device_rows(c, first, (uint32_t)n64, a, "gsr_move_device", false); },
-                     [&](float*, hipStream_t, const float** Pnew, double*) { *Pnew = a->P; return hipSuccess; });
+    launch_sh(c->has_sh, [&](auto sh) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_f32<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, first, n, c->cap, src, inv, c->geoA, c->geoB, c->col, c->colrow);
+    });
 }
 
 // the resident geometry as it is stored (tests hold gsr_update to a fresh upload with it)
@@ -3723,612 +3328,6 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
 }
 
 // ---------------------------------------------------------------------------
-// Visibility (k_visibility.h): resident splats hidden by crop volumes or a mask.  The verb and three hooks -- behind a
-// complete upload, behind an alpha update, behind a move -- that run only while a visibility is in force.
-static_assert(sizeof(gsr_crop_volume) == sizeof(GsrVisVolume) && offsetof(gsr_visibility, mask) == sizeof(GsrVisRule) &&
-              offsetof(gsr_visibility, volume) == offsetof(GsrVisRule, vol) && GSR_VIS_MAX_VOLUMES == GSR_VIS_VOLUMES &&
-              GSR_VOL_BOX == GSR_VISK_BOX && GSR_VOL_ELLIPSOID == GSR_VISK_ELLIPSOID, "gsr_visibility begins with the kernel's rule");
-
-// what is wrong with the caller's struct (NULL: nothing; v == NULL is "everything visible")
-static const char* visibility_error(const gsr_visibility* v)
-{
-    if (!v) return nullptr;
-    if (v->n_volumes < 0 || v->n_volumes > GSR_VIS_MAX_VOLUMES) return "n_volumes is not within 0..GSR_VIS_MAX_VOLUMES";
-    if (v->reserved_ != 0) return "reserved_ is not 0";
-    for (int k = 0; k < v->n_volumes; ++k) {
-        if (v->volume[k].kind != GSR_VOL_BOX && v->volume[k].kind != GSR_VOL_ELLIPSOID) return "unknown volume kind";
-        if (v->volume[k].invert != 0 && v->volume[k].invert != 1) return "invert is neither 0 nor 1";
-    }
-    return nullptr;
-}
-// the rule of v as the kernel takes it (volumes beyond n_volumes zeroed)
-static GsrVisRule visibility_rule(const gsr_visibility* v)
-{
-    GsrVisRule r{};
-    if (v) {
-        r.n_volumes = v->n_volumes;
-        std::memcpy(r.vol, v->volume, sizeof(GsrVisVolume) * (size_t)v->n_volumes);
-    }
-    return r;
-}
-
-extern "C" int gsr_visibility_eval(const gsr_visibility* v, const float* P, int64_t first, int64_t n, uint8_t* visible_out)
-{
-    const char* bad = visibility_error(v);
-    if (bad) return set_err(GSR_E_INVALID, "gsr_visibility_eval: %s", bad);
-    if (first < 0 || n < 0 || (n > 0 && (!P || !visible_out))) return set_err(GSR_E_INVALID, "gsr_visibility_eval: bad argument");
-    const uint32_t* const mask = v ? v->mask : nullptr;
-    if (mask && (v->mask_splats < 0 || first > v->mask_splats || n > v->mask_splats - first))
-        return set_err(GSR_E_INVALID, "gsr_visibility_eval: splats [%lld, %lld + %lld) are not within the %lld of the mask", (long long)first, (long long)first,
-                       (long long)n, (long long)v->mask_splats);
-    const GsrVisRule rule = visibility_rule(v);
-    for (int64_t k = 0; k < n; ++k) {
-        const uint64_t i = (uint64_t)(first + k);
-        visible_out[k] = gsr_splat_visible(rule, P[3 * k], P[3 * k + 1], P[3 * k + 2], mask ? mask[i >> 5] : 0u, (uint32_t)(i & 31u)) ? 1 : 0;
-    }
-    return GSR_OK;
-}
-
-// room for the true alphas and the counters: before the first write of whoever applies the rule
-static int vis_ensure_buffers(gsr_context* c)
-{
-    int rc = GSR_OK;
-    if (!c->alpha0 && (rc = dev_alloc(&c->alpha0, (size_t)c->cap))) return rc;
-    const size_t words = (size_t)GSR_VIS_COUNTER_SLOTS * GSR_VIS_COUNTER_STRIDE;
-    if (!c->vis_counters && (rc = dev_alloc(&c->vis_counters, words))) return rc;
-    if (!c->vis_h_counters && hipHostMalloc(reinterpret_cast<void**>(&c->vis_h_counters), words * 8, 0) != hipSuccess) {
-        c->vis_h_counters = nullptr;
-        (void)hipGetLastError();
-        return set_err(GSR_E_OOM, "no pinned host memory for the visibility counters");
-    }
-    return GSR_OK;
-}
-
-// On `us`: the true alphas of the splats [cap_first, cap_first + cap_cnt) (upload order; geoA holds them; 0: none) into alpha0 -- through
-// the inverse of the storage order, which the caller has ensured -- then, with `apply`, the rule over every storage slot.  Waits for
-// the counters: *changed = a resident bit changed, c->vis_hidden = what is hidden now.
-static hipError_t vis_apply(gsr_context* c, hipStream_t us, uint32_t cap_first, uint32_t cap_cnt, bool apply, const GsrVisRule& rule,
-                            const uint32_t* mask, bool* changed)
-{
-    const uint32_t n = c->n;
-    if (changed) *changed = false;
-    if (n == 0) { c->vis_hidden = 0; return hipSuccess; }
-    if (!c->alpha0 || !c->vis_counters || !c->vis_h_counters) return hipErrorInvalidValue;       // (the callers allocate before their first write)
-    if (cap_cnt) hipLaunchKernelGGL(k_alpha_capture, dim3(div_up(cap_cnt, 256)), dim3(256), 0, us, cap_first, cap_cnt,
-                                    c->perm ? c->wire_inv : (const uint32_t*)nullptr, c->geoA, c->alpha0);
-    if (!apply) return hipGetLastError();
-    const size_t words = (size_t)GSR_VIS_COUNTER_SLOTS * GSR_VIS_COUNTER_STRIDE;
-    hipError_t e = hipMemsetAsync(c->vis_counters, 0, words * 8, us);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_visibility, dim3(div_up(n, 256)), dim3(256), 0, us, n, c->perm, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, c->alpha0,
-                       mask, rule, c->vis_counters);
-    e = hipGetLastError();
-    const unsigned long long* const h = c->vis_h_counters;
-    if (e == hipSuccess) e = hipMemcpyAsync(c->vis_h_counters, c->vis_counters, words * 8, hipMemcpyDeviceToHost, us);
-    if (e == hipSuccess) e = hipStreamSynchronize(us);
-    if (e != hipSuccess) return e;
-    unsigned long long n_hidden = 0, n_changed = 0;        // (a slot's words cannot carry: each counts at most n <= 2^31 splats)
-    for (size_t k = 0; k < words; k += GSR_VIS_COUNTER_STRIDE) { n_hidden += h[k] & 0xffffffffull; n_changed += h[k] >> 32; }
-    c->vis_hidden = (int64_t)n_hidden;
-    if (changed) *changed = n_changed != 0;
-    return hipSuccess;
-}
-
-// behind a complete upload (the generation is the new cloud's): its mask is gone; the volumes in force hide their share of it
-static int vis_after_upload(gsr_context* c)
-{
-    vis_drop_mask(c);
-    c->vis_hidden = 0;
-    if (!c->vis_on || c->n == 0) return GSR_OK;
-    int rc = vis_ensure_buffers(c);
-    if (!rc) rc = ensure_inverse_perm(c);
-    if (rc) return rc;
-    const hipError_t e = vis_apply(c, c->slot[0].own, 0u, c->n, true, c->vis, nullptr, nullptr);
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_upload_end: applying the visibility: %s", hipGetErrorString(e));
-    return GSR_OK;
-}
-
-extern "C" int gsr_set_visibility(gsr_context* c, const gsr_visibility* v)
-{
-    if (!c) return set_err(GSR_E_INVALID, "gsr_set_visibility: ctx is NULL");
-    const char* bad = visibility_error(v);
-    if (bad) return set_err(GSR_E_INVALID, "gsr_set_visibility: %s", bad);
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_set_visibility: upload in progress");
-    const bool has_mask = v && v->mask;
-    if (has_mask && !c->has_geometry) return set_err(GSR_E_INVALID, "gsr_set_visibility: a mask belongs to a cloud, and none is resident");
-    if (has_mask && v->mask_splats != (int64_t)c->n)
-        return set_err(GSR_E_INVALID, "gsr_set_visibility: the mask covers %lld splats, %u are resident", (long long)v->mask_splats, c->n);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);      // no in-place write under a frame in flight
-    if (rc) return rc;
-    const GsrVisRule rule = visibility_rule(v);
-    if (!c->has_geometry || c->n == 0) {               // nothing to hide yet: the volumes wait for gsr_upload_end
-        dev_free(c->vis_mask);
-        c->vis = rule; c->vis_on = rule.n_volumes > 0; c->vis_hidden = 0;
-        return GSR_OK;
-    }
-    const bool on = rule.n_volumes > 0 || has_mask;
-    if (!on && !c->vis_on) return GSR_OK;              // everything is visible already
-    // ---- everything the call needs, before the first write
-    if ((rc = vis_ensure_buffers(c))) return rc;
-    const size_t words = ((size_t)c->n + 31) / 32;
-    uint32_t* mask_new = nullptr;
-    if (has_mask && (rc = dev_alloc(&mask_new, words))) return rc;
-    // (geoA holds every true alpha exactly while no visibility is in force: that is when they are put aside)
-    const bool capture = !c->vis_on;
-    if (capture && (rc = ensure_inverse_perm(c))) { dev_free(mask_new); return rc; }
-    hipStream_t us = c->slot[0].own;
-    hipError_t e = has_mask ? hipMemcpyAsync(mask_new, v->mask, words * 4, hipMemcpyHostToDevice, us) : hipSuccess;
-    if (e != hipSuccess) { dev_free(mask_new); return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e)); }
-    // ---- from here on a failure leaves no geometry (as a failed gsr_move does), and no visibility
-    bool changed = false;
-    e = vis_apply(c, us, 0u, capture ? c->n : 0u, true, rule, mask_new, &changed);
-    // a change of the hidden set is a shape edit, like new alphas: horizons, prefixes, hints and policies of the cloud's frames go
-    if (e == hipSuccess && changed) e = after_update(c, true, us, e);
-    if (e != hipSuccess) {
-        dev_free(mask_new);
-        c->vis = GsrVisRule{}; c->vis_on = false;
-        drop_geometry(c);
-        return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e));
-    }
-    dev_free(c->vis_mask);
-    c->vis_mask = mask_new;
-    c->vis = rule;
-    c->vis_on = on;
-    return GSR_OK;
-}
-
-extern "C" int gsr_get_visibility(gsr_context* c, gsr_visibility* out, int64_t* hidden)
-{
-    if (!c) return set_err(GSR_E_INVALID, "gsr_get_visibility: ctx is NULL");
-    if (out) {
-        std::memset(out, 0, sizeof(*out));
-        std::memcpy(out, &c->vis, sizeof(GsrVisRule));
-        out->mask_splats = c->vis_mask ? (int64_t)c->n : 0;
-    }
-    if (hidden) *hidden = c->vis_hidden;
-    return GSR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Removal (k_remove.h): resident splats deleted on the GPU.  A move whose source is a subset: mark, scan and compact in
-// upload order, then the ordering of an upload over the survivors' positions, k_repack into the spare planes, the swap.
-extern "C" int gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_index, int64_t* n_left)
-{
-    if (n < 0 || n > 0x7fffffffll || (n > 0 && !mask)) return set_err(GSR_E_INVALID, "gsr_remove_map: bad argument");
-    int64_t left = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        const bool gone = ((mask[i >> 5] >> (i & 31)) & 1u) != 0u;
-        if (new_index) new_index[i] = gone ? -1 : (int32_t)left;
-        if (!gone) ++left;
-    }
-    if (n_left) *n_left = left;
-    return GSR_OK;
-}
-
-extern "C" int gsr_get_removal(gsr_context* c, int64_t* removals, int64_t* removed_last, double ms[4])
-{
-    if (!c) return set_err(GSR_E_INVALID, "gsr_get_removal: ctx is NULL");
-    if (removals) *removals = c->rm_calls;
-    if (removed_last) *removed_last = c->rm_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->rm_ms[k];
-    return GSR_OK;
-}
-
-// gsr_multi_remove: ranks that disagree keep nothing
-__attribute__((visibility("hidden"))) void gsr_internal_drop_geometry(gsr_context* c) { if (c) drop_geometry(c); }
-
-extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_device, int flags, int64_t* n_left)
-{
-    const char* const who = "gsr_remove";
-    if (!c) return set_err(GSR_E_INVALID, "gsr_remove: ctx is NULL");
-    if (flags & ~GSR_REMOVE_HIDDEN) return set_err(GSR_E_INVALID, "gsr_remove: unknown flag bits %#x", flags & ~GSR_REMOVE_HIDDEN);
-    if (!mask && !(flags & GSR_REMOVE_HIDDEN)) return set_err(GSR_E_INVALID, "gsr_remove: mask is NULL and GSR_REMOVE_HIDDEN is not set");
-    if (c->uploading) return set_err(GSR_E_INVALID, "gsr_remove: upload in progress");
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "gsr_remove: no geometry: nothing uploaded");
-    const uint32_t n = c->n;
-    const size_t words = ((size_t)n + 31) / 32;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = GSR_OK;
-    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
-    const double t_begin = up_now_ms();
-    if ((rc = sync_all(c))) return rc;   // the public stream (a producer of a device mask queued there has finished), and no write under a frame in flight
-    const bool hidden = (flags & GSR_REMOVE_HIDDEN) && c->vis_on;
-    if (n == 0 || (!mask && !hidden)) {                // nothing can go
-        if (n_left) *n_left = (int64_t)n;
-        return GSR_OK;
-    }
-    FrameSlot& sl = c->slot[0];
-    hipStream_t us = sl.stream;
-    // ---- the scratch of mark, scan and compaction, in the staging arena (kept between uploads and edits; grown only when too small)
-    const uint32_t nblocks = div_up(n, (uint32_t)GSR_REMOVE_BLOCK);
-    const size_t al = 256;
-    size_t off = 0;
-    auto place = [&](size_t bytes) { const size_t at = off; off += (bytes + al - 1) / al * al; return at; };
-    const size_t oMask = place(mask && !mask_is_device ? words * 4 : 0), oKeep = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8), oCnt = place((size_t)nblocks * 4),
-                 oOff = place(((size_t)nblocks + 1) * 4), oP = place((size_t)n * 12), oSlot = place((size_t)n * 4);
-    if (off > c->stage_cap) {
-        dev_free(c->stage);
-        c->stage_cap = 0;
-        if ((rc = dev_alloc(&c->stage, off + 256))) return rc;
-        c->stage_cap = off + 256;
-    }
-    if (!c->rm_h_total && hipHostMalloc(reinterpret_cast<void**>(&c->rm_h_total), 2 * sizeof(uint32_t), 0) != hipSuccess) {
-        c->rm_h_total = nullptr;
-        (void)hipGetLastError();
-        return set_err(GSR_E_OOM, "gsr_remove: no pinned host memory for the survivor count");
-    }
-    for (int k = 0; k < 3; ++k)
-        if (!c->up_ev[k]) HIP_TRY(hipEventCreate(&c->up_ev[k]));
-    if ((rc = ensure_inverse_perm(c))) return rc;      // (the OLD order's inverse; built on slot 0's own stream)
-    HIP_TRY(hipStreamSynchronize(sl.own));
-    unsigned long long* const keep = reinterpret_cast<unsigned long long*>(c->stage + oKeep);
-    uint32_t* const counts = reinterpret_cast<uint32_t*>(c->stage + oCnt);
-    uint32_t* const offsets = reinterpret_cast<uint32_t*>(c->stage + oOff);
-    float* const Pup = reinterpret_cast<float*>(c->stage + oP);
-    uint32_t* const src_slot = reinterpret_cast<uint32_t*>(c->stage + oSlot);
-    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    // ---- 1, 2. which splats stay, and how many: nothing resident is written yet
-    const uint32_t* dmask = mask;
-    double h2d_ms = 0.0;
-    if (mask && !mask_is_device) {
-        const double t0 = up_now_ms();
-        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
-        HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
-        HIP_TRY(hipStreamSynchronize(us));             // the caller's mask may be freed on return
-        h2d_ms = up_now_ms() - t0;
-        dmask = staged;
-    }
-    HIP_TRY(hipEventRecord(c->up_ev[0], us));
-    if (hidden)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<true>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, c->vis_mask, c->vis, keep, counts);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<false>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, (const uint32_t*)nullptr, GsrVisRule{}, keep, counts);
-    hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, counts, offsets);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->rm_h_total, offsets + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us));
-    HIP_TRY(hipStreamSynchronize(us));
-    const uint32_t n1 = c->rm_h_total[0];
-    if (n1 > n) return set_err(GSR_E_HIP, "gsr_remove: the scan counted %u survivors of %u splats", n1, n);
-    if (n1 == n) {                                     // nothing goes: no resident bit changes, nothing is invalidated
-        if (n_left) *n_left = (int64_t)n;
-        return GSR_OK;
-    }
-    // ---- everything the rest needs, before the first write to resident memory or to the visibility's state
-    const bool may_order = c->opt_morton && n1 > 1;
-    const bool vis = c->vis_on;
-    uint32_t *perm_new = nullptr, *mask_new = nullptr;
-    if (n1 > 0) {
-        if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
-        if (may_order && (rc = ensure_order_buffers(c, n1, &perm_new, who))) return rc;
-        if ((rc = ensure_spare_planes(c))) { dev_free(perm_new); return rc; }
-        if (vis) {
-            if (!(rc = vis_ensure_buffers(c)) && !c->alpha0_2) rc = dev_alloc(&c->alpha0_2, (size_t)c->cap);
-            if (!rc && c->vis_mask) rc = dev_alloc(&mask_new, words);
-            if (rc) { dev_free(perm_new); dev_free(mask_new); return rc; }
-        }
-    }
-    // ---- from here on a failure leaves no geometry (as a failed gsr_move does)
-    auto lost = [&](int code) { dev_free(perm_new); dev_free(mask_new); drop_geometry(c); return code; };
-    hipError_t e = hipSuccess;
-    if (n1 == 0) {
-        // the empty cloud, as gsr_upload of 0 splats leaves it: no order, no clusters, no mask
-        dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); dev_free(c->clusA2); dev_free(c->clusB2);
-        c->n = 0; c->nclus = 0; c->h_perm.clear(); c->bbox_ok = false; c->up_total = c->up_filled = 0;
-        vis_drop_mask(c);
-        c->vis_hidden = 0;
-        e = hipEventRecord(c->up_ev[1], us);
-        if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
-        if (e == hipSuccess) e = hipStreamSynchronize(us);
-        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    } else {
-        // 3. the survivors' positions, old slots, true alphas and mask bits at their new upload indices
-        if (mask_new) e = hipMemsetAsync(mask_new, 0, words * 4, us);
-        if (e == hipSuccess) {
-            if (vis)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_compact<true>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, keep, offsets, inv_old, c->geoA, Pup, src_slot,
-                                   c->alpha0, c->alpha0_2, c->vis_mask, mask_new);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_compact<false>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, keep, offsets, inv_old, c->geoA, Pup, src_slot,
-                                   (const float*)nullptr, (float*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-        // 4. the ordering of an upload over the survivors, and their planes into the spare set: k_repack as a move runs it, with the
-        // survivors' old slots in the place of the old order's inverse
-        if ((rc = position_box(c, Pup, n1, us, who))) return lost(rc);
-        const bool ordered = may_order && c->bbox_ok;
-        if (ordered && (rc = morton_order(c, Pup, n1, perm_new, who))) return lost(rc);
-        if (!ordered) dev_free(perm_new);
-        e = hipEventRecord(c->up_ev[1], us);
-        if (e == hipSuccess) e = queue_repack(c, us, n1, perm_new, src_slot);
-        if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
-        if (e == hipSuccess) e = hipStreamSynchronize(us);
-        if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-        // 5. the swap, and the upload-ordered state of the visibility with it
-        swap_planes(c, perm_new);
-        c->h_perm.clear();
-        c->n = n1; c->nclus = div_up(n1, GSR_CLUSTER); c->up_total = c->up_filled = n1;
-        if (vis) {
-            std::swap(c->alpha0, c->alpha0_2);
-            if (c->vis_mask) { dev_free(c->vis_mask); c->vis_mask = mask_new; mask_new = nullptr; }
-            // 6. the volumes against the survivors, in the order they sit in now (as a move's step 6)
-            if ((e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess)
-                return lost(set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e)));
-        }
-    }
-    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }
-    c->st.n_splats = c->n;
-    c->rm_calls += 1;
-    c->rm_last = (int64_t)n - (int64_t)n1;
-    float ms = 0.0f;
-    c->rm_ms[0] = h2d_ms;
-    c->rm_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? ms : 0.0;
-    c->rm_ms[2] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? ms : 0.0;
-    c->rm_ms[3] = up_now_ms() - t_begin;
-    if (n_left) *n_left = (int64_t)n1;
-    return GSR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Adding (k_add.h): splats appended to the resident cloud on the GPU.  gsr_remove the other way round: the new rows are
-// staged, every position goes through the ordering of an upload, k_add_pack writes the spare planes from the resident planes (old
-// splats) and the staged rows (new ones), the swap.  The one verb that can need MORE room than the context has: the capacity policy.
-extern "C" int64_t gsr_add_capacity(int64_t capacity, int64_t n_needed)
-{
-    if (capacity < 0 || n_needed < 0 || n_needed > 0x7fffffffll)
-        return (int64_t)set_err(GSR_E_INVALID, "gsr_add_capacity: bad argument (%lld, %lld)", (long long)capacity, (long long)n_needed);
-    if (n_needed <= capacity) return capacity;
-    return std::min<int64_t>(n_needed + n_needed / 4, 0x7fffffffll);     // (the 25 % headroom the list buffers take)
-}
-
-extern "C" int gsr_get_add(gsr_context* c, int64_t* adds, int64_t* added_last, int64_t* capacity, int64_t* grows, double ms[4])
-{
-    if (!c) return set_err(GSR_E_INVALID, "gsr_get_add: ctx is NULL");
-    if (adds) *adds = c->add_calls;
-    if (added_last) *added_last = c->add_last;
-    if (capacity) *capacity = (int64_t)c->cap;
-    if (grows) *grows = c->add_grows;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->add_ms[k];
-    return GSR_OK;
-}
-
-// what both forms refuse before they look at their arrays; *done: m == 0, there is nothing to do
-static int add_refuse(gsr_context* c, int64_t m, int64_t* n_total, const char* who, bool* done)
-{
-    *done = false;
-    if (!c) return set_err(GSR_E_INVALID, "%s: ctx is NULL", who);
-    if (m < 0) return set_err(GSR_E_INVALID, "%s: bad splat count %lld", who, (long long)m);
-    if (c->uploading) return set_err(GSR_E_INVALID, "%s: upload in progress", who);
-    if (!c->has_geometry) return set_err(GSR_E_INVALID, "%s: no geometry: nothing uploaded", who);
-    if ((int64_t)c->n + m > 0x7fffffffll) return set_err(GSR_E_INVALID, "%s: %u + %lld splats are more than a context holds", who, c->n, (long long)m);
-    if (m == 0) {                                      // nothing changes, nothing is invalidated
-        if (n_total) *n_total = (int64_t)c->n;
-        *done = true;
-    }
-    return GSR_OK;
-}
-
-// The body of gsr_add and gsr_add_device, behind their refusals.  stage_rows(arena of m rows, stream, &link_ms): the new rows into the
-// arena in gsr_upload_append's layout, complete when it returns.
-template <class StageRows>
-static int add_body(gsr_context* c, const char* who, uint32_t m, StageRows&& stage_rows, int64_t* n_total)
-{
-    HIP_TRY(hipSetDevice(c->device));
-    const double t_begin = up_now_ms();
-    int rc = sync_all(c);      // the public stream (a producer of a device source queued there has finished), and no write under a frame in flight
-    if (rc) return rc;
-    const uint32_t n0 = c->n, n1 = n0 + m, nclus1 = div_up(n1, GSR_CLUSTER);
-    FrameSlot& sl = c->slot[0];
-    hipStream_t us = sl.stream;
-    const uint32_t cap0 = c->cap, cap1 = (uint32_t)gsr_add_capacity((int64_t)cap0, (int64_t)n1);
-    const bool grow = cap1 != cap0;
-    const bool vis = c->vis_on;
-    // ---- everything the call needs, before the first write to resident memory or to the visibility's state
-    const size_t al = 256;
-    auto pad = [&](size_t b) { return (b + al - 1) / al * al; };
-    const size_t oAll = pad(up_arena(nullptr, m, c->has_sh).bytes), need = oAll + pad((size_t)n1 * 12);
-    if (need > c->stage_cap) {
-        dev_free(c->stage);
-        c->stage_cap = 0;
-        if ((rc = dev_alloc(&c->stage, need + 256))) return rc;
-        c->stage_cap = need + 256;
-    }
-    const bool may_order = c->opt_morton && n1 > 1;
-    uint32_t *perm_new = nullptr, *mask_new = nullptr;
-    float4 *clusA_new = nullptr, *clusB_new = nullptr;
-    float* alpha0_new = nullptr;
-    SlotSplatArrays slot_new[GSR_MAX_SLOTS];
-    auto give_up = [&](int code) {
-        dev_free(perm_new); dev_free(mask_new); dev_free(clusA_new); dev_free(clusB_new); dev_free(alpha0_new);
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_new[k].release();
-        return code;
-    };
-    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
-    if (may_order && (rc = ensure_order_buffers(c, n1, &perm_new, who))) return give_up(rc);
-    if (grow) {
-        // the spare set is at the old capacity: it goes first (nothing reads it), and the destination set comes at the new one
-        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-        const size_t cap = cap1;
-        if ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
-            (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8)))) {
-            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-            return give_up(rc);
-        }
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k)
-            if ((rc = alloc_splat_arrays(slot_new[k], cap))) {
-                dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-                return give_up(rc);
-            }
-    } else if ((rc = ensure_spare_planes(c))) {
-        return give_up(rc);
-    }
-    // (ensure_spare_planes sizes the spare cluster bounds for a removal, which only ever needs fewer: an add brings its own)
-    if ((rc = dev_alloc(&clusA_new, nclus1)) || (rc = dev_alloc(&clusB_new, nclus1))) return give_up(rc);
-    if (vis) {
-        if ((rc = vis_ensure_buffers(c))) return give_up(rc);
-        if (grow && (rc = dev_alloc(&alpha0_new, (size_t)cap1))) return give_up(rc);
-        if (c->vis_mask && (rc = dev_alloc(&mask_new, ((size_t)n1 + 31) / 32))) return give_up(rc);
-    }
-    for (int k = 0; k < 3; ++k)
-        if (!c->up_ev[k] && hipEventCreate(&c->up_ev[k]) != hipSuccess) return give_up(set_err(GSR_E_HIP, "%s: no event", who));
-    if ((rc = ensure_inverse_perm(c))) return give_up(rc);      // (the OLD order's inverse; built on slot 0's own stream)
-    if (hipStreamSynchronize(sl.own) != hipSuccess) return give_up(set_err(GSR_E_HIP, "%s: the inverse of the storage order", who));
-    // nothing can fail for lack of memory any more: the larger buffers take their places (none of them holds anything a frame keeps)
-    dev_free(c->clusA2); dev_free(c->clusB2);
-    c->clusA2 = clusA_new; c->clusB2 = clusB_new; clusA_new = clusB_new = nullptr;
-    if (grow) {
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], slot_new[k]);
-        dev_free(c->alpha0_2);
-        if (!vis) dev_free(c->alpha0);                 // (at the old capacity, and valid only while a visibility is in force)
-    }
-    // ---- from here on a failure leaves no geometry (as a failed gsr_move does)
-    auto lost = [&](int code) {
-        give_up(code);
-        if (grow) {                                    // (the planes that stay are at the old capacity)
-            dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-        }
-        drop_geometry(c);
-        return code;
-    };
-    // 1. the new rows, staged
-    const UpArena A = up_arena(c->stage, m, c->has_sh);
-    double link_ms = 0.0;
-    hipError_t e = stage_rows(A, us, &link_ms);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: staging the new rows: %s", who, hipGetErrorString(e)));
-    // 2. every position in upload order: the resident ones from geoA through the old order's inverse, the new ones behind them
-    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
-    const uint32_t* const inv_old = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
-    e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess && n0) {
-        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n0, 256)), dim3(256), 0, us, 0u, 0u, n0, (const float*)nullptr, inv_old, c->geoA, (uint4*)nullptr, Pall);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(Pall + 3 * (size_t)n0, A.P, (size_t)m * 12, hipMemcpyDeviceToDevice, us);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    // 3. the ordering of an upload over all of them
-    if ((rc = position_box(c, Pall, n1, us, who))) return lost(rc);
-    const bool ordered = may_order && c->bbox_ok;
-    if (ordered && (rc = morton_order(c, Pall, n1, perm_new, who))) return lost(rc);
-    if (!ordered) dev_free(perm_new);
-    e = hipEventRecord(c->up_ev[1], us);
-    // 4. the planes of the larger cloud into the spare set: resident splats from the planes, new ones from the staged rows
-    if (e == hipSuccess) {
-        const GsrPackSrc src{A.P, A.alpha, A.Cd, A.scale, A.orient, A.shx, A.shy, A.shz};
-        if (c->has_sh)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_add_pack<true>), dim3(nclus1), dim3(GSR_PACK_THREADS), 0, us, n1, n0, cap0, cap1, src, perm_new, inv_old,
-                               c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_add_pack<false>), dim3(nclus1), dim3(GSR_PACK_THREADS), 0, us, n1, n0, cap0, cap1, src, perm_new, inv_old,
-                               c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
-    // ... and the upload-ordered state of a visibility in force: the true alphas of the new rows behind the old ones, the mask extended
-    // by clear bits
-    if (e == hipSuccess && vis) {
-        float* const a0 = grow ? alpha0_new : c->alpha0;
-        if (grow && n0) e = hipMemcpyAsync(a0, c->alpha0, (size_t)n0 * 4, hipMemcpyDeviceToDevice, us);
-        if (e == hipSuccess) e = hipMemcpyAsync(a0 + n0, A.alpha, (size_t)m * 4, hipMemcpyDeviceToDevice, us);
-        if (e == hipSuccess && mask_new) {
-            const uint32_t words1 = (uint32_t)(((size_t)n1 + 31) / 32);
-            hipLaunchKernelGGL(k_add_mask_extend, dim3(div_up(words1, 256)), dim3(256), 0, us, n0, words1, c->vis_mask, mask_new);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(us);
-    if (e != hipSuccess) return lost(set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e)));
-    // 5. the swap.  What becomes the spare set is the cloud before: its cluster bounds are too few for the next edit of this one, and
-    // after a growth its planes are at the wrong capacity -- both go, and the next edit that needs spare planes allocates them again
-    swap_planes(c, perm_new);
-    c->h_perm.clear();
-    dev_free(c->clusA2); dev_free(c->clusB2);
-    if (grow) {
-        dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-        c->cap = cap1;
-        if (vis) { dev_free(c->alpha0); c->alpha0 = alpha0_new; alpha0_new = nullptr; }
-    }
-    c->n = n1; c->nclus = nclus1; c->up_total = c->up_filled = n1;
-    c->st.n_splats = n1;
-    if (mask_new) { dev_free(c->vis_mask); c->vis_mask = mask_new; mask_new = nullptr; }
-    // 6. a visibility in force: the rule over the whole cloud, in the order it sits in now (as a move's step 6)
-    if (vis && (e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr)) != hipSuccess) {
-        drop_geometry(c);
-        return set_err(GSR_E_HIP, "%s: applying the visibility: %s", who, hipGetErrorString(e));
-    }
-    // 7. a new cloud to everything a frame keeps
-    if ((rc = new_cloud_state(c, who))) { drop_geometry(c); return rc; }
-    c->add_calls += 1;
-    c->add_last = (int64_t)m;
-    if (grow) c->add_grows += 1;
-    float ms = 0.0f;
-    c->add_ms[0] = link_ms;
-    c->add_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? ms : 0.0;
-    c->add_ms[2] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? ms : 0.0;
-    c->add_ms[3] = up_now_ms() - t_begin;
-    if (n_total) *n_total = (int64_t)n1;
-    return GSR_OK;
-}
-
-extern "C" int gsr_add(gsr_context* c, int64_t m64, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
-                       const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total)
-{
-    const char* const who = "gsr_add";
-    bool done = false;
-    int rc = add_refuse(c, m64, n_total, who, &done);
-    if (rc || done) return rc;
-    if (!P || !Cd || !alpha || !scale || !orient) return set_err(GSR_E_INVALID, "gsr_add: NULL attribute array");
-    const int nsh = (shx ? 1 : 0) + (shy ? 1 : 0) + (shz ? 1 : 0);
-    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_add: SH arrays for a cloud uploaded without SH");
-    if (c->has_sh && nsh != 3) return set_err(GSR_E_INVALID, "gsr_add: the cloud has SH and the three SH arrays are not all given");
-    const uint32_t m = (uint32_t)m64;
-    const bool has_sh = c->has_sh;
-    return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double* link_ms) {
-        // host -> device, nothing else (as gsr_upload_append)
-        const double t0 = up_now_ms();
-        hipError_t e = hipSuccess;
-        auto h2d = [&](void* d, const void* h, size_t bytes) { if (e == hipSuccess) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, us); };
-        h2d(A.P, P, (size_t)m * 12); h2d(A.alpha, alpha, (size_t)m * 4); h2d(A.Cd, Cd, (size_t)m * 6);
-        h2d(A.scale, scale, (size_t)m * 6); h2d(A.orient, orient, (size_t)m * 8);
-        if (has_sh) { h2d(A.shx, shx, (size_t)m * 32); h2d(A.shy, shy, (size_t)m * 32); h2d(A.shz, shz, (size_t)m * 32); }
-        if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be freed on return
-        *link_ms = up_now_ms() - t0;
-        return e;
-    }, n_total);
-}
-
-extern "C" int gsr_add_device(gsr_context* c, int64_t m64, const gsr_device_attrs* a, int64_t* n_total)
-{
-    const char* const who = "gsr_add_device";
-    bool done = false;
-    int rc = add_refuse(c, m64, n_total, who, &done);
-    if (rc || done) return rc;
-    if (!a) return set_err(GSR_E_INVALID, "gsr_add_device: attrs is NULL");
-    if (!a->P) return set_err(GSR_E_INVALID, "gsr_add_device: P is NULL");
-    if (c->has_sh != (a->sh != nullptr)) return set_err(GSR_E_INVALID, "gsr_add_device: SH presence differs from the resident cloud's");
-    if (a->sh && (a->sh_vec3_per_point < 1 || a->sh_vec3_per_point > 16))
-        return set_err(GSR_E_INVALID, "gsr_add_device: sh_vec3_per_point = %d is not within 1..16", a->sh_vec3_per_point);
-    const uint32_t m = (uint32_t)m64;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = check_device_attrs(c, a, m, who))) return rc;
-    const bool has_sh = c->has_sh;
-    return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double*) {
-        // P and alpha as they are (the runtime picks the direction: a source may be pinned host memory); the rest is quantised straight
-        // from the caller's arrays (as gsr_upload_append_device)
-        hipError_t e = hipMemcpyAsync(A.P, a->P, (size_t)m * 12, hipMemcpyDefault, us);
-        if (e == hipSuccess)
-            e = a->alpha ? hipMemcpyAsync(A.alpha, a->alpha, (size_t)m * 4, hipMemcpyDefault, us)
-                         : hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(A.alpha), 0x3f800000, m, us);      // missing opacity: opaque
-        if (e == hipSuccess) {
-            GsrRawSh sh{};
-            sh.scheme = a->sh ? 1 : 0;
-            sh.vec3_per_point = a->sh_vec3_per_point;
-            sh.array = a->sh;
-            hipLaunchKernelGGL(k_quantize_raw, dim3(div_up(m, 256)), dim3(256), 0, us, m, a->Cd, a->scale, a->orient, sh, A.Cd, A.scale, A.orient,
-                               has_sh ? A.shx : (uint16_t*)nullptr, has_sh ? A.shy : (uint16_t*)nullptr, has_sh ? A.shz : (uint16_t*)nullptr);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(us);   // the caller's arrays may be overwritten on return
-        return e;
-    }, n_total);
-}
+// Edits of the resident cloud without a re-upload: update, move, the device sources, visibility, remove, add.
+// (Behind everything else: the kernel templates they launch first keep their places at the end of the code object.)
+#include "gsr_resident_edit.h"
