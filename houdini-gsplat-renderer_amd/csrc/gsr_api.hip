@@ -47,6 +47,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_visibility.h"   // (last: the kernels of the frame keep their places in the code object)
 #include "k_remove.h"
 #include "k_add.h"
+#include "k_read.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -370,6 +371,9 @@ struct gsr_context {
     // gsr_add (k_add.h): what gsr_get_add reports (the capacity in force is c->cap)
     int64_t add_calls = 0, add_last = 0, add_grows = 0;
     double add_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // gsr_read / gsr_read_device (k_read.h): what gsr_get_read reports
+    int64_t rd_calls = 0, rd_last = 0;
+    double rd_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -3331,3 +3335,5 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
 // Edits of the resident cloud without a re-upload: update, move, the device sources, visibility, remove, add.
 // (Behind everything else: the kernel templates they launch first keep their places at the end of the code object.)
 #include "gsr_resident_edit.h"
+// ... and read back in upload order: it shares the edits' refusals and pointer check, and k_unpack comes last of all.
+#include "gsr_resident_read.h"

@@ -679,6 +679,16 @@ extern "C" int gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const 
     return GSR_OK;
 }
 
+// ... and read back from rank 0's replica (gsr_read: the caller's thread; no rank's state changes)
+extern "C" int gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_arrays* out)
+{
+    if (!m || !out) return fail(GSR_E_INVALID, "gsr_multi_read: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_read: upload in progress");
+    const int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return gsr_read(m->ctx[0], first, n, out);
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

@@ -97,6 +97,18 @@ class gsr_device_attrs(C.Structure):
                 ("sh", C.c_void_p), ("sh_vec3_per_point", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_read_arrays(C.Structure):
+    """include/gsplat_hip.h: the HOST destinations of gsr_read, in gsr_upload_append's layout (NULL = not wanted)"""
+    _fields_ = [("P", C.c_void_p), ("Cd", C.c_void_p), ("alpha", C.c_void_p), ("scale", C.c_void_p), ("orient", C.c_void_p),
+                ("shx", C.c_void_p), ("shy", C.c_void_p), ("shz", C.c_void_p)]
+
+
+class gsr_device_out(C.Structure):
+    """include/gsplat_hip.h: the float32 DEVICE destinations of gsr_read_device, in gsr_device_attrs' layout (NULL = not wanted)"""
+    _fields_ = [("P", C.c_void_p), ("Cd", C.c_void_p), ("alpha", C.c_void_p), ("scale", C.c_void_p), ("orient", C.c_void_p),
+                ("sh", C.c_void_p), ("sh_vec3_per_point", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gsr_crop_volume(C.Structure):
     """include/gsplat_hip.h: one crop volume -- a 3x4 affine map (rows) from upload space onto the unit box / unit ball"""
     _fields_ = [("kind", C.c_int32), ("invert", C.c_int32), ("to_unit", C.c_float * 12)]
@@ -177,6 +189,7 @@ C_ABI_SYMBOLS = [
     "gsr_set_visibility", "gsr_get_visibility", "gsr_visibility_eval", "gsr_multi_set_visibility", "gsplat_renderer_set_visibility",
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
+    "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
 ]
 
 
@@ -250,6 +263,11 @@ def load_library() -> C.CDLL:
     L.gsr_add_capacity.restype = i64
     L.gsr_get_add.argtypes = [vp] + [C.POINTER(C.c_int64)] * 4 + [C.POINTER(C.c_double)]
     L.gsr_multi_add.argtypes = [vp, i64] + [vp] * 8 + [C.POINTER(C.c_int64)]
+    L.gsr_read_info.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int), f32p]
+    L.gsr_read.argtypes = [vp, i64, i64, C.POINTER(gsr_read_arrays)]
+    L.gsr_read_device.argtypes = [vp, i64, i64, C.POINTER(gsr_device_out)]
+    L.gsr_get_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_read.argtypes = [vp, i64, i64, C.POINTER(gsr_read_arrays)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -693,6 +711,52 @@ def device_attrs_struct(n=None, sh_vec3_per_point=None, **arrays):
     return a, (n or 0), keep
 
 
+def device_out_struct(n=None, sh_vec3_per_point=None, **arrays):
+    """gsr_device_out from keyword DESTINATIONS in device memory (P, Cd, alpha, scale, orient, sh; None = not wanted) -> (struct, n, the
+    objects it points into: keep them alive during the call).  Built like device_attrs_struct: an array is an int -- a device pointer;
+    then n must be given, and sh_vec3_per_point with sh -- or an object with data_ptr() (a torch tensor): float32, contiguous, on a
+    GPU, its first axis the rows; n and sh_vec3_per_point (1..16) come from the shapes and are cross-checked.  Nothing is written here."""
+    a, n, keep = device_attrs_struct(n, sh_vec3_per_point, **arrays)       # (the same rules for what an array may be)
+    out = gsr_device_out()
+    for name, _ in DEVICE_ATTRS:
+        setattr(out, name, getattr(a, name))
+    if out.sh:
+        if not 1 <= a.sh_vec3_per_point <= 16:
+            raise GsrError(-1, f"device_out_struct: sh_vec3_per_point = {a.sh_vec3_per_point} is not within 1..16")
+        out.sh_vec3_per_point = a.sh_vec3_per_point
+    return out, n, keep
+
+
+READ_ARRAYS = (("P", np.float32, 3), ("Cd", np.uint16, 3), ("alpha", np.float32, 1), ("scale", np.uint16, 3), ("orient", np.uint16, 4),
+               ("shx", np.uint16, 16), ("shy", np.uint16, 16), ("shz", np.uint16, 16))     # gsr_read_arrays: (name, dtype, values per row)
+
+
+def read_arrays_struct(n: int, names):
+    """gsr_read_arrays for n rows of the arrays `names` -> (struct, {name: the fresh array it points into})"""
+    unknown = set(names) - {name for name, _, _ in READ_ARRAYS}
+    if unknown:
+        raise GsrError(-1, f"read: unknown array(s) {sorted(unknown)}")
+    r, arrays = gsr_read_arrays(), {}
+    for name, dtype, width in READ_ARRAYS:
+        if name in names:
+            arrays[name] = np.zeros((n, width) if width > 1 else (n,), dtype)
+            setattr(r, name, arrays[name].ctypes.data)
+    return r, arrays
+
+
+def _read_splats(L, verb, handle, info, first, n, names):
+    """Engine.read / MultiEngine.read behind their handles: info = (resident count, has_sh)"""
+    from .scenes import Splats
+    total, has_sh = info
+    first = int(first)
+    n = total - first if n is None else int(n)
+    if names is None:
+        names = [name for name, _, _ in READ_ARRAYS if has_sh or not name.startswith("sh")]
+    r, arrays = read_arrays_struct(max(n, 0), tuple(names))
+    _check(verb(handle, first, n, C.byref(r)))
+    return Splats(*[arrays.get(name) for name, _, _ in READ_ARRAYS])
+
+
 class _Arrays:
     """contiguous, correctly typed views of a Splats-like object (kept alive during the call)"""
 
@@ -912,6 +976,38 @@ class Engine:
         calls, last, cap, grows, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
         _check(self.L.gsr_get_add(self.h, C.byref(calls), C.byref(last), C.byref(cap), C.byref(grows), ms))
         return {"adds": calls.value, "added_last": last.value, "capacity": cap.value, "grows": grows.value, "ms": [float(x) for x in ms]}
+
+    # ---- reading back: the resident cloud in upload order (include/gsplat_hip.h, "reading back")
+    def read_info(self) -> dict:
+        """gsr_read_info -> {n_splats: resident now, has_sh, origin: the GSplatOrigin in force}; no kernel, no synchronisation"""
+        n, sh, origin = C.c_int64(0), C.c_int(0), (C.c_float * 3)()
+        _check(self.L.gsr_read_info(self.h, C.byref(n), C.byref(sh), origin))
+        return {"n_splats": n.value, "has_sh": bool(sh.value), "origin": tuple(float(x) for x in origin)}
+
+    def read(self, first: int = 0, n=None, names=None):
+        """gsr_read: the attributes of the resident splats [first, first + n) (upload order; n = None: to the end) as a scenes.Splats
+        in upload's layout, bit for bit what a fresh upload would have to be given: raw P bits, TRUE alphas also under a visibility,
+        the resident halves.  names = the arrays wanted (the others are None); default: all, SH only when the cloud has it.  Changes
+        and invalidates nothing."""
+        info = self.read_info()
+        return _read_splats(self.L, self.L.gsr_read, self.h, (info["n_splats"], info["has_sh"]), first, n, names)
+
+    def read_device(self, dst: dict, first: int = 0, n=None, sh_vec3_per_point=None) -> int:
+        """gsr_read_device: the same rows into float32 arrays in DEVICE memory, dst = {P, Cd, alpha, scale, orient, sh} (any subset) of
+        raw device pointers (then n must be given, and sh_vec3_per_point with sh) or torch tensors (device_out_struct); every half
+        arrives as the float32 of exactly that value; SH slots >= sh_vec3_per_point are not written out.  Waits for the work queued on
+        the stream given to set_stream first; synchronous -> the rows read"""
+        if not isinstance(dst, dict):
+            raise GsrError(-1, "read_device: dst is not a dict of device arrays")
+        out, n, keep = device_out_struct(n, sh_vec3_per_point, **dst)
+        _check(self.L.gsr_read_device(self.h, int(first), n, C.byref(out)))
+        return n
+
+    def get_read(self) -> dict:
+        """gsr_get_read -> {reads: calls that read something, rows_last, ms: the last call's clock [kernel, device -> host copies, 0, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_read(self.h, C.byref(calls), C.byref(last), ms))
+        return {"reads": calls.value, "rows_last": last.value, "ms": [float(x) for x in ms]}
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
@@ -1448,6 +1544,12 @@ class MultiEngine:
         total = C.c_int64(0)
         _check(self.L.gsr_multi_add(self.h, a.n, *a.ptrs(), C.byref(total)))
         return total.value
+
+    def read(self, first: int = 0, n=None, names=None):
+        """gsr_multi_read: Engine.read of rank 0's copy (the cloud is replicated) -> scenes.Splats"""
+        cnt, sh = C.c_int64(0), C.c_int(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), C.byref(sh), None))
+        return _read_splats(self.L, self.L.gsr_multi_read, self.h, (cnt.value, bool(sh.value)), first, n, names)
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

@@ -451,6 +451,71 @@ int  gsr_add_device(gsr_context* ctx, int64_t m, const gsr_device_attrs* a, int6
 int64_t gsr_add_capacity(int64_t capacity, int64_t n_needed);   /* host, no context, no GPU */
 int  gsr_get_add(gsr_context* ctx, int64_t* adds, int64_t* added_last, int64_t* capacity, int64_t* grows, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- reading back (the resident cloud in upload order, from the GPU) -------------------------------------------------------------- */
+/* Saving what a densify / prune / crop session left, or handing it to the next tool on the GPU: the attributes of the resident splats
+ * [first, first + n) come back in UPLOAD order -- the index space in force now, after every remove and add -- without the caller
+ * keeping a shadow copy of every array and replaying every edit.  One streaming kernel (k_read.h: k_pack run backwards) gathers the
+ * rows through the inverse of the storage order; the resident layout loses nothing of what was uploaded.
+ * gsr_read_info: what a caller needs to size the arrays -- the resident count, whether the cloud has SH, the origin in force; no
+ * kernel, no synchronisation; any pointer may be NULL.
+ * gsr_read: HOST destinations in gsr_upload_append's layout (P float[3n]; Cd half[3n]; alpha float[n]; scale half[3n]; orient
+ * half[4n]; shx / shy / shz half[16n], all three or none and only for a cloud with SH), rows for [first, first + n); NULL = not
+ * wanted.  The kernel writes device rows of the context's own (the upload staging arena, sized for the range), then every wanted array
+ * is copied device -> host.
+ * gsr_read_device: DEVICE destinations, float32, in gsr_device_attrs' layout -- SH coefficient j, channel c of row t at
+ * sh[(t * vpp + j) * 3 + c], vpp = sh_vec3_per_point in 1..16; slots j >= vpp are not written out.  The kernel writes the caller's
+ * arrays where they are: nothing is staged and nothing crosses the link.
+ * CONTRACT: after GSR_OK rows [0, n) of every array given hold, bit for bit, what a fresh gsr_upload would have to be given to leave
+ * the context as it is:
+ *   P       the raw position bits: NaN payloads, infinities and -0 come back as they went in;
+ *   alpha   the splat's TRUE alpha: under a visibility in force a hidden splat reads back its own alpha, not the resident +0.0f (the
+ *           hidden set is gsr_visibility_eval on the P read);
+ *   halves  the resident bits.  The extent half of geoB is derived and is not returned.  Index 15 of the x / y / z rows (slot 15 of a
+ *           16-slot sh row) is not resident -- the renderer never reads it -- and comes back as a zero half (+0.0f);
+ *   the device form returns every half as the float32 of exactly that value (denormals included, no rounding anywhere); a NaN half
+ *           becomes a NaN float with unspecified sign and payload (the NaN rule of the target formats above).
+ * So a fresh context given gsr_upload of a whole-cloud gsr_read -- or gsr_upload_append_device of a whole-cloud gsr_read_device with
+ * sh_vec3_per_point = 16 -- with the same GSR_OPT_STORAGE_ORDER, the origin of gsr_read_info and, under a visibility, the same
+ * gsr_set_visibility, holds the same geoA, geoB, colour chunks, colour rows, cluster bounds and storage order.
+ * A READ CHANGES AND INVALIDATES NOTHING: no resident bit changes; depth horizons, cached depth orders, policies and the visibility
+ * stay; gsr_stats.uploads, moves, upload_ms and move_ms stay; the next frame runs the launches it would have run.  It does not wait
+ * for the frames in flight: they never write resident planes.  A context that never reads launches nothing new.
+ * ORDERING: the device form first waits for the work queued on the context's public stream (gsr_set_stream) -- a consumer still
+ * reading the destinations from the previous iteration has finished.  Both forms are synchronous: on return the destinations are
+ * complete.  Every non-NULL device destination is checked before anything is launched, exactly as the device sources above are
+ * (4-byte aligned; device memory of the context's device or pinned host memory; all n x row bytes inside the allocation).
+ * Overlapping destinations are the caller's mistake and are not detected.
+ * GSR_E_INVALID, nothing written: NULL ctx or struct; no geometry ever uploaded, or an upload in progress; first < 0, n < 0 or
+ * first + n beyond the resident count; one or two of the three SH arrays; SH destinations for a cloud without SH;
+ * sh_vec3_per_point outside 1..16 with sh given; reserved_ != 0; a device destination that fails the pointer check.
+ * n == 0, or nothing asked for: GSR_OK, nothing happens and nothing is counted.  The empty cloud (after removing everything) reads 0
+ * rows.  Everything is allocated before the launch: GSR_E_OOM leaves the context untouched, and so does a HIP failure, since nothing
+ * resident is written.
+ * gsr_get_read: the calls that read something, the rows of the last one, and its clock ms[4]: [0] the kernel (HIP events)
+ * [1] device -> host copies, wall clock (0.0 for the device form)   [2] 0.0 (reserved)   [3] wall clock of the call.
+ * gsr_multi_read (below, with the other gsr_multi verbs): rank 0's copy -- the cloud is replicated.
+ * Out of scope: the GSplatRenderer shim and the HDK glue (their rows are the caller's own host arrays already); gsr_comm_* (each
+ * rank is a plain context and reads for itself); reading by an index list or a mask; an asynchronous form; half destinations in
+ * device memory; a PLY writer (the INRIA activations are not bit-invertible, and a writer with a tolerance is its own piece of
+ * work); a hidden-mask output. */
+int  gsr_read_info(gsr_context* ctx, int64_t* n_splats, int* has_sh, float origin[3]);   /* any pointer may be NULL */
+typedef struct gsr_read_arrays {          /* HOST destinations in gsr_upload_append's layout, rows for [first, first + n); NULL = not wanted */
+    float*    P;                          /* float[3n] */
+    uint16_t* Cd;                         /* half[3n]  */
+    float*    alpha;                      /* float[n]  */
+    uint16_t* scale;                      /* half[3n]  */
+    uint16_t* orient;                     /* half[4n] (x, y, z, w) */
+    uint16_t *shx, *shy, *shz;            /* half[16n] each */
+} gsr_read_arrays;
+int  gsr_read(gsr_context* ctx, int64_t first, int64_t n, const gsr_read_arrays* out);
+typedef struct gsr_device_out {           /* DEVICE destinations, float32, the layout of gsr_device_attrs; NULL = not wanted */
+    float *P, *Cd, *alpha, *scale, *orient, *sh;
+    int32_t sh_vec3_per_point;            /* 1..16 when sh is given: slots j >= it are not written out */
+    int32_t reserved_;                    /* 0 */
+} gsr_device_out;
+int  gsr_read_device(gsr_context* ctx, int64_t first, int64_t n, const gsr_device_out* out);
+int  gsr_get_read(gsr_context* ctx, int64_t* reads, int64_t* rows_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -560,6 +625,8 @@ int  gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int flags, int64_
  * upload. */
 int  gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
                    const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total);
+/* gsr_read of rank 0's copy (the cloud is replicated), after the same synchronisation; no rank's state changes */
+int  gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_arrays* out);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
