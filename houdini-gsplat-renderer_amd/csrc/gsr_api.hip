@@ -1,6 +1,8 @@
 // gsr_api.hip -- host side of libgsplat_hip.so: context, HBM buffers, the
 // per-frame kernel pipeline and the C ABI declared in include/gsplat_hip.h.
-// (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end.)
+// (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end; the kernels that
+// write, edit and read the resident layout -- once per geometry change, not per frame -- in k_resident.h, k_visibility.h, k_remove.h,
+// k_add.h and k_read.h.)
 //
 // Pipeline per gsr_render (all on one HIP stream):
 //   k_cluster_cull         clusters of 64 Morton-ordered splats vs clip planes / screen / band / depth horizons (k_cluster.h)
@@ -35,7 +37,7 @@
 #include "k_blend.h"
 #include "k_cluster.h"
 #include "k_colour.h"
-#include "k_preprocess.h"
+#include "k_preprocess.h"   // (and, through it, k_resident.h)
 #ifdef GSR_HOST_TIMING
 static double g_t_verdict = 0, g_acc_py = 0, g_acc_pre = 0, g_acc_launch = 0; static long g_acc_n = 0;
 static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }

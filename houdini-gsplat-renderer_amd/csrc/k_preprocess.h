@@ -1,4 +1,4 @@
-// k_preprocess.h -- K0 (repack at upload) and K1 (per-splat vertex stage).
+// k_preprocess.h -- K1, the per-splat vertex stage of a frame.  (K0, what writes the resident layout K1 reads, is k_resident.h.)
 //
 // K1 replaces the reference's main vertex shader
 // (/root/reference/gsplat_plugin/shaders/GSplatShaderSource.h:190-288 with the
@@ -16,496 +16,8 @@
 #define GSR_K1_THREADS 256
 #endif
 
-// ---------------------------------------------------------------------------
-// K0 (round 6): the registerUpdate()-layout arrays of a whole upload (in the staging arena, device memory, upload order) -> the
-// resident layout, straight INTO STORAGE ORDER, with the cluster bounds on the way out.  Runs once per geometry change.
-//   storage slot j <- splat perm[j] (the stable order of the positions' Morton codes, k_cluster.h; NULL: upload order)
-// One workgroup of 512 threads = 64 slots = ONE CLUSTER, eight lanes per splat; lane q of a splat's eight:
-//   q = 0      P (12 B) + opacity (4 B)            -> geoA[j], and colrow[j][0]
-//   q = 1..6   16 bytes of the x / y / z SH rows   -> LDS; then chunk c = q - 1 of the 48 colour halves (Cd.rgb, sh1.rgb, ..., sh15.rgb:
-//              half h = 3 * coefficient + channel) <- LDS: a 16 x 3 -> 3 x 16 transpose per splat -> col[c][j] and colrow[j][1 + c]
-//   q = 7      scale (6 B) + orient (8 B)          -> geoB[j] with its extent bound; colrow[j][7] = 0
-// so a wave WRITES eight whole 128-byte colrow lines, 128 contiguous bytes of geoA, of geoB and of each colour chunk, and READS, per
-// splat, its rows of the source arrays (96 + 36 bytes; a gather when perm is a permutation).  Before round 6 this was three passes:
-// k_repack (one thread per splat, 2-byte loads at a 32-byte stride, 16-byte stores at a 128-byte stride: 1.5 x write amplification,
-// 0.19 of HBM), then k_permute_geo + k_permute_rows over a second copy of the geometry, then k_cluster_bounds.
-// eighth half of geoB: an upper bound of |diag(scale) R(orient)^T|_F, the only thing K1's cheap extent bound needs of the
-// scale and the (unnormalised) quaternion -- so the bound costs a dozen instructions per splat instead of ninety.
-// One function for k_pack and k_update: an updated splat's bound is bit for bit what a fresh upload gives it.
-__device__ __forceinline__ uint16_t gsr_extent_half(uint16_t s0, uint16_t s1, uint16_t s2, uint16_t o0, uint16_t o1, uint16_t o2, uint16_t o3)
-{
-    const float sx = gsr_h2f(s0), sy = gsr_h2f(s1), sz = gsr_h2f(s2);
-    const float qi = gsr_h2f(o0), qj = gsr_h2f(o1), qk = gsr_h2f(o2), qr = gsr_h2f(o3);
-    const float r00 = 1.0f - 2.0f * gsr_fma(qj, qj, qk * qk), r01 = 2.0f * gsr_fma(qi, qj, -(qr * qk)), r02 = 2.0f * gsr_fma(qi, qk, qr * qj);
-    const float r10 = 2.0f * gsr_fma(qi, qj, qr * qk), r11 = 1.0f - 2.0f * gsr_fma(qi, qi, qk * qk), r12 = 2.0f * gsr_fma(qj, qk, -(qr * qi));
-    const float r20 = 2.0f * gsr_fma(qi, qk, -(qr * qj)), r21 = 2.0f * gsr_fma(qj, qk, qr * qi), r22 = 1.0f - 2.0f * gsr_fma(qi, qi, qj * qj);
-    const float mf2 = sx * sx * (r00 * r00 + r10 * r10 + r20 * r20) + sy * sy * (r01 * r01 + r11 * r11 + r21 * r21) +
-                      sz * sz * (r02 * r02 + r12 * r12 + r22 * r22);
-    const float mfv = __builtin_sqrtf(mf2) * 1.001f;
-    const _Float16 hh = (_Float16)mfv;              // rounded up (to nearest, then one step if that fell short): mf >= 0
-    uint16_t mf_h = __builtin_bit_cast(uint16_t, hh);
-    if ((float)hh < mfv) mf_h += 1;                 // (0x7bff + 1 = inf; inf / NaN stay what they are: K1 then takes the full path)
-    return mf_h;
-}
-// chunk c (eight halves) of a splat's 48 colour halves from its LDS row x[16] y[16] z[16] Cd[3]: the 16 x 3 -> 3 x 16 transpose
-template <bool SH>
-__device__ __forceinline__ uint4 gsr_colour_chunk(const uint16_t* row, int c)
-{
-    uint16_t h[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int hh = 8 * c + k, co = hh / 3, chn = hh - 3 * co;     // coefficient (0 = Cd), channel
-        // coefficient co of the reference's row-major 4x4 sits at flat index co - 1 of the x / y / z rows (co = 1..15)
-        h[k] = co == 0 ? row[48 + chn] : (SH ? row[16 * chn + (co - 1)] : (uint16_t)0);
-    }
-    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
-    return make_uint4(pk(h[0], h[1]), pk(h[2], h[3]), pk(h[4], h[5]), pk(h[6], h[7]));
-}
-// The bounds of ONE cluster (k_cluster.h: clusA = lo.xyz of the positions + the largest extent bound, clusB = hi.xyz + "never cull"
-// flag), folded by a workgroup of GSR_PACK_THREADS in k_pack's shape: of a splat's eight lanes, lane 0 brings its position in lo = hi
-// (and bad = a non-finite coordinate), lane 7 its extent bound in mf (and bad = !(mf < 6e4)); every other lane, and every lane of a
-// slot behind n, brings the neutral values.  One function for k_pack, k_repack and k_cluster_bounds: the same operands meet in the
-// same order, so a cluster's bounds after gsr_move are bit for bit what a fresh upload gives it.
-#define GSR_PACK_THREADS 512
-__device__ __forceinline__ void gsr_cluster_fold(float (&lo)[3], float (&hi)[3], float mf, bool bad, float (&s_red)[8][8],
-                                                 float4* __restrict__ clusA, float4* __restrict__ clusB)
-{
-    const int tid = threadIdx.x, wave = tid >> 6;
-    const bool any_bad = __ballot(bad) != 0ull;
-#pragma unroll
-    for (int d = 8; d < 64; d <<= 1) {     // (the position lanes are q = 0, the extent lanes q = 7: strides of eight)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = __builtin_fminf(lo[k], __shfl_xor(lo[k], d, 64));
-            hi[k] = __builtin_fmaxf(hi[k], __shfl_xor(hi[k], d, 64));
-        }
-        mf = __builtin_fmaxf(mf, __shfl_xor(mf, d, 64));
-    }
-    const int lane = tid & 63;
-    if (lane == 0) { s_red[wave][0] = lo[0]; s_red[wave][1] = lo[1]; s_red[wave][2] = lo[2]; s_red[wave][3] = hi[0]; s_red[wave][4] = hi[1]; s_red[wave][5] = hi[2]; s_red[wave][7] = any_bad ? 1.0f : 0.0f; }
-    if (lane == 7) s_red[wave][6] = mf;
-    __syncthreads();
-    if (tid == 0) {
-        float l0 = 3.0e38f, l1 = 3.0e38f, l2 = 3.0e38f, h0 = -3.0e38f, h1 = -3.0e38f, h2 = -3.0e38f, m = 0.0f, b = 0.0f;
-        for (int w = 0; w < 8; ++w) {
-            l0 = __builtin_fminf(l0, s_red[w][0]); l1 = __builtin_fminf(l1, s_red[w][1]); l2 = __builtin_fminf(l2, s_red[w][2]);
-            h0 = __builtin_fmaxf(h0, s_red[w][3]); h1 = __builtin_fmaxf(h1, s_red[w][4]); h2 = __builtin_fmaxf(h2, s_red[w][5]);
-            m = __builtin_fmaxf(m, s_red[w][6]); b = __builtin_fmaxf(b, s_red[w][7]);
-        }
-        clusA[blockIdx.x] = make_float4(l0, l1, l2, m);
-        clusB[blockIdx.x] = make_float4(h0, h1, h2, b != 0.0f ? 1.0f : 0.0f);
-    }
-}
-struct GsrPackSrc {
-    const float* P; const float* alpha;
-    const uint16_t *Cd, *scale, *orient, *shx, *shy, *shz;
-};
-template <bool SH>
-__global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_pack(uint32_t n, uint32_t cap, GsrPackSrc src, const uint32_t* __restrict__ perm,
-       float4* __restrict__ geoA, uint4* __restrict__ geoB, uint4* __restrict__ col, uint4* __restrict__ colrow,
-       float4* __restrict__ clusA, float4* __restrict__ clusB)
-{
-    static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = one cluster");
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad: 112 B rows)
-    __shared__ float s_red[8][8];                                           // per wave: lo.xyz hi.xyz mf bad
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
-    const uint32_t j = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
-    const bool live = j < n;
-    const uint32_t i = live ? (perm ? perm[j] : j) : 0u;
-    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mf = 0.0f;
-    bool bad = false;
-    uint4 rowpiece = make_uint4(0u, 0u, 0u, 0u);       // this lane's eighth of the splat's 128-byte row (lane 7: padding)
-    if (live) {
-        if (q == 0) {
-            const float px = src.P[3 * (size_t)i], py = src.P[3 * (size_t)i + 1], pz = src.P[3 * (size_t)i + 2], op = src.alpha[i];
-            geoA[j] = make_float4(px, py, pz, op);
-            rowpiece = make_uint4(__float_as_uint(px), __float_as_uint(py), __float_as_uint(pz), __float_as_uint(op));
-            s_h[sp][48] = src.Cd[3 * (size_t)i]; s_h[sp][49] = src.Cd[3 * (size_t)i + 1]; s_h[sp][50] = src.Cd[3 * (size_t)i + 2];
-            bad = !(__builtin_fabsf(px) < 3.0e38f) || !(__builtin_fabsf(py) < 3.0e38f) || !(__builtin_fabsf(pz) < 3.0e38f);
-            lo[0] = hi[0] = px; lo[1] = hi[1] = py; lo[2] = hi[2] = pz;
-        } else if (q == 7) {
-            const uint16_t* s = src.scale + 3 * (size_t)i;
-            const uint16_t* o = src.orient + 4 * (size_t)i;
-            const uint16_t s0 = s[0], s1 = s[1], s2 = s[2], o0 = o[0], o1 = o[1], o2 = o[2], o3 = o[3];
-            const uint16_t mf_h = gsr_extent_half(s0, s1, s2, o0, o1, o2, o3);
-            geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, mf_h));
-            mf = gsr_h2f(mf_h);
-            bad = !(mf < 6.0e4f);
-        } else if (SH) {
-            // lanes 1..6: x[0..7] x[8..15] y[0..7] y[8..15] z[0..7] z[8..15] (rows of 16 halves = 32 bytes, 16-byte loads)
-            const int ch = (q - 1) >> 1, part = (q - 1) & 1;
-            const uint16_t* row = (ch == 0 ? src.shx : (ch == 1 ? src.shy : src.shz)) + 16 * (size_t)i + 8 * part;
-            *reinterpret_cast<uint4*>(&s_h[sp][16 * ch + 8 * part]) = *reinterpret_cast<const uint4*>(row);
-        }
-    }
-    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (live && q >= 1 && (SH ? q <= 6 : q == 1)) {
-        const int c = q - 1;
-        const uint4 v = gsr_colour_chunk<SH>(s_h[sp], c);
-        col[(size_t)c * cap + j] = v;                  // SoA chunks: coalesced for a pass over ALL splats (eager colour)
-        rowpiece = v;
-    }
-    // ... and as ONE 128-byte row per splat, gathered by index (lazy colour): piece q from lane q, the eight pieces of a row in ONE store
-    // instruction (as three -- position, colours, padding -- a quarter of the rows went out as partial lines: PMC 1.16 x the output)
-    if (SH && live) colrow[(size_t)j * 8 + q] = rowpiece;
-    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA, clusB);
-}
-
-// ---------------------------------------------------------------------------
-// K0u: attributes of RESIDENT splats rewritten in place (gsr_update): k_pack mirrored.  The source arrays (the staging arena, upload
-// order, rows [0, cnt) = splats [first, first + cnt) of the upload) are read coalesced and scattered into the storage slots
-//   j = inv[first + t]     (inv: upload index -> storage slot, the inverse of perm; NULL: upload order, j = first + t)
-// One workgroup = 64 splats, eight lanes per splat with k_pack's roles; an array that is NULL is left as it is in HBM:
-//   q = 0      alpha -> geoA[j].w and colrow[j][0].w (4-byte stores; the position stays); Cd (or, SH without Cd, the resident Cd) -> LDS
-//   q = 1..6   SH rows -> LDS, then chunk q - 1 -> col[q - 1][j] and colrow[j][q]; Cd alone: lane 1 rewrites halves 0..2 of chunk 0
-//              (an SH context: read-modify-write, sh1.rgb and sh2.rg survive; no SH: Cd + zero halves, and there is no colrow)
-//   q = 7      scale and / or orient (the other from the resident geoB[j]) -> geoB[j] with its extent bound
-// Pieces of a splat's 128-byte colrow line that do not change are not written.  The cluster bounds follow in k_cluster_extents.
-struct GsrUpdateSrc {
-    const float* alpha;
-    const uint16_t *Cd, *scale, *orient, *shx, *shy, *shz;
-};
-template <bool SH>
-__global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_update(uint32_t first, uint32_t cnt, uint32_t cap, GsrUpdateSrc src, const uint32_t* __restrict__ inv,
-         float4* __restrict__ geoA, uint4* __restrict__ geoB, uint4* __restrict__ col, uint4* __restrict__ colrow)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad), as in k_pack
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
-    const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
-    const bool live = t < cnt;
-    const uint32_t j = live ? (inv ? inv[first + t] : first + t) : 0u;
-    const bool sh = SH && src.shx;                     // (all three or none: the host checks)
-    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
-    if (live) {
-        if (q == 0) {
-            if (src.alpha) {
-                const float op = src.alpha[t];
-                reinterpret_cast<float*>(geoA + j)[3] = op;
-                if (SH) reinterpret_cast<float*>(colrow + (size_t)j * 8)[3] = op;
-            }
-            if (src.Cd) {
-                s_h[sp][48] = src.Cd[3 * (size_t)t]; s_h[sp][49] = src.Cd[3 * (size_t)t + 1]; s_h[sp][50] = src.Cd[3 * (size_t)t + 2];
-            } else if (sh) {                           // new SH under the resident Cd: halves 0..2 of chunk 0
-                const uint2 w = *reinterpret_cast<const uint2*>(col + j);
-                s_h[sp][48] = (uint16_t)(w.x & 0xffffu); s_h[sp][49] = (uint16_t)(w.x >> 16); s_h[sp][50] = (uint16_t)(w.y & 0xffffu);
-            }
-        } else if (q == 7) {
-            if (src.scale || src.orient) {
-                uint4 b = make_uint4(0u, 0u, 0u, 0u);
-                if (!src.scale || !src.orient) b = geoB[j];
-                uint16_t s0 = (uint16_t)(b.x & 0xffffu), s1 = (uint16_t)(b.x >> 16), s2 = (uint16_t)(b.y & 0xffffu);
-                uint16_t o0 = (uint16_t)(b.y >> 16), o1 = (uint16_t)(b.z & 0xffffu), o2 = (uint16_t)(b.z >> 16), o3 = (uint16_t)(b.w & 0xffffu);
-                if (src.scale) { const uint16_t* s = src.scale + 3 * (size_t)t; s0 = s[0]; s1 = s[1]; s2 = s[2]; }
-                if (src.orient) { const uint16_t* o = src.orient + 4 * (size_t)t; o0 = o[0]; o1 = o[1]; o2 = o[2]; o3 = o[3]; }
-                geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, gsr_extent_half(s0, s1, s2, o0, o1, o2, o3)));
-            }
-        } else if (sh) {
-            const int ch = (q - 1) >> 1, part = (q - 1) & 1;
-            const uint16_t* row = (ch == 0 ? src.shx : (ch == 1 ? src.shy : src.shz)) + 16 * (size_t)t + 8 * part;
-            *reinterpret_cast<uint4*>(&s_h[sp][16 * ch + 8 * part]) = *reinterpret_cast<const uint4*>(row);
-        }
-    }
-    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!live) return;
-    if (sh) {
-        if (q >= 1 && q <= 6) {
-            const uint4 v = gsr_colour_chunk<true>(s_h[sp], q - 1);
-            col[(size_t)(q - 1) * cap + j] = v;
-            colrow[(size_t)j * 8 + q] = v;
-        }
-    } else if (q == 1 && src.Cd) {
-        const uint32_t w0 = pk(s_h[sp][48], s_h[sp][49]), c2 = s_h[sp][50];
-        if (SH) {
-            uint4 v = col[j];
-            v.x = w0; v.y = (v.y & 0xffff0000u) | c2;
-            col[j] = v;
-            colrow[(size_t)j * 8 + 1] = v;
-        } else {
-            col[j] = make_uint4(w0, c2, 0u, 0u);
-        }
-    }
-}
-
-// ... and the w fields of the cluster bounds after scale / orient changed: clusA[c].w = the largest extent bound of the cluster's live
-// slots, clusB[c].w = the "never cull" flag (a non-finite position or !(mf < 6e4) anywhere in it) -- from the resident geoA / geoB, by
-// k_pack's rule, so a bound is neither stale-large after a shrink nor stale-small after a growth.  lo.xyz / hi.xyz depend on the
-// positions alone and are not touched.  One wave per cluster, 32 bytes read per splat.
-__global__ void __launch_bounds__(256)
-k_cluster_extents(uint32_t n, uint32_t nclus, const float4* __restrict__ geoA, const uint4* __restrict__ geoB,
-                  float4* __restrict__ clusA, float4* __restrict__ clusB)
-{
-    static_assert(GSR_CLUSTER == 64, "one wave = one cluster");
-    const int lane = threadIdx.x & 63;
-    const uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (c >= nclus) return;                            // (wave-uniform)
-    const uint32_t j = c * (uint32_t)GSR_CLUSTER + (uint32_t)lane;
-    float mf = 0.0f;
-    bool bad = false;
-    if (j < n) {
-        const float4 a = geoA[j];
-        mf = gsr_h2f(geoB[j].w >> 16);
-        bad = !(mf < 6.0e4f) || !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
-    }
-    const bool any_bad = __ballot(bad) != 0ull;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) mf = __builtin_fmaxf(mf, __shfl_xor(mf, d, 64));
-    // (k_pack folds the same values with fmaxf, which drops a NaN operand, so the order of the fold does not matter; its last fold
-    //  starts from 0, which turns a cluster whose bounds are ALL NaN into 0: so does this one)
-    mf = __builtin_fmaxf(0.0f, mf);
-    if (lane == 0) {
-        reinterpret_cast<float*>(clusA + c)[3] = mf;
-        reinterpret_cast<float*>(clusB + c)[3] = any_bad ? 1.0f : 0.0f;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// K0m: new POSITIONS for resident splats (gsr_move).  A position decides the storage order, so a move is: the new rows written where
-// the splats sit now (k_move_positions), the ordering of an upload over ALL positions in upload order (k_bbox_partials,
-// k_morton_codes, the radix sort), and the resident planes carried from the old order into the new one (k_repack) -- nothing but
-// the new P rows crosses the link.
-// k_move_positions: one thread per resident splat i (upload order), old slot j = inv[i] (inv: the inverse of the storage permutation
-// in force; NULL: j = i).  Splats [first, first + cnt) take row i - first of Pnew into geoA[j].xyz and, with SH, into piece 0 of
-// their colour row (three 4-byte stores each; .w, the opacity, stays); the others keep what geoA holds, which is the raw P bits of
-// their upload.  Either way the position goes to Pup[3 i ..]: the whole cloud's positions in upload order, what the ordering reads.
-__global__ void __launch_bounds__(256)
-k_move_positions(uint32_t first, uint32_t cnt, uint32_t n, const float* __restrict__ Pnew, const uint32_t* __restrict__ inv,
-                 float4* __restrict__ geoA, uint4* __restrict__ colrow /* NULL: no SH */, float* __restrict__ Pup)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t j = inv ? inv[i] : i;
-    float px, py, pz;
-    if (i - first < cnt) {                             // (unsigned: also false for i < first)
-        const float* p = Pnew + 3 * (size_t)(i - first);
-        px = p[0]; py = p[1]; pz = p[2];
-        float* a = reinterpret_cast<float*>(geoA + j);
-        a[0] = px; a[1] = py; a[2] = pz;
-        if (colrow) {
-            float* r = reinterpret_cast<float*>(colrow + (size_t)j * 8);
-            r[0] = px; r[1] = py; r[2] = pz;
-        }
-    } else {
-        const float4 a = geoA[j];
-        px = a.x; py = a.y; pz = a.z;
-    }
-    float* o = Pup + 3 * (size_t)i;
-    o[0] = px; o[1] = py; o[2] = pz;
-}
-
-// k_repack: the resident planes from the old storage order into the new one, into the SPARE copy of the planes (the host swaps the
-// two sets afterwards).  One workgroup = one destination cluster of 64 slots, eight lanes per splat -- k_pack's shape:
-//   slot j' <- the splat i = perm_new[j'] (NULL: i = j'), which sits in slot j = inv_old[i] (NULL: j = i)
-// and lane q of the eight carries 16-byte pieces, one vector load and one vector store each:
-//   q = 0      geoA[j] -> geoA'[j'] (and the position into the cluster's box)
-//   q = 1..6   col[q - 1][j] -> col'[q - 1][j'] (chunks strided by the capacity; without SH there is only chunk 0)
-//   q = 7      geoB[j] -> geoB'[j'] (and its extent half into the cluster's bound)
-//   every q    colrow[j][q] -> colrow'[j'][q] (SH only): whole 128-byte lines in and out
-// Slots behind n in the last cluster are not written, as k_pack leaves them.  The cluster bounds come from gsr_cluster_fold.
-template <bool SH>
-__global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_repack(uint32_t n, uint32_t cap, const uint32_t* __restrict__ perm_new, const uint32_t* __restrict__ inv_old,
-         const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col, const uint4* __restrict__ colrow,
-         float4* __restrict__ geoA2, uint4* __restrict__ geoB2, uint4* __restrict__ col2, uint4* __restrict__ colrow2,
-         float4* __restrict__ clusA2, float4* __restrict__ clusB2)
-{
-    static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = one cluster");
-    __shared__ float s_red[8][8];
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
-    const uint32_t jn = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
-    const bool live = jn < n;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mf = 0.0f;
-    bool bad = false;
-    if (live) {
-        const uint32_t i = perm_new ? perm_new[jn] : jn;
-        const uint32_t j = inv_old ? inv_old[i] : i;
-        if (SH) colrow2[(size_t)jn * 8 + q] = colrow[(size_t)j * 8 + q];
-        if (q == 0) {
-            const float4 a = geoA[j];
-            geoA2[jn] = a;
-            bad = !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
-            lo[0] = hi[0] = a.x; lo[1] = hi[1] = a.y; lo[2] = hi[2] = a.z;
-        } else if (q == 7) {
-            const uint4 b = geoB[j];
-            geoB2[jn] = b;
-            mf = gsr_h2f((uint16_t)(b.w >> 16));
-            bad = !(mf < 6.0e4f);
-        } else if (SH || q == 1) {
-            col2[(size_t)(q - 1) * cap + jn] = col[(size_t)(q - 1) * cap + j];
-        }
-    }
-    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA2, clusB2);
-}
-
-// ... and where no permutation is in force before or after the move (upload order kept): the splats stay where they are and only the
-// cluster bounds are formed again, in place, from the resident geoA / geoB -- k_repack without the copies.
-__global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_cluster_bounds(uint32_t n, const float4* __restrict__ geoA, const uint4* __restrict__ geoB, float4* __restrict__ clusA, float4* __restrict__ clusB)
-{
-    __shared__ float s_red[8][8];
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
-    const uint32_t j = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
-    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mf = 0.0f;
-    bool bad = false;
-    if (j < n) {
-        if (q == 0) {
-            const float4 a = geoA[j];
-            bad = !(__builtin_fabsf(a.x) < 3.0e38f) || !(__builtin_fabsf(a.y) < 3.0e38f) || !(__builtin_fabsf(a.z) < 3.0e38f);
-            lo[0] = hi[0] = a.x; lo[1] = hi[1] = a.y; lo[2] = hi[2] = a.z;
-        } else if (q == 7) {
-            mf = gsr_h2f((uint16_t)(geoB[j].w >> 16));
-            bad = !(mf < 6.0e4f);
-        }
-    }
-    gsr_cluster_fold(lo, hi, mf, bad, s_red, clusA, clusB);
-}
-
-// ---------------------------------------------------------------------------
-// K0': raw float32 point attributes (as a Houdini detail holds them) -> the half arrays k_pack takes.  What
-// GR_PrimGsplat::update does on the CPU in a tbb::parallel_for (/root/reference/gsplat_plugin/src/GR_GSplat.C:302-372):
-// fp32 -> fp16 (HDK's fpreal16: round to nearest even, overflow to infinity -- what v_cvt_f16_f32 does), the defaults for
-// missing attributes, and the three spherical-harmonics naming schemes -> coefficient j in flat slot j of the x / y / z rows.
-__device__ __forceinline__ uint16_t gsr_f2h(float f)
-{
-    const _Float16 h = (_Float16)f;      // v_cvt_f16_f32: round to nearest even
-    return __builtin_bit_cast(uint16_t, h);
-}
-struct GsrRawSh {
-    int32_t scheme;              // 0 none, 1 = one array of `vec3_per_point` vec3 per point, 2 = sh1..sh15 (vec3 arrays), 3 = f_rest_0..44 (float arrays)
-    int32_t vec3_per_point;      // scheme 1
-    const float* array;          // scheme 1
-    const float* ptr[45];        // scheme 2: [0..14] (NULL from the first gap on), scheme 3: [0..44] (likewise)
-};
-__global__ void __launch_bounds__(256)
-k_quantize_raw(uint32_t n, const float* __restrict__ Cd, const float* __restrict__ scale, const float* __restrict__ orient, GsrRawSh sh,
-               uint16_t* __restrict__ oCd, uint16_t* __restrict__ oS, uint16_t* __restrict__ oO,
-               uint16_t* __restrict__ ox, uint16_t* __restrict__ oy, uint16_t* __restrict__ oz)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        oCd[3 * (size_t)i + k] = Cd ? gsr_f2h(Cd[3 * (size_t)i + k]) : (uint16_t)0;            // missing Cd: black
-        oS[3 * (size_t)i + k] = scale ? gsr_f2h(scale[3 * (size_t)i + k]) : (uint16_t)0x3c00;  // missing scale: 1
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) oO[4 * (size_t)i + k] = orient ? gsr_f2h(orient[4 * (size_t)i + k]) : (uint16_t)(k == 3 ? 0x3c00 : 0);   // (0, 0, 0, 1)
-    if (sh.scheme == 0) return;
-    for (int j = 0; j < 16; ++j) {
-        float x = 0.0f, y = 0.0f, z = 0.0f;
-        bool have = false;
-        if (sh.scheme == 1) {
-            have = j < sh.vec3_per_point;
-            if (have) { const float* v = sh.array + ((size_t)i * sh.vec3_per_point + j) * 3; x = v[0]; y = v[1]; z = v[2]; }
-        } else if (sh.scheme == 2) {
-            have = j < 15 && sh.ptr[j];
-            if (have) { const float* v = sh.ptr[j] + 3 * (size_t)i; x = v[0]; y = v[1]; z = v[2]; }
-        } else if (j < 15) {   // channel-major INRIA layout: (f_rest_j, f_rest_{j+15}, f_rest_{j+30}); a missing array leaves zeros
-            have = true;
-            x = sh.ptr[j] ? sh.ptr[j][i] : 0.0f; y = sh.ptr[j + 15] ? sh.ptr[j + 15][i] : 0.0f; z = sh.ptr[j + 30] ? sh.ptr[j + 30][i] : 0.0f;
-        }
-        // (a slot without data is a zero HALF, not the conversion of 0.0f: the same bits, said explicitly)
-        ox[16 * (size_t)i + j] = have ? gsr_f2h(x) : (uint16_t)0;
-        oy[16 * (size_t)i + j] = have ? gsr_f2h(y) : (uint16_t)0;
-        oz[16 * (size_t)i + j] = have ? gsr_f2h(z) : (uint16_t)0;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// K0u': k_update for float32 sources in DEVICE memory (gsr_update_device): the caller's rows are read once, quantised in registers
-// (gsr_f2h) and scattered to j = inv[first + t] -- no staging copy of the halves, and nothing crosses the link.  One workgroup = 64
-// splats, eight lanes per splat with k_update's roles; an array that is NULL is left as it is in HBM:
-//   q = 0      alpha -> geoA[j].w and colrow[j][0].w; Cd (three floats; or, SH without Cd, the resident Cd) -> LDS halves 48..50
-//   q = 1..6   floats [8 (q - 1), 8 (q - 1) + 8) of the splat's 3 * vpp SH floats (coefficient j, channel ch at float 3 j + ch) -> LDS
-//              half 16 ch + j: the x / y / z rows k_update loads; a slot j >= vpp is a zero half.  Then chunk q - 1 -> col[q - 1][j]
-//              and colrow[j][q]; Cd alone: lane 1 rewrites halves 0..2 of chunk 0 as k_update does
-//   q = 7      scale (three floats) and / or orient (four), the other from the resident geoB[j] -> geoB[j] with its extent bound
-// Every source value is ONE 4-byte load inside its array (rows are not 16-byte aligned: 15 vec3 are 180 bytes), and only rows
-// t < cnt are touched.  Per splat: 4 + 12 + 12 + 16 + 12 vpp bytes read of what is given (224 with everything at vpp = 15) against
-// k_update's 122 of halves; the bytes written are k_update's (16 + 16 + 96 + 128 with everything, 4 + 4 + 16 + 16 for Cd + alpha
-// with SH).  The extent bound and the colour chunks come from gsr_extent_half / gsr_colour_chunk, the functions of k_pack.
-struct GsrUpdateSrcF32 {
-    const float *alpha, *Cd, *scale, *orient, *sh;
-    int32_t vpp;                 // vec3 per point of sh: 1..16
-};
-template <bool SH>
-__global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_update_f32(uint32_t first, uint32_t cnt, uint32_t cap, GsrUpdateSrcF32 src, const uint32_t* __restrict__ inv,
-             float4* __restrict__ geoA, uint4* __restrict__ geoB, uint4* __restrict__ col, uint4* __restrict__ colrow)
-{
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad), as in k_pack
-    const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
-    const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
-    const bool live = t < cnt;
-    const uint32_t j = live ? (inv ? inv[first + t] : first + t) : 0u;
-    const bool sh = SH && src.sh;
-    auto pk = [](uint16_t lo, uint16_t hi) { return (uint32_t)lo | ((uint32_t)hi << 16); };
-    if (live) {
-        if (q == 0) {
-            if (src.alpha) {
-                const float op = src.alpha[t];
-                reinterpret_cast<float*>(geoA + j)[3] = op;
-                if (SH) reinterpret_cast<float*>(colrow + (size_t)j * 8)[3] = op;
-            }
-            if (src.Cd) {
-                const float* cd = src.Cd + 3 * (size_t)t;
-                s_h[sp][48] = gsr_f2h(cd[0]); s_h[sp][49] = gsr_f2h(cd[1]); s_h[sp][50] = gsr_f2h(cd[2]);
-            } else if (sh) {                           // new SH under the resident Cd: halves 0..2 of chunk 0
-                const uint2 w = *reinterpret_cast<const uint2*>(col + j);
-                s_h[sp][48] = (uint16_t)(w.x & 0xffffu); s_h[sp][49] = (uint16_t)(w.x >> 16); s_h[sp][50] = (uint16_t)(w.y & 0xffffu);
-            }
-        } else if (q == 7) {
-            if (src.scale || src.orient) {
-                uint4 b = make_uint4(0u, 0u, 0u, 0u);
-                if (!src.scale || !src.orient) b = geoB[j];
-                uint16_t s0 = (uint16_t)(b.x & 0xffffu), s1 = (uint16_t)(b.x >> 16), s2 = (uint16_t)(b.y & 0xffffu);
-                uint16_t o0 = (uint16_t)(b.y >> 16), o1 = (uint16_t)(b.z & 0xffffu), o2 = (uint16_t)(b.z >> 16), o3 = (uint16_t)(b.w & 0xffffu);
-                if (src.scale) { const float* s = src.scale + 3 * (size_t)t; s0 = gsr_f2h(s[0]); s1 = gsr_f2h(s[1]); s2 = gsr_f2h(s[2]); }
-                if (src.orient) { const float* o = src.orient + 4 * (size_t)t; o0 = gsr_f2h(o[0]); o1 = gsr_f2h(o[1]); o2 = gsr_f2h(o[2]); o3 = gsr_f2h(o[3]); }
-                geoB[j] = make_uint4(pk(s0, s1), pk(s2, o0), pk(o1, o2), pk(o3, gsr_extent_half(s0, s1, s2, o0, o1, o2, o3)));
-            }
-        } else if (sh) {
-            const int nf = 3 * src.vpp;                // floats of a splat's row (<= 48)
-            const float* row = src.sh + (size_t)t * (size_t)nf;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int f = 8 * (q - 1) + k, co = f / 3, chn = f - 3 * co;
-                // (a slot without data is a zero HALF, as k_quantize_raw leaves it)
-                s_h[sp][16 * chn + co] = f < nf ? gsr_f2h(row[f]) : (uint16_t)0;
-            }
-        }
-    }
-    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!live) return;
-    if (sh) {
-        if (q >= 1 && q <= 6) {
-            const uint4 v = gsr_colour_chunk<true>(s_h[sp], q - 1);
-            col[(size_t)(q - 1) * cap + j] = v;
-            colrow[(size_t)j * 8 + q] = v;
-        }
-    } else if (q == 1 && src.Cd) {
-        const uint32_t w0 = pk(s_h[sp][48], s_h[sp][49]), c2 = s_h[sp][50];
-        if (SH) {
-            uint4 v = col[j];
-            v.x = w0; v.y = (v.y & 0xffff0000u) | c2;
-            col[j] = v;
-            colrow[(size_t)j * 8 + 1] = v;
-        } else {
-            col[j] = make_uint4(w0, c2, 0u, 0u);
-        }
-    }
-}
+// (K1 uses nothing of it; included HERE so that K0's kernels keep their places in the code object)
+#include "k_resident.h"
 
 // ---------------------------------------------------------------------------
 // SH evaluation for one channel; expressions are written and associated exactly

@@ -1,37 +1,27 @@
 // k_read.h -- K0r: the resident cloud read back in UPLOAD order (gsr_read, gsr_read_device): k_pack run backwards, in
 // k_update's shape.  Rows [0, cnt) of the destination arrays get the attributes of the splats [first, first + cnt) of the upload:
 //   row t  <-  storage slot j = inv[first + t]     (inv: upload index -> storage slot, the inverse of perm; NULL: upload order)
-// One workgroup of GSR_PACK_THREADS = 64 rows, eight lanes per splat with k_pack's roles, a splat's eight lanes in ONE wave.
+// One workgroup of GSR_PACK_THREADS = 64 rows, k_resident.h's lane roles.
 // LOADS (a lane whose piece feeds no array that is wanted loads nothing; the wanted set is uniform: it sits in the argument segment):
 //   SH and a colour array wanted:  lane q = 0..6 loads piece q of the splat's 128-byte colrow line (ONE request per splat: piece 0 is
 //                                  geoA[j] bit for bit, pieces 1..6 the colour chunks), lane 7 geoB[j]
 //   otherwise:                     lane 0 geoA[j], lane 1 col[j] (chunk 0: Cd), lane 7 geoB[j] -- a P-only read touches 16 bytes per splat
 //   a visibility in force:         lane 0 takes the alpha from alpha0[first + t] (the TRUE alphas, upload order: a coalesced read), not
 //                                  from the resident .w, which is +0.0f for a hidden splat
-// TRANSPOSE (SH arrays wanted): lanes 1..6 put the eight halves of chunk q - 1 into the splat's LDS row x[16] y[16] z[16] -- the
-// inverse of gsr_colour_chunk's index rule, gsr_colour_half_slot below -- and the row is read back as k_pack wrote it.  The row is
-// written and read by one wave: wave-local fences, no workgroup barrier.  Index 15 of the x / y / z rows (slot 15 of a 16-slot sh
-// row) is not resident -- k_pack never reads it -- and comes back as a zero half (+0.0f).
+// TRANSPOSE (SH arrays wanted): lanes 1..6 put the eight halves of chunk q - 1 into the splat's LDS row by gsr_colour_half_slot, the
+// rule gsr_colour_chunk reads it by, and the row is read back as k_pack wrote it.  Whole splats behind cnt leave in front of the sync.
+// Index 15 of the x / y / z rows (slot 15 of a 16-slot sh row) is not resident -- k_pack never reads it -- and comes back as a zero
+// half (+0.0f).
 // STORES (plain vector stores; only rows t < cnt are touched):
 //   halves (F32 = false; the destinations are the verb's own 256-byte aligned device rows in gsr_upload_append's layout):
 //     lane 0 P (3 x 4 B) + alpha (4 B); lane 1 Cd (3 x 2 B: halves 0..2 of chunk 0); lanes 1..6 16 bytes of the x / y / z rows;
 //     lane 7 scale (3 x 2 B) + orient (8 B)
 //   float32 (F32 = true; the caller's arrays, gsr_device_attrs' layout; every half as the float32 of exactly that value, gsr_h2f):
 //     every value is ONE 4-byte store inside its array (rows are not 16-byte aligned: 15 vec3 are 180 bytes); lanes 1..6 store floats
-//     [8 (q - 1), 8 (q - 1) + 8) of the splat's 3 * vpp floats (coefficient slot s, channel ch at float 3 s + ch <- LDS half 16 ch + s);
-//     slots >= vpp are not written out
+//     [8 (q - 1), 8 (q - 1) + 8) of the splat's 3 * vpp floats (float f <- LDS half gsr_sh_float_slot(f)); slots >= vpp are not written out
 // Per splat with everything: 128 + 16 bytes read, 122 (halves) or 64 + 12 vpp (float32) written.  Nothing resident is written.
 #pragma once
-#include "k_preprocess.h"
-
-// Where half k of colour chunk c belongs in a splat's LDS row x[16] y[16] z[16] Cd[3]: the inverse of gsr_colour_chunk's rule (half
-// hh = 8 c + k is coefficient co = hh / 3, channel chn = hh - 3 co; coefficient 0 is Cd, coefficient co >= 1 sits at flat index
-// co - 1 of its channel's row).
-__device__ __forceinline__ int gsr_colour_half_slot(int c, int k)
-{
-    const int hh = 8 * c + k, co = hh / 3, chn = hh - 3 * co;
-    return co == 0 ? 48 + chn : 16 * chn + (co - 1);
-}
+#include "k_resident.h"
 
 template <bool F32> struct GsrReadDst;
 template <> struct GsrReadDst<false> {      // device rows in gsr_upload_append's layout (NULL: not wanted)
@@ -52,7 +42,7 @@ k_unpack(uint32_t first, uint32_t cnt, GsrReadDst<F32> dst, const uint32_t* __re
          const float* __restrict__ alpha0)
 {
     static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = 64 rows, eight lanes per splat");
-    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][56];   // per splat: x[16] y[16] z[16] Cd[3] (+ pad), as in k_pack
+    __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][GSR_ROW_HALVES];
     const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
     const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
     if (t >= cnt) return;              // (whole splats leave: the lanes that meet at the wave barrier below are those that stay)
@@ -65,14 +55,12 @@ k_unpack(uint32_t first, uint32_t cnt, GsrReadDst<F32> dst, const uint32_t* __re
         if (q == 7) { if (shape) piece = geoB[j]; }
         else if (q == 0 ? geo : (q == 1 || sh)) piece = colrow[(size_t)j * 8 + q];
     } else if (q == 0) {
-        if (geo) { const float4 a = geoA[j]; piece = make_uint4(__float_as_uint(a.x), __float_as_uint(a.y), __float_as_uint(a.z), __float_as_uint(a.w)); }
+        if (geo) piece = gsr_as_uint4(geoA[j]);
     } else if (q == 1) {
         if (colour) piece = col[j];
     } else if (q == 7) {
         if (shape) piece = geoB[j];
     }
-    auto lo16 = [](uint32_t w) { return (uint16_t)(w & 0xffffu); };
-    auto hi16 = [](uint32_t w) { return (uint16_t)(w >> 16); };
     if (q == 0) {
         if (dst.P) {
             float* p = dst.P + 3 * (size_t)t;
@@ -81,45 +69,39 @@ k_unpack(uint32_t first, uint32_t cnt, GsrReadDst<F32> dst, const uint32_t* __re
         if (dst.alpha) dst.alpha[t] = alpha0 ? alpha0[first + t] : __uint_as_float(piece.w);
         if (sh) { s_h[sp][15] = 0; s_h[sp][31] = 0; s_h[sp][47] = 0; }       // (the index no chunk holds)
     } else if (q == 7) {
-        const uint16_t s0 = lo16(piece.x), s1 = hi16(piece.x), s2 = lo16(piece.y);
+        const GsrShape h = gsr_shape_split(piece);
         if constexpr (F32) {
-            if (dst.scale) { float* s = dst.scale + 3 * (size_t)t; s[0] = gsr_h2f(s0); s[1] = gsr_h2f(s1); s[2] = gsr_h2f(s2); }
-            if (dst.orient) {
-                float* o = dst.orient + 4 * (size_t)t;
-                o[0] = gsr_h2f(hi16(piece.y)); o[1] = gsr_h2f(lo16(piece.z)); o[2] = gsr_h2f(hi16(piece.z)); o[3] = gsr_h2f(lo16(piece.w));
-            }
+            if (dst.scale) { float* s = dst.scale + 3 * (size_t)t; s[0] = gsr_h2f(h.s0); s[1] = gsr_h2f(h.s1); s[2] = gsr_h2f(h.s2); }
+            if (dst.orient) { float* o = dst.orient + 4 * (size_t)t; o[0] = gsr_h2f(h.o0); o[1] = gsr_h2f(h.o1); o[2] = gsr_h2f(h.o2); o[3] = gsr_h2f(h.o3); }
         } else {
-            if (dst.scale) { uint16_t* s = dst.scale + 3 * (size_t)t; s[0] = s0; s[1] = s1; s[2] = s2; }
+            if (dst.scale) { uint16_t* s = dst.scale + 3 * (size_t)t; s[0] = h.s0; s[1] = h.s1; s[2] = h.s2; }
             // (orient rows are 8 bytes in a 256-byte aligned section; the extent half, the high half of .w, is derived and stays behind)
             if (dst.orient) *reinterpret_cast<uint2*>(dst.orient + 4 * (size_t)t) = make_uint2((piece.y >> 16) | (piece.z << 16), (piece.z >> 16) | (piece.w << 16));
         }
     } else {
         if (q == 1 && dst.Cd) {        // halves 0..2 of chunk 0
-            if constexpr (F32) { float* c = dst.Cd + 3 * (size_t)t; c[0] = gsr_h2f(lo16(piece.x)); c[1] = gsr_h2f(hi16(piece.x)); c[2] = gsr_h2f(lo16(piece.y)); }
-            else { uint16_t* c = dst.Cd + 3 * (size_t)t; c[0] = lo16(piece.x); c[1] = hi16(piece.x); c[2] = lo16(piece.y); }
+            if constexpr (F32) { float* c = dst.Cd + 3 * (size_t)t; c[0] = gsr_h2f(gsr_lo16(piece.x)); c[1] = gsr_h2f(gsr_hi16(piece.x)); c[2] = gsr_h2f(gsr_lo16(piece.y)); }
+            else { uint16_t* c = dst.Cd + 3 * (size_t)t; c[0] = gsr_lo16(piece.x); c[1] = gsr_hi16(piece.x); c[2] = gsr_lo16(piece.y); }
         }
         if (sh) {
             const uint32_t w[4] = {piece.x, piece.y, piece.z, piece.w};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int at = gsr_colour_half_slot(q - 1, k);
-                if (at < 48) s_h[sp][at] = (k & 1) ? hi16(w[k >> 1]) : lo16(w[k >> 1]);      // (the Cd halves went out above)
+                if (at < 48) s_h[sp][at] = (k & 1) ? gsr_hi16(w[k >> 1]) : gsr_lo16(w[k >> 1]);      // (the Cd halves went out above)
             }
         }
     }
     if (!sh) return;
-    // (a splat's eight lanes sit in one wave: its LDS row is written and read by that wave only)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    gsr_wave_lds_sync();
     if (q < 1 || q > 6) return;
     if constexpr (F32) {
         const int nf = 3 * dst.vpp;                    // floats of a splat's row (<= 48)
         float* row = dst.sh + (size_t)t * (size_t)nf;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int f = 8 * (q - 1) + k, slot = f / 3, chn = f - 3 * slot;
-            if (f < nf) row[f] = gsr_h2f(s_h[sp][16 * chn + slot]);
+            const int f = 8 * (q - 1) + k;
+            if (f < nf) row[f] = gsr_h2f(s_h[sp][gsr_sh_float_slot(f)]);
         }
     } else {
         // lanes 1..6: x[0..7] x[8..15] y[0..7] y[8..15] z[0..7] z[8..15] (rows of 16 halves = 32 bytes, 16-byte stores)

@@ -1,11 +1,16 @@
 """Attribute updates without a GPU: the NULL-handle errors of gsr_update / gsr_multi_update, and the bookkeeping of
 GSplatRenderer::updateAttributes on a dry instance -- which upload-order range of the resident plan a registered row is, and that the
-row holds the new arrays for the next re-stage."""
+row holds the new arrays for the next re-stage -- and the resources the compiler gives the update kernels."""
 import ctypes as C
+import os
+import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GSR_E_INVALID = -1
 
 
@@ -126,3 +131,27 @@ def test_dry_shim_truncated_row_updates_what_is_resident(pkg):
         assert L.gsplat_renderer_row_array(h, ids[1], 2) == alpha.ctypes.data
     finally:
         L.gsplat_renderer_destroy(h)
+
+
+def test_update_kernels_stay_within_k_packs_budget():
+    """from the code object, as tools/kernel_resources.py reads it (a cross-compile: no GPU): both instantiations of k_update and of
+    k_update_f32, and k_cluster_extents, exist, use no scratch, and no more vector registers or LDS than k_pack<true> -- the kernel
+    whose shape (512 threads, eight lanes per splat, one LDS row per splat) the update kernels share"""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py")], capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    rows = {}
+    for ln in res.stdout.splitlines():
+        m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", ln)
+        if m:
+            rows[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
+
+    def find(prefix):
+        hit = [v for k, v in rows.items() if k.startswith(prefix)]
+        assert len(hit) == 1, (prefix, [k for k in rows if k.startswith(prefix)])
+        return hit[0]
+
+    pack = find("_Z6k_packILb1E")
+    for name in ("_Z8k_updateILb0E", "_Z8k_updateILb1E", "_Z12k_update_f32ILb0E", "_Z12k_update_f32ILb1E", "_Z17k_cluster_extents"):
+        vg, sg, lds, scratch = find(name)
+        print(f"{name}: vgpr {vg} sgpr {sg} lds {lds} scratch {scratch}; k_pack<true>: vgpr {pack[0]} lds {pack[2]}")
+        assert scratch == 0 and vg <= pack[0] and lds <= pack[2], (name, (vg, sg, lds, scratch), pack)
