@@ -3,6 +3,8 @@
 // (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end; the kernels that
 // write, edit and read the resident layout -- once per geometry change, not per frame -- in k_resident.h, k_visibility.h, k_remove.h,
 // k_add.h and k_read.h.)
+// What the context, its frame slots and an edit in progress allocate is held by the handles of gsr_host_buffers.h: a member that owns
+// is a handle, a raw pointer never owns.  There is no free list: gsr_destroy deletes the context, and a call that fails returns.
 //
 // Pipeline per gsr_render (all on one HIP stream):
 //   k_cluster_cull         clusters of 64 Morton-ordered splats vs clip planes / screen / band / depth horizons (k_cluster.h)
@@ -127,111 +129,111 @@ struct FrameJob {
     GsrBgArgs bg{};                // a background (k_blend.h: k_blend_over): kind 0 = a frame without one; the image on the device
 };
 
-// Everything one frame in flight owns: its HIP stream, the per-frame HBM arrays, the small
+// A frame slot's arrays that are sized by the capacity, as a set of their own: gsr_upload_begin allocates them for a new capacity, and
+// gsr_add allocates the larger set before its first write and hands it over once nothing can fail for lack of memory any more.
+struct SlotSplatArrays {
+    DevMem<GsrRecord> rec;
+    DevMem<uint32_t> keyA, keyB;
+    DevMem<uint32_t> blk_cnt;          // splats each K1 workgroup kept (their keys/payloads head the workgroup's 256 slots)
+    DevMem<uint2> valA, valB;          // depth-sort payload: (splat index, packed tile rect)
+    DevMem<float> zwin;                // per-splat window depth (depth-tested frames)
+    DevMem<uint32_t> cseg;             // cluster culling (k_cluster.h): the ordered list of surviving clusters, as per-workgroup segments [ngroups * per]
+};
+
+// Everything one frame in flight owns: its HIP stream, the per-frame HBM arrays (the per-splat ones: SlotSplatArrays), the small
 // mailboxes and the stage events.  Two slots alternate, so that frame f+1's memory-bound front end
 // (k_preprocess, depth sort, binning) overlaps frame f's VALU-bound k_blend on the GPU.
-struct FrameSlot {
-    hipStream_t own = nullptr;         // the slot's private stream
-    hipStream_t stream = nullptr;      // the stream its frame runs on: `own` with two frames in flight; with strictly serial
-                                       // frames the context's PUBLIC stream itself (no hand-over events at all)
-    hipEvent_t ev_done = nullptr;      // end of the frame on `stream`
-    hipEvent_t ev_user = nullptr;      // caller's stream position at gsr_render entry
+struct FrameSlot : SlotSplatArrays {
+    Stream own;                        // the slot's private stream
+    hipStream_t stream = nullptr;      // (not owned) the stream its frame runs on: `own` with two frames in flight; with strictly
+                                       // serial frames the context's PUBLIC stream itself (no hand-over events at all)
+    Event ev_done;                     // end of the frame on `stream`
+    Event ev_user;                     // caller's stream position at gsr_render entry
     // host-target frames: the blend launch in bands of tile rows, each band's rows copied back while the next ones composite
-    hipEvent_t ev_band[GSR_HOST_BANDS_MAX] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    Event ev_band[GSR_HOST_BANDS_MAX];
     int bands = 0;                     // bands of the frame's last blend launch (0 / 1: one launch, one copy)
     int band_row[GSR_HOST_BANDS_MAX + 1] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    hipEvent_t ev_pairs = nullptr;     // the frame's pair count has reached host memory
-    // per-splat frame buffers
-    GsrRecord* rec = nullptr;
-    uint32_t *keyA = nullptr, *keyB = nullptr;
-    uint32_t* blk_cnt = nullptr;       // splats each K1 workgroup kept (their keys/payloads head the workgroup's 256 slots)
-    uint2 *valA = nullptr, *valB = nullptr;      // depth-sort payload: (splat index, packed tile rect)
-    uint32_t* d_n = nullptr;           // splats that survived culling = items after the first sort pass
-    float* zwin = nullptr;             // per-splat window depth (depth-tested frames)
+    Event ev_pairs;                    // the frame's pair count has reached host memory
+    DevMem<uint32_t> d_n;              // splats that survived culling = items after the first sort pass
     StageBuf depth_stage;              // device copy of a host depth buffer
-    float* dpyr = nullptr;             // depth-tested frames: the two tile-max pyramids of the opaque pass's depth (k_cluster.h), by
+    DevMem<float> dpyr;                // depth-tested frames: the two tile-max pyramids of the opaque pass's depth (k_cluster.h), by
     size_t dpyr_cap = 0;               // frame parity: [par][which], dpyr_cap floats each
-    uint32_t* dactive = nullptr;       // [2] by parity: "some tile's largest depth is below 1" (something can be culled)
+    DevMem<uint32_t> dactive;          // [2] by parity: "some tile's largest depth is below 1" (something can be culled)
     int dpar = 0;                      // parity of the slot's last depth-tested frame
     bool dpyr_built = false;           // the pyramids of parity `dpar` hold this frame's depth buffer (a frame that only LOOKED for covered pixels has none)
     bool sorted_dculled = false;       // the cached depth order holds a frame that was culled against its depth buffer
     // scan / sort scratch
-    uint32_t* hist = nullptr;
+    DevMem<uint32_t> hist;
     size_t hist_cap = 0;
-    uint32_t* totals = nullptr;        // [512] per-digit totals of the current radix pass
+    DevMem<uint32_t> totals;           // [512] per-digit totals of the current radix pass
     // pairs
-    uint2* pvA = nullptr;                        // super-tile lists: (splat index, tile column/row mask) per entry
+    DevMem<uint2> pvA;                           // super-tile lists: (splat index, tile column/row mask) per entry
     size_t pair_cap = 0;
-    int32_t *sstart = nullptr, *send = nullptr;  // super-tile ranges
-    uint4* tile_work = nullptr;        // per tile: entries scanned, records gathered, wave-record evaluations
+    DevMem<int32_t> sstart, send;                // super-tile ranges
+    DevMem<uint4> tile_work;           // per tile: entries scanned, records gathered, wave-record evaluations
     size_t tile_cap = 0;
     // front-slab frames
-    uint4* tile_work_a = nullptr;      // phase 1's per-tile bookkeeping (tile_cap entries)
-    float* tbuf = nullptr;             // per pixel of the band: the transmittance phase 1 left
+    DevMem<uint4> tile_work_a;         // phase 1's per-tile bookkeeping (tile_cap entries)
+    DevMem<float> tbuf;                // per pixel of the band: the transmittance phase 1 left
     size_t tbuf_cap = 0;
-    float* hpyr2 = nullptr;            // the pyramid of "this tile is finished" phase 2 culls against (GSR_PYR_FLOATS)
-    uint32_t* slab = nullptr;          // [GSR_SLAB_BINS + 8] histogram of the surviving clusters' nearest keys; then [0] the slab key, [1] clusters,
+    DevMem<float> hpyr2;               // the pyramid of "this tile is finished" phase 2 culls against (GSR_PYR_FLOATS)
+    DevMem<uint32_t> slab;             // [GSR_SLAB_BINS + 8] histogram of the surviving clusters' nearest keys; then [0] the slab key, [1] clusters,
                                        // [2..5] the bucket ranges of the two phases' small-frame sorts (k_slab_pick)
     bool slab_dirty = false;           // a phase 1 filled the histogram and no phase 2 followed (its cull pass is what clears it): the
                                        // next front-slab frame clears it itself before it counts
-    int32_t* redo = nullptr;           // lazy colour: tiles the plain blend kernel gave up (tile_cap entries)
-    int32_t* order = nullptr;          // blockIdx -> tile, heaviest tiles first: written by k_tile_order at the end of a frame
+    DevMem<int32_t> redo;              // lazy colour: tiles the plain blend kernel gave up (tile_cap entries)
+    DevMem<int32_t> order;             // blockIdx -> tile, heaviest tiles first: written by k_tile_order at the end of a frame
     size_t order_cap = 0;              //   for this slot's next frame (valid while the tile geometry stays what it was)
     bool order_valid = false;
     int order_age = 0;                 // frames the table has stood (tiles alike: it is rebuilt every opt_order_keep frames only)
     int order_sig[6] = {0, 0, 0, 0, 0, 0}, order_per_xcd = 0;
-    uint32_t* st_scan = nullptr;       // [512] per super-tile: deepest scan of its opaque tiles / "a tile stayed open" (k_tile_pass -> k_sum_work)
-    GsrTilePartial* partial = nullptr; // [4096] per 8x8-tile block: partial sums of the frame's counters (k_tile_pass -> k_sum_work)
-    uint32_t* sup_work = nullptr;      // [2][256] per-super-tile work sums of the blend kernel, by frame parity
+    DevMem<uint32_t> st_scan;          // [512] per super-tile: deepest scan of its opaque tiles / "a tile stayed open" (k_tile_pass -> k_sum_work)
+    DevMem<GsrTilePartial> partial;    // [4096] per 8x8-tile block: partial sums of the frame's counters (k_tile_pass -> k_sum_work)
+    DevMem<uint32_t> sup_work;         // [2][256] per-super-tile work sums of the blend kernel, by frame parity
     int sup_par = 0;
     // Depth horizons (occlusion culling): per TILE, the distance^2 beyond which this slot's NEXT frame needs nothing -- a max
     // pyramid written by k_sum_work at the end of every frame from how deep the frame's tiles had to look.  A culled frame is
     // checked there too (did a tile look past the horizon its splats were culled against?); the verdict goes to the mapped word
     // h_end, and the host renders a frame that failed again, without culling, before it hands it over.
-    float* hpyr = nullptr;             // pyramid levels 0..3 (k_cluster.h), GSR_PYR_FLOATS floats: what the slot's next frame culls against
-    float* hpyr_next = nullptr;        // ... double-buffered: a frame's last kernels read the one it was culled against while they fill the other
-    float* hraw = nullptr;             // per-tile horizons before dilation (k_tile_pass -> k_horizon_dilate)
-    float* hstat = nullptr;            // per tile: every tile of its neighbourhood was "classic" in the frame that left the horizons (k_blend.h: GsrHorizonArgs.stat)
+    DevMem<float> hpyr;                // pyramid levels 0..3 (k_cluster.h), GSR_PYR_FLOATS floats: what the slot's next frame culls against
+    DevMem<float> hpyr_next;           // ... double-buffered: a frame's last kernels read the one it was culled against while they fill the other
+    DevMem<float> hraw;                // per-tile horizons before dilation (k_tile_pass -> k_horizon_dilate)
+    DevMem<float> hstat;               // per tile: every tile of its neighbourhood was "classic" in the frame that left the horizons (k_blend.h: GsrHorizonArgs.stat)
     bool hstat_valid = false;          // ... written by a depth-tested frame's end (as old as the horizons)
-    uint32_t* dbg_viol = nullptr;      // GSR_DEBUG_VIOL in the environment: which tiles broke their promise (k_tile_pass)
+    DevMem<uint32_t> dbg_viol;         // GSR_DEBUG_VIOL in the environment: which tiles broke their promise (k_tile_pass)
     int hpyr_re = 0;                   // the dilation radius built into hpyr
-    // cluster culling (k_cluster.h): the ordered list of surviving clusters of the frame, as per-workgroup segments
-    uint32_t* cseg = nullptr;          // [ngroups * per]
-    uint32_t* ccnt = nullptr;          // [CC_MAX_GROUPS]
-    uint32_t* d_counts = nullptr;      // [0] slots K1 filled, [1] surviving clusters, [2] the small-frame sort gave a bucket up
-    uint32_t* bkt_key = nullptr;       // small-frame sort (k_sort.h): the bucket regions, BK_BUCKETS x BK_CAP keys ...
-    uint2* bkt_val = nullptr;          // ... and payloads
-    uint32_t* bkt_cnt = nullptr;       // ... and the bucket counters, BK_STRIDE apart
+    DevMem<uint32_t> ccnt;             // cluster culling: [CC_MAX_GROUPS] the segments' counts
+    DevMem<uint32_t> d_counts;         // [0] slots K1 filled, [1] surviving clusters, [2] the small-frame sort gave a bucket up
+    DevMem<uint32_t> bkt_key;          // small-frame sort (k_sort.h): the bucket regions, BK_BUCKETS x BK_CAP keys ...
+    DevMem<uint2> bkt_val;             // ... and payloads
+    DevMem<uint32_t> bkt_cnt;          // ... and the bucket counters, BK_STRIDE apart
     GsrSlotHints hints;                // what the slot's last frame kept, from how many clusters, between which keys (gsr_frame_plan.h)
     GsrLocalSortPolicy local_pol;      // back-off of the small-frame sort (gsr_policy.h): a run of > 64 equal keys defeats it EVERY frame
-    unsigned long long* h_end = nullptr;      // pinned + mapped: ticket << 32 | violation
+    PinnedMem<unsigned long long> h_end;      // pinned + mapped: ticket << 32 | violation
     // GSR_OPT_ROW_WORK: per global tile row, ticket << 32 | blend work of the row (k_blend.h: k_row_work), pinned + mapped + coherent,
     // GSR_MAX_TILES_SIDE words; allocated when the option is switched on
-    unsigned long long* h_rows = nullptr;
-    unsigned long long* h_rows_dev = nullptr;
+    PinnedMem<unsigned long long> h_rows;
     uint32_t rows_ticket = 0;          // ticket of the attempt whose frame end queued the slot's last k_row_work (0: none yet)
     int rows_tiles_y = 0;              // ... and the tile rows of its image
-    unsigned long long* h_end_dev = nullptr;
     bool horizon_valid = false;
     int horizon_sig[7] = {0, 0, 0, 0, 0, 0, 0};   // tile geometry + geometry generation the horizons belong to
     gsr_camera horizon_cam{};                     // ... and the camera of the frame that left them (camera_jumped)
     bool sorted_culled = false;        // the cached depth order holds a culled frame's splats only
-    unsigned long long* lazy_ctr = nullptr;   // [0] low word: redo count of the frame, [1]: colours evaluated (running)
-    uint32_t* colour_evals = nullptr;         // [256] colours evaluated per super-tile list (this frame; folded into lazy_ctr[1])
+    DevMem<unsigned long long> lazy_ctr;      // [0] low word: redo count of the frame, [1]: colours evaluated (running)
+    DevMem<uint32_t> colour_evals;            // [256] colours evaluated per super-tile list (this frame; folded into lazy_ctr[1])
     bool last_lazy = false;            // the last frame of this slot left colours pending
     StageBuf fb;                       // staging for host-pointer output: pixels of the context's target format; cleared per band shape and format
     StageBuf aovb;                     // staging for a host-pointer AOV plane: two floats per band pixel; cleared per band shape
-    float* fb32 = nullptr;             // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
+    DevMem<float> fb32;                // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
     size_t fb32_cap = 0;
     StageBuf bgb;                      // device copy of a host background image: per slot, staged anew by every attempt of a frame
     // small device/host mailboxes
-    unsigned long long* counters = nullptr;  // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
+    DevMem<unsigned long long> counters;     // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
                                              // scanned, [5] wave-record evaluations (running)
-    unsigned long long* h_total = nullptr;      // pinned + mapped + coherent [4]: k_bin_ranges writes (frame ticket << 32 | pair count), hints, survivors
-    unsigned long long* h_total_dev = nullptr;  // its device-side address
+    PinnedMem<unsigned long long> h_total;      // pinned + mapped + coherent [4]: k_bin_ranges writes (frame ticket << 32 | pair count), hints, survivors
     uint32_t ticket = 0;                        // ticket of the frame queued last in this slot
-    unsigned long long* h_counters = nullptr;  // host copy of the frame's bookkeeping (fetched from d_frame when stats are asked for)
-    unsigned long long* d_frame = nullptr;     // device: k_sum_work's per-frame summary [8]
+    PinnedMem<unsigned long long> h_counters;  // host copy of the frame's bookkeeping (fetched from d_frame when stats are asked for)
+    DevMem<unsigned long long> d_frame;        // device: k_sum_work's per-frame summary [8]
     // depth-sort cache: the frame description whose order is in (keyA, valA)
     bool sort_valid = false;
     SortKey sort_key{};
@@ -243,16 +245,15 @@ struct FrameSlot {
     uint32_t last_pairs = 0;
     int super_tile = 0, stiles_x = 0, stiles_y = 0;
     uint64_t frame_id = 0;             // 1-based id of that frame, 0 = never used
-    hipEvent_t ev[GSR_STAGE_EVENTS];
+    Event ev[GSR_STAGE_EVENTS];
     bool ev_pending = false;
     bool ev_all = false;             // all seven stage events were recorded (timing level 2), not just the blend kernel's
-    bool ev_ok = false;
 };
 
 struct gsr_context {
     int device = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;      // the PUBLIC stream: results are ordered on it
+    Stream own_stream;
+    hipStream_t stream = nullptr;      // (not owned) the PUBLIC stream: results are ordered on it
 
     // geometry (SoA of 16-byte vectors), shared read-only by the frame slots
     uint32_t n = 0, cap = 0;
@@ -261,26 +262,26 @@ struct gsr_context {
     uint64_t geo_gen = 0;              // generation of the resident geometry: only ever counts up (cached orders, horizons, the wire overlay's
                                        // inverse permutation are stamped with it), so a stamp of an older cloud can never match a newer one
     bool has_geometry = false;         // a complete upload is resident (gsr_render: GSR_E_NO_GEOMETRY otherwise)
-    float4* geoA = nullptr;
-    uint4* geoB = nullptr;
-    uint4* col = nullptr;              // colour halves as SoA chunks (eager colour in K1)
-    uint4* colrow = nullptr;           // ... and as one contiguous row per splat (lazy colour gathers by index)
+    DevMem<float4> geoA;
+    DevMem<uint4> geoB;
+    DevMem<uint4> col;                 // colour halves as SoA chunks (eager colour in K1)
+    DevMem<uint4> colrow;              // ... and as one contiguous row per splat (lazy colour gathers by index)
     int col_chunks = 0;
     // gsr_move: the SPARE copy of the planes (at the capacity c->cap) that k_repack writes the new storage order into; the two sets are
     // then swapped by pointer.  Allocated at the first move that re-orders, kept until the geometry is freed or an add grows the
     // capacity (gsr_add: the set it leaves as the spare one is at the old capacity and is freed); the spare cluster bounds (nclus
     // entries) go whenever an upload gives the live ones up, and after every add (they are the smaller cloud's).
-    float4* geoA2 = nullptr;
-    uint4 *geoB2 = nullptr, *col2 = nullptr, *colrow2 = nullptr;
-    float4 *clusA2 = nullptr, *clusB2 = nullptr;
+    DevMem<float4> geoA2;
+    DevMem<uint4> geoB2, col2, colrow2;
+    DevMem<float4> clusA2, clusB2;
     // spatially ordered storage (k_cluster.h): storage slot j holds the perm[j]-th splat of the upload; clusters of 64 slots
-    uint32_t* perm = nullptr;          // NULL = upload order
+    DevMem<uint32_t> perm;             // NULL = upload order
     std::vector<int32_t> h_perm;       // host copy (debug read-backs un-permute through it), fetched on demand
-    float4 *clusA = nullptr, *clusB = nullptr;
+    DevMem<float4> clusA, clusB;
     uint32_t nclus = 0;
-    uint32_t* prefix = nullptr;        // lazy colour: per super-tile, list entries to colour next frame (k_sum_work writes it)
-    uint32_t* prefix_all = nullptr;    // 256 x 0xffffffff: colour every list completely (first frame, debug read-back)
-    uint32_t* prefix_none = nullptr;   // 256 x 0: colour nothing ahead of time (GSR_FLAG_LAZY_NO_PREFIX: every tile takes the fallback)
+    DevMem<uint32_t> prefix;           // lazy colour: per super-tile, list entries to colour next frame (k_sum_work writes it)
+    DevMem<uint32_t> prefix_all;       // 256 x 0xffffffff: colour every list completely (first frame, debug read-back)
+    DevMem<uint32_t> prefix_none;      // 256 x 0: colour nothing ahead of time (GSR_FLAG_LAZY_NO_PREFIX: every tile takes the fallback)
     bool prefix_valid = false;
     bool uploading = false;
     uint32_t up_total = 0, up_filled = 0;
@@ -290,27 +291,27 @@ struct gsr_context {
 
     FrameSlot slot[GSR_MAX_SLOTS];
     // position-keyed order (GSR_OPT_SORT_CACHE = 2): all splats in depth order for one camera position
-    uint32_t* pos_order = nullptr;
+    DevMem<uint32_t> pos_order;
     size_t pos_cap = 0;
     bool pos_valid = false;
     uint64_t pos_gen = 0;
     float pos_cam[3] = {0, 0, 0}, last_cam[3] = {0, 0, 0};
     uint32_t pos_kmin = 0, pos_kmax = 0;
     bool last_cam_set = false;
-    uint32_t* blk_pre = nullptr;       // exclusive prefix of K1's per-iteration counts (k_scan_counts)
+    DevMem<uint32_t> blk_pre;          // exclusive prefix of K1's per-iteration counts (k_scan_counts)
     size_t blk_pre_cap = 0;
     int opt_order_keep = 32;           // (A/B hook, GSR_ORDER_KEEP in the environment: 0 = no tile order where the tiles are alike)
     int opt_fuse_order = 1;            // (A/B hook, GSR_FUSE_ORDER) the tile order is built in the frame-end launch instead of behind it
     int opt_mid_sort = 1;              // (A/B hook, GSR_MID_SORT) RS_ITEMS_MID keys per thread in the global sort passes of mid-size frames
     int opt_host_bands = 4;            // (A/B hook, GSR_HOST_BANDS) host-target frames: bands of tile rows whose copy-back overlaps the compositing of the next (1: off)
-    hipStream_t copy_stream = nullptr; // ... and the stream the copies run on
+    Stream copy_stream;                // ... and the stream the copies run on
     int opt_k1_scatter = 1;            // (A/B hook, GSR_K1_SCATTER) the small-frame sort's bucket pass inside K1 (0: a kernel of its own behind it)
     int opt_scatter_direct = 1;        // (A/B hook, GSR_SCATTER_DIRECT in the environment) the small-frame sort's scatter: one workgroup per K1 block
     int opt_bn_items = 0;              // (A/B hook, GSR_BN_ITEMS in the environment: 1, 2 or 4 splats per binning thread; 0 = by frame size)
     int nslots = 1;                    // frames in flight (GSR_OPT_FRAMES_IN_FLIGHT): serial by default -- occlusion culling wants the
                                        // horizons of the frame just before, and two slots hand it those of the frame before that
 
-    int32_t* tile_map = nullptr;       // blockIdx -> tile (XCD-aware order), -1 = idle block
+    DevMem<int32_t> tile_map;          // blockIdx -> tile (XCD-aware order), -1 = idle block
     size_t map_cap = 0;
     int map_w = 0, map_h = 0, map_si = -1, map_sc = 0, map_rpb = -1, map_first = -1, map_shift = -1, map_grid = 0;
 
@@ -329,7 +330,7 @@ struct gsr_context {
     uint64_t frame_no = 0;
     size_t pair_want = 0;              // largest list buffer any frame slot needed so far
     int64_t lazy_base = 0;             // lazy_colours_total at the last gsr_stats_reset
-    uint32_t* lazy_hint = nullptr;     // device: would lazy colour pay? (k_sum_work -> k_bin_ranges -> mailbox -> lazy_pays)
+    DevMem<uint32_t> lazy_hint;        // device: would lazy colour pay? (k_sum_work -> k_bin_ranges -> mailbox -> lazy_pays)
     bool lazy_pays = false;
     GsrCullPolicy cull_pol;            // occlusion culling: pays / weak / hold-off / back-off / dilation radius (gsr_policy.h; DESIGN.md section 4's state table)
     GsrSlabPolicy slab_pol;            // front-slab frames: held off for 256 frames after one that kept more than a third of an unculled frame (B1 at 0.46 loses 9 %)
@@ -338,36 +339,36 @@ struct gsr_context {
                                        // builds its depth pyramid in a launch of its own, IN FRONT of k_cluster_cull (which then culls against it
                                        // too); otherwise the pyramid is built beside the cluster tests, for K1 alone (no extra launch)
     bool order_pays = false;           // k_sum_work's other verdict: the tiles differ enough in work for k_tile_order to pay
-    unsigned long long* wire_zbuf = nullptr;   // wireframe overlay: (depth bits, splat index) per pixel ...
-    float* wire_out = nullptr;                 // ... and the image staged for a host target
-    uint32_t* wire_inv = nullptr;              // ... and, with spatially ordered storage, upload index -> storage slot (built on first use per geometry; gsr_update scatters through it too)
+    DevMem<unsigned long long> wire_zbuf;      // wireframe overlay: (depth bits, splat index) per pixel ...
+    DevMem<float> wire_out;                    // ... and the image staged for a host target
+    DevMem<uint32_t> wire_inv;                 // ... and, with spatially ordered storage, upload index -> storage slot (built on first use per geometry; gsr_update scatters through it too)
     uint64_t wire_inv_gen = 0;
     size_t wire_cap = 0;                       // pixels both hold
     // An upload in progress.  The registerUpdate()-layout arrays of ALL its entries sit in one device arena (sized at gsr_upload_begin,
     // kept between uploads: an animated sequence re-stages every cook), in upload order; gsr_upload_end orders and packs them (k_pack).
-    char* stage = nullptr;
+    DevMem<char> stage;
     size_t stage_cap = 0;
-    char* stage_raw = nullptr;                 // ... and the raw float arrays of ONE gsr_upload_append_raw call (quantised into the arena)
+    DevMem<char> stage_raw;                    // ... and the raw float arrays of ONE gsr_upload_append_raw call (quantised into the arena)
     size_t stage_raw_cap = 0;
-    uint32_t *up_kA = nullptr, *up_kB = nullptr, *up_vA = nullptr, *up_vB = nullptr;   // Morton codes / upload indices, ping-pong (kept between uploads)
+    DevMem<uint32_t> up_kA, up_kB, up_vA, up_vB;   // Morton codes / upload indices, ping-pong (kept between uploads)
     size_t up_sort_cap = 0;
-    float* up_part = nullptr;                  // bounding-box partials
-    hipEvent_t up_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevMem<float> up_part;                     // bounding-box partials
+    Event up_ev[4];
     double up_t_begin = 0.0, up_h2d_ms = 0.0, up_quant_ms = 0.0;
     // gsr_set_visibility (k_visibility.h): the rule in force, the TRUE alphas in upload order (one float per splat of capacity, valid
     // while vis_on: geoA holds +0.0f for the hidden splats), the mask of the resident cloud, and the counter slots of k_visibility.
     // (Behind everything a frame reads: the fields above lie where they lay before there was a visibility.)
     bool vis_on = false;               // volumes or a mask are in force: the hooks of upload / update / move run
     GsrVisRule vis{};
-    float* alpha0 = nullptr;
-    uint32_t* vis_mask = nullptr;      // ceil(n / 32) words, NULL: no mask
-    unsigned long long* vis_counters = nullptr;   // k_visibility's counter slots ...
-    unsigned long long* vis_h_counters = nullptr; // ... and where they are read back: pinned host memory, like the slots' read-backs
+    DevMem<float> alpha0;
+    DevMem<uint32_t> vis_mask;         // ceil(n / 32) words, NULL: no mask
+    DevMem<unsigned long long> vis_counters;      // k_visibility's counter slots ...
+    PinnedMem<unsigned long long> vis_h_counters; // ... and where they are read back: pinned host memory, like the slots' read-backs
     int64_t vis_hidden = 0;            // what the last application hid
     // gsr_remove (k_remove.h): the SECOND array of true alphas the compaction writes (swapped with alpha0 like the planes; only with a
     // visibility in force), the pinned words the survivor count arrives in, and what gsr_get_removal reports
-    float* alpha0_2 = nullptr;
-    uint32_t* rm_h_total = nullptr;
+    DevMem<float> alpha0_2;
+    PinnedMem<uint32_t> rm_h_total;
     int64_t rm_calls = 0, rm_last = 0;
     double rm_ms[4] = {0.0, 0.0, 0.0, 0.0};
     // gsr_add (k_add.h): what gsr_get_add reports (the capacity in force is c->cap)
@@ -427,6 +428,13 @@ extern "C" int gsr_device_count(void)
     return n;
 }
 
+extern "C" int gsr_debug_live_handles(int64_t out4[4])
+{
+    if (!out4) return set_err(GSR_E_INVALID, "gsr_debug_live_handles: out4 is NULL");
+    for (int k = 0; k < 4; ++k) out4[k] = g_live[k].load(std::memory_order_relaxed);
+    return GSR_OK;
+}
+
 extern "C" const char* gsr_last_error(void) { return g_err; }
 extern "C" const char* gsr_version(void) { return GSR_VERSION_STR; }
 
@@ -444,113 +452,56 @@ static int sync_all(gsr_context* c)
 
 static bool slot_init(FrameSlot& sl)
 {
-    bool ok = hipStreamCreateWithFlags(&sl.own, hipStreamNonBlocking) == hipSuccess;
+    const unsigned mailbox = hipHostMallocMapped | hipHostMallocCoherent;
+    const size_t tiles = (size_t)GSR_MAX_TILES_SIDE * GSR_MAX_TILES_SIDE;
+    bool ok = sl.own.create(hipStreamNonBlocking) == hipSuccess;
     sl.stream = sl.own;
-    ok = ok && hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&sl.ev_user, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&sl.ev_pairs, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.counters), 8 * sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.d_n), sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.d_n, 0, sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.totals), 512 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.lazy_ctr), 2 * sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMemset(sl.lazy_ctr, 0, 2 * sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.colour_evals), 256 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.colour_evals, 0, 256 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.hpyr), GSR_PYR_FLOATS * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.hpyr_next), GSR_PYR_FLOATS * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.hraw), (size_t)GSR_MAX_TILES_SIDE * GSR_MAX_TILES_SIDE * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.hstat), (size_t)GSR_MAX_TILES_SIDE * GSR_MAX_TILES_SIDE * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.hpyr2), GSR_PYR_FLOATS * sizeof(float)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.slab), (GSR_SLAB_BINS + 8) * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.slab, 0, (GSR_SLAB_BINS + 8) * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.ccnt), CC_MAX_GROUPS * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.bkt_key), (size_t)BK_BUCKETS * BK_CAP * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.bkt_val), (size_t)BK_BUCKETS * BK_CAP * sizeof(uint2)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.bkt_cnt), (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.bkt_cnt, 0, (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.d_counts), 4 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.d_counts, 0, 4 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&sl.h_end), sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-    if (ok) sl.h_end[0] = 0ull;
-    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.h_end_dev), sl.h_end, 0) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.st_scan), 512 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.st_scan, 0, 512 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.partial), (size_t)(GSR_MAX_TILES_SIDE / 8) * (GSR_MAX_TILES_SIDE / 8) * sizeof(GsrTilePartial)) == hipSuccess;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.sup_work), 512 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipMemset(sl.sup_work, 0, 512 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&sl.h_total), 4 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;
-    if (ok) { sl.h_total[0] = 0ull; sl.h_total[1] = 0ull; sl.h_total[2] = 0ull; sl.h_total[3] = 0ull; }
-    ok = ok && hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.h_total_dev), sl.h_total, 0) == hipSuccess;
-    ok = ok && hipHostMalloc(reinterpret_cast<void**>(&sl.h_counters), 8 * sizeof(unsigned long long), 0) == hipSuccess;
-    if (ok) for (int j = 0; j < 8; ++j) sl.h_counters[j] = 0;
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&sl.d_frame), 8 * sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMemset(sl.d_frame, 0, 8 * sizeof(unsigned long long)) == hipSuccess;
-    ok = ok && hipMemset(sl.counters, 0, 8 * sizeof(unsigned long long)) == hipSuccess;
-    if (ok) {
-        for (int k = 0; k < GSR_STAGE_EVENTS; ++k) sl.ev[k] = nullptr;
-        sl.ev_ok = true;
-        for (int k = 0; k < GSR_STAGE_EVENTS && ok; ++k) ok = hipEventCreate(&sl.ev[k]) == hipSuccess;
-    }
+    ok = ok && sl.ev_done.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && sl.ev_user.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && sl.ev_pairs.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && !sl.counters.alloc_zeroed(8);
+    ok = ok && !sl.d_n.alloc_zeroed(1);
+    ok = ok && !sl.totals.alloc(512);
+    ok = ok && !sl.lazy_ctr.alloc_zeroed(2);
+    ok = ok && !sl.colour_evals.alloc_zeroed(256);
+    ok = ok && !sl.hpyr.alloc(GSR_PYR_FLOATS);
+    ok = ok && !sl.hpyr_next.alloc(GSR_PYR_FLOATS);
+    ok = ok && !sl.hraw.alloc(tiles);
+    ok = ok && !sl.hstat.alloc(tiles);
+    ok = ok && !sl.hpyr2.alloc(GSR_PYR_FLOATS);
+    ok = ok && !sl.slab.alloc_zeroed(GSR_SLAB_BINS + 8);
+    ok = ok && !sl.ccnt.alloc(CC_MAX_GROUPS);
+    ok = ok && !sl.bkt_key.alloc((size_t)BK_BUCKETS * BK_CAP);
+    ok = ok && !sl.bkt_val.alloc((size_t)BK_BUCKETS * BK_CAP);
+    ok = ok && !sl.bkt_cnt.alloc_zeroed((size_t)BK_BUCKETS * BK_STRIDE);
+    ok = ok && !sl.d_counts.alloc_zeroed(4);
+    ok = ok && !sl.h_end.alloc(1, mailbox);
+    ok = ok && !sl.st_scan.alloc_zeroed(512);
+    ok = ok && !sl.partial.alloc((size_t)(GSR_MAX_TILES_SIDE / 8) * (GSR_MAX_TILES_SIDE / 8));
+    ok = ok && !sl.sup_work.alloc_zeroed(512);
+    ok = ok && !sl.h_total.alloc(4, mailbox);
+    ok = ok && !sl.h_counters.alloc(8, 0);
+    ok = ok && !sl.d_frame.alloc_zeroed(8);
+    for (int k = 0; k < GSR_STAGE_EVENTS && ok; ++k) ok = sl.ev[k].create(hipEventDefault) == hipSuccess;
     return ok;
 }
 
-static void slot_free_splat_arrays(FrameSlot& sl)
-{
-    dev_free(sl.rec); dev_free(sl.keyA); dev_free(sl.keyB); dev_free(sl.valA); dev_free(sl.valB); dev_free(sl.blk_cnt);
-    dev_free(sl.zwin); dev_free(sl.cseg);
-    sl.sort_valid = false;
-}
-
-// A frame slot's arrays that are sized by the capacity, as a set of their own: gsr_upload_begin allocates them for a new capacity, and
-// gsr_add allocates the larger set before its first write and hands it over once nothing can fail for lack of memory any more.
-struct SlotSplatArrays {
-    GsrRecord* rec = nullptr;
-    uint32_t *keyA = nullptr, *keyB = nullptr, *blk_cnt = nullptr, *cseg = nullptr;
-    uint2 *valA = nullptr, *valB = nullptr;
-    float* zwin = nullptr;
-    void release() { dev_free(rec); dev_free(keyA); dev_free(keyB); dev_free(valA); dev_free(valB); dev_free(blk_cnt); dev_free(zwin); dev_free(cseg); }
-};
 static int alloc_splat_arrays(SlotSplatArrays& a, size_t cap)
 {
     int rc = GSR_OK;
     // (+256: K1 writes what it keeps at the head of its workgroup's 256 slots)
-    if ((rc = dev_alloc(&a.rec, cap)) || (rc = dev_alloc(&a.keyA, cap + 256)) || (rc = dev_alloc(&a.keyB, cap + 256)) ||
-        (rc = dev_alloc(&a.valA, cap + 256)) || (rc = dev_alloc(&a.valB, cap + 256)) ||
-        (rc = dev_alloc(&a.zwin, cap)) || (rc = dev_alloc(&a.blk_cnt, cap / 256 + 16)) ||
-        (rc = dev_alloc(&a.cseg, cap / GSR_CLUSTER + (size_t)CC_THREADS * 64 + 16)))
-        a.release();
+    if ((rc = a.rec.alloc(cap)) || (rc = a.keyA.alloc(cap + 256)) || (rc = a.keyB.alloc(cap + 256)) ||
+        (rc = a.valA.alloc(cap + 256)) || (rc = a.valB.alloc(cap + 256)) ||
+        (rc = a.zwin.alloc(cap)) || (rc = a.blk_cnt.alloc(cap / 256 + 16)) ||
+        (rc = a.cseg.alloc(cap / GSR_CLUSTER + (size_t)CC_THREADS * 64 + 16)))
+        a = SlotSplatArrays{};
     return rc;
 }
-// (nothing of the slot is in flight)
-static void slot_take_splat_arrays(FrameSlot& sl, SlotSplatArrays& a)
+// (nothing of the slot is in flight; an empty set takes the slot's arrays away)
+static void slot_take_splat_arrays(FrameSlot& sl, SlotSplatArrays&& a)
 {
-    slot_free_splat_arrays(sl);
-    sl.rec = a.rec; sl.keyA = a.keyA; sl.keyB = a.keyB; sl.valA = a.valA; sl.valB = a.valB; sl.blk_cnt = a.blk_cnt; sl.zwin = a.zwin; sl.cseg = a.cseg;
-    a = SlotSplatArrays{};
-}
-
-static void slot_destroy(FrameSlot& sl)
-{
-    slot_free_splat_arrays(sl);
-    dev_free(sl.hist); dev_free(sl.totals);
-    dev_free(sl.pvA);
-    dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.tile_work); dev_free(sl.order); dev_free(sl.sup_work); sl.fb.release(); dev_free(sl.fb32); sl.aovb.release(); sl.bgb.release();
-    dev_free(sl.hpyr); dev_free(sl.hpyr_next); dev_free(sl.hraw); dev_free(sl.hstat); dev_free(sl.hpyr2); dev_free(sl.slab); dev_free(sl.tile_work_a); dev_free(sl.tbuf); dev_free(sl.ccnt); dev_free(sl.bkt_key); dev_free(sl.bkt_val); dev_free(sl.bkt_cnt); dev_free(sl.d_counts); dev_free(sl.st_scan); dev_free(sl.partial);
-    if (sl.h_end) (void)hipHostFree(sl.h_end); if (sl.h_rows) (void)hipHostFree(sl.h_rows); sl.depth_stage.release(); dev_free(sl.dpyr); dev_free(sl.dactive);
-    dev_free(sl.redo); dev_free(sl.lazy_ctr); dev_free(sl.colour_evals);
-    dev_free(sl.counters); dev_free(sl.d_n);
-    if (sl.h_total) (void)hipHostFree(sl.h_total);
-    if (sl.h_counters) (void)hipHostFree(sl.h_counters);
-    dev_free(sl.d_frame);
-    if (sl.ev_ok)
-        for (int k = 0; k < GSR_STAGE_EVENTS; ++k)
-            if (sl.ev[k]) (void)hipEventDestroy(sl.ev[k]);
-    if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
-    if (sl.ev_user) (void)hipEventDestroy(sl.ev_user);
-    for (int k = 0; k < GSR_HOST_BANDS_MAX; ++k) if (sl.ev_band[k]) (void)hipEventDestroy(sl.ev_band[k]);
-    if (sl.ev_pairs) (void)hipEventDestroy(sl.ev_pairs);
-    if (sl.own) (void)hipStreamDestroy(sl.own);
+    static_cast<SlotSplatArrays&>(sl) = std::move(a);
+    sl.sort_valid = false;
 }
 
 extern "C" int gsr_create(int device, gsr_context** out)
@@ -574,7 +525,7 @@ extern "C" int gsr_create(int device, gsr_context** out)
     if (const char* e = std::getenv("GSR_SLAB_MIN")) { const int v = std::atoi(e); if (v >= 1) c->slab_min = v; }                 // (A/B hook)
     if (const char* e = std::getenv("GSR_SLAB_MAX")) { const int v = std::atoi(e); if (v >= 1) c->slab_max = v; }                 // (A/B hook)
     if (const char* e = std::getenv("GSR_BN_ITEMS")) { const int v = std::atoi(e); if (v == 1 || v == 2 || v == 4) c->opt_bn_items = v; }   // (A/B hook)
-    hipError_t e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
+    hipError_t e = c->own_stream.create(hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return set_err(GSR_E_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e)); }
     c->stream = c->own_stream;
     bool ok = true;
@@ -583,12 +534,9 @@ extern "C" int gsr_create(int device, gsr_context** out)
         gsr_destroy(c);
         return set_err(GSR_E_HIP, "gsr_create: allocating frame slots (streams/events/mailboxes) failed");
     }
-    if (hipMalloc(reinterpret_cast<void**>(&c->prefix), 256 * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->prefix_all), 256 * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->prefix_none), 256 * 4) != hipSuccess ||
+    if (c->prefix.alloc(256) || c->prefix_all.alloc(256) || c->prefix_none.alloc(256) ||
         hipMemset(c->prefix, 0xff, 256 * 4) != hipSuccess || hipMemset(c->prefix_all, 0xff, 256 * 4) != hipSuccess ||
-        hipMemset(c->prefix_none, 0, 256 * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&c->lazy_hint), 4) != hipSuccess || hipMemset(c->lazy_hint, 0, 4) != hipSuccess) {
+        hipMemset(c->prefix_none, 0, 256 * 4) != hipSuccess || c->lazy_hint.alloc_zeroed(1)) {
         gsr_destroy(c);
         return set_err(GSR_E_HIP, "gsr_create: allocating the colour-prefix tables failed");
     }
@@ -601,40 +549,38 @@ extern "C" int gsr_create(int device, gsr_context** out)
 // the mask belongs to a cloud: gone with it (a visibility that was a mask alone is then no visibility)
 static void vis_drop_mask(gsr_context* c)
 {
-    dev_free(c->vis_mask);
+    c->vis_mask.reset();
     if (c->vis.n_volumes == 0) { c->vis_on = false; c->vis_hidden = 0; }
 }
 
+// the storage order and the cluster bounds, live and spare: gone whenever the arrays are filled in upload order again
+static void drop_order(gsr_context* c)
+{
+    c->perm.reset(); c->clusA.reset(); c->clusB.reset(); c->clusA2.reset(); c->clusB2.reset();
+    c->nclus = 0; c->h_perm.clear();
+}
+// the spare planes of the edits (gsr_resident_edit.h: ensure_spare_planes)
+static void free_spare_planes(gsr_context* c) { c->geoA2.reset(); c->geoB2.reset(); c->col2.reset(); c->colrow2.reset(); }
+
 static void free_geometry(gsr_context* c)
 {
-    dev_free(c->geoA); dev_free(c->geoB); dev_free(c->col); dev_free(c->colrow);
-    dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->nclus = 0; c->h_perm.clear();
-    dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2); dev_free(c->clusA2); dev_free(c->clusB2);
-    dev_free(c->alpha0);               // (sized by the capacity; the volumes stay in force, the next complete upload captures again)
-    dev_free(c->alpha0_2);
+    c->geoA.reset(); c->geoB.reset(); c->col.reset(); c->colrow.reset();
+    drop_order(c);
+    free_spare_planes(c);
+    c->alpha0.reset();                 // (sized by the capacity; the volumes stay in force, the next complete upload captures again)
+    c->alpha0_2.reset();
     vis_drop_mask(c);
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_free_splat_arrays(c->slot[k]);
+    for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], SlotSplatArrays{});
     c->cap = 0; c->n = 0;
 }
 
+// (the handles of the context and its slots release on the device that is current)
 extern "C" void gsr_destroy(gsr_context* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)sync_all(c);
     gsr_internal_comm_release(c);
-    free_geometry(c);
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_destroy(c->slot[k]);
-    dev_free(c->tile_map);
-    dev_free(c->wire_zbuf); dev_free(c->wire_out); dev_free(c->wire_inv); dev_free(c->stage); dev_free(c->stage_raw);
-    dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB); dev_free(c->up_part);
-    for (int k = 0; k < 4; ++k) if (c->up_ev[k]) (void)hipEventDestroy(c->up_ev[k]);
-    dev_free(c->prefix); dev_free(c->prefix_all); dev_free(c->prefix_none); dev_free(c->lazy_hint);
-    dev_free(c->pos_order); dev_free(c->blk_pre); dev_free(c->vis_counters);
-    if (c->vis_h_counters) (void)hipHostFree(c->vis_h_counters);
-    if (c->rm_h_total) (void)hipHostFree(c->rm_h_total);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
 }
 
@@ -674,10 +620,8 @@ extern "C" int gsr_set_option(gsr_context* c, int option, int value)
             HIP_TRY(hipSetDevice(c->device));
             for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
                 FrameSlot& sl = c->slot[k];
-                if (sl.h_rows) continue;
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_rows), GSR_MAX_TILES_SIDE * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-                std::memset(sl.h_rows, 0, GSR_MAX_TILES_SIDE * sizeof(unsigned long long));
-                HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&sl.h_rows_dev), sl.h_rows, 0));
+                int rc = GSR_OK;
+                if (!sl.h_rows && (rc = sl.h_rows.alloc(GSR_MAX_TILES_SIDE, hipHostMallocMapped | hipHostMallocCoherent))) return rc;
             }
         }
         c->opt_row_work = value ? 1 : 0;
@@ -728,7 +672,7 @@ extern "C" int gsr_set_target_format(gsr_context* c, int format)
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) {   // the staging images are laid out for the old pixel size
         FrameSlot& sl = c->slot[k];
         sl.fb.release();
-        dev_free(sl.fb32); sl.fb32_cap = 0;
+        sl.fb32.reset(); sl.fb32_cap = 0;
     }
     c->target_format = format;
     return GSR_OK;
@@ -787,13 +731,7 @@ static double up_now_ms() { return std::chrono::duration<double, std::milli>(std
 // The arena holds `bytes` (kept between uploads and edits; only ever grown, and what it held does not survive a growth).
 static int ensure_stage(gsr_context* c, size_t bytes)
 {
-    if (bytes <= c->stage_cap) return GSR_OK;
-    dev_free(c->stage);
-    c->stage_cap = 0;
-    const int rc = dev_alloc(&c->stage, bytes + 256);
-    if (rc) return rc;
-    c->stage_cap = bytes + 256;
-    return GSR_OK;
+    return bytes <= c->stage_cap ? GSR_OK : replace(c->stage, c->stage_cap, bytes + 256, bytes + 256);
 }
 // The first `count` events of the upload / edit clock.  oom_code: hipErrorOutOfMemory comes back as GSR_E_OOM (upload, update, remove)
 // or, like every other failure, as GSR_E_HIP (move, add): the verbs differ there, and each keeps its code.
@@ -801,7 +739,7 @@ static int ensure_up_events(gsr_context* c, int count, const char* who, bool oom
 {
     for (int k = 0; k < count; ++k) {
         if (c->up_ev[k]) continue;
-        const hipError_t e = hipEventCreate(&c->up_ev[k]);
+        const hipError_t e = c->up_ev[k].create(hipEventDefault);
         if (e != hipSuccess) return set_err(oom_code && e == hipErrorOutOfMemory ? GSR_E_OOM : GSR_E_HIP, "%s: no event: %s", who, hipGetErrorString(e));
     }
     return GSR_OK;
@@ -842,19 +780,16 @@ extern "C" int gsr_upload_begin(gsr_context* c, int64_t total, int has_sh, const
     if (n > c->cap || chunks != c->col_chunks) {
         free_geometry(c);
         const size_t cap = n ? n : 1;
-        if ((rc = dev_alloc(&c->geoA, cap)) || (rc = dev_alloc(&c->geoB, cap)) || (rc = dev_alloc(&c->col, cap * chunks)) ||
-            (has_sh && (rc = dev_alloc(&c->colrow, cap * 8)))) {
+        if ((rc = c->geoA.alloc(cap)) || (rc = c->geoB.alloc(cap)) || (rc = c->col.alloc(cap * chunks)) ||
+            (has_sh && (rc = c->colrow.alloc(cap * 8)))) {
             free_geometry(c);
             return rc;
         }
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
-            SlotSplatArrays a;
-            if ((rc = alloc_splat_arrays(a, cap))) {
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k)
+            if ((rc = alloc_splat_arrays(c->slot[k], cap))) {      // (free_geometry left the slot's set empty, and no order cached)
                 free_geometry(c);
                 return rc;
             }
-            slot_take_splat_arrays(c->slot[k], a);
-        }
         c->cap = (uint32_t)cap;
         c->col_chunks = chunks;
     }
@@ -868,9 +803,7 @@ extern "C" int gsr_upload_begin(gsr_context* c, int64_t total, int has_sh, const
     c->uploading = true;
     for (int k = 0; k < 3; ++k) c->origin[k] = origin ? origin[k] : 0.0f;
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) c->slot[k].sort_valid = false;
-    dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB);   // (the arrays are filled in upload order again)
-    dev_free(c->clusA2); dev_free(c->clusB2);
-    c->nclus = 0; c->h_perm.clear();
+    drop_order(c);                     // (the arrays are filled in upload order again)
     return GSR_OK;
 }
 
@@ -908,13 +841,12 @@ static hipError_t vis_apply(gsr_context* c, hipStream_t us, uint32_t cap_first, 
 // an upload that failed after the arrays were filled: the context goes back to "nothing uploaded"
 static void drop_geometry(gsr_context* c)
 {
-    c->n = 0; c->nclus = 0; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
-    dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); c->h_perm.clear();
-    dev_free(c->clusA2); dev_free(c->clusB2);
+    c->n = 0; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
+    drop_order(c);
     vis_drop_mask(c);
     c->has_geometry = false;           // gsr_render: GSR_E_NO_GEOMETRY (the generation is NOT rewound: stamps of the lost cloud stay stale)
     c->geo_gen++;
-    dev_free(c->wire_inv); c->wire_inv_gen = 0;
+    c->wire_inv.reset(); c->wire_inv_gen = 0;
     c->pos_valid = false; c->prefix_valid = false;
     for (int k = 0; k < GSR_MAX_SLOTS; ++k) {
         FrameSlot& sl = c->slot[k];
@@ -1134,16 +1066,10 @@ __attribute__((visibility("hidden"))) int gsr_internal_stitch(gsr_context* c, co
 
 // ---------------------------------------------------------------------------
 // scan + sort drivers (all on the slot's stream)
-static int ensure_u32(uint32_t** p, size_t* cap, size_t need)
+static int ensure_u32(DevMem<uint32_t>& p, size_t& cap, size_t need)
 {
-    if (need <= *cap) return GSR_OK;
-    dev_free(*p);
-    *cap = 0;
-    size_t want = need + need / 4 + 1024;
-    int rc = dev_alloc(p, want);
-    if (rc) return rc;
-    *cap = want;
-    return GSR_OK;
+    const size_t want = need + need / 4 + 1024;
+    return need <= cap ? GSR_OK : replace(p, cap, want, want);
 }
 
 template <typename V, int DBITS, bool GATHER, int ITEMS>
@@ -1177,7 +1103,7 @@ static int radix_sort(FrameSlot& sl, uint32_t*& kA, V*& vA, uint32_t*& kB, V*& v
     }
     if (bits <= 0) bits = 1;
     const uint32_t nblk = div_up(n, (uint32_t)RS_THREADS * (uint32_t)(mid ? RS_ITEMS_MID : RS_ITEMS));
-    int rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * nblk + 8);
+    int rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)512 * nblk + 8);
     if (rc) return rc;
     const int p8 = (bits + 7) / 8, p9 = (bits + 8) / 9;
     const bool use9 = allow9 && p9 < p8;
@@ -1216,7 +1142,7 @@ static int position_box(gsr_context* c, const float* P, uint32_t n, hipStream_t 
 {
     const int grid = 512;
     int rc = GSR_OK;
-    if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)grid * 6))) return rc;
+    if (!c->up_part && (rc = c->up_part.alloc((size_t)grid * 6))) return rc;
     hipLaunchKernelGGL(k_bbox_partials, dim3(grid), dim3(256), 0, us, P, n, c->up_part);
     std::vector<float> hp((size_t)grid * 6);
     hipError_t e = hipMemcpyAsync(hp.data(), c->up_part, hp.size() * 4, hipMemcpyDeviceToHost, us);
@@ -1238,11 +1164,12 @@ static int position_box(gsr_context* c, const float* P, uint32_t n, hipStream_t 
 static bool ensure_order_scratch(gsr_context* c, uint32_t n)
 {
     if ((size_t)n <= c->up_sort_cap) return true;
-    dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
+    auto drop = [&]() { c->up_kA.reset(); c->up_kB.reset(); c->up_vA.reset(); c->up_vB.reset(); };
+    drop();
     c->up_sort_cap = 0;
     const size_t want = (size_t)n + n / 8 + 1024;
-    if (dev_alloc(&c->up_kA, want) || dev_alloc(&c->up_kB, want) || dev_alloc(&c->up_vA, want) || dev_alloc(&c->up_vB, want)) {
-        dev_free(c->up_kA); dev_free(c->up_kB); dev_free(c->up_vA); dev_free(c->up_vB);
+    if (c->up_kA.alloc(want) || c->up_kB.alloc(want) || c->up_vA.alloc(want) || c->up_vB.alloc(want)) {
+        drop();
         (void)hipGetLastError();
         return false;
     }
@@ -1279,14 +1206,14 @@ static int order_and_pack(gsr_context* c)
     HIP_TRY(hipEventRecord(c->up_ev[0], us));
     if ((rc = position_box(c, A.P, n, us, "gsr_upload_end"))) return rc;
     // the storage order: perm[j] = upload index of the splat in slot j (NULL: upload order)
-    dev_free(c->perm);
+    c->perm.reset();
     if (c->opt_morton && c->bbox_ok && n > 1) {
         // without the scratch the splats simply stay in upload order (perm = NULL: ties then break by upload index, the
         // documented meaning of an unordered store) and get their clusters
         const bool have = ensure_order_scratch(c, n);
-        if (have && !(rc = dev_alloc(&c->perm, (size_t)n))) {
+        if (have && !(rc = c->perm.alloc((size_t)n))) {
             rc = morton_order(c, A.P, n, c->perm, "gsr_upload_end");
-            if (rc) { dev_free(c->perm); return rc; }
+            if (rc) { c->perm.reset(); return rc; }
         } else if (have) {
             (void)hipGetLastError();
             rc = GSR_OK;           // (no room for the permutation: upload order)
@@ -1294,8 +1221,8 @@ static int order_and_pack(gsr_context* c)
     }
     HIP_TRY(hipEventRecord(c->up_ev[1], us));
     c->nclus = div_up(n, GSR_CLUSTER);
-    dev_free(c->clusA); dev_free(c->clusB);
-    if ((rc = dev_alloc(&c->clusA, c->nclus)) || (rc = dev_alloc(&c->clusB, c->nclus))) return rc;
+    c->clusA.reset(); c->clusB.reset();
+    if ((rc = c->clusA.alloc(c->nclus)) || (rc = c->clusB.alloc(c->nclus))) return rc;
     const GsrPackSrc src{A.P, A.alpha, A.Cd, A.scale, A.orient, A.shx, A.shy, A.shz};
     launch_sh(c->has_sh, [&](auto sh) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack<decltype(sh)::value>), dim3(c->nclus), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, src, c->perm, c->geoA, c->geoB, c->col, c->colrow, c->clusA, c->clusB);
@@ -1315,8 +1242,7 @@ static int order_and_pack(gsr_context* c)
 static int ensure_inverse_perm(gsr_context* c)
 {
     if (!c->perm || c->n == 0 || (c->wire_inv && c->wire_inv_gen == c->geo_gen)) return GSR_OK;
-    dev_free(c->wire_inv);
-    int rc = dev_alloc(&c->wire_inv, (size_t)c->n);
+    int rc = c->wire_inv.alloc((size_t)c->n);
     if (rc) return rc;
     hipLaunchKernelGGL(k_invert_perm, dim3(div_up(c->n, 256)), dim3(256), 0, c->slot[0].own, c->perm, c->n, c->wire_inv);
     c->wire_inv_gen = c->geo_gen;
@@ -1557,13 +1483,7 @@ static int build_tile_map(gsr_context* c, const GsrFrame& f)
     std::vector<int32_t> map(chunk * 8 + 8, -1);
     for (int x = 0; x < 8; ++x)
         for (size_t k = 0; k < per_xcd[x].size(); ++k) map[k * 8 + x] = per_xcd[x][k];
-    if (map.size() > c->map_cap) {
-        dev_free(c->tile_map);
-        c->map_cap = 0;
-        rc = dev_alloc(&c->tile_map, map.size());
-        if (rc) return rc;
-        c->map_cap = map.size();
-    }
+    if (map.size() > c->map_cap && (rc = replace(c->tile_map, c->map_cap, map.size(), map.size()))) return rc;
     HIP_TRY(hipMemcpy(c->tile_map, map.data(), map.size() * 4, hipMemcpyHostToDevice));
     c->map_grid = (int)(chunk * 8);
     c->map_w = f.width; c->map_h = f.height; c->map_si = c->shard_index; c->map_sc = c->shard_count; c->map_rpb = f.shard_rpb; c->map_first = f.shard_first;
@@ -1575,7 +1495,7 @@ static void harvest_slot(gsr_context* c, FrameSlot& sl)
 {
     if (!sl.ev_pending) return;
     sl.ev_pending = false;
-    hipEvent_t* e = sl.ev;
+    const Event* e = sl.ev;
     if (hipEventSynchronize(e[6]) != hipSuccess) return;
     float ms[6] = {0, 0, 0, 0, 0, 0};
     if (!sl.ev_all) {   // only the blend kernel was bracketed
@@ -1627,8 +1547,8 @@ static GsrRangeArgs range_args(gsr_context* c, FrameSlot& sl)
 {
     const FrameJob& j = sl.job;
     GsrRangeArgs a;
-    a.totals = sl.totals; a.n_super = j.n_super; a.sstart = sl.sstart; a.send = sl.send; a.host_total = sl.h_total_dev;
-    a.ticket = j.ticket; a.max_pairs = (unsigned long long)GSR_MAX_PAIRS; a.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
+    a.totals = sl.totals; a.n_super = j.n_super; a.sstart = sl.sstart; a.send = sl.send; a.host_total = sl.h_total.dev();
+    a.ticket = j.ticket; a.max_pairs = (unsigned long long)GSR_MAX_PAIRS; a.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr.get());
     a.lazy_hint = c->lazy_hint; a.n_sorted = sl.d_n; a.k1_counts = sl.d_counts; a.sorted_keys = sl.keyA;
     a.depth_active = j.dcull ? sl.dactive + j.dpar : (const uint32_t*)nullptr;
     return a;
@@ -1696,7 +1616,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     GsrLazyArgs lz;
     lz.f = f; lz.colrow = c->colrow;
     lz.redo = j.lazy ? sl.redo : nullptr;
-    lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr);
+    lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr.get());
     // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
     // (a frame over a background is laid out like a packed one whatever its format: the composited pixel goes to the target, the raw one
     //  of a front slab's phase 1 to the slot's own buffer -- phase 2 must never continue from a composited pixel)
@@ -1719,9 +1639,9 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     // The launches walk the same tile table; a workgroup of another band's tile leaves at once (~3 us per extra launch).
     int nb = 1;
     if (!j.args.out_is_device && j.phase != 1 && c->opt_host_bands > 1 && c->shard_count == 1 && c->band_tile_rows < 0 && f.local_tiles_y >= 4 * c->opt_host_bands) nb = c->opt_host_bands;
-    if (nb > 1 && !c->copy_stream && hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) { c->copy_stream = nullptr; nb = 1; (void)hipGetLastError(); }
+    if (nb > 1 && !c->copy_stream && c->copy_stream.create(hipStreamNonBlocking) != hipSuccess) { nb = 1; (void)hipGetLastError(); }
     for (int b = 0; b < nb && nb > 1; ++b)
-        if (!sl.ev_band[b] && hipEventCreateWithFlags(&sl.ev_band[b], hipEventDisableTiming) != hipSuccess) { sl.ev_band[b] = nullptr; nb = 1; (void)hipGetLastError(); }
+        if (!sl.ev_band[b] && sl.ev_band[b].create(hipEventDisableTiming) != hipSuccess) { nb = 1; (void)hipGetLastError(); }
     sl.bands = nb;
     for (int b = 0; b < nb; ++b) {
         a.row_lo = nb > 1 ? (int)((int64_t)f.local_tiles_y * b / nb) : 0;
@@ -1794,7 +1714,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     if (c->opt_cull && c->opt_cull != 3 && j.n > 0 && !j.deferred && (c->opt_cull >= 2 || j.cull || j.phase == 2 || (c->cull_pol.vis_unculled >= 300000u && c->cull_pol.holdoff <= 2))) {
         hz = horizon_args(c, sl);
         hz.raw = sl.hraw; hz.pyr_in = sl.hpyr; hz.pyr_out = sl.hpyr_next; hz.dilate = j.f.cull_dilate; hz.culled = j.cull ? 1 : 0;
-        hz.host_end = j.cull ? sl.h_end_dev : nullptr; hz.ticket = j.ticket;
+        hz.host_end = j.cull ? sl.h_end.dev() : nullptr; hz.ticket = j.ticket;
         // (depth-tested frames leave, and culled ones check, the tiles' status: k_blend.h.  A frame without a depth buffer leaves every
         //  tile classic: the sign bits of its raw horizons are clear)
         hz.stat = sl.hstat;
@@ -1802,7 +1722,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
         hz.depth_culled = (j.dcull && !j.dblind) ? 1 : 0;
         static const bool dbgv = std::getenv("GSR_DEBUG_VIOL") != nullptr;
         if (dbgv) {
-            if (!sl.dbg_viol && hipMalloc(reinterpret_cast<void**>(&sl.dbg_viol), 80 * 4) != hipSuccess) sl.dbg_viol = nullptr;
+            if (!sl.dbg_viol) (void)sl.dbg_viol.alloc(80);
             if (sl.dbg_viol) (void)hipMemsetAsync(sl.dbg_viol, 0, 80 * 4, s);
             hz.dbg = sl.dbg_viol;
         }
@@ -1811,7 +1731,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     const int nblocks8 = ((j.f.tiles_x + 7) >> 3) * ((j.f.tiles_y + 7) >> 3);
     hipLaunchKernelGGL(k_tile_pass, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tile_work, g, sl.sstart, sl.send, hz, sl.partial, sl.st_scan);
     uint32_t* const prefix_arg = (j.f.sh_order > 0 && c->opt_lazy) ? c->prefix : (uint32_t*)nullptr;
-    const uint32_t* const redo_arg = j.lazy ? reinterpret_cast<const uint32_t*>(sl.lazy_ctr) : (const uint32_t*)nullptr;
+    const uint32_t* const redo_arg = j.lazy ? reinterpret_cast<const uint32_t*>(sl.lazy_ctr.get()) : (const uint32_t*)nullptr;
     uint32_t* const work_next = sl.sup_work ? sl.sup_work + 256 * (sl.sup_par ^ 1) : (uint32_t*)nullptr;
     sl.horizon_valid = hz.raw != nullptr;
     sl.hstat_valid = hz.raw != nullptr;       // (the dilation writes it beside the pyramid)
@@ -1868,10 +1788,10 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
         sl.order_valid = true;
         sl.order_age = 0;
     }
-    if (c->opt_row_work && sl.h_rows_dev) {
+    if (c->opt_row_work && sl.h_rows.dev()) {
         // the tile rows' work, into the slot's mapped words (one launch more; nothing waits for it)
         hipLaunchKernelGGL(k_row_work, dim3((unsigned)((j.f.tiles_y + RW_THREADS / 64 - 1) / (RW_THREADS / 64))), dim3(RW_THREADS), 0, s, sl.tile_work,
-                           j.phase == 2 ? sl.tile_work_a : (const uint4*)nullptr, g, sl.h_rows_dev, j.ticket);
+                           j.phase == 2 ? sl.tile_work_a : (const uint4*)nullptr, g, sl.h_rows.dev(), j.ticket);
         HIP_TRY(hipGetLastError());
         sl.rows_ticket = j.ticket; sl.rows_tiles_y = j.f.tiles_y;
     }
@@ -1889,7 +1809,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
                 if (r1 <= r0) continue;
                 const size_t off = r0 * (size_t)j.f.width * bpp;
                 HIP_TRY(hipStreamWaitEvent(c->copy_stream, sl.ev_band[b], 0));
-                HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, static_cast<const char*>(sl.fb.p) + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
+                HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(j.args.out) + off, sl.fb.p + off, (r1 - r0) * (size_t)j.f.width * bpp, hipMemcpyDeviceToHost, c->copy_stream));
             }
             HIP_TRY(hipStreamSynchronize(c->copy_stream));
         } else {
@@ -2147,18 +2067,16 @@ static int build_pos_order(gsr_context* c, FrameSlot& sl, const GsrFrame& f, int
 {
     const uint32_t n = c->n;
     int rc;
-    uint32_t *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr;
-    auto drop = [&]() { dev_free(kA); dev_free(kB); dev_free(vA); dev_free(vB); };
-    if ((rc = dev_alloc(&kA, (size_t)n + 256)) || (rc = dev_alloc(&kB, (size_t)n + 256)) || (rc = dev_alloc(&vA, (size_t)n + 256)) ||
-        (rc = dev_alloc(&vB, (size_t)n + 256))) { drop(); return rc; }
+    DevMem<uint32_t> scratch[4];           // the pairs (kA, vA) and (kB, vB) of the sort, gone with the call
+    for (DevMem<uint32_t>& m : scratch)
+        if ((rc = m.alloc((size_t)n + 256))) return rc;
+    uint32_t *kA = scratch[0], *vA = scratch[1], *kB = scratch[2], *vB = scratch[3];
     hipStream_t s = sl.stream;
     hipLaunchKernelGGL(k_pos_keys, dim3(div_up(n, 256)), dim3(256), 0, s, c->geoA, n, f.cam[0], f.cam[1], f.cam[2], f.key_min, f.key_max, kA, vA);
     rc = radix_sort(sl, kA, vA, kB, vB, n, key_bits, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);
     if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(GSR_E_HIP, "position-keyed order: sort failed");
-    if (rc) { drop(); return rc; }
-    dev_free(c->pos_order);
-    c->pos_order = vA; vA = nullptr;       // (radix_sort leaves the result in the A pair)
-    drop();
+    if (rc) return rc;
+    c->pos_order = std::move(scratch[vA == scratch[1] ? 1 : 3]);   // (radix_sort leaves the result in what vA names now)
     c->pos_valid = true;
     c->pos_gen = c->geo_gen;
     std::memcpy(c->pos_cam, f.cam, sizeof c->pos_cam);
@@ -2282,10 +2200,10 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     // per-tile bookkeeping + super-tile ranges
     if ((size_t)j.local_tiles + 1 > sl.tile_cap || !sl.sstart) {
         HIP_TRY(hipStreamSynchronize(s));
-        dev_free(sl.tile_work); dev_free(sl.tile_work_a); dev_free(sl.sstart); dev_free(sl.send); dev_free(sl.redo);
+        sl.tile_work.reset(); sl.tile_work_a.reset(); sl.sstart.reset(); sl.send.reset(); sl.redo.reset();
         sl.tile_cap = 0;
-        if ((rc = dev_alloc(&sl.tile_work, (size_t)j.local_tiles + 1)) || (rc = dev_alloc(&sl.tile_work_a, (size_t)j.local_tiles + 1)) || (rc = dev_alloc(&sl.sstart, (size_t)65536 + 1)) ||
-            (rc = dev_alloc(&sl.send, (size_t)65536 + 1)) || (rc = dev_alloc(&sl.redo, (size_t)j.local_tiles + 1))) return rc;
+        if ((rc = sl.tile_work.alloc((size_t)j.local_tiles + 1)) || (rc = sl.tile_work_a.alloc((size_t)j.local_tiles + 1)) || (rc = sl.sstart.alloc((size_t)65536 + 1)) ||
+            (rc = sl.send.alloc((size_t)65536 + 1)) || (rc = sl.redo.alloc((size_t)j.local_tiles + 1))) return rc;
         sl.tile_cap = (size_t)j.local_tiles + 1;
     }
     // (the transmittance a front slab leaves behind, per pixel of the band)
@@ -2294,7 +2212,7 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     j.d_depth = a.depth;
     if (a.depth && !a.depth_is_device) {
         if ((rc = sl.depth_stage.upload(s, a.depth, (size_t)cam->width * cam->height * sizeof(float)))) return rc;
-        j.d_depth = static_cast<const float*>(sl.depth_stage.p);
+        j.d_depth = reinterpret_cast<const float*>(sl.depth_stage.p.get());
     }
     // A background: the colour as it is; a device image read in place; a host image staged in the slot's own buffer like a host depth
     // buffer -- by EVERY attempt of the frame (a repair, a re-queue, a front slab's phase 2 come through here again with the caller's
@@ -2305,7 +2223,7 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
         j.bg.image = a.bg.kind == GSR_BG_IMAGE ? a.bg.image : nullptr;
         if (a.bg.kind == GSR_BG_IMAGE && !a.bg.image_is_device) {
             if ((rc = sl.bgb.upload(s, a.bg.image, (size_t)cam->width * cam->height * (size_t)gsr_format_pixel_bytes(a.bg.format)))) return rc;
-            j.bg.image = sl.bgb.p;
+            j.bg.image = sl.bgb.p.get();
         }
     }
     // Depth-tested frames: the tile-max pyramid of the opaque pass's depth (k_cluster.h), rebuilt every frame (the buffer's content is
@@ -2318,7 +2236,7 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
             if ((rc = regrow(s, sl.dpyr, sl.dpyr_cap, 5 * need, need))) return rc;   // (+ the per-tile "covered" array k_blend reads)
             HIP_TRY(hipMemsetAsync(sl.dpyr, 0, 5 * need * sizeof(float), s));   // (levels 4 and 5 start cleared; afterwards every frame clears the next one's)
             if (!sl.dactive) {
-                if ((rc = dev_alloc(&sl.dactive, 2))) return rc;
+                if ((rc = sl.dactive.alloc(2))) return rc;
                 HIP_TRY(hipMemsetAsync(sl.dactive, 0, 2 * sizeof(uint32_t), s));   // (on the frame's stream: a null-stream memset is not ordered against it)
             }
         }
@@ -2338,14 +2256,14 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     if (!a.out_is_device) {
         band[5] = j.format;
         if ((rc = sl.fb.ensure(s, j.out_px * bpp)) || (rc = sl.fb.clear_if_reshaped(s, band, j.out_px * bpp))) return rc;
-        j.target = static_cast<float*>(sl.fb.p);
+        j.target = reinterpret_cast<float*>(sl.fb.p.get());
     }
     if (a.aov != 0 && a.aov_out != nullptr) {
         j.aov_target = reinterpret_cast<float2*>(a.aov_out);
         if (!a.out_is_device) {
             band[5] = 0;
             if ((rc = sl.aovb.ensure(s, j.out_px * sizeof(float2))) || (rc = sl.aovb.clear_if_reshaped(s, band, j.out_px * sizeof(float2)))) return rc;
-            j.aov_target = static_cast<float2*>(sl.aovb.p);
+            j.aov_target = reinterpret_cast<float2*>(sl.aovb.p.get());
         }
     }
     return GSR_OK;
@@ -2514,7 +2432,7 @@ static int queue_sort(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     if (p.ordered) {
         // K1 walked the splats nearest first: the heads of its 256-slot blocks, one after the other, ARE the sorted frame
         const uint32_t m_max = p.n_slots / RS_SRC_BLOCK;
-        if ((rc = ensure_u32(&c->blk_pre, &c->blk_pre_cap, (size_t)m_max + 8))) return rc;
+        if ((rc = ensure_u32(c->blk_pre, c->blk_pre_cap, (size_t)m_max + 8))) return rc;
         hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, sl.blk_cnt, sl.d_counts, c->blk_pre, sl.d_n);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compact_blocks<uint2>), dim3(m_max), dim3(RS_SRC_BLOCK), 0, s, sl.keyB, sl.valB, sl.blk_cnt, c->blk_pre,
                            sl.d_counts, sl.keyA, sl.valA);
@@ -2525,9 +2443,14 @@ static int queue_sort(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
         sl.sorted_culled = j.cull;
         return GSR_OK;
     }
-    rc = (p.local_phase || p.local) ? queue_local_sort(c, sl, fe)
-                                    : radix_sort(sl, sl.keyA, sl.valA, sl.keyB, sl.valB, p.n_slots, p.key_bits, !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n,
-                                                 RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, p.mid_sort);
+    if (p.local_phase || p.local) {
+        rc = queue_local_sort(c, sl, fe);
+    } else {
+        uint32_t *kA = sl.keyA, *kB = sl.keyB;
+        uint2 *vA = sl.valA, *vB = sl.valB;
+        rc = radix_sort(sl, kA, vA, kB, vB, p.n_slots, p.key_bits, !(c->opt_flags & GSR_FLAG_FULL_KEYS), sl.d_n, RS_XCD_DEPTH != 0, sl.blk_cnt, sl.d_counts, p.mid_sort);
+        if (kA != sl.keyA) { sl.keyA.swap(sl.keyB); sl.valA.swap(sl.valB); }   // (the handles follow the pairs' ping-pong: the result is in the A pair)
+    }
     if (rc) return rc;
     sl.key_min = j.f.key_min;
     sl.sort_valid = j.phase == 0;    // (a phase's order holds a part of the frame only)
@@ -2550,7 +2473,7 @@ static int queue_binning(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     if (j.n > 0) {
         const uint32_t bn_tile = (uint32_t)BN_THREADS * (uint32_t)j.bn_items;
         const uint32_t nblk = fe.p.bn_blocks;
-        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)BN_BINS * nblk + 8))) return rc;
+        if ((rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)BN_BINS * nblk + 8))) return rc;
         const GsrShard shd = gsr_frame_shard(f, f.rect_shift);
         // (+ the extra work items of the blocks that are split by rows of super-tiles: k_binning.h, BN_SPLIT_TILES)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
@@ -2881,10 +2804,10 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
     const size_t npix = (size_t)cam->width * cam->height;
     // the z-buffer (and the staging image for a host target) are kept between calls: an overlay redraw allocates nothing
     if (npix > c->wire_cap) {   // (the staging image holds 16 bytes per pixel: enough for every target format)
-        dev_free(c->wire_zbuf); dev_free(c->wire_out);
+        c->wire_zbuf.reset(); c->wire_out.reset();
         c->wire_cap = 0;
-        if ((rc = dev_alloc(&c->wire_zbuf, npix)) || (rc = dev_alloc(&c->wire_out, npix * 4))) {
-            dev_free(c->wire_zbuf); dev_free(c->wire_out);
+        if ((rc = c->wire_zbuf.alloc(npix)) || (rc = c->wire_out.alloc(npix * 4))) {
+            c->wire_zbuf.reset();
             return rc;
         }
         c->wire_cap = npix;
@@ -3297,11 +3220,10 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
     if (rc) return rc;
     FrameSlot& sl = c->slot[0];
     const uint32_t n = (uint32_t)n64;
-    uint32_t *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr;
-    if ((rc = dev_alloc(&kA, n)) || (rc = dev_alloc(&kB, n)) || (rc = dev_alloc(&vA, n)) || (rc = dev_alloc(&vB, n))) {
-        dev_free(kA); dev_free(kB); dev_free(vA); dev_free(vB);
-        return rc;
-    }
+    DevMem<uint32_t> scratch[4];           // the pairs (kA, vA) and (kB, vB) of the sort, gone with the call
+    for (DevMem<uint32_t>& m : scratch)
+        if ((rc = m.alloc(n))) return rc;
+    uint32_t *kA = scratch[0], *vA = scratch[1], *kB = scratch[2], *vB = scratch[3];
     hipError_t e = hipMemcpyAsync(kA, keys, (size_t)n * 4, hipMemcpyHostToDevice, sl.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(vA, vals, (size_t)n * 4, hipMemcpyHostToDevice, sl.stream);
     if (e == hipSuccess) {
@@ -3311,9 +3233,9 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
             hipError_t e2 = hipMemsetAsync(sl.bkt_cnt, 0, (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t), sl.stream);
             if (e2 == hipSuccess) e2 = hipMemsetAsync(sl.d_counts + 2, 0, 4, sl.stream);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint32_t, false>), dim3(nblk), dim3(RS_THREADS), 0, sl.stream, kA, vA, n, (const uint32_t*)nullptr,
-                               dbg_shift, dbg_lo, (const uint32_t*)nullptr, sl.bkt_cnt, sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val), (uint32_t*)nullptr, sl.d_counts + 2);
+                               dbg_shift, dbg_lo, (const uint32_t*)nullptr, sl.bkt_cnt, sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val.get()), (uint32_t*)nullptr, sl.d_counts + 2);
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint32_t>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, sl.stream, sl.bkt_cnt, dbg_shift, key_bits, dbg_lo,
-                               sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val), kA, vA, (uint32_t*)nullptr, (uint32_t*)nullptr);
+                               sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val.get()), kA, vA, (uint32_t*)nullptr, (uint32_t*)nullptr);
             uint32_t over = 0;
             if (e2 == hipSuccess) e2 = hipMemcpyAsync(&over, sl.d_counts + 2, 4, hipMemcpyDeviceToHost, sl.stream);
             if (e2 == hipSuccess) e2 = hipStreamSynchronize(sl.stream);
@@ -3328,7 +3250,6 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
             if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
         }
     }
-    dev_free(kA); dev_free(kB); dev_free(vA); dev_free(vB);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_debug_sort_pairs: %s", hipGetErrorString(e));
     return rc;
 }

@@ -7,8 +7,9 @@
 // Every edit promises "bit for bit a fresh upload of the result" and "a failure before the first write leaves the context as it was".
 // Move, remove and add keep both through ONE pipeline (Reorder): prepare -- everything the new storage order needs, before the first
 // write; order -- the ordering of an upload over every position of the new cloud; commit / finish -- the swap of the spare planes, the
-// counts, the visibility rule over the whole cloud, a new generation.  What a verb still owns when it fails goes through
-// Reorder::refuse (the context as it was) or Reorder::lost (no geometry, as a failed gsr_upload_end leaves it).
+// counts, the visibility rule over the whole cloud, a new generation.  What a call allocated and did not hand over goes with its
+// Reorder (handles, gsr_host_buffers.h): a failure before the first write is a plain return (the context as it was), one after it
+// goes through Reorder::lost (no geometry, as a failed gsr_upload_end leaves it).
 #pragma once
 
 // ---------------------------------------------------------------------------
@@ -124,34 +125,28 @@ extern "C" int gsr_update(gsr_context* c, int64_t first, int64_t n64, const gsr_
 // that grows, which has released the old set first) and, with `bounds`, of the cluster bounds (at the cluster count in force: a
 // removal only ever needs fewer, and an add brings its own).  Allocated at the first call that writes a new storage order, kept until
 // the geometry is freed or an add grows the capacity.  A failure leaves no half of a set behind.
-static void free_spare_planes(gsr_context* c)
-{
-    dev_free(c->geoA2); dev_free(c->geoB2); dev_free(c->col2); dev_free(c->colrow2);
-}
 static int ensure_spare_planes(gsr_context* c, size_t cap, bool bounds)
 {
     int rc = GSR_OK;
-    if (!c->geoA2 && ((rc = dev_alloc(&c->geoA2, cap)) || (rc = dev_alloc(&c->geoB2, cap)) || (rc = dev_alloc(&c->col2, cap * c->col_chunks)) ||
-                      (c->has_sh && (rc = dev_alloc(&c->colrow2, cap * 8))))) {
+    if (!c->geoA2 && ((rc = c->geoA2.alloc(cap)) || (rc = c->geoB2.alloc(cap)) || (rc = c->col2.alloc(cap * c->col_chunks)) ||
+                      (c->has_sh && (rc = c->colrow2.alloc(cap * 8))))) {
         free_spare_planes(c);
         return rc;
     }
-    if (bounds && !c->clusA2 && ((rc = dev_alloc(&c->clusA2, c->nclus)) || (rc = dev_alloc(&c->clusB2, c->nclus)))) {
-        dev_free(c->clusA2); dev_free(c->clusB2);
+    if (bounds && !c->clusA2 && ((rc = c->clusA2.alloc(c->nclus)) || (rc = c->clusB2.alloc(c->nclus)))) {
+        c->clusA2.reset();
         return rc;
     }
     return GSR_OK;
 }
 
-// The spare set becomes the resident one, under the storage order perm_new (taken over; NULL: upload order).  Nothing is in flight, and
+// The spare set becomes the resident one, under the storage order perm_new (taken over; empty: upload order).  Nothing is in flight, and
 // every frame takes the planes from the context.
-static void swap_planes(gsr_context* c, uint32_t*& perm_new)
+static void swap_planes(gsr_context* c, DevMem<uint32_t>& perm_new)
 {
-    std::swap(c->geoA, c->geoA2); std::swap(c->geoB, c->geoB2); std::swap(c->col, c->col2); std::swap(c->colrow, c->colrow2);
-    std::swap(c->clusA, c->clusA2); std::swap(c->clusB, c->clusB2);
-    dev_free(c->perm);
-    c->perm = perm_new;
-    perm_new = nullptr;
+    c->geoA.swap(c->geoA2); c->geoB.swap(c->geoB2); c->col.swap(c->col2); c->colrow.swap(c->colrow2);
+    c->clusA.swap(c->clusA2); c->clusB.swap(c->clusB2);
+    c->perm = std::move(perm_new);
 }
 
 // The re-order pipeline of move, remove and add.  The verb forms every position of the NEW cloud in upload order (device memory) and
@@ -164,30 +159,22 @@ struct Reorder {
     const hipStream_t us;              // slot 0's stream: everything the pipeline queues
     const double t_begin = up_now_ms();
     double link_ms = 0.0;              // what the verb's staging took
-    const uint32_t* inv_old = nullptr; // upload index -> slot of the OLD order (NULL: upload order), from old_inverse() on
+    const uint32_t* inv_old = nullptr; // (not owned: c->wire_inv) upload index -> slot of the OLD order (NULL: upload order), from old_inverse() on
     bool may_order = false;            // GSR_OPT_STORAGE_ORDER and more than one splat: whether the new cloud IS ordered is known only once its box is
-    uint32_t* perm_new = nullptr;      // the new storage order: until the swap takes it over, or the new cloud turns out to stay in upload order
-    uint32_t* mask_new = nullptr;      // remove, add: the mask of a visibility in force, at the new upload indices (commit hands it over)
+    DevMem<uint32_t> perm_new;         // the new storage order: until the swap takes it over, or the new cloud turns out to stay in upload order
+    DevMem<uint32_t> mask_new;         // remove, add: the mask of a visibility in force, at the new upload indices (commit hands it over)
     // gsr_add's: the true alphas at a grown capacity, the spare cluster bounds of the larger cloud, the slot arrays at a grown capacity
-    float* alpha0_new = nullptr;
-    float4 *clusA_new = nullptr, *clusB_new = nullptr;
+    DevMem<float> alpha0_new;
+    DevMem<float4> clusA_new, clusB_new;
     SlotSplatArrays slot_new[GSR_MAX_SLOTS];
     bool spare_outgrown = false;       // gsr_add, growing: the spare planes are at the new capacity, and go when the geometry is lost
 
     Reorder(gsr_context* ctx, const char* verb, bool oom) : c(ctx), who(verb), oom_code(oom), us(ctx->slot[0].stream) {}
 
-    // ---- the one clean-up path
-    void release()
-    {
-        dev_free(perm_new); dev_free(mask_new); dev_free(alpha0_new); dev_free(clusA_new); dev_free(clusB_new);
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_new[k].release();
-    }
-    // a failure before the first write: the context stays as it was
-    int refuse(int code) { release(); return code; }
-    // a failure after it: no geometry (as a failed gsr_upload_end leaves the context)
+    // A failure before the first write is a plain `return rc`: the context stays as it was, and what the call allocated goes with the
+    // object.  A failure after it: no geometry (as a failed gsr_upload_end leaves the context)
     int lost(int code)
     {
-        release();
         if (spare_outgrown) free_spare_planes(c);      // (the planes that stay are at the old capacity)
         drop_geometry(c);
         return code;
@@ -200,12 +187,12 @@ struct Reorder {
     {
         FrameSlot& sl = c->slot[0];
         int rc = GSR_OK;
-        if (!c->up_part && (rc = dev_alloc(&c->up_part, (size_t)512 * 6))) return rc;
+        if (!c->up_part && (rc = c->up_part.alloc((size_t)512 * 6))) return rc;
         may_order = c->opt_morton && n_new > 1;
         if (!may_order) return GSR_OK;
         if (!ensure_order_scratch(c, n_new)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
-        if ((rc = ensure_u32(&sl.hist, &sl.hist_cap, (size_t)512 * div_up(n_new, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
-        return dev_alloc(&perm_new, (size_t)n_new);
+        if ((rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)512 * div_up(n_new, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+        return perm_new.alloc((size_t)n_new);
     }
     // the OLD order's inverse (built on slot 0's own stream, and waited for) and the three events of the clock.  events_first: gsr_remove
     // and gsr_add create the events in front of the inverse, gsr_move behind it; each keeps its sequence.
@@ -229,7 +216,7 @@ struct Reorder {
         if (rc) return rc;
         const bool ordered = may_order && c->bbox_ok;
         if (ordered && (rc = morton_order(c, P, n_new, perm_new, who))) return rc;
-        if (!ordered) dev_free(perm_new);
+        if (!ordered) perm_new.reset();
         const hipError_t e = hipEventRecord(c->up_ev[1], us);
         return e == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
     }
@@ -243,7 +230,7 @@ struct Reorder {
         c->h_perm.clear();
         c->n = n_new; c->nclus = nclus_new; c->up_total = c->up_filled = n_new;
         c->st.n_splats = n_new;
-        if (mask_new) { dev_free(c->vis_mask); c->vis_mask = mask_new; mask_new = nullptr; }
+        if (mask_new) c->vis_mask = std::move(mask_new);
     }
     // a visibility in force: the rule over the whole cloud, at the positions the splats have now, in the order they sit in now; and a new
     // cloud to everything a frame keeps; then the clock as ms[4]: the link, up_ev[0] -> [1] (the ordering), up_ev[1] -> [2] (the planes),
@@ -285,9 +272,9 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
     const size_t oNew = 0, oAll = pad256(new_bytes);
     if ((rc = ensure_stage(c, std::max(oAll + pad256((size_t)n * 12), upd_bytes)))) return rc;
-    if ((rc = ro.prepare(n))) return ro.refuse(rc);
-    if ((ro.may_order || c->perm) && (rc = ensure_spare_planes(c, c->cap, true))) return ro.refuse(rc);
-    if ((rc = ro.old_inverse(false))) return ro.refuse(rc);
+    if ((rc = ro.prepare(n))) return rc;
+    if ((ro.may_order || c->perm) && (rc = ensure_spare_planes(c, c->cap, true))) return rc;
+    if ((rc = ro.old_inverse(false))) return rc;
     // ---- from here on a failure leaves no geometry
     // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
     if (attrs) {
@@ -295,7 +282,7 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
         // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
         //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
         if (rc == GSR_E_HIP) return ro.lost(rc);
-        if (rc) return ro.refuse(rc);  // (refused before its first write)
+        if (rc) return rc;  // (refused before its first write)
         ro.link_ms = c->st.upload_ms[4];
     }
     // 2. the new rows where the splats sit now, and every position in upload order
@@ -556,11 +543,10 @@ extern "C" int gsr_visibility_eval(const gsr_visibility* v, const float* P, int6
 static int vis_ensure_buffers(gsr_context* c)
 {
     int rc = GSR_OK;
-    if (!c->alpha0 && (rc = dev_alloc(&c->alpha0, (size_t)c->cap))) return rc;
+    if (!c->alpha0 && (rc = c->alpha0.alloc((size_t)c->cap))) return rc;
     const size_t words = (size_t)GSR_VIS_COUNTER_SLOTS * GSR_VIS_COUNTER_STRIDE;
-    if (!c->vis_counters && (rc = dev_alloc(&c->vis_counters, words))) return rc;
-    if (!c->vis_h_counters && hipHostMalloc(reinterpret_cast<void**>(&c->vis_h_counters), words * 8, 0) != hipSuccess) {
-        c->vis_h_counters = nullptr;
+    if (!c->vis_counters && (rc = c->vis_counters.alloc(words))) return rc;
+    if (!c->vis_h_counters && c->vis_h_counters.alloc(words, 0)) {
         (void)hipGetLastError();
         return set_err(GSR_E_OOM, "no pinned host memory for the visibility counters");
     }
@@ -627,7 +613,7 @@ extern "C" int gsr_set_visibility(gsr_context* c, const gsr_visibility* v)
     if ((rc = sync_all(c))) return rc;      // no in-place write under a frame in flight
     const GsrVisRule rule = visibility_rule(v);
     if (!c->has_geometry || c->n == 0) {               // nothing to hide yet: the volumes wait for gsr_upload_end
-        dev_free(c->vis_mask);
+        c->vis_mask.reset();
         c->vis = rule; c->vis_on = rule.n_volumes > 0; c->vis_hidden = 0;
         return GSR_OK;
     }
@@ -636,27 +622,25 @@ extern "C" int gsr_set_visibility(gsr_context* c, const gsr_visibility* v)
     // ---- everything the call needs, before the first write
     if ((rc = vis_ensure_buffers(c))) return rc;
     const size_t words = ((size_t)c->n + 31) / 32;
-    uint32_t* mask_new = nullptr;
-    if (has_mask && (rc = dev_alloc(&mask_new, words))) return rc;
+    DevMem<uint32_t> mask_new;
+    if (has_mask && (rc = mask_new.alloc(words))) return rc;
     // (geoA holds every true alpha exactly while no visibility is in force: that is when they are put aside)
     const bool capture = !c->vis_on;
-    if (capture && (rc = ensure_inverse_perm(c))) { dev_free(mask_new); return rc; }
+    if (capture && (rc = ensure_inverse_perm(c))) return rc;
     hipStream_t us = c->slot[0].own;
     hipError_t e = has_mask ? hipMemcpyAsync(mask_new, v->mask, words * 4, hipMemcpyHostToDevice, us) : hipSuccess;
-    if (e != hipSuccess) { dev_free(mask_new); return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e));
     // ---- from here on a failure leaves no geometry (as a failed gsr_move does), and no visibility
     bool changed = false;
     e = vis_apply(c, us, 0u, capture ? c->n : 0u, true, rule, mask_new, &changed);
     // a change of the hidden set is a shape edit, like new alphas: horizons, prefixes, hints and policies of the cloud's frames go
     if (e == hipSuccess && changed) e = after_update(c, true, us, e);
     if (e != hipSuccess) {
-        dev_free(mask_new);
         c->vis = GsrVisRule{}; c->vis_on = false;
         drop_geometry(c);
         return set_err(GSR_E_HIP, "gsr_set_visibility: %s", hipGetErrorString(e));
     }
-    dev_free(c->vis_mask);
-    c->vis_mask = mask_new;
+    c->vis_mask = std::move(mask_new);
     c->vis = rule;
     c->vis_on = on;
     return GSR_OK;
@@ -726,8 +710,7 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     const size_t oMask = place(mask && !mask_is_device ? words * 4 : 0), oKeep = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8), oCnt = place((size_t)nblocks * 4),
                  oOff = place(((size_t)nblocks + 1) * 4), oP = place((size_t)n * 12), oSlot = place((size_t)n * 4);
     if ((rc = ensure_stage(c, off))) return rc;
-    if (!c->rm_h_total && hipHostMalloc(reinterpret_cast<void**>(&c->rm_h_total), 2 * sizeof(uint32_t), 0) != hipSuccess) {
-        c->rm_h_total = nullptr;
+    if (!c->rm_h_total && c->rm_h_total.alloc(2, 0)) {
         (void)hipGetLastError();
         return set_err(GSR_E_OOM, "gsr_remove: no pinned host memory for the survivor count");
     }
@@ -766,19 +749,19 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     // ---- everything the rest needs, before the first write to resident memory or to the visibility's state
     const bool vis = c->vis_on;
     if (n1 > 0) {
-        if ((rc = ro.prepare(n1)) || (rc = ensure_spare_planes(c, c->cap, true))) return ro.refuse(rc);
+        if ((rc = ro.prepare(n1)) || (rc = ensure_spare_planes(c, c->cap, true))) return rc;
         if (vis) {
-            if (!(rc = vis_ensure_buffers(c)) && !c->alpha0_2) rc = dev_alloc(&c->alpha0_2, (size_t)c->cap);
-            if (!rc && c->vis_mask) rc = dev_alloc(&ro.mask_new, words);
-            if (rc) return ro.refuse(rc);
+            if (!(rc = vis_ensure_buffers(c)) && !c->alpha0_2) rc = c->alpha0_2.alloc((size_t)c->cap);
+            if (!rc && c->vis_mask) rc = ro.mask_new.alloc(words);
+            if (rc) return rc;
         }
     }
     // ---- from here on a failure leaves no geometry
     hipError_t e = hipSuccess;
     if (n1 == 0) {
         // the empty cloud, as gsr_upload of 0 splats leaves it: no order, no clusters, no mask
-        dev_free(c->perm); dev_free(c->clusA); dev_free(c->clusB); dev_free(c->clusA2); dev_free(c->clusB2);
-        c->n = 0; c->nclus = 0; c->h_perm.clear(); c->bbox_ok = false; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
+        drop_order(c);
+        c->n = 0; c->bbox_ok = false; c->up_total = c->up_filled = 0; c->st.n_splats = 0;
         vis_drop_mask(c);
         c->vis_hidden = 0;
         e = hipEventRecord(c->up_ev[1], us);
@@ -807,7 +790,7 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
         if (e != hipSuccess) return ro.lost(e);
         // 5. the swap, and the upload-ordered state of the visibility with it
         ro.commit(n1, div_up(n1, GSR_CLUSTER), true);
-        if (vis) std::swap(c->alpha0, c->alpha0_2);
+        if (vis) c->alpha0.swap(c->alpha0_2);
     }
     // 6. the volumes against the survivors, in the order they sit in now; a new cloud to everything a frame keeps
     if ((rc = ro.finish(c->rm_ms, false))) return rc;
@@ -873,34 +856,33 @@ static int add_body(gsr_context* c, const char* who, uint32_t m, StageRows&& sta
     // ---- everything the call needs, before the first write to resident memory or to the visibility's state
     const size_t oAll = pad256(up_arena(nullptr, m, c->has_sh).bytes);
     if ((rc = ensure_stage(c, oAll + pad256((size_t)n1 * 12)))) return rc;
-    if ((rc = ro.prepare(n1))) return ro.refuse(rc);
+    if ((rc = ro.prepare(n1))) return rc;
     if (grow) {
         // the spare set is at the old capacity: it goes first (nothing reads it), and the destination set comes at the new one
         free_spare_planes(c);
-        if ((rc = ensure_spare_planes(c, cap1, false))) return ro.refuse(rc);
+        if ((rc = ensure_spare_planes(c, cap1, false))) return rc;
         for (int k = 0; k < GSR_MAX_SLOTS; ++k)
             if ((rc = alloc_splat_arrays(ro.slot_new[k], cap1))) {
                 free_spare_planes(c);
-                return ro.refuse(rc);
+                return rc;
             }
     } else if ((rc = ensure_spare_planes(c, cap0, true))) {
-        return ro.refuse(rc);
+        return rc;
     }
     // (the spare cluster bounds in force are sized for a removal, which only ever needs fewer: an add brings its own)
-    if ((rc = dev_alloc(&ro.clusA_new, nclus1)) || (rc = dev_alloc(&ro.clusB_new, nclus1))) return ro.refuse(rc);
+    if ((rc = ro.clusA_new.alloc(nclus1)) || (rc = ro.clusB_new.alloc(nclus1))) return rc;
     if (vis) {
-        if ((rc = vis_ensure_buffers(c))) return ro.refuse(rc);
-        if (grow && (rc = dev_alloc(&ro.alpha0_new, (size_t)cap1))) return ro.refuse(rc);
-        if (c->vis_mask && (rc = dev_alloc(&ro.mask_new, ((size_t)n1 + 31) / 32))) return ro.refuse(rc);
+        if ((rc = vis_ensure_buffers(c))) return rc;
+        if (grow && (rc = ro.alpha0_new.alloc((size_t)cap1))) return rc;
+        if (c->vis_mask && (rc = ro.mask_new.alloc(((size_t)n1 + 31) / 32))) return rc;
     }
-    if ((rc = ro.old_inverse(true))) return ro.refuse(rc);
+    if ((rc = ro.old_inverse(true))) return rc;
     // nothing can fail for lack of memory any more: the larger buffers take their places (none of them holds anything a frame keeps)
-    dev_free(c->clusA2); dev_free(c->clusB2);
-    c->clusA2 = ro.clusA_new; c->clusB2 = ro.clusB_new; ro.clusA_new = ro.clusB_new = nullptr;
+    c->clusA2 = std::move(ro.clusA_new); c->clusB2 = std::move(ro.clusB_new);
     if (grow) {
-        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], ro.slot_new[k]);
-        dev_free(c->alpha0_2);
-        if (!vis) dev_free(c->alpha0);                 // (at the old capacity, and valid only while a visibility is in force)
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], std::move(ro.slot_new[k]));
+        c->alpha0_2.reset();
+        if (!vis) c->alpha0.reset();                 // (at the old capacity, and valid only while a visibility is in force)
     }
     // ---- from here on a failure leaves no geometry
     ro.spare_outgrown = grow;
@@ -945,11 +927,11 @@ static int add_body(gsr_context* c, const char* who, uint32_t m, StageRows&& sta
     // 5. the swap.  What becomes the spare set is the cloud before: its cluster bounds are too few for the next edit of this one, and
     // after a growth its planes are at the wrong capacity -- both go, and the next edit that needs spare planes allocates them again
     ro.commit(n1, nclus1, true);
-    dev_free(c->clusA2); dev_free(c->clusB2);
+    c->clusA2.reset(); c->clusB2.reset();
     if (grow) {
         free_spare_planes(c);
         c->cap = cap1;
-        if (vis) { dev_free(c->alpha0); c->alpha0 = ro.alpha0_new; ro.alpha0_new = nullptr; }
+        if (vis) c->alpha0 = std::move(ro.alpha0_new);
     }
     // 6, 7. the rule of a visibility in force over the whole cloud; a new cloud to everything a frame keeps
     if ((rc = ro.finish(c->add_ms, false))) return rc;

@@ -190,7 +190,16 @@ C_ABI_SYMBOLS = [
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
+    "gsr_debug_live_handles",
 ]
+
+
+def live_handles():
+    """gsr_debug_live_handles (no context, no GPU): what the library's host code holds in this process right now, as
+    (device buffers, pinned host buffers, events, streams).  Four zeros before the first context, and again after the last close()"""
+    out = (C.c_int64 * 4)()
+    _check(load_library().gsr_debug_live_handles(out))
+    return tuple(int(v) for v in out)
 
 
 def balance_rows(row_work, count: int, cur_first=None, min_gain_permille: int = 0):
@@ -247,6 +256,7 @@ def load_library() -> C.CDLL:
     L.gsr_update_device.argtypes = [vp, i64, i64, C.POINTER(gsr_device_attrs)]
     L.gsr_move_device.argtypes = [vp, i64, i64, f32p, C.POINTER(gsr_device_attrs)]
     L.gsr_debug_check_device_source.argtypes = [vp, vp, i64]
+    L.gsr_debug_live_handles.argtypes = [C.POINTER(C.c_int64)]
     L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
     L.gsr_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
     L.gsr_get_visibility.argtypes = [vp, C.POINTER(gsr_visibility), C.POINTER(C.c_int64)]

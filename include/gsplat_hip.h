@@ -894,6 +894,10 @@ int  gsr_debug_sort_pairs_local(gsr_context* ctx, uint32_t* keys, uint32_t* vals
  * No context, no GPU: what tests/test_policy.py drives.  gsr_debug_policy_state reads a live context's state in the same layout. */
 int  gsr_debug_policy(int32_t* state16, int event, long long a, long long b);
 int  gsr_debug_policy_state(gsr_context* ctx, int32_t* state16);
+/* What the library's host code holds at this moment, in the whole process: out4 = {device buffers, pinned host buffers, events,
+ * streams} (the owning handles of csrc/gsr_host_buffers.h; the multi-GPU layer's own buffers are not counted).  Every count goes back
+ * to what it was when a context is destroyed.  No context, no GPU: four zeros in a process that never created one. */
+int  gsr_debug_live_handles(int64_t out4[4]);
 /* The frame driver's decisions (csrc/gsr_frame_plan.h, which documents the flat int32 layouts) as pure functions: which = 0 plans a
  * frame (in: the plan inputs, the slot's hints, classic_once; policy16: gsr_debug_policy's state, updated by the frame's policy events),
  * which = 1 reads an attempt's outcome from its mailbox (policy16 unused).  No context, no GPU: what tests/test_frame_plan.py drives. */
