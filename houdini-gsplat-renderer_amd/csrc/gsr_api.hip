@@ -243,6 +243,7 @@ struct FrameSlot : SlotSplatArrays {
     int last_tiles_x = 0, last_local_ty = 0, last_supers = 0;
     uint32_t last_cc_groups = 0, last_cc_per = 0;   // the grid of the slot's last k_cluster_cull (0: none, or slots in cached order instead of clusters)
     uint32_t last_pairs = 0;
+    GsrFramePlan last_plan;            // the plan of the attempt queued last in this slot (gsr_debug_last_plan)
     int super_tile = 0, stiles_x = 0, stiles_y = 0;
     uint64_t frame_id = 0;             // 1-based id of that frame, 0 = never used
     Event ev[GSR_STAGE_EVENTS];
@@ -2170,6 +2171,7 @@ static void plan_frame(gsr_context* c, FrameSlot& sl, FrontEnd& fe, bool allow_c
     fe.pos_match = in.pos_match;
     fe.p = gsr_plan_frame(in, c->cull_pol, c->slab_pol, sl.local_pol, c->classic_once, [&] { return camera_jumped(c, sl.horizon_cam, *cam); });
     const GsrFramePlan& p = fe.p;
+    sl.last_plan = p;
     j.deferred = p.deferred; j.lazy = p.lazy; j.cull = p.cull; j.phase = p.phase; j.timing = p.timing; j.timing_all = p.timing_all;
     j.dcull = p.dcull; j.local_sort = p.local || p.local_phase; j.bn_items = p.bn_items; j.bn_grid = p.bn_grid; j.k1_grid = p.k1_grid;
     j.f.cull_dilate = p.cull_dilate;
@@ -2390,32 +2392,69 @@ static int queue_preprocess(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     return e == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "k_preprocess: %s", hipGetErrorString(e));
 }
 
-// the small-frame sort (k_sort.h): K1's compacted slots -> bucket regions (counters and *d_n were cleared by K1) -> sorted (keyA, valA),
+// The small-frame sort's launches (k_sort.h) on operands given one by one: what queue_local_sort queues for a frame and what
+// gsr_debug_sort_frame queues for a test's arrays.  K1's compacted slots (keys, vals: cnt[b] items at the head of block b, *slots_dev
+// slots filled, n_slots at most) -> the bucket regions (bkt_cnt zero on entry) -> sorted, in place of the slots; *n_out = their number.
+enum LocalScatter { LS_IN_K1 = 0, LS_DIRECT = 1, LS_PER_WAVE = 2, LS_GATHER = 3 };
+struct LocalSortOps {
+    uint32_t* keys; uint2* vals;       // K1's slots in, the sorted frame out
+    const uint32_t* cnt;               // per 256-slot block
+    const uint32_t* slots_dev;
+    uint32_t n_slots;
+    LocalScatter scatter;              // which kernel fills the buckets (LS_IN_K1: K1 did)
+    uint32_t wave_grid;                // LS_PER_WAVE: workgroups (a grid below div_up(blocks, 4) loops)
+    int shift; uint32_t lo; int key_bits;
+    const uint32_t* range;             // or: { lo, shift } on the device (LS_PER_WAVE and the local kernel read them there)
+    uint32_t* bkt_cnt; uint32_t* bkt_key; uint2* bkt_val;
+    uint32_t* failed; uint32_t* n_out;
+};
+static int launch_local_sort(hipStream_t s, const LocalSortOps& o)
+{
+    if (o.scatter == LS_DIRECT)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_direct<uint2>), dim3(o.n_slots / RS_SRC_BLOCK), dim3(RS_SRC_BLOCK), 0, s, o.keys, o.vals,
+                           o.slots_dev, o.shift, o.lo, o.cnt, o.bkt_cnt, o.bkt_key, o.bkt_val, o.failed);
+    else if (o.scatter == LS_PER_WAVE)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(o.wave_grid), dim3(256), 0, s, o.keys, o.vals,
+                           o.n_slots / RS_SRC_BLOCK, o.slots_dev, o.shift, o.lo, o.cnt, o.bkt_cnt, o.bkt_key, o.bkt_val, o.failed, o.range);
+    else if (o.scatter == LS_GATHER)   // (A/B: the general gathering scatter, 2048 slots per workgroup)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint2, true>), dim3(div_up(o.n_slots, RS_TILE)), dim3(RS_THREADS), 0, s, o.keys, o.vals, o.n_slots, o.slots_dev,
+                           o.shift, o.lo, o.cnt, o.bkt_cnt, o.bkt_key, o.bkt_val, (uint32_t*)nullptr, o.failed);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, o.bkt_cnt, o.shift, o.key_bits, o.lo,
+                       o.bkt_key, o.bkt_val, o.keys, o.vals, o.failed, o.n_out, o.range);
+    return hipGetLastError() == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "small-frame sort: launch failed");
+}
+
+// the small-frame sort of a frame: K1's compacted slots -> bucket regions (counters and *d_n were cleared by K1) -> sorted (keyA, valA),
 // over the plan's buckets; a front-slab phase: over the phase's own key range, which k_slab_pick left on the device
 static int queue_local_sort(gsr_context* c, FrameSlot& sl, const FrontEnd& fe)
 {
     const FrameJob& j = sl.job;
     const GsrFramePlan& p = fe.p;
-    hipStream_t s = sl.stream;
-    const uint32_t* range = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
-    const uint32_t lo = p.local_phase ? 0u : p.bk_lo;
-    const int bshift = p.local_phase ? 0 : p.bk_shift;
-    const uint32_t n_slots = p.n_slots;
-    if (p.k1_scatters) {
-        // (K1 did it)
-    } else if (p.scatter_direct && !p.local_phase)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_direct<uint2>), dim3(n_slots / RS_SRC_BLOCK), dim3(RS_SRC_BLOCK), 0, s, sl.keyA, sl.valA,
-                           sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2);
-    else if (c->opt_scatter_direct >= 0 || p.local_phase)
-        // (grid: K1's own estimate of its workgroup-iterations, four per workgroup here)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter_k1<uint2>), dim3(std::max(1u, std::min(div_up(n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u))), dim3(256), 0, s, sl.keyA, sl.valA,
-                           n_slots / RS_SRC_BLOCK, sl.d_counts, bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, sl.d_counts + 2, range);
-    else   // (A/B: the general gathering scatter, 2048 slots per workgroup)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint2, true>), dim3(div_up(n_slots, RS_TILE)), dim3(RS_THREADS), 0, s, sl.keyA, sl.valA, n_slots, sl.d_counts,
-                           bshift, lo, sl.blk_cnt, sl.bkt_cnt, sl.bkt_key, sl.bkt_val, (uint32_t*)nullptr, sl.d_counts + 2);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint2>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, s, sl.bkt_cnt, bshift, p.key_bits, lo,
-                       sl.bkt_key, sl.bkt_val, sl.keyA, sl.valA, sl.d_counts + 2, sl.d_n, range);
-    return hipGetLastError() == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "small-frame sort: launch failed");
+    LocalSortOps o{};
+    o.keys = sl.keyA; o.vals = sl.valA; o.cnt = sl.blk_cnt; o.slots_dev = sl.d_counts; o.n_slots = p.n_slots;
+    o.scatter = p.k1_scatters ? LS_IN_K1
+              : (p.scatter_direct && !p.local_phase) ? LS_DIRECT
+              : (c->opt_scatter_direct >= 0 || p.local_phase) ? LS_PER_WAVE : LS_GATHER;
+    // (grid: K1's own estimate of its workgroup-iterations, four per workgroup here)
+    o.wave_grid = std::max(1u, std::min(div_up(p.n_slots / RS_SRC_BLOCK, 4u), div_up(j.k1_grid, 4u) + 16u));
+    o.range = p.local_phase ? sl.slab + GSR_SLAB_BINS + (j.phase == 1 ? 2 : 4) : (const uint32_t*)nullptr;
+    o.lo = p.local_phase ? 0u : p.bk_lo;
+    o.shift = p.local_phase ? 0 : p.bk_shift;
+    o.key_bits = p.key_bits;
+    o.bkt_cnt = sl.bkt_cnt; o.bkt_key = sl.bkt_key; o.bkt_val = sl.bkt_val;
+    o.failed = sl.d_counts + 2; o.n_out = sl.d_n;
+    return launch_local_sort(sl.stream, o);
+}
+
+// The position-keyed order's launches: the heads of K1's 256-slot blocks (cnt[k] items each, *slots_dev slots filled, 256 m_max at
+// most), one after the other -> dense (keys_out, vals_out); *n_out = their number.  pre: m_max words of scratch.
+static int launch_ordered_compact(hipStream_t s, const uint32_t* keys_in, const uint2* vals_in, const uint32_t* cnt, const uint32_t* slots_dev,
+                                  uint32_t m_max, uint32_t* pre, uint32_t* keys_out, uint2* vals_out, uint32_t* n_out)
+{
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, cnt, slots_dev, pre, n_out);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compact_blocks<uint2>), dim3(m_max), dim3(RS_SRC_BLOCK), 0, s, keys_in, vals_in, cnt, pre,
+                       slots_dev, keys_out, vals_out);
+    return hipGetLastError() == hipSuccess ? GSR_OK : set_err(GSR_E_HIP, "position-keyed order: launch failed");
 }
 
 // the frame's depth order in (keyA, valA): kept (a static redraw), compacted from K1's blocks (the position-keyed order), or sorted
@@ -2433,10 +2472,7 @@ static int queue_sort(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
         // K1 walked the splats nearest first: the heads of its 256-slot blocks, one after the other, ARE the sorted frame
         const uint32_t m_max = p.n_slots / RS_SRC_BLOCK;
         if ((rc = ensure_u32(c->blk_pre, c->blk_pre_cap, (size_t)m_max + 8))) return rc;
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, sl.blk_cnt, sl.d_counts, c->blk_pre, sl.d_n);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_compact_blocks<uint2>), dim3(m_max), dim3(RS_SRC_BLOCK), 0, s, sl.keyB, sl.valB, sl.blk_cnt, c->blk_pre,
-                           sl.d_counts, sl.keyA, sl.valA);
-        if (hipGetLastError() != hipSuccess) return set_err(GSR_E_HIP, "position-keyed order: launch failed");
+        if ((rc = launch_ordered_compact(s, sl.keyB, sl.valB, sl.blk_cnt, sl.d_counts, m_max, c->blk_pre, sl.keyA, sl.valA, sl.d_n))) return rc;
         c->st.sorts_skipped += 1;
         sl.key_min = j.f.key_min;
         sl.sort_valid = false;       // (what the slot holds is this frame's kept set only)
@@ -3252,6 +3288,100 @@ static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int6
     }
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_debug_sort_pairs: %s", hipGetErrorString(e));
     return rc;
+}
+
+// The depth sort of a FRAME on a test's arrays: K1's block-compacted layout in, what the frame's own drivers (radix_sort<uint2> with a
+// compacting first pass, launch_local_sort, launch_ordered_compact) make of it out.  Every array is a DevMem of this call; the bucket
+// regions are the slot's (as in gsr_debug_sort_pairs_local), and the slot's histogram is set aside for the call and put back.
+extern "C" int gsr_debug_sort_frame(gsr_context* c, int mode, uint32_t* keys, uint32_t* vals2, const uint32_t* blk_cnt, int64_t n_slots64,
+                                    int64_t n_slots_dev64, int key_bits, int allow9, uint32_t lo, int shift, int range_dev, int k1_grid,
+                                    int64_t* n_kept, uint32_t* failed)
+{
+    const bool local = mode == GSR_SORT_LOCAL_GATHER || mode == GSR_SORT_LOCAL_K1 || mode == GSR_SORT_LOCAL_DIRECT;
+    if (!c || !keys || !vals2 || !blk_cnt || !n_kept || !failed || mode < GSR_SORT_GLOBAL || mode > GSR_SORT_ORDERED)
+        return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: bad argument");
+    if (n_slots64 <= 0 || n_slots64 > 0x7fffff00ll || n_slots64 % RS_SRC_BLOCK || n_slots_dev64 < 0 || n_slots_dev64 > n_slots64 || n_slots_dev64 % RS_SRC_BLOCK)
+        return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: slot counts are multiples of %d, 0 < n_slots, 0 <= n_slots_dev <= n_slots", RS_SRC_BLOCK);
+    if (key_bits < 1 || key_bits > 32 || shift < 0 || shift > 31) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: bad key bits or bucket shift");
+    if (range_dev && mode != GSR_SORT_LOCAL_K1) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: only LOCAL_K1 reads its range from the device");
+    if (mode == GSR_SORT_LOCAL_K1 && k1_grid < 1) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: LOCAL_K1 needs a grid of at least one workgroup");
+    const uint32_t n_slots = (uint32_t)n_slots64, n_blocks = n_slots / RS_SRC_BLOCK;
+    for (uint32_t b = 0; b < n_blocks; ++b)
+        if (blk_cnt[b] > (uint32_t)RS_SRC_BLOCK) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: block %u counts %u items of %d slots", b, blk_cnt[b], RS_SRC_BLOCK);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = sync_all(c);
+    if (rc) return rc;
+    FrameSlot& sl = c->slot[0];
+    hipStream_t s = sl.stream;
+    DevMem<uint32_t> kbuf[2], cnt, ctl, pre;   // ctl: [0] slots filled, [1] items kept, [2] the sort gave up, [4..5] { lo, shift }
+    DevMem<uint2> vbuf[2];
+    if ((rc = kbuf[0].alloc(n_slots)) || (rc = kbuf[1].alloc(n_slots)) || (rc = vbuf[0].alloc(n_slots)) || (rc = vbuf[1].alloc(n_slots)) ||
+        (rc = cnt.alloc(n_blocks)) || (rc = ctl.alloc(8)) || (rc = pre.alloc((size_t)n_blocks + 8)))
+        return rc;
+    const uint32_t h_ctl[8] = {(uint32_t)n_slots_dev64, 0u, 0u, 0u, lo, (uint32_t)shift, 0u, 0u};
+    HIP_TRY(hipMemcpyAsync(kbuf[0], keys, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(vbuf[0], vals2, (size_t)n_slots * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(cnt, blk_cnt, (size_t)n_blocks * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctl, h_ctl, sizeof h_ctl, hipMemcpyHostToDevice, s));
+    uint32_t *kA = kbuf[0], *kB = kbuf[1];
+    uint2 *vA = vbuf[0], *vB = vbuf[1];
+    if (local) {
+        HIP_TRY(hipMemsetAsync(sl.bkt_cnt, 0, (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t), s));
+        LocalSortOps o{};
+        o.keys = kA; o.vals = vA; o.cnt = cnt; o.slots_dev = ctl; o.n_slots = n_slots;
+        o.scatter = mode == GSR_SORT_LOCAL_DIRECT ? LS_DIRECT : (mode == GSR_SORT_LOCAL_K1 ? LS_PER_WAVE : LS_GATHER);
+        o.wave_grid = std::min(div_up(n_blocks, 4u), (uint32_t)std::max(k1_grid, 1));
+        o.range = range_dev ? ctl + 4 : (const uint32_t*)nullptr;
+        o.lo = range_dev ? 0u : lo;       // (as a front-slab phase passes them: the kernels must take the device's)
+        o.shift = range_dev ? 0 : shift;
+        o.key_bits = key_bits;
+        o.bkt_cnt = sl.bkt_cnt; o.bkt_key = sl.bkt_key; o.bkt_val = sl.bkt_val;
+        o.failed = ctl + 2; o.n_out = ctl + 1;
+        rc = launch_local_sort(s, o);
+    } else if (mode == GSR_SORT_ORDERED) {
+        rc = launch_ordered_compact(s, kA, vA, cnt, ctl, n_blocks, pre, kB, vB, ctl + 1);
+        std::swap(kA, kB); std::swap(vA, vB);
+    } else {
+        DevMem<uint32_t> hist;             // (the slot's own histogram comes back as it was)
+        size_t hist_cap = 0;
+        sl.hist.swap(hist); std::swap(sl.hist_cap, hist_cap);
+        rc = radix_sort(sl, kA, vA, kB, vB, n_slots, key_bits, allow9 != 0, ctl + 1, RS_XCD_DEPTH != 0, cnt, ctl, mode == GSR_SORT_GLOBAL_MID);
+        const hipError_t e = hipStreamSynchronize(s);   // (before the call's histogram goes)
+        sl.hist.swap(hist); std::swap(sl.hist_cap, hist_cap);
+        if (!rc && e != hipSuccess) rc = set_err(GSR_E_HIP, "gsr_debug_sort_frame: %s", hipGetErrorString(e));
+    }
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    uint32_t out_ctl[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(out_ctl, ctl, sizeof out_ctl, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_ctl[1] > n_slots) return set_err(GSR_E_HIP, "gsr_debug_sort_frame: the device counted %u items in %u slots", out_ctl[1], n_slots);
+    *n_kept = out_ctl[1];
+    *failed = out_ctl[2];
+    if (out_ctl[1]) {
+        HIP_TRY(hipMemcpy(keys, kA, (size_t)out_ctl[1] * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(vals2, vA, (size_t)out_ctl[1] * 8, hipMemcpyDeviceToHost));
+    }
+    return GSR_OK;
+}
+
+// the plan of the attempt queued last (GSR_PLAN_OUT_FIELDS of csrc/gsr_frame_plan.h, in their order, one int32 each)
+extern "C" int gsr_debug_last_plan(gsr_context* c, int32_t* out32)
+{
+    if (!c || !out32) return set_err(GSR_E_INVALID, "gsr_debug_last_plan: NULL argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = sync_all(c);        // (a deferred frame that is rendered again is planned again)
+    if (rc) return rc;
+    FrameSlot* sl = latest_slot(c);
+    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_last_plan: no frame rendered yet");
+    const GsrFramePlan& r = sl->last_plan;
+    int o = 0;
+#define GSR_PUT(t, name) out32[o++] = (int32_t)r.name;
+    GSR_PLAN_OUT_FIELDS(GSR_PUT)
+#undef GSR_PUT
+#define GSR_COUNT(t, name) + 1
+    static_assert(0 GSR_PLAN_OUT_FIELDS(GSR_COUNT) <= 32, "gsr_debug_last_plan writes at most 32 words");
+#undef GSR_COUNT
+    return GSR_OK;
 }
 
 // ---------------------------------------------------------------------------

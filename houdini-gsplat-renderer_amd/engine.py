@@ -190,7 +190,7 @@ C_ABI_SYMBOLS = [
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
-    "gsr_debug_live_handles",
+    "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan",
 ]
 
 
@@ -216,6 +216,13 @@ def balance_rows(row_work, count: int, cur_first=None, min_gain_permille: int = 
     _check(rc if rc < 0 else 0)
     return bool(rc), out
 
+
+# gsr_debug_sort_frame's modes (include/gsplat_hip.h)
+SORT_GLOBAL, SORT_GLOBAL_MID, SORT_LOCAL_GATHER, SORT_LOCAL_K1, SORT_LOCAL_DIRECT, SORT_ORDERED = range(6)
+# GSR_PLAN_OUT_FIELDS of csrc/gsr_frame_plan.h, in their order (gsr_debug_last_plan)
+PLAN_FIELDS = ("deferred", "lazy", "cull", "jumped", "cull_dilate", "phase", "timing", "timing_all", "dcull", "cache_hit", "want_pos",
+               "ordered", "key_bits", "n_slots", "held", "local", "local_phase", "k1_scatters", "bk_lo", "bk_shift", "scatter_direct",
+               "mid_sort", "k1_grid", "bn_items", "bn_blocks", "bn_grid")
 
 POLICY_FIELDS = ("cull_pays", "cull_weak", "vis_unculled", "cull_holdoff", "cull_backoff", "cull_streak", "cull_dilate", "opt_dilate",
                  "slab_holdoff", "local_fails", "local_holdoff")
@@ -308,6 +315,8 @@ def load_library() -> C.CDLL:
     L.gsr_debug_read_storage_order.argtypes = [vp, vp, i64]
     L.gsr_debug_sort_pairs.argtypes = [vp, vp, vp, i64, i32]
     L.gsr_debug_sort_pairs_local.argtypes = [vp, vp, vp, i64, i32, C.c_uint32, i32]
+    L.gsr_debug_sort_frame.argtypes = [vp, i32, vp, vp, vp, i64, i64, i32, i32, C.c_uint32, i32, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint32)]
+    L.gsr_debug_last_plan.argtypes = [vp, vp]
     L.gsr_debug_policy.argtypes = [vp, i32, C.c_longlong, C.c_longlong]
     L.gsr_debug_policy_state.argtypes = [vp, vp]
     L.gsr_debug_frame_plan.argtypes = [i32, vp, vp, vp]
@@ -1277,6 +1286,28 @@ class Engine:
         else:
             _check(self.L.gsr_debug_sort_pairs_local(self.h, k.ctypes.data, v.ctypes.data, k.shape[0], key_bits, int(local[0]), int(local[1])))
         return k, v
+
+    def debug_sort_frame(self, mode: int, keys: np.ndarray, vals: np.ndarray, blk_cnt: np.ndarray, n_slots_dev=None, key_bits: int = 32,
+                         allow9: bool = True, lo: int = 0, shift: int = 0, range_dev: bool = False, k1_grid: int = 1 << 30):
+        """gsr_debug_sort_frame: a frame's own depth sort (mode = SORT_*) on K1's block-compacted layout -- keys[n_slots] uint32,
+        vals[n_slots, 2] uint32, blk_cnt[n_slots / 256] items at the head of every 256 slots, n_slots_dev of the slots filled as far as
+        the device knows.  Returns (sorted keys[kept], their payloads [kept, 2], failed: the local sort's "gave up" word)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1).copy()
+        v = np.ascontiguousarray(vals, dtype=np.uint32).reshape(-1).copy()
+        c = np.ascontiguousarray(blk_cnt, dtype=np.uint32).reshape(-1)
+        if v.shape[0] != 2 * k.shape[0] or c.shape[0] * 256 < k.shape[0]:
+            raise ValueError("debug_sort_frame: vals holds one pair per slot and blk_cnt one count per 256 slots")
+        kept, failed = C.c_int64(), C.c_uint32()
+        _check(self.L.gsr_debug_sort_frame(self.h, int(mode), k.ctypes.data, v.ctypes.data, c.ctypes.data if c.size else None, k.shape[0],
+                                           k.shape[0] if n_slots_dev is None else int(n_slots_dev), int(key_bits), int(bool(allow9)),
+                                           int(lo), int(shift), int(bool(range_dev)), int(min(k1_grid, 1 << 30)), C.byref(kept), C.byref(failed)))
+        return k[:kept.value], v.reshape(-1, 2)[:kept.value], int(failed.value)
+
+    def debug_last_plan(self) -> dict:
+        """the plan of the attempt queued last (csrc/gsr_frame_plan.h): which sort the frame really took"""
+        out = np.zeros(32, np.int32)
+        _check(self.L.gsr_debug_last_plan(self.h, out.ctypes.data))
+        return {k: int(x) & 0xffffffff for k, x in zip(PLAN_FIELDS, out)}
 
 
 class GSplatRenderer:

@@ -886,6 +886,29 @@ int  gsr_debug_sort_pairs(gsr_context* ctx, uint32_t* keys, uint32_t* vals, int6
  * GSR_E_INVALID if a bucket outgrows its region of 8192 keys (the pipeline then falls back to the global sort). */
 int  gsr_debug_sort_pairs_local(gsr_context* ctx, uint32_t* keys, uint32_t* vals, int64_t n, int key_bits,
                                 uint32_t bucket_lo, int bucket_shift);
+/* The depth sort of a FRAME on given data, through the frame's own host functions and kernel instantiations (uint2 payloads, the
+ * compacting first pass, a live `failed` word).  The input is K1's block-compacted layout: blk_cnt[b] (<= 256) items at the head of
+ * slots [256 b, 256 b + 256) of keys[n_slots] / vals2[n_slots][2]; what the other slots hold is never read as an item.  n_slots is
+ * the host's bound (a multiple of 256, > 0); n_slots_dev (a multiple of 256, <= n_slots) is the slot count the kernels read from
+ * device memory: only blocks below it count.  mode:
+ *   GSR_SORT_GLOBAL        the LSD passes on bits [0, key_bits), 3072 slots per workgroup; allow9 = 9-bit digits where they save a pass
+ *   GSR_SORT_GLOBAL_MID    ... in the mid-size form, 1024 slots per workgroup
+ *   GSR_SORT_LOCAL_GATHER  1024 buckets of width 2^shift from lo filled by the gathering scatter, then every bucket on its own
+ *   GSR_SORT_LOCAL_K1      ... filled by one wave per block: k1_grid workgroups of four blocks (a smaller grid loops); range_dev != 0
+ *                          hands lo and shift over in device memory, as a front-slab phase does
+ *   GSR_SORT_LOCAL_DIRECT  ... filled with one atomic per key
+ *   GSR_SORT_ORDERED       the position-keyed order: the blocks' heads one behind the other, as they are
+ * Equal keys leave the global passes in slot order and the local kernel in the order of vals2[.][0].  On return keys / vals2 hold the
+ * *n_kept items the device counted, sorted, and *failed what the local sort's "gave up" word held (a bucket beyond 8192 keys, a run of
+ * more than 64 equal keys: the order means nothing then).  GSR_E_INVALID for sizes that are no multiples of 256, n_slots == 0 and
+ * counts above 256.  All memory of the call goes with it. */
+enum { GSR_SORT_GLOBAL = 0, GSR_SORT_GLOBAL_MID = 1, GSR_SORT_LOCAL_GATHER = 2, GSR_SORT_LOCAL_K1 = 3, GSR_SORT_LOCAL_DIRECT = 4, GSR_SORT_ORDERED = 5 };
+int  gsr_debug_sort_frame(gsr_context* ctx, int mode, uint32_t* keys, uint32_t* vals2, const uint32_t* blk_cnt, int64_t n_slots,
+                          int64_t n_slots_dev, int key_bits, int allow9, uint32_t lo, int shift, int range_dev, int k1_grid,
+                          int64_t* n_kept, uint32_t* failed);
+/* The plan of the attempt queued last (csrc/gsr_frame_plan.h: GSR_PLAN_OUT_FIELDS in their order, one int32 each; out32 holds 32):
+ * which sort the frame really took. */
+int  gsr_debug_last_plan(gsr_context* ctx, int32_t* out32);
 /* The host-side policies (csrc/gsr_policy.h; DESIGN.md section 4: state table) as a pure function: state16 holds
  * [0] cull.pays [1] cull.weak [2] cull.vis_unculled [3] cull.holdoff [4] cull.backoff [5] cull.streak [6] cull.dilate [7] cull.opt_dilate
  * [8] slab.holdoff [9] local.fails [10] local.holdoff [11] (out) the event's answer; event = GsrPolicyEvent (0 upload, 1 cull allows?(a = opt),

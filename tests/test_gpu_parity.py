@@ -846,10 +846,15 @@ def test_multi_gpu_in_library_matches_single_gpu(pkg, oracle, engine, ranks, lay
     _check_contract(want, oracle, splats, cam)
 
 
-@pytest.mark.parametrize("direct,items", [("2", "1"), ("-1", "2"), ("0", "4"), ("2", "4")])
-def test_small_frame_kernel_variants_do_not_change_pixels(pkg, engine, direct, items):
-    """the small-frame sort's scatter (general gathering / one wave per K1 block / one atomic per key) and the binning kernels'
-    splats per thread are chosen by frame size; forced through the A/B hooks, every combination renders the same frames"""
+@pytest.mark.parametrize("direct,items,k1", [("2", "1", None), ("-1", "2", None), ("0", "4", None), ("2", "4", None), ("2", "1", "0"), ("0", "4", "0")],
+                         ids=["2-1", "-1-2", "0-4", "2-4", "2-1-k1off", "0-4-k1off"])
+def test_small_frame_kernel_variants_do_not_change_pixels(pkg, engine, direct, items, k1):
+    """the small-frame sort's scatter and the binning kernels' splats per thread are chosen by frame size; forced through the A/B
+    hooks, every combination renders the same frames.  Which kernel fills the buckets: with GSR_K1_SCATTER at its default (1) and
+    GSR_SCATTER_DIRECT >= 0 K1 scatters itself (cases 2-1, 0-4, 2-4: no scatter kernel at all); GSR_SCATTER_DIRECT = -1 launches the
+    general gathering k_bucket_scatter<uint2, true> (case -1-2); GSR_K1_SCATTER = 0 leaves the scatter to a kernel of its own:
+    k_bucket_scatter_direct<uint2>, one atomic per key, with GSR_SCATTER_DIRECT = 2 (case 2-1-k1off) and k_bucket_scatter_k1<uint2>, one
+    wave per K1 block, with GSR_SCATTER_DIRECT = 0 (case 0-4-k1off).  The plans the frames kept (debug_last_plan) prove it"""
     import os
     splats = pkg.scenes.make_scene(300000, seed=77, sh=True)
     w, h = 800, 608
@@ -860,8 +865,10 @@ def test_small_frame_kernel_variants_do_not_change_pixels(pkg, engine, direct, i
         want = [engine.render(c) for c in cams]
     finally:
         engine.set_option(pkg.engine.OPT_OCCLUSION_CULL, 1)
-    old = {k: os.environ.get(k) for k in ("GSR_SCATTER_DIRECT", "GSR_BN_ITEMS")}
+    old = {k: os.environ.get(k) for k in ("GSR_SCATTER_DIRECT", "GSR_BN_ITEMS", "GSR_K1_SCATTER")}
     os.environ["GSR_SCATTER_DIRECT"], os.environ["GSR_BN_ITEMS"] = direct, items
+    if k1 is not None:
+        os.environ["GSR_K1_SCATTER"] = k1
     try:
         eng = pkg.Engine(0)                     # (the hooks are read when a context is created)
     finally:
@@ -872,9 +879,15 @@ def test_small_frame_kernel_variants_do_not_change_pixels(pkg, engine, direct, i
         eng.set_option(pkg.engine.OPT_OCCLUSION_CULL, 2)
         eng.set_option(pkg.engine.OPT_LOCAL_SORT, 2)      # the small-frame sort whatever the frame keeps
         eng.upload(splats)
+        plans = []
         for k, c in enumerate(cams):
             assert np.array_equal(eng.render(c), want[k]), f"frame {k} differs"
+            plans.append(eng.debug_last_plan())
         assert eng.stats()["frames_culled"] >= 4 and eng.stats()["frames_resorted"] == 0
+        local = [p for p in plans if p["local"]]            # (the first frame has no prediction; a repaired frame ends on the global passes)
+        assert len(local) >= 2
+        for p in local:
+            assert p["k1_scatters"] == (1 if k1 is None and direct != "-1" else 0) and p["scatter_direct"] == (direct == "2")
     finally:
         eng.close()
 
