@@ -2,9 +2,10 @@
 // per-frame kernel pipeline and the C ABI declared in include/gsplat_hip.h.
 // (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end; the kernels that
 // write, edit and read the resident layout -- once per geometry change, not per frame -- in k_resident.h, k_visibility.h, k_remove.h,
-// k_add.h and k_read.h.)
+// k_add.h and k_read.h.  The debug read-backs and sort doors are in gsr_debug_read.h, included in front of the edits.)
 // What the context, its frame slots and an edit in progress allocate is held by the handles of gsr_host_buffers.h: a member that owns
-// is a handle, a raw pointer never owns.  There is no free list: gsr_destroy deletes the context, and a call that fails returns.
+// is a handle, a raw pointer never owns, and a buffer that grows carries its capacity (DevVec; TileSet, WirePair and MortonScratch
+// where several share one).  There is no free list: gsr_destroy deletes the context, and a call that fails returns.
 //
 // Pipeline per gsr_render (all on one HIP stream):
 //   k_cluster_cull         clusters of 64 Morton-ordered splats vs clip planes / screen / band / depth horizons (k_cluster.h)
@@ -156,34 +157,27 @@ struct FrameSlot : SlotSplatArrays {
     Event ev_pairs;                    // the frame's pair count has reached host memory
     DevMem<uint32_t> d_n;              // splats that survived culling = items after the first sort pass
     StageBuf depth_stage;              // device copy of a host depth buffer
-    DevMem<float> dpyr;                // depth-tested frames: the two tile-max pyramids of the opaque pass's depth (k_cluster.h), by
-    size_t dpyr_cap = 0;               // frame parity: [par][which], dpyr_cap floats each
+    DevVec<float> dpyr;                // depth-tested frames: the two tile-max pyramids of the opaque pass's depth (k_cluster.h), by frame parity:
+                                       // [par][which], cap() floats each; behind them the per-tile "covered" array k_blend reads (5 planes of cap())
     DevMem<uint32_t> dactive;          // [2] by parity: "some tile's largest depth is below 1" (something can be culled)
     int dpar = 0;                      // parity of the slot's last depth-tested frame
     bool dpyr_built = false;           // the pyramids of parity `dpar` hold this frame's depth buffer (a frame that only LOOKED for covered pixels has none)
     bool sorted_dculled = false;       // the cached depth order holds a frame that was culled against its depth buffer
     // scan / sort scratch
-    DevMem<uint32_t> hist;
-    size_t hist_cap = 0;
+    DevVec<uint32_t> hist;             // (ensure_counts)
     DevMem<uint32_t> totals;           // [512] per-digit totals of the current radix pass
     // pairs
-    DevMem<uint2> pvA;                           // super-tile lists: (splat index, tile column/row mask) per entry
-    size_t pair_cap = 0;
-    DevMem<int32_t> sstart, send;                // super-tile ranges
-    DevMem<uint4> tile_work;           // per tile: entries scanned, records gathered, wave-record evaluations
-    size_t tile_cap = 0;
+    DevVec<uint2> pvA;                 // super-tile lists: (splat index, tile column/row mask) per entry; cap() + 4 (the blend kernel scans in 4-entry steps)
+    TileSet tiles;                     // the super-tile ranges, the per-tile bookkeeping, the tiles lazy colour gave up: one capacity
     // front-slab frames
-    DevMem<uint4> tile_work_a;         // phase 1's per-tile bookkeeping (tile_cap entries)
-    DevMem<float> tbuf;                // per pixel of the band: the transmittance phase 1 left
-    size_t tbuf_cap = 0;
+    DevVec<float> tbuf;                // per pixel of the band: the transmittance phase 1 left
     DevMem<float> hpyr2;               // the pyramid of "this tile is finished" phase 2 culls against (GSR_PYR_FLOATS)
     DevMem<uint32_t> slab;             // [GSR_SLAB_BINS + 8] histogram of the surviving clusters' nearest keys; then [0] the slab key, [1] clusters,
                                        // [2..5] the bucket ranges of the two phases' small-frame sorts (k_slab_pick)
     bool slab_dirty = false;           // a phase 1 filled the histogram and no phase 2 followed (its cull pass is what clears it): the
                                        // next front-slab frame clears it itself before it counts
-    DevMem<int32_t> redo;              // lazy colour: tiles the plain blend kernel gave up (tile_cap entries)
-    DevMem<int32_t> order;             // blockIdx -> tile, heaviest tiles first: written by k_tile_order at the end of a frame
-    size_t order_cap = 0;              //   for this slot's next frame (valid while the tile geometry stays what it was)
+    DevVec<int32_t> order;             // blockIdx -> tile, heaviest tiles first: written by k_tile_order at the end of a frame
+                                       //   for this slot's next frame (valid while the tile geometry stays what it was)
     bool order_valid = false;
     int order_age = 0;                 // frames the table has stood (tiles alike: it is rebuilt every opt_order_keep frames only)
     int order_sig[6] = {0, 0, 0, 0, 0, 0}, order_per_xcd = 0;
@@ -224,8 +218,7 @@ struct FrameSlot : SlotSplatArrays {
     bool last_lazy = false;            // the last frame of this slot left colours pending
     StageBuf fb;                       // staging for host-pointer output: pixels of the context's target format; cleared per band shape and format
     StageBuf aovb;                     // staging for a host-pointer AOV plane: two floats per band pixel; cleared per band shape
-    DevMem<float> fb32;                // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
-    size_t fb32_cap = 0;
+    DevVec<float> fb32;                // packed target formats and over-frames, front-slab frames: the f32 pixels phase 1 leaves for phase 2 (k_blend.h: out_format)
     StageBuf bgb;                      // device copy of a host background image: per slot, staged anew by every attempt of a frame
     // small device/host mailboxes
     DevMem<unsigned long long> counters;     // k_sum_work's layout: [1]/[2] records gathered (frame/running), [3]/[4] list entries
@@ -293,14 +286,12 @@ struct gsr_context {
     FrameSlot slot[GSR_MAX_SLOTS];
     // position-keyed order (GSR_OPT_SORT_CACHE = 2): all splats in depth order for one camera position
     DevMem<uint32_t> pos_order;
-    size_t pos_cap = 0;
     bool pos_valid = false;
     uint64_t pos_gen = 0;
     float pos_cam[3] = {0, 0, 0}, last_cam[3] = {0, 0, 0};
     uint32_t pos_kmin = 0, pos_kmax = 0;
     bool last_cam_set = false;
-    DevMem<uint32_t> blk_pre;          // exclusive prefix of K1's per-iteration counts (k_scan_counts)
-    size_t blk_pre_cap = 0;
+    DevVec<uint32_t> blk_pre;          // exclusive prefix of K1's per-iteration counts (k_scan_counts; ensure_counts)
     int opt_order_keep = 32;           // (A/B hook, GSR_ORDER_KEEP in the environment: 0 = no tile order where the tiles are alike)
     int opt_fuse_order = 1;            // (A/B hook, GSR_FUSE_ORDER) the tile order is built in the frame-end launch instead of behind it
     int opt_mid_sort = 1;              // (A/B hook, GSR_MID_SORT) RS_ITEMS_MID keys per thread in the global sort passes of mid-size frames
@@ -312,8 +303,7 @@ struct gsr_context {
     int nslots = 1;                    // frames in flight (GSR_OPT_FRAMES_IN_FLIGHT): serial by default -- occlusion culling wants the
                                        // horizons of the frame just before, and two slots hand it those of the frame before that
 
-    DevMem<int32_t> tile_map;          // blockIdx -> tile (XCD-aware order), -1 = idle block
-    size_t map_cap = 0;
+    DevVec<int32_t> tile_map;          // blockIdx -> tile (XCD-aware order), -1 = idle block
     int map_w = 0, map_h = 0, map_si = -1, map_sc = 0, map_rpb = -1, map_first = -1, map_shift = -1, map_grid = 0;
 
     int shard_index = 0, shard_count = 1, shard_layout = 0;   // layout: 0 = interleaved rows, 1 = contiguous bands
@@ -340,19 +330,14 @@ struct gsr_context {
                                        // builds its depth pyramid in a launch of its own, IN FRONT of k_cluster_cull (which then culls against it
                                        // too); otherwise the pyramid is built beside the cluster tests, for K1 alone (no extra launch)
     bool order_pays = false;           // k_sum_work's other verdict: the tiles differ enough in work for k_tile_order to pay
-    DevMem<unsigned long long> wire_zbuf;      // wireframe overlay: (depth bits, splat index) per pixel ...
-    DevMem<float> wire_out;                    // ... and the image staged for a host target
+    WirePair wire;                             // wireframe overlay: the z-buffer and the image staged for a host target, kept between calls
     DevMem<uint32_t> wire_inv;                 // ... and, with spatially ordered storage, upload index -> storage slot (built on first use per geometry; gsr_update scatters through it too)
     uint64_t wire_inv_gen = 0;
-    size_t wire_cap = 0;                       // pixels both hold
     // An upload in progress.  The registerUpdate()-layout arrays of ALL its entries sit in one device arena (sized at gsr_upload_begin,
     // kept between uploads: an animated sequence re-stages every cook), in upload order; gsr_upload_end orders and packs them (k_pack).
-    DevMem<char> stage;
-    size_t stage_cap = 0;
-    DevMem<char> stage_raw;                    // ... and the raw float arrays of ONE gsr_upload_append_raw call (quantised into the arena)
-    size_t stage_raw_cap = 0;
-    DevMem<uint32_t> up_kA, up_kB, up_vA, up_vB;   // Morton codes / upload indices, ping-pong (kept between uploads)
-    size_t up_sort_cap = 0;
+    DevVec<char> stage;                        // (ensure_stage)
+    DevVec<char> stage_raw;                    // ... and the raw float arrays of ONE gsr_upload_append_raw call (quantised into the arena); exact
+    MortonScratch up_sort;                     // Morton codes / upload indices, ping-pong (kept between uploads)
     DevMem<float> up_part;                     // bounding-box partials
     Event up_ev[4];
     double up_t_begin = 0.0, up_h2d_ms = 0.0, up_quant_ms = 0.0;
@@ -670,11 +655,7 @@ extern "C" int gsr_set_target_format(gsr_context* c, int format)
     if (rc) return rc;
     rc = gsr_internal_comm_sync(c);
     if (rc) return rc;
-    for (int k = 0; k < GSR_MAX_SLOTS; ++k) {   // the staging images are laid out for the old pixel size
-        FrameSlot& sl = c->slot[k];
-        sl.fb.release();
-        sl.fb32.reset(); sl.fb32_cap = 0;
-    }
+    for (FrameSlot& sl : c->slot) { sl.fb.release(); sl.fb32.reset(); }   // the staging images are laid out for the old pixel size
     c->target_format = format;
     return GSR_OK;
 }
@@ -729,11 +710,8 @@ static UpArena up_arena(char* base, size_t total, bool has_sh)
 }
 static double up_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// The arena holds `bytes` (kept between uploads and edits; only ever grown, and what it held does not survive a growth).
-static int ensure_stage(gsr_context* c, size_t bytes)
-{
-    return bytes <= c->stage_cap ? GSR_OK : replace(c->stage, c->stage_cap, bytes + 256, bytes + 256);
-}
+// The arena holds `bytes` (kept between uploads and edits; only ever grown, to 256 bytes beyond the need; what it held does not survive it).
+static int ensure_stage(gsr_context* c, size_t bytes) { return bytes <= c->stage.cap() ? GSR_OK : c->stage.ensure(bytes + 256); }
 // The first `count` events of the upload / edit clock.  oom_code: hipErrorOutOfMemory comes back as GSR_E_OOM (upload, update, remove)
 // or, like every other failure, as GSR_E_HIP (move, add): the verbs differ there, and each keeps its code.
 static int ensure_up_events(gsr_context* c, int count, const char* who, bool oom_code)
@@ -884,7 +862,7 @@ extern "C" int gsr_upload_append_raw(gsr_context* c, int64_t n64, const gsr_raw_
     const size_t rEach = a->sh_scheme == 2 ? pad256((size_t)n * 12) : (a->sh_scheme == 3 ? pad256((size_t)n * 4) : 0);
     const size_t need = rC + rS + rO + rArr + rEach * sh_live + 256;
     int rc = GSR_OK;
-    if (need > c->stage_raw_cap && (rc = regrow(us, c->stage_raw, c->stage_raw_cap, need, need))) return rc;
+    if ((rc = c->stage_raw.ensure_drained(us, need))) return rc;
     char* base = c->stage_raw;
     auto take = [&](size_t bytes) { char* p = base; base += bytes; return p; };
     hipError_t e = hipSuccess;
@@ -1067,11 +1045,8 @@ __attribute__((visibility("hidden"))) int gsr_internal_stitch(gsr_context* c, co
 
 // ---------------------------------------------------------------------------
 // scan + sort drivers (all on the slot's stream)
-static int ensure_u32(DevMem<uint32_t>& p, size_t& cap, size_t need)
-{
-    const size_t want = need + need / 4 + 1024;
-    return need <= cap ? GSR_OK : replace(p, cap, want, want);
-}
+// the sort histogram and K1's prefix follow a frame's (or a cloud's) size: a quarter and 1024 words beyond the need
+static int ensure_counts(DevVec<uint32_t>& v, size_t need) { return need <= v.cap() ? GSR_OK : v.ensure(need + need / 4 + 1024); }
 
 template <typename V, int DBITS, bool GATHER, int ITEMS>
 static int radix_pass(FrameSlot& sl, uint32_t* kA, V* vA, uint32_t* kB, V* vB, uint32_t n, const uint32_t* n_dev,
@@ -1104,7 +1079,7 @@ static int radix_sort(FrameSlot& sl, uint32_t*& kA, V*& vA, uint32_t*& kB, V*& v
     }
     if (bits <= 0) bits = 1;
     const uint32_t nblk = div_up(n, (uint32_t)RS_THREADS * (uint32_t)(mid ? RS_ITEMS_MID : RS_ITEMS));
-    int rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)512 * nblk + 8);
+    int rc = ensure_counts(sl.hist, (size_t)512 * nblk + 8);
     if (rc) return rc;
     const int p8 = (bits + 7) / 8, p9 = (bits + 8) / 9;
     const bool use9 = allow9 && p9 < p8;
@@ -1161,22 +1136,7 @@ static int position_box(gsr_context* c, const float* P, uint32_t n, hipStream_t 
     c->bbox_ok = ok;
     return GSR_OK;
 }
-// (2) the scratch of the sort: Morton codes / upload indices, ping-pong (kept between uploads and moves)
-static bool ensure_order_scratch(gsr_context* c, uint32_t n)
-{
-    if ((size_t)n <= c->up_sort_cap) return true;
-    auto drop = [&]() { c->up_kA.reset(); c->up_kB.reset(); c->up_vA.reset(); c->up_vB.reset(); };
-    drop();
-    c->up_sort_cap = 0;
-    const size_t want = (size_t)n + n / 8 + 1024;
-    if (c->up_kA.alloc(want) || c->up_kB.alloc(want) || c->up_vA.alloc(want) || c->up_vB.alloc(want)) {
-        drop();
-        (void)hipGetLastError();
-        return false;
-    }
-    c->up_sort_cap = want;
-    return true;
-}
+// (2) the scratch of the sort, kept between uploads and moves: c->up_sort.hold(n) (MortonScratch, gsr_host_buffers.h)
 // (3) 30-bit Morton codes in the box of (1), sorted stably with the upload index as the value: perm[j] = upload index of the splat
 // in slot j (perm: n entries; the scratch of (2) is there)
 static int morton_order(gsr_context* c, const float* P, uint32_t n, uint32_t* perm, const char* who)
@@ -1189,7 +1149,7 @@ static int morton_order(gsr_context* c, const float* P, uint32_t n, uint32_t* pe
         sc[k] = ext > 0.0 ? (float)(1023.999 / ext) : 0.0f;
         if (!std::isfinite(sc[k])) sc[k] = 0.0f;
     }
-    uint32_t *kA = c->up_kA, *kB = c->up_kB, *vA = c->up_vA, *vB = c->up_vB;
+    uint32_t *kA = c->up_sort.kA, *kB = c->up_sort.kB, *vA = c->up_sort.vA, *vB = c->up_sort.vB;
     hipLaunchKernelGGL(k_morton_codes, dim3(div_up(n, 256)), dim3(256), 0, sl.stream, P, n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], kA, vA);
     int rc = radix_sort(sl, kA, vA, kB, vB, n, 30, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);   // (leaves the result in what kA / vA name now)
     if (!rc && hipMemcpyAsync(perm, vA, (size_t)n * 4, hipMemcpyDeviceToDevice, sl.stream) != hipSuccess) rc = set_err(GSR_E_HIP, "%s: storage order", who);
@@ -1211,7 +1171,7 @@ static int order_and_pack(gsr_context* c)
     if (c->opt_morton && c->bbox_ok && n > 1) {
         // without the scratch the splats simply stay in upload order (perm = NULL: ties then break by upload index, the
         // documented meaning of an unordered store) and get their clusters
-        const bool have = ensure_order_scratch(c, n);
+        const bool have = c->up_sort.hold(n) == GSR_OK;
         if (have && !(rc = c->perm.alloc((size_t)n))) {
             rc = morton_order(c, A.P, n, c->perm, "gsr_upload_end");
             if (rc) { c->perm.reset(); return rc; }
@@ -1484,7 +1444,7 @@ static int build_tile_map(gsr_context* c, const GsrFrame& f)
     std::vector<int32_t> map(chunk * 8 + 8, -1);
     for (int x = 0; x < 8; ++x)
         for (size_t k = 0; k < per_xcd[x].size(); ++k) map[k * 8 + x] = per_xcd[x][k];
-    if (map.size() > c->map_cap && (rc = replace(c->tile_map, c->map_cap, map.size(), map.size()))) return rc;
+    if ((rc = c->tile_map.ensure(map.size()))) return rc;
     HIP_TRY(hipMemcpy(c->tile_map, map.data(), map.size() * 4, hipMemcpyHostToDevice));
     c->map_grid = (int)(chunk * 8);
     c->map_w = f.width; c->map_h = f.height; c->map_si = c->shard_index; c->map_sc = c->shard_count; c->map_rpb = f.shard_rpb; c->map_first = f.shard_first;
@@ -1543,12 +1503,12 @@ static inline int mark(FrameSlot& sl, int k)
 // large enough, so when a buffer exists the back end is queued SPECULATIVELY right behind the count (both
 // kernels clamp to the buffer's capacity) and the host reads D while the GPU is already placing: the stream
 // never drains mid-frame.  Only if D turns out to exceed the capacity (first frame, or the pair count grew by
-// more than the 25 % headroom) is the buffer regrown and the back end run again.
+// more than the 25 % headroom) is the buffer grown and the back end run again.
 static GsrRangeArgs range_args(gsr_context* c, FrameSlot& sl)
 {
     const FrameJob& j = sl.job;
     GsrRangeArgs a;
-    a.totals = sl.totals; a.n_super = j.n_super; a.sstart = sl.sstart; a.send = sl.send; a.host_total = sl.h_total.dev();
+    a.totals = sl.totals; a.n_super = j.n_super; a.sstart = sl.tiles.sstart; a.send = sl.tiles.send; a.host_total = sl.h_total.dev();
     a.ticket = j.ticket; a.max_pairs = (unsigned long long)GSR_MAX_PAIRS; a.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr.get());
     a.lazy_hint = c->lazy_hint; a.n_sorted = sl.d_n; a.k1_counts = sl.d_counts; a.sorted_keys = sl.keyA;
     a.depth_active = j.dcull ? sl.dactive + j.dpar : (const uint32_t*)nullptr;
@@ -1562,7 +1522,7 @@ static inline void tile_sig(const GsrFrame& f, int* sig /* [6] */)
     std::memcpy(sig, now, sizeof now);
 }
 
-static inline int32_t list_cap(const FrameSlot& sl) { return (int32_t)std::min<size_t>(sl.pair_cap, (size_t)0x7fffffff); }
+static inline int32_t list_cap(const FrameSlot& sl) { return (int32_t)std::min<size_t>(sl.pvA.cap(), (size_t)0x7fffffff); }
 
 static GsrSumArgs sum_args(const FrameJob& j)
 {
@@ -1598,16 +1558,16 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
         a.near_alpha = persp ? 0.5f * (1.0f - f.pr[10]) : 0.0f;
         a.near_scale = persp ? 1.12f : 0.0f;
     }
-    a.tile_cov = (with_depth && j.dcull && !j.dblind) ? sl.dpyr + 4 * sl.dpyr_cap : (const float*)nullptr;
+    a.tile_cov = (with_depth && j.dcull && !j.dblind) ? sl.dpyr + 4 * sl.dpyr.cap() : (const float*)nullptr;
     a.idx_mask = f.idx_mask; a.zq0 = f.zq0; a.zqs = f.zqs;
-    a.tile_dmax = (with_depth && j.dcull && !j.dblind && f.idx_mask != 0xffffffffu) ? sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap + f.pyr_off[0] : (const float*)nullptr;
+    a.tile_dmax = (with_depth && j.dcull && !j.dblind && f.idx_mask != 0xffffffffu) ? sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr.cap() + f.pyr_off[0] : (const float*)nullptr;
     a.width = f.width; a.height = f.height; a.tiles_x = f.tiles_x; a.local_tiles = j.local_tiles;
     a.shard = gsr_frame_shard(f, 0); a.band_rows = j.band_rows;
     a.super_shift = f.super_shift; a.rect_shift = f.rect_shift; a.stiles_x = f.stiles_x; a.use_map = j.use_map ? 1 : 0; a.flags = f.flags;
     a.list_cap = list_cap(sl);
     a.sup_work = (a.use_map && c->opt_swizzle >= 2 && sl.sup_work) ? sl.sup_work + 256 * sl.sup_par : nullptr;
-    a.slab = j.phase; a.tbuf = sl.tbuf; a.tile_work_a = sl.tile_work_a;
-    uint4* const tw = j.phase == 1 ? sl.tile_work_a : sl.tile_work;   // (phase 1's bookkeeping is kept for phase 2 and the frame end)
+    a.slab = j.phase; a.tbuf = sl.tbuf; a.tile_work_a = sl.tiles.tile_work_a;
+    uint4* const tw = j.phase == 1 ? sl.tiles.tile_work_a : sl.tiles.tile_work;   // (phase 1's bookkeeping is kept for phase 2 and the frame end)
     // heaviest-first table of this slot's previous frame, if that frame had the same tiles
     int sig[6];
     tile_sig(f, sig);
@@ -1616,7 +1576,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     const unsigned grid = ordered ? (unsigned)(8 * sl.order_per_xcd) : a.use_map ? (unsigned)c->map_grid : (unsigned)j.local_tiles;
     GsrLazyArgs lz;
     lz.f = f; lz.colrow = c->colrow;
-    lz.redo = j.lazy ? sl.redo : nullptr;
+    lz.redo = j.lazy ? sl.tiles.redo : nullptr;
     lz.redo_count = reinterpret_cast<uint32_t*>(sl.lazy_ctr.get());
     // (a packed target: the kernel converts at its store; the f32 pointer is the slot's own buffer, which only front-slab frames use)
     // (a frame over a background is laid out like a packed one whatever its format: the composited pixel goes to the target, the raw one
@@ -1627,7 +1587,7 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
     // One launch of the blend family: every member takes the same arguments up to the lazy-colour block; the AOV kernels take the
     // plane behind them (k_blend.h: k_blend_aov), the background kernels what the frame is composited over (k_blend_over)
     auto launch = [&](auto kernel, unsigned g, const int32_t* map, uint4* work, auto... tail) {
-        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, a, map, sl.pvA, sl.sstart, sl.send, sl.rec, tgt, work, sl.zwin, j.d_depth, lz, tail...);
+        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), 0, s, a, map, sl.pvA, sl.tiles.sstart, sl.tiles.send, sl.rec, tgt, work, sl.zwin, j.d_depth, lz, tail...);
     };
     auto launch_verb = [&](auto plain, auto aov, auto bg, unsigned g, const int32_t* map, uint4* work) {
         if (j.aov_target) launch(aov, g, map, work, j.aov_target);
@@ -1651,8 +1611,8 @@ static int queue_blend(gsr_context* c, FrameSlot& sl, bool with_depth, bool guar
         if (with_depth) launch_verb(k_blend<true>, k_blend_aov<true>, k_blend_over<true>, grid, tmap, tw);
         else launch_verb(k_blend<false>, k_blend_aov<false>, k_blend_over<false>, grid, tmap, tw);
         // the tiles that met a pending colour, with on-demand evaluation (normally none: the blocks exit at once)
-        if (j.lazy && with_depth) launch_verb(k_blend_lazy<true>, k_blend_aov_lazy<true>, k_blend_over_lazy<true>, (unsigned)j.local_tiles, c->tile_map, sl.tile_work);
-        else if (j.lazy) launch_verb(k_blend_lazy<false>, k_blend_aov_lazy<false>, k_blend_over_lazy<false>, (unsigned)j.local_tiles, c->tile_map, sl.tile_work);
+        if (j.lazy && with_depth) launch_verb(k_blend_lazy<true>, k_blend_aov_lazy<true>, k_blend_over_lazy<true>, (unsigned)j.local_tiles, c->tile_map, sl.tiles.tile_work);
+        else if (j.lazy) launch_verb(k_blend_lazy<false>, k_blend_aov_lazy<false>, k_blend_over_lazy<false>, (unsigned)j.local_tiles, c->tile_map, sl.tiles.tile_work);
         if (nb > 1) HIP_TRY(hipEventRecord(sl.ev_band[b], s));
     }
     HIP_TRY(hipGetLastError());
@@ -1675,7 +1635,7 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
         const uint32_t grid = std::min(nblk, j.bn_grid) + bn_extra + (j.ranges_folded ? 1u : 0u);
 #define GSR_PLACE(I) hipLaunchKernelGGL((f.idx_mask != 0xffffffffu ? k_bin_place<I, true> : k_bin_place<I, false>), dim3(grid), dim3(BN_THREADS), lds, s, sl.valA, sl.d_n,          \
-                                        f.super_shift - f.rect_shift, shd, f.stiles_x, j.n_super, sl.hist, sl.sstart, nblk, (uint32_t)sl.pair_cap, sl.pvA, ra,   \
+                                        f.super_shift - f.rect_shift, shd, f.stiles_x, j.n_super, sl.hist, sl.tiles.sstart, nblk, (uint32_t)sl.pvA.cap(), sl.pvA, ra,   \
                                         f.idx_mask != 0xffffffffu ? sl.zwin : (const float*)nullptr, f.zq0, f.zqs)
         if (j.bn_items == 1) GSR_PLACE(1); else if (j.bn_items == 2) GSR_PLACE(2); else GSR_PLACE(4);
 #undef GSR_PLACE
@@ -1686,7 +1646,7 @@ static int queue_back_end(gsr_context* c, FrameSlot& sl)
         // colours for the front of every super-tile list: as deep as the previous frame's tiles scanned (+ headroom)
         const bool predict = c->prefix_valid && !(f.flags & GSR_FLAG_LAZY_NO_PREFIX);
         hipLaunchKernelGGL(k_colour_prefix, dim3((unsigned)(j.n_super * CL_BLOCKS_PER_LIST)), dim3(CL_THREADS), 0, s, f, sl.pvA,
-                           sl.sstart, sl.send, (f.flags & GSR_FLAG_LAZY_NO_PREFIX) ? c->prefix_none : (predict ? c->prefix : c->prefix_all),
+                           sl.tiles.sstart, sl.tiles.send, (f.flags & GSR_FLAG_LAZY_NO_PREFIX) ? c->prefix_none : (predict ? c->prefix : c->prefix_all),
                            (int)list_cap(sl), c->colrow, sl.rec, sl.colour_evals);
         HIP_TRY(hipGetLastError());
     }
@@ -1728,9 +1688,9 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
             hz.dbg = sl.dbg_viol;
         }
     }
-    if (j.phase == 2) { hz.slab = 2; hz.tile_work_a = sl.tile_work_a; }
+    if (j.phase == 2) { hz.slab = 2; hz.tile_work_a = sl.tiles.tile_work_a; }
     const int nblocks8 = ((j.f.tiles_x + 7) >> 3) * ((j.f.tiles_y + 7) >> 3);
-    hipLaunchKernelGGL(k_tile_pass, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tile_work, g, sl.sstart, sl.send, hz, sl.partial, sl.st_scan);
+    hipLaunchKernelGGL(k_tile_pass, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tiles.tile_work, g, sl.tiles.sstart, sl.tiles.send, hz, sl.partial, sl.st_scan);
     uint32_t* const prefix_arg = (j.f.sh_order > 0 && c->opt_lazy) ? c->prefix : (uint32_t*)nullptr;
     const uint32_t* const redo_arg = j.lazy ? reinterpret_cast<const uint32_t*>(sl.lazy_ctr.get()) : (const uint32_t*)nullptr;
     uint32_t* const work_next = sl.sup_work ? sl.sup_work + 256 * (sl.sup_par ^ 1) : (uint32_t*)nullptr;
@@ -1748,28 +1708,26 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     if (order_kept) sl.order_age += 1; else sl.order_valid = false;
     const bool order_now = j.use_map && (order_due || order_refresh) && j.local_tiles > 0 && j.n_super <= 256 && sl.sup_work;
     const int per_xcd = 2 * ((j.n_super + 15) / 16) << (2 * j.f.super_shift);
-    if (order_now && (size_t)8 * per_xcd > sl.order_cap) {
-        const int rc = regrow(s, sl.order, sl.order_cap, (size_t)8 * per_xcd, (size_t)8 * per_xcd);
-        if (rc) return rc;
-    }
+    if (order_now)
+        if (const int rc = sl.order.ensure_drained(s, (size_t)8 * per_xcd)) return rc;
     // the next frame's tile order is built BESIDE the frame's sums (and the horizon dilation), in the same launch (k_blend.h: k_frame_end_order)
     const bool fused_order = order_now && c->opt_fuse_order != 0;
     if (sl.horizon_valid) sl.hpyr_re = std::min(c->cull_pol.dilate, GSR_DILATE_EXACT_MAX);
     if (fused_order) {
-        const GsrOrderArgs oa{sl.tile_work, j.f.tiles_y, sl.sup_work + 256 * sl.sup_par, per_xcd, sl.order};
+        const GsrOrderArgs oa{sl.tiles.tile_work, j.f.tiles_y, sl.sup_work + 256 * sl.sup_par, per_xcd, sl.order};
         const int ndil = sl.horizon_valid ? nblocks8 : 0;
         hipLaunchKernelGGL(k_frame_end_order, dim3(9u + (unsigned)((ndil + TO_THREADS / 64 - 1) / (TO_THREADS / 64))), dim3(TO_THREADS), 0, s, sl.partial, nblocks8, ndil, g, sl.counters, sl.d_n, sl.d_frame,
-                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.sstart, sl.send, c->lazy_hint, work_next, hz, sl.st_scan, sl.hpyr_re, oa);
+                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.tiles.sstart, sl.tiles.send, c->lazy_hint, work_next, hz, sl.st_scan, sl.hpyr_re, oa);
         HIP_TRY(hipGetLastError());
     } else if (sl.horizon_valid) {
         // the frame's sums and verdict, and BESIDE them (one launch) the next frame's pyramid: every tile's horizon widened to its
         // neighbourhood, into the slot's other pyramid buffer
         hipLaunchKernelGGL(k_frame_end, dim3((unsigned)nblocks8 + 1u), dim3(SW_THREADS), 0, s, sl.partial, nblocks8, g, sl.counters, sl.d_n, sl.d_frame,
-                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.sstart, sl.send, c->lazy_hint, work_next, hz, sl.st_scan, sl.hpyr_re);
+                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.tiles.sstart, sl.tiles.send, c->lazy_hint, work_next, hz, sl.st_scan, sl.hpyr_re);
         HIP_TRY(hipGetLastError());
     } else {
         hipLaunchKernelGGL(k_sum_work, dim3(1), dim3(SW_THREADS), 0, s, sl.partial, nblocks8, g, sl.counters, sl.d_n, sl.d_frame,
-                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.sstart, sl.send, c->lazy_hint, work_next, hz, sl.st_scan);
+                           prefix_arg, redo_arg, sl.colour_evals, sl.lazy_ctr + 1, sl.tiles.sstart, sl.tiles.send, c->lazy_hint, work_next, hz, sl.st_scan);
         HIP_TRY(hipGetLastError());
     }
     if (sl.horizon_valid) {
@@ -1780,7 +1738,7 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     }
     if (order_now) {
         if (!fused_order) {
-            hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(TO_THREADS), 0, s, sl.tile_work, g, j.f.tiles_y, sl.sup_work + 256 * sl.sup_par,
+            hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(TO_THREADS), 0, s, sl.tiles.tile_work, g, j.f.tiles_y, sl.sup_work + 256 * sl.sup_par,
                                per_xcd, sl.order);
             HIP_TRY(hipGetLastError());
         }
@@ -1791,8 +1749,8 @@ static int queue_frame_end(gsr_context* c, FrameSlot& sl)
     }
     if (c->opt_row_work && sl.h_rows.dev()) {
         // the tile rows' work, into the slot's mapped words (one launch more; nothing waits for it)
-        hipLaunchKernelGGL(k_row_work, dim3((unsigned)((j.f.tiles_y + RW_THREADS / 64 - 1) / (RW_THREADS / 64))), dim3(RW_THREADS), 0, s, sl.tile_work,
-                           j.phase == 2 ? sl.tile_work_a : (const uint4*)nullptr, g, sl.h_rows.dev(), j.ticket);
+        hipLaunchKernelGGL(k_row_work, dim3((unsigned)((j.f.tiles_y + RW_THREADS / 64 - 1) / (RW_THREADS / 64))), dim3(RW_THREADS), 0, s, sl.tiles.tile_work,
+                           j.phase == 2 ? sl.tiles.tile_work_a : (const uint4*)nullptr, g, sl.h_rows.dev(), j.ticket);
         HIP_TRY(hipGetLastError());
         sl.rows_ticket = j.ticket; sl.rows_tiles_y = j.f.tiles_y;
     }
@@ -1837,7 +1795,7 @@ static int queue_slab_mid(gsr_context* c, FrameSlot& sl)
     GsrHorizonArgs hz = horizon_args(c, sl);
     hz.raw = (c->opt_cull && c->opt_cull != 3) ? sl.hraw : nullptr;          // the finished tiles' horizons for the slot's NEXT frame
     const int nblocks8 = ((j.f.tiles_x + 7) >> 3) * ((j.f.tiles_y + 7) >> 3);
-    hipLaunchKernelGGL(k_slab_mid, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tile_work_a, g, sl.sstart, sl.send, hz, sl.hpyr2,
+    hipLaunchKernelGGL(k_slab_mid, dim3((unsigned)nblocks8), dim3(64), 0, s, sl.tiles.tile_work_a, g, sl.tiles.sstart, sl.tiles.send, hz, sl.hpyr2,
                        sl.slab + GSR_SLAB_BINS, j.f.key_min);
     HIP_TRY(hipGetLastError());
     return GSR_OK;
@@ -1953,7 +1911,7 @@ static int frame_finish(gsr_context* c, FrameSlot& sl)
     GsrOutcomeIn in;
     in.has_splats = j.n > 0; in.phase = j.phase; in.cull = j.cull; in.local_sort = j.local_sort; in.dcull = j.dcull; in.dblind = j.dblind;
     in.speculative = j.speculative; in.deferred = j.deferred; in.blend_guess_plain = j.blend_guess_plain; in.key_min = j.f.key_min;
-    in.pair_cap = sl.pair_cap; in.has_list_buffer = sl.pvA != nullptr; in.max_pairs = (uint64_t)GSR_MAX_PAIRS;
+    in.pair_cap = sl.pvA.cap(); in.has_list_buffer = sl.pvA != nullptr; in.max_pairs = (uint64_t)GSR_MAX_PAIRS;
     in.mb_pairs = mb.pairs; in.mb_hints = mb.hints; in.mb_kept = mb.kept; in.mb_clusters = mb.clusters; in.mb_key_lo = mb.key_lo; in.mb_key_hi = mb.key_hi;
     const GsrFrameOutcome o = gsr_frame_outcome(in, sl.hints);
     const uint32_t D = mb.pairs;
@@ -1993,11 +1951,10 @@ static int frame_finish(gsr_context* c, FrameSlot& sl)
     //  a rank whose rows see nothing, under forced culling or forced front-slab frames, faulted on the null pointer)
     if (o.grow) {
         // (a slot's first buffer may be sized by a frame -- or a front slab -- that shows next to nothing: at least two entries per splat
-        //  then, up to 32 MB, so that the frames behind it need not each regrow it.  The sync: a clamped back end may still read the old one)
+        //  then, up to 32 MB, so that the frames behind it need not each grow it again.  The sync: a clamped back end may still read the old one)
         const size_t floor_ = sl.pvA ? 0 : std::min<size_t>((size_t)2 * j.n + 4096, (size_t)1 << 22);
         const size_t want = std::max<size_t>((size_t)D + D / 4 + 4096, std::max(floor_, c->pair_want));
-        const int rc = regrow(sl.stream, sl.pvA, sl.pair_cap, want + 4, want);   // (+4: the blend kernel scans in 4-entry steps)
-        if (rc) return frame_abort(sl, rc);
+        if (const int rc = sl.pvA.ensure_drained(sl.stream, want, want + 4)) return frame_abort(sl, rc);
         c->pair_want = std::max(c->pair_want, want);   // the other frame slot grows before its next frame
     }
     if (o.end == GSR_FE_SLAB_OVERRUN) {
@@ -2124,7 +2081,7 @@ static int frame_open(gsr_context* c, const FrameArgs& a, FrameSlot*& slot)
         sl.stream = want;
     }
     // (the other slot met a frame that outgrew this slot's list buffer)
-    if (sl.pair_cap > 0 && sl.pair_cap < c->pair_want && (rc = regrow(sl.stream, sl.pvA, sl.pair_cap, c->pair_want + 4, c->pair_want))) return rc;
+    if (sl.pvA.cap() > 0 && (rc = sl.pvA.ensure_drained(sl.stream, c->pair_want, c->pair_want + 4))) return rc;
 
     FrameJob& j = sl.job;
     j = FrameJob();
@@ -2200,16 +2157,9 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     if (!j.direct) HIP_TRY(hipEventRecord(sl.ev_user, c->stream));
 
     // per-tile bookkeeping + super-tile ranges
-    if ((size_t)j.local_tiles + 1 > sl.tile_cap || !sl.sstart) {
-        HIP_TRY(hipStreamSynchronize(s));
-        sl.tile_work.reset(); sl.tile_work_a.reset(); sl.sstart.reset(); sl.send.reset(); sl.redo.reset();
-        sl.tile_cap = 0;
-        if ((rc = sl.tile_work.alloc((size_t)j.local_tiles + 1)) || (rc = sl.tile_work_a.alloc((size_t)j.local_tiles + 1)) || (rc = sl.sstart.alloc((size_t)65536 + 1)) ||
-            (rc = sl.send.alloc((size_t)65536 + 1)) || (rc = sl.redo.alloc((size_t)j.local_tiles + 1))) return rc;
-        sl.tile_cap = (size_t)j.local_tiles + 1;
-    }
+    if ((rc = sl.tiles.ensure_drained(s, (size_t)j.local_tiles + 1))) return rc;
     // (the transmittance a front slab leaves behind, per pixel of the band)
-    if (j.phase == 1 && j.out_px > sl.tbuf_cap && (rc = regrow(s, sl.tbuf, sl.tbuf_cap, j.out_px, j.out_px))) return rc;
+    if (j.phase == 1 && (rc = sl.tbuf.ensure_drained(s, j.out_px))) return rc;
     if (j.use_map && (rc = build_tile_map(c, f))) return rc;
     j.d_depth = a.depth;
     if (a.depth && !a.depth_is_device) {
@@ -2234,8 +2184,9 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     if (j.dcull) {
         frame_depth_codes(c, cam, &j.f);
         const size_t need = (size_t)f.pyr_off[GSR_PYR_LEVELS - 1] + (size_t)gsr_pyr_dim(f.tiles_x, GSR_PYR_LEVELS - 1) * gsr_pyr_dim(f.tiles_y, GSR_PYR_LEVELS - 1) + 16;
-        if (need > sl.dpyr_cap || !sl.dactive) {
-            if ((rc = regrow(s, sl.dpyr, sl.dpyr_cap, 5 * need, need))) return rc;   // (+ the per-tile "covered" array k_blend reads)
+        if (!sl.dactive) sl.dpyr.reset();   // (a slot whose first depth-tested frame failed half-way starts over)
+        if (need > sl.dpyr.cap()) {
+            if ((rc = sl.dpyr.ensure_drained(s, need, 5 * need))) return rc;
             HIP_TRY(hipMemsetAsync(sl.dpyr, 0, 5 * need * sizeof(float), s));   // (levels 4 and 5 start cleared; afterwards every frame clears the next one's)
             if (!sl.dactive) {
                 if ((rc = sl.dactive.alloc(2))) return rc;
@@ -2250,7 +2201,7 @@ static int stage_frame_buffers(gsr_context* c, FrameSlot& sl)
     const size_t bpp = (size_t)gsr_format_pixel_bytes(j.format);
     // (a packed target, front-slab frame: phase 2 continues from phase 1's f32 pixels, kept in a buffer of the slot's own)
     // (... and so does a frame over a background in any format: the target holds composited pixels)
-    if ((j.format != GSR_TARGET_RGBA32F || a.bg.kind != 0) && j.phase == 1 && j.out_px * 4 > sl.fb32_cap && (rc = regrow(s, sl.fb32, sl.fb32_cap, j.out_px * 4, j.out_px * 4))) return rc;
+    if ((j.format != GSR_TARGET_RGBA32F || a.bg.kind != 0) && j.phase == 1 && (rc = sl.fb32.ensure_drained(s, j.out_px * 4))) return rc;
     // Host targets: the band is composited into the slot's staging image -- and plane, with the depth AOV -- and copied back by
     // queue_frame_end.  Padding rows read as zeros (StageBuf): the image is cleared per band shape and format, the plane per band shape.
     int band[6];
@@ -2309,13 +2260,13 @@ static int queue_cull(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     // Whatever the guess, the pixels are the same: the tests are conservative and k_blend compares every fragment.
     GsrDepthPyrArgs& dp = fe.dp;
     if (j.dcull) {
-        float* const dp0 = sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr_cap;
-        float* const dq0 = sl.dpyr + (size_t)(2 * (j.dpar ^ 1)) * sl.dpyr_cap;
-        fe.dc_k1 = GsrDepthCull{dp0, j.phase == 2 ? (const float*)nullptr : dp0 + sl.dpyr_cap, sl.dactive + j.dpar};
+        float* const dp0 = sl.dpyr + (size_t)(2 * j.dpar) * sl.dpyr.cap();
+        float* const dq0 = sl.dpyr + (size_t)(2 * (j.dpar ^ 1)) * sl.dpyr.cap();
+        fe.dc_k1 = GsrDepthCull{dp0, j.phase == 2 ? (const float*)nullptr : dp0 + sl.dpyr.cap(), sl.dactive + j.dpar};
         if (j.phase == 2 && !sl.dpyr_built) { fe.dc_k1 = GsrDepthCull{nullptr, nullptr, nullptr}; j.dblind = true; }   // (phase 1 built none)
         if (j.phase != 2) {
-            dp.depth = j.d_depth; dp.pyr = dp0; dp.pyrc = dp0 + sl.dpyr_cap; dp.pyr_next = dq0; dp.pyrc_next = dq0 + sl.dpyr_cap; dp.active = sl.dactive; dp.par = j.dpar;
-            dp.tcov = sl.dpyr + 4 * sl.dpyr_cap;
+            dp.depth = j.d_depth; dp.pyr = dp0; dp.pyrc = dp0 + sl.dpyr.cap(); dp.pyr_next = dq0; dp.pyrc_next = dq0 + sl.dpyr.cap(); dp.active = sl.dactive; dp.par = j.dpar;
+            dp.tcov = sl.dpyr + 4 * sl.dpyr.cap();
             // (a culled frame: the tiles that were classic when the horizons were left get no depth clause)
             dp.stat = (j.cull && sl.hstat_valid) ? sl.hstat : (const float*)nullptr;
             j.dstat = dp.stat != nullptr;
@@ -2471,7 +2422,7 @@ static int queue_sort(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     if (p.ordered) {
         // K1 walked the splats nearest first: the heads of its 256-slot blocks, one after the other, ARE the sorted frame
         const uint32_t m_max = p.n_slots / RS_SRC_BLOCK;
-        if ((rc = ensure_u32(c->blk_pre, c->blk_pre_cap, (size_t)m_max + 8))) return rc;
+        if ((rc = ensure_counts(c->blk_pre, (size_t)m_max + 8))) return rc;
         if ((rc = launch_ordered_compact(s, sl.keyB, sl.valB, sl.blk_cnt, sl.d_counts, m_max, c->blk_pre, sl.keyA, sl.valA, sl.d_n))) return rc;
         c->st.sorts_skipped += 1;
         sl.key_min = j.f.key_min;
@@ -2509,7 +2460,7 @@ static int queue_binning(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
     if (j.n > 0) {
         const uint32_t bn_tile = (uint32_t)BN_THREADS * (uint32_t)j.bn_items;
         const uint32_t nblk = fe.p.bn_blocks;
-        if ((rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)BN_BINS * nblk + 8))) return rc;
+        if ((rc = ensure_counts(sl.hist, (size_t)BN_BINS * nblk + 8))) return rc;
         const GsrShard shd = gsr_frame_shard(f, f.rect_shift);
         // (+ the extra work items of the blocks that are split by rows of super-tiles: k_binning.h, BN_SPLIT_TILES)
         const uint32_t bn_extra = (uint32_t)BN_SPLIT_TILES * (uint32_t)std::max(f.stiles_y - 1, 0);
@@ -2520,14 +2471,14 @@ static int queue_binning(gsr_context* c, FrameSlot& sl, FrontEnd& fe)
         hipLaunchKernelGGL(k_scan_rows, dim3(BN_BINS), dim3(SC_THREADS), 0, s, sl.hist, nblk, sl.totals, sl.d_n, j.n, bn_tile);
         // the list ranges and the pair count: formed by k_bin_place itself (queue_back_end) when the back end is queued
         // speculatively; a frame without a list buffer needs the count first
-        if (!(sl.pair_cap > 0)) hipLaunchKernelGGL(k_bin_ranges, dim3(1), dim3(BN_BINS), 0, s, range_args(c, sl));
+        if (!(sl.pvA.cap() > 0)) hipLaunchKernelGGL(k_bin_ranges, dim3(1), dim3(BN_BINS), 0, s, range_args(c, sl));
         e = hipGetLastError();
     } else {
-        e = hipMemsetAsync(sl.sstart, 0, ((size_t)j.n_super + 1) * 4, s);
-        if (e == hipSuccess) e = hipMemsetAsync(sl.send, 0, ((size_t)j.n_super + 1) * 4, s);
+        e = hipMemsetAsync(sl.tiles.sstart, 0, ((size_t)j.n_super + 1) * 4, s);
+        if (e == hipSuccess) e = hipMemsetAsync(sl.tiles.send, 0, ((size_t)j.n_super + 1) * 4, s);
     }
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render: binning: %s", hipGetErrorString(e));
-    j.speculative = j.n > 0 && sl.pair_cap > 0;
+    j.speculative = j.n > 0 && sl.pvA.cap() > 0;
     j.ranges_folded = j.speculative;
     if (j.speculative || j.n == 0) {
         if ((rc = queue_back_end(c, sl))) return rc;
@@ -2599,7 +2550,7 @@ static int frame_check(gsr_context* c, FrameSlot& first, const FrameArgs& a)
 {
     // A frame that is rendered again is checked again: the repair of a culled frame may itself meet a bucket its small-frame sort
     // gives up, or -- as a front-slab frame -- a list buffer its second phase overruns.  Every reason removes itself (the re-sort
-    // takes the global passes, the redo finds the buffer regrown, the repair does not cull), so a handful of rounds is the most a
+    // takes the global passes, the redo finds the buffer grown, the repair does not cull), so a handful of rounds is the most a
     // frame can need; found by tools/fuzz_parity.py: the second re-render used to be handed over unchecked.
     FrameSlot* cur = &first;
     for (int round = 0; round < 8; ++round) {
@@ -2839,30 +2790,22 @@ static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, i
     build_frame(c, cam, &f);
     const size_t npix = (size_t)cam->width * cam->height;
     // the z-buffer (and the staging image for a host target) are kept between calls: an overlay redraw allocates nothing
-    if (npix > c->wire_cap) {   // (the staging image holds 16 bytes per pixel: enough for every target format)
-        c->wire_zbuf.reset(); c->wire_out.reset();
-        c->wire_cap = 0;
-        if ((rc = c->wire_zbuf.alloc(npix)) || (rc = c->wire_out.alloc(npix * 4))) {
-            c->wire_zbuf.reset();
-            return rc;
-        }
-        c->wire_cap = npix;
-    }
+    if ((rc = c->wire.ensure(npix))) return rc;
     // outlines at the same depth are drawn in UPLOAD order (k_wire.h): with spatially ordered storage the resolve pass goes back
     // from the winner's upload index to its slot through the inverse of the storage permutation, built once per geometry (gsr_update shares it)
     if ((rc = ensure_inverse_perm(c))) return rc;
     const uint32_t* const inv = (c->perm && c->n > 0) ? c->wire_inv : (const uint32_t*)nullptr;
-    unsigned long long* zbuf = c->wire_zbuf;
-    float* target = out_is_device ? rgba_out : c->wire_out;
+    unsigned long long* zbuf = c->wire.zbuf;
+    float* target = out_is_device ? rgba_out : c->wire.out;
     hipError_t e = hipMemsetAsync(zbuf, 0xff, npix * 8, s);
-    if (e == hipSuccess && over && !out_is_device) e = hipMemcpyAsync(c->wire_out, rgba_out, npix * bpp, hipMemcpyHostToDevice, s);   // (the frame underneath)
+    if (e == hipSuccess && over && !out_is_device) e = hipMemcpyAsync(c->wire.out, rgba_out, npix * bpp, hipMemcpyHostToDevice, s);   // (the frame underneath)
     if (e == hipSuccess && c->n > 0)
         hipLaunchKernelGGL(k_wire_splats, dim3(div_up(c->n, 256)), dim3(256), 0, s, c->n, f, c->geoA, c->geoB, zbuf, inv ? c->perm : (const uint32_t*)nullptr);
     if (e == hipSuccess)
         hipLaunchKernelGGL(k_wire_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, zbuf, npix, c->col,
                            target, c->target_format, inv, over);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess && !out_is_device) e = hipMemcpyAsync(rgba_out, c->wire_out, npix * bpp, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !out_is_device) e = hipMemcpyAsync(rgba_out, c->wire.out, npix * bpp, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render_wire: %s", hipGetErrorString(e));
     return GSR_OK;
@@ -3046,343 +2989,8 @@ extern "C" int gsr_stats_reset(gsr_context* c)
 }
 
 // ---------------------------------------------------------------------------
-// debug / test access: intermediates of the most recent frame
-// number of entries of the depth-sorted list of the last frame (= visible splats of that frame)
-static uint32_t sorted_count(FrameSlot* sl)
-{
-    (void)hipMemcpy(sl->h_counters, sl->d_frame, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    return (uint32_t)(sl->h_counters[6] & 0xffffffffull);
-}
-
-// storage slot -> upload index, on the host (debug read-backs speak upload indices); empty = identity
-static int host_perm(gsr_context* c)
-{
-    if (!c->perm || c->h_perm.size() == c->n) return GSR_OK;
-    c->h_perm.resize(c->n);
-    if (c->n) HIP_TRY(hipMemcpy(c->h_perm.data(), c->perm, (size_t)c->n * 4, hipMemcpyDeviceToHost));
-    return GSR_OK;
-}
-static inline uint32_t to_upload_index(const gsr_context* c, uint32_t slot) { return c->perm && slot < c->h_perm.size() ? (uint32_t)c->h_perm[slot] : slot; }
-
-extern "C" int gsr_debug_read_storage_order(gsr_context* c, int32_t* perm, int64_t n)
-{
-    if (!c || !perm || n < 0 || (uint64_t)n != c->n) return set_err(GSR_E_INVALID, "gsr_debug_read_storage_order: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    if ((rc = host_perm(c))) return rc;
-    for (int64_t j = 0; j < n; ++j) perm[j] = (int32_t)to_upload_index(c, (uint32_t)j);
-    return GSR_OK;
-}
-
-extern "C" int gsr_debug_read_records(gsr_context* c, gsr_debug_record* out, int64_t n)
-{
-    if (!c || !out || n < 0 || (uint64_t)n > c->n) return set_err(GSR_E_INVALID, "gsr_debug_read_records: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int src = sync_all(c);
-    if (src) return src;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_read_records: no frame rendered yet");
-    if (sl->last_lazy && sl->last_supers > 0 && c->n > 0) {
-        // lazy colour leaves most records pending: evaluate every list completely before reading them back
-        hipLaunchKernelGGL(k_colour_prefix, dim3((unsigned)(sl->last_supers * CL_BLOCKS_PER_LIST)), dim3(CL_THREADS), 0, sl->stream,
-                           sl->job.f, sl->pvA, sl->sstart, sl->send, c->prefix_all, (int)std::min<size_t>(sl->pair_cap, (size_t)0x7fffffff),
-                           c->colrow, sl->rec, sl->colour_evals);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(sl->stream));
-    }
-    if ((src = host_perm(c))) return src;
-    const uint32_t ns = sorted_count(sl);
-    const int64_t n_out = n;
-    n = (int64_t)c->n;   // (records live at storage slots: read them all, hand back the caller's first n_out upload indices)
-    GsrRecord* hr = new (std::nothrow) GsrRecord[n ? n : 1];
-    uint32_t* hk = new (std::nothrow) uint32_t[ns ? ns : 1];
-    uint2* hv = new (std::nothrow) uint2[ns ? ns : 1];
-    int rc = GSR_OK;
-    if (!hr || !hk || !hv) rc = set_err(GSR_E_OOM, "gsr_debug_read_records: host allocation failed");
-    hipError_t e = hipSuccess;
-    if (!rc && n) {
-        e = hipMemcpy(hr, sl->rec, (size_t)n * sizeof(GsrRecord), hipMemcpyDeviceToHost);
-        // keys and rects live in depth order and only for the visible splats: un-permute through the payload
-        if (e == hipSuccess && ns) e = hipMemcpy(hk, sl->keyA, (size_t)ns * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && ns) e = hipMemcpy(hv, sl->valA, (size_t)ns * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = set_err(GSR_E_HIP, "gsr_debug_read_records: %s", hipGetErrorString(e));
-    }
-    if (!rc) {
-        for (int64_t i = 0; i < n_out; ++i) std::memset(&out[i], 0, sizeof(out[i]));
-        for (uint32_t r = 0; r < ns; ++r) {
-            const uint32_t slot = hv[r].x;
-            if ((int64_t)slot >= n) continue;
-            const uint32_t i = to_upload_index(c, slot);
-            if ((int64_t)i >= n_out) continue;
-            gsr_debug_record& o = out[i];
-            const GsrRecord& q = hr[slot];
-            o.visible = 1;
-            o.cx = q.cx; o.cy = q.cy; o.a1x = q.a1x; o.a1y = q.a1y; o.b1x = q.b1x; o.b1y = q.b1y;
-            o.hx = q.hx; o.hy = q.hy; o.r = q.r; o.g = q.g; o.b = q.b; o.la = q.la;
-            const uint32_t kb = hk[r] + sl->key_min;   // keys are stored relative to the frame's key_min
-            std::memcpy(&o.key, &kb, 4);
-        }
-    }
-    delete[] hr; delete[] hk; delete[] hv;
-    return rc;
-}
-
-extern "C" int gsr_debug_read_cull(gsr_context* c, uint32_t* rect, int64_t n, uint32_t* clusters, int64_t cap, int64_t* n_clusters)
-{
-    if (!c || !rect || n < 0 || (uint64_t)n > c->n || cap < 0 || (cap > 0 && !clusters) || !n_clusters) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: no frame rendered yet");
-    if (!sl->last_cc_groups) return set_err(GSR_E_INVALID, "gsr_debug_read_cull: the last frame ran no cluster pass over clusters");
-    if ((rc = host_perm(c))) return rc;
-    // rects live in depth order beside the storage slots of the splats that stayed (gsr_debug_read_records)
-    const uint32_t ns = sorted_count(sl);
-    std::vector<uint2> hv(ns ? ns : 1);
-    if (ns) HIP_TRY(hipMemcpy(hv.data(), sl->valA, (size_t)ns * 8, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < n; ++i) rect[i] = 0xffffffffu;
-    for (uint32_t r = 0; r < ns; ++r) {
-        const uint32_t slot = hv[r].x;
-        if ((uint64_t)slot >= c->n) continue;
-        const uint32_t i = to_upload_index(c, slot);
-        if ((int64_t)i < n) rect[i] = hv[r].y;
-    }
-    // the survivors: workgroup g left cnt[g] of them, in cluster order, at seg[g * per ...]
-    const uint32_t ng = sl->last_cc_groups, per = sl->last_cc_per;
-    std::vector<uint32_t> cnt(ng), seg((size_t)ng * per);
-    HIP_TRY(hipMemcpy(cnt.data(), sl->ccnt, (size_t)ng * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(seg.data(), sl->cseg, (size_t)ng * per * 4, hipMemcpyDeviceToHost));
-    int64_t m = 0;
-    for (uint32_t g = 0; g < ng; ++g)
-        for (uint32_t k = 0; k < cnt[g] && k < per; ++k, ++m)
-            if (m < cap) clusters[m] = seg[(size_t)g * per + k];
-    *n_clusters = m;
-    return GSR_OK;
-}
-
-extern "C" int gsr_debug_read_depth_order(gsr_context* c, int32_t* perm, int64_t cap, int64_t* n_sorted)
-{
-    if (!c || !perm || !n_sorted || cap < 0) return set_err(GSR_E_INVALID, "gsr_debug_read_depth_order: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_read_depth_order: no frame rendered yet");
-    const uint32_t ns = sorted_count(sl);
-    *n_sorted = ns;
-    const int64_t m = (int64_t)ns < cap ? (int64_t)ns : cap;
-    if (m) HIP_TRY(hipMemcpy2D(perm, 4, sl->valA, 8, 4, (size_t)m, hipMemcpyDeviceToHost));
-    if ((rc = host_perm(c))) return rc;
-    for (int64_t r = 0; r < m; ++r) perm[r] = (int32_t)to_upload_index(c, (uint32_t)perm[r]);
-    return GSR_OK;
-}
-
-extern "C" int gsr_debug_read_tile_lists(gsr_context* c, int32_t* list_start, int32_t* list_end, int64_t n_lists,
-                                         int32_t* pair_splat, int64_t n_pairs)
-{
-    if (!c || !list_start || !list_end) return set_err(GSR_E_INVALID, "gsr_debug_read_tile_lists: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_read_tile_lists: no frame rendered yet");
-    if (n_lists != (int64_t)sl->last_supers || n_pairs != (int64_t)sl->last_pairs || (n_pairs > 0 && !pair_splat))
-        return set_err(GSR_E_INVALID, "gsr_debug_read_tile_lists: expected %d lists / %u pairs", sl->last_supers, sl->last_pairs);
-    if (n_lists) {
-        HIP_TRY(hipMemcpy(list_start, sl->sstart, (size_t)n_lists * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(list_end, sl->send, (size_t)n_lists * 4, hipMemcpyDeviceToHost));
-    }
-    if (n_pairs) HIP_TRY(hipMemcpy2D(pair_splat, 4, sl->pvA, 8, 4, (size_t)n_pairs, hipMemcpyDeviceToHost));
-    if ((rc = host_perm(c))) return rc;
-    for (int64_t r = 0; r < n_pairs; ++r) pair_splat[r] = (int32_t)to_upload_index(c, (uint32_t)pair_splat[r] & sl->job.f.idx_mask);   // (depth bits off: gsr_device.h)
-    return GSR_OK;
-}
-
-extern "C" int gsr_debug_read_tile_work(gsr_context* c, uint32_t* work4, int64_t n_tiles)
-{
-    if (!c || !work4) return set_err(GSR_E_INVALID, "gsr_debug_read_tile_work: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl || n_tiles != (int64_t)sl->last_tiles_x * sl->last_local_ty)
-        return set_err(GSR_E_INVALID, "gsr_debug_read_tile_work: expected %d tiles", sl ? sl->last_tiles_x * sl->last_local_ty : 0);
-    if (n_tiles) HIP_TRY(hipMemcpy(work4, sl->tile_work, (size_t)n_tiles * 16, hipMemcpyDeviceToHost));
-    return GSR_OK;
-}
-
-// what the slot's NEXT frame would be culled against, per tile of the whole image: [0] the (dilated) depth horizons (distance^2, +inf = none),
-// [1] the raw horizons before dilation with the tile's status in the sign (k_blend.h: GsrHorizonArgs.stat), [2] the dilated status, [3] the
-// covered depths of the last depth-tested frame as K1 saw them (level 0 of pyrc, k_cluster.h)
-extern "C" int gsr_debug_read_horizons(gsr_context* c, float* out4, int64_t n_tiles)
-{
-    if (!c || !out4) return set_err(GSR_E_INVALID, "gsr_debug_read_horizons: bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl || n_tiles <= 0) return set_err(GSR_E_INVALID, "gsr_debug_read_horizons: no frame");
-    std::vector<float> zero((size_t)n_tiles, 0.0f);
-    HIP_TRY(hipMemcpy(out4, sl->hpyr, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));                     // (level 0 starts at offset 0)
-    HIP_TRY(hipMemcpy(out4 + n_tiles, sl->hraw, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out4 + 2 * n_tiles, sl->hstat, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));
-    if (sl->dpyr && sl->dpyr_cap >= (size_t)n_tiles) HIP_TRY(hipMemcpy(out4 + 3 * n_tiles, sl->dpyr + (size_t)(2 * sl->dpar + 1) * sl->dpyr_cap, (size_t)n_tiles * 4, hipMemcpyDeviceToHost));
-    else std::memcpy(out4 + 3 * n_tiles, zero.data(), (size_t)n_tiles * 4);
-    return GSR_OK;
-}
-
-static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int64_t n64, int key_bits, bool local);
-extern "C" int gsr_debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int64_t n64, int key_bits)
-{
-    return debug_sort_pairs(c, keys, vals, n64, key_bits, false);
-}
-static thread_local uint32_t dbg_lo = 0;
-static thread_local int dbg_shift = 0;
-extern "C" int gsr_debug_sort_pairs_local(gsr_context* c, uint32_t* keys, uint32_t* vals, int64_t n64, int key_bits, uint32_t bucket_lo, int bucket_shift)
-{
-    if (bucket_shift < 0 || bucket_shift > 31) return set_err(GSR_E_INVALID, "gsr_debug_sort_pairs_local: bad bucket shift");
-    dbg_lo = bucket_lo; dbg_shift = bucket_shift;
-    return debug_sort_pairs(c, keys, vals, n64, key_bits, true);
-}
-static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int64_t n64, int key_bits, bool local)
-{
-    if (!c || n64 < 0 || n64 > 0x7fffffffll || key_bits < 1 || key_bits > 32 || (n64 > 0 && (!keys || !vals)))
-        return set_err(GSR_E_INVALID, "gsr_debug_sort_pairs: bad argument");
-    if (n64 == 0) return GSR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot& sl = c->slot[0];
-    const uint32_t n = (uint32_t)n64;
-    DevMem<uint32_t> scratch[4];           // the pairs (kA, vA) and (kB, vB) of the sort, gone with the call
-    for (DevMem<uint32_t>& m : scratch)
-        if ((rc = m.alloc(n))) return rc;
-    uint32_t *kA = scratch[0], *vA = scratch[1], *kB = scratch[2], *vB = scratch[3];
-    hipError_t e = hipMemcpyAsync(kA, keys, (size_t)n * 4, hipMemcpyHostToDevice, sl.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(vA, vals, (size_t)n * 4, hipMemcpyHostToDevice, sl.stream);
-    if (e == hipSuccess) {
-        if (local) {   // one scatter into BK_BUCKETS buckets of width 2^shift from lo, then every bucket on its own (k_radix_local)
-            // (uint32 payloads in the slot's bucket regions: the payload region is large enough for either type)
-            const uint32_t nblk = div_up(n, RS_TILE);
-            hipError_t e2 = hipMemsetAsync(sl.bkt_cnt, 0, (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t), sl.stream);
-            if (e2 == hipSuccess) e2 = hipMemsetAsync(sl.d_counts + 2, 0, 4, sl.stream);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bucket_scatter<uint32_t, false>), dim3(nblk), dim3(RS_THREADS), 0, sl.stream, kA, vA, n, (const uint32_t*)nullptr,
-                               dbg_shift, dbg_lo, (const uint32_t*)nullptr, sl.bkt_cnt, sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val.get()), (uint32_t*)nullptr, sl.d_counts + 2);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_radix_local<uint32_t>), dim3(BK_BUCKETS), dim3(RL_THREADS), 0, sl.stream, sl.bkt_cnt, dbg_shift, key_bits, dbg_lo,
-                               sl.bkt_key, reinterpret_cast<uint32_t*>(sl.bkt_val.get()), kA, vA, (uint32_t*)nullptr, (uint32_t*)nullptr);
-            uint32_t over = 0;
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(&over, sl.d_counts + 2, 4, hipMemcpyDeviceToHost, sl.stream);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(sl.stream);
-            if (e2 != hipSuccess) rc = set_err(GSR_E_HIP, "gsr_debug_sort_pairs_local: %s", hipGetErrorString(e2));
-            else if (over) rc = set_err(GSR_E_INVALID, "gsr_debug_sort_pairs_local: a bucket overflowed its region of %d keys (the pipeline would fall back to the global sort)", BK_CAP);
-        } else {
-            rc = radix_sort(sl, kA, vA, kB, vB, n, key_bits, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0);
-        }
-        if (!rc) {
-            e = hipMemcpyAsync(keys, kA, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(vals, vA, (size_t)n * 4, hipMemcpyDeviceToHost, sl.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(sl.stream);
-        }
-    }
-    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_debug_sort_pairs: %s", hipGetErrorString(e));
-    return rc;
-}
-
-// The depth sort of a FRAME on a test's arrays: K1's block-compacted layout in, what the frame's own drivers (radix_sort<uint2> with a
-// compacting first pass, launch_local_sort, launch_ordered_compact) make of it out.  Every array is a DevMem of this call; the bucket
-// regions are the slot's (as in gsr_debug_sort_pairs_local), and the slot's histogram is set aside for the call and put back.
-extern "C" int gsr_debug_sort_frame(gsr_context* c, int mode, uint32_t* keys, uint32_t* vals2, const uint32_t* blk_cnt, int64_t n_slots64,
-                                    int64_t n_slots_dev64, int key_bits, int allow9, uint32_t lo, int shift, int range_dev, int k1_grid,
-                                    int64_t* n_kept, uint32_t* failed)
-{
-    const bool local = mode == GSR_SORT_LOCAL_GATHER || mode == GSR_SORT_LOCAL_K1 || mode == GSR_SORT_LOCAL_DIRECT;
-    if (!c || !keys || !vals2 || !blk_cnt || !n_kept || !failed || mode < GSR_SORT_GLOBAL || mode > GSR_SORT_ORDERED)
-        return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: bad argument");
-    if (n_slots64 <= 0 || n_slots64 > 0x7fffff00ll || n_slots64 % RS_SRC_BLOCK || n_slots_dev64 < 0 || n_slots_dev64 > n_slots64 || n_slots_dev64 % RS_SRC_BLOCK)
-        return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: slot counts are multiples of %d, 0 < n_slots, 0 <= n_slots_dev <= n_slots", RS_SRC_BLOCK);
-    if (key_bits < 1 || key_bits > 32 || shift < 0 || shift > 31) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: bad key bits or bucket shift");
-    if (range_dev && mode != GSR_SORT_LOCAL_K1) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: only LOCAL_K1 reads its range from the device");
-    if (mode == GSR_SORT_LOCAL_K1 && k1_grid < 1) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: LOCAL_K1 needs a grid of at least one workgroup");
-    const uint32_t n_slots = (uint32_t)n_slots64, n_blocks = n_slots / RS_SRC_BLOCK;
-    for (uint32_t b = 0; b < n_blocks; ++b)
-        if (blk_cnt[b] > (uint32_t)RS_SRC_BLOCK) return set_err(GSR_E_INVALID, "gsr_debug_sort_frame: block %u counts %u items of %d slots", b, blk_cnt[b], RS_SRC_BLOCK);
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = sync_all(c);
-    if (rc) return rc;
-    FrameSlot& sl = c->slot[0];
-    hipStream_t s = sl.stream;
-    DevMem<uint32_t> kbuf[2], cnt, ctl, pre;   // ctl: [0] slots filled, [1] items kept, [2] the sort gave up, [4..5] { lo, shift }
-    DevMem<uint2> vbuf[2];
-    if ((rc = kbuf[0].alloc(n_slots)) || (rc = kbuf[1].alloc(n_slots)) || (rc = vbuf[0].alloc(n_slots)) || (rc = vbuf[1].alloc(n_slots)) ||
-        (rc = cnt.alloc(n_blocks)) || (rc = ctl.alloc(8)) || (rc = pre.alloc((size_t)n_blocks + 8)))
-        return rc;
-    const uint32_t h_ctl[8] = {(uint32_t)n_slots_dev64, 0u, 0u, 0u, lo, (uint32_t)shift, 0u, 0u};
-    HIP_TRY(hipMemcpyAsync(kbuf[0], keys, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(vbuf[0], vals2, (size_t)n_slots * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(cnt, blk_cnt, (size_t)n_blocks * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ctl, h_ctl, sizeof h_ctl, hipMemcpyHostToDevice, s));
-    uint32_t *kA = kbuf[0], *kB = kbuf[1];
-    uint2 *vA = vbuf[0], *vB = vbuf[1];
-    if (local) {
-        HIP_TRY(hipMemsetAsync(sl.bkt_cnt, 0, (size_t)BK_BUCKETS * BK_STRIDE * sizeof(uint32_t), s));
-        LocalSortOps o{};
-        o.keys = kA; o.vals = vA; o.cnt = cnt; o.slots_dev = ctl; o.n_slots = n_slots;
-        o.scatter = mode == GSR_SORT_LOCAL_DIRECT ? LS_DIRECT : (mode == GSR_SORT_LOCAL_K1 ? LS_PER_WAVE : LS_GATHER);
-        o.wave_grid = std::min(div_up(n_blocks, 4u), (uint32_t)std::max(k1_grid, 1));
-        o.range = range_dev ? ctl + 4 : (const uint32_t*)nullptr;
-        o.lo = range_dev ? 0u : lo;       // (as a front-slab phase passes them: the kernels must take the device's)
-        o.shift = range_dev ? 0 : shift;
-        o.key_bits = key_bits;
-        o.bkt_cnt = sl.bkt_cnt; o.bkt_key = sl.bkt_key; o.bkt_val = sl.bkt_val;
-        o.failed = ctl + 2; o.n_out = ctl + 1;
-        rc = launch_local_sort(s, o);
-    } else if (mode == GSR_SORT_ORDERED) {
-        rc = launch_ordered_compact(s, kA, vA, cnt, ctl, n_blocks, pre, kB, vB, ctl + 1);
-        std::swap(kA, kB); std::swap(vA, vB);
-    } else {
-        DevMem<uint32_t> hist;             // (the slot's own histogram comes back as it was)
-        size_t hist_cap = 0;
-        sl.hist.swap(hist); std::swap(sl.hist_cap, hist_cap);
-        rc = radix_sort(sl, kA, vA, kB, vB, n_slots, key_bits, allow9 != 0, ctl + 1, RS_XCD_DEPTH != 0, cnt, ctl, mode == GSR_SORT_GLOBAL_MID);
-        const hipError_t e = hipStreamSynchronize(s);   // (before the call's histogram goes)
-        sl.hist.swap(hist); std::swap(sl.hist_cap, hist_cap);
-        if (!rc && e != hipSuccess) rc = set_err(GSR_E_HIP, "gsr_debug_sort_frame: %s", hipGetErrorString(e));
-    }
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    uint32_t out_ctl[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(out_ctl, ctl, sizeof out_ctl, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (out_ctl[1] > n_slots) return set_err(GSR_E_HIP, "gsr_debug_sort_frame: the device counted %u items in %u slots", out_ctl[1], n_slots);
-    *n_kept = out_ctl[1];
-    *failed = out_ctl[2];
-    if (out_ctl[1]) {
-        HIP_TRY(hipMemcpy(keys, kA, (size_t)out_ctl[1] * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(vals2, vA, (size_t)out_ctl[1] * 8, hipMemcpyDeviceToHost));
-    }
-    return GSR_OK;
-}
-
-// the plan of the attempt queued last (GSR_PLAN_OUT_FIELDS of csrc/gsr_frame_plan.h, in their order, one int32 each)
-extern "C" int gsr_debug_last_plan(gsr_context* c, int32_t* out32)
-{
-    if (!c || !out32) return set_err(GSR_E_INVALID, "gsr_debug_last_plan: NULL argument");
-    HIP_TRY(hipSetDevice(c->device));
-    const int rc = sync_all(c);        // (a deferred frame that is rendered again is planned again)
-    if (rc) return rc;
-    FrameSlot* sl = latest_slot(c);
-    if (!sl) return set_err(GSR_E_INVALID, "gsr_debug_last_plan: no frame rendered yet");
-    const GsrFramePlan& r = sl->last_plan;
-    int o = 0;
-#define GSR_PUT(t, name) out32[o++] = (int32_t)r.name;
-    GSR_PLAN_OUT_FIELDS(GSR_PUT)
-#undef GSR_PUT
-#define GSR_COUNT(t, name) + 1
-    static_assert(0 GSR_PLAN_OUT_FIELDS(GSR_COUNT) <= 32, "gsr_debug_last_plan writes at most 32 words");
-#undef GSR_COUNT
-    return GSR_OK;
-}
+// debug / test access: intermediates of the most recent frame, the pipeline's sorts on a test's arrays (HERE: it places two kernel templates)
+#include "gsr_debug_read.h"
 
 // ---------------------------------------------------------------------------
 // Edits of the resident cloud without a re-upload: update, move, the device sources, visibility, remove, add.

@@ -213,7 +213,7 @@ enum GsrBackEndStep : int {
 #define GSR_OUTCOME_OUT_FIELDS(X)                                                                                                  \
     X(int, end)               /* GsrFrameEnd */                                                                                 \
     X(int, back_end)          /* GsrBackEndStep */                                                                              \
-    X(bool, grow)             /* the list buffer is regrown (before anything is queued again) */                                \
+    X(bool, grow)             /* the list buffer is grown   (before anything is queued again) */                                \
     X(bool, guard_miss)       /* the guarded plain blend kernel found covered pixels: the depth-tested one draws the frame */   \
     X(int, local_result)      /* GsrLocalSortPolicy::on_sort_result: -1 none, 0 held, 1 gave a bucket up */                     \
     X(int, depth_active)      /* the context's depth_active: -1 unchanged, else the new value */                                \

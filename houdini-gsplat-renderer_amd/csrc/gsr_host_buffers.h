@@ -1,14 +1,17 @@
-// gsr_host_buffers.h -- host side of gsr_api.hip's buffer handling: the thread's last error, HIP_TRY, the four handles that own what
-// the host code allocates, buffers that grow (replace, regrow) and the staging buffer a frame slot keeps for a caller's host memory
-// (StageBuf).  No kernels; included by gsr_api.hip alone.
+// gsr_host_buffers.h -- host side of gsr_api.hip's buffer handling: the thread's last error, HIP_TRY, the handles that own what the host
+// code allocates, and what is built of them: groups of buffers that share a capacity (DevGroup: TileSet, WirePair, MortonScratch) and the
+// staging buffer a frame slot keeps for a caller's host memory (StageBuf).  No kernels; included by gsr_api.hip alone.
 //
 //   DevMem<T>      device memory (hipMalloc): alloc / alloc_zeroed, converts to T*
 //   PinnedMem<T>   pinned host memory (hipHostMalloc); where mapped, dev() is the address the kernels write it at
 //   Event, Stream  hipEventCreateWithFlags / hipStreamCreateWithFlags; convert to the HIP handle
+//   DevVec<T>      a DevMem and its capacity in elements, kept in step by construction: ensure / ensure_drained grow it, converts to T*
 //
-// The rule: a member that owns is a handle; a raw pointer never owns.  A handle releases in its destructor (on whatever device is
-// current: gsr_destroy sets it once, in front of `delete c`), moves by std::move or swap, and is never copied or made from a raw pointer
-// (DevMem::adopt takes one over, explicitly).  g_live counts the live objects of each kind (gsr_debug_live_handles).
+// The rule: a member that owns is a handle; a raw pointer never owns; a capacity lives inside the handle it speaks of.  A handle
+// releases in its destructor (on whatever device is current: gsr_destroy sets it once, in front of `delete c`), moves by std::move or
+// swap, and is never copied or made from a raw pointer (DevMem::adopt takes one over, explicitly).  g_live counts the live objects of
+// each kind (gsr_debug_live_handles).  How much beyond its need a buffer allocates is written once per rule: at its one site, or in
+// the helper its users share (ensure_counts, ensure_stage, MortonScratch::hold).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -134,22 +137,95 @@ struct Stream : Owned<hipStream_t, GSR_LIVE_STREAM> {
     }
 };
 
-// p is to hold `count` elements in place of what it held (cap = the new capacity; 0 and an empty handle after a failure)
+// A device buffer that grows: a DevMem and the capacity it answers for, in elements -- zero exactly when the handle is empty.
+//   ensure(count, alloc_count)   count <= cap(): nothing, not a HIP call.  Otherwise what it held is released, THEN alloc_count elements
+//                                (count, unless the site allocates slack that is no capacity) are allocated and cap() is count; a
+//                                failure leaves it empty, cap() 0, and returns DevMem::alloc's code
+//   ensure_drained(s, ...)       the same for a buffer that work queued on `s` may still read: drained first, only when it has to go
 template <typename T>
-static int replace(DevMem<T>& p, size_t& cap, size_t count, size_t new_cap)
-{
-    cap = 0;
-    const int rc = p.alloc(count);
-    if (!rc) cap = new_cap;
-    return rc;
-}
-// a slot buffer too small for this frame: drain what may still read the old one, then replace it
-template <typename T>
-static int regrow(hipStream_t s, DevMem<T>& p, size_t& cap, size_t count, size_t new_cap)
-{
-    HIP_TRY(hipStreamSynchronize(s));
-    return replace(p, cap, count, new_cap);
-}
+class DevVec {
+    DevMem<T> p_;
+    size_t cap_ = 0;
+
+public:
+    DevVec() = default;
+    DevVec(DevVec&& o) noexcept : p_(std::move(o.p_)), cap_(o.cap_) { o.cap_ = 0; }
+    DevVec& operator=(DevVec&& o) noexcept { if (this != &o) { p_ = std::move(o.p_); cap_ = o.cap_; o.cap_ = 0; } return *this; }
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t cap() const { return cap_; }
+    void reset() { p_.reset(); cap_ = 0; }
+    void swap(DevVec& o) noexcept { p_.swap(o.p_); std::swap(cap_, o.cap_); }
+    int ensure(size_t count, size_t alloc_count)
+    {
+        if (count <= cap_) return GSR_OK;
+        const int rc = p_.alloc(alloc_count);
+        cap_ = rc ? 0 : count;
+        return rc;
+    }
+    int ensure(size_t count) { return ensure(count, count); }
+    int ensure_drained(hipStream_t s, size_t count, size_t alloc_count)
+    {
+        if (count <= cap_) return GSR_OK;
+        HIP_TRY(hipStreamSynchronize(s));
+        return ensure(count, alloc_count);
+    }
+    int ensure_drained(hipStream_t s, size_t count) { return ensure_drained(s, count, count); }
+};
+
+// Buffers that share ONE capacity.  A group lists its members once, in each(f, n): f(member, its elements at capacity n), in the order
+// they are released and allocated.  ensure / ensure_drained as DevVec's; a member that cannot be allocated leaves ALL of them empty,
+// the capacity 0, and its code is the group's.
+template <class Group>
+class DevGroup {
+    size_t cap_ = 0;
+    Group& self() { return static_cast<Group&>(*this); }
+
+public:
+    size_t cap() const { return cap_; }
+    void release() { self().each([](auto& m, size_t) { m.reset(); }, 0); cap_ = 0; }
+    int ensure(size_t n)
+    {
+        if (n <= cap_) return GSR_OK;
+        release();
+        int rc = GSR_OK;
+        self().each([&rc](auto& m, size_t count) { if (!rc) rc = m.alloc(count); }, n);
+        if (rc) release(); else cap_ = n;
+        return rc;
+    }
+    int ensure_drained(hipStream_t s, size_t n)
+    {
+        if (n <= cap_) return GSR_OK;
+        HIP_TRY(hipStreamSynchronize(s));
+        return ensure(n);
+    }
+};
+
+// a frame slot's per-tile arrays (per tile: entries scanned, records gathered, wave-record evaluations; phase 1's copy of a front-slab
+// frame; the tiles lazy colour gave up) and its super-tile ranges (65537 each)
+struct TileSet : DevGroup<TileSet> {
+    DevMem<uint4> tile_work, tile_work_a;
+    DevMem<int32_t> sstart, send, redo;
+    template <class F> void each(F f, size_t n) { f(tile_work, n); f(tile_work_a, n); f(sstart, (size_t)65536 + 1); f(send, (size_t)65536 + 1); f(redo, n); }
+};
+// the wire overlay: (depth bits, splat index) per pixel, and the image staged for a host target (16 bytes per pixel: enough for every format)
+struct WirePair : DevGroup<WirePair> {
+    DevMem<unsigned long long> zbuf;
+    DevMem<float> out;
+    template <class F> void each(F f, size_t n) { f(zbuf, n); f(out, n * 4); }
+};
+// the scratch of a Morton sort: codes / upload indices, ping-pong.  hold(n): an eighth and 1024 entries beyond the need; the callers go
+// on without it (upload order) or word their own refusal, so a failure also clears the runtime's sticky error
+struct MortonScratch : DevGroup<MortonScratch> {
+    DevMem<uint32_t> kA, kB, vA, vB;
+    template <class F> void each(F f, size_t n) { f(kA, n); f(kB, n); f(vA, n); f(vB, n); }
+    int hold(size_t n)
+    {
+        const int rc = n <= cap() ? GSR_OK : ensure(n + n / 8 + 1024);
+        if (rc) (void)hipGetLastError();
+        return rc;
+    }
+};
 
 // The device side of a caller's HOST buffer, kept by a frame slot from frame to frame: the image and the AOV plane a frame is
 // composited into before it is copied back, the copies of a host depth buffer and of a host background image.  Bytes throughout.
@@ -159,21 +235,14 @@ static int regrow(hipStream_t s, DevMem<T>& p, size_t& cap, size_t count, size_t
 // buffer is cleared whenever the band it is to hold is not the one it was last cleared for, and a buffer that was just allocated
 // has been cleared for none.
 struct StageBuf {
-    DevMem<char> p;
-    size_t cap = 0;
+    DevVec<char> p;                    // (grown to the exact size asked for)
     int sig[6] = {-1, -1, -1, -1, -1, -1};
 
-    void release()
-    {
-        p.reset();
-        cap = 0;
-        std::memset(sig, 0xff, sizeof sig);
-    }
+    void release() { p.reset(); std::memset(sig, 0xff, sizeof sig); }
     int ensure(hipStream_t s, size_t bytes)
     {
-        if (bytes <= cap) return GSR_OK;
-        std::memset(sig, 0xff, sizeof sig);
-        return regrow(s, p, cap, bytes, bytes);
+        if (bytes > p.cap()) std::memset(sig, 0xff, sizeof sig);
+        return p.ensure_drained(s, bytes);
     }
     int clear_if_reshaped(hipStream_t s, const int (&now)[6], size_t bytes)
     {
@@ -184,8 +253,7 @@ struct StageBuf {
     }
     int upload(hipStream_t s, const void* host, size_t bytes)
     {
-        const int rc = ensure(s, bytes);
-        if (rc) return rc;
+        if (const int rc = ensure(s, bytes)) return rc;
         HIP_TRY(hipMemcpyAsync(p, host, bytes, hipMemcpyHostToDevice, s));
         return GSR_OK;
     }

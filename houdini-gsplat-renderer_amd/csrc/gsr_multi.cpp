@@ -775,7 +775,7 @@ extern "C" int gsr_multi_render_depth(gsr_multi* m, const gsr_camera* cam, const
     int rc;
     harvest_gather_time(m, b);
     if (balanced && (rc = balance_bands(m, H))) return rc;
-    {   // a frame of another shape: buffers are about to be regrown, and frames in flight still use them (new boundaries: balance_bands
+    {   // a frame of another shape: buffers are about to be grown, and frames in flight still use them (new boundaries: balance_bands
         // has synchronised already; the generation keeps the rule in one place)
         const int sig[5] = {W, H, bands ? m->layout : 0, fpp, balanced ? (int)m->rebalances : 0};
         if (std::memcmp(sig, m->shape_sig, sizeof sig) != 0) {
@@ -1077,7 +1077,7 @@ extern "C" int gsr_comm_render(gsr_context* ctx, const gsr_camera* cam, const fl
     const int b = (int)(st.frame & 1u);
     int rc;
     HIP_OK(hipSetDevice(st.dev));
-    {   // a frame of another shape: the buffers are about to be regrown, and frames in flight still use them
+    {   // a frame of another shape: the buffers are about to be grown, and frames in flight still use them
         const int sig[4] = {W, H, bands ? 1 : 0, fpp};
         if (std::memcmp(sig, st.shape_sig, sizeof sig) != 0) {
             HIP_OK(hipStreamSynchronize(st.exec));

@@ -190,8 +190,8 @@ struct Reorder {
         if (!c->up_part && (rc = c->up_part.alloc((size_t)512 * 6))) return rc;
         may_order = c->opt_morton && n_new > 1;
         if (!may_order) return GSR_OK;
-        if (!ensure_order_scratch(c, n_new)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
-        if ((rc = ensure_u32(sl.hist, sl.hist_cap, (size_t)512 * div_up(n_new, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+        if (c->up_sort.hold(n_new)) return set_err(GSR_E_OOM, "%s: no room for the sort of the storage order", who);
+        if ((rc = ensure_counts(sl.hist, (size_t)512 * div_up(n_new, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
         return perm_new.alloc((size_t)n_new);
     }
     // the OLD order's inverse (built on slot 0's own stream, and waited for) and the three events of the clock.  events_first: gsr_remove

@@ -3,6 +3,7 @@
 // told to fail the k-th acquisition from now on with hipErrorOutOfMemory.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <cstring>
 
@@ -18,12 +19,18 @@ enum { STUB_DEV = 0, STUB_PINNED = 1, STUB_EVENT = 2, STUB_STREAM = 3 };
 static long stub_live[4] = {0, 0, 0, 0};
 static long stub_fail_in = 0;          // k > 0: the k-th acquisition from now fails; 0: none does
 static long stub_syncs = 0;            // hipStreamSynchronize calls
+static long stub_calls = 0;            // every stubbed call that acquires, releases, synchronises or clears the last error
+static long stub_peak[4] = {0, 0, 0, 0};   // the largest live count per kind since the test last set it
+static long stub_errors_cleared = 0;   // hipGetLastError calls
+struct uint4 { unsigned x, y, z, w; };
 
 static inline void stub_fail_kth(long k) { stub_fail_in = k; }
 static inline bool stub_acquire(int kind)
 {
+    stub_calls += 1;
     if (stub_fail_in > 0 && --stub_fail_in == 0) return false;
     stub_live[kind] += 1;
+    if (stub_live[kind] > stub_peak[kind]) stub_peak[kind] = stub_live[kind];
     return true;
 }
 
@@ -37,6 +44,7 @@ static inline hipError_t hipMalloc(void** p, size_t bytes)
 }
 static inline hipError_t hipFree(void* p)
 {
+    stub_calls += 1;
     if (p) stub_live[STUB_DEV] -= 1;
     std::free(p);
     return hipSuccess;
@@ -84,4 +92,5 @@ static inline hipError_t hipStreamDestroy(hipStream_t s)
     delete s;
     return hipSuccess;
 }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { stub_syncs += 1; return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t) { stub_syncs += 1; stub_calls += 1; return hipSuccess; }
+static inline hipError_t hipGetLastError() { stub_errors_cleared += 1; stub_calls += 1; return hipSuccess; }

@@ -1,9 +1,10 @@
-"""CPU tests of the owning handles (csrc/gsr_host_buffers.h: DevMem, PinnedMem, Event, Stream, regrow, StageBuf).
+"""CPU tests of the owning handles (csrc/gsr_host_buffers.h: DevMem, PinnedMem, Event, Stream, DevVec, StageBuf, the groups).
 
 tests/host_buffers_main.cpp includes the header through tests/hip_stub/hip/hip_runtime.h -- the HIP calls the header uses, backed by
 malloc / free, with a count of live objects per kind and a way to fail the k-th acquisition -- and is built here with the host
 compiler under the address and undefined-behaviour sanitizers, then run as a program of its own.  The program checks scope exit, move
-construction and assignment, swap, reset, alloc(0), failed allocations, regrow, StageBuf and the pinned aliases, and that every
+construction and assignment, swap, reset, alloc(0), failed allocations, the growing buffers (DevVec: what grows, what drains, what
+a failure leaves), StageBuf, the groups that share a capacity (every member or none) and the pinned aliases, and that every
 counter is 0 at its end (its exit status); the sanitizers add use-after-free, double free and leaks."""
 import os
 import shutil
