@@ -53,6 +53,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_remove.h"
 #include "k_add.h"
 #include "k_read.h"
+#include "k_select.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -363,6 +364,11 @@ struct gsr_context {
     // gsr_read / gsr_read_device (k_read.h): what gsr_get_read reports
     int64_t rd_calls = 0, rd_last = 0;
     double rd_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // gsr_select (k_select.h): the counter slots of k_select, where they are read back, and what gsr_get_select reports
+    DevMem<unsigned long long> sel_counters;
+    PinnedMem<unsigned long long> sel_h_counters;
+    int64_t sel_calls = 0, sel_last = 0;
+    double sel_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -2998,3 +3004,5 @@ extern "C" int gsr_stats_reset(gsr_context* c)
 #include "gsr_resident_edit.h"
 // ... and read back in upload order: it shares the edits' refusals and pointer check, and k_unpack comes last of all.
 #include "gsr_resident_read.h"
+// ... and selected by screen region: read's contract, and k_select behind k_unpack.
+#include "gsr_resident_select.h"

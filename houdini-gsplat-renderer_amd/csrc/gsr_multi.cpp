@@ -689,6 +689,16 @@ extern "C" int gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_
     return gsr_read(m->ctx[0], first, n, out);
 }
 
+// ... and selected by screen region on rank 0's replica (gsr_select into a host mask: the caller's thread; no rank's state changes)
+extern "C" int gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set)
+{
+    if (!m || !cam || !region || !mask_host) return fail(GSR_E_INVALID, "gsr_multi_select: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_select: upload in progress");
+    const int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return gsr_select(m->ctx[0], cam, region, mask_host, 0, n_hit, n_set);
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

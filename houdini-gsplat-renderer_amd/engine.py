@@ -120,6 +120,13 @@ class gsr_visibility(C.Structure):
                 ("mask", C.c_void_p), ("mask_splats", C.c_int64)]
 
 
+class gsr_select_region(C.Structure):
+    """include/gsplat_hip.h: the screen region of gsr_select -- a rect, and optionally a bit image and a depth buffer (host or device)"""
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float),
+                ("image", C.c_void_p), ("image_is_device", C.c_int32), ("depth", C.c_void_p), ("depth_is_device", C.c_int32),
+                ("depth_bias", C.c_float), ("op", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -153,6 +160,9 @@ VOL_BOX = 1            # gsr_crop_volume.kind: inside iff max(|q|) <= 1
 VOL_ELLIPSOID = 2      # ... iff |q|^2 <= 1
 REMOVE_HIDDEN = 1      # GSR_REMOVE_HIDDEN: gsr_remove also removes what the visibility in force hides
 REMOVE_BLOCK = 4096    # GSR_REMOVE_BLOCK: upload indices one workgroup of the compaction kernels spans
+SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_INTERSECT, SELECT_TOGGLE = range(5)     # GSR_SELECT_*: what gsr_select does to the mask
+SELECT_ANY_OPACITY = 1 # GSR_SELECT_ANY_OPACITY (flags): no opacity test, so hidden splats can be hit
+SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the selection kernel spans
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -190,6 +200,7 @@ C_ABI_SYMBOLS = [
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
+    "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan",
 ]
 
@@ -285,6 +296,10 @@ def load_library() -> C.CDLL:
     L.gsr_read_device.argtypes = [vp, i64, i64, C.POINTER(gsr_device_out)]
     L.gsr_get_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_read.argtypes = [vp, i64, i64, C.POINTER(gsr_read_arrays)]
+    L.gsr_select.argtypes = [vp, C.POINTER(gsr_camera), C.POINTER(gsr_select_region), vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_eval.argtypes = [C.POINTER(gsr_camera), f32p, C.POINTER(gsr_select_region), vp, vp, i64, vp, vp]
+    L.gsr_get_select.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_select.argtypes = [vp, C.POINTER(gsr_camera), C.POINTER(gsr_select_region), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -605,6 +620,74 @@ def remove_map(mask, n=None):
     out, left = np.zeros(max(int(n), 0), np.int32), C.c_int64(0)
     _check(load_library().gsr_remove_map(words.ctypes.data, int(n), out.ctypes.data if out.size else None, C.byref(left)))
     return out, left.value
+
+
+def pack_image(painted) -> np.ndarray:
+    """a boolean image (height, width), row 0 at the BOTTOM (GL window coordinates), True = painted -> the uint32 words
+    gsr_select_region.image takes: one bit per pixel, packed across rows without padding"""
+    words = pack_mask(np.asarray(painted, dtype=bool).reshape(-1))
+    return words if words.size else np.zeros(1, np.uint32)
+
+
+def select_region(rect=None, image=None, depth=None, depth_bias: float = 0.0, op: int = SELECT_REPLACE, any_opacity: bool = False,
+                  image_device: int | None = None, depth_device: int | None = None):
+    """gsr_select_region -> (struct, the arrays it points into: keep them alive during the call).  rect = (x0, y0, x1, y1) in GL window
+    coordinates, half-open (None: everywhere); image = a boolean (height, width) array, row 0 at the bottom, or packed uint32 words
+    (pack_image); depth = float32 (height, width) window depths; image_device / depth_device = raw device pointers in their place.
+    What the sizes must be is the camera's to say: Engine.select and select_eval check them."""
+    r, keep = gsr_select_region(), []
+    inf = float("inf")
+    r.x0, r.y0, r.x1, r.y1 = (-inf, -inf, inf, inf) if rect is None else [float(v) for v in rect]
+    if image is not None and image_device is not None or depth is not None and depth_device is not None:
+        raise GsrError(-1, "select_region: a source is given both as an array and as a device pointer")
+    if image is not None:
+        m = np.asarray(image)
+        words = np.ascontiguousarray(m).reshape(-1) if m.dtype == np.uint32 else pack_image(m)
+        keep.append(words)
+        r.image, r.image_is_device = words.ctypes.data, 0
+    elif image_device is not None:
+        r.image, r.image_is_device = int(image_device), 1
+    if depth is not None:
+        d = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1)
+        keep.append(d)
+        r.depth, r.depth_is_device = d.ctypes.data, 0
+    elif depth_device is not None:
+        r.depth, r.depth_is_device = int(depth_device), 1
+    r.depth_bias, r.op, r.flags = float(depth_bias), int(op), SELECT_ANY_OPACITY if any_opacity else 0
+    return r, keep
+
+
+def _region_fits(cam, keep, who):
+    """the host arrays of a select_region against the camera's size: the library reads ceil(w h / 32) words and w h floats"""
+    px = int(cam.width) * int(cam.height)
+    for a in keep:
+        need = (px + 31) // 32 if a.dtype == np.uint32 else px
+        if 1 <= int(cam.width) <= MAX_DIM and 1 <= int(cam.height) <= MAX_DIM and a.size < need:
+            raise GsrError(-1, f"{who}: the region's {'image' if a.dtype == np.uint32 else 'depth'} holds {a.size} entries, {cam.width}x{cam.height} needs {need}")
+
+
+def select_eval(cam, origin, region, P, opacity=None, centres: bool = False):
+    """gsr_select_eval (host only, no GPU): the rule of gsr_select through the function the kernel evaluates.  region: a gsr_select_region
+    or the (struct, keep) pair select_region returns, with HOST sources; P: float32 (n, 3) raw positions; opacity: float32 (n,) RESIDENT
+    opacities (None = 1) -> bool (n,) hit, and with centres also float32 (n, 3) = cx, cy, zw of every selectable splat, else NaN"""
+    r, keep = region if isinstance(region, tuple) else (region, [])
+    _region_fits(cam, keep, "select_eval")
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    n = P.shape[0]
+    a = None if opacity is None else np.ascontiguousarray(opacity, dtype=np.float32).reshape(-1)
+    if a is not None and a.size != n:
+        raise GsrError(-1, f"select_eval: {a.size} opacities for {n} positions")
+    hit, c = np.zeros(max(n, 1), np.uint8), np.zeros((max(n, 1), 3), np.float32) if centres else None
+    cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+    _check(load_library().gsr_select_eval(C.byref(cs), _f3(origin), C.byref(r), P.ctypes.data if n else None, _ptr(a) if n else None, n,
+                                          hit.ctypes.data, _ptr(c)))
+    return (hit[:n].astype(bool), c[:n]) if centres else hit[:n].astype(bool)
+
+
+def unpack_mask(words, n: int) -> np.ndarray:
+    """the first n bits of packed uint32 mask words -> bool (n,): pack_mask the other way round"""
+    w = np.ascontiguousarray(words, dtype="<u4").reshape(-1)
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:int(n)].astype(bool)
 
 
 def add_capacity(cap: int, need: int) -> int:
@@ -1027,6 +1110,40 @@ class Engine:
         calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
         _check(self.L.gsr_get_read(self.h, C.byref(calls), C.byref(last), ms))
         return {"reads": calls.value, "rows_last": last.value, "ms": [float(x) for x in ms]}
+
+    # ---- selection: resident splats by screen region (include/gsplat_hip.h, "selection")
+    def select(self, cam, region, mask=None):
+        """gsr_select into a HOST mask: the resident splats whose centre projects into the region (a gsr_select_region, or the
+        (struct, keep) pair select_region returns) -> (bool (n,) mask in upload order, n_hit, n_set).  mask = the prior selection the
+        region's op combines with (a boolean array over the resident splats or packed uint32 words; None: nothing selected).  The
+        result feeds set_visibility(mask=...) and remove(...) as it is.  Changes and invalidates nothing."""
+        r, keep = region if isinstance(region, tuple) else (region, [])
+        _region_fits(cam, keep, "select")
+        n = self.read_info()["n_splats"]
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+        _check(self.L.gsr_select(self.h, C.byref(cs), C.byref(r), words.ctypes.data, 0, C.byref(hit), C.byref(nset)))
+        return unpack_mask(words, n), hit.value, nset.value
+
+    def select_device(self, cam, region, mask_ptr: int):
+        """gsr_select into packed uint32 mask words in DEVICE memory (a raw pointer or an object with data_ptr(); ceil(n / 32) words,
+        read first by every op but SELECT_REPLACE); the region's image / depth may be device pointers too (select_region's
+        image_device / depth_device).  Waits for the work queued on the stream given to set_stream first; synchronous
+        -> (n_hit, n_set).  The mask goes straight into remove_device."""
+        r, keep = region if isinstance(region, tuple) else (region, [])
+        _region_fits(cam, keep, "select_device")
+        ptr = int(mask_ptr.data_ptr()) if hasattr(mask_ptr, "data_ptr") else int(mask_ptr)
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+        _check(self.L.gsr_select(self.h, C.byref(cs), C.byref(r), C.c_void_p(ptr), 1, C.byref(hit), C.byref(nset)))
+        return hit.value, nset.value
+
+    def get_select(self) -> dict:
+        """gsr_get_select -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_select(self.h, C.byref(calls), C.byref(last), ms))
+        return {"selects": calls.value, "hit_last": last.value, "ms": [float(x) for x in ms]}
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""
@@ -1591,6 +1708,19 @@ class MultiEngine:
         cnt, sh = C.c_int64(0), C.c_int(0)
         _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), C.byref(sh), None))
         return _read_splats(self.L, self.L.gsr_multi_read, self.h, (cnt.value, bool(sh.value)), first, n, names)
+
+    def select(self, cam, region, mask=None):
+        """gsr_multi_select: Engine.select on rank 0's copy (the cloud is replicated), into a host mask -> (bool mask, n_hit, n_set)"""
+        r, keep = region if isinstance(region, tuple) else (region, [])
+        _region_fits(cam, keep, "select")
+        cnt = C.c_int64(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), None, None))
+        n = cnt.value
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+        _check(self.L.gsr_multi_select(self.h, C.byref(cs), C.byref(r), words.ctypes.data, C.byref(hit), C.byref(nset)))
+        return unpack_mask(words, n), hit.value, nset.value
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

@@ -333,7 +333,7 @@ int  gsr_debug_check_device_source(gsr_context* ctx, const void* p, int64_t byte
  * how many resident splats the last application hid; either pointer may be NULL.
  * Out of scope: skipping wholly hidden clusters in k_cluster_cull (K1 still loads the 16 bytes of every hidden splat); the wire
  * overlay, which outlines every resident splat as before; a mask in device memory; a mask through the GSplatRenderer shim or the HDK
- * glue; gsr_comm_* (each rank is a plain context and sets its own visibility); picking. */
+ * glue; gsr_comm_* (each rank is a plain context and sets its own visibility). */
 #define GSR_VIS_MAX_VOLUMES 4
 #define GSR_VOL_BOX         1   /* inside iff max(|q.x|, |q.y|, |q.z|) <= 1 */
 #define GSR_VOL_ELLIPSOID   2   /* inside iff fmaf(q.x, q.x, fmaf(q.y, q.y, q.z * q.z)) <= 1 */
@@ -516,6 +516,83 @@ typedef struct gsr_device_out {           /* DEVICE destinations, float32, the l
 int  gsr_read_device(gsr_context* ctx, int64_t first, int64_t n, const gsr_device_out* out);
 int  gsr_get_read(gsr_context* ctx, int64_t* reads, int64_t* rows_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- selection (resident splats picked by screen region, on the GPU) --------------------------------------------------------------- */
+/* The masks gsr_set_visibility and gsr_remove take, made from what the user sees: drag a box or paint a lasso over the floaters, and
+ * the splats whose CENTRE projects into it come back as a bit mask in upload order -- without reading P and alpha back over the
+ * link and restating the vertex stage on the host.  One kernel (k_select.h), one thread per upload index.
+ * THE RULE (one function, evaluated by the kernel and by gsr_select_eval; x86 and gfx950 agree bit for bit).  For splat i with raw
+ * position bits (px, py, pz) and RESIDENT opacity a, the steps are the vertex stage's own, in its order, every multiply-add one fmaf:
+ *   1. x = (px - origin.x) + origin.x, likewise y, z                                  (the origin round trip)
+ *   2. tv = obj_view rows . (x, y, z, 1);  ftvy = -tv.y
+ *   3. cl = proj rows . (tv.x, ftvy, tv.z, 1)
+ *   4. selectable: cl.w > 0 && !(cl.z < -cl.w || cl.z > cl.w) && a >= 1/255; GSR_SELECT_ANY_OPACITY drops the last term.  Under a
+ *      visibility in force a hidden splat's resident opacity is +0.0f: by default it is never hit, with the flag it can be.
+ *   5. cx = fmaf(cl.x / cl.w, 0.5, 0.5) * W;  cy = fmaf((-cl.y) / cl.w, 0.5, 0.5) * H;  zw = fmaf(cl.z / cl.w, 0.5, 0.5)
+ *      (W, H = (float)width, (float)height of the camera; IEEE divisions) -- the centre and window depth of the frame's record.
+ * A splat is HIT iff it is selectable and passes every clause that is given; a NaN anywhere (centre or window depth) means no hit:
+ *   rect   always: x0 <= cx && cx < x1 && y0 <= cy && cy < y1 -- GL window coordinates, row 0 at the bottom, half-open.  Infinities
+ *          are allowed: (-inf, -inf, +inf, +inf) is "everywhere".
+ *   pixel  only when an image or a depth buffer is given: cx >= 0 && cx < W && cy >= 0 && cy < H, otherwise no hit; then
+ *          p = (int)cy * width + (int)cx.  No index is ever formed from a centre outside the image.
+ *   image  a lasso, a brush, any painted region, rasterised by the caller: bit p & 31 of word p >> 5 is set.  One bit per pixel,
+ *          packed across rows without padding, ceil(width * height / 32) words.
+ *   depth  zw <= depth[p] + depth_bias (one float32 add, one compare).  depth: float[height * width] window depths as
+ *          gsr_render_depth takes them.  The opaque pass's depth selects only what geometry does not hide; gsr_resolve_depth of the
+ *          depth AOV with a small positive bias selects only the surface layer of the splats themselves.
+ * THE MASK has the layout and sense of gsr_visibility.mask and of gsr_remove's mask: bit i & 31 of word i >> 5 is upload index i,
+ * ceil(n / 32) words (n: the resident count, gsr_read_info), and the result feeds either verb as it is -- a device mask goes
+ * straight into gsr_remove(mask, 1, ...) with nothing crossing the link.  With hit = the rule's verdicts, op decides what the mask
+ * holds afterwards (GSR_SELECT_*); every op but REPLACE reads the mask first (a host mask is copied in).  After any op the bits at and
+ * behind n in the last word are 0, and not one byte behind word ceil(n / 32) - 1 is written.  The result is deterministic: no atomic
+ * touches the mask.
+ * n_hit: the splats the rule hit, whatever the op; n_set: the bits set afterwards.  Either may be NULL.
+ * SOURCES: host images and depth buffers are copied when the call is made; device ones (image_is_device / depth_is_device) are read in
+ * place.  Every device pointer -- mask, image, depth -- is checked with its exact byte size before anything is launched, exactly as the
+ * device sources above are; a bad pointer gives GSR_E_INVALID, never a fault.
+ * gsr_select_eval: the rule on the host, with no context and no GPU, through the function the kernel evaluates.  P: float[3n] raw
+ * positions; opacity: float[n] RESIDENT opacities (NULL = 1); image and depth of the region are HOST pointers whatever the _is_device
+ * fields say; op is checked and not applied.  hit_out[k] = 0 / 1; centre_out (or NULL): [n][3] = cx, cy, zw of a selectable splat,
+ * else three NaNs.
+ * A SELECT CHANGES AND INVALIDATES NOTHING -- gsr_read's contract: no resident bit changes; depth horizons, cached depth orders,
+ * policies, the visibility and every entry of gsr_stats stay; it does not wait for the frames in flight; the next frame runs the
+ * launches it would have run.  A context that never selects launches nothing new.
+ * ORDERING: gsr_read's (host mask) and gsr_read_device's (device mask): with any device pointer the call first waits for the work
+ * queued on the context's public stream (gsr_set_stream) -- a gsr_resolve_depth_device queued there has finished.  Both forms are
+ * synchronous: on return the mask and the counts are complete.
+ * GSR_E_INVALID, nothing written: NULL ctx, camera, region or mask; no geometry ever uploaded, or an upload in progress; width or
+ * height outside 1..GSR_MAX_DIM; an unknown op, unknown flag bits, or reserved_ != 0; a device pointer that fails the check.  The
+ * empty cloud gives GSR_OK, writes nothing, and both counts are 0.
+ * gsr_get_select: the calls that selected, the splats hit by the last one, and its clock ms[4]: [0] the kernel (HIP events)
+ * [1] the copies, wall clock   [2] 0.0 (reserved)   [3] wall clock of the call.
+ * gsr_multi_select (below, with the other gsr_multi verbs): rank 0's context and a host mask -- the cloud is replicated.
+ * Out of scope: the GSplatRenderer shim and the HDK glue (renderPick speaks Houdini's pick-buffer protocol); gsr_comm_* (each rank
+ * selects for itself); rasterising a lasso polygon into the image; a device mask for gsr_set_visibility; per-pixel id buffers;
+ * selecting by a splat's footprint instead of its centre; an asynchronous form. */
+#define GSR_SELECT_REPLACE   0   /* mask = hit                */
+#define GSR_SELECT_ADD       1   /* mask |= hit               */
+#define GSR_SELECT_SUBTRACT  2   /* mask &= ~hit              */
+#define GSR_SELECT_INTERSECT 3   /* mask &= hit               */
+#define GSR_SELECT_TOGGLE    4   /* mask ^= hit               */
+#define GSR_SELECT_ANY_OPACITY 1 /* flags: no opacity test -- splats below 1/255, and the ones a visibility hides, can be hit */
+#define GSR_SELECT_BLOCK     256 /* upload indices one workgroup of the selection kernel spans (k_select.h) */
+typedef struct gsr_select_region {
+    float x0, y0, x1, y1;                 /* the rect, GL window coordinates, half-open */
+    const uint32_t* image;                /* NULL: no image clause */
+    int32_t image_is_device;
+    const float*    depth;                /* NULL: no depth clause */
+    int32_t depth_is_device;
+    float   depth_bias;
+    int32_t op;                           /* GSR_SELECT_REPLACE .. GSR_SELECT_TOGGLE */
+    int32_t flags;                        /* GSR_SELECT_ANY_OPACITY or 0 */
+    int32_t reserved_;                    /* 0 */
+} gsr_select_region;
+int  gsr_select(gsr_context* ctx, const gsr_camera* cam, const gsr_select_region* region,
+                uint32_t* mask, int mask_is_device, int64_t* n_hit, int64_t* n_set);
+int  gsr_select_eval(const gsr_camera* cam, const float origin[3], const gsr_select_region* region /* host pointers */,
+                     const float* P, const float* opacity /* resident; NULL = 1 */, int64_t n,
+                     uint8_t* hit_out, float* centre_out /* [n][3] = cx, cy, zw of a selectable splat, else NaN; or NULL */);   /* host, no context, no GPU */
+int  gsr_get_select(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -627,6 +704,9 @@ int  gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const uint16_t* 
                    const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total);
 /* gsr_read of rank 0's copy (the cloud is replicated), after the same synchronisation; no rank's state changes */
 int  gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_arrays* out);
+/* gsr_select on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
+int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host,
+                      int64_t* n_hit, int64_t* n_set);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
