@@ -699,6 +699,29 @@ extern "C" int gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_s
     return gsr_select(m->ctx[0], cam, region, mask_host, 0, n_hit, n_set);
 }
 
+// ... and transformed on every rank: each bakes the transform into its own replica and re-orders it.  gsr_multi_remove's agreement rule.
+extern "C" int gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved)
+{
+    if (!m || !x) return fail(GSR_E_INVALID, "gsr_multi_transform: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_transform: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> moved((size_t)G, -1);
+    int64_t* const mp = moved.data();
+    rc = for_each_rank(m, [=](int g) { return gsr_transform(m->ctx[g], mask_host, 0, x, mp + g); });
+    bool any_done = false, same = rc == GSR_OK;
+    for (int g = 0; g < G; ++g) any_done = any_done || moved[(size_t)g] >= 0;
+    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
+    for (int g = 1; g < G && same; ++g) same = moved[(size_t)g] == moved[0];
+    if (!same) {
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_transform: the ranks do not agree on the splats moved: the geometry is dropped on all of them");
+    }
+    if (n_moved) *n_moved = moved[0];
+    return GSR_OK;
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

@@ -1,5 +1,5 @@
-// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7): gsr_update, gsr_move, the
-// device sources, gsr_set_visibility, gsr_remove, gsr_add.  Host code only; included once, at the end of gsr_api.hip, which has the
+// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10): gsr_update, gsr_move, the
+// device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_transform.  Host code only; included once, at the end of gsr_api.hip, which has the
 // context, the frame slots, the upload arena (ensure_stage, ensure_up_events, stage_host_rows), the ordering of an upload (position_box,
 // morton_order), new_cloud_state / drop_geometry, and the <SH> launches of k_update, k_update_f32 and k_repack (launch_update,
 // queue_repack).
@@ -255,51 +255,38 @@ struct Reorder {
 };
 
 // ---------------------------------------------------------------------------
-// The body of gsr_move and gsr_move_device, behind their refusals.  new_bytes: what the new rows take at the head of the arena (0: they
-// stay in the caller's device memory); upd_bytes: what the attribute step stages there; attr_step(): the update verb for the same rows
-// (attrs: whether there is one; it leaves its link time in upload_ms[4]); new_rows(arena, stream, &Pnew, &link_ms): the device pointer
-// of the new rows, after whatever copy brings them there.
-template <class AttrStep, class NewRows>
-static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64, const float origin[3], size_t new_bytes, size_t upd_bytes,
-                     bool attrs, AttrStep&& attr_step, NewRows&& new_rows)
+// The body of every verb that gives resident splats new positions and keeps their number: gsr_move, gsr_move_device, gsr_transform.
+// stage_bytes: what the call needs of the staging arena; ms: the verb's clock (keep_unread: Reorder::finish).
+//   before_write(ro, &nothing)   behind the last allocation and in front of the first write: what the verb can still find out
+//                                without changing anything; nothing = true: the call is over, GSR_OK, and nothing was changed
+//   positions(ro, &Pall)         the position step: the verb's own writes into the resident planes (from here on a failure leaves no
+//                                geometry: the step goes through ro.lost itself), up_ev[0] in front of its kernel, and Pall = every
+//                                position of the cloud in upload order, device memory, for the ordering of an upload
+template <class BeforeWrite, class Positions>
+static int reposition_body(gsr_context* c, const char* who, size_t stage_bytes, const float origin[3], double ms[4], bool keep_unread,
+                           BeforeWrite&& before_write, Positions&& positions)
 {
     HIP_TRY(hipSetDevice(c->device));
     Reorder ro(c, who, false);
     int rc = sync_all(c);      // no write under a frame in flight
     if (rc) return rc;
-    const uint32_t n = c->n, cnt = (uint32_t)n64;
+    const uint32_t n = c->n;
     // ---- everything the call needs, before the first write: an allocation failure leaves the context as it was
     // (whether the new cloud is ordered is known only once its box is: with GSR_OPT_STORAGE_ORDER = 1 the sort and the spare planes are provided for)
-    const size_t oNew = 0, oAll = pad256(new_bytes);
-    if ((rc = ensure_stage(c, std::max(oAll + pad256((size_t)n * 12), upd_bytes)))) return rc;
+    if ((rc = ensure_stage(c, stage_bytes))) return rc;
     if ((rc = ro.prepare(n))) return rc;
     if ((ro.may_order || c->perm) && (rc = ensure_spare_planes(c, c->cap, true))) return rc;
     if ((rc = ro.old_inverse(false))) return rc;
+    bool nothing = false;
+    if ((rc = before_write(ro, &nothing)) || nothing) return rc;
     // ---- from here on a failure leaves no geometry
-    // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
-    if (attrs) {
-        rc = attr_step();              // (a visibility in force: the step puts new alphas aside; the rule is applied at the end, at the new positions)
-        // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
-        //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
-        if (rc == GSR_E_HIP) return ro.lost(rc);
-        if (rc) return rc;  // (refused before its first write)
-        ro.link_ms = c->st.upload_ms[4];
-    }
-    // 2. the new rows where the splats sit now, and every position in upload order
-    float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
-    const float* Pnew = nullptr;       // the new rows, in device memory
-    hipError_t e = new_rows(reinterpret_cast<float*>(c->stage + oNew), ro.us, &Pnew, &ro.link_ms);
-    if (e != hipSuccess) return ro.lost(e);
-    hipStream_t us = ro.us;
-    e = hipEventRecord(c->up_ev[0], us);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, us, (uint32_t)first, cnt, n, Pnew, ro.inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess) return ro.lost(e);
-    // 3. the ordering of an upload
+    const float* Pall = nullptr;
+    if ((rc = positions(ro, &Pall))) return rc;
+    // the ordering of an upload
     if ((rc = ro.order(Pall, n))) return ro.lost(rc);
-    // 4. the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
+    // the planes into the new order (the spare copy), or -- upload order before and after -- only the cluster bounds again, in place
+    hipStream_t us = ro.us;
+    hipError_t e = hipSuccess;
     const bool repack = ro.perm_new || c->perm;
     if (repack) {
         e = queue_repack(c, us, n, ro.perm_new, ro.inv_old);
@@ -310,10 +297,49 @@ static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64
     if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
     if (e == hipSuccess) e = hipStreamSynchronize(us);
     if (e != hipSuccess) return ro.lost(e);
-    // 5. the swap, and the cloud at its new positions
+    // the swap, and the cloud at its new positions
     ro.commit(n, c->nclus, repack);
     if (origin) for (int k = 0; k < 3; ++k) c->origin[k] = origin[k];
-    if ((rc = ro.finish(c->st.move_ms, true))) return rc;
+    return ro.finish(ms, keep_unread);
+}
+
+// The body of gsr_move and gsr_move_device, behind their refusals.  new_bytes: what the new rows take at the head of the arena (0: they
+// stay in the caller's device memory); upd_bytes: what the attribute step stages there; attr_step(): the update verb for the same rows
+// (attrs: whether there is one; it leaves its link time in upload_ms[4]); new_rows(arena, stream, &Pnew, &link_ms): the device pointer
+// of the new rows, after whatever copy brings them there.
+template <class AttrStep, class NewRows>
+static int move_body(gsr_context* c, const char* who, int64_t first, int64_t n64, const float origin[3], size_t new_bytes, size_t upd_bytes,
+                     bool attrs, AttrStep&& attr_step, NewRows&& new_rows)
+{
+    const uint32_t n = c->n, cnt = (uint32_t)n64;
+    const size_t oNew = 0, oAll = pad256(new_bytes);
+    const int rc = reposition_body(c, who, std::max(oAll + pad256((size_t)n * 12), upd_bytes), origin, c->st.move_ms, true,
+        [](Reorder&, bool*) { return GSR_OK; },
+        [&](Reorder& ro, const float** Pout) {
+            // 1. the attributes of the same rows, through the old inverse: the update verb as it is (it refuses nothing here that was not refused before)
+            if (attrs) {
+                const int rca = attr_step();   // (a visibility in force: the step puts new alphas aside; the rule is applied at the end, at the new positions)
+                // (stricter than promised: gsr_update does not say whether a HIP failure of its own came before or after its first write --
+                //  hipSetDevice, a host -> device copy into the arena, or a kernel -- so ANY of them counts as after it)
+                if (rca == GSR_E_HIP) return ro.lost(rca);
+                if (rca) return rca;  // (refused before its first write)
+                ro.link_ms = c->st.upload_ms[4];
+            }
+            // 2. the new rows where the splats sit now, and every position in upload order
+            float* const Pall = reinterpret_cast<float*>(c->stage + oAll);
+            const float* Pnew = nullptr;       // the new rows, in device memory
+            hipError_t e = new_rows(reinterpret_cast<float*>(c->stage + oNew), ro.us, &Pnew, &ro.link_ms);
+            if (e != hipSuccess) return ro.lost(e);
+            e = hipEventRecord(c->up_ev[0], ro.us);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(k_move_positions, dim3(div_up(n, 256)), dim3(256), 0, ro.us, (uint32_t)first, cnt, n, Pnew, ro.inv_old, c->geoA, c->has_sh ? c->colrow : (uint4*)nullptr, Pall);
+                e = hipGetLastError();
+            }
+            if (e != hipSuccess) return ro.lost(e);
+            *Pout = Pall;
+            return GSR_OK;
+        });
+    if (rc) return rc;
     c->st.moves += 1;
     return GSR_OK;
 }
@@ -977,4 +1003,227 @@ extern "C" int gsr_add_device(gsr_context* c, int64_t m64, const gsr_device_attr
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = check_device_attrs(c, a, m, who))) return rc;
     return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double*) { return stage_device_rows(c, A, 0, m, a, us); }, n_total);
+}
+
+// ---------------------------------------------------------------------------
+// Transform (k_transform.h): selected resident splats rotated, scaled and translated where they are.  A move whose new
+// positions, shapes and SH rows are formed on the GPU from the resident ones: k_transform in the place of k_move_positions, then
+// reposition_body as gsr_move runs it.
+static_assert(sizeof(gsr_xform_rule) == sizeof(GsrXformRule) && offsetof(gsr_xform_rule, t) == offsetof(GsrXformRule, t) &&
+              offsetof(gsr_xform_rule, s) == offsetof(GsrXformRule, s) && offsetof(gsr_xform_rule, q) == offsetof(GsrXformRule, q) &&
+              offsetof(gsr_xform_rule, D1) == offsetof(GsrXformRule, D1) && offsetof(gsr_xform_rule, D2) == offsetof(GsrXformRule, D2) &&
+              offsetof(gsr_xform_rule, D3) == offsetof(GsrXformRule, D3), "gsr_xform_rule is the kernel's rule");
+
+// Y_l(d), l = 1..3, in double: the 2l + 1 polynomials gsr_shade_sh (k_preprocess.h) multiplies band l's coefficients with, its float32
+// constants and its signs included
+static void xform_sh_basis(int l, const double d[3], double* y)
+{
+    const double x = d[0], yy_ = d[1], z = d[2];
+    const double xx = x * x, yy = yy_ * yy_, zz = z * z, xy = x * yy_, yz = yy_ * z, xz = x * z;
+    if (l == 1) {
+        const double C1 = 0.4886025f;
+        y[0] = -C1 * yy_; y[1] = C1 * z; y[2] = -C1 * x;
+    } else if (l == 2) {
+        const double C0 = 1.0925484f, C1 = -1.0925484f, C2 = 0.3153916f, C3 = -1.0925484f, C4 = 0.5462742f;
+        y[0] = C0 * xy; y[1] = C1 * yz; y[2] = C2 * (2.0 * zz - xx - yy); y[3] = C3 * xz; y[4] = C4 * (xx - yy);
+    } else {
+        const double C0 = -0.5900436f, C1 = 2.8906114f, C2 = -0.4570458f, C3 = 0.3731763f, C4 = -0.4570458f, C5 = 1.4453057f, C6 = -0.5900436f;
+        y[0] = C0 * yy_ * (3.0 * xx - yy); y[1] = C1 * xy * z; y[2] = C2 * yy_ * (4.0 * zz - xx - yy);
+        y[3] = C3 * z * (2.0 * zz - 3.0 * xx - 3.0 * yy); y[4] = C4 * x * (4.0 * zz - xx - yy); y[5] = C5 * z * (xx - yy);
+        y[6] = C6 * x * (xx - 3.0 * yy);
+    }
+}
+
+// D_l with Y_l(R d)^T D_l = Y_l(d)^T for every unit d, by a linear solve over N = 2l + 1 fixed sample directions e_i built from those
+// same polynomials (so the sign conventions are right by construction): with d = R^T e the condition reads Y_l(e)^T D_l = Y_l(R^T e)^T,
+// i.e. B D = C with the rows B_i = Y_l(e_i), C_i = Y_l(R^T e_i).  Solved as D = I + B^-1 (C - B): the correction is exactly zero where R
+// is the identity, without a special case.  The e_i spiral down the sphere off any symmetry (cond(B) < 8 in every band).  Gaussian
+// elimination with partial pivoting, double.
+static void xform_band_matrix(int l, const double R[9], float* D)
+{
+    const int N = 2 * l + 1;
+    double B[7][7], X[7][7];
+    for (int i = 0; i < N; ++i) {
+        const double th = 0.4 + 2.2 * (double)i / (double)N, ph = (double)i * 2.399963229728653;
+        const double e[3] = {std::sin(th) * std::cos(ph), std::sin(th) * std::sin(ph), std::cos(th)};
+        const double re[3] = {R[0] * e[0] + R[3] * e[1] + R[6] * e[2], R[1] * e[0] + R[4] * e[1] + R[7] * e[2], R[2] * e[0] + R[5] * e[1] + R[8] * e[2]};   // R^T e
+        double c[7];
+        xform_sh_basis(l, e, B[i]);
+        xform_sh_basis(l, re, c);
+        for (int k = 0; k < N; ++k) X[i][k] = c[k] - B[i][k];
+    }
+    for (int k = 0; k < N; ++k) {
+        int p = k;
+        for (int i = k + 1; i < N; ++i) if (std::fabs(B[i][k]) > std::fabs(B[p][k])) p = i;
+        if (p != k) for (int j = 0; j < N; ++j) { std::swap(B[k][j], B[p][j]); std::swap(X[k][j], X[p][j]); }
+        for (int i = k + 1; i < N; ++i) {
+            const double f = B[i][k] / B[k][k];
+            for (int j = k; j < N; ++j) B[i][j] -= f * B[k][j];
+            for (int j = 0; j < N; ++j) X[i][j] -= f * X[k][j];
+        }
+    }
+    for (int i = N - 1; i >= 0; --i)
+        for (int j = 0; j < N; ++j) {
+            double v = X[i][j];
+            for (int k = i + 1; k < N; ++k) v -= B[i][k] * X[k][j];
+            X[i][j] = v / B[i][i];
+        }
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < N; ++j) D[i * N + j] = (float)((i == j ? 1.0 : 0.0) + X[i][j]);
+}
+
+// what is wrong with the caller's transform (NULL: nothing)
+static const char* xform_error(const gsr_xform* x)
+{
+    const float* f = x->rotate;        // rotate[4], scale, translate[3], pivot[3]: eleven floats in a row
+    static_assert(offsetof(gsr_xform, reserved_) == 11 * sizeof(float), "gsr_xform begins with eleven floats");
+    for (int k = 0; k < 11; ++k) if (!std::isfinite(f[k])) return "a field is not finite";
+    if (!(x->scale > 0.0f)) return "scale is not > 0";
+    if (x->rotate[0] == 0.0f && x->rotate[1] == 0.0f && x->rotate[2] == 0.0f && x->rotate[3] == 0.0f) return "the quaternion is zero";
+    if (x->reserved_ != 0) return "reserved_ is not 0";
+    return nullptr;
+}
+static GsrXformRule xform_rule(const gsr_xform* x)
+{
+    GsrXformRule r{};
+    const double qx = x->rotate[0], qy = x->rotate[1], qz = x->rotate[2], qw = x->rotate[3];
+    const double len = std::sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
+    const double i = qx / len, j = qy / len, k = qz / len, w = qw / len, s = x->scale;
+    const double R[9] = {1.0 - 2.0 * (j * j + k * k), 2.0 * (i * j - w * k), 2.0 * (i * k + w * j),
+                         2.0 * (i * j + w * k), 1.0 - 2.0 * (i * i + k * k), 2.0 * (j * k - w * i),
+                         2.0 * (i * k - w * j), 2.0 * (j * k + w * i), 1.0 - 2.0 * (i * i + j * j)};
+    for (int e = 0; e < 9; ++e) r.A[e] = (float)(s * R[e]);
+    for (int a = 0; a < 3; ++a) {
+        const double sRp = s * R[3 * a] * (double)x->pivot[0] + s * R[3 * a + 1] * (double)x->pivot[1] + s * R[3 * a + 2] * (double)x->pivot[2];
+        r.t[a] = (float)((double)x->pivot[a] + (double)x->translate[a] - sRp);
+    }
+    r.s = x->scale;
+    r.q[0] = (float)i; r.q[1] = (float)j; r.q[2] = (float)k; r.q[3] = (float)w;
+    xform_band_matrix(1, R, r.D1);
+    xform_band_matrix(2, R, r.D2);
+    xform_band_matrix(3, R, r.D3);
+    return r;
+}
+
+extern "C" int gsr_xform_prepare(const gsr_xform* x, gsr_xform_rule* rule)
+{
+    if (!x || !rule) return set_err(GSR_E_INVALID, "gsr_xform_prepare: NULL argument");
+    const char* bad = xform_error(x);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_xform_prepare: %s", bad);
+    const GsrXformRule r = xform_rule(x);
+    std::memcpy(rule, &r, sizeof(r));
+    return GSR_OK;
+}
+
+extern "C" int gsr_transform_eval(const gsr_xform* x, int64_t n, const uint32_t* mask, float* P, uint16_t* scale, uint16_t* orient,
+                                  uint16_t* shx, uint16_t* shy, uint16_t* shz)
+{
+    if (!x) return set_err(GSR_E_INVALID, "gsr_transform_eval: x is NULL");
+    const char* bad = xform_error(x);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_transform_eval: %s", bad);
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && (!P || !scale || !orient))) return set_err(GSR_E_INVALID, "gsr_transform_eval: bad argument");
+    const int nsh = (shx ? 1 : 0) + (shy ? 1 : 0) + (shz ? 1 : 0);
+    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_transform_eval: the three SH arrays come together or not at all");
+    const GsrXformRule r = xform_rule(x);
+    uint16_t* const sh[3] = {shx, shy, shz};
+    for (int64_t i = 0; i < n; ++i) {
+        if (mask && !((mask[i >> 5] >> (i & 31)) & 1u)) continue;
+        float* p = P + 3 * i;
+        const float px = p[0], py = p[1], pz = p[2];
+        for (int a = 0; a < 3; ++a) p[a] = gsr_xf_position(r, a, px, py, pz);
+        uint16_t* s = scale + 3 * i;
+        for (int k = 0; k < 3; ++k) s[k] = gsr_xf_scale(r, s[k]);
+        uint16_t* o = orient + 4 * i;
+        gsr_xf_orient(r, o[0], o[1], o[2], o[3]);
+        if (nsh)
+            for (int ch = 0; ch < 3; ++ch)
+                for (int part = 0; part < 2; ++part) gsr_xf_sh_part(r, part, sh[ch] + 16 * i);
+    }
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_transform(gsr_context* c, int64_t* calls, int64_t* moved_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_transform: ctx is NULL");
+    if (calls) *calls = c->xf_calls;
+    if (moved_last) *moved_last = c->xf_last;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->xf_ms[k];
+    return GSR_OK;
+}
+
+extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_device, const gsr_xform* x, int64_t* n_moved)
+{
+    const char* const who = "gsr_transform";
+    if (!c || !x) return set_err(GSR_E_INVALID, "gsr_transform: NULL argument");
+    const char* bad = xform_error(x);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_transform: %s", bad);
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const uint32_t n = c->n;
+    const size_t words = ((size_t)n + 31) / 32;
+    HIP_TRY(hipSetDevice(c->device));
+    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    if (n == 0) {                      // the empty cloud: no word of the mask exists
+        rc = sync_all(c);
+        if (rc) return rc;
+        c->xf_calls += 1; c->xf_last = 0;
+        if (n_moved) *n_moved = 0;
+        return GSR_OK;
+    }
+    const GsrXformRule rule = xform_rule(x);
+    // ---- the arena: every position in upload order, the rule, the count, a host mask's copy
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
+    const size_t oP = place((size_t)n * 12), oRule = place(sizeof(GsrXformRule)), oCount = place(4), oMask = place(mask && !mask_is_device ? words * 4 : 0);
+    if (!c->xf_h_count && c->xf_h_count.alloc(1, 0)) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "gsr_transform: no pinned host memory for the count");
+    }
+    const uint32_t* dmask = mask;
+    uint32_t count = n;
+    rc = reposition_body(c, who, off, nullptr, c->xf_ms, false,
+        [&](Reorder& ro, bool* nothing) {
+            // the rule and a host mask into the arena (no resident byte), then the count: a mask with no bit set below n ends the call here
+            hipStream_t us = ro.us;
+            const double t0 = up_now_ms();
+            HIP_TRY(hipMemcpyAsync(c->stage + oRule, &rule, sizeof(rule), hipMemcpyHostToDevice, us));
+            if (mask && !mask_is_device) {
+                uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
+                HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
+                dmask = staged;
+            }
+            HIP_TRY(hipStreamSynchronize(us));         // the caller's mask may be freed on return
+            ro.link_ms = up_now_ms() - t0;
+            if (dmask) {
+                uint32_t* const dcount = reinterpret_cast<uint32_t*>(c->stage + oCount);
+                HIP_TRY(hipMemsetAsync(dcount, 0, 4, us));
+                hipLaunchKernelGGL(k_transform_count, dim3(div_up((uint32_t)words, 256)), dim3(256), 0, us, n, dmask, dcount);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(c->xf_h_count, dcount, 4, hipMemcpyDeviceToHost, us));
+                HIP_TRY(hipStreamSynchronize(us));
+                count = c->xf_h_count[0];
+                if (count > n) return set_err(GSR_E_HIP, "gsr_transform: the reduction counted %u bits below %u", count, n);
+            }
+            *nothing = count == 0;
+            return GSR_OK;
+        },
+        [&](Reorder& ro, const float** Pout) {
+            float* const Pup = reinterpret_cast<float*>(c->stage + oP);
+            hipError_t e = hipEventRecord(c->up_ev[0], ro.us);
+            if (e == hipSuccess) {
+                launch_sh(c->has_sh, [&](auto sh) {
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_transform<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, ro.us, n, c->cap, dmask,
+                                       reinterpret_cast<const GsrXformRule*>(c->stage + oRule), ro.inv_old, c->geoA, c->geoB, c->col, c->colrow, Pup);
+                });
+                e = hipGetLastError();
+            }
+            if (e != hipSuccess) return ro.lost(e);
+            *Pout = Pup;
+            return GSR_OK;
+        });
+    if (rc) return rc;
+    c->xf_calls += 1;
+    c->xf_last = (int64_t)count;
+    if (n_moved) *n_moved = (int64_t)count;
+    return GSR_OK;
 }

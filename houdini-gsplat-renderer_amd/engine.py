@@ -127,6 +127,17 @@ class gsr_select_region(C.Structure):
                 ("depth_bias", C.c_float), ("op", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_xform(C.Structure):
+    """include/gsplat_hip.h: the similarity of gsr_transform -- p' = s R (p - pivot) + pivot + translate"""
+    _fields_ = [("rotate", C.c_float * 4), ("scale", C.c_float), ("translate", C.c_float * 3), ("pivot", C.c_float * 3), ("reserved_", C.c_int32)]
+
+
+class gsr_xform_rule(C.Structure):
+    """include/gsplat_hip.h: what gsr_xform_prepare derives from a gsr_xform (100 float32)"""
+    _fields_ = [("A", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float), ("q", C.c_float * 4),
+                ("D1", C.c_float * 9), ("D2", C.c_float * 25), ("D3", C.c_float * 49)]
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -201,6 +212,7 @@ C_ABI_SYMBOLS = [
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
+    "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan",
 ]
 
@@ -300,6 +312,11 @@ def load_library() -> C.CDLL:
     L.gsr_select_eval.argtypes = [C.POINTER(gsr_camera), f32p, C.POINTER(gsr_select_region), vp, vp, i64, vp, vp]
     L.gsr_get_select.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_select.argtypes = [vp, C.POINTER(gsr_camera), C.POINTER(gsr_select_region), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_xform_prepare.argtypes = [C.POINTER(gsr_xform), C.POINTER(gsr_xform_rule)]
+    L.gsr_transform_eval.argtypes = [C.POINTER(gsr_xform), i64] + [vp] * 7
+    L.gsr_transform.argtypes = [vp, vp, i32, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
+    L.gsr_get_transform.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_transform.argtypes = [vp, vp, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -690,6 +707,46 @@ def unpack_mask(words, n: int) -> np.ndarray:
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:int(n)].astype(bool)
 
 
+def xform(rotate=(0.0, 0.0, 0.0, 1.0), scale: float = 1.0, translate=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0), axis_angle=None) -> gsr_xform:
+    """gsr_xform: p' = scale * R (p - pivot) + pivot + translate.  rotate = a quaternion (x, y, z, w), orient's order, of any length;
+    axis_angle = ((ax, ay, az), degrees) instead: the quaternion of that turn about that axis (formed in double).  What the fields may
+    hold is the library's to refuse (xform_prepare, transform_eval, Engine.transform)."""
+    x = gsr_xform()
+    if axis_angle is not None:
+        axis, deg = axis_angle
+        a = np.asarray(axis, dtype=np.float64).reshape(3)
+        half = np.deg2rad(float(deg)) / 2.0
+        rotate = tuple(a / np.linalg.norm(a) * np.sin(half)) + (np.cos(half),)
+    x.rotate[:] = [float(v) for v in np.asarray(rotate, dtype=np.float32).reshape(4)]
+    x.scale = float(np.float32(scale))
+    x.translate[:] = [float(v) for v in np.asarray(translate, dtype=np.float32).reshape(3)]
+    x.pivot[:] = [float(v) for v in np.asarray(pivot, dtype=np.float32).reshape(3)]
+    return x
+
+
+def xform_prepare(x: gsr_xform) -> dict:
+    """gsr_xform_prepare (host only, no GPU): the float32 rule of a transform -> {A (3, 3) = s R, t (3,), s, q (4,) = the unit
+    quaternion (i, j, k, r), D1 (3, 3), D2 (5, 5), D3 (7, 7): the SH band matrices}"""
+    r = gsr_xform_rule()
+    _check(load_library().gsr_xform_prepare(C.byref(x) if x is not None else None, C.byref(r)))
+    arr = lambda field, *shape: np.array(list(field), dtype=np.float32).reshape(*shape)
+    return {"A": arr(r.A, 3, 3), "t": arr(r.t, 3), "s": np.float32(r.s), "q": arr(r.q, 4), "D1": arr(r.D1, 3, 3), "D2": arr(r.D2, 5, 5), "D3": arr(r.D3, 7, 7)}
+
+
+def transform_eval(x: gsr_xform, splats, mask=None):
+    """gsr_transform_eval (host only, no GPU): the arrays of a Splats-like object with the transform baked into the rows the mask
+    selects (a boolean array over the splats or packed uint32 words; None: every row), through the functions the kernel evaluates
+    -> a new scenes.Splats; Cd and alpha are copies, the input is not written"""
+    from .scenes import Splats
+    a = _Arrays(splats)
+    P, scale, orient = a.P.copy(), a.scale.copy(), a.orient.copy()
+    sh = [None if v is None else v.copy() for v in (a.shx, a.shy, a.shz)]
+    words = removal_words(mask, a.n)
+    _check(load_library().gsr_transform_eval(C.byref(x) if x is not None else None, a.n, None if words is None else words.ctypes.data,
+                                             _ptr(P), _ptr(scale), _ptr(orient), *[_ptr(v) for v in sh]))
+    return Splats(P, a.Cd.copy(), a.alpha.copy(), scale, orient, *sh)
+
+
 def add_capacity(cap: int, need: int) -> int:
     """gsr_add_capacity (host only, no GPU): the capacity a context of capacity cap has after an add that brings it to need splats --
     cap while need fits, else need + need // 4, clamped to 0x7fffffff"""
@@ -1043,6 +1100,33 @@ class Engine:
         left = C.c_int64(0)
         _check(self.L.gsr_remove(self.h, C.c_void_p(ptr), 1, REMOVE_HIDDEN if hidden else 0, C.byref(left)))
         return left.value
+
+    # ---- transform: selected resident splats rotated, scaled, translated (include/gsplat_hip.h, "transform")
+    def transform(self, x: gsr_xform, mask=None) -> int:
+        """gsr_transform from a HOST mask: the transform (xform) is baked into the resident splats whose mask entry is True (a boolean
+        array over the resident splats in upload order, or the packed uint32 words; None: every splat) -- positions, scales, orients
+        and SH rows -- and the cloud is re-ordered on the GPU with no re-upload, bit for bit a fresh upload of transform_eval of what
+        read returns -> the splats moved"""
+        words = removal_words(mask, self.stats()["n_splats"])
+        moved = C.c_int64(0)
+        _check(self.L.gsr_transform(self.h, None if words is None else words.ctypes.data, 0, C.byref(x) if x is not None else None, C.byref(moved)))
+        return moved.value
+
+    def transform_device(self, x: gsr_xform, mask_ptr) -> int:
+        """gsr_transform from packed uint32 mask words in DEVICE (or pinned) memory: a raw pointer or an object with data_ptr(),
+        ceil(n / 32) words, as select_device writes them; never written.  Waits for the work queued on the stream given to set_stream
+        first -> the splats moved"""
+        ptr = int(mask_ptr.data_ptr()) if hasattr(mask_ptr, "data_ptr") else int(mask_ptr)
+        moved = C.c_int64(0)
+        _check(self.L.gsr_transform(self.h, C.c_void_p(ptr), 1, C.byref(x) if x is not None else None, C.byref(moved)))
+        return moved.value
+
+    def get_transform(self) -> dict:
+        """gsr_get_transform -> {transforms: the calls, moved_last, ms: the last call's stage clock [mask copy, kernel .. sort,
+        repack, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_transform(self.h, C.byref(calls), C.byref(last), ms))
+        return {"transforms": calls.value, "moved_last": last.value, "ms": [float(v) for v in ms]}
 
     def get_removal(self) -> dict:
         """gsr_get_removal -> {removals: calls that removed something, removed_last, ms: the last call's stage clock
@@ -1702,6 +1786,14 @@ class MultiEngine:
         total = C.c_int64(0)
         _check(self.L.gsr_multi_add(self.h, a.n, *a.ptrs(), C.byref(total)))
         return total.value
+
+    def transform(self, x: gsr_xform, mask=None) -> int:
+        """gsr_multi_transform: Engine.transform on every rank, from a host mask -> the splats moved (the ranks agree, or none keeps
+        geometry)"""
+        words = removal_words(mask, self.stats(0)["n_splats"])
+        moved = C.c_int64(0)
+        _check(self.L.gsr_multi_transform(self.h, None if words is None else words.ctypes.data, C.byref(x) if x is not None else None, C.byref(moved)))
+        return moved.value
 
     def read(self, first: int = 0, n=None, names=None):
         """gsr_multi_read: Engine.read of rank 0's copy (the cloud is replicated) -> scenes.Splats"""

@@ -593,6 +593,69 @@ int  gsr_select_eval(const gsr_camera* cam, const float origin[3], const gsr_sel
                      uint8_t* hit_out, float* centre_out /* [n][3] = cx, cy, zw of a selectable splat, else NaN; or NULL */);   /* host, no context, no GPU */
 int  gsr_get_select(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- transform: selected resident splats rotated, scaled, translated on the GPU ---- */
+/* What a mask of gsr_select is for besides hiding and removing: the selected splats are moved, turned and resized where they are
+ * resident -- p' = s R (p - pivot) + pivot + translate -- with their scale, orient and SH coefficients following, and nothing but
+ * the mask crosses the link.  One kernel (k_transform.h) in gsr_update's work shape, then gsr_move's re-order pipeline.
+ * THE MASK has the layout and sense of gsr_remove's mask and gsr_select's output: bit i & 31 of word i >> 5 is upload index i,
+ * ceil(n / 32) words; bits at and behind n are ignored; NULL selects every resident splat.  It may live in host memory
+ * (mask_is_device = 0) or in device / pinned memory (1: checked with its exact size before anything is launched, as the device sources
+ * are -- a bad pointer gives GSR_E_INVALID, never a fault).  It is never written.
+ * gsr_xform_prepare derives the float32 RULE from x, in double, each entry rounded to float once: the quaternion normalised, R, A = s R,
+ * t = pivot + translate - (s R) pivot, and the SH band matrices D_l (l = 1, 2, 3): with Y_l(d) the vector of the 2l + 1 polynomials
+ * the shader multiplies band l's coefficients with (constants and signs included) at a unit direction d, D_l is the matrix with
+ * Y_l(R d)^T D_l = Y_l(d)^T for every d -- a rotated splat shows, from the rotated direction, the colour it showed before.  The
+ * identity is not special-cased (and comes out exact).  GSR_E_INVALID: a NULL argument, a non-finite field, scale <= 0, a zero
+ * quaternion, reserved_ != 0.
+ * THE ARITHMETIC per selected splat (one set of functions, evaluated by the kernel and by gsr_transform_eval; x86 and gfx950 agree bit
+ * for bit; every multiply-add one fmaf; the normative statement of each chain heads csrc/k_transform.h):
+ *   P       P'.r = fmaf(A[3r], x, fmaf(A[3r+1], y, fmaf(A[3r+2], z, t[r]))) on the raw position bits
+ *   scale   each half: f2h(s * h2f(scale_k))
+ *   orient  f2h of the quaternion product q (x) orient, the transform first, the resident quaternion as it is (unnormalised, as the
+ *           vertex stage uses it).  For a non-unit orient this is what a Transform SOP does to the attribute, not an exact rotation of
+ *           the matrix the vertex stage forms from it.
+ *   SH      per channel and band, c'_m = f2h(sum_k D_l[m][k] h2f(c_k)), a chain of fmaf with k ascending; coefficient order sh[0..2],
+ *           sh[3..7], sh[8..14]; slot 15 of a row, Cd and alpha stay; a cloud without SH has no SH step.
+ * An unselected splat keeps every bit.  NaN and infinite inputs follow the arithmetic; a half that comes out NaN is NaN on both sides,
+ * sign and payload unspecified.
+ * gsr_transform_eval: the same on the host, in place, with no context and no GPU: n rows in gsr_upload's layout (shx, shy, shz all
+ * three or none), mask as above (host).  CONTRACT of gsr_transform: after GSR_OK the resident geometry -- the planes, the colour rows,
+ * the cluster bounds, the storage order -- is bit for bit what a fresh context holds after gsr_upload of what gsr_read returned
+ * before the call, passed through gsr_transform_eval, with the same options, origin and SH presence; so is every later frame.
+ * A transform invalidates what a move does (depth horizons, cached depth orders, policies).  A visibility in force is evaluated at the
+ * new positions; the true alphas and its mask are kept.  A mask with no bit set below n changes, invalidates and writes nothing.
+ * *n_moved (may be NULL): the bits set below n.  gsr_stats.uploads, moves and move_ms are not touched: gsr_get_transform has the calls
+ * (one with an empty selection counts, with 0 moved and the clock left as it was), the last count and the clock ms[4], laid out as gsr_get_removal's: [0] the mask over the link
+ * [1] the kernel .. the sort of the storage order   [2] the planes into the new order   [3] wall clock of the call.
+ * ORDERING: synchronous; waits for the public stream (gsr_set_stream) and for the frames in flight, as the device-source verbs do.
+ * MEMORY: the second copy of the planes, as a move keeps it.  Everything is allocated before the first write: GSR_E_OOM leaves the
+ * context untouched; a HIP failure after the first write leaves no geometry, as with gsr_move.
+ * GSR_E_INVALID, context untouched: NULL ctx or x; what gsr_xform_prepare refuses; no geometry; an upload in progress; a device mask
+ * that fails the check.
+ * Out of scope: non-uniform scale, shear and reflection (the covariance no longer factors into scale and orient); a shortcut for
+ * pure translations; transforming the crop volumes along; the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for
+ * gsr_multi_transform; an asynchronous form; a per-splat transform array. */
+typedef struct gsr_xform {
+    float rotate[4];     /* quaternion (x, y, z, w), orient's order; need not be normalised */
+    float scale;         /* uniform, finite, > 0 */
+    float translate[3];
+    float pivot[3];      /* upload space */
+    int32_t reserved_;   /* 0 */
+} gsr_xform;
+typedef struct gsr_xform_rule {   /* what gsr_xform_prepare derives; float32; 100 dwords */
+    float A[9];          /* fl32(s * R), rows */
+    float t[3];          /* fl32(pivot + translate - (s R) pivot), formed in double */
+    float s;             /* fl32(scale) */
+    float q[4];          /* fl32 of the quaternion normalised in double, (i, j, k, r) */
+    float D1[9], D2[25], D3[49];   /* SH band matrices, rows */
+} gsr_xform_rule;
+int  gsr_xform_prepare(const gsr_xform* x, gsr_xform_rule* rule);             /* host, no context, no GPU */
+int  gsr_transform_eval(const gsr_xform* x, int64_t n, const uint32_t* mask /* NULL: all */,
+                        float* P, uint16_t* scale, uint16_t* orient,
+                        uint16_t* shx, uint16_t* shy, uint16_t* shz);         /* host, in place, no GPU */
+int  gsr_transform(gsr_context* ctx, const uint32_t* mask, int mask_is_device, const gsr_xform* x, int64_t* n_moved);
+int  gsr_get_transform(gsr_context* ctx, int64_t* calls, int64_t* moved_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -707,6 +770,9 @@ int  gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_array
 /* gsr_select on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
 int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host,
                       int64_t* n_hit, int64_t* n_set);
+/* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
+ * rule: if the ranks do not agree on the count, or a rank fails after its first write, the verb fails and NO rank keeps geometry. */
+int  gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
