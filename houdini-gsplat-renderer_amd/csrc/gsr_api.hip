@@ -55,6 +55,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_read.h"
 #include "k_select.h"
 #include "k_transform.h"
+#include "k_grade.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -374,6 +375,9 @@ struct gsr_context {
     PinnedMem<uint32_t> xf_h_count;
     int64_t xf_calls = 0, xf_last = 0;
     double xf_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // gsr_grade (k_grade.h): what gsr_get_grade reports (the mask's bit count arrives in xf_h_count)
+    int64_t gr_calls = 0, gr_last = 0;
+    double gr_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }

@@ -722,6 +722,29 @@ extern "C" int gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, cons
     return GSR_OK;
 }
 
+// ... and graded on every rank: each bakes the rule into its own replica, in place.  gsr_multi_transform's agreement rule.
+extern "C" int gsr_multi_grade(gsr_multi* m, const uint32_t* mask_host, const gsr_grade_rule* rule, int64_t* n_graded)
+{
+    if (!m || !rule) return fail(GSR_E_INVALID, "gsr_multi_grade: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_grade: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> graded((size_t)G, -1);
+    int64_t* const gp = graded.data();
+    rc = for_each_rank(m, [=](int g) { return gsr_grade(m->ctx[g], mask_host, 0, rule, gp + g); });
+    bool any_done = false, same = rc == GSR_OK;
+    for (int g = 0; g < G; ++g) any_done = any_done || graded[(size_t)g] >= 0;
+    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
+    for (int g = 1; g < G && same; ++g) same = graded[(size_t)g] == graded[0];
+    if (!same) {
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_grade: the ranks do not agree on the splats graded: the geometry is dropped on all of them");
+    }
+    if (n_graded) *n_graded = graded[0];
+    return GSR_OK;
+}
+
 // ---- balanced bands ------------------------------------------------------------------------------
 extern "C" int gsr_debug_balance_rows(const uint32_t* row_work, int tiles_y, int count, const int32_t* cur_first, int min_gain_permille,
                                       int32_t* out_first)

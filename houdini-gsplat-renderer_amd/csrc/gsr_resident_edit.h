@@ -1,5 +1,5 @@
-// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10): gsr_update, gsr_move, the
-// device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_transform.  Host code only; included once, at the end of gsr_api.hip, which has the
+// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10, 3.11): gsr_update, gsr_move, the
+// device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_transform, gsr_grade.  Host code only; included once, at the end of gsr_api.hip, which has the
 // context, the frame slots, the upload arena (ensure_stage, ensure_up_events, stage_host_rows), the ordering of an upload (position_box,
 // morton_order), new_cloud_state / drop_geometry, and the <SH> launches of k_update, k_update_f32 and k_repack (launch_update,
 // queue_repack).
@@ -1225,5 +1225,176 @@ extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_d
     c->xf_calls += 1;
     c->xf_last = (int64_t)count;
     if (n_moved) *n_moved = (int64_t)count;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Grade (k_grade.h): the colour and the opacity of selected resident splats changed where they are.  An update whose
+// new Cd, SH and alpha are formed on the GPU from the resident ones: k_grade in the place of k_update, then gsr_update's invalidation.
+// No position changes: the storage order, the cluster bounds and the spare planes are not touched.
+static_assert(sizeof(gsr_grade_rule) == sizeof(GsrGradeRule) && offsetof(gsr_grade_rule, M) == offsetof(GsrGradeRule, M) &&
+              offsetof(gsr_grade_rule, b) == offsetof(GsrGradeRule, b) && offsetof(gsr_grade_rule, ag) == offsetof(GsrGradeRule, ag) &&
+              offsetof(gsr_grade_rule, ab) == offsetof(GsrGradeRule, ab) && offsetof(gsr_grade_rule, flags) == offsetof(GsrGradeRule, flags) &&
+              GSR_GRADE_COLOUR == GSR_GRADEF_COLOUR && GSR_GRADE_ALPHA == GSR_GRADEF_ALPHA, "gsr_grade_rule is the kernel's rule");
+
+// what is wrong with the caller's rule (NULL: nothing)
+static const char* grade_rule_error(const gsr_grade_rule* r)
+{
+    const float* f = r->M;             // M[9], b[3], ag, ab: fourteen floats in a row
+    static_assert(offsetof(gsr_grade_rule, flags) == 14 * sizeof(float), "gsr_grade_rule begins with fourteen floats");
+    for (int k = 0; k < 14; ++k) if (!std::isfinite(f[k])) return "a float of the rule is not finite";
+    if (r->flags & ~(GSR_GRADE_COLOUR | GSR_GRADE_ALPHA)) return "unknown flag bit";
+    return nullptr;
+}
+
+extern "C" int gsr_grade_prepare(const gsr_grade_params* p, gsr_grade_rule* rule)
+{
+    if (!p || !rule) return set_err(GSR_E_INVALID, "gsr_grade_prepare: NULL argument");
+    const float* f = &p->exposure;     // exposure, gain[3], saturation, contrast, pivot, offset[3], alpha_gain, alpha_offset: twelve floats in a row
+    static_assert(sizeof(gsr_grade_params) == 12 * sizeof(float) && offsetof(gsr_grade_params, alpha_offset) == 11 * sizeof(float), "gsr_grade_params is twelve floats");
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(f[k])) return set_err(GSR_E_INVALID, "gsr_grade_prepare: a field is not finite");
+    // c1 = 2^exposure gain o c;  c2 = L + saturation (c1 - L), L = w . c1;  c3 = contrast (c2 - pivot) + pivot + offset -- in double
+    const double w[3] = {0.2126, 0.7152, 0.0722};
+    const double ex = std::exp2((double)p->exposure), sat = p->saturation, con = p->contrast;
+    gsr_grade_rule r{};
+    for (int row = 0; row < 3; ++row) {
+        for (int k = 0; k < 3; ++k) r.M[3 * row + k] = (float)(con * ((row == k ? sat : 0.0) + (1.0 - sat) * w[k]) * (ex * (double)p->gain[k]));
+        r.b[row] = (float)((double)p->pivot * (1.0 - con) + (double)p->offset[row]);
+    }
+    r.ag = p->alpha_gain;
+    r.ab = p->alpha_offset;
+    bool identity = true;
+    for (int k = 0; k < 9; ++k) identity = identity && r.M[k] == ((k % 4 == 0) ? 1.0f : 0.0f);
+    for (int k = 0; k < 3; ++k) identity = identity && r.b[k] == 0.0f;
+    r.flags = (identity ? 0u : GSR_GRADE_COLOUR) | ((r.ag == 1.0f && r.ab == 0.0f) ? 0u : GSR_GRADE_ALPHA);
+    const char* bad = grade_rule_error(&r);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_grade_prepare: the parameters overflow float32: %s", bad);
+    *rule = r;
+    return GSR_OK;
+}
+
+static GsrGradeRule grade_kernel_rule(const gsr_grade_rule* rule)
+{
+    GsrGradeRule g;
+    std::memcpy(&g, rule, sizeof(g));
+    return g;
+}
+
+extern "C" int gsr_grade_eval(const gsr_grade_rule* rule, int64_t n, const uint32_t* mask, int has_sh, uint16_t* Cd, float* alpha,
+                              uint16_t* shx, uint16_t* shy, uint16_t* shz)
+{
+    if (!rule) return set_err(GSR_E_INVALID, "gsr_grade_eval: rule is NULL");
+    const char* bad = grade_rule_error(rule);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_grade_eval: %s", bad);
+    const bool colour = rule->flags & GSR_GRADE_COLOUR, alph = rule->flags & GSR_GRADE_ALPHA;
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && ((colour && !Cd) || (alph && !alpha) || (colour && has_sh && (!shx || !shy || !shz)))))
+        return set_err(GSR_E_INVALID, "gsr_grade_eval: bad argument");
+    const GsrGradeRule g = grade_kernel_rule(rule);
+    for (int64_t i = 0; i < n; ++i) {
+        if (mask && !((mask[i >> 5] >> (i & 31)) & 1u)) continue;
+        if (alph) alpha[i] = gsr_grade_alpha(g, alpha[i]);
+        if (!colour) continue;
+        uint16_t* c = Cd + 3 * i;
+        const uint16_t cr = c[0], cg = c[1], cb = c[2];
+        for (int r = 0; r < 3; ++r) c[r] = gsr_grade_half(g, r, true, cr, cg, cb);
+        if (!has_sh) continue;
+        uint16_t* const row[3] = {shx + 16 * i, shy + 16 * i, shz + 16 * i};
+        for (int s = 0; s < 15; ++s) {                 // (slot 15 stays)
+            const uint16_t hr = row[0][s], hg = row[1][s], hb = row[2][s];
+            for (int r = 0; r < 3; ++r) row[r][s] = gsr_grade_half(g, r, false, hr, hg, hb);
+        }
+    }
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_grade(gsr_context* c, int64_t* calls, int64_t* graded_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_grade: ctx is NULL");
+    if (calls) *calls = c->gr_calls;
+    if (graded_last) *graded_last = c->gr_last;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->gr_ms[k];
+    return GSR_OK;
+}
+
+extern "C" int gsr_grade(gsr_context* c, const uint32_t* mask, int mask_is_device, const gsr_grade_rule* rule, int64_t* n_graded)
+{
+    const char* const who = "gsr_grade";
+    if (!c || !rule) return set_err(GSR_E_INVALID, "gsr_grade: NULL argument");
+    const char* bad = grade_rule_error(rule);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_grade: %s", bad);
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const double t_begin = up_now_ms();
+    const uint32_t n = c->n;
+    const size_t words = ((size_t)n + 31) / 32;
+    HIP_TRY(hipSetDevice(c->device));
+    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    if ((rc = sync_all(c))) return rc;      // the public stream (a select queued there has written the mask), and no in-place write under a frame in flight
+    auto nothing = [&]() {                  // empty work: a call that changes, invalidates and writes nothing
+        c->gr_calls += 1; c->gr_last = 0;
+        if (n_graded) *n_graded = 0;
+        return GSR_OK;
+    };
+    if (n == 0 || !rule->flags) return nothing();
+    const GsrGradeRule g = grade_kernel_rule(rule);
+    const bool alph = g.flags & GSR_GRADEF_ALPHA, vis = c->vis_on && alph;
+    // ---- everything the call needs, before the first write: the arena (the count, a host mask's copy), the inverse of the storage
+    // order, the clock's events, the pinned word of the count, the visibility's buffers
+    const size_t oCount = 0, oMask = 256;
+    hipStream_t us = c->slot[0].own;
+    if ((rc = ensure_stage(c, oMask + (mask && !mask_is_device ? pad256(words * 4) : 0))) || (rc = ensure_inverse_perm(c)) ||
+        (rc = ensure_up_events(c, 2, who, true)) || (vis && (rc = vis_ensure_buffers(c)))) return rc;
+    if (!c->xf_h_count && c->xf_h_count.alloc(1, 0)) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "gsr_grade: no pinned host memory for the count");
+    }
+    // ---- a host mask into the arena (no resident byte), then the count: a mask with no bit set below n ends the call here
+    const uint32_t* dmask = mask;
+    uint32_t count = n;
+    if (mask && !mask_is_device) {
+        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
+        HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
+        HIP_TRY(hipStreamSynchronize(us));             // the caller's mask may be freed on return
+        dmask = staged;
+    }
+    if (dmask) {
+        uint32_t* const dcount = reinterpret_cast<uint32_t*>(c->stage + oCount);
+        HIP_TRY(hipMemsetAsync(dcount, 0, 4, us));
+        hipLaunchKernelGGL(k_transform_count, dim3(div_up((uint32_t)words, 256)), dim3(256), 0, us, n, dmask, dcount);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c->xf_h_count, dcount, 4, hipMemcpyDeviceToHost, us));
+        HIP_TRY(hipStreamSynchronize(us));
+        count = c->xf_h_count[0];
+        if (count > n) return set_err(GSR_E_HIP, "gsr_grade: the reduction counted %u bits below %u", count, n);
+    }
+    if (count == 0) return nothing();
+    const double t_counted = up_now_ms();
+    // ---- the kernel, in place; with a visibility in force and a new opacity, the rule in force over the graded true alphas (no
+    // capture: the hidden splats' resident zeros never reach alpha0); then gsr_update's invalidation
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    hipError_t e = hipEventRecord(c->up_ev[0], us);
+    double t_kernel = t_counted;
+    if (e == hipSuccess) {
+        launch_sh(c->has_sh, [&](auto sh) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grade<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, dmask, g, inv,
+                               c->geoA, c->col, c->has_sh ? c->colrow : (uint4*)nullptr, vis ? c->alpha0 : (float*)nullptr);
+        });
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    t_kernel = up_now_ms();
+    if (e == hipSuccess && vis) e = vis_apply(c, us, 0u, 0u, true, c->vis, c->vis_mask, nullptr);
+    const double t_vis = up_now_ms();
+    e = after_update(c, alph, us, e);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_grade: %s", hipGetErrorString(e));
+    float ms = 0.0f;
+    c->gr_ms[0] = t_counted - t_begin;
+    c->gr_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
+    c->gr_ms[2] = vis ? t_vis - t_kernel : 0.0;
+    c->gr_ms[3] = up_now_ms() - t_begin;
+    c->gr_calls += 1;
+    c->gr_last = (int64_t)count;
+    if (n_graded) *n_graded = (int64_t)count;
     return GSR_OK;
 }

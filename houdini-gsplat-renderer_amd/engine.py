@@ -138,6 +138,20 @@ class gsr_xform_rule(C.Structure):
                 ("D1", C.c_float * 9), ("D2", C.c_float * 25), ("D3", C.c_float * 49)]
 
 
+class gsr_grade_params(C.Structure):
+    """include/gsplat_hip.h: what a user turns to grade a selection (grade_params() has the neutral defaults)"""
+    _fields_ = [("exposure", C.c_float), ("gain", C.c_float * 3), ("saturation", C.c_float), ("contrast", C.c_float), ("pivot", C.c_float),
+                ("offset", C.c_float * 3), ("alpha_gain", C.c_float), ("alpha_offset", C.c_float)]
+
+
+class gsr_grade_rule(C.Structure):
+    """include/gsplat_hip.h: what gsr_grade evaluates -- c' = M c + b, alpha' = clamp(ag alpha + ab, 0, 1), and which of the two run"""
+    _fields_ = [("M", C.c_float * 9), ("b", C.c_float * 3), ("ag", C.c_float), ("ab", C.c_float), ("flags", C.c_uint32)]
+
+
+GRADE_COLOUR, GRADE_ALPHA = 1, 2
+
+
 class gsplat_attrs(C.Structure):
     _fields_ = [("count", C.c_int64), ("P", C.c_void_p), ("Cd", C.c_void_p), ("opacity", C.c_void_p), ("Alpha", C.c_void_p),
                 ("scale", C.c_void_p), ("orient", C.c_void_p), ("sh_coefficients", C.c_void_p),
@@ -213,6 +227,7 @@ C_ABI_SYMBOLS = [
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
+    "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan",
 ]
 
@@ -317,6 +332,11 @@ def load_library() -> C.CDLL:
     L.gsr_transform.argtypes = [vp, vp, i32, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
     L.gsr_get_transform.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_transform.argtypes = [vp, vp, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
+    L.gsr_grade_prepare.argtypes = [C.POINTER(gsr_grade_params), C.POINTER(gsr_grade_rule)]
+    L.gsr_grade_eval.argtypes = [C.POINTER(gsr_grade_rule), i64, vp, i32] + [vp] * 5
+    L.gsr_grade.argtypes = [vp, vp, i32, C.POINTER(gsr_grade_rule), C.POINTER(C.c_int64)]
+    L.gsr_get_grade.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_grade.argtypes = [vp, vp, C.POINTER(gsr_grade_rule), C.POINTER(C.c_int64)]
     L.gsplat_renderer_update_attributes.argtypes = [vp, C.c_char_p] + [vp] * 7 + [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsplat_renderer_row_array.argtypes = [vp, C.c_char_p, i32]
     L.gsplat_renderer_row_array.restype = vp
@@ -747,6 +767,70 @@ def transform_eval(x: gsr_xform, splats, mask=None):
     return Splats(P, a.Cd.copy(), a.alpha.copy(), scale, orient, *sh)
 
 
+def grade_params(exposure: float = 0.0, gain=(1.0, 1.0, 1.0), saturation: float = 1.0, contrast: float = 1.0, pivot: float = 0.5,
+                 offset=(0.0, 0.0, 0.0), alpha_gain: float = 1.0, alpha_offset: float = 0.0) -> gsr_grade_params:
+    """gsr_grade_params with the neutral defaults: colour x 2^exposure x gain per channel, saturation about the Rec.709 luma,
+    contrast about pivot, offset added last; opacity -> clamp(alpha_gain alpha + alpha_offset, 0, 1).  What the fields may hold is the
+    library's to refuse (grade_prepare)."""
+    p = gsr_grade_params()
+    p.exposure, p.saturation, p.contrast, p.pivot = float(exposure), float(saturation), float(contrast), float(pivot)
+    p.gain[:] = [float(v) for v in np.asarray(gain, dtype=np.float32).reshape(3)]
+    p.offset[:] = [float(v) for v in np.asarray(offset, dtype=np.float32).reshape(3)]
+    p.alpha_gain, p.alpha_offset = float(alpha_gain), float(alpha_offset)
+    return p
+
+
+def _grade_rule_struct(rule) -> gsr_grade_rule:
+    """a gsr_grade_rule as it is, or the struct of a dict grade_prepare / grade_rule returned (its arrays may have been edited)"""
+    if rule is None or isinstance(rule, gsr_grade_rule):
+        return rule
+    r = gsr_grade_rule()
+    r.M[:] = [float(v) for v in np.asarray(rule["M"], dtype=np.float32).reshape(9)]
+    r.b[:] = [float(v) for v in np.asarray(rule["b"], dtype=np.float32).reshape(3)]
+    r.ag, r.ab, r.flags = float(rule["ag"]), float(rule["ab"]), int(rule["flags"])
+    return r
+
+
+def _grade_rule_dict(r: gsr_grade_rule) -> dict:
+    return {"M": np.array(list(r.M), dtype=np.float32).reshape(3, 3), "b": np.array(list(r.b), dtype=np.float32),
+            "ag": np.float32(r.ag), "ab": np.float32(r.ab), "flags": int(r.flags)}
+
+
+def grade_prepare(params: gsr_grade_params) -> dict:
+    """gsr_grade_prepare (host only, no GPU): the float32 rule of a grade -> {M (3, 3), b (3,), ag, ab, flags: GRADE_COLOUR |
+    GRADE_ALPHA, which of the two steps run}; what Engine.grade and grade_eval take"""
+    r = gsr_grade_rule()
+    _check(load_library().gsr_grade_prepare(C.byref(params) if params is not None else None, C.byref(r)))
+    return _grade_rule_dict(r)
+
+
+def grade_rule(M, b=(0.0, 0.0, 0.0), alpha_gain: float = 1.0, alpha_offset: float = 0.0) -> dict:
+    """the rule of a caller's own colour matrix (rows; a colour-space change, a hue rotation, a channel swap): c' = M c + b, rounded to
+    float32; the colour step runs unless M is the identity and b zero, the opacity step unless (alpha_gain, alpha_offset) == (1, 0)"""
+    r = gsr_grade_rule()
+    r.M[:] = [float(v) for v in np.asarray(M, dtype=np.float32).reshape(9)]
+    r.b[:] = [float(v) for v in np.asarray(b, dtype=np.float32).reshape(3)]
+    r.ag, r.ab = float(alpha_gain), float(alpha_offset)
+    identity = list(r.M) == [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0] and list(r.b) == [0.0, 0.0, 0.0]
+    r.flags = (0 if identity else GRADE_COLOUR) | (0 if (r.ag == 1.0 and r.ab == 0.0) else GRADE_ALPHA)
+    return _grade_rule_dict(r)
+
+
+def grade_eval(rule, splats, mask=None):
+    """gsr_grade_eval (host only, no GPU): the arrays of a Splats-like object with the rule (grade_prepare / grade_rule, or a
+    gsr_grade_rule) baked into the rows the mask selects (a boolean array over the splats or packed uint32 words; None: every row),
+    through the functions the kernel evaluates -> a new scenes.Splats; P, scale and orient are copies, the input is not written"""
+    from .scenes import Splats
+    a = _Arrays(splats)
+    Cd, alpha = a.Cd.copy(), a.alpha.copy()
+    sh = [None if v is None else v.copy() for v in (a.shx, a.shy, a.shz)]
+    words = removal_words(mask, a.n)
+    r = _grade_rule_struct(rule)
+    _check(load_library().gsr_grade_eval(C.byref(r) if r is not None else None, a.n, None if words is None else words.ctypes.data,
+                                         1 if sh[0] is not None else 0, _ptr(Cd), _ptr(alpha), *[_ptr(v) for v in sh]))
+    return Splats(a.P.copy(), Cd, alpha, a.scale.copy(), a.orient.copy(), *sh)
+
+
 def add_capacity(cap: int, need: int) -> int:
     """gsr_add_capacity (host only, no GPU): the capacity a context of capacity cap has after an add that brings it to need splats --
     cap while need fits, else need + need // 4, clamped to 0x7fffffff"""
@@ -1127,6 +1211,35 @@ class Engine:
         calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
         _check(self.L.gsr_get_transform(self.h, C.byref(calls), C.byref(last), ms))
         return {"transforms": calls.value, "moved_last": last.value, "ms": [float(v) for v in ms]}
+
+    # ---- grade: the colour and the opacity of selected resident splats (include/gsplat_hip.h, "grade")
+    def grade(self, rule, mask=None) -> int:
+        """gsr_grade from a HOST mask: the rule (grade_prepare / grade_rule, or a gsr_grade_rule) is baked into the Cd, the SH rows and
+        the opacity of the resident splats whose mask entry is True (a boolean array over the resident splats in upload order, or the
+        packed uint32 words; None: every splat), in place on the GPU, bit for bit a fresh upload of grade_eval of what read returns
+        -> the splats graded"""
+        words = removal_words(mask, self.stats()["n_splats"])
+        r = _grade_rule_struct(rule)
+        graded = C.c_int64(0)
+        _check(self.L.gsr_grade(self.h, None if words is None else words.ctypes.data, 0, C.byref(r) if r is not None else None, C.byref(graded)))
+        return graded.value
+
+    def grade_device(self, rule, mask_ptr) -> int:
+        """gsr_grade from packed uint32 mask words in DEVICE (or pinned) memory: a raw pointer or an object with data_ptr(),
+        ceil(n / 32) words, as select_device writes them; never written.  Waits for the work queued on the stream given to set_stream
+        first -> the splats graded"""
+        ptr = int(mask_ptr.data_ptr()) if hasattr(mask_ptr, "data_ptr") else int(mask_ptr)
+        r = _grade_rule_struct(rule)
+        graded = C.c_int64(0)
+        _check(self.L.gsr_grade(self.h, C.c_void_p(ptr), 1, C.byref(r) if r is not None else None, C.byref(graded)))
+        return graded.value
+
+    def get_grade(self) -> dict:
+        """gsr_get_grade -> {grades: the calls, graded_last, ms: the stage clock of the last call that wrote [mask copy and count,
+        kernel, visibility, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_grade(self.h, C.byref(calls), C.byref(last), ms))
+        return {"grades": calls.value, "graded_last": last.value, "ms": [float(v) for v in ms]}
 
     def get_removal(self) -> dict:
         """gsr_get_removal -> {removals: calls that removed something, removed_last, ms: the last call's stage clock
@@ -1794,6 +1907,15 @@ class MultiEngine:
         moved = C.c_int64(0)
         _check(self.L.gsr_multi_transform(self.h, None if words is None else words.ctypes.data, C.byref(x) if x is not None else None, C.byref(moved)))
         return moved.value
+
+    def grade(self, rule, mask=None) -> int:
+        """gsr_multi_grade: Engine.grade on every rank, from a host mask -> the splats graded (the ranks agree, or none keeps
+        geometry)"""
+        words = removal_words(mask, self.stats(0)["n_splats"])
+        r = _grade_rule_struct(rule)
+        graded = C.c_int64(0)
+        _check(self.L.gsr_multi_grade(self.h, None if words is None else words.ctypes.data, C.byref(r) if r is not None else None, C.byref(graded)))
+        return graded.value
 
     def read(self, first: int = 0, n=None, names=None):
         """gsr_multi_read: Engine.read of rank 0's copy (the cloud is replicated) -> scenes.Splats"""

@@ -656,6 +656,70 @@ int  gsr_transform_eval(const gsr_xform* x, int64_t n, const uint32_t* mask /* N
 int  gsr_transform(gsr_context* ctx, const uint32_t* mask, int mask_is_device, const gsr_xform* x, int64_t* n_moved);
 int  gsr_get_transform(gsr_context* ctx, int64_t* calls, int64_t* moved_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- grade: the colour and the opacity of selected resident splats changed on the GPU ---- */
+/* The look of a selection -- exposure, tint / white balance, saturation, contrast, brightness, transparency -- baked into the
+ * resident splats a mask selects, with nothing but the mask crossing the link.  The vertex stage forms max(Cd + sum_k Y_k(d) sh_k, 0)
+ * per channel, which is linear in (Cd, sh_1 .. sh_15) in front of the clamp: an affine colour map c' = M c + b is therefore baked
+ * EXACTLY, from every view direction, by Cd' = M Cd + b and sh_k' = M sh_k for every coefficient.  One kernel (k_grade.h) in
+ * gsr_update's work shape, in place: no position changes, so the storage order and the cluster bounds stay.
+ * THE MASK is gsr_transform's: bit i & 31 of word i >> 5 is upload index i, ceil(n / 32) words, bits at and behind n ignored, NULL
+ * selects every resident splat; host memory (mask_is_device = 0) or device / pinned memory (1: checked with its exact size before
+ * anything is launched -- a bad pointer gives GSR_E_INVALID, never a fault).  It is never written.
+ * gsr_grade TAKES THE RULE, not the parameters: a caller with a colour matrix of its own (a colour-space change, a hue rotation, a
+ * channel swap) fills M, b and the flags itself.  gsr_grade_prepare composes, in double, each entry rounded to float32 once:
+ *   c1 = 2^exposure * gain o c;   c2 = L + saturation (c1 - L), L = w . c1, w = (0.2126, 0.7152, 0.0722);
+ *   c3 = contrast (c2 - pivot) + pivot + offset
+ * i.e. M[r][k] = contrast (saturation [r == k] + (1 - saturation) w_k) 2^exposure gain_k, b[r] = pivot (1 - contrast) + offset[r],
+ * ag = alpha_gain, ab = alpha_offset.  It sets GSR_GRADE_COLOUR unless the rounded M is the identity and b is zero, GSR_GRADE_ALPHA
+ * unless (ag, ab) == (1, 0).  GSR_E_INVALID: a NULL argument, a field that is not finite, an entry of the rule that does not round to
+ * a finite float32.
+ * THE ARITHMETIC per selected splat (one set of functions, evaluated by the kernel and by gsr_grade_eval; x86 and gfx950 agree bit for
+ * bit; the normative statement heads csrc/k_grade.h), (R, G, B) the three halves of one coefficient, r the channel that comes out:
+ *   Cd      f2h(fmaf(M[3r], R, fmaf(M[3r+1], G, fmaf(M[3r+2], B, b[r]))))
+ *   SH      coefficients 1..15: f2h(fmaf(M[3r], R, fmaf(M[3r+1], G, M[3r+2] * B))); slot 15 of a row stays; no SH step without SH
+ *   alpha   min(max(fmaf(ag, alpha, ab), 0), 1) on the TRUE alpha; a NaN becomes 0
+ * A step whose flag is clear does not run at all, and a rule without flags is a no-op.  The colour step under the identity is NOT one:
+ * a -0 half becomes +0 and an infinite half turns its coefficient NaN -- which is why gsr_grade_prepare clears the flag.  An unselected
+ * splat keeps every bit.  Non-finite halves follow the arithmetic; a half that comes out NaN is NaN on both sides.
+ * gsr_grade_eval: the same on the host, in place, with no context and no GPU: n rows in gsr_upload's layout; has_sh = 0: shx, shy, shz
+ * are not looked at.  CONTRACT of gsr_grade: after GSR_OK the resident geometry is bit for bit what a fresh context holds after
+ * gsr_upload of what gsr_read returned before the call, passed through gsr_grade_eval, with the same options, origin, SH presence
+ * and visibility; so is every later frame.
+ * INVALIDATION is gsr_update's: a colour-only grade drops the cached depth orders and keeps horizons, prefixes and policies; one
+ * with GSR_GRADE_ALPHA is a change of shape, like new alphas.  A VISIBILITY in force: the true alphas kept aside are graded, and the
+ * rule in force is applied again -- a hidden splat stays +0.0f with its graded alpha aside, and gsr_read returns the graded alphas.
+ * EMPTY WORK -- no bit set below n, a rule without flags, no splat resident -- changes, invalidates and writes nothing, and counts as
+ * a call.  *n_graded (may be NULL): the bits set below n; 0 for a rule without flags.  gsr_get_grade has the calls that passed their
+ * refusals, the last count and the clock ms[4] of the last call that wrote: [0] the mask over the link and its count  [1] the kernel
+ * (HIP events)  [2] the visibility rule applied again  [3] wall clock of the call.
+ * ORDERING: synchronous; waits for the public stream (gsr_set_stream) and for the frames in flight.  MEMORY: the staging arena (the
+ * mask's copy); no spare planes.  GSR_E_INVALID, context untouched: NULL ctx or rule; a float of the rule that is not finite; an
+ * unknown flag bit; no geometry; an upload in progress; a device mask that fails the check.
+ * Out of scope: maps that are not affine in colour (gamma, curves, hue selection by range); per-splat rules; the GSplatRenderer shim
+ * and the HDK glue; gsr_comm_*; a device mask for gsr_multi_grade; an asynchronous form; undo (a caller can invert an invertible M
+ * itself, but the roundings to halves do not invert). */
+#define GSR_GRADE_COLOUR 1u
+#define GSR_GRADE_ALPHA  2u
+typedef struct gsr_grade_params {      /* what a user turns; every field finite, else GSR_E_INVALID */
+    float exposure;                    /* stops: colour x 2^exposure                    (neutral 0) */
+    float gain[3];                     /* tint / white balance, per channel             (neutral 1,1,1) */
+    float saturation;                  /* 0 = grey, 1 = as is, > 1 more; Rec.709 luma weights (0.2126, 0.7152, 0.0722) */
+    float contrast, pivot;             /* c -> contrast (c - pivot) + pivot             (neutral 1, any pivot) */
+    float offset[3];                   /* added last: brightness / lift                 (neutral 0,0,0) */
+    float alpha_gain, alpha_offset;    /* opacity -> clamp(alpha_gain * alpha + alpha_offset, 0, 1)   (neutral 1, 0) */
+} gsr_grade_params;
+typedef struct gsr_grade_rule {        /* what the kernel evaluates: 15 dwords */
+    float M[9];                        /* rows */
+    float b[3];
+    float ag, ab;
+    uint32_t flags;                    /* GSR_GRADE_COLOUR | GSR_GRADE_ALPHA: which of the two steps run */
+} gsr_grade_rule;
+int  gsr_grade_prepare(const gsr_grade_params* p, gsr_grade_rule* rule);          /* host, no context, no GPU */
+int  gsr_grade_eval(const gsr_grade_rule* rule, int64_t n, const uint32_t* mask /* NULL: all */, int has_sh,
+                    uint16_t* Cd, float* alpha, uint16_t* shx, uint16_t* shy, uint16_t* shz);   /* host, in place, no GPU */
+int  gsr_grade(gsr_context* ctx, const uint32_t* mask, int mask_is_device, const gsr_grade_rule* rule, int64_t* n_graded);
+int  gsr_get_grade(gsr_context* ctx, int64_t* calls, int64_t* graded_last, double ms[4]);      /* any pointer may be NULL */
+
 /* ---- multi-GPU: tile-row shard ------------------------------------------ */
 /* This context renders only the tile rows of shard `index` of `count`: rows r with r % count == index (layout 0,
  * interleaved: balances any scene) or the contiguous band [index*rpb, (index+1)*rpb), rpb = ceil(tile rows / count)
@@ -773,6 +837,9 @@ int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_regi
 /* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
  * rule: if the ranks do not agree on the count, or a rank fails after its first write, the verb fails and NO rank keeps geometry. */
 int  gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved);
+/* gsr_grade on every rank's replica, after the same synchronisation, from a HOST mask (NULL: every splat), under the same agreement
+ * rule: ranks that do not agree on the count, or a rank that fails after its first write, and NO rank keeps geometry. */
+int  gsr_multi_grade(gsr_multi* m, const uint32_t* mask_host, const gsr_grade_rule* rule, int64_t* n_graded);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
