@@ -2,7 +2,7 @@
 // per-frame kernel pipeline and the C ABI declared in include/gsplat_hip.h.
 // (The verbs that edit the resident cloud without a re-upload are in gsr_resident_edit.h, included at the end; the kernels that
 // write, edit and read the resident layout -- once per geometry change, not per frame -- in k_resident.h, k_visibility.h, k_remove.h,
-// k_add.h and k_read.h.  The debug read-backs and sort doors are in gsr_debug_read.h, included in front of the edits.)
+// k_add.h, k_read.h and k_copy.h.  The debug read-backs and sort doors are in gsr_debug_read.h, included in front of the edits.)
 // What the context, its frame slots and an edit in progress allocate is held by the handles of gsr_host_buffers.h: a member that owns
 // is a handle, a raw pointer never owns, and a buffer that grows carries its capacity (DevVec; TileSet, WirePair and MortonScratch
 // where several share one).  There is no free list: gsr_destroy deletes the context, and a call that fails returns.
@@ -53,6 +53,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_remove.h"
 #include "k_add.h"
 #include "k_read.h"
+#include "k_copy.h"
 #include "k_select.h"
 #include "k_transform.h"
 #include "k_grade.h"
@@ -378,6 +379,10 @@ struct gsr_context {
     // gsr_grade (k_grade.h): what gsr_get_grade reports (the mask's bit count arrives in xf_h_count)
     int64_t gr_calls = 0, gr_last = 0;
     double gr_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // gsr_read_masked / gsr_duplicate (k_copy.h): the pinned word the selection's count arrives in, and what gsr_get_duplicate reports
+    PinnedMem<uint32_t> cp_h_total;
+    int64_t dup_calls = 0, dup_last = 0;
+    double dup_ms[4] = {0.0, 0.0, 0.0, 0.0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -1235,11 +1240,12 @@ static void launch_update(gsr_context* c, hipStream_t us, uint32_t first, uint32
     });
 }
 // k_repack on `us`: the n splats of the new order perm_new (NULL: upload order) from the slots old_slot names (upload index -> resident
-// slot; NULL: upload order) into the spare planes, with the bounds of their clusters
-static hipError_t queue_repack(gsr_context* c, hipStream_t us, uint32_t n, const uint32_t* perm_new, const uint32_t* old_slot)
+// slot; NULL: upload order) into the spare planes, with the bounds of their clusters.  cap_dst: the capacity of the spare planes (0: the
+// resident planes' own, c->cap -- everything but a gsr_duplicate that grows the context)
+static hipError_t queue_repack(gsr_context* c, hipStream_t us, uint32_t n, const uint32_t* perm_new, const uint32_t* old_slot, uint32_t cap_dst = 0u)
 {
     launch_sh(c->has_sh, [&](auto sh) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, perm_new, old_slot,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_repack<decltype(sh)::value>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, n, c->cap, cap_dst ? cap_dst : c->cap, perm_new, old_slot,
                            c->geoA, c->geoB, c->col, c->colrow, c->geoA2, c->geoB2, c->col2, c->colrow2, c->clusA2, c->clusB2);
     });
     return hipGetLastError();

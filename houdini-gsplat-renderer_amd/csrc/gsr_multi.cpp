@@ -689,6 +689,41 @@ extern "C" int gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_
     return gsr_read(m->ctx[0], first, n, out);
 }
 
+// ... and read back by a mask from rank 0's replica (gsr_read_masked from a host mask: the caller's thread; no rank's state changes)
+extern "C" int gsr_multi_read_masked(gsr_multi* m, const uint32_t* mask_host, int64_t max_rows, const gsr_read_arrays* out, int64_t* n_rows)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_read_masked: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_read_masked: upload in progress");
+    const int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    return gsr_read_masked(m->ctx[0], mask_host, 0, max_rows, out, n_rows);
+}
+
+// ... and duplicated on every rank: each compacts, orders and repacks its own replica.  gsr_multi_add's agreement rule.
+extern "C" int gsr_multi_duplicate(gsr_multi* m, const uint32_t* mask_host, int64_t* n_copied, int64_t* n_total)
+{
+    if (!m) return fail(GSR_E_INVALID, "gsr_multi_duplicate: NULL");
+    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_duplicate: upload in progress");
+    int rc = gsr_multi_synchronize(m);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> total((size_t)G, -1), copied((size_t)G, -1);
+    int64_t* const tp = total.data();
+    int64_t* const cp = copied.data();
+    rc = for_each_rank(m, [=](int g) { return gsr_duplicate(m->ctx[g], mask_host, 0, cp + g, tp + g); });
+    bool any_done = false, same = rc == GSR_OK;
+    for (int g = 0; g < G; ++g) any_done = any_done || total[(size_t)g] >= 0;
+    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
+    for (int g = 1; g < G && same; ++g) same = total[(size_t)g] == total[0] && copied[(size_t)g] == copied[0];
+    if (!same) {
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_duplicate: the ranks do not agree on the splat count: the geometry is dropped on all of them");
+    }
+    if (n_copied) *n_copied = copied[0];
+    if (n_total) *n_total = total[0];
+    return GSR_OK;
+}
+
 // ... and selected by screen region on rank 0's replica (gsr_select into a host mask: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set)
 {

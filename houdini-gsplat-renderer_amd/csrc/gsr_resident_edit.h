@@ -1,5 +1,5 @@
-// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10, 3.11): gsr_update, gsr_move, the
-// device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_transform, gsr_grade.  Host code only; included once, at the end of gsr_api.hip, which has the
+// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10 - 3.12): gsr_update, gsr_move, the
+// device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_duplicate, gsr_transform, gsr_grade.  Host code only; included once, at the end of gsr_api.hip, which has the
 // context, the frame slots, the upload arena (ensure_stage, ensure_up_events, stage_host_rows), the ordering of an upload (position_box,
 // morton_order), new_cloud_state / drop_geometry, and the <SH> launches of k_update, k_update_f32 and k_repack (launch_update,
 // queue_repack).
@@ -1003,6 +1003,218 @@ extern "C" int gsr_add_device(gsr_context* c, int64_t m64, const gsr_device_attr
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = check_device_attrs(c, a, m, who))) return rc;
     return add_body(c, who, m, [&](const UpArena& A, hipStream_t us, double*) { return stage_device_rows(c, A, 0, m, a, us); }, n_total);
+}
+
+// ---------------------------------------------------------------------------
+// Copying (k_copy.h): selected resident splats read out (gsr_read_masked*, gsr_resident_read.h) or duplicated.  Both
+// begin with gsr_remove's compaction, the SELECTED splats in the survivors' place.
+extern "C" int gsr_copy_map(const uint32_t* mask, int64_t n, int32_t* rows, int64_t* m)
+{
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && !mask)) return set_err(GSR_E_INVALID, "gsr_copy_map: bad argument");
+    int64_t r = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (((mask[i >> 5] >> (i & 31)) & 1u) == 0u) continue;
+        if (rows) rows[r] = (int32_t)i;
+        ++r;
+    }
+    if (m) *m = r;
+    return GSR_OK;
+}
+
+// The selection of a mask over the n resident splats, counted: the scratch of mark and scan at the head of the staging arena (a host
+// mask staged, the bitmap, the block counts, the block offsets; `bytes` in all), and the two launches.  What a verb needs behind the
+// count -- the row list, the positions, the destination rows -- lies behind `bytes`, sized by the count: grow() makes that room, and
+// counts again if the arena had to move (a host mask is still the caller's until the verb returns).
+struct CopySelection {
+    const uint32_t n, nblocks;
+    const size_t words;
+    const uint32_t* const mask;        // the caller's (NULL: every splat)
+    const bool is_device;
+    size_t oMask = 0, oSel = 0, oCnt = 0, oOff = 0, bytes = 0;
+
+    CopySelection(uint32_t n_, const uint32_t* mask_, bool dev) : n(n_), nblocks(div_up(n_, (uint32_t)GSR_REMOVE_BLOCK)), words(((size_t)n_ + 31) / 32), mask(mask_), is_device(dev)
+    {
+        auto place = [&](size_t b) { const size_t at = bytes; bytes += pad256(b); return at; };
+        oMask = place(mask && !is_device ? words * 4 : 0); oSel = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8); oCnt = place((size_t)nblocks * 4);
+        oOff = place(((size_t)nblocks + 1) * 4);
+    }
+    const unsigned long long* sel(const gsr_context* c) const { return reinterpret_cast<const unsigned long long*>(c->stage + oSel); }
+    const uint32_t* offsets(const gsr_context* c) const { return reinterpret_cast<const uint32_t*>(c->stage + oOff); }
+
+    // what the call needs before count(): the arena for the scratch, the pinned word of the count
+    int prepare(gsr_context* c, const char* who) const
+    {
+        const int rc = ensure_stage(c, bytes);
+        if (rc) return rc;
+        if (!c->cp_h_total && c->cp_h_total.alloc(2, 0)) {
+            (void)hipGetLastError();
+            return set_err(GSR_E_OOM, "%s: no pinned host memory for the selection's count", who);
+        }
+        return GSR_OK;
+    }
+    // mark and scan on `us`, and the wait for the total: *m = the selected splats.  link_ms (may be NULL) += what a host mask took.
+    hipError_t count(gsr_context* c, hipStream_t us, uint32_t* m, double* link_ms) const
+    {
+        const uint32_t* dmask = mask;
+        hipError_t e = hipSuccess;
+        if (mask && !is_device) {
+            const double t0 = up_now_ms();
+            uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
+            e = hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us);
+            if (e == hipSuccess) e = hipStreamSynchronize(us);     // the caller's mask may be freed on return
+            if (e != hipSuccess) return e;
+            if (link_ms) *link_ms += up_now_ms() - t0;
+            dmask = staged;
+        }
+        uint32_t* const counts = reinterpret_cast<uint32_t*>(c->stage + oCnt);
+        uint32_t* const offs = reinterpret_cast<uint32_t*>(c->stage + oOff);
+        hipLaunchKernelGGL(k_copy_mark, dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, reinterpret_cast<unsigned long long*>(c->stage + oSel), counts);
+        hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, counts, offs);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(c->cp_h_total, offs + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us);
+        if (e == hipSuccess) e = hipStreamSynchronize(us);
+        if (e == hipSuccess) *m = c->cp_h_total[0];
+        return e;
+    }
+    // room for `total` bytes of the arena (the scratch included), behind count(): the bitmap and the offsets are there afterwards.
+    // Whether the arena was replaced is read off its CAPACITY: ensure_stage releases before it allocates, and the larger allocation
+    // may well come back at the address of the one released, with nothing of its content.
+    int grow(gsr_context* c, hipStream_t us, size_t total, uint32_t m, const char* who) const
+    {
+        const bool replaced = total > c->stage.cap();
+        const int rc = ensure_stage(c, total);
+        if (rc || !replaced) return rc;
+        uint32_t again = 0;
+        const hipError_t e = count(c, us, &again, nullptr);
+        if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
+        if (again != m) return set_err(GSR_E_HIP, "%s: the mask changed during the call (%u selected, then %u)", who, m, again);
+        return GSR_OK;
+    }
+};
+
+extern "C" int64_t gsr_debug_stage_bytes(gsr_context* c)
+{
+    if (!c) return (int64_t)set_err(GSR_E_INVALID, "gsr_debug_stage_bytes: ctx is NULL");
+    return (int64_t)c->stage.cap();
+}
+
+extern "C" int gsr_get_duplicate(gsr_context* c, int64_t* calls, int64_t* copied_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_duplicate: ctx is NULL");
+    if (calls) *calls = c->dup_calls;
+    if (copied_last) *copied_last = c->dup_last;
+    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->dup_ms[k];
+    return GSR_OK;
+}
+
+// A copy of each selected splat appended.  A move whose source is a multiset: the compaction leaves the n + m positions and the slot
+// each of them is carried from (a copy: its original's), the ordering of an upload runs over them, k_repack writes the spare planes at
+// the capacity gsr_add's policy gives, the swap.  The steps around that are add_body's.
+extern "C" int gsr_duplicate(gsr_context* c, const uint32_t* mask, int mask_is_device, int64_t* m_out, int64_t* n_total)
+{
+    const char* const who = "gsr_duplicate";
+    if (!c) return set_err(GSR_E_INVALID, "gsr_duplicate: ctx is NULL");
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const uint32_t n0 = c->n;
+    HIP_TRY(hipSetDevice(c->device));
+    const CopySelection s(n0, mask, mask_is_device != 0);
+    if (mask && mask_is_device && n0 && (rc = check_device_source(c, mask, s.words * 4, who, "mask"))) return rc;
+    Reorder ro(c, who, false);
+    if ((rc = sync_all(c))) return rc;   // the public stream (a producer of a device mask queued there has finished), and no write under a frame in flight
+    auto nothing = [&]() {             // nothing is selected: no resident bit changes, nothing is invalidated
+        if (m_out) *m_out = 0;
+        if (n_total) *n_total = (int64_t)n0;
+        return GSR_OK;
+    };
+    if (n0 == 0) return nothing();
+    hipStream_t us = ro.us;
+    // ---- 1, 2. which splats are copied, and how many: nothing resident is written yet
+    if ((rc = s.prepare(c, who)) || (rc = ro.old_inverse(true))) return rc;
+    HIP_TRY(hipEventRecord(c->up_ev[0], us));
+    uint32_t m = 0;
+    HIP_TRY(s.count(c, us, &m, &ro.link_ms));
+    if (m > n0) return set_err(GSR_E_HIP, "gsr_duplicate: the scan counted %u selected of %u splats", m, n0);
+    if (m == 0) return nothing();
+    if ((int64_t)n0 + (int64_t)m > 0x7fffffffll) return set_err(GSR_E_INVALID, "gsr_duplicate: %u + %u splats are more than a context holds", n0, m);
+    const uint32_t n1 = n0 + m, nclus1 = div_up(n1, GSR_CLUSTER);
+    const uint32_t cap0 = c->cap, cap1 = (uint32_t)gsr_add_capacity((int64_t)cap0, (int64_t)n1);
+    const bool grow = cap1 != cap0;
+    const bool vis = c->vis_on;
+    // ---- everything the rest needs, before the first write to resident memory or to the visibility's state (add_body's list)
+    size_t off = s.bytes;
+    auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
+    const size_t oRows = place((size_t)m * 4), oP = place((size_t)n1 * 12), oSlot = place((size_t)n1 * 4);
+    if ((rc = s.grow(c, us, off, m, who))) return rc;
+    if ((rc = ro.prepare(n1))) return rc;
+    if (grow) {
+        free_spare_planes(c);
+        if ((rc = ensure_spare_planes(c, cap1, false))) return rc;
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k)
+            if ((rc = alloc_splat_arrays(ro.slot_new[k], cap1))) {
+                free_spare_planes(c);
+                return rc;
+            }
+    } else if ((rc = ensure_spare_planes(c, cap0, true))) {
+        return rc;
+    }
+    if ((rc = ro.clusA_new.alloc(nclus1)) || (rc = ro.clusB_new.alloc(nclus1))) return rc;
+    if (vis) {
+        if ((rc = vis_ensure_buffers(c))) return rc;
+        if (grow && (rc = ro.alpha0_new.alloc((size_t)cap1))) return rc;
+        if (c->vis_mask && (rc = ro.mask_new.alloc(((size_t)n1 + 31) / 32))) return rc;
+    }
+    // nothing can fail for lack of memory any more: the larger buffers take their places (none of them holds anything a frame keeps)
+    c->clusA2 = std::move(ro.clusA_new); c->clusB2 = std::move(ro.clusB_new);
+    if (grow) {
+        for (int k = 0; k < GSR_MAX_SLOTS; ++k) slot_take_splat_arrays(c->slot[k], std::move(ro.slot_new[k]));
+        c->alpha0_2.reset();
+        if (!vis) c->alpha0.reset();
+    }
+    // ---- from here on a failure leaves no geometry
+    ro.spare_outgrown = grow;
+    // 3. every position of the larger cloud in upload order, the slot each splat is carried from, the copies' true alphas
+    uint32_t* const rows = reinterpret_cast<uint32_t*>(c->stage + oRows);
+    float* const Pall = reinterpret_cast<float*>(c->stage + oP);
+    uint32_t* const src_slot = reinterpret_cast<uint32_t*>(c->stage + oSlot);
+    float* const a0 = !vis ? (float*)nullptr : grow ? (float*)ro.alpha0_new : (float*)c->alpha0;
+    hipError_t e = hipSuccess;
+    if (vis && grow) e = hipMemcpyAsync(a0, c->alpha0, (size_t)n0 * 4, hipMemcpyDeviceToDevice, us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_copy_compact<true>), dim3(s.nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n0, s.sel(c), s.offsets(c), rows, ro.inv_old, c->geoA,
+                           Pall, src_slot, vis ? (const float*)c->alpha0 : (const float*)nullptr, a0);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return ro.lost(e);
+    // 4. the ordering of an upload over all of them, and the planes into the spare set: k_repack as a move runs it, with the slot list in
+    // the place of the old order's inverse and the spare planes' own capacity
+    if ((rc = ro.order(Pall, n1))) return ro.lost(rc);
+    e = queue_repack(c, us, n1, ro.perm_new, src_slot, cap1);
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], us);
+    // ... and the mask of a visibility in force, extended by clear bits
+    if (e == hipSuccess && ro.mask_new) {
+        const uint32_t words1 = (uint32_t)(((size_t)n1 + 31) / 32);
+        hipLaunchKernelGGL(k_add_mask_extend, dim3(div_up(words1, 256)), dim3(256), 0, us, n0, words1, c->vis_mask, ro.mask_new);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return ro.lost(e);
+    // 5. the swap; what becomes the spare set goes as after an add
+    ro.commit(n1, nclus1, true);
+    c->clusA2.reset(); c->clusB2.reset();
+    if (grow) {
+        free_spare_planes(c);
+        c->cap = cap1;
+        if (vis) c->alpha0 = std::move(ro.alpha0_new);
+    }
+    // 6, 7. the rule of a visibility in force over the whole cloud; a new cloud to everything a frame keeps
+    if ((rc = ro.finish(c->dup_ms, false))) return rc;
+    c->dup_calls += 1;
+    c->dup_last = (int64_t)m;
+    if (grow) c->add_grows += 1;
+    if (m_out) *m_out = (int64_t)m;
+    if (n_total) *n_total = (int64_t)n1;
+    return GSR_OK;
 }
 
 // ---------------------------------------------------------------------------

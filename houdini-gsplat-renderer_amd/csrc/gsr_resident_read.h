@@ -1,5 +1,5 @@
 // gsr_resident_read.h -- the verbs that read the resident cloud back in UPLOAD order: gsr_read_info, gsr_read,
-// gsr_read_device, gsr_get_read.  Host code only; included once, behind gsr_resident_edit.h, whose refusals (refuse_edit,
+// gsr_read_device, gsr_get_read, and over a mask in the place of a range gsr_read_masked, gsr_read_masked_device.  Host code only; included once, behind gsr_resident_edit.h, whose refusals (refuse_edit,
 // refuse_range) and pointer check (check_device_source) it shares.  The kernel is k_unpack (k_read.h).
 //
 // A read writes NOTHING the context keeps: no resident bit, no horizon, no cached order, no policy, no visibility state, no entry of
@@ -29,17 +29,18 @@ extern "C" int gsr_get_read(gsr_context* c, int64_t* reads, int64_t* rows_last, 
 }
 
 // k_unpack over rows [first, first + n) on slot 0's own stream, between up_ev[0] and up_ev[1]; the caller has ensured the inverse of
-// the storage order and the events, and waits for the stream.
+// the storage order and the events, and waits for the stream.  rows (device memory, n upload indices; NULL: none): the row list of a
+// masked read in the place of the range; its caller has recorded up_ev[0] in front of the compaction that wrote the list.
 template <bool F32>
-static hipError_t queue_unpack(gsr_context* c, hipStream_t us, uint32_t first, uint32_t n, const GsrReadDst<F32>& dst)
+static hipError_t queue_unpack(gsr_context* c, hipStream_t us, uint32_t first, uint32_t n, const GsrReadDst<F32>& dst, const uint32_t* rows = nullptr)
 {
     const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
     const float* const alpha0 = c->vis_on ? c->alpha0 : (const float*)nullptr;       // (a visibility in force: geoA holds +0.0f for the hidden)
-    hipError_t e = hipEventRecord(c->up_ev[0], us);
+    hipError_t e = rows ? hipSuccess : hipEventRecord(c->up_ev[0], us);
     if (e != hipSuccess) return e;
     launch_sh(c->has_sh, [&](auto sh) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_unpack<decltype(sh)::value, F32>), dim3(div_up(n, GSR_CLUSTER)), dim3(GSR_PACK_THREADS), 0, us, first, n, dst, inv,
-                           c->geoA, c->geoB, c->col, c->colrow, alpha0);
+                           c->geoA, c->geoB, c->col, c->colrow, alpha0, rows);
     });
     e = hipGetLastError();
     return e == hipSuccess ? hipEventRecord(c->up_ev[1], us) : e;
@@ -128,4 +129,124 @@ extern "C" int gsr_read_device(gsr_context* c, int64_t first, int64_t n64, const
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_read_device: %s", hipGetErrorString(e));
     read_done(c, n64, 0.0 /* nothing crossed the link */, t_begin);
     return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Reading by a mask (k_copy.h): gsr_remove's compaction, the selected splats in the survivors' place, writes the row
+// list k_unpack then reads.  Both forms share everything up to the destinations: the refusals, the count (mark, scan, one word over the
+// link), max_rows, and the row list behind the selection's scratch in the staging arena.
+//   wanted                   whether the caller's struct names a destination (none: the call is a count); wait_public: the device form
+//   check()                  the device destinations' pointer check for max_rows rows, before anything is launched
+//   out_bytes(m)             what the form stages of m rows in the arena, behind the row list
+//   unpack(us, m, rows, arena behind the row list, &copy_ms)   k_unpack and the copies; complete on return
+template <class Check, class Bytes, class Unpack>
+static int read_masked_body(gsr_context* c, const char* who, const uint32_t* mask, int mask_is_device, int64_t max_rows, bool wanted, bool wait_public,
+                            int64_t* m_out, Check&& check, Bytes&& out_bytes, Unpack&& unpack)
+{
+    if (wanted && max_rows < 0) return set_err(GSR_E_INVALID, "%s: max_rows = %lld", who, (long long)max_rows);
+    const uint32_t n = c->n;
+    const double t_begin = up_now_ms();
+    HIP_TRY(hipSetDevice(c->device));
+    const CopySelection s(n, mask, mask_is_device != 0);
+    int rc = GSR_OK;
+    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, s.words * 4, who, "mask"))) return rc;
+    if (wanted && (rc = check())) return rc;
+    if (n == 0) {                                      // the empty cloud selects no row
+        if (m_out) *m_out = 0;
+        return GSR_OK;
+    }
+    // a producer of a device mask, or a consumer of device destinations, queued on the public stream has finished
+    if (c->stream && (wait_public || (mask && mask_is_device))) HIP_TRY(hipStreamSynchronize(c->stream));
+    if ((rc = s.prepare(c, who)) || (rc = ensure_inverse_perm(c)) || (rc = ensure_up_events(c, 2, who, true))) return rc;
+    hipStream_t us = c->slot[0].own;
+    uint32_t m = 0;
+    HIP_TRY(s.count(c, us, &m, nullptr));
+    if (m > n) return set_err(GSR_E_HIP, "%s: the scan counted %u selected of %u splats", who, m, n);
+    if (m_out) *m_out = (int64_t)m;
+    if (!wanted) return GSR_OK;                        // a count
+    if ((int64_t)m > max_rows) return set_err(GSR_E_INVALID, "%s: the selection holds %u rows, the destinations %lld", who, m, (long long)max_rows);
+    if (m == 0) return GSR_OK;
+    const size_t oRows = s.bytes, oOut = oRows + pad256((size_t)m * 4);
+    if ((rc = s.grow(c, us, oOut + out_bytes((size_t)m), m, who))) return rc;
+    uint32_t* const rows = reinterpret_cast<uint32_t*>(c->stage + oRows);
+    hipError_t e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_copy_compact<false>), dim3(s.nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, s.sel(c), s.offsets(c), rows, (const uint32_t*)nullptr,
+                           (const float4*)nullptr, (float*)nullptr, (uint32_t*)nullptr, (const float*)nullptr, (float*)nullptr);
+        e = hipGetLastError();
+    }
+    double copy_ms = 0.0;
+    if (e == hipSuccess) e = unpack(us, m, rows, c->stage + oOut, &copy_ms);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    read_done(c, (int64_t)m, copy_ms, t_begin);
+    return GSR_OK;
+}
+
+extern "C" int gsr_read_masked(gsr_context* c, const uint32_t* mask, int mask_is_device, int64_t max_rows, const gsr_read_arrays* out, int64_t* m_out)
+{
+    const char* const who = "gsr_read_masked";
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    static const gsr_read_arrays none{};
+    if (!out) out = &none;
+    const int nsh = (out->shx ? 1 : 0) + (out->shy ? 1 : 0) + (out->shz ? 1 : 0);
+    if (nsh != 0 && nsh != 3) return set_err(GSR_E_INVALID, "gsr_read_masked: the three SH arrays come together or not at all");
+    if (nsh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_read_masked: SH arrays for a cloud uploaded without SH");
+    const bool wanted = out->P || out->Cd || out->alpha || out->scale || out->orient || nsh;
+    void* const host[8] = {out->P, out->alpha, out->Cd, out->scale, out->orient, out->shx, out->shy, out->shz};
+    const size_t row[8] = {12, 4, 6, 6, 8, 32, 32, 32};
+    size_t at[8];
+    return read_masked_body(c, who, mask, mask_is_device, max_rows, wanted, false, m_out,
+        []() { return GSR_OK; },
+        [&](size_t m) {                                // device rows in gsr_upload_append's layout, one section per array that is wanted
+            size_t bytes = 0;
+            for (int k = 0; k < 8; ++k) { at[k] = bytes; if (host[k]) bytes += pad256(m * row[k]); }
+            return bytes;
+        },
+        [&](hipStream_t us, uint32_t m, const uint32_t* rows, char* arena, double* copy_ms) {
+            char* d[8];
+            for (int k = 0; k < 8; ++k) d[k] = host[k] ? arena + at[k] : nullptr;
+            auto f32 = [&](int k) { return reinterpret_cast<float*>(d[k]); };
+            auto h16 = [&](int k) { return reinterpret_cast<uint16_t*>(d[k]); };
+            const GsrReadDst<false> dst{f32(0), f32(1), h16(2), h16(3), h16(4), h16(5), h16(6), h16(7)};
+            hipError_t e = queue_unpack(c, us, 0u, m, dst, rows);
+            if (e == hipSuccess) e = hipStreamSynchronize(us);
+            const double t0 = up_now_ms();
+            for (int k = 0; k < 8; ++k)
+                if (host[k] && e == hipSuccess) e = hipMemcpyAsync(host[k], d[k], (size_t)m * row[k], hipMemcpyDeviceToHost, us);
+            if (e == hipSuccess) e = hipStreamSynchronize(us);
+            *copy_ms = up_now_ms() - t0;
+            return e;
+        });
+}
+
+extern "C" int gsr_read_masked_device(gsr_context* c, const uint32_t* mask, int mask_is_device, int64_t max_rows, const gsr_device_out* out, int64_t* m_out)
+{
+    const char* const who = "gsr_read_masked_device";
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    static const gsr_device_out none{};
+    if (!out) out = &none;
+    if (out->reserved_ != 0) return set_err(GSR_E_INVALID, "gsr_read_masked_device: reserved_ is not 0");
+    if (out->sh && !c->has_sh) return set_err(GSR_E_INVALID, "gsr_read_masked_device: sh for a cloud uploaded without SH");
+    if (out->sh && (out->sh_vec3_per_point < 1 || out->sh_vec3_per_point > 16))
+        return set_err(GSR_E_INVALID, "gsr_read_masked_device: sh_vec3_per_point = %d is not within 1..16", out->sh_vec3_per_point);
+    const bool wanted = out->P || out->Cd || out->alpha || out->scale || out->orient || out->sh;
+    return read_masked_body(c, who, mask, mask_is_device, max_rows, wanted, true, m_out,
+        [&]() {                                        // every destination for max_rows rows: a wrong pointer must never be found out by a kernel
+            int bad = GSR_OK;
+            auto look = [&](const float* p, size_t floats_per_row, const char* name) {
+                if (p && !bad) bad = check_device_source(c, p, (size_t)max_rows * floats_per_row * 4, who, name);
+            };
+            look(out->P, 3, "P"); look(out->Cd, 3, "Cd"); look(out->alpha, 1, "alpha"); look(out->scale, 3, "scale"); look(out->orient, 4, "orient");
+            look(out->sh, out->sh ? (size_t)out->sh_vec3_per_point * 3 : 0, "sh");
+            return bad;
+        },
+        [](size_t) { return (size_t)0; },              // k_unpack writes the caller's arrays where they are
+        [&](hipStream_t us, uint32_t m, const uint32_t* rows, char*, double*) {
+            const GsrReadDst<true> dst{out->P, out->alpha, out->Cd, out->scale, out->orient, out->sh, out->sh ? out->sh_vec3_per_point : 0};
+            hipError_t e = queue_unpack(c, us, 0u, m, dst, rows);
+            if (e == hipSuccess) e = hipStreamSynchronize(us);
+            return e;
+        });
 }

@@ -1,6 +1,8 @@
 // k_read.h -- K0r: the resident cloud read back in UPLOAD order (gsr_read, gsr_read_device): k_pack run backwards, in
 // k_update's shape.  Rows [0, cnt) of the destination arrays get the attributes of the splats [first, first + cnt) of the upload:
 //   row t  <-  storage slot j = inv[first + t]     (inv: upload index -> storage slot, the inverse of perm; NULL: upload order)
+// With a row list (rows: device memory, cnt upload indices; NULL: none -- gsr_read_masked's, written by k_copy_compact) row t is the
+// splat rows[t] in the place of first + t, and everything below reads "first + t" as "rows[t]".
 // One workgroup of GSR_PACK_THREADS = 64 rows, k_resident.h's lane roles.
 // LOADS (a lane whose piece feeds no array that is wanted loads nothing; the wanted set is uniform: it sits in the argument segment):
 //   SH and a colour array wanted:  lane q = 0..6 loads piece q of the splat's 128-byte colrow line (ONE request per splat: piece 0 is
@@ -39,14 +41,15 @@ template <bool SH, bool F32>
 __global__ void __launch_bounds__(GSR_PACK_THREADS)
 k_unpack(uint32_t first, uint32_t cnt, GsrReadDst<F32> dst, const uint32_t* __restrict__ inv,
          const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col, const uint4* __restrict__ colrow,
-         const float* __restrict__ alpha0)
+         const float* __restrict__ alpha0, const uint32_t* __restrict__ rows)
 {
     static_assert(GSR_PACK_THREADS == 8 * GSR_CLUSTER, "one workgroup = 64 rows, eight lanes per splat");
     __shared__ __attribute__((aligned(16))) uint16_t s_h[GSR_CLUSTER][GSR_ROW_HALVES];
     const int tid = threadIdx.x, q = tid & 7, sp = tid >> 3;
     const uint32_t t = blockIdx.x * (uint32_t)GSR_CLUSTER + (uint32_t)sp;
     if (t >= cnt) return;              // (whole splats leave: the lanes that meet at the wave barrier below are those that stay)
-    const uint32_t j = inv ? inv[first + t] : first + t;
+    const uint32_t u = rows ? rows[t] : first + t;     // the row's upload index
+    const uint32_t j = inv ? inv[u] : u;
     const bool sh = SH && dst.wants_sh();
     const bool colour = dst.Cd || sh, shape = dst.scale || dst.orient;
     const bool geo = dst.P || (dst.alpha && !alpha0);          // the resident P + opacity word is needed
@@ -66,7 +69,7 @@ k_unpack(uint32_t first, uint32_t cnt, GsrReadDst<F32> dst, const uint32_t* __re
             float* p = dst.P + 3 * (size_t)t;
             p[0] = __uint_as_float(piece.x); p[1] = __uint_as_float(piece.y); p[2] = __uint_as_float(piece.z);
         }
-        if (dst.alpha) dst.alpha[t] = alpha0 ? alpha0[first + t] : __uint_as_float(piece.w);
+        if (dst.alpha) dst.alpha[t] = alpha0 ? alpha0[u] : __uint_as_float(piece.w);
         if (sh) { s_h[sp][15] = 0; s_h[sp][31] = 0; s_h[sp][47] = 0; }       // (the index no chunk holds)
     } else if (q == 7) {
         const GsrShape h = gsr_shape_split(piece);

@@ -424,10 +424,12 @@ k_move_positions(uint32_t first, uint32_t cnt, uint32_t n, const float* __restri
 //   slot j' <- the splat i = perm_new[j'] (NULL: i = j'), which sits in slot j = inv_old[i] (NULL: j = i)
 // Every lane carries its pieces as they are, each load and its store in the SAME lane branch: with the loads in one set of branches and
 // the stores in another the compiler waits in front of each store for the store before it, 0.1 ms of 0.9 at 6 M splats (LAB_NOTES.md,
-// "Resident-layout kernels in one header").  Slots behind n in the last cluster are not written, as k_pack leaves them.
+// "Resident-layout kernels in one header").  Slots behind n in the last cluster are not written, as k_pack leaves them.  The colour
+// chunks are strided by the SOURCE capacity where they are read and by the DESTINATION capacity where they are written, as k_add_pack's
+// are: the two differ only for a gsr_duplicate that grows the context.
 template <bool SH>
 __global__ void __launch_bounds__(GSR_PACK_THREADS)
-k_repack(uint32_t n, uint32_t cap, const uint32_t* __restrict__ perm_new, const uint32_t* __restrict__ inv_old,
+k_repack(uint32_t n, uint32_t cap_src, uint32_t cap_dst, const uint32_t* __restrict__ perm_new, const uint32_t* __restrict__ inv_old,
          const float4* __restrict__ geoA, const uint4* __restrict__ geoB, const uint4* __restrict__ col, const uint4* __restrict__ colrow,
          float4* __restrict__ geoA2, uint4* __restrict__ geoB2, uint4* __restrict__ col2, uint4* __restrict__ colrow2,
          float4* __restrict__ clusA2, float4* __restrict__ clusB2)
@@ -443,7 +445,7 @@ k_repack(uint32_t n, uint32_t cap, const uint32_t* __restrict__ perm_new, const 
         if (SH) colrow2[(size_t)jn * 8 + q] = colrow[(size_t)j * 8 + q];
         if (q == 0) gsr_store_geo(0, jn, gsr_as_uint4(geoA[j]), geoA2, geoB2, in);
         else if (q == 7) gsr_store_geo(7, jn, geoB[j], geoA2, geoB2, in);
-        else if (gsr_colour_lane<SH>(q)) col2[(size_t)(q - 1) * cap + jn] = col[(size_t)(q - 1) * cap + j];
+        else if (gsr_colour_lane<SH>(q)) col2[(size_t)(q - 1) * cap_dst + jn] = col[(size_t)(q - 1) * cap_src + j];
     }
     gsr_cluster_fold(in, s_red, clusA2, clusB2);
 }

@@ -185,6 +185,7 @@ VOL_BOX = 1            # gsr_crop_volume.kind: inside iff max(|q|) <= 1
 VOL_ELLIPSOID = 2      # ... iff |q|^2 <= 1
 REMOVE_HIDDEN = 1      # GSR_REMOVE_HIDDEN: gsr_remove also removes what the visibility in force hides
 REMOVE_BLOCK = 4096    # GSR_REMOVE_BLOCK: upload indices one workgroup of the compaction kernels spans
+COPY_BLOCK = REMOVE_BLOCK      # ... and of k_copy.h's, which keep that shape
 SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_INTERSECT, SELECT_TOGGLE = range(5)     # GSR_SELECT_*: what gsr_select does to the mask
 SELECT_ANY_OPACITY = 1 # GSR_SELECT_ANY_OPACITY (flags): no opacity test, so hidden splats can be hit
 SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the selection kernel spans
@@ -225,10 +226,11 @@ C_ABI_SYMBOLS = [
     "gsr_remove", "gsr_remove_map", "gsr_get_removal", "gsr_multi_remove",
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
+    "gsr_copy_map", "gsr_read_masked", "gsr_read_masked_device", "gsr_duplicate", "gsr_get_duplicate", "gsr_multi_read_masked", "gsr_multi_duplicate",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
-    "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan",
+    "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan", "gsr_debug_stage_bytes",
 ]
 
 
@@ -302,6 +304,8 @@ def load_library() -> C.CDLL:
     L.gsr_move_device.argtypes = [vp, i64, i64, f32p, C.POINTER(gsr_device_attrs)]
     L.gsr_debug_check_device_source.argtypes = [vp, vp, i64]
     L.gsr_debug_live_handles.argtypes = [C.POINTER(C.c_int64)]
+    L.gsr_debug_stage_bytes.argtypes = [vp]
+    L.gsr_debug_stage_bytes.restype = i64
     L.gsr_debug_read_resident.argtypes = [vp, i32, vp, i64]
     L.gsr_set_visibility.argtypes = [vp, C.POINTER(gsr_visibility)]
     L.gsr_get_visibility.argtypes = [vp, C.POINTER(gsr_visibility), C.POINTER(C.c_int64)]
@@ -323,6 +327,13 @@ def load_library() -> C.CDLL:
     L.gsr_read_device.argtypes = [vp, i64, i64, C.POINTER(gsr_device_out)]
     L.gsr_get_read.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_read.argtypes = [vp, i64, i64, C.POINTER(gsr_read_arrays)]
+    L.gsr_copy_map.argtypes = [vp, i64, vp, C.POINTER(C.c_int64)]
+    L.gsr_read_masked.argtypes = [vp, vp, i32, i64, C.POINTER(gsr_read_arrays), C.POINTER(C.c_int64)]
+    L.gsr_read_masked_device.argtypes = [vp, vp, i32, i64, C.POINTER(gsr_device_out), C.POINTER(C.c_int64)]
+    L.gsr_duplicate.argtypes = [vp, vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_get_duplicate.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_read_masked.argtypes = [vp, vp, i64, C.POINTER(gsr_read_arrays), C.POINTER(C.c_int64)]
+    L.gsr_multi_duplicate.argtypes = [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_select.argtypes = [vp, C.POINTER(gsr_camera), C.POINTER(gsr_select_region), vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_select_eval.argtypes = [C.POINTER(gsr_camera), f32p, C.POINTER(gsr_select_region), vp, vp, i64, vp, vp]
     L.gsr_get_select.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -657,6 +668,65 @@ def remove_map(mask, n=None):
     out, left = np.zeros(max(int(n), 0), np.int32), C.c_int64(0)
     _check(load_library().gsr_remove_map(words.ctypes.data, int(n), out.ctypes.data if out.size else None, C.byref(left)))
     return out, left.value
+
+
+def copy_map(mask, n=None):
+    """gsr_copy_map (host only, no GPU): the rows gsr_read_masked returns and gsr_duplicate copies.  mask as removal_mask takes it (True =
+    selected); n = the splat count (from a boolean mask's length when None) -> (int32 rows[m]: the upload indices of the selected splats,
+    ascending; m)"""
+    m = np.asarray(mask)
+    if n is None:
+        if m.dtype != np.bool_:
+            raise GsrError(-1, "copy_map: packed words do not say how many splats they cover: n must be given")
+        n = m.size
+    words = removal_mask(m)
+    if words.size * 32 < int(n):
+        raise GsrError(-1, f"copy_map: {words.size} words do not cover {int(n)} splats")
+    out, cnt = np.zeros(max(int(n), 0), np.int32), C.c_int64(0)
+    _check(load_library().gsr_copy_map(words.ctypes.data, int(n), out.ctypes.data if out.size else None, C.byref(cnt)))
+    return out[:cnt.value].copy(), cnt.value
+
+
+def range_mask(first: int, count: int, n: int) -> np.ndarray:
+    """the packed mask words over n splats with the bits [first, first + count) set: after duplicate() -> (m, n_total) the mask of the
+    fresh copies is range_mask(n_total - m, m, n_total), what a following transform or grade takes"""
+    first, count, n = int(first), int(count), int(n)
+    if first < 0 or count < 0 or n < 0 or first + count > n:
+        raise GsrError(-1, f"range_mask: [{first}, {first} + {count}) is not within the {n} splats")
+    bits = np.zeros(n, bool)
+    bits[first:first + count] = True
+    return removal_mask(bits)
+
+
+def _device_mask_ptr(mask, who: str) -> int:
+    """a device mask as the *_device verbs take it: an int (a device pointer) or an object with data_ptr() -> the pointer"""
+    if isinstance(mask, (bool, np.bool_)) or mask is None:
+        raise GsrError(-1, f"{who}: the mask is neither a device pointer (int) nor an object with data_ptr()")
+    if isinstance(mask, (int, np.integer)):
+        return int(mask)
+    if hasattr(mask, "data_ptr"):
+        return int(mask.data_ptr())
+    raise GsrError(-1, f"{who}: the mask is neither a device pointer (int) nor an object with data_ptr()")
+
+
+def _read_masked_splats(verb, info, mask, names):
+    """Engine.read_masked / MultiEngine.read_masked behind their handles: verb(mask pointer, max_rows, struct, &m); info = (resident
+    count, has_sh).  A count call sizes the arrays."""
+    from .scenes import Splats
+    total, has_sh = info
+    words = removal_words(mask, total)
+    ptr = None if words is None else words.ctypes.data
+    if names is None:
+        names = [name for name, _, _ in READ_ARRAYS if has_sh or not name.startswith("sh")]
+    unknown = set(names) - {name for name, _, _ in READ_ARRAYS}
+    if unknown:
+        raise GsrError(-1, f"read_masked: unknown array(s) {sorted(unknown)}")
+    m = C.c_int64(0)
+    _check(verb(ptr, 0, None, C.byref(m)))
+    r, arrays = read_arrays_struct(m.value, tuple(names))
+    if m.value and names:
+        _check(verb(ptr, m.value, C.byref(r), C.byref(m)))
+    return Splats(*[arrays.get(name) for name, _, _ in READ_ARRAYS])
 
 
 def pack_image(painted) -> np.ndarray:
@@ -1302,6 +1372,69 @@ class Engine:
         _check(self.L.gsr_read_device(self.h, int(first), n, C.byref(out)))
         return n
 
+    # ---- copying: the selection read out, or duplicated (include/gsplat_hip.h, "copying")
+    def read_masked(self, mask, names=None):
+        """gsr_read_masked from a HOST mask (a boolean array over the resident splats in upload order, or the packed uint32 words;
+        None: every splat): read's rows for the selected splats, in ascending upload order (copy_map), as a scenes.Splats of m rows.
+        Changes and invalidates nothing."""
+        info = self.read_info()
+        verb = lambda ptr, max_rows, r, m: self.L.gsr_read_masked(self.h, ptr, 0, max_rows, r, m)     # noqa: E731
+        return _read_masked_splats(verb, (info["n_splats"], info["has_sh"]), mask, names)
+
+    def read_masked_device(self, dst: dict, mask, max_rows=None, sh_vec3_per_point=None, mask_is_device: bool = True) -> int:
+        """gsr_read_masked_device: the same rows into float32 arrays in DEVICE memory, dst as read_device takes it, each array holding
+        max_rows rows (from the tensors' shapes when None); mask = packed uint32 words in device (or pinned) memory -- a raw pointer or
+        an object with data_ptr(), as select_device writes them -- or, with mask_is_device = False, a host mask as read_masked takes it;
+        None: every splat.  A selection of more than max_rows rows raises (GSR_E_INVALID) and writes nothing; an empty dst is a count
+        -> the rows of the selection"""
+        if not isinstance(dst, dict):
+            raise GsrError(-1, "read_masked_device: dst is not a dict of device arrays")
+        keep_words = None
+        if mask is None:
+            ptr, dev = None, 0
+        elif mask_is_device:
+            ptr, dev = C.c_void_p(_device_mask_ptr(mask, "read_masked_device")), 1
+        else:
+            keep_words = removal_words(mask, self.read_info()["n_splats"])
+            ptr, dev = keep_words.ctypes.data, 0
+        m = C.c_int64(0)
+        if not any(v is not None for v in dst.values()):
+            _check(self.L.gsr_read_masked_device(self.h, ptr, dev, 0, None, C.byref(m)))
+            return m.value
+        out, max_rows, keep = device_out_struct(max_rows, sh_vec3_per_point, **dst)
+        _check(self.L.gsr_read_masked_device(self.h, ptr, dev, max_rows, C.byref(out), C.byref(m)))
+        return m.value
+
+    def duplicate(self, mask=None):
+        """gsr_duplicate from a HOST mask (a boolean array over the resident splats in upload order, or the packed uint32 words; None:
+        every splat): a copy of each selected splat joins the cloud behind its last upload index, in the ascending upload order of the
+        originals, on the GPU with no re-upload -- bit for bit a fresh upload of concat(read(), read()[copy_map]) -> (m: the copies,
+        n_total: the splats resident now).  range_mask(n_total - m, m, n_total) selects the copies."""
+        words = removal_words(mask, self.stats()["n_splats"])
+        m, total = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_duplicate(self.h, None if words is None else words.ctypes.data, 0, C.byref(m), C.byref(total)))
+        return m.value, total.value
+
+    def duplicate_device(self, mask_ptr):
+        """gsr_duplicate from packed uint32 mask words in DEVICE (or pinned) memory: a raw pointer or an object with data_ptr(),
+        ceil(n / 32) words, as select_device writes them; never written.  Waits for the work queued on the stream given to set_stream
+        first -> (m, n_total)"""
+        ptr = _device_mask_ptr(mask_ptr, "duplicate_device")
+        m, total = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_duplicate(self.h, C.c_void_p(ptr), 1, C.byref(m), C.byref(total)))
+        return m.value, total.value
+
+    def debug_stage_bytes(self) -> int:
+        """gsr_debug_stage_bytes: the bytes the context's staging arena answers for right now"""
+        return int(self.L.gsr_debug_stage_bytes(self.h))
+
+    def get_duplicate(self) -> dict:
+        """gsr_get_duplicate -> {duplicates: calls that copied something, copied_last, ms: the last call's stage clock [mask copy,
+        mark .. sort, repack, wall]}"""
+        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
+        _check(self.L.gsr_get_duplicate(self.h, C.byref(calls), C.byref(last), ms))
+        return {"duplicates": calls.value, "copied_last": last.value, "ms": [float(x) for x in ms]}
+
     def get_read(self) -> dict:
         """gsr_get_read -> {reads: calls that read something, rows_last, ms: the last call's clock [kernel, device -> host copies, 0, wall]}"""
         calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
@@ -1922,6 +2055,21 @@ class MultiEngine:
         cnt, sh = C.c_int64(0), C.c_int(0)
         _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), C.byref(sh), None))
         return _read_splats(self.L, self.L.gsr_multi_read, self.h, (cnt.value, bool(sh.value)), first, n, names)
+
+    def read_masked(self, mask, names=None):
+        """gsr_multi_read_masked: Engine.read_masked of rank 0's copy (the cloud is replicated), from a host mask -> scenes.Splats"""
+        cnt, sh = C.c_int64(0), C.c_int(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), C.byref(sh), None))
+        verb = lambda ptr, max_rows, r, m: self.L.gsr_multi_read_masked(self.h, ptr, max_rows, r, m)     # noqa: E731
+        return _read_masked_splats(verb, (cnt.value, bool(sh.value)), mask, names)
+
+    def duplicate(self, mask=None):
+        """gsr_multi_duplicate: Engine.duplicate on every rank, from a host mask -> (the copies, the splats resident now) (the ranks
+        agree, or none keeps geometry)"""
+        words = removal_words(mask, self.stats(0)["n_splats"])
+        m, total = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_multi_duplicate(self.h, None if words is None else words.ctypes.data, C.byref(m), C.byref(total)))
+        return m.value, total.value
 
     def select(self, cam, region, mask=None):
         """gsr_multi_select: Engine.select on rank 0's copy (the cloud is replicated), into a host mask -> (bool mask, n_hit, n_set)"""

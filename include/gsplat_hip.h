@@ -495,7 +495,7 @@ int  gsr_get_add(gsr_context* ctx, int64_t* adds, int64_t* added_last, int64_t* 
  * [1] device -> host copies, wall clock (0.0 for the device form)   [2] 0.0 (reserved)   [3] wall clock of the call.
  * gsr_multi_read (below, with the other gsr_multi verbs): rank 0's copy -- the cloud is replicated.
  * Out of scope: the GSplatRenderer shim and the HDK glue (their rows are the caller's own host arrays already); gsr_comm_* (each
- * rank is a plain context and reads for itself); reading by an index list or a mask; an asynchronous form; half destinations in
+ * rank is a plain context and reads for itself); reading by an index list (by a mask: "copying", below); an asynchronous form; half destinations in
  * device memory; a PLY writer (the INRIA activations are not bit-invertible, and a writer with a tolerance is its own piece of
  * work); a hidden-mask output. */
 int  gsr_read_info(gsr_context* ctx, int64_t* n_splats, int* has_sh, float origin[3]);   /* any pointer may be NULL */
@@ -515,6 +515,49 @@ typedef struct gsr_device_out {           /* DEVICE destinations, float32, the l
 } gsr_device_out;
 int  gsr_read_device(gsr_context* ctx, int64_t first, int64_t n, const gsr_device_out* out);
 int  gsr_get_read(gsr_context* ctx, int64_t* reads, int64_t* rows_last, double ms[4]);   /* any pointer may be NULL */
+
+/* ---- copying (selected resident splats read out, or duplicated, on the GPU) ---------------------------------------------------------- */
+/* The two verbs an editor offers next to delete, move and grade, for the mask gsr_select makes: EXTRACT the selection (gsr_read's
+ * contract over a mask in the place of a range) and DUPLICATE it (a copy of each selected splat appended to the cloud), without
+ * carrying the cloud over the link.  Kernels: k_copy.h -- gsr_remove's compaction with the selected splats in the survivors' place --
+ * in front of k_unpack (a read) or the ordering of an upload and k_repack (a duplicate).
+ * THE MASK is gsr_select's and gsr_remove's: ceil(n / 32) words, bit i % 32 of word i / 32 = splat i of the upload is selected; bits at
+ * indices >= n in the last word are ignored; NULL selects every splat.  mask_is_device = 0: host memory, copied before the call
+ * returns; 1: device memory of the context's device or pinned host memory, read where it is, checked like a device source before
+ * anything is launched and never written.  gsr_copy_map is the rule on the host (no context, no GPU): rows[r] (NULL: not wanted) =
+ * the upload index of the r-th set bit, ascending; *m = their number.
+ * gsr_read_masked / gsr_read_masked_device: row r of every wanted array is what gsr_read / gsr_read_device return for the splat
+ * rows[r], bit for bit -- the raw P bits, the TRUE alpha of a splat a visibility hides, the resident halves (the device form: each as
+ * the float32 of exactly that value), index 15 of the SH rows a zero half.  The destinations hold max_rows rows; the device form checks
+ * every one of them for max_rows rows before anything is launched.  *m (may be NULL) = the rows of the selection.  A selection of more
+ * than max_rows rows: GSR_E_INVALID, *m is set and no destination byte is written.  With every destination NULL (out may then be NULL
+ * too) the call is a count: *m is filled and nothing else happens; max_rows is not looked at.  Like gsr_read the call changes and
+ * invalidates nothing, does not wait for the frames in flight, and is counted by gsr_get_read (a count, a refusal and a read of no rows
+ * are not).  Of the link, a device mask and device destinations use one word: the count.
+ * gsr_duplicate: a copy of each selected splat joins the cloud at the upload indices [n, n + m), in the ascending upload order of the
+ * originals; every resident splat keeps its index.  Afterwards geoA, geoB, colour chunks, colour rows, cluster bounds, storage order and
+ * every later frame are, bit for bit, those of a fresh gsr_upload of concat(R, R[rows]), R = what gsr_read(0, n) returned before.  No
+ * row leaves the resident planes and nothing is quantised again.  Under a visibility in force the result is what gsr_add of those rows
+ * leaves: the copies carry their originals' TRUE alphas, the volumes apply to them, a mask is extended by clear bits.  A duplicate that
+ * does not fit grows the context by gsr_add_capacity as an add does; gsr_get_add reports the capacity and counts the growth (its adds
+ * and added_last stay).  *m, *n_total (may be NULL) = the copies, the splats resident now.  An empty selection changes, invalidates and
+ * writes nothing.  gsr_stats.n_splats follows; uploads and moves stay.  Synchronous; waits for every frame in flight and for the public
+ * stream first.  A failure before the first write leaves the context as it was; one after it leaves no geometry, as gsr_add's does.
+ * gsr_get_duplicate: the calls that copied something, the copies of the last one, its clock ms[4]: [0] host mask over the link
+ * [1] mark .. sort (HIP events)   [2] repack (HIP events)   [3] wall clock of the call.
+ * GSR_E_INVALID, nothing written: NULL ctx; no geometry, or an upload in progress; a device mask that fails the pointer check; for the
+ * reads what gsr_read / gsr_read_device refuse of their structs, max_rows < 0 with a destination given, a device destination that fails
+ * the pointer check for max_rows rows; for a duplicate n + m beyond 2^31 - 1.
+ * gsr_multi_read_masked: rank 0's copy, from a host mask into host arrays.  gsr_multi_duplicate: every rank, from a host mask, under
+ * gsr_multi_add's agreement rule.
+ * Out of scope: the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for the multi verbs; reading by an explicit index
+ * list; copies with a built-in offset (gsr_transform with the mask of the copies); copying between two contexts; asynchronous forms;
+ * half destinations in device memory; giving memory back. */
+int  gsr_copy_map(const uint32_t* mask, int64_t n, int32_t* rows, int64_t* m);   /* host, no context, no GPU */
+int  gsr_read_masked(gsr_context* ctx, const uint32_t* mask, int mask_is_device, int64_t max_rows, const gsr_read_arrays* out, int64_t* m);
+int  gsr_read_masked_device(gsr_context* ctx, const uint32_t* mask, int mask_is_device, int64_t max_rows, const gsr_device_out* out, int64_t* m);
+int  gsr_duplicate(gsr_context* ctx, const uint32_t* mask, int mask_is_device, int64_t* m, int64_t* n_total);
+int  gsr_get_duplicate(gsr_context* ctx, int64_t* calls, int64_t* copied_last, double ms[4]);   /* any pointer may be NULL */
 
 /* ---- selection (resident splats picked by screen region, on the GPU) --------------------------------------------------------------- */
 /* The masks gsr_set_visibility and gsr_remove take, made from what the user sees: drag a box or paint a lasso over the floaters, and
@@ -840,6 +883,12 @@ int  gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xfor
 /* gsr_grade on every rank's replica, after the same synchronisation, from a HOST mask (NULL: every splat), under the same agreement
  * rule: ranks that do not agree on the count, or a rank that fails after its first write, and NO rank keeps geometry. */
 int  gsr_multi_grade(gsr_multi* m, const uint32_t* mask_host, const gsr_grade_rule* rule, int64_t* n_graded);
+/* gsr_read_masked of rank 0's copy (the cloud is replicated), from a HOST mask (NULL: every splat) into host arrays, after the same
+ * synchronisation; no rank's state changes */
+int  gsr_multi_read_masked(gsr_multi* m, const uint32_t* mask_host, int64_t max_rows, const gsr_read_arrays* out, int64_t* n_rows);
+/* gsr_duplicate on every rank's replica, after the same synchronisation, from a HOST mask (NULL: every splat), under gsr_multi_add's
+ * agreement rule: ranks that do not agree on the total, or a rank that fails after its first write, and NO rank keeps geometry. */
+int  gsr_multi_duplicate(gsr_multi* m, const uint32_t* mask_host, int64_t* n_copied, int64_t* n_total);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);
@@ -1134,6 +1183,9 @@ int  gsr_debug_policy_state(gsr_context* ctx, int32_t* state16);
  * streams} (the owning handles of csrc/gsr_host_buffers.h; the multi-GPU layer's own buffers are not counted).  Every count goes back
  * to what it was when a context is destroyed.  No context, no GPU: four zeros in a process that never created one. */
 int  gsr_debug_live_handles(int64_t out4[4]);
+/* The bytes the context's staging arena answers for right now (uploads, the host forms of the edits and reads and the copy verbs
+ * stage there; it only grows): tests read it to know that a call had to replace the arena.  -1: ctx is NULL. */
+int64_t gsr_debug_stage_bytes(gsr_context* ctx);
 /* The frame driver's decisions (csrc/gsr_frame_plan.h, which documents the flat int32 layouts) as pure functions: which = 0 plans a
  * frame (in: the plan inputs, the slot's hints, classic_once; policy16: gsr_debug_policy's state, updated by the frame's policy events),
  * which = 1 reads an attempt's outcome from its mailbox (policy16 unused).  No context, no GPU: what tests/test_frame_plan.py drives. */
