@@ -179,6 +179,39 @@ extern "C" int gsr_debug_read_horizons(gsr_context* c, float* out4, int64_t n_ti
     return GSR_OK;
 }
 
+// every level of the pyramid the slot's NEXT frame would be culled against (sl->hpyr behind queue_frame_end's swap: levels 1..3 from the
+// dilation's wave shuffles, 4..5 from its atomics), level l at meta[2 + l], and in `meta` what gsr_pyr_max, gsr_k1_back's look-up and
+// k_tile_pass's rules took from the last frame (gsplat_hip.h lists the words).  Reads only: no resident bit, horizon, cached order,
+// hint or policy changes.
+extern "C" int gsr_debug_read_horizon_pyramid(gsr_context* c, float* out, int64_t n_floats, int32_t* meta24)
+{
+    const bool query = !out && n_floats == 0;      // (the words alone: how large is the pyramid?)
+    if (!c || !meta24 || (!query && (!out || n_floats <= 0))) return set_err(GSR_E_INVALID, "gsr_debug_read_horizon_pyramid: bad argument");
+    FrameSlot* sl = nullptr;
+    if (const int rc = debug_enter(c, "gsr_debug_read_horizon_pyramid", &sl, true)) return rc;
+    if (!sl->horizon_valid) return set_err(GSR_E_INVALID, "gsr_debug_read_horizon_pyramid: the last frame left no horizons");
+    const FrameJob& j = sl->job;
+    const GsrFrame& f = j.f;
+    const int top = GSR_PYR_LEVELS - 1;
+    const int64_t cells = (int64_t)f.pyr_off[top] + (int64_t)gsr_pyr_dim(f.tiles_x, top) * gsr_pyr_dim(f.tiles_y, top);
+    if ((!query && n_floats != cells) || cells > (int64_t)GSR_PYR_FLOATS)
+        return set_err(GSR_E_INVALID, "gsr_debug_read_horizon_pyramid: expected %lld floats", (long long)cells);
+    if (!query) HIP_TRY(hipMemcpy(out, sl->hpyr, (size_t)cells * 4, hipMemcpyDeviceToHost));
+    int o = 0;
+    meta24[o++] = f.tiles_x; meta24[o++] = f.tiles_y;
+    for (int l = 0; l < GSR_PYR_LEVELS; ++l) meta24[o++] = f.pyr_off[l];
+    meta24[o++] = f.rect_shift; meta24[o++] = f.super_shift;
+    meta24[o++] = (int32_t)f.key_min; meta24[o++] = (int32_t)f.key_max;
+    meta24[o++] = sl->hpyr_re; meta24[o++] = sl->horizon_valid ? 1 : 0;
+    meta24[o++] = f.stiles_x; meta24[o++] = list_cap(*sl);
+    // (k_tile_pass's switches of the attempt queued last: queue_frame_end)
+    meta24[o++] = (j.cull && j.dcull && j.dstat) ? 1 : 0; meta24[o++] = (j.dcull && !j.dblind) ? 1 : 0; meta24[o++] = j.cull ? 1 : 0;
+    meta24[o++] = f.shard_index; meta24[o++] = f.shard_count; meta24[o++] = f.shard_rpb; meta24[o++] = f.shard_first;
+    meta24[o++] = f.local_tiles_y;
+    static_assert(2 + GSR_PYR_LEVELS + 16 == 24, "gsr_debug_read_horizon_pyramid writes 24 words");
+    return GSR_OK;
+}
+
 // the pipeline's stable sort of (key, value) pairs on host arrays; local: the small-frame form, one scatter into BK_BUCKETS buckets of
 // width 2^shift from lo, then every bucket on its own (k_radix_local)
 static int debug_sort_pairs(gsr_context* c, uint32_t* keys, uint32_t* vals, int64_t n64, int key_bits, bool local, uint32_t lo, int shift)

@@ -881,7 +881,7 @@ k_tile_pass(const uint4* __restrict__ tile_work, GsrSumArgs g, const int32_t* __
     const uint32_t first = ((w.w >> 1) & 0x1fffu) << 10;   // list position (1024-entry granularity) of the tile's first hit
     // where the tile's next horizon sits: a quarter of what it scanned from its first hit on (+1024 entries) beyond the scan -- a
     // tile high up in a super-tile over oblique ground starts deep in the shared list, and that part is not its depth range
-    const uint32_t want = rd + ((rd > first ? rd - first : 0u) >> 2) + 1024u;
+    const uint32_t want = rd + ((rd > first ? rd - first : 0u) >> SW_HEADROOM_SHIFT) + SW_HEADROOM_ADD;
     {   // per super-tile: deepest scan of its opaque tiles, and whether one stayed open.  The tiles of a super-tile are CONSECUTIVE
         // lanes (Morton order): reduce over them first -- atomics that share a cache line serialise like atomics on one address
         // (8160 of them on five lines took 20 us).
@@ -911,7 +911,7 @@ k_tile_pass(const uint4* __restrict__ tile_work, GsrSumArgs g, const int32_t* __
         // horizons -- checks itself as always.
         const bool c3 = ok && !c2 && !(hold < 3.0e38f) && hz.depth_culled != 0;
         const uint32_t i2 = hz.lists[c2 ? (uint32_t)s0 + want : (c3 ? (uint32_t)s0 + len - 1u : 0u)].x & hz.idx_mask;      // the entry its next horizon sits at
-        const float4 P1 = hz.geoA[c1 ? i1 : 0u], P2 = hz.geoA[c2 ? i2 : 0u];
+        const float4 P1 = hz.geoA[c1 ? i1 : 0u], P2 = hz.geoA[(c2 || c3) ? i2 : 0u];   // (c3 too: its stand-in is the list's LAST ENTRY, not splat 0)
         // distance^2 = the sort key of k_preprocess.h, same operations
         float klast, hnew;
         { const float dx = P1.x - hz.cam[0], dy = P1.y - hz.cam[1], dz = P1.z - hz.cam[2]; klast = gsr_fma(dz, dz, gsr_fma(dy, dy, dx * dx)); }
@@ -1015,7 +1015,7 @@ k_slab_mid(const uint4* __restrict__ tile_work_a, GsrSumArgs g, const int32_t* _
         const uint32_t es = (w.w >> 16) & 0xffu;      // (a finished tile: every pixel opaque, covered or not)
         const uint32_t rd = (es == 0xffu || (es << 10) > w.x) ? w.x : (es << 10);
         const uint32_t first = ((w.w >> 1) & 0x1fffu) << 10;
-        const uint32_t want = rd + ((rd > first ? rd - first : 0u) >> 2) + 1024u;
+        const uint32_t want = rd + ((rd > first ? rd - first : 0u) >> SW_HEADROOM_SHIFT) + SW_HEADROOM_ADD;
         const bool c2 = opaque && rd > 0u && rd <= len && want < len;
         const uint32_t i2 = hz.lists[c2 ? (uint32_t)s0 + want : 0u].x & hz.idx_mask;
         const float4 P2 = hz.geoA[c2 ? i2 : 0u];

@@ -197,7 +197,7 @@ C_ABI_SYMBOLS = [
     "gsr_upload_begin", "gsr_upload_append", "gsr_upload_append_raw", "gsr_upload_end", "gsr_upload_abort", "gsr_upload", "gsr_set_row_shard", "gsr_band_rows",
     "gsr_stitch_bands", "gsr_render", "gsr_render_depth", "gsr_render_wire", "gsr_render_wire_over", "gsr_synchronize", "gsr_get_stats", "gsr_stats_reset", "gsr_set_option",
     "gsr_debug_read_records", "gsr_debug_read_depth_order", "gsr_debug_read_storage_order", "gsr_debug_read_tile_lists", "gsr_debug_sort_pairs", "gsr_debug_sort_pairs_local", "gsr_debug_policy", "gsr_debug_policy_state", "gsr_debug_frame_plan",
-    "gsr_debug_read_tile_work", "gsr_debug_read_horizons", "gsr_debug_read_cull",
+    "gsr_debug_read_tile_work", "gsr_debug_read_horizons", "gsr_debug_read_horizon_pyramid", "gsr_debug_read_cull",
     "gsr_multi_create", "gsr_multi_destroy", "gsr_multi_count", "gsr_multi_transport", "gsr_multi_context",
     "gsr_multi_set_stream", "gsr_multi_set_option", "gsr_multi_upload_begin", "gsr_multi_upload_append",
     "gsr_multi_upload_end", "gsr_multi_upload_abort", "gsr_multi_upload", "gsr_multi_render", "gsr_multi_render_depth",
@@ -263,6 +263,11 @@ SORT_GLOBAL, SORT_GLOBAL_MID, SORT_LOCAL_GATHER, SORT_LOCAL_K1, SORT_LOCAL_DIREC
 PLAN_FIELDS = ("deferred", "lazy", "cull", "jumped", "cull_dilate", "phase", "timing", "timing_all", "dcull", "cache_hit", "want_pos",
                "ordered", "key_bits", "n_slots", "held", "local", "local_phase", "k1_scatters", "bk_lo", "bk_shift", "scatter_direct",
                "mid_sort", "k1_grid", "bn_items", "bn_blocks", "bn_grid")
+
+# the int32 words of gsr_debug_read_horizon_pyramid, in their order (the six level offsets are one entry)
+PYRAMID_LEVELS = 6
+PYRAMID_META_FIELDS = ("tiles_x", "tiles_y", "pyr_off", "rect_shift", "super_shift", "key_min", "key_max", "hpyr_re", "horizon_valid", "stiles_x",
+                       "list_cap", "stat_in_use", "depth_culled", "culled", "shard_index", "shard_count", "shard_rpb", "shard_first", "local_tiles_y")
 
 POLICY_FIELDS = ("cull_pays", "cull_weak", "vis_unculled", "cull_holdoff", "cull_backoff", "cull_streak", "cull_dilate", "opt_dilate",
                  "slab_holdoff", "local_fails", "local_holdoff")
@@ -385,6 +390,7 @@ def load_library() -> C.CDLL:
     L.gsr_debug_frame_plan.argtypes = [i32, vp, vp, vp]
     L.gsr_debug_read_tile_work.argtypes = [vp, vp, i64]
     L.gsr_debug_read_horizons.argtypes = [vp, vp, i64]
+    L.gsr_debug_read_horizon_pyramid.argtypes = [vp, vp, i64, vp]
     L.gsr_target_pixel_bytes.argtypes = [i32]
     L.gsr_set_target_format.argtypes = [vp, i32]
     L.gsr_get_target_format.argtypes = [vp]
@@ -1722,6 +1728,24 @@ class Engine:
         out = np.zeros((4, tiles_y, tiles_x), np.float32)
         _check(self.L.gsr_debug_read_horizons(self.h, out.ctypes.data, tiles_x * tiles_y))
         return out
+
+    def debug_horizon_pyramid(self):
+        """(levels, meta): the six levels of the max pyramid the slot's next frame would be culled against, level l a float32 array
+        [((tiles_y - 1) >> l) + 1, ((tiles_x - 1) >> l) + 1] over the whole image of the last frame, and the dict of
+        PYRAMID_META_FIELDS (pyr_off: the six level offsets; key_min / key_max as unsigned)"""
+        words = np.zeros(24, np.int32)
+        _check(self.L.gsr_debug_read_horizon_pyramid(self.h, None, 0, words.ctypes.data))      # (the sizes)
+        tx, ty = int(words[0]), int(words[1])
+        dims = [(((ty - 1) >> l) + 1, ((tx - 1) >> l) + 1) for l in range(PYRAMID_LEVELS)]
+        flat = np.zeros(sum(h * w for h, w in dims), np.float32)
+        _check(self.L.gsr_debug_read_horizon_pyramid(self.h, flat.ctypes.data, flat.size, words.ctypes.data))
+        w = [int(x) for x in words]
+        vals = w[:2] + [w[2:2 + PYRAMID_LEVELS]] + w[2 + PYRAMID_LEVELS:]
+        meta = dict(zip(PYRAMID_META_FIELDS, vals))
+        meta["key_min"] &= 0xffffffff
+        meta["key_max"] &= 0xffffffff
+        levels = [flat[o:o + h * w_].reshape(h, w_).copy() for o, (h, w_) in zip(meta["pyr_off"], dims)]
+        return levels, meta
 
     def debug_sort_pairs(self, keys: np.ndarray, vals: np.ndarray, key_bits: int = 32, local=None):
         """the pipeline's stable radix sort on host arrays; local = (bucket_lo, bucket_shift): the small-frame form (BK_BUCKETS = 1024 buckets of

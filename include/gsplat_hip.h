@@ -1139,6 +1139,16 @@ int  gsr_debug_read_tile_work(gsr_context* ctx, uint32_t* work4, int64_t n_tiles
  * next frame would be culled against (distance^2, dilated; +inf = none), the raw horizons (sign bit = the tile's status), the dilated
  * status, and the covered depths of the last depth-tested frame as K1 saw them */
 int  gsr_debug_read_horizons(gsr_context* ctx, float* out4, int64_t n_tiles);
+/* ALL levels of the max pyramid the slot's next frame would be culled against (six: level l holds ((tiles_x - 1) >> l) + 1 by
+ * ((tiles_y - 1) >> l) + 1 cells, row by row, from float meta24[2 + l] on; level 0 is the first plane of gsr_debug_read_horizons), and
+ * what a look-up in it needs, as 24 int32: [0] tiles_x [1] tiles_y (whole image) [2..7] the levels' first cells [8] rect_shift
+ * [9] super_shift [10] key_min [11] key_max of the last frame (uint32 bits) [12] the dilation radius built into the pyramid
+ * [13] horizons valid (1) [14] stiles_x [15] the entries the list buffer holds; of the attempt queued last: [16] it applied the tiles'
+ * status [17] it dropped splats behind the depth buffer where no horizon applied [18] it was culled; [19] shard index [20] count
+ * [21] rows per band (0 = interleaved) [22] the band's first tile row [23] tile rows of this shard.  n_floats = the cells of all levels;
+ * out = NULL with n_floats = 0 fills the words alone (the sizes a caller needs for the call proper).
+ * GSR_E_INVALID before the first frame, after a frame that left no horizons, and for another count.  Changes nothing. */
+int  gsr_debug_read_horizon_pyramid(gsr_context* ctx, float* out, int64_t n_floats, int32_t* meta24);
 
 /* Stand-alone device radix sort of (key,value) u32 pairs on bits [0, key_bits):
  * the sort the pipeline uses, exposed for parity tests (host pointers). */

@@ -223,6 +223,26 @@ def test_read_backs_after_a_frame(pkg):
             assert len(pv) == st["pairs_total"] and set(pv.tolist()) <= set(depth_order.tolist())
             assert eng.debug_records(n)["visible"].sum() == len(depth_order)
             assert eng.debug_tile_work().shape == (2, 2, 4) and eng.debug_horizons(2, 2).shape == (4, 2, 2)
+            # (a frame this small leaves no horizons: the pyramid's door says so in its own name; a context that prepares them on every
+            #  frame hands back six levels over the 2 x 2 tiles, and refuses another count and NULL outputs)
+            pyr, words = _buf(4 + 5, np.float32), _buf(24, np.int32)
+            assert eng.L.gsr_debug_read_horizon_pyramid(eng.h, pyr.ctypes.data, 9, words.ctypes.data) == GSR_E_INVALID
+            assert b"gsr_debug_read_horizon_pyramid" in eng.L.gsr_last_error()
+            with pkg.Engine(0) as H:
+                H.set_option(pkg.engine.OPT_OCCLUSION_CULL, 2)
+                H.upload(s)
+                assert H.L.gsr_debug_read_horizon_pyramid(H.h, pyr.ctypes.data, 9, words.ctypes.data) == GSR_E_INVALID, "no frame yet"
+                assert_same_pixels(H.render(cam), first, "the frame that leaves horizons")
+                levels, meta = H.debug_horizon_pyramid()
+                assert [l.shape for l in levels] == [(2, 2)] + [(1, 1)] * 5 and all(l.dtype == np.float32 for l in levels)
+                assert set(meta) == set(pkg.engine.PYRAMID_META_FIELDS) and meta["pyr_off"] == [0, 4, 5, 6, 7, 8]
+                assert (meta["tiles_x"], meta["tiles_y"], meta["horizon_valid"], meta["rect_shift"]) == (2, 2, 1, 0)
+                assert np.array_equal(levels[0].view(np.uint32), H.debug_horizons(2, 2)[0].view(np.uint32))
+                for count, out, wd in ((8, pyr, words), (10, pyr, words), (9, None, words), (9, pyr, None)):
+                    rc = H.L.gsr_debug_read_horizon_pyramid(H.h, None if out is None else out.ctypes.data, count, None if wd is None else wd.ctypes.data)
+                    assert rc == GSR_E_INVALID, (count, out is None, wd is None)
+                words[:] = 0                # (no output and no count: the words alone)
+                assert H.L.gsr_debug_read_horizon_pyramid(H.h, None, 0, words.ctypes.data) == 0 and words[:3].tolist() == [2, 2, 0]
             assert set(eng.debug_last_plan()) == set(pkg.engine.PLAN_FIELDS)
             # the pipeline's sort on 1000 pairs, both forms
             rng = np.random.default_rng(5)
