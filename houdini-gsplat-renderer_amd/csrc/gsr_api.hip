@@ -248,6 +248,20 @@ struct FrameSlot : SlotSplatArrays {
     bool ev_all = false;             // all seven stage events were recorded (timing level 2), not just the blend kernel's
 };
 
+// What a gsr_get_* of the resident-edit family reports of its verb: the calls, the count of the last one, and its clock (each verb's
+// header names the four entries).  report(): into the caller's pointers, any of them NULL.
+struct EditTally {
+    int64_t calls = 0, last = 0;
+    double ms[4] = {0.0, 0.0, 0.0, 0.0};
+    int report(int64_t* calls_out, int64_t* last_out, double* ms_out) const
+    {
+        if (calls_out) *calls_out = calls;
+        if (last_out) *last_out = last;
+        if (ms_out) for (int k = 0; k < 4; ++k) ms_out[k] = ms[k];
+        return GSR_OK;
+    }
+};
+
 struct gsr_context {
     int device = 0;
     Stream own_stream;
@@ -356,33 +370,18 @@ struct gsr_context {
     PinnedMem<unsigned long long> vis_h_counters; // ... and where they are read back: pinned host memory, like the slots' read-backs
     int64_t vis_hidden = 0;            // what the last application hid
     // gsr_remove (k_remove.h): the SECOND array of true alphas the compaction writes (swapped with alpha0 like the planes; only with a
-    // visibility in force), the pinned words the survivor count arrives in, and what gsr_get_removal reports
+    // visibility in force)
     DevMem<float> alpha0_2;
-    PinnedMem<uint32_t> rm_h_total;
-    int64_t rm_calls = 0, rm_last = 0;
-    double rm_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_add (k_add.h): what gsr_get_add reports (the capacity in force is c->cap)
-    int64_t add_calls = 0, add_last = 0, add_grows = 0;
-    double add_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_read / gsr_read_device (k_read.h): what gsr_get_read reports
-    int64_t rd_calls = 0, rd_last = 0;
-    double rd_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_select (k_select.h): the counter slots of k_select, where they are read back, and what gsr_get_select reports
+    // gsr_select (k_select.h): the counter slots of k_select, and where they are read back
     DevMem<unsigned long long> sel_counters;
     PinnedMem<unsigned long long> sel_h_counters;
-    int64_t sel_calls = 0, sel_last = 0;
-    double sel_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_transform (k_transform.h): the pinned word the mask's bit count arrives in, and what gsr_get_transform reports
-    PinnedMem<uint32_t> xf_h_count;
-    int64_t xf_calls = 0, xf_last = 0;
-    double xf_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_grade (k_grade.h): what gsr_get_grade reports (the mask's bit count arrives in xf_h_count)
-    int64_t gr_calls = 0, gr_last = 0;
-    double gr_ms[4] = {0.0, 0.0, 0.0, 0.0};
-    // gsr_read_masked / gsr_duplicate (k_copy.h): the pinned word the selection's count arrives in, and what gsr_get_duplicate reports
-    PinnedMem<uint32_t> cp_h_total;
-    int64_t dup_calls = 0, dup_last = 0;
-    double dup_ms[4] = {0.0, 0.0, 0.0, 0.0};
+    // the mask verbs (gsr_remove, gsr_read_masked, gsr_duplicate, gsr_transform, gsr_grade): the pinned words a count arrives in
+    // (ensure_h_word; two words, read behind a wait of the verb's own)
+    PinnedMem<uint32_t> h_word;
+    // what gsr_get_removal, _add, _read, _select, _transform, _grade and _duplicate report (gsr_get_add: also the capacity in force,
+    // c->cap, and the adds that grew it)
+    EditTally rm, add, rd, sel, xf, gr, dup;
+    int64_t add_grows = 0;
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }

@@ -48,6 +48,7 @@
 
 #include "../../include/gsplat_hip.h"
 #include "gsr_balance.h"
+#include "gsr_replica.h"
 
 // hooks into gsr_api.hip (hidden symbols of the same library)
 int gsr_internal_frame_begin(gsr_context* c, const gsr_camera* cam, const float* depth, int depth_is_device, float* out_dev);
@@ -600,184 +601,124 @@ extern "C" int gsr_multi_upload(gsr_multi* m, int64_t n, const float* P, const u
     return rc;
 }
 
+// What every gsr_multi_* verb on the resident cloud does first: a NULL m or argument (args: the verb's own pointers are given), an
+// upload in progress, and then the frames and the gather in flight finished on every rank
+static int multi_enter(gsr_multi* m, bool args, const char* who)
+{
+    if (!m || !args) return fail(GSR_E_INVALID, "%s: NULL", who);
+    if (m->uploading) return fail(GSR_E_INVALID, "%s: upload in progress", who);
+    return gsr_multi_synchronize(m);
+}
+
+// A verb that edits every rank's replica (remove, add, duplicate, transform, grade): verb(g, counts) on every rank, its K counts
+// starting at -1, then gsr_replica.h's verdict.  The replicas must stay replicas: ranks that do not agree on the counts (or of which
+// one failed behind its first write, and so holds nothing) all give their geometry up.  out[K]: rank 0's counts (NULL: not wanted).
+// Balanced bands: as after an upload, the boundaries stay, and the next evaluation reads the row sums of the new cloud's frames.
+template <int K, class Verb>
+static int multi_edit(gsr_multi* m, bool args, const char* who, const char* noun, int64_t* const (&out)[K], Verb verb)
+{
+    int rc = multi_enter(m, args, who);
+    if (rc) return rc;
+    const int G = (int)m->ctx.size();
+    std::vector<int64_t> counts((size_t)G * K, -1);
+    int64_t* const cp = counts.data();
+    rc = for_each_rank(m, [=](int g) { return verb(g, cp + (size_t)g * K); });
+    switch (gsr_replica_verdict(rc, G, K, cp)) {
+    case GSR_REPLICA_KEEP_REFUSAL: return rc;     // every rank refused before its first write: the replicas are what they were
+    case GSR_REPLICA_AGREED: break;
+    default:
+        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
+        return rc ? rc : fail(GSR_E_INVALID, "%s: the ranks do not agree on %s: the geometry is dropped on all of them", who, noun);
+    }
+    for (int k = 0; k < K; ++k)
+        if (out[k]) *out[k] = counts[(size_t)k];
+    return GSR_OK;
+}
+
+extern "C" int gsr_debug_replica_verdict(int rc, int ranks, int per_rank, const int64_t* counts, int* verdict)
+{
+    const int v = verdict ? gsr_replica_verdict(rc, ranks, per_rank, counts) : -1;
+    if (v < 0) return fail(GSR_E_INVALID, "gsr_debug_replica_verdict: bad argument");
+    *verdict = v;
+    return GSR_OK;
+}
+
 // the resident cloud edited in place on every rank (it is replicated)
 extern "C" int gsr_multi_update(gsr_multi* m, int64_t first, int64_t n, const gsr_attr_update* u)
 {
-    if (!m || !u) return fail(GSR_E_INVALID, "gsr_multi_update: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_update: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return for_each_rank(m, [=](int g) { return gsr_update(m->ctx[g], first, n, u); });
+    const int rc = multi_enter(m, u, "gsr_multi_update");
+    return rc ? rc : for_each_rank(m, [=](int g) { return gsr_update(m->ctx[g], first, n, u); });
 }
 
 // ... and moved on every rank: each orders and repacks its own replica
 extern "C" int gsr_multi_move(gsr_multi* m, int64_t first, int64_t n, const float* P, const float origin[3], const gsr_attr_update* u)
 {
-    if (!m || !P) return fail(GSR_E_INVALID, "gsr_multi_move: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_move: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return for_each_rank(m, [=](int g) { return gsr_move(m->ctx[g], first, n, P, origin, u); });
+    const int rc = multi_enter(m, P, "gsr_multi_move");
+    return rc ? rc : for_each_rank(m, [=](int g) { return gsr_move(m->ctx[g], first, n, P, origin, u); });
 }
 
 // ... and hidden on every rank: each applies the rule to its own replica
 extern "C" int gsr_multi_set_visibility(gsr_multi* m, const gsr_visibility* v)
 {
-    if (!m) return fail(GSR_E_INVALID, "gsr_multi_set_visibility: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_set_visibility: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return for_each_rank(m, [=](int g) { return gsr_set_visibility(m->ctx[g], v); });
+    const int rc = multi_enter(m, true, "gsr_multi_set_visibility");
+    return rc ? rc : for_each_rank(m, [=](int g) { return gsr_set_visibility(m->ctx[g], v); });
 }
 
-// ... and removed on every rank: each compacts, orders and repacks its own replica.  The replicas must stay replicas: ranks that do
-// not agree on the splats left (or of which one failed behind its first write, and so holds nothing) all give their geometry up.
-// Balanced bands: as after an upload, the boundaries stay, and the next evaluation reads the row sums of the survivors' frames.
+// ... and removed on every rank: each compacts, orders and repacks its own replica
 extern "C" int gsr_multi_remove(gsr_multi* m, const uint32_t* mask_host, int flags, int64_t* n_left)
 {
-    if (!m) return fail(GSR_E_INVALID, "gsr_multi_remove: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_remove: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    const int G = (int)m->ctx.size();
-    std::vector<int64_t> left((size_t)G, -1);
-    int64_t* const lp = left.data();
-    rc = for_each_rank(m, [=](int g) { return gsr_remove(m->ctx[g], mask_host, 0, flags, lp + g); });
-    bool any_done = false, same = rc == GSR_OK;
-    for (int g = 0; g < G; ++g) any_done = any_done || left[(size_t)g] >= 0;
-    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
-    for (int g = 1; g < G && same; ++g) same = left[(size_t)g] == left[0];
-    if (!same) {
-        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
-        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_remove: the ranks do not agree on the splats left: the geometry is dropped on all of them");
-    }
-    if (n_left) *n_left = left[0];
-    return GSR_OK;
+    return multi_edit<1>(m, true, "gsr_multi_remove", "the splats left", {n_left},
+                         [=](int g, int64_t* k) { return gsr_remove(m->ctx[g], mask_host, 0, flags, k); });
 }
 
-// ... and added to on every rank: each stages the new rows, orders and packs its own replica.  gsr_multi_remove's agreement rule.
+// ... and added to on every rank: each stages the new rows, orders and packs its own replica
 extern "C" int gsr_multi_add(gsr_multi* m, int64_t n_new, const float* P, const uint16_t* Cd, const float* alpha, const uint16_t* scale,
                              const uint16_t* orient, const uint16_t* shx, const uint16_t* shy, const uint16_t* shz, int64_t* n_total)
 {
-    if (!m) return fail(GSR_E_INVALID, "gsr_multi_add: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_add: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    const int G = (int)m->ctx.size();
-    std::vector<int64_t> total((size_t)G, -1);
-    int64_t* const tp = total.data();
-    rc = for_each_rank(m, [=](int g) { return gsr_add(m->ctx[g], n_new, P, Cd, alpha, scale, orient, shx, shy, shz, tp + g); });
-    bool any_done = false, same = rc == GSR_OK;
-    for (int g = 0; g < G; ++g) any_done = any_done || total[(size_t)g] >= 0;
-    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
-    for (int g = 1; g < G && same; ++g) same = total[(size_t)g] == total[0];
-    if (!same) {
-        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
-        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_add: the ranks do not agree on the splat count: the geometry is dropped on all of them");
-    }
-    if (n_total) *n_total = total[0];
-    return GSR_OK;
+    return multi_edit<1>(m, true, "gsr_multi_add", "the splat count", {n_total},
+                         [=](int g, int64_t* k) { return gsr_add(m->ctx[g], n_new, P, Cd, alpha, scale, orient, shx, shy, shz, k); });
 }
 
 // ... and read back from rank 0's replica (gsr_read: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_arrays* out)
 {
-    if (!m || !out) return fail(GSR_E_INVALID, "gsr_multi_read: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_read: upload in progress");
-    const int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return gsr_read(m->ctx[0], first, n, out);
+    const int rc = multi_enter(m, out, "gsr_multi_read");
+    return rc ? rc : gsr_read(m->ctx[0], first, n, out);
 }
 
 // ... and read back by a mask from rank 0's replica (gsr_read_masked from a host mask: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_read_masked(gsr_multi* m, const uint32_t* mask_host, int64_t max_rows, const gsr_read_arrays* out, int64_t* n_rows)
 {
-    if (!m) return fail(GSR_E_INVALID, "gsr_multi_read_masked: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_read_masked: upload in progress");
-    const int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return gsr_read_masked(m->ctx[0], mask_host, 0, max_rows, out, n_rows);
+    const int rc = multi_enter(m, true, "gsr_multi_read_masked");
+    return rc ? rc : gsr_read_masked(m->ctx[0], mask_host, 0, max_rows, out, n_rows);
 }
 
-// ... and duplicated on every rank: each compacts, orders and repacks its own replica.  gsr_multi_add's agreement rule.
+// ... and duplicated on every rank: each compacts, orders and repacks its own replica
 extern "C" int gsr_multi_duplicate(gsr_multi* m, const uint32_t* mask_host, int64_t* n_copied, int64_t* n_total)
 {
-    if (!m) return fail(GSR_E_INVALID, "gsr_multi_duplicate: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_duplicate: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    const int G = (int)m->ctx.size();
-    std::vector<int64_t> total((size_t)G, -1), copied((size_t)G, -1);
-    int64_t* const tp = total.data();
-    int64_t* const cp = copied.data();
-    rc = for_each_rank(m, [=](int g) { return gsr_duplicate(m->ctx[g], mask_host, 0, cp + g, tp + g); });
-    bool any_done = false, same = rc == GSR_OK;
-    for (int g = 0; g < G; ++g) any_done = any_done || total[(size_t)g] >= 0;
-    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
-    for (int g = 1; g < G && same; ++g) same = total[(size_t)g] == total[0] && copied[(size_t)g] == copied[0];
-    if (!same) {
-        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
-        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_duplicate: the ranks do not agree on the splat count: the geometry is dropped on all of them");
-    }
-    if (n_copied) *n_copied = copied[0];
-    if (n_total) *n_total = total[0];
-    return GSR_OK;
+    return multi_edit<2>(m, true, "gsr_multi_duplicate", "the splat count", {n_copied, n_total},
+                         [=](int g, int64_t* k) { return gsr_duplicate(m->ctx[g], mask_host, 0, k, k + 1); });
 }
 
 // ... and selected by screen region on rank 0's replica (gsr_select into a host mask: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set)
 {
-    if (!m || !cam || !region || !mask_host) return fail(GSR_E_INVALID, "gsr_multi_select: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_select: upload in progress");
-    const int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    return gsr_select(m->ctx[0], cam, region, mask_host, 0, n_hit, n_set);
+    const int rc = multi_enter(m, cam && region && mask_host, "gsr_multi_select");
+    return rc ? rc : gsr_select(m->ctx[0], cam, region, mask_host, 0, n_hit, n_set);
 }
 
-// ... and transformed on every rank: each bakes the transform into its own replica and re-orders it.  gsr_multi_remove's agreement rule.
+// ... and transformed on every rank: each bakes the transform into its own replica and re-orders it
 extern "C" int gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved)
 {
-    if (!m || !x) return fail(GSR_E_INVALID, "gsr_multi_transform: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_transform: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    const int G = (int)m->ctx.size();
-    std::vector<int64_t> moved((size_t)G, -1);
-    int64_t* const mp = moved.data();
-    rc = for_each_rank(m, [=](int g) { return gsr_transform(m->ctx[g], mask_host, 0, x, mp + g); });
-    bool any_done = false, same = rc == GSR_OK;
-    for (int g = 0; g < G; ++g) any_done = any_done || moved[(size_t)g] >= 0;
-    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
-    for (int g = 1; g < G && same; ++g) same = moved[(size_t)g] == moved[0];
-    if (!same) {
-        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
-        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_transform: the ranks do not agree on the splats moved: the geometry is dropped on all of them");
-    }
-    if (n_moved) *n_moved = moved[0];
-    return GSR_OK;
+    return multi_edit<1>(m, x, "gsr_multi_transform", "the splats moved", {n_moved},
+                         [=](int g, int64_t* k) { return gsr_transform(m->ctx[g], mask_host, 0, x, k); });
 }
 
-// ... and graded on every rank: each bakes the rule into its own replica, in place.  gsr_multi_transform's agreement rule.
+// ... and graded on every rank: each bakes the rule into its own replica, in place
 extern "C" int gsr_multi_grade(gsr_multi* m, const uint32_t* mask_host, const gsr_grade_rule* rule, int64_t* n_graded)
 {
-    if (!m || !rule) return fail(GSR_E_INVALID, "gsr_multi_grade: NULL");
-    if (m->uploading) return fail(GSR_E_INVALID, "gsr_multi_grade: upload in progress");
-    int rc = gsr_multi_synchronize(m);
-    if (rc) return rc;
-    const int G = (int)m->ctx.size();
-    std::vector<int64_t> graded((size_t)G, -1);
-    int64_t* const gp = graded.data();
-    rc = for_each_rank(m, [=](int g) { return gsr_grade(m->ctx[g], mask_host, 0, rule, gp + g); });
-    bool any_done = false, same = rc == GSR_OK;
-    for (int g = 0; g < G; ++g) any_done = any_done || graded[(size_t)g] >= 0;
-    if (rc && rc != GSR_E_HIP && !any_done) return rc;             // every rank refused before its first write: the replicas are what they were
-    for (int g = 1; g < G && same; ++g) same = graded[(size_t)g] == graded[0];
-    if (!same) {
-        for (gsr_context* c : m->ctx) gsr_internal_drop_geometry(c);
-        return rc ? rc : fail(GSR_E_INVALID, "gsr_multi_grade: the ranks do not agree on the splats graded: the geometry is dropped on all of them");
-    }
-    if (n_graded) *n_graded = graded[0];
-    return GSR_OK;
+    return multi_edit<1>(m, rule, "gsr_multi_grade", "the splats graded", {n_graded},
+                         [=](int g, int64_t* k) { return gsr_grade(m->ctx[g], mask_host, 0, rule, k); });
 }
 
 // ---- balanced bands ------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10 - 3.12): gsr_update, gsr_move, the
+// gsr_resident_edit.h -- the verbs that edit the resident cloud without a re-upload (DESIGN.md 3.2 - 3.7, 3.10 - 3.13): gsr_update, gsr_move, the
 // device sources, gsr_set_visibility, gsr_remove, gsr_add, gsr_duplicate, gsr_transform, gsr_grade.  Host code only; included once, at the end of gsr_api.hip, which has the
 // context, the frame slots, the upload arena (ensure_stage, ensure_up_events, stage_host_rows), the ordering of an upload (position_box,
 // morton_order), new_cloud_state / drop_geometry, and the <SH> launches of k_update, k_update_f32 and k_repack (launch_update,
@@ -685,6 +685,65 @@ extern "C" int gsr_get_visibility(gsr_context* c, gsr_visibility* out, int64_t* 
 }
 
 // ---------------------------------------------------------------------------
+// The mask intake of gsr_remove, gsr_read_masked*, gsr_duplicate, gsr_transform and gsr_grade: the caller's
+// ceil(n / 32) words over the n resident splats, in host or device memory (NULL: the verb says what).  Where each verb checks, waits
+// and stages is the verb's own.
+struct MaskArg {
+    const uint32_t* mask;
+    bool is_device;
+    uint32_t n;
+
+    size_t words() const { return ((size_t)n + 31) / 32; }
+    // what a host mask takes of the staging arena (0: a device or NULL mask)
+    size_t stage_bytes() const { return mask && !is_device ? words() * 4 : 0; }
+    // a device mask before anything is launched (the empty cloud has no word to look at)
+    int check(gsr_context* c, const char* who) const
+    {
+        return mask && is_device && n ? check_device_source(c, mask, words() * 4, who, "mask") : GSR_OK;
+    }
+    // *dmask = the words the kernels read: a host mask copied to `at` of the arena and waited for (the caller's mask may be freed on
+    // return; link_ms, may be NULL, += what that took), a device mask as it is, NULL for NULL
+    hipError_t to_device(gsr_context* c, hipStream_t us, size_t at, double* link_ms, const uint32_t** dmask) const
+    {
+        *dmask = mask;
+        if (!stage_bytes()) return hipSuccess;
+        const double t0 = up_now_ms();
+        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + at);
+        hipError_t e = hipMemcpyAsync(staged, mask, words() * 4, hipMemcpyHostToDevice, us);
+        if (e == hipSuccess) e = hipStreamSynchronize(us);
+        if (e != hipSuccess) return e;
+        if (link_ms) *link_ms += up_now_ms() - t0;
+        *dmask = staged;
+        return hipSuccess;
+    }
+};
+
+// the pinned words a mask verb's count is read back into
+static int ensure_h_word(gsr_context* c, const char* who)
+{
+    if (!c->h_word && c->h_word.alloc(2, 0)) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "%s: no pinned host memory for the count", who);
+    }
+    return GSR_OK;
+}
+
+// *count = the set bits of the device mask dmask below n (k_mask_count into the word at `at` of the arena; waited for).  The caller
+// has ensured the arena and the pinned words.  More than n is a HIP failure.
+static int count_mask_bits(gsr_context* c, hipStream_t us, uint32_t n, const uint32_t* dmask, size_t at, const char* who, uint32_t* count)
+{
+    uint32_t* const dcount = reinterpret_cast<uint32_t*>(c->stage + at);
+    HIP_TRY(hipMemsetAsync(dcount, 0, 4, us));
+    hipLaunchKernelGGL(k_mask_count, dim3(div_up((uint32_t)(((size_t)n + 31) / 32), 256)), dim3(256), 0, us, n, dmask, dcount);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_word, dcount, 4, hipMemcpyDeviceToHost, us));
+    HIP_TRY(hipStreamSynchronize(us));
+    *count = c->h_word[0];
+    if (*count > n) return set_err(GSR_E_HIP, "%s: the reduction counted %u bits below %u", who, *count, n);
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Removal (k_remove.h): resident splats deleted on the GPU.  A move whose source is a subset: mark, scan and compact in
 // upload order, then the ordering of an upload over the survivors' positions, k_repack into the spare planes, the swap.
 extern "C" int gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_index, int64_t* n_left)
@@ -703,10 +762,7 @@ extern "C" int gsr_remove_map(const uint32_t* mask, int64_t n, int32_t* new_inde
 extern "C" int gsr_get_removal(gsr_context* c, int64_t* removals, int64_t* removed_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_removal: ctx is NULL");
-    if (removals) *removals = c->rm_calls;
-    if (removed_last) *removed_last = c->rm_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->rm_ms[k];
-    return GSR_OK;
+    return c->rm.report(removals, removed_last, ms);
 }
 
 extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_device, int flags, int64_t* n_left)
@@ -718,9 +774,10 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     int rc = refuse_edit(c, who);
     if (rc) return rc;
     const uint32_t n = c->n;
-    const size_t words = ((size_t)n + 31) / 32;
+    const MaskArg mk{mask, mask_is_device != 0, n};
+    const size_t words = mk.words();
     HIP_TRY(hipSetDevice(c->device));
-    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    if ((rc = mk.check(c, who))) return rc;
     Reorder ro(c, who, true);
     if ((rc = sync_all(c))) return rc;   // the public stream (a producer of a device mask queued there has finished), and no write under a frame in flight
     const bool hidden = (flags & GSR_REMOVE_HIDDEN) && c->vis_on;
@@ -733,13 +790,9 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     const uint32_t nblocks = div_up(n, (uint32_t)GSR_REMOVE_BLOCK);
     size_t off = 0;
     auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
-    const size_t oMask = place(mask && !mask_is_device ? words * 4 : 0), oKeep = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8), oCnt = place((size_t)nblocks * 4),
+    const size_t oMask = place(mk.stage_bytes()), oKeep = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8), oCnt = place((size_t)nblocks * 4),
                  oOff = place(((size_t)nblocks + 1) * 4), oP = place((size_t)n * 12), oSlot = place((size_t)n * 4);
-    if ((rc = ensure_stage(c, off))) return rc;
-    if (!c->rm_h_total && c->rm_h_total.alloc(2, 0)) {
-        (void)hipGetLastError();
-        return set_err(GSR_E_OOM, "gsr_remove: no pinned host memory for the survivor count");
-    }
+    if ((rc = ensure_stage(c, off)) || (rc = ensure_h_word(c, who))) return rc;
     if ((rc = ro.old_inverse(true))) return rc;        // (the mark reads through it)
     const uint32_t* const inv_old = ro.inv_old;
     unsigned long long* const keep = reinterpret_cast<unsigned long long*>(c->stage + oKeep);
@@ -748,15 +801,8 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
     float* const Pup = reinterpret_cast<float*>(c->stage + oP);
     uint32_t* const src_slot = reinterpret_cast<uint32_t*>(c->stage + oSlot);
     // ---- 1, 2. which splats stay, and how many: nothing resident is written yet
-    const uint32_t* dmask = mask;
-    if (mask && !mask_is_device) {
-        const double t0 = up_now_ms();
-        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
-        HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
-        HIP_TRY(hipStreamSynchronize(us));             // the caller's mask may be freed on return
-        ro.link_ms = up_now_ms() - t0;
-        dmask = staged;
-    }
+    const uint32_t* dmask = nullptr;
+    HIP_TRY(mk.to_device(c, us, oMask, &ro.link_ms, &dmask));
     HIP_TRY(hipEventRecord(c->up_ev[0], us));
     if (hidden)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<true>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, c->vis_mask, c->vis, keep, counts);
@@ -764,9 +810,9 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_remove_mark<false>), dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, inv_old, c->geoA, (const uint32_t*)nullptr, GsrVisRule{}, keep, counts);
     hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, counts, offsets);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->rm_h_total, offsets + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us));
+    HIP_TRY(hipMemcpyAsync(c->h_word, offsets + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us));
     HIP_TRY(hipStreamSynchronize(us));
-    const uint32_t n1 = c->rm_h_total[0];
+    const uint32_t n1 = c->h_word[0];
     if (n1 > n) return set_err(GSR_E_HIP, "gsr_remove: the scan counted %u survivors of %u splats", n1, n);
     if (n1 == n) {                                     // nothing goes: no resident bit changes, nothing is invalidated
         if (n_left) *n_left = (int64_t)n;
@@ -819,9 +865,9 @@ extern "C" int gsr_remove(gsr_context* c, const uint32_t* mask, int mask_is_devi
         if (vis) c->alpha0.swap(c->alpha0_2);
     }
     // 6. the volumes against the survivors, in the order they sit in now; a new cloud to everything a frame keeps
-    if ((rc = ro.finish(c->rm_ms, false))) return rc;
-    c->rm_calls += 1;
-    c->rm_last = (int64_t)n - (int64_t)n1;
+    if ((rc = ro.finish(c->rm.ms, false))) return rc;
+    c->rm.calls += 1;
+    c->rm.last = (int64_t)n - (int64_t)n1;
     if (n_left) *n_left = (int64_t)n1;
     return GSR_OK;
 }
@@ -841,12 +887,9 @@ extern "C" int64_t gsr_add_capacity(int64_t capacity, int64_t n_needed)
 extern "C" int gsr_get_add(gsr_context* c, int64_t* adds, int64_t* added_last, int64_t* capacity, int64_t* grows, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_add: ctx is NULL");
-    if (adds) *adds = c->add_calls;
-    if (added_last) *added_last = c->add_last;
     if (capacity) *capacity = (int64_t)c->cap;
     if (grows) *grows = c->add_grows;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->add_ms[k];
-    return GSR_OK;
+    return c->add.report(adds, added_last, ms);
 }
 
 // what both forms refuse before they look at their arrays; *done: m == 0, there is nothing to do
@@ -960,9 +1003,9 @@ static int add_body(gsr_context* c, const char* who, uint32_t m, StageRows&& sta
         if (vis) c->alpha0 = std::move(ro.alpha0_new);
     }
     // 6, 7. the rule of a visibility in force over the whole cloud; a new cloud to everything a frame keeps
-    if ((rc = ro.finish(c->add_ms, false))) return rc;
-    c->add_calls += 1;
-    c->add_last = (int64_t)m;
+    if ((rc = ro.finish(c->add.ms, false))) return rc;
+    c->add.calls += 1;
+    c->add.last = (int64_t)m;
     if (grow) c->add_grows += 1;
     if (n_total) *n_total = (int64_t)n1;
     return GSR_OK;
@@ -1026,16 +1069,14 @@ extern "C" int gsr_copy_map(const uint32_t* mask, int64_t n, int32_t* rows, int6
 // count -- the row list, the positions, the destination rows -- lies behind `bytes`, sized by the count: grow() makes that room, and
 // counts again if the arena had to move (a host mask is still the caller's until the verb returns).
 struct CopySelection {
+    const MaskArg mask;                // the caller's (NULL: every splat)
     const uint32_t n, nblocks;
-    const size_t words;
-    const uint32_t* const mask;        // the caller's (NULL: every splat)
-    const bool is_device;
     size_t oMask = 0, oSel = 0, oCnt = 0, oOff = 0, bytes = 0;
 
-    CopySelection(uint32_t n_, const uint32_t* mask_, bool dev) : n(n_), nblocks(div_up(n_, (uint32_t)GSR_REMOVE_BLOCK)), words(((size_t)n_ + 31) / 32), mask(mask_), is_device(dev)
+    explicit CopySelection(const MaskArg& m) : mask(m), n(m.n), nblocks(div_up(m.n, (uint32_t)GSR_REMOVE_BLOCK))
     {
         auto place = [&](size_t b) { const size_t at = bytes; bytes += pad256(b); return at; };
-        oMask = place(mask && !is_device ? words * 4 : 0); oSel = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8); oCnt = place((size_t)nblocks * 4);
+        oMask = place(mask.stage_bytes()); oSel = place((size_t)nblocks * GSR_REMOVE_SLOTS * 8); oCnt = place((size_t)nblocks * 4);
         oOff = place(((size_t)nblocks + 1) * 4);
     }
     const unsigned long long* sel(const gsr_context* c) const { return reinterpret_cast<const unsigned long long*>(c->stage + oSel); }
@@ -1045,35 +1086,22 @@ struct CopySelection {
     int prepare(gsr_context* c, const char* who) const
     {
         const int rc = ensure_stage(c, bytes);
-        if (rc) return rc;
-        if (!c->cp_h_total && c->cp_h_total.alloc(2, 0)) {
-            (void)hipGetLastError();
-            return set_err(GSR_E_OOM, "%s: no pinned host memory for the selection's count", who);
-        }
-        return GSR_OK;
+        return rc ? rc : ensure_h_word(c, who);
     }
     // mark and scan on `us`, and the wait for the total: *m = the selected splats.  link_ms (may be NULL) += what a host mask took.
     hipError_t count(gsr_context* c, hipStream_t us, uint32_t* m, double* link_ms) const
     {
-        const uint32_t* dmask = mask;
-        hipError_t e = hipSuccess;
-        if (mask && !is_device) {
-            const double t0 = up_now_ms();
-            uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
-            e = hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us);
-            if (e == hipSuccess) e = hipStreamSynchronize(us);     // the caller's mask may be freed on return
-            if (e != hipSuccess) return e;
-            if (link_ms) *link_ms += up_now_ms() - t0;
-            dmask = staged;
-        }
+        const uint32_t* dmask = nullptr;
+        hipError_t e = mask.to_device(c, us, oMask, link_ms, &dmask);
+        if (e != hipSuccess) return e;
         uint32_t* const counts = reinterpret_cast<uint32_t*>(c->stage + oCnt);
         uint32_t* const offs = reinterpret_cast<uint32_t*>(c->stage + oOff);
         hipLaunchKernelGGL(k_copy_mark, dim3(nblocks), dim3(GSR_REMOVE_THREADS), 0, us, n, dmask, reinterpret_cast<unsigned long long*>(c->stage + oSel), counts);
         hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, counts, offs);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(c->cp_h_total, offs + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->h_word, offs + nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, us);
         if (e == hipSuccess) e = hipStreamSynchronize(us);
-        if (e == hipSuccess) *m = c->cp_h_total[0];
+        if (e == hipSuccess) *m = c->h_word[0];
         return e;
     }
     // room for `total` bytes of the arena (the scratch included), behind count(): the bitmap and the offsets are there afterwards.
@@ -1101,10 +1129,7 @@ extern "C" int64_t gsr_debug_stage_bytes(gsr_context* c)
 extern "C" int gsr_get_duplicate(gsr_context* c, int64_t* calls, int64_t* copied_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_duplicate: ctx is NULL");
-    if (calls) *calls = c->dup_calls;
-    if (copied_last) *copied_last = c->dup_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->dup_ms[k];
-    return GSR_OK;
+    return c->dup.report(calls, copied_last, ms);
 }
 
 // A copy of each selected splat appended.  A move whose source is a multiset: the compaction leaves the n + m positions and the slot
@@ -1118,8 +1143,8 @@ extern "C" int gsr_duplicate(gsr_context* c, const uint32_t* mask, int mask_is_d
     if (rc) return rc;
     const uint32_t n0 = c->n;
     HIP_TRY(hipSetDevice(c->device));
-    const CopySelection s(n0, mask, mask_is_device != 0);
-    if (mask && mask_is_device && n0 && (rc = check_device_source(c, mask, s.words * 4, who, "mask"))) return rc;
+    const CopySelection s(MaskArg{mask, mask_is_device != 0, n0});
+    if ((rc = s.mask.check(c, who))) return rc;
     Reorder ro(c, who, false);
     if ((rc = sync_all(c))) return rc;   // the public stream (a producer of a device mask queued there has finished), and no write under a frame in flight
     auto nothing = [&]() {             // nothing is selected: no resident bit changes, nothing is invalidated
@@ -1208,9 +1233,9 @@ extern "C" int gsr_duplicate(gsr_context* c, const uint32_t* mask, int mask_is_d
         if (vis) c->alpha0 = std::move(ro.alpha0_new);
     }
     // 6, 7. the rule of a visibility in force over the whole cloud; a new cloud to everything a frame keeps
-    if ((rc = ro.finish(c->dup_ms, false))) return rc;
-    c->dup_calls += 1;
-    c->dup_last = (int64_t)m;
+    if ((rc = ro.finish(c->dup.ms, false))) return rc;
+    c->dup.calls += 1;
+    c->dup.last = (int64_t)m;
     if (grow) c->add_grows += 1;
     if (m_out) *m_out = (int64_t)m;
     if (n_total) *n_total = (int64_t)n1;
@@ -1357,10 +1382,7 @@ extern "C" int gsr_transform_eval(const gsr_xform* x, int64_t n, const uint32_t*
 extern "C" int gsr_get_transform(gsr_context* c, int64_t* calls, int64_t* moved_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_transform: ctx is NULL");
-    if (calls) *calls = c->xf_calls;
-    if (moved_last) *moved_last = c->xf_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->xf_ms[k];
-    return GSR_OK;
+    return c->xf.report(calls, moved_last, ms);
 }
 
 extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_device, const gsr_xform* x, int64_t* n_moved)
@@ -1372,13 +1394,13 @@ extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_d
     int rc = refuse_edit(c, who);
     if (rc) return rc;
     const uint32_t n = c->n;
-    const size_t words = ((size_t)n + 31) / 32;
+    const MaskArg mk{mask, mask_is_device != 0, n};
     HIP_TRY(hipSetDevice(c->device));
-    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    if ((rc = mk.check(c, who))) return rc;
     if (n == 0) {                      // the empty cloud: no word of the mask exists
         rc = sync_all(c);
         if (rc) return rc;
-        c->xf_calls += 1; c->xf_last = 0;
+        c->xf.calls += 1; c->xf.last = 0;
         if (n_moved) *n_moved = 0;
         return GSR_OK;
     }
@@ -1386,38 +1408,22 @@ extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_d
     // ---- the arena: every position in upload order, the rule, the count, a host mask's copy
     size_t off = 0;
     auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
-    const size_t oP = place((size_t)n * 12), oRule = place(sizeof(GsrXformRule)), oCount = place(4), oMask = place(mask && !mask_is_device ? words * 4 : 0);
-    if (!c->xf_h_count && c->xf_h_count.alloc(1, 0)) {
-        (void)hipGetLastError();
-        return set_err(GSR_E_OOM, "gsr_transform: no pinned host memory for the count");
-    }
-    const uint32_t* dmask = mask;
+    const size_t oP = place((size_t)n * 12), oRule = place(sizeof(GsrXformRule)), oCount = place(4), oMask = place(mk.stage_bytes());
+    if ((rc = ensure_h_word(c, who))) return rc;
+    const uint32_t* dmask = nullptr;
     uint32_t count = n;
-    rc = reposition_body(c, who, off, nullptr, c->xf_ms, false,
+    rc = reposition_body(c, who, off, nullptr, c->xf.ms, false,
         [&](Reorder& ro, bool* nothing) {
             // the rule and a host mask into the arena (no resident byte), then the count: a mask with no bit set below n ends the call here
             hipStream_t us = ro.us;
             const double t0 = up_now_ms();
             HIP_TRY(hipMemcpyAsync(c->stage + oRule, &rule, sizeof(rule), hipMemcpyHostToDevice, us));
-            if (mask && !mask_is_device) {
-                uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
-                HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
-                dmask = staged;
-            }
-            HIP_TRY(hipStreamSynchronize(us));         // the caller's mask may be freed on return
+            HIP_TRY(mk.to_device(c, us, oMask, nullptr, &dmask));
+            if (!mk.stage_bytes()) HIP_TRY(hipStreamSynchronize(us));      // (to_device has waited for a host mask, the rule with it)
             ro.link_ms = up_now_ms() - t0;
-            if (dmask) {
-                uint32_t* const dcount = reinterpret_cast<uint32_t*>(c->stage + oCount);
-                HIP_TRY(hipMemsetAsync(dcount, 0, 4, us));
-                hipLaunchKernelGGL(k_transform_count, dim3(div_up((uint32_t)words, 256)), dim3(256), 0, us, n, dmask, dcount);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(c->xf_h_count, dcount, 4, hipMemcpyDeviceToHost, us));
-                HIP_TRY(hipStreamSynchronize(us));
-                count = c->xf_h_count[0];
-                if (count > n) return set_err(GSR_E_HIP, "gsr_transform: the reduction counted %u bits below %u", count, n);
-            }
+            const int counted = dmask ? count_mask_bits(c, us, n, dmask, oCount, who, &count) : GSR_OK;
             *nothing = count == 0;
-            return GSR_OK;
+            return counted;
         },
         [&](Reorder& ro, const float** Pout) {
             float* const Pup = reinterpret_cast<float*>(c->stage + oP);
@@ -1434,8 +1440,8 @@ extern "C" int gsr_transform(gsr_context* c, const uint32_t* mask, int mask_is_d
             return GSR_OK;
         });
     if (rc) return rc;
-    c->xf_calls += 1;
-    c->xf_last = (int64_t)count;
+    c->xf.calls += 1;
+    c->xf.last = (int64_t)count;
     if (n_moved) *n_moved = (int64_t)count;
     return GSR_OK;
 }
@@ -1522,10 +1528,7 @@ extern "C" int gsr_grade_eval(const gsr_grade_rule* rule, int64_t n, const uint3
 extern "C" int gsr_get_grade(gsr_context* c, int64_t* calls, int64_t* graded_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_grade: ctx is NULL");
-    if (calls) *calls = c->gr_calls;
-    if (graded_last) *graded_last = c->gr_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->gr_ms[k];
-    return GSR_OK;
+    return c->gr.report(calls, graded_last, ms);
 }
 
 extern "C" int gsr_grade(gsr_context* c, const uint32_t* mask, int mask_is_device, const gsr_grade_rule* rule, int64_t* n_graded)
@@ -1538,12 +1541,12 @@ extern "C" int gsr_grade(gsr_context* c, const uint32_t* mask, int mask_is_devic
     if (rc) return rc;
     const double t_begin = up_now_ms();
     const uint32_t n = c->n;
-    const size_t words = ((size_t)n + 31) / 32;
+    const MaskArg mk{mask, mask_is_device != 0, n};
     HIP_TRY(hipSetDevice(c->device));
-    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, words * 4, who, "mask"))) return rc;
+    if ((rc = mk.check(c, who))) return rc;
     if ((rc = sync_all(c))) return rc;      // the public stream (a select queued there has written the mask), and no in-place write under a frame in flight
     auto nothing = [&]() {                  // empty work: a call that changes, invalidates and writes nothing
-        c->gr_calls += 1; c->gr_last = 0;
+        c->gr.calls += 1; c->gr.last = 0;
         if (n_graded) *n_graded = 0;
         return GSR_OK;
     };
@@ -1554,31 +1557,13 @@ extern "C" int gsr_grade(gsr_context* c, const uint32_t* mask, int mask_is_devic
     // order, the clock's events, the pinned word of the count, the visibility's buffers
     const size_t oCount = 0, oMask = 256;
     hipStream_t us = c->slot[0].own;
-    if ((rc = ensure_stage(c, oMask + (mask && !mask_is_device ? pad256(words * 4) : 0))) || (rc = ensure_inverse_perm(c)) ||
-        (rc = ensure_up_events(c, 2, who, true)) || (vis && (rc = vis_ensure_buffers(c)))) return rc;
-    if (!c->xf_h_count && c->xf_h_count.alloc(1, 0)) {
-        (void)hipGetLastError();
-        return set_err(GSR_E_OOM, "gsr_grade: no pinned host memory for the count");
-    }
+    if ((rc = ensure_stage(c, oMask + pad256(mk.stage_bytes()))) || (rc = ensure_inverse_perm(c)) ||
+        (rc = ensure_up_events(c, 2, who, true)) || (vis && (rc = vis_ensure_buffers(c))) || (rc = ensure_h_word(c, who))) return rc;
     // ---- a host mask into the arena (no resident byte), then the count: a mask with no bit set below n ends the call here
-    const uint32_t* dmask = mask;
+    const uint32_t* dmask = nullptr;
     uint32_t count = n;
-    if (mask && !mask_is_device) {
-        uint32_t* const staged = reinterpret_cast<uint32_t*>(c->stage + oMask);
-        HIP_TRY(hipMemcpyAsync(staged, mask, words * 4, hipMemcpyHostToDevice, us));
-        HIP_TRY(hipStreamSynchronize(us));             // the caller's mask may be freed on return
-        dmask = staged;
-    }
-    if (dmask) {
-        uint32_t* const dcount = reinterpret_cast<uint32_t*>(c->stage + oCount);
-        HIP_TRY(hipMemsetAsync(dcount, 0, 4, us));
-        hipLaunchKernelGGL(k_transform_count, dim3(div_up((uint32_t)words, 256)), dim3(256), 0, us, n, dmask, dcount);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->xf_h_count, dcount, 4, hipMemcpyDeviceToHost, us));
-        HIP_TRY(hipStreamSynchronize(us));
-        count = c->xf_h_count[0];
-        if (count > n) return set_err(GSR_E_HIP, "gsr_grade: the reduction counted %u bits below %u", count, n);
-    }
+    HIP_TRY(mk.to_device(c, us, oMask, nullptr, &dmask));
+    if (dmask && (rc = count_mask_bits(c, us, n, dmask, oCount, who, &count))) return rc;
     if (count == 0) return nothing();
     const double t_counted = up_now_ms();
     // ---- the kernel, in place; with a visibility in force and a new opacity, the rule in force over the graded true alphas (no
@@ -1601,12 +1586,12 @@ extern "C" int gsr_grade(gsr_context* c, const uint32_t* mask, int mask_is_devic
     e = after_update(c, alph, us, e);
     if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_grade: %s", hipGetErrorString(e));
     float ms = 0.0f;
-    c->gr_ms[0] = t_counted - t_begin;
-    c->gr_ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
-    c->gr_ms[2] = vis ? t_vis - t_kernel : 0.0;
-    c->gr_ms[3] = up_now_ms() - t_begin;
-    c->gr_calls += 1;
-    c->gr_last = (int64_t)count;
+    c->gr.ms[0] = t_counted - t_begin;
+    c->gr.ms[1] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
+    c->gr.ms[2] = vis ? t_vis - t_kernel : 0.0;
+    c->gr.ms[3] = up_now_ms() - t_begin;
+    c->gr.calls += 1;
+    c->gr.last = (int64_t)count;
     if (n_graded) *n_graded = (int64_t)count;
     return GSR_OK;
 }

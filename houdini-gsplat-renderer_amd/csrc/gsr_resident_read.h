@@ -22,10 +22,7 @@ extern "C" int gsr_read_info(gsr_context* c, int64_t* n_splats, int* has_sh, flo
 extern "C" int gsr_get_read(gsr_context* c, int64_t* reads, int64_t* rows_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_read: ctx is NULL");
-    if (reads) *reads = c->rd_calls;
-    if (rows_last) *rows_last = c->rd_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->rd_ms[k];
-    return GSR_OK;
+    return c->rd.report(reads, rows_last, ms);
 }
 
 // k_unpack over rows [first, first + n) on slot 0's own stream, between up_ev[0] and up_ev[1]; the caller has ensured the inverse of
@@ -50,12 +47,12 @@ static hipError_t queue_unpack(gsr_context* c, hipStream_t us, uint32_t first, u
 static void read_done(gsr_context* c, int64_t rows, double copy_ms, double t_begin)
 {
     float ms = 0.0f;
-    c->rd_ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
-    c->rd_ms[1] = copy_ms;
-    c->rd_ms[2] = 0.0;
-    c->rd_ms[3] = up_now_ms() - t_begin;
-    c->rd_calls += 1;
-    c->rd_last = rows;
+    c->rd.ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
+    c->rd.ms[1] = copy_ms;
+    c->rd.ms[2] = 0.0;
+    c->rd.ms[3] = up_now_ms() - t_begin;
+    c->rd.calls += 1;
+    c->rd.last = rows;
 }
 
 // ---------------------------------------------------------------------------
@@ -147,16 +144,17 @@ static int read_masked_body(gsr_context* c, const char* who, const uint32_t* mas
     const uint32_t n = c->n;
     const double t_begin = up_now_ms();
     HIP_TRY(hipSetDevice(c->device));
-    const CopySelection s(n, mask, mask_is_device != 0);
+    const MaskArg mk{mask, mask_is_device != 0, n};
+    const CopySelection s(mk);
     int rc = GSR_OK;
-    if (mask && mask_is_device && n && (rc = check_device_source(c, mask, s.words * 4, who, "mask"))) return rc;
+    if ((rc = mk.check(c, who))) return rc;
     if (wanted && (rc = check())) return rc;
     if (n == 0) {                                      // the empty cloud selects no row
         if (m_out) *m_out = 0;
         return GSR_OK;
     }
     // a producer of a device mask, or a consumer of device destinations, queued on the public stream has finished
-    if (c->stream && (wait_public || (mask && mask_is_device))) HIP_TRY(hipStreamSynchronize(c->stream));
+    if (c->stream && (wait_public || (mask && mk.is_device))) HIP_TRY(hipStreamSynchronize(c->stream));
     if ((rc = s.prepare(c, who)) || (rc = ensure_inverse_perm(c)) || (rc = ensure_up_events(c, 2, who, true))) return rc;
     hipStream_t us = c->slot[0].own;
     uint32_t m = 0;

@@ -56,10 +56,7 @@ extern "C" int gsr_select_eval(const gsr_camera* cam, const float origin[3], con
 extern "C" int gsr_get_select(gsr_context* c, int64_t* calls, int64_t* hit_last, double ms[4])
 {
     if (!c) return set_err(GSR_E_INVALID, "gsr_get_select: ctx is NULL");
-    if (calls) *calls = c->sel_calls;
-    if (hit_last) *hit_last = c->sel_last;
-    if (ms) for (int k = 0; k < 4; ++k) ms[k] = c->sel_ms[k];
-    return GSR_OK;
+    return c->sel.report(calls, hit_last, ms);
 }
 
 extern "C" int gsr_select(gsr_context* c, const gsr_camera* cam, const gsr_select_region* r, uint32_t* mask, int mask_is_device,
@@ -139,11 +136,11 @@ extern "C" int gsr_select(gsr_context* c, const gsr_camera* cam, const gsr_selec
     if (n_hit) *n_hit = (int64_t)hits;
     if (n_set) *n_set = (int64_t)set;
     float ms = 0.0f;
-    c->sel_ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
-    c->sel_ms[1] = copy_ms;
-    c->sel_ms[2] = 0.0;
-    c->sel_ms[3] = up_now_ms() - t_begin;
-    c->sel_calls += 1;
-    c->sel_last = (int64_t)hits;
+    c->sel.ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
+    c->sel.ms[1] = copy_ms;
+    c->sel.ms[2] = 0.0;
+    c->sel.ms[3] = up_now_ms() - t_begin;
+    c->sel.calls += 1;
+    c->sel.last = (int64_t)hits;
     return GSR_OK;
 }

@@ -6,7 +6,8 @@
 // object is pinned as it is; tests/test_select.py holds the restatement to the oracle's records bit for bit.  Every multiply-add is an
 // explicit fmaf and no product feeds an add anywhere else (the translation units are compiled with -ffp-contract=off), the
 // divisions are IEEE divisions: x86 and gfx950 agree in every bit, and gsr_select_eval (host) and k_select go through the one function.
-// No frame kernel changes, and a context that never selects launches nothing of this file.
+// No frame kernel changes, and a context that never selects launches nothing of this file but k_mask_count (the bit count of a mask,
+// at the end: gsr_transform and gsr_grade).
 #pragma once
 #include "gsr_device.h"
 
@@ -124,4 +125,23 @@ k_select(uint32_t n, const uint32_t* __restrict__ inv, const float4* __restrict_
     const unsigned long long counts = (unsigned long long)__popcll(ballot) | ((unsigned long long)n_set << 32);
     if (lane == 0u && counts)
         atomicAdd(counters + (size_t)(blockIdx.x & (GSR_SEL_COUNTER_SLOTS - 1u)) * GSR_SEL_COUNTER_STRIDE, counts);
+}
+
+// How many of the first n bits of a mask are set (gsr_transform and gsr_grade count the mask a selection leaves before they write
+// anything): one thread per word, bits at and behind n dropped, a wave's sum in ONE atomic on a counter word of the staging arena
+// (zeroed in front).  Reads the mask, writes nothing else: a verb returns on a zero count before it has changed anything.
+__global__ void __launch_bounds__(256)
+k_mask_count(uint32_t n, const uint32_t* __restrict__ mask, uint32_t* __restrict__ count)
+{
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x, words = (n >> 5) + ((n & 31u) ? 1u : 0u);
+    uint32_t set = 0u;
+    if (w < words) {
+        uint32_t v = mask[w];
+        const uint32_t left = n - w * 32u;             // splats from this word's first bit on (>= 1)
+        if (left < 32u) v &= (1u << left) - 1u;
+        set = (uint32_t)__popc(v);
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) set += __shfl_xor(set, d, 64);
+    if ((threadIdx.x & 63u) == 0u && set) atomicAdd(count, set);
 }

@@ -95,25 +95,6 @@ __host__ __device__ __forceinline__ void gsr_xf_sh_part(const GsrXformRule& r, i
     }
 }
 
-// how many of the first n bits of a mask are set: one thread per word, bits at and behind n dropped, a wave's sum in ONE atomic on a
-// counter word of the staging arena (zeroed in front).  Reads the mask, writes nothing else: the verb returns on a zero count before
-// it has changed anything.
-__global__ void __launch_bounds__(256)
-k_transform_count(uint32_t n, const uint32_t* __restrict__ mask, uint32_t* __restrict__ count)
-{
-    const uint32_t w = blockIdx.x * 256u + threadIdx.x, words = (n >> 5) + ((n & 31u) ? 1u : 0u);
-    uint32_t set = 0u;
-    if (w < words) {
-        uint32_t v = mask[w];
-        const uint32_t left = n - w * 32u;             // splats from this word's first bit on (>= 1)
-        if (left < 32u) v &= (1u << left) - 1u;
-        set = (uint32_t)__popc(v);
-    }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) set += __shfl_xor(set, d, 64);
-    if ((threadIdx.x & 63u) == 0u && set) atomicAdd(count, set);
-}
-
 // K0t: the rule over the resident planes, in k_update's / k_unpack's work shape (k_resident.h): 512 threads cover 64 consecutive UPLOAD
 // indices i, eight lanes per splat, all eight in one wave; storage slot j = inv[i] (inv: the inverse of the storage order in force;
 // NULL: j = i).  A wave covers eight splats, whose mask bits lie in ONE word: it reads that word once, and for a group of eight with no

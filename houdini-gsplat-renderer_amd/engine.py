@@ -227,6 +227,7 @@ C_ABI_SYMBOLS = [
     "gsr_add", "gsr_add_device", "gsr_add_capacity", "gsr_get_add", "gsr_multi_add",
     "gsr_read_info", "gsr_read", "gsr_read_device", "gsr_get_read", "gsr_multi_read",
     "gsr_copy_map", "gsr_read_masked", "gsr_read_masked_device", "gsr_duplicate", "gsr_get_duplicate", "gsr_multi_read_masked", "gsr_multi_duplicate",
+    "gsr_debug_replica_verdict",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
@@ -255,6 +256,21 @@ def balance_rows(row_work, count: int, cur_first=None, min_gain_permille: int = 
     rc = L.gsr_debug_balance_rows(_ptr(w) if w.size else None, int(w.size), int(count), _ptr(cur), int(min_gain_permille), out.ctypes.data)
     _check(rc if rc < 0 else 0)
     return bool(rc), out
+
+
+REPLICA_KEEP_REFUSAL, REPLICA_AGREED, REPLICA_DROP_ALL = range(3)     # GSR_REPLICA_*: gsr_debug_replica_verdict
+
+
+def replica_verdict(rc: int, counts) -> int:
+    """gsr_debug_replica_verdict (host only, no GPU): the agreement rule of gsr_multi_remove, _add, _duplicate, _transform and _grade.
+    rc: what the ranks returned together; counts: int64 (ranks, per_rank), -1 where a rank did not return GSR_OK -> REPLICA_*.
+    Raises GsrError on a bad argument"""
+    a = np.ascontiguousarray(counts, dtype=np.int64)
+    if a.ndim != 2:
+        raise ValueError("counts is (ranks, per_rank)")
+    out = C.c_int(-1)
+    _check(load_library().gsr_debug_replica_verdict(int(rc), a.shape[0], a.shape[1], _ptr(a) if a.size else None, C.byref(out)))
+    return out.value
 
 
 # gsr_debug_sort_frame's modes (include/gsplat_hip.h)
@@ -465,6 +481,7 @@ def load_library() -> C.CDLL:
     L.gsr_set_row_band.argtypes = [vp, i32, i32]
     L.gsr_read_row_work.argtypes = [vp, vp, i32, C.POINTER(C.c_int64)]
     L.gsr_debug_balance_rows.argtypes = [vp, i32, i32, vp, i32, vp]
+    L.gsr_debug_replica_verdict.argtypes = [i32, i32, i32, vp, C.POINTER(C.c_int)]
     L.gsr_multi_get_bands.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.gsr_multi_gather_stats.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     L.gsr_comm_info.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -1284,9 +1301,7 @@ class Engine:
     def get_transform(self) -> dict:
         """gsr_get_transform -> {transforms: the calls, moved_last, ms: the last call's stage clock [mask copy, kernel .. sort,
         repack, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_transform(self.h, C.byref(calls), C.byref(last), ms))
-        return {"transforms": calls.value, "moved_last": last.value, "ms": [float(v) for v in ms]}
+        return self._tally(self.L.gsr_get_transform, "transforms", "moved_last")
 
     # ---- grade: the colour and the opacity of selected resident splats (include/gsplat_hip.h, "grade")
     def grade(self, rule, mask=None) -> int:
@@ -1313,16 +1328,12 @@ class Engine:
     def get_grade(self) -> dict:
         """gsr_get_grade -> {grades: the calls, graded_last, ms: the stage clock of the last call that wrote [mask copy and count,
         kernel, visibility, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_grade(self.h, C.byref(calls), C.byref(last), ms))
-        return {"grades": calls.value, "graded_last": last.value, "ms": [float(v) for v in ms]}
+        return self._tally(self.L.gsr_get_grade, "grades", "graded_last")
 
     def get_removal(self) -> dict:
         """gsr_get_removal -> {removals: calls that removed something, removed_last, ms: the last call's stage clock
         [mask copy, mark .. sort, repack, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_removal(self.h, C.byref(calls), C.byref(last), ms))
-        return {"removals": calls.value, "removed_last": last.value, "ms": [float(x) for x in ms]}
+        return self._tally(self.L.gsr_get_removal, "removals", "removed_last")
 
     def add(self, splats) -> int:
         """gsr_add: the splats (a Splats-like object, arrays in upload's layout) join the resident cloud behind its last upload index,
@@ -1348,9 +1359,7 @@ class Engine:
     def get_add(self) -> dict:
         """gsr_get_add -> {adds: calls that added something, added_last, capacity: splats the context has room for, grows: adds that
         grew it, ms: the last call's stage clock [new rows over the link, positions .. sort, pack, wall]}"""
-        calls, last, cap, grows, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_add(self.h, C.byref(calls), C.byref(last), C.byref(cap), C.byref(grows), ms))
-        return {"adds": calls.value, "added_last": last.value, "capacity": cap.value, "grows": grows.value, "ms": [float(x) for x in ms]}
+        return self._tally(self.L.gsr_get_add, "adds", "added_last", "capacity", "grows")
 
     # ---- reading back: the resident cloud in upload order (include/gsplat_hip.h, "reading back")
     def read_info(self) -> dict:
@@ -1437,15 +1446,11 @@ class Engine:
     def get_duplicate(self) -> dict:
         """gsr_get_duplicate -> {duplicates: calls that copied something, copied_last, ms: the last call's stage clock [mask copy,
         mark .. sort, repack, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_duplicate(self.h, C.byref(calls), C.byref(last), ms))
-        return {"duplicates": calls.value, "copied_last": last.value, "ms": [float(x) for x in ms]}
+        return self._tally(self.L.gsr_get_duplicate, "duplicates", "copied_last")
 
     def get_read(self) -> dict:
         """gsr_get_read -> {reads: calls that read something, rows_last, ms: the last call's clock [kernel, device -> host copies, 0, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_read(self.h, C.byref(calls), C.byref(last), ms))
-        return {"reads": calls.value, "rows_last": last.value, "ms": [float(x) for x in ms]}
+        return self._tally(self.L.gsr_get_read, "reads", "rows_last")
 
     # ---- selection: resident splats by screen region (include/gsplat_hip.h, "selection")
     def select(self, cam, region, mask=None):
@@ -1477,9 +1482,14 @@ class Engine:
 
     def get_select(self) -> dict:
         """gsr_get_select -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
-        calls, last, ms = C.c_int64(0), C.c_int64(0), (C.c_double * 4)()
-        _check(self.L.gsr_get_select(self.h, C.byref(calls), C.byref(last), ms))
-        return {"selects": calls.value, "hit_last": last.value, "ms": [float(x) for x in ms]}
+        return self._tally(self.L.gsr_get_select, "selects", "hit_last")
+
+    def _tally(self, get, *keys) -> dict:
+        """a gsr_get_* of the resident-edit family: its int64 outputs (the calls, the last count, and what else the verb reports) under
+        `keys`, in their order, then "ms": the last call's clock"""
+        v, ms = [C.c_int64(0) for _ in keys], (C.c_double * 4)()
+        _check(get(self.h, *[C.byref(x) for x in v], ms))
+        return {**{k: x.value for k, x in zip(keys, v)}, "ms": [float(x) for x in ms]}
 
     def debug_resident(self, which: int) -> np.ndarray:
         """gsr_debug_read_resident: the bytes of one plane of the resident geometry (RESIDENT_*), in storage order"""

@@ -889,6 +889,18 @@ int  gsr_multi_read_masked(gsr_multi* m, const uint32_t* mask_host, int64_t max_
 /* gsr_duplicate on every rank's replica, after the same synchronisation, from a HOST mask (NULL: every splat), under gsr_multi_add's
  * agreement rule: ranks that do not agree on the total, or a rank that fails after its first write, and NO rank keeps geometry. */
 int  gsr_multi_duplicate(gsr_multi* m, const uint32_t* mask_host, int64_t* n_copied, int64_t* n_total);
+/* The agreement rule of those five verbs, a pure host function (no context, no GPU).  rc: what the ranks returned together (the
+ * first failure, GSR_OK if none); counts[ranks * per_rank]: rank g's per_rank counts at [g * per_rank ..], -1 where the rank did
+ * not return GSR_OK (a rank writes them only then).  *verdict =
+ *   GSR_REPLICA_KEEP_REFUSAL  rc is a refusal (not GSR_E_HIP) and no rank has a count: every rank refused before its first write,
+ *                             the replicas are what they were, and the verb returns rc;
+ *   GSR_REPLICA_AGREED        rc == GSR_OK and every rank's counts equal rank 0's: the verb returns rank 0's counts;
+ *   GSR_REPLICA_DROP_ALL      anything else (GSR_E_HIP may have come behind a rank's first write): every rank drops its geometry.
+ * Returns GSR_E_INVALID for NULL counts / verdict, ranks < 1 or per_rank < 1. */
+#define GSR_REPLICA_KEEP_REFUSAL 0
+#define GSR_REPLICA_AGREED       1
+#define GSR_REPLICA_DROP_ALL     2
+int  gsr_debug_replica_verdict(int rc, int ranks, int per_rank, const int64_t* counts, int* verdict);
 /* full frame on devices[0] (device pointer there, asynchronous, ordered on the stream of gsr_multi_set_stream) or in host
  * memory (synchronous): height*width pixels of the target format */
 int  gsr_multi_render(gsr_multi* m, const gsr_camera* cam, float* rgba_out, int out_is_device);

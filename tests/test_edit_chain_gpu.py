@@ -145,3 +145,94 @@ def test_visibility_state_across_the_swap_chain(pkg, sh):
         _same_as_fresh(pkg, U, s, f"the visibility cleared: the true alphas (sh {sh})", sh)
         assert U.stats()["uploads"] == 1 and U.stats()["n_splats"] == s.n
         _same_last_frame(pkg, U, s, f"visibility across the swap chain (sh {sh})")
+
+
+# ---- 4. one mask intake: a host mask and the same words in device memory ----------------------------------------------------------
+def _intake_masks(pkg, n):
+    """(label, packed words) of a fixed-seed selection over n splats -- the first and the last splat selected -- and of one with no bit
+    set below n; in the last word of both every bit at and behind n is set, which no verb may read"""
+    rng = np.random.default_rng(40 + n)
+    sel = rng.random(n) < 0.4
+    sel[0] = sel[-1] = True
+    out = []
+    for label, bits in (("selection", sel), ("no bit below n", np.zeros(n, bool))):
+        words = pkg.engine.pack_mask(bits)
+        if n % 32:
+            words[-1] |= np.uint32((0xffffffff << (n % 32)) & 0xffffffff)
+        out.append((label, words))
+    return out
+
+
+def _assert_same_splats(got, want, label):
+    for k in ("P", "Cd", "alpha", "scale", "orient", "shx", "shy", "shz"):
+        g, w = getattr(got, k), getattr(want, k)
+        assert (g is None) == (w is None), (label, k)
+        if w is not None:
+            assert g.shape == w.shape and np.array_equal(g.view(np.uint8), w.view(np.uint8)), (label, k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", (1, 33, 64, 4097))
+def test_one_mask_intake_host_and_device(pkg, n):
+    """remove, duplicate, transform, grade and read_masked take a mask through one intake: from host words and from the same words
+    in device memory each verb, on a fresh upload, returns the host model's count, leaves bit for bit the model's cloud (read()), and
+    advances its tally by one with *_last = that count.  n: a word edge (1, 33), a wave edge (64), one past GSR_REMOVE_BLOCK (4097).
+    A mask with no bit below n selects nothing: every verb counts 0 and the cloud stays the upload (remove, duplicate and a masked read
+    then leave their tallies as they were -- they count calls that did something --, transform and grade count the call)"""
+    import ctypes as Ct
+    from helpers import HipBuffers
+    E, L = pkg.engine, pkg.load_library()
+    A = M._cloud(pkg, 31, n=n)
+    x = E.xform(axis_angle=((0.3, 1.0, 0.2), 40.0), scale=1.5, translate=(0.1, -0.2, 0.3), pivot=(0.05, 0.0, 0.0))
+    rule = E.grade_prepare(E.grade_params(exposure=0.3, saturation=0.7, alpha_gain=0.8, alpha_offset=0.05))
+    assert rule["flags"] == E.GRADE_COLOUR | E.GRADE_ALPHA
+
+    def read_masked_device(U, dptr, words):
+        verb = lambda ptr, max_rows, r, m: L.gsr_read_masked(U.h, Ct.c_void_p(dptr), 1, max_rows, r, m)    # noqa: E731
+        return E._read_masked_splats(verb, (n, True), words, None)
+
+    hb = HipBuffers()
+    try:
+        with pkg.Engine(0) as U:
+            for label, words in _intake_masks(pkg, n):
+                dptr = hb.upload(words)
+                sel = E.unpack_mask(words, n)
+                rows, m = E.copy_map(words, n)
+                _, left = E.remove_map(words, n)
+                assert m == int(sel.sum()) and left == n - m and (m > 0) == (label == "selection"), (label, m, left)
+                # verb -> (run from host words, run from device words: the count; the tally's getter and keys; the model's cloud)
+                verbs = {
+                    "remove": (lambda: n - U.remove(words), lambda: n - U.remove_device(dptr), U.get_removal, "removals", "removed_last",
+                               A.subset(~sel)),
+                    "duplicate": (lambda: U.duplicate(words)[0], lambda: U.duplicate_device(dptr)[0], U.get_duplicate, "duplicates",
+                                  "copied_last", A.concat(A.subset(rows))),
+                    "transform": (lambda: U.transform(x, words), lambda: U.transform_device(x, dptr), U.get_transform, "transforms",
+                                  "moved_last", E.transform_eval(x, A, words)),
+                    "grade": (lambda: U.grade(rule, words), lambda: U.grade_device(rule, dptr), U.get_grade, "grades", "graded_last",
+                              E.grade_eval(rule, A, words)),
+                    "read_masked": (lambda: U.read_masked(words), lambda: read_masked_device(U, dptr, words),
+                                    U.get_read, "reads", "rows_last", A),
+                }
+                for verb, (host, device, tally, calls, key, want) in verbs.items():
+                    runs = []
+                    for form, run in (("host", host), ("device", device)):
+                        case = f"n {n}, {label}, {verb} from a {form} mask"
+                        U.upload(A)
+                        before = tally()
+                        got = run()
+                        after = tally()
+                        advanced = 1 if (m or verb in ("transform", "grade")) else 0
+                        assert after[calls] == before[calls] + advanced, (case, before, after)
+                        if advanced:
+                            assert after[key] == m, (case, after)
+                        if verb == "read_masked":
+                            _assert_same_splats(got, A.subset(rows), case)
+                            got = got.P.shape[0]
+                        assert got == m, (case, got, m)
+                        cloud = U.read()
+                        _assert_same_splats(cloud, want, case)
+                        runs.append((got, cloud))
+                    assert runs[0][0] == runs[1][0], (n, label, verb)
+                    _assert_same_splats(runs[1][1], runs[0][1], f"n {n}, {label}, {verb}: device run against host run")
+    finally:
+        hb.free()

@@ -281,7 +281,7 @@ def test_the_kernel_uses_no_scratch():
         m = re.match(r"(\S+)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+lds\s+(\d+)\s+scratch\s+(\d+)", ln)
         if m:
             rows[m.group(1)] = tuple(int(v) for v in m.groups()[1:])
-    for prefix, lds_max in (("_Z11k_transformILb0E", 0), ("_Z11k_transformILb1E", 64 * 112), ("_Z17k_transform_count", 0)):
+    for prefix, lds_max in (("_Z11k_transformILb0E", 0), ("_Z11k_transformILb1E", 64 * 112), ("_Z12k_mask_count", 0)):
         hit = [v for k, v in rows.items() if k.startswith(prefix)]
         assert len(hit) == 1, (prefix, sorted(rows))
         vg, sg, lds, scratch = hit[0]
