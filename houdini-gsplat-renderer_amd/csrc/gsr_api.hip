@@ -57,6 +57,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_select.h"
 #include "k_transform.h"
 #include "k_grade.h"
+#include "k_select_attrs.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -372,15 +373,15 @@ struct gsr_context {
     // gsr_remove (k_remove.h): the SECOND array of true alphas the compaction writes (swapped with alpha0 like the planes; only with a
     // visibility in force)
     DevMem<float> alpha0_2;
-    // gsr_select (k_select.h): the counter slots of k_select, and where they are read back
+    // gsr_select (k_select.h) and gsr_select_attrs (k_select_attrs.h): the counter slots of either kernel, and where they are read back
     DevMem<unsigned long long> sel_counters;
     PinnedMem<unsigned long long> sel_h_counters;
     // the mask verbs (gsr_remove, gsr_read_masked, gsr_duplicate, gsr_transform, gsr_grade): the pinned words a count arrives in
     // (ensure_h_word; two words, read behind a wait of the verb's own)
     PinnedMem<uint32_t> h_word;
-    // what gsr_get_removal, _add, _read, _select, _transform, _grade and _duplicate report (gsr_get_add: also the capacity in force,
-    // c->cap, and the adds that grew it)
-    EditTally rm, add, rd, sel, xf, gr, dup;
+    // what gsr_get_removal, _add, _read, _select, _transform, _grade, _duplicate and _select_attrs report (gsr_get_add: also the
+    // capacity in force, c->cap, and the adds that grew it)
+    EditTally rm, add, rd, sel, xf, gr, dup, sela;
     int64_t add_grows = 0;
 };
 

@@ -707,6 +707,13 @@ extern "C" int gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_s
     return rc ? rc : gsr_select(m->ctx[0], cam, region, mask_host, 0, n_hit, n_set);
 }
 
+// ... and selected by attribute on rank 0's replica (gsr_select_attrs into a host mask: the caller's thread; no rank's state changes)
+extern "C" int gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set)
+{
+    const int rc = multi_enter(m, rule && mask_host, "gsr_multi_select_attrs");
+    return rc ? rc : gsr_select_attrs(m->ctx[0], rule, mask_host, 0, n_hit, n_set);
+}
+
 // ... and transformed on every rank: each bakes the transform into its own replica and re-orders it
 extern "C" int gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved)
 {

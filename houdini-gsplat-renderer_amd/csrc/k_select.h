@@ -96,18 +96,13 @@ __host__ __device__ __forceinline__ uint32_t gsr_select_apply(int op, uint32_t p
 #define GSR_SELECT_THREADS     256
 #define GSR_SEL_COUNTER_SLOTS  512
 #define GSR_SEL_COUNTER_STRIDE 8       // in 64-bit words
-__global__ void __launch_bounds__(GSR_SELECT_THREADS)
-k_select(uint32_t n, const uint32_t* __restrict__ inv, const float4* __restrict__ geoA, GsrSelectRule rule,
-         const uint32_t* __restrict__ image /* NULL: none */, const float* __restrict__ depth /* NULL: none */, int op,
-         uint32_t* __restrict__ mask, unsigned long long* __restrict__ counters)
+// The epilogue of every selection kernel (k_select, k_select_attrs.h): thread i = blockIdx.x * GSR_SELECT_THREADS + threadIdx.x holds
+// the verdict of upload index i (false for i >= n); every lane of the wave must call it.  The ballot, the two mask words of lanes 0
+// and 32, and the wave's counts, as described above.
+__device__ __forceinline__ void gsr_select_epilogue(uint32_t n, uint32_t i, bool hit, int op, uint32_t* __restrict__ mask,
+                                                    unsigned long long* __restrict__ counters)
 {
-    const uint32_t i = blockIdx.x * (uint32_t)GSR_SELECT_THREADS + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
-    bool hit = false;
-    if (i < n) {
-        const float4 a = geoA[inv ? inv[i] : i];
-        hit = gsr_select_hit(rule, a.x, a.y, a.z, a.w, image, depth, nullptr);
-    }
     const unsigned long long ballot = __ballot(hit);   // (every lane of the wave is here: nobody has left)
     uint32_t set = 0u;
     if ((lane & 31u) == 0u) {
@@ -125,6 +120,20 @@ k_select(uint32_t n, const uint32_t* __restrict__ inv, const float4* __restrict_
     const unsigned long long counts = (unsigned long long)__popcll(ballot) | ((unsigned long long)n_set << 32);
     if (lane == 0u && counts)
         atomicAdd(counters + (size_t)(blockIdx.x & (GSR_SEL_COUNTER_SLOTS - 1u)) * GSR_SEL_COUNTER_STRIDE, counts);
+}
+
+__global__ void __launch_bounds__(GSR_SELECT_THREADS)
+k_select(uint32_t n, const uint32_t* __restrict__ inv, const float4* __restrict__ geoA, GsrSelectRule rule,
+         const uint32_t* __restrict__ image /* NULL: none */, const float* __restrict__ depth /* NULL: none */, int op,
+         uint32_t* __restrict__ mask, unsigned long long* __restrict__ counters)
+{
+    const uint32_t i = blockIdx.x * (uint32_t)GSR_SELECT_THREADS + threadIdx.x;
+    bool hit = false;
+    if (i < n) {
+        const float4 a = geoA[inv ? inv[i] : i];
+        hit = gsr_select_hit(rule, a.x, a.y, a.z, a.w, image, depth, nullptr);
+    }
+    gsr_select_epilogue(n, i, hit, op, mask, counters);
 }
 
 // How many of the first n bits of a mask are set (gsr_transform and gsr_grade count the mask a selection leaves before they write

@@ -127,6 +127,14 @@ class gsr_select_region(C.Structure):
                 ("depth_bias", C.c_float), ("op", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_attr_rule(C.Structure):
+    """include/gsplat_hip.h: the rule of gsr_select_attrs -- clauses on the true alpha, the scale halves, the base colour and crop volumes"""
+    _fields_ = [("clauses", C.c_int32), ("flags", C.c_int32), ("op", C.c_int32), ("n_volumes", C.c_int32),
+                ("alpha_lo", C.c_float), ("alpha_hi", C.c_float), ("scale_max_lo", C.c_float), ("scale_max_hi", C.c_float),
+                ("scale_min_lo", C.c_float), ("scale_min_hi", C.c_float), ("anisotropy", C.c_float),
+                ("colour_lo", C.c_float * 3), ("colour_hi", C.c_float * 3), ("reserved_", C.c_int32), ("volume", gsr_crop_volume * 4)]
+
+
 class gsr_xform(C.Structure):
     """include/gsplat_hip.h: the similarity of gsr_transform -- p' = s R (p - pivot) + pivot + translate"""
     _fields_ = [("rotate", C.c_float * 4), ("scale", C.c_float), ("translate", C.c_float * 3), ("pivot", C.c_float * 3), ("reserved_", C.c_int32)]
@@ -189,6 +197,9 @@ COPY_BLOCK = REMOVE_BLOCK      # ... and of k_copy.h's, which keep that shape
 SELECT_REPLACE, SELECT_ADD, SELECT_SUBTRACT, SELECT_INTERSECT, SELECT_TOGGLE = range(5)     # GSR_SELECT_*: what gsr_select does to the mask
 SELECT_ANY_OPACITY = 1 # GSR_SELECT_ANY_OPACITY (flags): no opacity test, so hidden splats can be hit
 SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the selection kernel spans
+# GSR_ATTR_* (gsr_attr_rule.clauses): what gsr_select_attrs looks at; ATTR_SKIP_HIDDEN (flags): hidden splats are never hit
+ATTR_ALPHA, ATTR_SCALE_MAX, ATTR_SCALE_MIN, ATTR_ANISOTROPY, ATTR_COLOUR, ATTR_VOLUME = 1, 2, 4, 8, 16, 32
+ATTR_SKIP_HIDDEN = 1
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -229,6 +240,7 @@ C_ABI_SYMBOLS = [
     "gsr_copy_map", "gsr_read_masked", "gsr_read_masked_device", "gsr_duplicate", "gsr_get_duplicate", "gsr_multi_read_masked", "gsr_multi_duplicate",
     "gsr_debug_replica_verdict",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
+    "gsr_select_attrs", "gsr_select_attrs_eval", "gsr_get_select_attrs", "gsr_multi_select_attrs",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan", "gsr_debug_stage_bytes",
@@ -359,6 +371,10 @@ def load_library() -> C.CDLL:
     L.gsr_select_eval.argtypes = [C.POINTER(gsr_camera), f32p, C.POINTER(gsr_select_region), vp, vp, i64, vp, vp]
     L.gsr_get_select.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_select.argtypes = [vp, C.POINTER(gsr_camera), C.POINTER(gsr_select_region), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_attrs.argtypes = [vp, C.POINTER(gsr_attr_rule), vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_attrs_eval.argtypes = [C.POINTER(gsr_attr_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp]
+    L.gsr_get_select_attrs.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_select_attrs.argtypes = [vp, C.POINTER(gsr_attr_rule), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_xform_prepare.argtypes = [C.POINTER(gsr_xform), C.POINTER(gsr_xform_rule)]
     L.gsr_transform_eval.argtypes = [C.POINTER(gsr_xform), i64] + [vp] * 7
     L.gsr_transform.argtypes = [vp, vp, i32, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
@@ -812,6 +828,54 @@ def select_eval(cam, origin, region, P, opacity=None, centres: bool = False):
     _check(load_library().gsr_select_eval(C.byref(cs), _f3(origin), C.byref(r), P.ctypes.data if n else None, _ptr(a) if n else None, n,
                                           hit.ctypes.data, _ptr(c)))
     return (hit[:n].astype(bool), c[:n]) if centres else hit[:n].astype(bool)
+
+
+def attr_rule(alpha=None, scale_max=None, scale_min=None, anisotropy=None, colour=None, volumes=(), op: int = SELECT_REPLACE,
+              skip_hidden: bool = False) -> gsr_attr_rule:
+    """gsr_attr_rule: every argument that is not None (volumes: not empty) sets its clause.  alpha, scale_max, scale_min = (lo, hi)
+    ranges, inclusive; anisotropy = k (hit iff smax > 0 and smax >= k smin); colour = (lo, hi) with each a scalar or (r, g, b);
+    volumes = [(kind, invert, to_unit12), ...] as crop_box / crop_ellipsoid build them; op = SELECT_*; skip_hidden: a splat the
+    visibility in force hides is never hit.  What the fields may hold is the library's to refuse."""
+    r = gsr_attr_rule()
+    r.op, r.flags = int(op), ATTR_SKIP_HIDDEN if skip_hidden else 0
+    for bit, rng, lo, hi in ((ATTR_ALPHA, alpha, "alpha_lo", "alpha_hi"), (ATTR_SCALE_MAX, scale_max, "scale_max_lo", "scale_max_hi"),
+                             (ATTR_SCALE_MIN, scale_min, "scale_min_lo", "scale_min_hi")):
+        if rng is not None:
+            r.clauses |= bit
+            setattr(r, lo, float(rng[0]))
+            setattr(r, hi, float(rng[1]))
+    if anisotropy is not None:
+        r.clauses |= ATTR_ANISOTROPY
+        r.anisotropy = float(anisotropy)
+    if colour is not None:
+        r.clauses |= ATTR_COLOUR
+        r.colour_lo[:] = np.broadcast_to(np.asarray(colour[0], np.float32), (3,)).tolist()
+        r.colour_hi[:] = np.broadcast_to(np.asarray(colour[1], np.float32), (3,)).tolist()
+    volumes = list(volumes)
+    if volumes:
+        r.clauses |= ATTR_VOLUME
+        r.n_volumes = len(volumes)
+        for k, (kind, invert, to_unit) in enumerate(volumes[:VIS_MAX_VOLUMES]):
+            r.volume[k].kind, r.volume[k].invert = int(kind), int(invert)
+            r.volume[k].to_unit[:] = np.asarray(to_unit, dtype=np.float32).reshape(12).tolist()
+    return r
+
+
+def select_attrs_eval(rule, P=None, alpha=None, scale=None, Cd=None, vis=None) -> np.ndarray:
+    """gsr_select_attrs_eval (host only, no GPU): the rule of gsr_select_attrs through the function the kernel evaluates.  Arrays in
+    read()'s layout: P float32 (n, 3), alpha float32 (n,) TRUE alphas, scale and Cd uint16 halves (n, 3); an array no set clause looks
+    at may be None (at least one array says n).  vis: the gsr_visibility (visibility_struct) that skip_hidden hides by, or None
+    -> bool (n,) hit"""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=t).reshape(-1, w) for a, t, w in
+            ((P, np.float32, 3), (alpha, np.float32, 1), (scale, np.uint16, 3), (Cd, np.uint16, 3))]
+    sizes = {a.shape[0] for a in arrs if a is not None}
+    if len(sizes) != 1:
+        raise GsrError(-1, f"select_attrs_eval: the arrays hold {sorted(sizes)} rows")
+    n = sizes.pop()
+    hit = np.zeros(max(n, 1), np.uint8)
+    _check(load_library().gsr_select_attrs_eval(C.byref(rule), C.byref(vis) if vis is not None else None, n,
+                                                *[a.ctypes.data if a is not None and n else None for a in arrs], hit.ctypes.data))
+    return hit[:n].astype(bool)
 
 
 def unpack_mask(words, n: int) -> np.ndarray:
@@ -1484,6 +1548,30 @@ class Engine:
         """gsr_get_select -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
         return self._tally(self.L.gsr_get_select, "selects", "hit_last")
 
+    # ---- selection by attribute (include/gsplat_hip.h, "selection by attribute")
+    def select_attrs(self, rule: gsr_attr_rule, mask=None):
+        """gsr_select_attrs into a HOST mask: the resident splats the rule (attr_rule) hits -> (bool (n,) mask in upload order, n_hit,
+        n_set).  mask = the prior selection the rule's op combines with (a boolean array over the resident splats or packed uint32 words;
+        None: nothing selected).  Changes and invalidates nothing."""
+        n = self.read_info()["n_splats"]
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_select_attrs(self.h, C.byref(rule), words.ctypes.data, 0, C.byref(hit), C.byref(nset)))
+        return unpack_mask(words, n), hit.value, nset.value
+
+    def select_attrs_device(self, rule: gsr_attr_rule, mask_ptr):
+        """gsr_select_attrs into packed uint32 mask words in DEVICE memory (a raw pointer or an object with data_ptr(); ceil(n / 32)
+        words, read first by every op but SELECT_REPLACE).  Waits for the work queued on the stream given to set_stream first;
+        synchronous -> (n_hit, n_set).  The mask goes straight into remove_device (a prune: nothing crosses the link)."""
+        ptr = _device_mask_ptr(mask_ptr, "select_attrs_device")
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_select_attrs(self.h, C.byref(rule), C.c_void_p(ptr), 1, C.byref(hit), C.byref(nset)))
+        return hit.value, nset.value
+
+    def get_select_attrs(self) -> dict:
+        """gsr_get_select_attrs -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
+        return self._tally(self.L.gsr_get_select_attrs, "selects", "hit_last")
+
     def _tally(self, get, *keys) -> dict:
         """a gsr_get_* of the resident-edit family: its int64 outputs (the calls, the last count, and what else the verb reports) under
         `keys`, in their order, then "ms": the last call's clock"""
@@ -2116,6 +2204,17 @@ class MultiEngine:
         hit, nset = C.c_int64(0), C.c_int64(0)
         cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
         _check(self.L.gsr_multi_select(self.h, C.byref(cs), C.byref(r), words.ctypes.data, C.byref(hit), C.byref(nset)))
+        return unpack_mask(words, n), hit.value, nset.value
+
+    def select_attrs(self, rule: gsr_attr_rule, mask=None):
+        """gsr_multi_select_attrs: Engine.select_attrs on rank 0's copy (the cloud is replicated), into a host mask -> (bool mask, n_hit,
+        n_set)"""
+        cnt = C.c_int64(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), None, None))
+        n = cnt.value
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        hit, nset = C.c_int64(0), C.c_int64(0)
+        _check(self.L.gsr_multi_select_attrs(self.h, C.byref(rule), words.ctypes.data, C.byref(hit), C.byref(nset)))
         return unpack_mask(words, n), hit.value, nset.value
 
     def render(self, cam, depth=None) -> np.ndarray:

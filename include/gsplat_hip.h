@@ -636,6 +636,71 @@ int  gsr_select_eval(const gsr_camera* cam, const float origin[3], const gsr_sel
                      uint8_t* hit_out, float* centre_out /* [n][3] = cx, cy, zw of a selectable splat, else NaN; or NULL */);   /* host, no context, no GPU */
 int  gsr_get_select(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- selection by attribute (resident splats picked by what they are, on the GPU) --------------------------------------------------- */
+/* The mask gsr_select makes, from what a splat IS instead of where its centre projects: prune everything below an opacity, larger than
+ * a size or thinner than a needle; pick what lies in a box or an ellipsoid; key out a base colour -- without reading P, alpha, scale
+ * and Cd back over the link.  One streaming kernel (k_select_attrs.h), one thread per upload index, gsr_select's mask epilogue.
+ * THE RULE (one function, evaluated by the kernel and by gsr_select_attrs_eval; x86 and gfx950 agree bit for bit).  For splat i,
+ * with a = its TRUE alpha (what gsr_read returns: under a visibility in force a hidden splat's own alpha, not the resident +0.0f),
+ * s_k = h2f(scale half k), smax / smin = the largest / smallest of |s_0|, |s_1|, |s_2|, and Cd_c = h2f(Cd half c), a splat is HIT
+ * iff it passes every clause that is set in `clauses` (none set: every splat):
+ *   GSR_ATTR_ALPHA       alpha_lo <= a <= alpha_hi
+ *   GSR_ATTR_SCALE_MAX   scale_max_lo <= smax <= scale_max_hi
+ *   GSR_ATTR_SCALE_MIN   scale_min_lo <= smin <= scale_min_hi
+ *   GSR_ATTR_ANISOTROPY  smax > 0 && smax >= anisotropy * smin      (one float32 multiply: a needle; all three scales 0 never pass)
+ *   GSR_ATTR_COLOUR      colour_lo[c] <= Cd_c <= colour_hi[c] for c = r, g, b
+ *   GSR_ATTR_VOLUME      every one of volume[0 .. n_volumes) passes: gsr_volume_inside(volume, raw P) != invert -- the function of
+ *                        gsr_set_visibility, with its float32 chains; an inverted volume passes what is NOT inside it
+ * A NaN anywhere a clause looks means no hit: a NaN alpha, a NaN scale half (for any of the three scale clauses), a NaN Cd half (for
+ * the colour clause), a NaN bound, a NaN coordinate of P (for the volume clause).  lo > hi is allowed and hits nothing; infinite bounds
+ * are allowed.  Non-finite matrix entries of a volume are the caller's data and follow the visibility's rule.
+ * flags: GSR_ATTR_SKIP_HIDDEN -- a splat the visibility in force hides (its volumes and mask, gsr_splat_visible on the raw P) is never
+ * hit; with no visibility in force nothing is hidden.
+ * THE MASK, op, n_hit and n_set are gsr_select's: ceil(n / 32) words in upload order, host (mask_is_device = 0) or device / pinned memory
+ * (1: checked with its exact size before anything is launched); every op but REPLACE reads the mask first; after any op the bits at and
+ * behind n are 0 and not one byte behind word ceil(n / 32) - 1 is written; no atomic touches the mask.  n_hit: the splats the rule
+ * hit, whatever the op; n_set: the bits set afterwards; either may be NULL.
+ * gsr_select_attrs_eval: the rule on the host, no context and no GPU.  Arrays in gsr_read's layout (P float[3n], alpha float[n] TRUE
+ * alphas, scale half[3n], Cd half[3n]); an array no set clause looks at may be NULL.  vis (NULL: none in force) is what SKIP_HIDDEN
+ * hides by, as gsr_visibility_eval takes it (a mask must cover the n splats).  op is checked and not applied.  hit_out[k] = 0 / 1.
+ * A SELECT CHANGES AND INVALIDATES NOTHING -- gsr_read's contract: no resident bit, depth horizon, cached depth order, policy or
+ * visibility state changes, no entry of gsr_stats; it does not wait for the frames in flight.  ORDERING: gsr_select's (with a device
+ * mask the call first waits for the work queued on the public stream); synchronous.
+ * GSR_E_INVALID, nothing written: NULL ctx, rule or mask; no geometry ever uploaded, or an upload in progress; unknown clause or flag
+ * bits; reserved_ != 0; n_volumes outside 1..GSR_VIS_MAX_VOLUMES with GSR_ATTR_VOLUME, or not 0 without it; an unknown volume kind;
+ * invert neither 0 nor 1; an unknown op; a device mask that fails the pointer check.  The empty cloud gives GSR_OK, writes nothing,
+ * and both counts are 0.
+ * gsr_get_select_attrs: the calls that selected, the splats hit by the last one, and its clock ms[4], laid out as gsr_get_select's:
+ * [0] the kernel (HIP events)   [1] the copies, wall clock   [2] 0.0 (reserved)   [3] wall clock of the call.
+ * gsr_multi_select_attrs (below, with the other gsr_multi verbs): rank 0's context and a host mask -- the cloud is replicated.
+ * Out of scope: the GSplatRenderer shim and the HDK glue; gsr_comm_* (each rank selects for itself); a device mask for the multi verb;
+ * clauses on SH energy or on view-dependent colour; a clause on screen-space size; a device mask for gsr_set_visibility; asynchronous
+ * forms. */
+#define GSR_ATTR_ALPHA       1   /* alpha_lo <= a <= alpha_hi; a = the TRUE alpha (what gsr_read returns) */
+#define GSR_ATTR_SCALE_MAX   2   /* scale_max_lo <= smax <= scale_max_hi */
+#define GSR_ATTR_SCALE_MIN   4   /* scale_min_lo <= smin <= scale_min_hi */
+#define GSR_ATTR_ANISOTROPY  8   /* smax > 0 && smax >= anisotropy * smin    (one f32 multiply) */
+#define GSR_ATTR_COLOUR     16   /* colour_lo[c] <= Cd_c <= colour_hi[c], c = r, g, b; Cd = h2f of the resident Cd halves */
+#define GSR_ATTR_VOLUME     32   /* every volume passes: gsr_volume_inside(vol, raw P) != invert, the visibility's own function */
+#define GSR_ATTR_SKIP_HIDDEN 1   /* flags: a splat the visibility in force hides is never hit */
+typedef struct gsr_attr_rule {
+    int32_t clauses;                      /* GSR_ATTR_* (0: every splat) */
+    int32_t flags;                        /* GSR_ATTR_SKIP_HIDDEN or 0 */
+    int32_t op;                           /* GSR_SELECT_REPLACE .. GSR_SELECT_TOGGLE */
+    int32_t n_volumes;                    /* 1..GSR_VIS_MAX_VOLUMES with GSR_ATTR_VOLUME, else 0 */
+    float   alpha_lo, alpha_hi;
+    float   scale_max_lo, scale_max_hi;
+    float   scale_min_lo, scale_min_hi;
+    float   anisotropy;
+    float   colour_lo[3], colour_hi[3];
+    int32_t reserved_;                    /* 0 */
+    gsr_crop_volume volume[GSR_VIS_MAX_VOLUMES];
+} gsr_attr_rule;
+int  gsr_select_attrs(gsr_context* ctx, const gsr_attr_rule* rule, uint32_t* mask, int mask_is_device, int64_t* n_hit, int64_t* n_set);
+int  gsr_select_attrs_eval(const gsr_attr_rule* rule, const gsr_visibility* vis /* NULL: none */, int64_t n, const float* P,
+                           const float* alpha, const uint16_t* scale, const uint16_t* Cd, uint8_t* hit_out);   /* host, no context, no GPU */
+int  gsr_get_select_attrs(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- transform: selected resident splats rotated, scaled, translated on the GPU ---- */
 /* What a mask of gsr_select is for besides hiding and removing: the selected splats are moved, turned and resized where they are
  * resident -- p' = s R (p - pivot) + pivot + translate -- with their scale, orient and SH coefficients following, and nothing but
@@ -877,6 +942,8 @@ int  gsr_multi_read(gsr_multi* m, int64_t first, int64_t n, const gsr_read_array
 /* gsr_select on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
 int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_region* region, uint32_t* mask_host,
                       int64_t* n_hit, int64_t* n_set);
+/* gsr_select_attrs on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
+int  gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set);
 /* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
  * rule: if the ranks do not agree on the count, or a rank fails after its first write, the verb fails and NO rank keeps geometry. */
 int  gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved);
