@@ -183,6 +183,20 @@ def camera_axes(cam):
     return -R.T @ V[:3, 3], R
 
 
+def _object_matrix():
+    a, b = np.deg2rad(25.0), np.deg2rad(-40.0)
+    rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+    rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
+    m = np.eye(4)
+    m[:3, :3] = rz @ rx @ np.diag([1.3, 0.8, 1.1])
+    m[:3, 3] = (0.1, -0.05, 0.2)
+    return m
+
+
+# an object transform with a rotation about two axes, a non-uniform scale and a translation (test_frame_constants_gpu.py, cull_edge_cases.py)
+OBJECT_MATRIX = _object_matrix()
+
+
 def unproject(cam, X, Y, D):
     """float64 world points at GL window coordinates (X, Y) (y up, pixel centres at +0.5) and view distance D, for a
     perspective camera whose projection has no off-centre terms"""

@@ -29,6 +29,8 @@ import os
 import numpy as np
 import pytest
 
+from helpers import OBJECT_MATRIX
+
 pytestmark = pytest.mark.gpu
 
 REC_FIELDS = ("cx", "cy", "a1x", "a1y", "b1x", "b1y", "r", "g", "b", "la")
@@ -36,17 +38,7 @@ ORIGIN = (0.25, -0.5, 0.125)
 N_FAR, N_WALL, N = 64, 8, 5 * 64 + 1
 
 
-def _object_matrix():
-    a, b = np.deg2rad(25.0), np.deg2rad(-40.0)
-    rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
-    rx = np.array([[1, 0, 0], [0, np.cos(b), -np.sin(b)], [0, np.sin(b), np.cos(b)]])
-    m = np.eye(4)
-    m[:3, :3] = rz @ rx @ np.diag([1.3, 0.8, 1.1])
-    m[:3, 3] = (0.1, -0.05, 0.2)
-    return m
-
-
-OBJ = _object_matrix()
+OBJ = OBJECT_MATRIX
 
 
 def _cameras(pkg, kind, sh_order, frames=3):
