@@ -417,11 +417,13 @@ k_compact_blocks(const uint32_t* __restrict__ keys_in, const V* __restrict__ val
 //                     (+ margins; what falls outside goes to the first / last bucket).  Every bucket owns a fixed region of
 //                     BK_CAP slots; a workgroup counts its keys per bucket in LDS and reserves room with one atomic per bucket
 //                     (counters 256 bytes apart: atomics that share a cache line serialise) -- no histogram / scan launches;
-//   k_radix_local     one workgroup per bucket sorts it on the bits the bucket index does not fix -- LSD passes of 8 bits that
-//                     never leave the CU for up to RL_CHUNK keys (registers + LDS), chunked through global memory beyond --
+//   k_radix_local     one workgroup per bucket sorts it on the bits the bucket index does not fix -- up to RL_CHUNK keys without
+//                     leaving the CU (registers + LDS): one distribution over RL_SUB_BINS sub-bins and a ranking inside each, or,
+//                     where a sub-bin overflows, LSD passes of 8 bits; chunked LSD passes through global memory beyond --
 //                     and writes it to its place in the dense output (exclusive prefix of the bucket counts).
 // The order INSIDE a bucket after the scatter is whatever the atomics made it, so the contract's tie order (equal keys in
-// storage order) is restored explicitly: runs of equal keys are re-ordered by their payload's splat index.
+// storage order) is restored explicitly: equal keys are ordered by their payload's splat index (ranked as (key, index) pairs, or,
+// behind the LSD passes, runs of equal keys re-ordered in place).
 // Correct for ANY prediction; what it cannot do in reasonable time -- a bucket that overflows its region, an endless run of
 // equal keys -- raises *failed, and the host renders the frame again with the three global passes (gsr_api.hip).
 #define RL_THREADS 256
@@ -433,6 +435,12 @@ k_compact_blocks(const uint32_t* __restrict__ keys_in, const V* __restrict__ val
 #define RL_BINS 256
 static_assert(BK_CAP >= RL_CHUNK, "a bucket's region holds at least one chunk");
 #define RL_MAX_RUN 64                        // longest run of equal keys re-ordered in place
+#define RL_SPEC_ROWS 2                       // rows of RL_THREADS items a workgroup of the local kernel requests before it knows its bucket's count
+#define RL_SUB_BITS 10
+#define RL_SUB_BINS (1 << RL_SUB_BITS)       // sub-bins of the one-pass distribution
+#define RL_SUB_MAX RL_MAX_RUN                // largest sub-bin whose items are ranked by counting
+static_assert(RL_SUB_MAX <= RL_MAX_RUN, "a run that the tie pass gives up on must reach the tie pass");
+static_assert(RL_SPEC_ROWS <= RL_ITEMS && RL_SPEC_ROWS * RL_THREADS <= BK_CAP, "the rows requested ahead of the count lie in the bucket's region");
 
 __device__ __forceinline__ uint32_t rl_id(uint32_t v) { return v; }
 __device__ __forceinline__ uint32_t rl_id(uint2 v) { return v.x; }
@@ -595,7 +603,9 @@ k_bucket_scatter_direct(const uint32_t* __restrict__ keys_in, const V* __restric
 // one stable 8-bit pass over the n (<= RL_CHUNK) items a workgroup holds in registers in (wave, round, lane) order:
 // on return skeys / svals hold them sorted by the digit, and dcount[d] = items with digit d, dbase[d] = their first position
 // wq = items per wave (a multiple of 64, <= RL_WAVE_ITEMS): wave w holds items [w * wq, (w + 1) * wq) -- a small bucket is
-// spread over the four waves instead of filling the first one round after round
+// spread over the four waves instead of filling the first one round after round.  wq == 0: the registers hold the bucket as it
+// was loaded, row-major over the workgroup (thread t: items t, 256 + t, ...) -- an enumeration in which the pass is not stable,
+// which the FIRST pass over a bucket need not be (the scatter's atomics left it in no order)
 template <typename V>
 __device__ __forceinline__ void rl_pass_in_lds(uint32_t (&k_)[RL_ITEMS], V (&v_)[RL_ITEMS], uint32_t n, uint32_t wq, int shift, uint32_t sub,
                                                uint32_t (*wc)[RL_BINS], uint32_t* dbase, uint32_t* dcount, uint32_t* s_wave,
@@ -608,8 +618,8 @@ __device__ __forceinline__ void rl_pass_in_lds(uint32_t (&k_)[RL_ITEMS], V (&v_)
     uint32_t meta[RL_ITEMS];
 #pragma unroll
     for (int r = 0; r < RL_ITEMS; ++r) {
-        const uint32_t li = (uint32_t)wave * wq + (uint32_t)r * 64u + (uint32_t)lane;
-        const bool valid = (uint32_t)r * 64u < wq && li < n;
+        const uint32_t li = wq ? (uint32_t)wave * wq + (uint32_t)r * 64u + (uint32_t)lane : (uint32_t)r * RL_THREADS + threadIdx.x;
+        const bool valid = (wq == 0u || (uint32_t)r * 64u < wq) && li < n;
         const uint32_t d = ((k_[r] - sub) >> shift) & (RL_BINS - 1);
         unsigned long long m = __ballot(valid);
         if (m == 0ull) { meta[r] = 0xffffffffu; continue; }   // (wave-uniform)
@@ -685,47 +695,77 @@ k_radix_local(const uint32_t* __restrict__ cnt, int low_bits, int full_bits, uin
     if (range_dev) { lo = range_dev[0]; low_bits = (int)range_dev[1]; }
     __shared__ uint32_t wc[4][RL_BINS];
     __shared__ uint32_t dbase[RL_BINS], dcount[RL_BINS], gbase[RL_BINS];
-    __shared__ uint32_t s_wave[4];
-    __shared__ uint32_t skeys[RL_CHUNK];
-    __shared__ V svals[RL_CHUNK];
+    __shared__ uint32_t s_wave[4], s_pre[4], s_over;
+    // one staging area: a chunk's keys and payloads for the LSD passes, or (key, splat index) pairs for the paths that rank by counting
+    __shared__ unsigned long long stage[RL_CHUNK * (sizeof(uint32_t) + sizeof(V)) / 8];
+    static_assert(sizeof(stage) >= 8 * RL_CHUNK && sizeof(V) % 4 == 0, "a packed pair per item of a chunk; payloads aligned behind the keys");
+    uint32_t* skeys = reinterpret_cast<uint32_t*>(stage);
+    V* svals = reinterpret_cast<V*>(skeys + RL_CHUNK);
+    unsigned long long* packed = stage;
+    const uint32_t t = threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int b = (int)blockIdx.x;
+    const bool last = b == BK_BUCKETS - 1;
     KPROFB(2, 0, BK_BUCKETS / 2)
     KPROF_BLK_BEGIN
-    // where the bucket goes: the (clamped) counts of the buckets before it
-    uint32_t before = 0;
-    for (int d = threadIdx.x; d < b; d += RL_THREADS) { const uint32_t c = cnt[(size_t)d * BK_STRIDE]; before += c < (uint32_t)BK_CAP ? c : (uint32_t)BK_CAP; }
-    uint32_t tot;
-    (void)block_excl_scan_256(before, s_wave, &tot);
-    const uint32_t start = tot;
-    KPROFB(2, 1, BK_BUCKETS / 2)
-    uint32_t n = cnt[(size_t)b * BK_STRIDE];
-    n = n < (uint32_t)BK_CAP ? n : (uint32_t)BK_CAP;
-    if (n_out && b == BK_BUCKETS - 1 && threadIdx.x == 0) *n_out = start + n;
-    if (n == 0u) return;
+    // ONE trip to memory for everything the workgroup needs first, requested together: the bucket's count, the head of its region
+    // (RL_SPEC_ROWS rows of one item per thread: the region always exists, what lies behind the count is stale and never used) and
+    // the counts of the buckets before it -- which only the final store needs, so they are summed after the sort
     uint32_t* ks = ksrc + (size_t)b * BK_CAP;
     V* vs = vsrc + (size_t)b * BK_CAP;
-    uint32_t* kd = kdst + start;
-    V* vd = vdst + start;
-    const bool middle = b > 0 && b < BK_BUCKETS - 1;
+    uint32_t n = cnt[(size_t)b * BK_STRIDE];
+    uint32_t k_[RL_ITEMS];
+    V v_[RL_ITEMS];
+#pragma unroll
+    for (int r = 0; r < RL_SPEC_ROWS; ++r) { k_[r] = ks[(uint32_t)r * RL_THREADS + t]; v_[r] = vs[(uint32_t)r * RL_THREADS + t]; }
+    uint32_t before[BK_BUCKETS / RL_THREADS];
+#pragma unroll
+    for (int i = 0; i < BK_BUCKETS / RL_THREADS; ++i) {
+        const int d = i * RL_THREADS + (int)t;
+        before[i] = cnt[(size_t)(d < b ? d : 0) * BK_STRIDE];             // (an address that exists, whatever b)
+    }
+    uint32_t* sc = &wc[0][0];                      // the distribution's RL_SUB_BINS counters, cleared while the loads travel
+    reinterpret_cast<uint4*>(sc)[t] = uint4{0u, 0u, 0u, 0u};
+    static_assert(RL_SUB_BINS == 4 * RL_THREADS && RL_SUB_BINS == 4 * RL_BINS, "a uint4 of sub-bin counters per thread, aliased onto wc");
+    if (t == 0u) s_over = 0u;
+    n = n < (uint32_t)BK_CAP ? n : (uint32_t)BK_CAP;
+    // where the bucket goes = the (clamped) counts of the buckets before it: post_before() leaves the waves' sums in LDS, and after
+    // the next barrier bucket_start() adds them up (the last bucket publishes the frame's count on the way)
+    auto post_before = [&]() {
+        uint32_t s = 0;
+#pragma unroll
+        for (int i = 0; i < BK_BUCKETS / RL_THREADS; ++i)                 // (first looked at here: the sort does not wait for them)
+            s += i * RL_THREADS + (int)t < b ? (before[i] < (uint32_t)BK_CAP ? before[i] : (uint32_t)BK_CAP) : 0u;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+        if (lane == 0) s_pre[wave] = s;
+    };
+    auto bucket_start = [&]() {
+        const uint32_t start = s_pre[0] + s_pre[1] + s_pre[2] + s_pre[3];
+        if (n_out && last && t == 0u) *n_out = start + n;
+        return start;
+    };
+    if (n == 0u) {
+        if (!(n_out && last)) return;
+        post_before();                             // (an empty last bucket still says how many keys the frame has)
+        __syncthreads();
+        (void)bucket_start();
+        return;
+    }
+    const bool middle = b > 0 && !last;
     const int sort_bits = middle ? low_bits : full_bits;
     const uint32_t sub = middle ? lo : 0u;
     const int npass = sort_bits <= 0 ? 0 : (sort_bits + 7) / 8;
-    uint32_t k_[RL_ITEMS];
-    V v_[RL_ITEMS];
     if (n <= 64u) {
         // a handful of keys (every bucket of a frame of ten thousand splats): every thread counts the keys
         // that come before its own -- (key, splat index) pairs, so the contract's tie order falls out -- and stores its key there.
         // n broadcast reads from LDS instead of two LSD passes with six barriers each: 8.6 -> 6.8 us on BASELINE C1.  (Not beyond:
         // at 100 - 256 keys the four waves, alone on their SIMDs, take longer over the comparisons than the passes take.)
-        unsigned long long* packed = reinterpret_cast<unsigned long long*>(svals);
-        static_assert(sizeof(V) * RL_CHUNK >= 8 * RL_THREADS, "the payload staging area holds one packed pair per thread");
-        const uint32_t t = threadIdx.x;
-        uint32_t key = 0u;
-        V val{};
-        if (t < n) { key = ks[t]; val = vs[t]; }
+        const uint32_t key = k_[0];
+        const V val = v_[0];
         const unsigned long long me = ((unsigned long long)key << 32) | (unsigned long long)rl_id(val);
         packed[t] = t < n ? me : ~0ull;           // (the padding never counts: nothing is below it, and it equals no pair)
+        post_before();
         __syncthreads();
         uint32_t rank = 0;
         for (uint32_t j0 = 0; j0 < n; j0 += 8u) {  // eight reads in flight: one at a time the loop is an LDS latency per key
@@ -735,31 +775,106 @@ k_radix_local(const uint32_t* __restrict__ cnt, int low_bits, int full_bits, uin
 #pragma unroll
             for (int u = 0; u < 8; ++u) rank += (o[u] < me || (o[u] == me && j0 + (uint32_t)u < t)) ? 1u : 0u;
         }
-        if (t < n) { kd[rank] = key; vd[rank] = val; }
+        const uint32_t start = bucket_start();
+        if (t < n) { kdst[start + rank] = key; vdst[start + rank] = val; }
         KPROF_BLK_END(2, n)
         return;
     }
     if (n <= (uint32_t)RL_CHUNK) {
-        // the whole bucket lives in registers + LDS for all passes, a quarter (rounded up to whole rounds of 64) per wave
+        // the whole bucket lives in registers, row-major over the workgroup as it was loaded (thread t: items t, 256 + t, ...)
+#pragma unroll
+        for (int r = RL_SPEC_ROWS; r < RL_ITEMS; ++r) {          // what lies beyond the rows requested at the top
+            const uint32_t li = (uint32_t)r * RL_THREADS + t;
+            k_[r] = 0u; v_[r] = V{};
+            if (li < n) { k_[r] = ks[li]; v_[r] = vs[li]; }
+        }
+        // ONE distribution on the top ten of the bits the bucket sorts on (a culled frame's buckets hold a few hundred to a thousand
+        // keys, nearly uniform over the bucket's range): counts by LDS atomics, one scan, every item's (key, splat index) pair dropped
+        // at its sub-bin's base + what the atomic returned -- and then every item counts the pairs of its own sub-bin that come
+        // before it: that is its place, and the contract's tie order.  Five barriers for the LSD passes' seven each and rl_fix_ties.
+        // A sub-bin beyond RL_SUB_MAX items (skewed keys; the first and the last bucket, which hold whatever fell outside the range;
+        // any run that rl_fix_ties would give up on) sends the whole bucket down the LSD passes below: slower, never wrong.
+        {
+            const int sh = sort_bits > RL_SUB_BITS ? sort_bits - RL_SUB_BITS : 0;
+            const uint32_t smask = sort_bits >= 32 ? 0xffffffffu : (sort_bits <= 0 ? 0u : (1u << sort_bits) - 1u);
+            uint32_t sr[RL_ITEMS];                     // sub-bin | arrival number in it << RL_SUB_BITS
+            static_assert(RL_SUB_BITS + 12 <= 32 && RL_CHUNK <= (1 << 12) && RL_SUB_MAX < (1 << 12), "packing of sr and bm");
+            __syncthreads();                           // (the counters are clear)
+#pragma unroll
+            for (int r = 0; r < RL_ITEMS; ++r) {
+                const uint32_t sbin = ((k_[r] - sub) & smask) >> sh;
+                sr[r] = sbin;
+                if ((uint32_t)r * RL_THREADS + t < n) sr[r] = sbin | (atomicAdd(&sc[sbin], 1u) << RL_SUB_BITS);
+            }
+            __syncthreads();
+            KPROFB(2, 1, BK_BUCKETS / 2)
+            const uint4 c4 = reinterpret_cast<const uint4*>(sc)[t];      // thread t owns sub-bins 4 t .. 4 t + 3
+            const uint32_t csum = c4.x + c4.y + c4.z + c4.w;
+            if (c4.x > (uint32_t)RL_SUB_MAX || c4.y > (uint32_t)RL_SUB_MAX || c4.z > (uint32_t)RL_SUB_MAX || c4.w > (uint32_t)RL_SUB_MAX) s_over = 1u;
+            const uint32_t inc = wave_incl_scan(csum);
+            if (lane == 63) s_wave[wave] = inc;
+            __syncthreads();
+            if (s_over == 0u) {                        // (workgroup-uniform)
+                uint32_t ex = inc - csum;
+#pragma unroll
+                for (int w = 0; w < 3; ++w) ex += w < wave ? s_wave[w] : 0u;
+                reinterpret_cast<uint4*>(sc)[t] = uint4{ex, ex + c4.x, ex + c4.x + c4.y, ex + c4.x + c4.y + c4.z};
+                post_before();
+                __syncthreads();
+                KPROFB(2, 2, BK_BUCKETS / 2)
+                uint32_t bm[RL_ITEMS];                 // the sub-bin's base | its items << 12; 0: no item
+#pragma unroll
+                for (int r = 0; r < RL_ITEMS; ++r) {
+                    bm[r] = 0u;
+                    if ((uint32_t)r * RL_THREADS + t < n) {
+                        const uint32_t sbin = sr[r] & (uint32_t)(RL_SUB_BINS - 1);
+                        const uint32_t base = sc[sbin];
+                        const uint32_t end = sbin + 1u < (uint32_t)RL_SUB_BINS ? sc[sbin + 1u] : n;
+                        bm[r] = base | ((end - base) << 12);
+                        packed[base + (sr[r] >> RL_SUB_BITS)] = ((unsigned long long)k_[r] << 32) | (unsigned long long)rl_id(v_[r]);
+                    }
+                }
+                __syncthreads();
+                KPROFB(2, 3, BK_BUCKETS / 2)
+                const uint32_t start = bucket_start();
+#pragma unroll
+                for (int r = 0; r < RL_ITEMS; ++r) {
+                    const uint32_t base = bm[r] & 4095u, members = bm[r] >> 12, arrival = sr[r] >> RL_SUB_BITS;
+                    if (members == 0u) continue;       // (no item)
+                    const unsigned long long me = ((unsigned long long)k_[r] << 32) | (unsigned long long)rl_id(v_[r]);
+                    uint32_t rank = 0;
+                    for (uint32_t j0 = 0; j0 < members; j0 += 4u) {   // (four reads in flight; a sub-bin mostly holds one to three items)
+                        unsigned long long o[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) { const uint32_t j = j0 + (uint32_t)u; o[u] = packed[base + (j < members ? j : members - 1u)]; }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const uint32_t j = j0 + (uint32_t)u;
+                            rank += (j < members && (o[u] < me || (o[u] == me && j < arrival))) ? 1u : 0u;
+                        }
+                    }
+                    kdst[start + base + rank] = k_[r];
+                    vdst[start + base + rank] = v_[r];
+                }
+                KPROFB(2, 4, BK_BUCKETS / 2)
+                KPROF_BLK_END(2, n)
+                return;
+            }
+        }
+        // LSD passes of 8 bits: the first one takes the items as the registers hold them (it need not be stable: the scatter's atomics
+        // left the bucket in no order), the later ones a quarter (rounded up to whole rounds of 64) per wave, in the order the pass before left
         const uint32_t wq = ((n + 255u) / 256u) * 64u;
         auto mine = [&](int r, uint32_t& li) { li = (uint32_t)wave * wq + (uint32_t)r * 64u + (uint32_t)lane; return (uint32_t)r * 64u < wq && li < n; };
-#pragma unroll
-        for (int r = 0; r < RL_ITEMS; ++r) {
-            uint32_t li;
-            k_[r] = 0u; v_[r] = V{};
-            if (mine(r, li)) { k_[r] = ks[li]; v_[r] = vs[li]; }
-        }
-        KPROFB(2, 2, BK_BUCKETS / 2)
         if (npass == 0) {      // (a bucket one key wide: nothing to sort but the ties)
 #pragma unroll
             for (int r = 0; r < RL_ITEMS; ++r) {
-                uint32_t li;
-                if (mine(r, li)) { skeys[li] = k_[r]; svals[li] = v_[r]; }
+                const uint32_t li = (uint32_t)r * RL_THREADS + t;
+                if (li < n) { skeys[li] = k_[r]; svals[li] = v_[r]; }
             }
             __syncthreads();
         }
         for (int p = 0; p < npass; ++p) {
-            rl_pass_in_lds(k_, v_, n, wq, 8 * p, sub, wc, dbase, dcount, s_wave, skeys, svals);
+            rl_pass_in_lds(k_, v_, n, p == 0 ? 0u : wq, 8 * p, sub, wc, dbase, dcount, s_wave, skeys, svals);
             if (p + 1 < npass) {
 #pragma unroll
                 for (int r = 0; r < RL_ITEMS; ++r) {
@@ -769,15 +884,19 @@ k_radix_local(const uint32_t* __restrict__ cnt, int low_bits, int full_bits, uin
                 __syncthreads();
             }
         }
-        KPROFB(2, 3, BK_BUCKETS / 2)
-        rl_fix_ties(skeys, svals, n, failed);
-        KPROFB(2, 4, BK_BUCKETS / 2)
+        post_before();
+        rl_fix_ties(skeys, svals, n, failed);      // (ends in a barrier)
+        uint32_t* kd = kdst + bucket_start();
+        V* vd = vdst + (kd - kdst);
         for (uint32_t j = threadIdx.x; j < n; j += RL_THREADS) { kd[j] = skeys[j]; vd[j] = svals[j]; }
-        KPROFB(2, 5, BK_BUCKETS / 2)
         KPROF_BLK_END(2, n)
         return;
     }
     // a bucket larger than one chunk: every pass goes through global memory, chunk by chunk in order (src -> dst -> src ...)
+    post_before();
+    __syncthreads();
+    uint32_t* kd = kdst + bucket_start();
+    V* vd = vdst + (kd - kdst);
     uint32_t* ka = ks; V* va = vs;
     uint32_t* kb = kd; V* vb = vd;
     for (int p = 0; p < npass; ++p) {

@@ -26,12 +26,12 @@ for f in range(40):
         acc += d; cnt += 1
 labels = {0: ("k_bin_place", ["ranges (scan of the totals)", "n, tile", "zero the lane masks", "load splats + (A) masks", "-", "(S) group positions", "(B) place"]),
           1: ("k_bucket_scatter", ["n, zero LDS", "gather + LDS count", "reservations (global atomics)", "scatter"]),
-          2: ("k_radix_local (bucket 512)", ["prefix of the bucket counts", "load keys", "LSD passes in LDS", "ties", "store"]),
+          2: ("k_radix_local (bucket 512, the one-pass distribution)", ["count + first rows arrive, sub-bin counts (LDS atomics)", "scan of the sub-bin counts, bases", "pairs into LDS; prefix of the bucket counts", "rank inside the sub-bin + store"]),
           4: ("k_preprocess (the workgroup in the middle of the grid, first iteration)", ["prologue: prefix of the cluster counts", "find cluster + geoA/geoB arrive", "front + back (chain, horizons, colour, record)", "compaction + key/payload store"])}
 for k, (nm, labs) in labels.items():
     print(nm)
     for i, l in enumerate(labs, start=1):
-        print("   %-34s %6.2f us" % (l, acc[k, i] / max(cnt, 1)))
+        print("   %-58s %6.2f us" % (l, acc[k, i] / max(cnt, 1)))
 
 fb = lib.gsr_debug_kprof_blocks; fb.argtypes = [C.c_void_p]
 blk = np.zeros((5, 2, 8192), np.uint32); fb(blk.ctypes.data)
@@ -48,4 +48,5 @@ for k, nm in ((4, "k_preprocess"), (1, "k_bucket_scatter"), (2, "k_radix_local")
     if k in (0, 3):   # which blocks are the slow ones?  (blocks are in depth order: index 0 = the nearest 1024 splats)
         idx = np.argsort(-np.where(live, dur, 0))[:8]
         print("      slowest workgroups (index: us): " + ", ".join("%d: %.1f" % (int(i), float(dur[i])) for i in idx) + "; sum over workgroups %.0f us" % float(dur[live].sum()))
+print("plan", {k: v for k, v in eng.debug_last_plan().items() if k in ("cull", "local", "k1_scatters", "key_bits", "bk_lo", "bk_shift")})
 print({k: eng.stats()[k] for k in ("frames_culled", "frames_repaired", "n_visible", "pairs_total")})
