@@ -58,6 +58,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_transform.h"
 #include "k_grade.h"
 #include "k_select_attrs.h"
+#include "k_marks.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -383,6 +384,7 @@ struct gsr_context {
     // capacity in force, c->cap, and the adds that grew it)
     EditTally rm, add, rd, sel, xf, gr, dup, sela;
     int64_t add_grows = 0;
+    EditTally marks;                   // gsr_get_marks (k_marks.h): the calls that drew, the pixels the last one wrote
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -2794,6 +2796,8 @@ extern "C" int gsr_render_wire(gsr_context* c, const gsr_camera* cam, float* rgb
 // wire-over display (the reference draws the outlines AND keeps the primitive in the splat pass, src/GR_GSplat.C:471-486): the outlines
 // go on top of the frame that is already in rgba_inout; pixels no outline covers are left as they are
 extern "C" int gsr_render_wire_over(gsr_context* c, const gsr_camera* cam, float* rgba_inout, int is_device) { return render_wire(c, cam, rgba_inout, is_device, 1); }
+// (gsr_render_marks, the selection overlay, shares this z-buffer and staging image; its body is at the end of the file, behind the
+// mask intake and the pointer check it takes from the resident edits)
 static int render_wire(gsr_context* c, const gsr_camera* cam, float* rgba_out, int out_is_device, int over)
 {
     if (!c || !cam || !rgba_out) return set_err(GSR_E_INVALID, "gsr_render_wire: NULL argument");
@@ -3021,3 +3025,135 @@ extern "C" int gsr_stats_reset(gsr_context* c)
 #include "gsr_resident_read.h"
 // ... and selected by screen region: read's contract, and k_select behind k_unpack.
 #include "gsr_resident_select.h"
+
+// ---------------------------------------------------------------------------
+// Selection overlay (k_marks.h): the splats a mask selects drawn into a finished frame.  render_wire(over = 1)'s
+// shape -- the same z-buffer, the same staging image for a host target, the same waits -- with gsr_select's intake in front of it:
+// the mask through MaskArg, every device pointer through check_device_source before anything is launched, what comes from host
+// memory copied when the call is made.  Writes nothing the context keeps but its own tally.
+static_assert(GSR_MARK_DOT == GSR_MARKK_DOT && GSR_MARK_OUTLINE == GSR_MARKK_OUTLINE && GSR_MARK_COLOUR_FIXED == GSR_MARKC_FIXED &&
+              GSR_MARK_COLOUR_CD == GSR_MARKC_CD && GSR_MARK_ANY_OPACITY == GSR_SELF_ANY_OPACITY, "the header's shapes, colour modes and flags are the kernels'");
+
+// what is wrong with the caller's camera or style (NULL: nothing)
+static const char* mark_style_error(const gsr_camera* cam, const gsr_mark_style* s)
+{
+    if (cam->width < 1 || cam->height < 1 || cam->width > GSR_MAX_DIM || cam->height > GSR_MAX_DIM) return "width or height is not within 1..GSR_MAX_DIM";
+    if (s->shape != GSR_MARK_DOT && s->shape != GSR_MARK_OUTLINE) return "unknown shape";
+    if (s->radius < 0 || s->radius > (s->shape == GSR_MARK_DOT ? GSR_MARK_MAX_RADIUS : 0)) return "radius is not within 0..8 (DOT) or not 0 (OUTLINE)";
+    if (s->colour_mode != GSR_MARK_COLOUR_FIXED && s->colour_mode != GSR_MARK_COLOUR_CD) return "unknown colour mode";
+    if (s->flags & ~GSR_MARK_ANY_OPACITY) return "unknown flag bits";
+    if (s->reserved_ != 0) return "reserved_ is not 0";
+    if (s->colour_mode == GSR_MARK_COLOUR_FIXED) {
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(s->rgba[k])) return "rgba is not finite";
+        if (!(s->rgba[3] >= 0.0f && s->rgba[3] <= 1.0f)) return "the colour's alpha is not within [0, 1]";
+    }
+    return nullptr;
+}
+
+extern "C" int gsr_get_marks(gsr_context* c, int64_t* calls, int64_t* pixels_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_marks: ctx is NULL");
+    return c->marks.report(calls, pixels_last, ms);
+}
+
+extern "C" int gsr_render_marks(gsr_context* c, const gsr_camera* cam, const uint32_t* mask, int mask_is_device, const gsr_mark_style* st,
+                                void* rgba_inout, int is_device, int64_t* n_pixels)
+{
+    const char* const who = "gsr_render_marks";
+    if (!c || !cam || !st || !rgba_inout) return set_err(GSR_E_INVALID, "gsr_render_marks: NULL argument");
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const char* bad = mark_style_error(cam, st);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_render_marks: %s", bad);
+    if (is_device && !target_aligned(c, rgba_inout))
+        return set_err(GSR_E_INVALID, "gsr_render_marks: the device target is not aligned to its %d-byte pixel", gsr_format_pixel_bytes(c->target_format));
+    const uint32_t n = c->n;
+    if (n == 0) {                                      // the empty cloud: no word of the mask exists, and nothing is drawn
+        if (n_pixels) *n_pixels = 0;
+        return GSR_OK;
+    }
+    const double t_begin = up_now_ms();
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t npix = (size_t)cam->width * (size_t)cam->height, bpp = (size_t)gsr_format_pixel_bytes(c->target_format);
+    const MaskArg mk{mask, mask_is_device != 0, n};
+    const bool depth_host = st->depth && !st->depth_is_device;
+    // every device pointer, with its exact size, before anything is launched: a wrong pointer must never be found out by a kernel
+    if ((rc = mk.check(c, who))) return rc;
+    if (st->depth && st->depth_is_device && (rc = check_device_source(c, st->depth, npix * 4, who, "depth"))) return rc;
+    if (is_device && (rc = check_device_source(c, rgba_inout, npix * bpp, who, "the target"))) return rc;
+    // the frames in flight (the frame underneath may be one of them) and the public stream (whoever produced a device source there)
+    if ((rc = sync_all(c))) return rc;
+    // ---- everything the call needs, before the first launch: a host mask and a host depth buffer are staged in the arena
+    const size_t oDepth = pad256(mk.stage_bytes());
+    const size_t cwords = (size_t)GSR_SEL_COUNTER_SLOTS * GSR_SEL_COUNTER_STRIDE;
+    if ((rc = ensure_stage(c, oDepth + (depth_host ? npix * 4 : 0))) || (rc = c->wire.ensure(npix)) || (rc = ensure_inverse_perm(c)) ||
+        (rc = ensure_up_events(c, 3, who, true)) || (rc = ensure_sel_counters(c, who)))
+        return rc;
+    hipStream_t s = c->slot[0].own;
+    double copy_ms = 0.0;
+    const uint32_t* dmask = nullptr;
+    const float* ddepth = st->depth;
+    void* const target = is_device ? rgba_inout : (void*)(float*)c->wire.out;
+    hipError_t e = mk.to_device(c, s, 0, &copy_ms, &dmask);
+    if (e == hipSuccess && (depth_host || !is_device)) {
+        const double t0 = up_now_ms();
+        if (depth_host) {
+            float* d = reinterpret_cast<float*>(c->stage + oDepth);
+            e = hipMemcpyAsync(d, st->depth, npix * 4, hipMemcpyHostToDevice, s);
+            ddepth = d;
+        }
+        if (e == hipSuccess && !is_device) e = hipMemcpyAsync(target, rgba_inout, npix * bpp, hipMemcpyHostToDevice, s);   // (the frame underneath)
+        if (e == hipSuccess) e = hipStreamSynchronize(s);                      // the caller's depth buffer may be freed on return
+        copy_ms += up_now_ms() - t0;
+    }
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render_marks: %s", hipGetErrorString(e));
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    unsigned long long* const zbuf = c->wire.zbuf;
+    const int any = (st->flags & GSR_MARK_ANY_OPACITY) ? 1 : 0;
+    e = hipMemsetAsync(c->sel_counters, 0, cwords * 8, s);
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[0], s);
+    if (e == hipSuccess) e = hipMemsetAsync(zbuf, 0xff, npix * 8, s);          // GSR_WIRE_EMPTY, per call
+    if (e == hipSuccess) {
+        const dim3 grid(div_up(n, GSR_MARK_THREADS)), block(GSR_MARK_THREADS);
+        if (st->shape == GSR_MARK_DOT) {
+            gsr_select_region everywhere{};
+            everywhere.x0 = everywhere.y0 = -INFINITY;
+            everywhere.x1 = everywhere.y1 = INFINITY;
+            everywhere.flags = any ? GSR_SELECT_ANY_OPACITY : 0;
+            const GsrSelectRule rule = select_rule(cam, c->origin, &everywhere);
+            hipLaunchKernelGGL(k_mark<GSR_MARKK_DOT>, grid, block, 0, s, n, dmask, inv, c->geoA, c->geoB, rule, any, (int)st->radius, zbuf);
+        } else {
+            GsrFrame f;
+            build_frame(c, cam, &f);
+            hipLaunchKernelGGL(k_mark<GSR_MARKK_OUTLINE>, grid, block, 0, s, n, dmask, inv, c->geoA, c->geoB, f, any, 0, zbuf);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_mark_resolve, dim3((unsigned)((npix + GSR_MARK_THREADS - 1) / GSR_MARK_THREADS)), dim3(GSR_MARK_THREADS), 0, s, zbuf, npix,
+                           c->col, inv, (int)st->colour_mode, make_float4(st->rgba[0], st->rgba[1], st->rgba[2], st->rgba[3]), ddepth,
+                           st->depth_bias, target, c->target_format, c->sel_counters);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[2], s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const double t1 = up_now_ms();
+    if (e == hipSuccess) e = hipMemcpyAsync(c->sel_h_counters, c->sel_counters, cwords * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && !is_device) e = hipMemcpyAsync(rgba_inout, target, npix * bpp, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_render_marks: %s", hipGetErrorString(e));
+    copy_ms += up_now_ms() - t1;
+    unsigned long long wrote = 0, unused = 0;
+    sum_sel_counters(c, &wrote, &unused);
+    if (n_pixels) *n_pixels = (int64_t)wrote;
+    float ms = 0.0f;
+    c->marks.ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess ? (double)ms : 0.0;
+    c->marks.ms[1] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? (double)ms : 0.0;
+    c->marks.ms[2] = copy_ms;
+    c->marks.ms[3] = up_now_ms() - t_begin;
+    c->marks.calls += 1;
+    c->marks.last = (int64_t)wrote;
+    return GSR_OK;
+}

@@ -38,15 +38,12 @@ __device__ __forceinline__ void gsr_wire_edge(float x0, float y0, float x1, floa
     }
 }
 
-__global__ void __launch_bounds__(256)
-k_wire_splats(uint32_t n, GsrFrame f, const float4* __restrict__ geoA, const uint4* __restrict__ geoB,
-              unsigned long long* __restrict__ zbuf,
-              const uint32_t* __restrict__ perm /* storage slot -> index in the upload (spatially ordered storage), or NULL */)
+// The outline of ONE splat: a, b = its geoA and geoB vectors; its fragments carry the index perm[i] (perm = NULL: i itself).  The
+// per-splat body of k_wire_splats, and of k_mark<GSR_MARKK_OUTLINE> (k_marks.h), which calls it with an upload index and no perm:
+// the two kernels cannot drift apart.
+__device__ __forceinline__ void gsr_wire_splat(const GsrFrame& f, const float4 a, const uint4 b, uint32_t i, const uint32_t* __restrict__ perm,
+                                               unsigned long long* __restrict__ zbuf)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float4 a = geoA[i];
-    const uint4 b = geoB[i];
     const float x = a.x, y = a.y, z = a.z;                        // no origin offset in the wire program
     const float tvx = aff4(&f.ov[0], x, y, z), tvy = aff4(&f.ov[4], x, y, z), tvz = aff4(&f.ov[8], x, y, z);
     const float ftvy = -tvy;
@@ -77,6 +74,16 @@ k_wire_splats(uint32_t n, GsrFrame f, const float4* __restrict__ geoA, const uin
     gsr_wire_edge(c1x, c1y, c2x, c2y, f.width, f.height, frag, zbuf);   // 2-3
     gsr_wire_edge(c2x, c2y, c3x, c3y, f.width, f.height, frag, zbuf);   // 4-5
     gsr_wire_edge(c3x, c3y, c0x, c0y, f.width, f.height, frag, zbuf);   // 6-7
+}
+
+__global__ void __launch_bounds__(256)
+k_wire_splats(uint32_t n, GsrFrame f, const float4* __restrict__ geoA, const uint4* __restrict__ geoB,
+              unsigned long long* __restrict__ zbuf,
+              const uint32_t* __restrict__ perm /* storage slot -> index in the upload (spatially ordered storage), or NULL */)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    gsr_wire_splat(f, geoA[i], geoB[i], i, perm, zbuf);
 }
 
 __global__ void __launch_bounds__(256)

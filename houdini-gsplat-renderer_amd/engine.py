@@ -127,6 +127,12 @@ class gsr_select_region(C.Structure):
                 ("depth_bias", C.c_float), ("op", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class gsr_mark_style(C.Structure):
+    """include/gsplat_hip.h: how gsr_render_marks draws a selection -- dots or outlines, a fixed colour or Cd, an optional depth test"""
+    _fields_ = [("shape", C.c_int32), ("radius", C.c_int32), ("colour_mode", C.c_int32), ("flags", C.c_int32), ("rgba", C.c_float * 4),
+                ("depth", C.c_void_p), ("depth_is_device", C.c_int32), ("depth_bias", C.c_float), ("reserved_", C.c_int32)]
+
+
 class gsr_attr_rule(C.Structure):
     """include/gsplat_hip.h: the rule of gsr_select_attrs -- clauses on the true alpha, the scale halves, the base colour and crop volumes"""
     _fields_ = [("clauses", C.c_int32), ("flags", C.c_int32), ("op", C.c_int32), ("n_volumes", C.c_int32),
@@ -200,6 +206,10 @@ SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the s
 # GSR_ATTR_* (gsr_attr_rule.clauses): what gsr_select_attrs looks at; ATTR_SKIP_HIDDEN (flags): hidden splats are never hit
 ATTR_ALPHA, ATTR_SCALE_MAX, ATTR_SCALE_MIN, ATTR_ANISOTROPY, ATTR_COLOUR, ATTR_VOLUME = 1, 2, 4, 8, 16, 32
 ATTR_SKIP_HIDDEN = 1
+MARK_DOT, MARK_OUTLINE = 1, 2                  # GSR_MARK_*: gsr_mark_style.shape
+MARK_COLOUR_FIXED, MARK_COLOUR_CD = 0, 1       # ... .colour_mode
+MARK_ANY_OPACITY = 1                           # ... .flags: also splats below 1/255 and the ones a visibility hides
+MARK_MAX_RADIUS = 8                            # GSR_MARK_MAX_RADIUS: a dot is at most 17 x 17 pixels
 TARGET_DTYPES = {TARGET_RGBA32F: np.dtype(np.float32), TARGET_RGBA16F: np.dtype(np.float16), TARGET_RGBA8: np.dtype(np.uint8)}
 
 # every symbol include/gsplat_hip.h and include/GSplatRenderer.h declare
@@ -241,6 +251,7 @@ C_ABI_SYMBOLS = [
     "gsr_debug_replica_verdict",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_select_attrs", "gsr_select_attrs_eval", "gsr_get_select_attrs", "gsr_multi_select_attrs",
+    "gsr_render_marks", "gsr_get_marks",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan", "gsr_debug_stage_bytes",
@@ -404,6 +415,8 @@ def load_library() -> C.CDLL:
     L.gsplat_renderer_set_background.argtypes = [vp, C.POINTER(gsr_background)]
     L.gsr_render_wire.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
     L.gsr_render_wire_over.argtypes = [vp, C.POINTER(gsr_camera), vp, i32]
+    L.gsr_render_marks.argtypes = [vp, C.POINTER(gsr_camera), vp, i32, C.POINTER(gsr_mark_style), vp, i32, C.POINTER(C.c_int64)]
+    L.gsr_get_marks.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_synchronize.argtypes = [vp]
     L.gsr_get_stats.argtypes = [vp, C.POINTER(gsr_stats)]
     L.gsr_stats_reset.argtypes = [vp]
@@ -828,6 +841,40 @@ def select_eval(cam, origin, region, P, opacity=None, centres: bool = False):
     _check(load_library().gsr_select_eval(C.byref(cs), _f3(origin), C.byref(r), P.ctypes.data if n else None, _ptr(a) if n else None, n,
                                           hit.ctypes.data, _ptr(c)))
     return (hit[:n].astype(bool), c[:n]) if centres else hit[:n].astype(bool)
+
+
+def mark_style(shape: int = MARK_DOT, radius: int = 0, colour=(1.0, 1.0, 0.0, 1.0), any_opacity: bool = False, depth=None,
+               depth_bias: float = 0.0, depth_device: int | None = None):
+    """gsr_mark_style -> (struct, the arrays it points into: keep them alive during the call).  shape = MARK_DOT (radius 0..8 pixels
+    around the centre's pixel) or MARK_OUTLINE (radius 0); colour = a premultiplied (r, g, b, a), finite, 0 <= a <= 1, or "cd": each
+    splat's own (Cd, 1); depth = float32 (height, width) window depths, depth_device = a raw device pointer in its place.  What the
+    depth buffer's size must be is the camera's to say: Engine.render_marks checks it."""
+    st, keep = gsr_mark_style(), []
+    if shape not in (MARK_DOT, MARK_OUTLINE):
+        raise GsrError(-1, f"mark_style: unknown shape {shape!r}")
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= (MARK_MAX_RADIUS if shape == MARK_DOT else 0):
+        raise GsrError(-1, f"mark_style: radius {radius!r} is not within 0..{MARK_MAX_RADIUS} (dots) or not 0 (outlines)")
+    st.shape, st.radius = int(shape), int(radius)
+    if isinstance(colour, str):
+        if colour.lower() != "cd":
+            raise GsrError(-1, f"mark_style: colour {colour!r} is neither (r, g, b, a) nor \"cd\"")
+        st.colour_mode = MARK_COLOUR_CD
+    else:
+        col = np.asarray(colour, dtype=np.float32).reshape(-1)
+        if col.size != 4 or not np.isfinite(col).all() or not 0.0 <= col[3] <= 1.0:
+            raise GsrError(-1, "mark_style: a colour is a finite premultiplied (r, g, b, a) with 0 <= a <= 1")
+        st.colour_mode = MARK_COLOUR_FIXED
+        st.rgba[:] = [float(x) for x in col]
+    if depth is not None and depth_device is not None:
+        raise GsrError(-1, "mark_style: the depth buffer is given both as an array and as a device pointer")
+    if depth is not None:
+        d = np.ascontiguousarray(depth, dtype=np.float32).reshape(-1)
+        keep.append(d)
+        st.depth, st.depth_is_device = d.ctypes.data, 0
+    elif depth_device is not None:
+        st.depth, st.depth_is_device = int(depth_device), 1
+    st.depth_bias, st.flags = float(depth_bias), MARK_ANY_OPACITY if any_opacity else 0
+    return st, keep
 
 
 def attr_rule(alpha=None, scale_max=None, scale_min=None, anisotropy=None, colour=None, volumes=(), op: int = SELECT_REPLACE,
@@ -1571,6 +1618,38 @@ class Engine:
     def get_select_attrs(self) -> dict:
         """gsr_get_select_attrs -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
         return self._tally(self.L.gsr_get_select_attrs, "selects", "hit_last")
+
+    # ---- selection overlay (include/gsplat_hip.h, "selection overlay")
+    def render_marks(self, cam, mask, style, under: np.ndarray):
+        """gsr_render_marks over a HOST frame: the splats `mask` selects (a boolean array over the resident splats or packed uint32
+        words; None: every splat) drawn on top of `under` (a finished frame [H, W, 4] in the target format) as `style` (a
+        gsr_mark_style, or the (struct, keep) pair mark_style returns) says -> (the combined image, the pixels written).  Changes and
+        invalidates nothing."""
+        st, keep = style if isinstance(style, tuple) else (style, [])
+        _region_fits(cam, keep, "render_marks")
+        n = self.read_info()["n_splats"]
+        words = None if mask is None else removal_words(mask, n)
+        out = np.ascontiguousarray(under, dtype=target_dtype(self.target_format)).reshape(cam.height, cam.width, 4).copy()
+        cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+        wrote = C.c_int64(0)
+        _check(self.L.gsr_render_marks(self.h, C.byref(cs), None if words is None else words.ctypes.data, 0, C.byref(st), out.ctypes.data, 0, C.byref(wrote)))
+        return out, wrote.value
+
+    def render_marks_device(self, cam, mask_ptr, style, ptr: int) -> int:
+        """gsr_render_marks with the mask words and the frame in DEVICE memory (raw pointers or objects with data_ptr(); mask_ptr None:
+        every splat); the style's depth buffer may be a device pointer too (mark_style's depth_device).  Waits for the frames in flight
+        and the work queued on the stream given to set_stream first; synchronous -> the pixels written.  Nothing crosses the link."""
+        st, keep = style if isinstance(style, tuple) else (style, [])
+        _region_fits(cam, keep, "render_marks_device")
+        mptr = None if mask_ptr is None else C.c_void_p(_device_mask_ptr(mask_ptr, "render_marks_device"))
+        cs = cam if isinstance(cam, gsr_camera) else camera_struct(cam)
+        wrote = C.c_int64(0)
+        _check(self.L.gsr_render_marks(self.h, C.byref(cs), mptr, 1, C.byref(st), C.c_void_p(_device_mask_ptr(ptr, "render_marks_device")), 1, C.byref(wrote)))
+        return wrote.value
+
+    def get_marks(self) -> dict:
+        """gsr_get_marks -> {calls: calls that drew, pixels_last, ms: the last call's clock [clear + k_mark, k_mark_resolve, copies, wall]}"""
+        return self._tally(self.L.gsr_get_marks, "calls", "pixels_last")
 
     def _tally(self, get, *keys) -> dict:
         """a gsr_get_* of the resident-edit family: its int64 outputs (the calls, the last count, and what else the verb reports) under

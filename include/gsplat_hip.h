@@ -1098,6 +1098,61 @@ int  gsr_render_wire(gsr_context* ctx, const gsr_camera* cam, float* rgba_out, i
  * covers keep their value. */
 int  gsr_render_wire_over(gsr_context* ctx, const gsr_camera* cam, float* rgba_inout, int is_device);
 
+/* ---- selection overlay (k_marks.h) ------------------------
+ * SHOW a selection: the splats a mask selects (gsr_select's and gsr_select_attrs' output; NULL: every splat) are drawn into the
+ * finished frame in rgba_inout -- the camera's size, the context's target format -- as centre dots or as the outlines of their +-2
+ * quads, nearest first, in a fixed colour or their own Cd.  On the GPU throughout: with a device mask and a device target nothing
+ * crosses the link.  Whole image (ignores the row shard), synchronous, a device target aligned to its pixel: gsr_render_wire_over's
+ * rules.
+ * THE RULE.  A DOT is drawn for upload index i iff its mask bit is set, gsr_select_hit says hit for the rect (-inf, -inf, +inf, +inf)
+ * with no image and no depth -- the vertex stage's centre (cx, cy, zw), the clip test and the opacity test on the RESIDENT opacity
+ * (GSR_MARK_ANY_OPACITY = GSR_SELECT_ANY_OPACITY drops it), NaN meaning no hit -- and 0 <= cx < W && 0 <= cy < H.  Its fragments are
+ * the pixels [qx - r, qx + r] x [qy - r, qy + r] clipped to the image, qx = (int)cx, qy = (int)cy, r = radius.  An OUTLINE is drawn
+ * iff its mask bit is set and (GSR_MARK_ANY_OPACITY is given or the resident a >= 1.0f / 255.0f); its fragments are exactly the wire
+ * overlay's for that splat (its clip test, its covariance axes, its four edges).  Every fragment carries the key
+ * (bits(zw) << 32) | i; per pixel the smallest key wins: nearest first, the lower upload index on equal depth.  A pixel with a
+ * winner (zw, i) is left untouched under a depth buffer unless zw <= depth[p] + depth_bias (one f32 add, one compare; the winner has
+ * the pixel's smallest zw, so this is the per-fragment test).  Otherwise c = style.rgba, or (Cd_i.rgb, 1) as the wire overlay colours
+ * a line; D = the target pixel decoded by the background's rule (RGBA32F as is, binary16 exact, RGBA8 (float)byte / 255.0f); each
+ * channel is out = fmaf(1 - c.a, D, c), through the function gsr_composite_over composites with, stored by the target format's
+ * store.  Every other pixel keeps its bytes; *n_pixels (may be NULL) = the pixels written.
+ * CONSEQUENCES.  Radius-0 dots write exactly the centre pixels of the splats gsr_select hits with the same mask as prior, the same
+ * depth clause and GSR_SELECT_INTERSECT.  A NULL mask with OUTLINE and COLOUR_CD is the wire-over display that honours the visibility
+ * in force (with GSR_MARK_ANY_OPACITY, over a finite frame: gsr_render_wire_over's bytes).  The verb changes and invalidates nothing the context keeps --
+ * gsr_select's contract, gsr_stats included -- and a context that never calls it launches nothing new.
+ * mask: ceil(n / 32) words, host or device / pinned memory.  style.depth: float[height * width] window depths as gsr_render_depth
+ * takes them, a host buffer copied when the call is made, a device buffer read in place.  ORDERING: like gsr_render_wire_over the
+ * call first waits for the frames in flight and for the work queued on the public stream, so a device mask, depth buffer or frame
+ * produced there is complete.  Every device pointer is checked (gsr_upload_append_device's test) before anything is launched.
+ * GSR_E_INVALID, nothing written: a NULL ctx, camera, style or target; no geometry, or an upload in progress; a bad frame size, shape,
+ * radius or colour mode; unknown flag bits; a non-finite rgba or an alpha outside [0, 1] (FIXED); reserved_ != 0; a misaligned
+ * device target; a device pointer that fails the check.  The empty cloud and an all-clear mask: GSR_OK, 0 pixels, the target
+ * byte-identical.
+ * gsr_get_marks: the calls that drew, the pixels the last one wrote, and its clock ms[4]: [0] the z-buffer clear and k_mark,
+ * [1] k_mark_resolve (HIP events both), [2] the copies over the link (a host mask, depth buffer or frame), [3] wall clock.
+ * NOT COVERED: gsr_multi_* and gsr_comm_*, the GSplatRenderer shim and the HDK glue; a filled or tinted footprint in the beauty pass;
+ * an asynchronous form; an AOV. */
+#define GSR_MARK_DOT      1   /* a (2r+1)^2 square of pixels around the centre's pixel */
+#define GSR_MARK_OUTLINE  2   /* the wire overlay's outline of the splat's +-2 quad */
+#define GSR_MARK_COLOUR_FIXED 0
+#define GSR_MARK_COLOUR_CD    1   /* (Cd.rgb, 1), as the wire overlay colours a line */
+#define GSR_MARK_ANY_OPACITY  1   /* flags: also splats below 1/255 and the ones a visibility hides */
+#define GSR_MARK_MAX_RADIUS   8
+typedef struct gsr_mark_style {
+    int32_t shape;            /* GSR_MARK_DOT / GSR_MARK_OUTLINE */
+    int32_t radius;           /* DOT: 0..8 pixels; OUTLINE: 0 */
+    int32_t colour_mode;
+    int32_t flags;
+    float   rgba[4];          /* FIXED: premultiplied, finite, 0 <= a <= 1 */
+    const float* depth;       /* NULL: no test; float[height*width] window depths as gsr_render_depth takes them */
+    int32_t depth_is_device;
+    float   depth_bias;
+    int32_t reserved_;        /* 0 */
+} gsr_mark_style;
+int  gsr_render_marks(gsr_context* ctx, const gsr_camera* cam, const uint32_t* mask, int mask_is_device,
+                      const gsr_mark_style* style, void* rgba_inout, int is_device, int64_t* n_pixels);
+int  gsr_get_marks(gsr_context* ctx, int64_t* calls, int64_t* pixels_last, double ms[4]);   /* any pointer may be NULL */
+
 int  gsr_synchronize(gsr_context* ctx);
 int  gsr_get_stats(gsr_context* ctx, gsr_stats* out);     /* synchronizes the stream */
 int  gsr_stats_reset(gsr_context* ctx);
