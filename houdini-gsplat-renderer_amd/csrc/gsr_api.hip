@@ -59,6 +59,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_grade.h"
 #include "k_select_attrs.h"
 #include "k_marks.h"
+#include "k_measure.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -385,6 +386,8 @@ struct gsr_context {
     EditTally rm, add, rd, sel, xf, gr, dup, sela;
     int64_t add_grows = 0;
     EditTally marks;                   // gsr_get_marks (k_marks.h): the calls that drew, the pixels the last one wrote
+    EditTally meas;                    // gsr_get_measure (k_measure.h): the calls that measured, the splats the last one measured
+    PinnedMem<uint32_t> meas_h;        // ... and the pinned words its result block arrives in (allocated by the first measure)
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -3025,6 +3028,8 @@ extern "C" int gsr_stats_reset(gsr_context* c)
 #include "gsr_resident_read.h"
 // ... and selected by screen region: read's contract, and k_select behind k_unpack.
 #include "gsr_resident_select.h"
+// ... and measured: select's contract; k_measure and k_measure_fold behind k_select_attrs.
+#include "gsr_resident_measure.h"
 
 // ---------------------------------------------------------------------------
 // Selection overlay (k_marks.h): the splats a mask selects drawn into a finished frame.  render_wire(over = 1)'s

@@ -714,6 +714,13 @@ extern "C" int gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, u
     return rc ? rc : gsr_select_attrs(m->ctx[0], rule, mask_host, 0, n_hit, n_set);
 }
 
+// ... and measured on rank 0's replica (gsr_measure from a host mask: the caller's thread; no rank's state changes)
+extern "C" int gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out)
+{
+    const int rc = multi_enter(m, request && out, "gsr_multi_measure");
+    return rc ? rc : gsr_measure(m->ctx[0], mask_host, 0, request, out, hist_out);
+}
+
 // ... and transformed on every rank: each bakes the transform into its own replica and re-orders it
 extern "C" int gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved)
 {

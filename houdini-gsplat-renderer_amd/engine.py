@@ -141,6 +141,39 @@ class gsr_attr_rule(C.Structure):
                 ("colour_lo", C.c_float * 3), ("colour_hi", C.c_float * 3), ("reserved_", C.c_int32), ("volume", gsr_crop_volume * 4)]
 
 
+class gsr_hist_spec(C.Structure):
+    """include/gsplat_hip.h: one histogram of gsr_measure -- a channel, [lo, hi) in `bins` bins, and what gsr_hist_prepare derives"""
+    _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("bins", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("inv_w", C.c_float)]
+
+
+class gsr_measure_request(C.Structure):
+    """include/gsplat_hip.h: what gsr_measure computes -- bounds, extent, moments about ref, up to four histograms"""
+    _fields_ = [("what", C.c_int32), ("flags", C.c_int32), ("ref", C.c_float * 3), ("extent_k", C.c_float), ("n_hist", C.c_int32),
+                ("hist", gsr_hist_spec * 4), ("reserved_", C.c_int32)]
+
+
+class gsr_measure_result(C.Structure):
+    """include/gsplat_hip.h: what gsr_measure reports.  The Python door also sets .ref (float32 (3,), the request's) and .hist (one
+    uint32 array of bins + 3 counts per spec: the bins, then under, over, nan)"""
+    _fields_ = [("n_selected", C.c_int64), ("n_measured", C.c_int64), ("n_extent", C.c_int64),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("lo_e", C.c_float * 3), ("hi_e", C.c_float * 3), ("sum", C.c_double * 9)]
+    ref = (0.0, 0.0, 0.0)
+    hist = ()
+
+    def centroid(self) -> np.ndarray:
+        """float64 (3,): ref + sum(d) / n_measured, formed on the host (NaN where nothing was measured; needs MEASURE_MOMENTS)"""
+        s = np.array(self.sum[:3], np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.asarray(self.ref, np.float64) + s / np.float64(self.n_measured)
+
+    def covariance(self) -> np.ndarray:
+        """float64 (3, 3): E[d d^T] - E[d] E[d]^T over the measured splats (the population covariance), formed on the host"""
+        xx, xy, xz, yy, yz, zz = [float(v) for v in self.sum[3:]]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.array(self.sum[:3], np.float64) / np.float64(self.n_measured)
+            return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], np.float64) / np.float64(self.n_measured) - np.outer(m, m)
+
+
 class gsr_xform(C.Structure):
     """include/gsplat_hip.h: the similarity of gsr_transform -- p' = s R (p - pivot) + pivot + translate"""
     _fields_ = [("rotate", C.c_float * 4), ("scale", C.c_float), ("translate", C.c_float * 3), ("pivot", C.c_float * 3), ("reserved_", C.c_int32)]
@@ -206,6 +239,13 @@ SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the s
 # GSR_ATTR_* (gsr_attr_rule.clauses): what gsr_select_attrs looks at; ATTR_SKIP_HIDDEN (flags): hidden splats are never hit
 ATTR_ALPHA, ATTR_SCALE_MAX, ATTR_SCALE_MIN, ATTR_ANISOTROPY, ATTR_COLOUR, ATTR_VOLUME = 1, 2, 4, 8, 16, 32
 ATTR_SKIP_HIDDEN = 1
+# GSR_MEASURE_* (gsr_measure_request.what / .flags) and GSR_HIST_* (gsr_hist_spec.channel / .flags): what gsr_measure computes
+MEASURE_BOUNDS, MEASURE_EXTENT, MEASURE_MOMENTS = 1, 2, 4
+MEASURE_SKIP_HIDDEN = 1
+HIST_X, HIST_Y, HIST_Z, HIST_ALPHA, HIST_SCALE_MAX, HIST_SCALE_MIN, HIST_CD_R, HIST_CD_G, HIST_CD_B = range(9)
+HIST_LOG2 = 1
+HIST_MAX_BINS = 256    # GSR_HIST_MAX_BINS
+MEASURE_MAX_HIST = 4   # GSR_MEASURE_MAX_HIST
 MARK_DOT, MARK_OUTLINE = 1, 2                  # GSR_MARK_*: gsr_mark_style.shape
 MARK_COLOUR_FIXED, MARK_COLOUR_CD = 0, 1       # ... .colour_mode
 MARK_ANY_OPACITY = 1                           # ... .flags: also splats below 1/255 and the ones a visibility hides
@@ -252,6 +292,7 @@ C_ABI_SYMBOLS = [
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_select_attrs", "gsr_select_attrs_eval", "gsr_get_select_attrs", "gsr_multi_select_attrs",
     "gsr_render_marks", "gsr_get_marks",
+    "gsr_measure", "gsr_measure_eval", "gsr_hist_prepare", "gsr_get_measure", "gsr_multi_measure",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
     "gsr_grade_prepare", "gsr_grade_eval", "gsr_grade", "gsr_get_grade", "gsr_multi_grade",
     "gsr_debug_live_handles", "gsr_debug_sort_frame", "gsr_debug_last_plan", "gsr_debug_stage_bytes",
@@ -386,7 +427,12 @@ def load_library() -> C.CDLL:
     L.gsr_select_attrs_eval.argtypes = [C.POINTER(gsr_attr_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp]
     L.gsr_get_select_attrs.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_select_attrs.argtypes = [vp, C.POINTER(gsr_attr_rule), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    L.gsr_xform_prepare.argtypes = [C.POINTER(gsr_xform), C.POINTER(gsr_xform_rule)]
+    L.gsr_measure.argtypes = [vp, vp, i32, C.POINTER(gsr_measure_request), C.POINTER(gsr_measure_result), vp]
+    L.gsr_measure_eval.argtypes = [C.POINTER(gsr_measure_request), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp, C.POINTER(gsr_measure_result), vp]
+    L.gsr_hist_prepare.argtypes = [i32, i32, C.c_double, C.c_double, i32, C.POINTER(gsr_hist_spec)]
+    L.gsr_get_measure.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_measure.argtypes = [vp, vp, C.POINTER(gsr_measure_request), C.POINTER(gsr_measure_result), vp]
+    L.gsr_xform_prepare.argtypes =[C.POINTER(gsr_xform), C.POINTER(gsr_xform_rule)]
     L.gsr_transform_eval.argtypes = [C.POINTER(gsr_xform), i64] + [vp] * 7
     L.gsr_transform.argtypes = [vp, vp, i32, C.POINTER(gsr_xform), C.POINTER(C.c_int64)]
     L.gsr_get_transform.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
@@ -923,6 +969,67 @@ def select_attrs_eval(rule, P=None, alpha=None, scale=None, Cd=None, vis=None) -
     _check(load_library().gsr_select_attrs_eval(C.byref(rule), C.byref(vis) if vis is not None else None, n,
                                                 *[a.ctypes.data if a is not None and n else None for a in arrs], hit.ctypes.data))
     return hit[:n].astype(bool)
+
+
+def hist_spec(channel: int, lo: float, hi: float, bins: int, log2: bool = False) -> gsr_hist_spec:
+    """gsr_hist_prepare (host only, no GPU): the histogram of `channel` (HIST_*) over [lo, hi) in `bins` bins; log2: of the
+    piecewise-linear log2 of the value (lo and hi are then exponents).  Raises GsrError on what the library refuses"""
+    s = gsr_hist_spec()
+    _check(load_library().gsr_hist_prepare(int(channel), HIST_LOG2 if log2 else 0, float(lo), float(hi), int(bins), C.byref(s)))
+    return s
+
+
+def measure_request(bounds: bool = False, extent=None, moments: bool = False, ref=(0.0, 0.0, 0.0), hists=(), skip_hidden: bool = False) -> gsr_measure_request:
+    """gsr_measure_request: bounds -> lo / hi; extent = k -> lo_e / hi_e (P -+ k smax) and n_extent; moments -> the nine sums about
+    ref (float32, upload space); hists = up to four gsr_hist_spec (hist_spec); skip_hidden: a splat the visibility in force hides is
+    not selected.  What the fields may hold is the library's to refuse."""
+    r = gsr_measure_request()
+    r.what = (MEASURE_BOUNDS if bounds else 0) | (MEASURE_EXTENT if extent is not None else 0) | (MEASURE_MOMENTS if moments else 0)
+    r.flags = MEASURE_SKIP_HIDDEN if skip_hidden else 0
+    r.ref[:] = [float(x) for x in np.asarray(ref, np.float32).reshape(3)]
+    r.extent_k = float(extent) if extent is not None else 0.0
+    hists = list(hists)
+    r.n_hist = len(hists)
+    for k, s in enumerate(hists[:MEASURE_MAX_HIST]):
+        r.hist[k] = s
+    return r
+
+
+def _measure_hist_words(request) -> int:
+    """the uint32 words the request's histograms take (bins + 3 per spec); the library refuses an n_hist out of range"""
+    return sum(max(int(request.hist[k].bins), 0) + 3 for k in range(min(max(int(request.n_hist), 0), MEASURE_MAX_HIST)))
+
+
+def _measure_result(request, res, words):
+    """the result as the Python door returns it: the struct with .ref and .hist (one array per spec) set"""
+    res.ref = np.array(list(request.ref), np.float32)
+    out, at = [], 0
+    for k in range(min(max(int(request.n_hist), 0), MEASURE_MAX_HIST)):
+        size = max(int(request.hist[k].bins), 0) + 3
+        out.append(words[at:at + size].copy())
+        at += size
+    res.hist = out
+    return res
+
+
+def measure_eval(request, P=None, alpha=None, scale=None, Cd=None, mask=None, vis=None, n=None) -> gsr_measure_result:
+    """gsr_measure_eval (host only, no GPU): what gsr_measure computes, through the functions the kernels evaluate.  Arrays in read()'s
+    layout: P float32 (n, 3), alpha float32 (n,) TRUE alphas, scale and Cd uint16 halves (n, 3); an array the request does not look at
+    may be None (at least one array, or n, says how many splats).  mask: a boolean array over the splats or packed uint32 words
+    (None: every splat); vis: the gsr_visibility (visibility_struct) that skip_hidden hides by, or None -> the result"""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=t).reshape(-1, w) for a, t, w in
+            ((P, np.float32, 3), (alpha, np.float32, 1), (scale, np.uint16, 3), (Cd, np.uint16, 3))]
+    sizes = {a.shape[0] for a in arrs if a is not None} | ({int(n)} if n is not None else set())
+    if len(sizes) != 1:
+        raise GsrError(-1, f"measure_eval: the arrays hold {sorted(sizes)} rows")
+    n = sizes.pop()
+    words = removal_words(mask, n)
+    res = gsr_measure_result()
+    hist = np.zeros(max(_measure_hist_words(request), 1), np.uint32)
+    _check(load_library().gsr_measure_eval(C.byref(request), C.byref(vis) if vis is not None else None, n, _ptr(words),
+                                           *[a.ctypes.data if a is not None and n else None for a in arrs], C.byref(res),
+                                           hist.ctypes.data if request.n_hist > 0 else None))
+    return _measure_result(request, res, hist)
 
 
 def unpack_mask(words, n: int) -> np.ndarray:
@@ -1619,6 +1726,32 @@ class Engine:
         """gsr_get_select_attrs -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
         return self._tally(self.L.gsr_get_select_attrs, "selects", "hit_last")
 
+    # ---- measuring a selection (include/gsplat_hip.h, "measuring a selection")
+    def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
+        """gsr_measure from a HOST mask (a boolean array over the resident splats or packed uint32 words; None: every splat): counts,
+        bounds, extent, moments and histograms of the selected splats as `request` (measure_request) asks -> the result, with
+        .centroid(), .covariance() and .hist.  Changes and invalidates nothing."""
+        n = self.read_info()["n_splats"]
+        words = removal_words(mask, n)
+        return self._measure(request, _ptr(words), 0)
+
+    def measure_device(self, request: gsr_measure_request, mask_ptr) -> gsr_measure_result:
+        """gsr_measure from packed uint32 mask words in DEVICE (or pinned) memory (a raw pointer or an object with data_ptr(); ceil(n /
+        32) words, as select_device writes them; never written).  Waits for the work queued on the stream given to set_stream first;
+        synchronous -> the result.  Only the result crosses the link."""
+        return self._measure(request, C.c_void_p(_device_mask_ptr(mask_ptr, "measure_device")), 1)
+
+    def _measure(self, request, mask_arg, is_device):
+        res = gsr_measure_result()
+        hist = np.zeros(max(_measure_hist_words(request), 1), np.uint32)
+        _check(self.L.gsr_measure(self.h, mask_arg, is_device, C.byref(request), C.byref(res), hist.ctypes.data if request.n_hist > 0 else None))
+        return _measure_result(request, res, hist)
+
+    def get_measure(self) -> dict:
+        """gsr_get_measure -> {measures: calls that measured, measured_last, ms: the last call's clock [k_measure, the launches that
+        finish the sums, copies, wall]}"""
+        return self._tally(self.L.gsr_get_measure, "measures", "measured_last")
+
     # ---- selection overlay (include/gsplat_hip.h, "selection overlay")
     def render_marks(self, cam, mask, style, under: np.ndarray):
         """gsr_render_marks over a HOST frame: the splats `mask` selects (a boolean array over the resident splats or packed uint32
@@ -2295,6 +2428,16 @@ class MultiEngine:
         hit, nset = C.c_int64(0), C.c_int64(0)
         _check(self.L.gsr_multi_select_attrs(self.h, C.byref(rule), words.ctypes.data, C.byref(hit), C.byref(nset)))
         return unpack_mask(words, n), hit.value, nset.value
+
+    def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
+        """gsr_multi_measure: Engine.measure on rank 0's copy (the cloud is replicated), from a host mask (None: every splat)"""
+        cnt = C.c_int64(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(cnt), None, None))
+        words = removal_words(mask, cnt.value)
+        res = gsr_measure_result()
+        hist = np.zeros(max(_measure_hist_words(request), 1), np.uint32)
+        _check(self.L.gsr_multi_measure(self.h, _ptr(words), C.byref(request), C.byref(res), hist.ctypes.data if request.n_hist > 0 else None))
+        return _measure_result(request, res, hist)
 
     def render(self, cam, depth=None) -> np.ndarray:
         out = np.empty((cam.height, cam.width, 4), dtype=target_dtype(self.target_format))

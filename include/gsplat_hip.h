@@ -701,6 +701,103 @@ int  gsr_select_attrs_eval(const gsr_attr_rule* rule, const gsr_visibility* vis 
                            const float* alpha, const uint16_t* scale, const uint16_t* Cd, uint8_t* hit_out);   /* host, no context, no GPU */
 int  gsr_get_select_attrs(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- measuring a selection (counts, bounds, moments and histograms of resident splats, on the GPU) ----------------------------------- */
+/* What a mask of gsr_select SAYS besides its bit count: where the selected splats are (a transform gizmo's pivot, "home on selection", a
+ * crop box around them), how they lie (nine second moments for a PCA on the host), and how their opacity, size, position and base
+ * colour are distributed (the histograms beside gsr_select_attrs' range sliders; a prune threshold) -- without reading P, alpha, scale
+ * and Cd back over the link.  One streaming kernel (k_measure.h) in gsr_select's shape, and at most three small launches that finish
+ * the sums; a few hundred bytes come back.
+ * THE RULE (one set of functions, evaluated by the kernels and by gsr_measure_eval; x86 and gfx950 agree bit for bit).  A splat is
+ * SELECTED iff its mask bit is set (a NULL mask: every splat) and, with GSR_MEASURE_SKIP_HIDDEN, the visibility in force does not hide
+ * it (gsr_splat_visible on the raw P; no visibility: nothing is hidden).  Everything is computed from what gsr_read returns: the raw P
+ * bits, the TRUE alpha, the resident scale and Cd halves.
+ *   n_selected  the selected splats.
+ *   n_measured  with any bit of `what` set: the selected splats whose three P components are finite (else 0).
+ *   n_extent    with GSR_MEASURE_EXTENT: the measured splats whose three scale halves are finite too (else 0).
+ *   GSR_MEASURE_BOUNDS   lo[3], hi[3]: the minimum and maximum of P over the measured splats in the TOTAL ORDER OF THE FLOATS' BITS
+ *                        (-0 < +0), so the result never depends on which of two equal-comparing values was met first; none measured
+ *                        (or the bit not set): +inf / -inf.
+ *   GSR_MEASURE_EXTENT   lo_e[3], hi_e[3]: the same over fmaf(-extent_k, smax, p) and fmaf(extent_k, smax, p) of the n_extent splats,
+ *                        smax = the largest |half| of the three scale halves as gsr_select_attrs forms it.
+ *   GSR_MEASURE_MOMENTS  sum[9]: per measured splat d = p - ref (one float32 subtraction per axis), and the binary64 terms d_x, d_y,
+ *                        d_z, d_x d_x, d_x d_y, d_x d_z, d_y d_y, d_y d_z, d_z d_z (each product of two doubles: exact).  Each sum IS
+ *                        THE VALUE OF THE PERFECT BINARY TREE OVER UPLOAD INDICES: leaf i holds splat i's term, +0.0 if i is not measured
+ *                        or not below n; every inner node is left + right in binary64; the tree spans the smallest 2^k >= max(n, 64)
+ *                        leaves.  No floating-point atomic and no re-associated add is involved anywhere, so the nine doubles do not
+ *                        depend on the launch shape or on the order the waves run in.  (A sum that overflows to a NaN is a NaN; its
+ *                        sign and payload are not specified.)  The bit not set: nine +0.0.
+ * HISTOGRAMS: n_hist (0..4) specs; gsr_hist_prepare fills one from doubles: lo and hi rounded to float32, inv_w = (float)(bins /
+ * ((double)hi - (double)lo)).  It refuses (GSR_E_INVALID) an unknown channel or flag, bins outside 1..256, non-finite bounds, hi <= lo
+ * (as float32), and a range so narrow that inv_w is not finite; gsr_measure refuses a spec that gsr_hist_prepare could not have made
+ * in the same way (it does not recompute inv_w).  The DOMAIN is the selected splats, not only the measured ones.  The channel's value
+ * x: X / Y / Z the raw P, ALPHA the true alpha, SCALE_MAX / SCALE_MIN the largest / smallest |half| (a NaN half: NaN), CD_R / G / B
+ * h2f of the Cd halves.  With GSR_HIST_LOG2 a NaN x counts as nan, x <= 0 as under, +inf as over, and a finite x > 0 is first replaced by
+ * (float)(int32_t)(bits(x) - 0x3f800000) * 0x1p-23f -- piecewise-linear in log2, integer and conversion arithmetic only.  Then: NaN ->
+ * nan; !(x >= lo) -> under; !(x < hi) -> over; else bin min((int)((x - lo) * inv_w), bins - 1): one float32 subtraction, one float32
+ * multiply, a truncation.  hist_out: bins + 3 uint32 per spec -- the bins, then under, over, nan -- the specs back to back.
+ * THE MASK is gsr_transform's: ceil(n / 32) words in upload order, host (mask_is_device = 0) or device / pinned memory (1: checked with
+ * its exact size before anything is launched), bits at and behind n ignored, never written; NULL: every resident splat.
+ * gsr_measure_eval: the rule on the host, no context and no GPU.  Arrays in gsr_read's layout (P float[3n], alpha float[n] TRUE alphas,
+ * scale half[3n], Cd half[3n]); an array the request does not look at may be NULL.  mask: host words or NULL; vis (NULL: none in
+ * force) is what SKIP_HIDDEN hides by, as gsr_visibility_eval takes it (a mask must cover the n splats).
+ * A MEASURE CHANGES AND INVALIDATES NOTHING -- gsr_select's contract: no resident bit, depth horizon, cached depth order, policy or
+ * visibility state changes, no entry of gsr_stats; it does not wait for the frames in flight.  ORDERING: gsr_select's (with a device
+ * mask the call first waits for the work queued on the public stream); synchronous.  The results always come back to host memory.
+ * GSR_E_INVALID, nothing written: NULL ctx, request or result; hist_out NULL with n_hist > 0, or not NULL with n_hist == 0; no geometry
+ * ever uploaded, or an upload in progress; unknown bits in what or flags; reserved_ != 0; a non-finite ref or extent_k; n_hist outside
+ * 0..4; a bad spec; a device mask that fails the pointer check.  The empty cloud gives GSR_OK with no launch and the EMPTY RESULT:
+ * counts 0, lo = +inf, hi = -inf (also of the extent), nine +0.0, every histogram word 0.
+ * gsr_get_measure: the calls that measured, n_measured of the last one, and its clock ms[4]:
+ * [0] k_measure (HIP events)   [1] the launches that finish the sums (HIP events)   [2] the copies, wall clock   [3] wall clock of the call.
+ * gsr_multi_measure (below, with the other gsr_multi verbs): rank 0's context and a host mask -- the cloud is replicated.
+ * Out of scope: the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for the multi verb; weighted moments and colour
+ * statistics beyond histograms; an asynchronous form, and results left in device memory. */
+#define GSR_MEASURE_BOUNDS   1   /* what: lo, hi */
+#define GSR_MEASURE_EXTENT   2   /* what: lo_e, hi_e, n_extent */
+#define GSR_MEASURE_MOMENTS  4   /* what: sum[9] */
+#define GSR_MEASURE_SKIP_HIDDEN 1 /* flags: a splat the visibility in force hides is not selected */
+#define GSR_HIST_X           0   /* gsr_hist_spec.channel */
+#define GSR_HIST_Y           1
+#define GSR_HIST_Z           2
+#define GSR_HIST_ALPHA       3
+#define GSR_HIST_SCALE_MAX   4
+#define GSR_HIST_SCALE_MIN   5
+#define GSR_HIST_CD_R        6
+#define GSR_HIST_CD_G        7
+#define GSR_HIST_CD_B        8
+#define GSR_HIST_LOG2        1   /* gsr_hist_spec.flags: bin the piecewise-linear log2 of x */
+#define GSR_HIST_MAX_BINS  256
+#define GSR_MEASURE_MAX_HIST 4
+typedef struct gsr_hist_spec {
+    int32_t channel;                      /* GSR_HIST_X .. GSR_HIST_CD_B */
+    int32_t flags;                        /* GSR_HIST_LOG2 or 0 */
+    int32_t bins;                         /* 1..GSR_HIST_MAX_BINS */
+    float   lo, hi;                       /* [lo, hi), finite, lo < hi */
+    float   inv_w;                        /* (float)(bins / (hi - lo)) */
+} gsr_hist_spec;
+typedef struct gsr_measure_request {
+    int32_t what;                         /* GSR_MEASURE_BOUNDS | _EXTENT | _MOMENTS (0: the count and the histograms alone) */
+    int32_t flags;                        /* GSR_MEASURE_SKIP_HIDDEN or 0 */
+    float   ref[3];                       /* the point the moments are taken about, upload space */
+    float   extent_k;                     /* the extent reaches extent_k * smax to either side */
+    int32_t n_hist;                       /* 0..GSR_MEASURE_MAX_HIST */
+    gsr_hist_spec hist[GSR_MEASURE_MAX_HIST];
+    int32_t reserved_;                    /* 0 */
+} gsr_measure_request;
+typedef struct gsr_measure_result {
+    int64_t n_selected, n_measured, n_extent;
+    float   lo[3], hi[3];                 /* GSR_MEASURE_BOUNDS */
+    float   lo_e[3], hi_e[3];             /* GSR_MEASURE_EXTENT */
+    double  sum[9];                       /* GSR_MEASURE_MOMENTS: d_x, d_y, d_z, xx, xy, xz, yy, yz, zz */
+} gsr_measure_result;
+int  gsr_measure(gsr_context* ctx, const uint32_t* mask, int mask_is_device, const gsr_measure_request* request, gsr_measure_result* out,
+                 uint32_t* hist_out /* host; NULL iff request->n_hist == 0 */);
+int  gsr_measure_eval(const gsr_measure_request* request, const gsr_visibility* vis /* NULL: none */, int64_t n, const uint32_t* mask /* NULL: all */,
+                      const float* P, const float* alpha, const uint16_t* scale, const uint16_t* Cd, gsr_measure_result* out,
+                      uint32_t* hist_out);   /* host, no context, no GPU */
+int  gsr_hist_prepare(int channel, int flags, double lo, double hi, int bins, gsr_hist_spec* out);   /* host */
+int  gsr_get_measure(gsr_context* ctx, int64_t* calls, int64_t* measured_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- transform: selected resident splats rotated, scaled, translated on the GPU ---- */
 /* What a mask of gsr_select is for besides hiding and removing: the selected splats are moved, turned and resized where they are
  * resident -- p' = s R (p - pivot) + pivot + translate -- with their scale, orient and SH coefficients following, and nothing but
@@ -944,6 +1041,8 @@ int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_regi
                       int64_t* n_hit, int64_t* n_set);
 /* gsr_select_attrs on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
 int  gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set);
+/* gsr_measure on rank 0's copy (the cloud is replicated) from a HOST mask (NULL: every splat), after the same synchronisation; no rank's state changes */
+int  gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out);
 /* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
  * rule: if the ranks do not agree on the count, or a rank fails after its first write, the verb fails and NO rank keeps geometry. */
 int  gsr_multi_transform(gsr_multi* m, const uint32_t* mask_host, const gsr_xform* x, int64_t* n_moved);
