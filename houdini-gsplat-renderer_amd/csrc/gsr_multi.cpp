@@ -714,6 +714,14 @@ extern "C" int gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, u
     return rc ? rc : gsr_select_attrs(m->ctx[0], rule, mask_host, 0, n_hit, n_set);
 }
 
+// ... and selected by density on rank 0's replica (gsr_select_density into a host mask and host counts: the caller's thread)
+extern "C" int gsr_multi_select_density(gsr_multi* m, const gsr_density_rule* rule, uint32_t* mask_host, uint32_t* counts_host,
+                                        gsr_density_result* result, int64_t* n_hit, int64_t* n_set)
+{
+    const int rc = multi_enter(m, rule && mask_host, "gsr_multi_select_density");
+    return rc ? rc : gsr_select_density(m->ctx[0], rule, mask_host, 0, counts_host, 0, result, n_hit, n_set);
+}
+
 // ... and measured on rank 0's replica (gsr_measure from a host mask: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out)
 {

@@ -2,7 +2,9 @@
 // gsr_get_select; and by attribute: gsr_select_attrs, gsr_select_attrs_eval, gsr_get_select_attrs.  Host code only;
 // included once, behind gsr_resident_read.h, whose contract it keeps and whose refusals (refuse_edit), pointer check
 // (check_device_source), mask intake (MaskArg) and visibility rule (visibility_error, visibility_rule) it shares.  The rules and the
-// kernels are k_select.h's and k_select_attrs.h's.
+// kernels are k_select.h's and k_select_attrs.h's.  At the end, by density (k_density.h): gsr_select_density,
+// gsr_select_density_eval, gsr_get_select_density -- the same mask contract, but it borrows the scratch of an upload's sort and
+// therefore DOES wait for the frames in flight; what it says there holds for it alone.
 //
 // A select writes NOTHING the context keeps: no resident bit, no horizon, no cached order, no policy, no visibility state, no entry of
 // gsr_stats.  It therefore does not wait for the frames in flight, and the next frame runs the launches it would have run.  What it
@@ -308,5 +310,222 @@ extern "C" int gsr_select_attrs(gsr_context* c, const gsr_attr_rule* r, uint32_t
     c->sela.ms[3] = up_now_ms() - t_begin;
     c->sela.calls += 1;
     c->sela.last = (int64_t)hits;
+    return GSR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Selection by density (k_density.h).  gsr_select's mask contract and epilogue; the rule counts the population of the
+// cells around a splat.  Unlike its two siblings the verb borrows the scratch of an upload's sort (c->up_sort, slot 0's histogram and
+// digit totals: nothing live between uploads and edits -- morton_order copies the permutation out), so it waits for the frames in
+// flight first, as gsr_move does, and queues everything on the stream that sort runs on.
+static_assert(GSR_DENSITY_SKIP_HIDDEN == GSR_DENF_SKIP_HIDDEN && GSR_DENSITY_HIT_OUTSIDE == GSR_DENF_HIT_OUTSIDE && GSR_DENSITY_CELLS == GSR_DEN_CELLS &&
+              GSR_DENSITY_HIST_BINS == GSR_DEN_BINS, "the header's flags and limits are the kernels'");
+static_assert(sizeof(gsr_density_rule) == 44 && offsetof(gsr_density_rule, reach) == 16 && offsetof(gsr_density_rule, count_lo) == 32 &&
+              offsetof(gsr_density_rule, alpha_min) == 40 && sizeof(gsr_density_result) == 8 * (3 + GSR_DENSITY_HIST_BINS), "the rule is 11 dwords, the result 67 counts");
+
+// what is wrong with the caller's rule (NULL: nothing)
+static const char* density_rule_error(const gsr_density_rule* r)
+{
+    if (!std::isfinite(r->cell) || !(r->cell > 0.0f)) return "cell is not a finite positive number";
+    if (!std::isfinite(1.0f / r->cell)) return "1 / cell is not finite";
+    if (!std::isfinite(r->origin[0]) || !std::isfinite(r->origin[1]) || !std::isfinite(r->origin[2])) return "origin is not finite";
+    if (r->reach < 0 || r->reach > GSR_DENSITY_MAX_REACH) return "reach is not within 0..GSR_DENSITY_MAX_REACH";
+    if (r->flags & ~(GSR_DENSITY_SKIP_HIDDEN | GSR_DENSITY_HIT_OUTSIDE)) return "unknown flag bits";
+    if (r->op < GSR_SELECT_REPLACE || r->op > GSR_SELECT_TOGGLE) return "unknown op";
+    if (r->reserved_ != 0) return "reserved_ is not 0";
+    if (r->alpha_min != r->alpha_min) return "alpha_min is a NaN";
+    return nullptr;
+}
+// the rule as the kernels take it: inv_cell by ONE IEEE float32 division, here and nowhere else
+static GsrDensityRule density_rule(const gsr_density_rule* r)
+{
+    GsrDensityRule d{};
+    d.inv_cell = 1.0f / r->cell;
+    for (int k = 0; k < 3; ++k) d.origin[k] = r->origin[k];
+    d.reach = r->reach; d.flags = r->flags; d.op = r->op;
+    d.count_lo = r->count_lo; d.count_hi = r->count_hi;
+    d.alpha_min = r->alpha_min;
+    return d;
+}
+
+// The rule on the host.  The classes come from gsr_density_class; the counts from a table of the OCCUPIED cells (the sorted unique keys
+// and the running population in front of each): N is formed once per cell, as the difference of two running populations per row of
+// gsr_density_row, and handed to every splat of the cell.
+extern "C" int gsr_select_density_eval(const gsr_density_rule* r, const gsr_visibility* vis, int64_t n, const float* P, const float* alpha,
+                                       uint8_t* hit_out, uint32_t* counts_out, gsr_density_result* result)
+{
+    if (!r) return set_err(GSR_E_INVALID, "gsr_select_density_eval: rule is NULL");
+    const char* bad = density_rule_error(r);
+    if (!bad) bad = visibility_error(vis);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_select_density_eval: %s", bad);
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && (!P || !hit_out))) return set_err(GSR_E_INVALID, "gsr_select_density_eval: bad argument");
+    const gsr_visibility* const hide = (r->flags & GSR_DENSITY_SKIP_HIDDEN) ? vis : nullptr;   // (no visibility: nothing is hidden)
+    const uint32_t* const vmask = hide ? hide->mask : nullptr;
+    if (vmask && hide->mask_splats < n)
+        return set_err(GSR_E_INVALID, "gsr_select_density_eval: the visibility's mask covers %lld of the %lld splats", (long long)hide->mask_splats, (long long)n);
+    const GsrDensityRule rule = density_rule(r);
+    const GsrVisRule vr = visibility_rule(hide);
+    gsr_density_result res;
+    std::memset(&res, 0, sizeof res);
+    std::vector<uint32_t> cls((size_t)n), cells;
+    for (int64_t k = 0; k < n; ++k) {
+        const float px = P[3 * k], py = P[3 * k + 1], pz = P[3 * k + 2];
+        const bool hidden = hide && !gsr_splat_visible(vr, px, py, pz, vmask ? vmask[k >> 5] : 0u, (uint32_t)(k & 31));
+        const uint32_t c = gsr_density_class(rule, px, py, pz, alpha ? alpha[k] : 1.0f, hidden);
+        cls[(size_t)k] = c;
+        if (c < GSR_DEN_NOKEY) cells.push_back(c);
+        else if (c == GSR_DEN_OUTSIDE) res.n_outside += 1;
+    }
+    res.n_population = (int64_t)cells.size();
+    // the occupied cells: ukey[u] rising, before[u] = the population of the cells in front of u (before[U] = all of it)
+    std::sort(cells.begin(), cells.end());
+    std::vector<uint32_t> ukey, before;
+    for (size_t k = 0; k < cells.size(); ++k)
+        if (k == 0 || cells[k] != cells[k - 1]) { ukey.push_back(cells[k]); before.push_back((uint32_t)k); }
+    before.push_back((uint32_t)cells.size());
+    res.n_cells = (int64_t)ukey.size();
+    std::vector<uint32_t> cell_n(ukey.size(), 0u);
+    for (size_t u = 0; u < ukey.size(); ++u) {
+        uint32_t N = 0u;
+        for (int dz = -rule.reach; dz <= rule.reach; ++dz)
+            for (int dy = -rule.reach; dy <= rule.reach; ++dy) {
+                uint32_t klo = 0u, khi = 0u;
+                if (!gsr_density_row(ukey[u], rule.reach, dy, dz, &klo, &khi)) continue;
+                const size_t a = (size_t)(std::lower_bound(ukey.begin(), ukey.end(), klo) - ukey.begin());
+                const size_t b = (size_t)(std::upper_bound(ukey.begin(), ukey.end(), khi) - ukey.begin());
+                N += before[b] - before[a];
+            }
+        cell_n[u] = N;
+        res.count_hist[gsr_density_bin(N)] += (int64_t)(before[u + 1] - before[u]);
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t c = cls[(size_t)k];
+        const uint32_t N = c < GSR_DEN_NOKEY ? cell_n[(size_t)(std::lower_bound(ukey.begin(), ukey.end(), c) - ukey.begin())] : 0u;
+        hit_out[k] = gsr_density_hit(rule, c == GSR_DEN_OUTSIDE ? GSR_DEN_CNT_OUTSIDE : N) ? 1 : 0;
+        if (counts_out) counts_out[k] = N;
+    }
+    if (result) *result = res;
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_select_density(gsr_context* c, int64_t* calls, int64_t* hit_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_select_density: ctx is NULL");
+    return c->seld.report(calls, hit_last, ms);
+}
+
+extern "C" int gsr_select_density(gsr_context* c, const gsr_density_rule* r, uint32_t* mask, int mask_is_device, uint32_t* counts_out,
+                                  int counts_is_device, gsr_density_result* result, int64_t* n_hit, int64_t* n_set)
+{
+    const char* const who = "gsr_select_density";
+    if (!c || !r || !mask) return set_err(GSR_E_INVALID, "gsr_select_density: NULL argument");
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const char* bad = density_rule_error(r);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_select_density: %s", bad);
+    const uint32_t n = c->n;
+    if (n == 0) {                                      // the empty cloud: no word of the mask or the counts exists
+        if (n_hit) *n_hit = 0;
+        if (n_set) *n_set = 0;
+        if (result) std::memset(result, 0, sizeof *result);
+        return GSR_OK;
+    }
+    const double t_begin = up_now_ms();
+    HIP_TRY(hipSetDevice(c->device));
+    const MaskArg mk{mask, mask_is_device != 0, n};
+    if ((rc = mk.check(c, who))) return rc;            // before anything is launched: a wrong pointer must never be found out by a kernel
+    const bool counts_dev = counts_out && counts_is_device;
+    if (counts_dev && (rc = check_device_source(c, counts_out, (size_t)n * 4, who, "counts_out"))) return rc;
+    // the sort's scratch is shared with the frames' sorts and an upload's: nothing may be in flight (this also waits for whoever
+    // produced a device mask on the public stream)
+    if ((rc = sync_all(c))) return rc;
+    // ---- everything the call needs, before the launch: a host mask, host counts and the result block are placed in the arena
+    FrameSlot& sl = c->slot[0];
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
+    const size_t oMask = place(mk.stage_bytes()), oRes = place((size_t)GSR_DEN_R_WORDS * 4), oCounts = place(counts_out && !counts_dev ? (size_t)n * 4 : 0);
+    const size_t cwords = (size_t)GSR_SEL_COUNTER_SLOTS * GSR_SEL_COUNTER_STRIDE;
+    if ((rc = ensure_stage(c, off)) || (rc = ensure_inverse_perm(c)) || (rc = ensure_up_events(c, 4, who, true)) || (rc = ensure_sel_counters(c, who)))
+        return rc;
+    if (!c->den_h && c->den_h.alloc((size_t)GSR_DEN_R_WORDS, 0)) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "gsr_select_density: no pinned host memory for the result");
+    }
+    if (c->up_sort.hold(n)) return set_err(GSR_E_OOM, "gsr_select_density: no room for the sort of the cell keys");
+    if ((rc = ensure_counts(sl.hist, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+    if ((rc = c->den_cnt.ensure((size_t)n, (size_t)n + n / 8 + 1024))) return rc;
+    HIP_TRY(hipStreamSynchronize(sl.own));             // the inverse of the storage order is built there
+    hipStream_t us = sl.stream;                        // where radix_sort queues its passes
+    uint32_t* const dmask = mk.is_device ? mask : reinterpret_cast<uint32_t*>(c->stage + oMask);
+    uint32_t* const dres = reinterpret_cast<uint32_t*>(c->stage + oRes);
+    uint32_t* const dcounts = !counts_out ? nullptr : counts_dev ? counts_out : reinterpret_cast<uint32_t*>(c->stage + oCounts);
+    double copy_ms = 0.0;
+    if (!mk.is_device && r->op != GSR_SELECT_REPLACE) {               // every op but REPLACE reads the mask first
+        const uint32_t* staged = nullptr;
+        const hipError_t e = mk.to_device(c, us, oMask, &copy_ms, &staged);
+        if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_density: %s", hipGetErrorString(e));
+    }
+    const bool vis = c->vis_on, hide = vis && (r->flags & GSR_DENSITY_SKIP_HIDDEN);
+    const GsrDensityRule rule = density_rule(r);
+    const GsrVisRule vrule = hide ? c->vis : GsrVisRule{};
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    const float* const alpha0 = vis ? (const float*)c->alpha0 : nullptr;
+    const uint32_t* const vis_mask = hide ? (const uint32_t*)c->vis_mask : nullptr;
+    uint32_t *kA = c->up_sort.kA, *kB = c->up_sort.kB, *vA = c->up_sort.vA, *vB = c->up_sort.vB;
+    const uint32_t nchunks = div_up(n, GSR_DENSITY_THREADS);
+    const dim3 grid(nchunks), capped(std::min(nchunks, (uint32_t)GSR_DENSITY_BLOCKS)), block(GSR_DENSITY_THREADS);
+    hipError_t e = hipMemsetAsync(c->sel_counters, 0, cwords * 8, us);
+    if (e == hipSuccess) e = hipMemsetAsync(dres, 0, (size_t)GSR_DEN_R_WORDS * 4, us);
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[0], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_density_keys, capped, block, 0, us, n, nchunks, inv, c->geoA, alpha0, vis_mask, hide ? 1 : 0, rule, vrule, kA, vA, c->den_cnt.get(), dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[1], us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_density: %s", hipGetErrorString(e));
+    // the 31-bit keys with their upload indices, in the instantiation morton_order launches (four 8-bit passes): the sentinels sort last
+    if ((rc = radix_sort(sl, kA, vA, kB, vB, n, 31, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0))) return rc;   // (leaves the result in what kA / vA name now)
+    e = hipEventRecord(c->up_ev[2], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_density_count, capped, block, 0, us, n, nchunks, (int)r->reach, kA, vA, c->den_cnt.get(), dres);
+        hipLaunchKernelGGL(k_density_hit, grid, block, 0, us, n, rule, c->den_cnt.get(), dcounts, dmask, c->sel_counters);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(c->up_ev[3], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    const double t1 = up_now_ms();
+    if (e == hipSuccess) e = hipMemcpyAsync(c->sel_h_counters, c->sel_counters, cwords * 8, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->den_h, dres, (size_t)GSR_DEN_R_WORDS * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_density: %s", hipGetErrorString(e));
+    // the counts the kernels left must add up before a word of the caller's is written
+    const uint32_t* const h = c->den_h;
+    gsr_density_result res;
+    std::memset(&res, 0, sizeof res);
+    res.n_population = (int64_t)h[GSR_DEN_R_POP];
+    res.n_outside = (int64_t)h[GSR_DEN_R_OUTSIDE];
+    res.n_cells = (int64_t)h[GSR_DEN_R_CELLS];
+    int64_t binned = 0;
+    for (int b = 0; b < GSR_DEN_BINS; ++b) binned += (res.count_hist[b] = (int64_t)h[GSR_DEN_R_HIST + b]);
+    if (res.n_population + res.n_outside > (int64_t)n || res.n_cells > res.n_population || binned != res.n_population)
+        return set_err(GSR_E_HIP, "gsr_select_density: the kernels counted %lld population, %lld outside, %lld cells, %lld binned among %u splats",
+                       (long long)res.n_population, (long long)res.n_outside, (long long)res.n_cells, (long long)binned, n);
+    if (!mk.is_device) e = hipMemcpyAsync(mask, dmask, mk.words() * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess && counts_out && !counts_dev) e = hipMemcpyAsync(counts_out, dcounts, (size_t)n * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_density: %s", hipGetErrorString(e));
+    copy_ms += up_now_ms() - t1;
+    unsigned long long hits = 0, set = 0;
+    sum_sel_counters(c, &hits, &set);
+    if (n_hit) *n_hit = (int64_t)hits;
+    if (n_set) *n_set = (int64_t)set;
+    if (result) *result = res;
+    float ms = 0.0f, ms2 = 0.0f;
+    c->seld.ms[0] = hipEventElapsedTime(&ms, c->up_ev[0], c->up_ev[1]) == hipSuccess && hipEventElapsedTime(&ms2, c->up_ev[2], c->up_ev[3]) == hipSuccess ? (double)ms + (double)ms2 : 0.0;
+    c->seld.ms[1] = copy_ms;
+    c->seld.ms[2] = hipEventElapsedTime(&ms, c->up_ev[1], c->up_ev[2]) == hipSuccess ? (double)ms : 0.0;
+    c->seld.ms[3] = up_now_ms() - t_begin;
+    c->seld.calls += 1;
+    c->seld.last = (int64_t)hits;
     return GSR_OK;
 }

@@ -141,6 +141,25 @@ class gsr_attr_rule(C.Structure):
                 ("colour_lo", C.c_float * 3), ("colour_hi", C.c_float * 3), ("reserved_", C.c_int32), ("volume", gsr_crop_volume * 4)]
 
 
+class gsr_density_rule(C.Structure):
+    """include/gsplat_hip.h: the rule of gsr_select_density -- a grid of 1024^3 cells, a reach, a range of neighbour counts, an alpha floor"""
+    _fields_ = [("cell", C.c_float), ("origin", C.c_float * 3), ("reach", C.c_int32), ("flags", C.c_int32), ("op", C.c_int32),
+                ("reserved_", C.c_int32), ("count_lo", C.c_uint32), ("count_hi", C.c_uint32), ("alpha_min", C.c_float)]
+
+
+class gsr_density_result(C.Structure):
+    """include/gsplat_hip.h: what gsr_select_density reports beside the mask.  hist() -> count_hist as an int64 array"""
+    _fields_ = [("n_population", C.c_int64), ("n_outside", C.c_int64), ("n_cells", C.c_int64), ("count_hist", C.c_int64 * 64)]
+
+    def hist(self) -> np.ndarray:
+        """int64 (64,): bin b < 63 holds the population splats with N == b + 1, bin 63 those with N >= 64"""
+        return np.array(self.count_hist[:], np.int64)
+
+    def fields(self) -> tuple:
+        """(n_population, n_outside, n_cells, count_hist as a tuple): what two results are compared by"""
+        return (self.n_population, self.n_outside, self.n_cells, tuple(self.count_hist[:]))
+
+
 class gsr_hist_spec(C.Structure):
     """include/gsplat_hip.h: one histogram of gsr_measure -- a channel, [lo, hi) in `bins` bins, and what gsr_hist_prepare derives"""
     _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("bins", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("inv_w", C.c_float)]
@@ -239,6 +258,11 @@ SELECT_BLOCK = 256     # GSR_SELECT_BLOCK: upload indices one workgroup of the s
 # GSR_ATTR_* (gsr_attr_rule.clauses): what gsr_select_attrs looks at; ATTR_SKIP_HIDDEN (flags): hidden splats are never hit
 ATTR_ALPHA, ATTR_SCALE_MAX, ATTR_SCALE_MIN, ATTR_ANISOTROPY, ATTR_COLOUR, ATTR_VOLUME = 1, 2, 4, 8, 16, 32
 ATTR_SKIP_HIDDEN = 1
+# GSR_DENSITY_* (gsr_density_rule.flags, and the limits of the rule): what gsr_select_density counts and hits
+DENSITY_SKIP_HIDDEN, DENSITY_HIT_OUTSIDE = 1, 2
+DENSITY_CELLS = 1024       # GSR_DENSITY_CELLS: cells per axis
+DENSITY_MAX_REACH = 2      # GSR_DENSITY_MAX_REACH
+DENSITY_HIST_BINS = 64     # GSR_DENSITY_HIST_BINS
 # GSR_MEASURE_* (gsr_measure_request.what / .flags) and GSR_HIST_* (gsr_hist_spec.channel / .flags): what gsr_measure computes
 MEASURE_BOUNDS, MEASURE_EXTENT, MEASURE_MOMENTS = 1, 2, 4
 MEASURE_SKIP_HIDDEN = 1
@@ -291,6 +315,7 @@ C_ABI_SYMBOLS = [
     "gsr_debug_replica_verdict",
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_select_attrs", "gsr_select_attrs_eval", "gsr_get_select_attrs", "gsr_multi_select_attrs",
+    "gsr_select_density", "gsr_select_density_eval", "gsr_get_select_density", "gsr_multi_select_density",
     "gsr_render_marks", "gsr_get_marks",
     "gsr_measure", "gsr_measure_eval", "gsr_hist_prepare", "gsr_get_measure", "gsr_multi_measure",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
@@ -427,6 +452,10 @@ def load_library() -> C.CDLL:
     L.gsr_select_attrs_eval.argtypes = [C.POINTER(gsr_attr_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp]
     L.gsr_get_select_attrs.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_select_attrs.argtypes = [vp, C.POINTER(gsr_attr_rule), vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_density.argtypes = [vp, C.POINTER(gsr_density_rule), vp, i32, vp, i32, C.POINTER(gsr_density_result), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_density_eval.argtypes = [C.POINTER(gsr_density_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, C.POINTER(gsr_density_result)]
+    L.gsr_get_select_density.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_multi_select_density.argtypes = [vp, C.POINTER(gsr_density_rule), vp, vp, C.POINTER(gsr_density_result), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_measure.argtypes = [vp, vp, i32, C.POINTER(gsr_measure_request), C.POINTER(gsr_measure_result), vp]
     L.gsr_measure_eval.argtypes = [C.POINTER(gsr_measure_request), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp, C.POINTER(gsr_measure_result), vp]
     L.gsr_hist_prepare.argtypes = [i32, i32, C.c_double, C.c_double, i32, C.POINTER(gsr_hist_spec)]
@@ -969,6 +998,61 @@ def select_attrs_eval(rule, P=None, alpha=None, scale=None, Cd=None, vis=None) -
     _check(load_library().gsr_select_attrs_eval(C.byref(rule), C.byref(vis) if vis is not None else None, n,
                                                 *[a.ctypes.data if a is not None and n else None for a in arrs], hit.ctypes.data))
     return hit[:n].astype(bool)
+
+
+def density_rule(cell, origin, reach: int = 1, count=(1, 0xffffffff), alpha_min: float = float("-inf"), op: int = SELECT_REPLACE,
+                 skip_hidden: bool = False, hit_outside: bool = False) -> gsr_density_rule:
+    """gsr_density_rule: a grid of 1024^3 cells of edge `cell` whose low corner is `origin` (upload space; density_grid makes both
+    from a bounding box); reach = how many cells around a splat's own count as its neighbourhood (0..2); count = (lo, hi), hit iff
+    lo <= N <= hi ((1, k - 1): the floaters); alpha_min: only splats with a true alpha >= it are counted and hit; op = SELECT_*;
+    skip_hidden: a splat the visibility in force hides is not counted; hit_outside: what lies outside the grid is hit.  What the
+    fields may hold is the library's to refuse."""
+    r = gsr_density_rule()
+    r.cell = float(cell)
+    r.origin[:] = [float(x) for x in np.asarray(origin, np.float32).reshape(3)]
+    r.reach, r.op = int(reach), int(op)
+    r.flags = (DENSITY_SKIP_HIDDEN if skip_hidden else 0) | (DENSITY_HIT_OUTSIDE if hit_outside else 0)
+    r.count_lo, r.count_hi = int(count[0]), int(count[1])
+    r.alpha_min = float(alpha_min)
+    return r
+
+
+def density_grid(lo, hi, cell):
+    """(origin float32 (3,), cell float32) of a gsr_density_rule for the bounding box lo .. hi (measure()'s bounds, say): the origin
+    lies one cell below lo, so every splat of the box has all its neighbour cells inside the grid.  The box must fit 1022 cells per
+    axis at that cell: ValueError otherwise, naming the smallest cell that does.  Pure host arithmetic."""
+    lo64, hi64 = np.asarray(lo, np.float64).reshape(3), np.asarray(hi, np.float64).reshape(3)
+    c = np.float32(cell)
+    if not (np.isfinite(lo64).all() and np.isfinite(hi64).all() and (hi64 >= lo64).all()):
+        raise ValueError("density_grid: the box is not finite, or hi is below lo")
+    if not (np.isfinite(c) and c > 0):
+        raise ValueError(f"density_grid: cell {cell!r} is not a finite positive number")
+    extent = float((hi64 - lo64).max())
+    smallest = np.float32(extent / (DENSITY_CELLS - 2))
+    while float(smallest) * (DENSITY_CELLS - 2) <= extent:         # (strictly more than the extent: hi itself lies inside a cell)
+        smallest = np.nextafter(smallest, np.float32(np.inf))
+    if float(c) < float(smallest):
+        raise ValueError(f"density_grid: a box of extent {extent:g} does not fit {DENSITY_CELLS - 2} cells of {float(c):g}; "
+                         f"the smallest cell that fits is {float(smallest):.9g}")
+    return (lo64 - float(c)).astype(np.float32), c
+
+
+def select_density_eval(rule, P, alpha=None, vis=None, counts: bool = False, result: bool = False):
+    """gsr_select_density_eval (host only, no GPU): the rule of gsr_select_density through the functions the kernels evaluate.  P
+    float32 (n, 3) and alpha float32 (n,) TRUE alphas in read()'s layout (None: every alpha 1); vis: the gsr_visibility
+    (visibility_struct) that skip_hidden hides by, or None -> bool (n,) hit; with counts / result also the uint32 (n,) neighbour
+    counts / the gsr_density_result, in that order"""
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    n = P.shape[0]
+    a = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
+    if a is not None and a.shape[0] != n:
+        raise GsrError(-1, f"select_density_eval: the arrays hold {sorted({n, a.shape[0]})} rows")
+    hit, cnt, res = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), gsr_density_result()
+    _check(load_library().gsr_select_density_eval(C.byref(rule), C.byref(vis) if vis is not None else None, n, P.ctypes.data if n else None,
+                                                  a.ctypes.data if a is not None and n else None, hit.ctypes.data,
+                                                  cnt.ctypes.data if counts else None, C.byref(res) if result else None))
+    out = (hit[:n].astype(bool),) + ((cnt[:n],) if counts else ()) + ((res,) if result else ())
+    return out[0] if len(out) == 1 else out
 
 
 def hist_spec(channel: int, lo: float, hi: float, bins: int, log2: bool = False) -> gsr_hist_spec:
@@ -1726,6 +1810,36 @@ class Engine:
         """gsr_get_select_attrs -> {selects: calls that selected, hit_last, ms: the last call's clock [kernel, copies, 0, wall]}"""
         return self._tally(self.L.gsr_get_select_attrs, "selects", "hit_last")
 
+    # ---- selection by density (include/gsplat_hip.h, "selection by density")
+    def select_density(self, rule: gsr_density_rule, mask=None, counts: bool = False):
+        """gsr_select_density into a HOST mask: the resident splats whose neighbour count the rule (density_rule) hits -> (bool (n,)
+        mask in upload order, n_hit, n_set, the gsr_density_result[, the uint32 (n,) neighbour counts]).  mask = the prior selection the
+        rule's op combines with (a boolean array over the resident splats or packed uint32 words; None: nothing selected).  Waits for the
+        frames in flight; changes and invalidates nothing."""
+        n = self.read_info()["n_splats"]
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        cnt = np.zeros(max(n, 1), np.uint32)
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_density_result()
+        _check(self.L.gsr_select_density(self.h, C.byref(rule), words.ctypes.data, 0, cnt.ctypes.data if counts else None, 0, C.byref(res),
+                                         C.byref(hit), C.byref(nset)))
+        return (unpack_mask(words, n), hit.value, nset.value, res) + ((cnt[:n],) if counts else ())
+
+    def select_density_device(self, rule: gsr_density_rule, mask_ptr, counts_ptr=None):
+        """gsr_select_density into packed uint32 mask words in DEVICE memory (a raw pointer or an object with data_ptr(); ceil(n / 32)
+        words, read first by every op but SELECT_REPLACE) and, with counts_ptr, n uint32 neighbour counts in device memory.  Waits for
+        the frames in flight and the work queued on the stream given to set_stream first; synchronous -> (n_hit, n_set, the
+        gsr_density_result).  The mask goes straight into remove_device: the floaters go and nothing crosses the link."""
+        ptr = _device_mask_ptr(mask_ptr, "select_density_device")
+        cptr = None if counts_ptr is None else C.c_void_p(_device_mask_ptr(counts_ptr, "select_density_device"))
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_density_result()
+        _check(self.L.gsr_select_density(self.h, C.byref(rule), C.c_void_p(ptr), 1, cptr, 1, C.byref(res), C.byref(hit), C.byref(nset)))
+        return hit.value, nset.value, res
+
+    def get_select_density(self) -> dict:
+        """gsr_get_select_density -> {selects: calls that selected, hit_last, ms: the last call's clock [the verb's kernels, copies,
+        the sort, wall]}"""
+        return self._tally(self.L.gsr_get_select_density, "selects", "hit_last")
+
     # ---- measuring a selection (include/gsplat_hip.h, "measuring a selection")
     def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
         """gsr_measure from a HOST mask (a boolean array over the resident splats or packed uint32 words; None: every splat): counts,
@@ -2428,6 +2542,19 @@ class MultiEngine:
         hit, nset = C.c_int64(0), C.c_int64(0)
         _check(self.L.gsr_multi_select_attrs(self.h, C.byref(rule), words.ctypes.data, C.byref(hit), C.byref(nset)))
         return unpack_mask(words, n), hit.value, nset.value
+
+    def select_density(self, rule: gsr_density_rule, mask=None, counts: bool = False):
+        """gsr_multi_select_density: Engine.select_density on rank 0's copy (the cloud is replicated), into a host mask -> (bool mask,
+        n_hit, n_set, the gsr_density_result[, the neighbour counts])"""
+        c64 = C.c_int64(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(c64), None, None))
+        n = c64.value
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        cnt = np.zeros(max(n, 1), np.uint32)
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_density_result()
+        _check(self.L.gsr_multi_select_density(self.h, C.byref(rule), words.ctypes.data, cnt.ctypes.data if counts else None, C.byref(res),
+                                               C.byref(hit), C.byref(nset)))
+        return (unpack_mask(words, n), hit.value, nset.value, res) + ((cnt[:n],) if counts else ())
 
     def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
         """gsr_multi_measure: Engine.measure on rank 0's copy (the cloud is replicated), from a host mask (None: every splat)"""

@@ -701,6 +701,80 @@ int  gsr_select_attrs_eval(const gsr_attr_rule* rule, const gsr_visibility* vis 
                            const float* alpha, const uint16_t* scale, const uint16_t* Cd, uint8_t* hit_out);   /* host, no context, no GPU */
 int  gsr_get_select_attrs(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
 
+/* ---- selection by density (resident splats picked by how many neighbours they have, on the GPU) -------------------------------------- */
+/* The mask gsr_select makes, from how CROWDED a splat's surroundings are: the floaters of a capture (a splat, or a small clump, alone
+ * in space), a trainer's density prune -- without reading P back and counting neighbours on the host.  Three kernels (k_density.h)
+ * around the stable radix sort that orders an upload; gsr_select's mask epilogue.
+ * THE RULE (one set of functions, evaluated by the kernels and by gsr_select_density_eval; x86 and gfx950 agree bit for bit).  The
+ * caller gives a uniform grid of 1024^3 cells: `cell`, the float32 edge length, and origin[3], the grid's low corner in upload space
+ * (the space of the raw P bits); reach in {0, 1, 2}; an unsigned range count_lo .. count_hi; alpha_min; an op; flags.
+ *   1. THE CELL of a splat, per axis c: t = (p_c - origin_c) * inv_cell -- one float32 subtraction and one float32 multiplication,
+ *      each rounded once, never fused; inv_cell = 1.0f / cell is one IEEE float32 division made once on the host.  f = floorf(t).
+ *      The splat is IN THE GRID iff 0 <= f && f < 1024 on all three axes, compared in float before any conversion: a NaN, an infinity
+ *      or a huge t is outside (-0.0f is cell 0).  The cell is (ix, iy, iz) = ((int)f_x, (int)f_y, (int)f_z), its key
+ *      ix | iy << 10 | iz << 20.
+ *   2. POPULATION: a splat that is in the grid, whose TRUE alpha a (what gsr_read returns: under a visibility in force a hidden
+ *      splat's own alpha) satisfies a >= alpha_min (a NaN alpha never does), and that -- under GSR_DENSITY_SKIP_HIDDEN -- the visibility
+ *      in force does not hide (gsr_splat_visible on the raw P; with no visibility in force nothing is hidden).  Without the flag a
+ *      hidden splat counts with its true alpha.
+ *   3. N(i): the number of population splats, i itself included, whose cell differs from i's by at most `reach` on every axis and lies
+ *      inside the grid -- a neighbour cell outside 0..1023 on an axis does not exist, so (1023, y, z) and (0, y + 1, z) never count
+ *      each other.  N(i) = 0 for a splat that is not population.
+ *   4. HIT: a population splat iff count_lo <= N(i) && N(i) <= count_hi, as unsigned integers (count_lo > count_hi is allowed and
+ *      hits nothing); an OUTSIDE splat -- one that passes the alpha and visibility tests but is not in the grid -- iff
+ *      GSR_DENSITY_HIT_OUTSIDE is set; nothing else.  "Floaters" is count = (1, k - 1).
+ *   5. THE MASK, op, n_hit and n_set are gsr_select's: ceil(n / 32) words in upload order, host (mask_is_device = 0) or device / pinned
+ *      memory (1: checked with its exact size before anything is launched); every op but REPLACE reads the mask first; after any op the
+ *      bits at and behind n are 0 and not one byte behind word ceil(n / 32) - 1 is written; no atomic touches the mask.
+ * THE RESULT (NULL: not wanted): n_population; n_outside; n_cells, the occupied cells (n_population / n_cells says whether `cell` was
+ * a sensible choice); count_hist[64]: bin b < 63 holds the population splats with N == b + 1, bin 63 those with N >= 64 -- the
+ * histogram a threshold k is chosen by.  Integer atomics only: nothing depends on the order the waves run in.
+ * counts_out (NULL: skipped): N(i) for every upload index, uint32[n], host (counts_is_device = 0) or device / pinned memory (1:
+ * checked for 4 n bytes before anything is launched).
+ * gsr_select_density_eval: the rule on the host, no context and no GPU.  P float[3n] and alpha float[n] (NULL: every alpha 1) in
+ * gsr_read's layout; vis (NULL: none in force) is what SKIP_HIDDEN hides by, as gsr_visibility_eval takes it (a mask must cover the n
+ * splats).  op is checked and not applied.  hit_out[k] = 0 / 1; counts_out and result may be NULL.
+ * WHAT THE VERB TOUCHES: nothing the context keeps -- no resident bit, depth horizon, cached depth order, policy, visibility state or
+ * entry of gsr_stats -- but a count buffer of its own (4 bytes per splat, kept between calls) and its tally.  It shares the scratch of
+ * an upload's sort (which holds nothing live between uploads and edits), so unlike gsr_select it WAITS for the frames in flight and the
+ * work queued on the public stream, as gsr_move does.  Synchronous.  A context that never calls it allocates and launches nothing new.
+ * GSR_E_INVALID, nothing launched and nothing written: NULL ctx, rule or mask; no geometry ever uploaded, or an upload in progress;
+ * cell not finite or <= 0, or 1.0f / cell not finite; a non-finite origin; reach outside 0..2; unknown flag bits; an unknown op;
+ * reserved_ != 0; a NaN alpha_min; a device mask or device counts that fail the pointer check.  The empty cloud gives GSR_OK, zeros,
+ * and touches no word.
+ * gsr_get_select_density: the calls that selected, the splats hit by the last one, and its clock ms[4], laid out as gsr_get_select's:
+ * [0] the verb's own kernels (HIP events)   [1] the copies, wall clock   [2] the sort (HIP events)   [3] wall clock of the call.
+ * gsr_multi_select_density (below, with the other gsr_multi verbs): rank 0's context, a host mask and host counts.
+ * Out of scope: exact k-nearest-neighbour distances or a radius in world units not tied to the grid; more than 1024 cells per axis; a
+ * per-splat grid; connected components ("select the clump"); the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for
+ * the multi verb; an asynchronous form; results left in device memory. */
+#define GSR_DENSITY_SKIP_HIDDEN 1   /* flags: a splat the visibility in force hides is not population */
+#define GSR_DENSITY_HIT_OUTSIDE 2   /* flags: a splat outside the grid (that passes the alpha and visibility tests) is hit */
+#define GSR_DENSITY_CELLS    1024   /* cells per axis */
+#define GSR_DENSITY_MAX_REACH   2
+#define GSR_DENSITY_HIST_BINS  64
+typedef struct gsr_density_rule {
+    float    cell;                        /* the cells' edge length: finite, > 0, 1.0f / cell finite */
+    float    origin[3];                   /* the grid's low corner, upload space */
+    int32_t  reach;                       /* 0..GSR_DENSITY_MAX_REACH */
+    int32_t  flags;                       /* GSR_DENSITY_* or 0 */
+    int32_t  op;                          /* GSR_SELECT_REPLACE .. GSR_SELECT_TOGGLE */
+    int32_t  reserved_;                   /* 0 */
+    uint32_t count_lo, count_hi;          /* hit iff count_lo <= N <= count_hi */
+    float    alpha_min;                   /* population iff a >= alpha_min (-INFINITY: every alpha but a NaN) */
+} gsr_density_rule;
+typedef struct gsr_density_result {
+    int64_t n_population, n_outside, n_cells;
+    int64_t count_hist[GSR_DENSITY_HIST_BINS];
+} gsr_density_result;
+int  gsr_select_density(gsr_context* ctx, const gsr_density_rule* rule, uint32_t* mask, int mask_is_device,
+                        uint32_t* counts_out /* NULL */, int counts_is_device, gsr_density_result* result /* NULL */,
+                        int64_t* n_hit, int64_t* n_set);
+int  gsr_select_density_eval(const gsr_density_rule* rule, const gsr_visibility* vis /* NULL: none */, int64_t n, const float* P,
+                             const float* alpha /* NULL: all 1 */, uint8_t* hit_out, uint32_t* counts_out /* NULL */,
+                             gsr_density_result* result /* NULL */);   /* host, no context, no GPU */
+int  gsr_get_select_density(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
+
 /* ---- measuring a selection (counts, bounds, moments and histograms of resident splats, on the GPU) ----------------------------------- */
 /* What a mask of gsr_select SAYS besides its bit count: where the selected splats are (a transform gizmo's pivot, "home on selection", a
  * crop box around them), how they lie (nine second moments for a PCA on the host), and how their opacity, size, position and base
@@ -1041,6 +1115,9 @@ int  gsr_multi_select(gsr_multi* m, const gsr_camera* cam, const gsr_select_regi
                       int64_t* n_hit, int64_t* n_set);
 /* gsr_select_attrs on rank 0's copy (the cloud is replicated) into a HOST mask, after the same synchronisation; no rank's state changes */
 int  gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, uint32_t* mask_host, int64_t* n_hit, int64_t* n_set);
+/* gsr_select_density on rank 0's copy into a HOST mask and HOST counts (NULL: skipped), after the same synchronisation; no rank's state changes */
+int  gsr_multi_select_density(gsr_multi* m, const gsr_density_rule* rule, uint32_t* mask_host, uint32_t* counts_host /* NULL */,
+                              gsr_density_result* result /* NULL */, int64_t* n_hit, int64_t* n_set);
 /* gsr_measure on rank 0's copy (the cloud is replicated) from a HOST mask (NULL: every splat), after the same synchronisation; no rank's state changes */
 int  gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out);
 /* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
