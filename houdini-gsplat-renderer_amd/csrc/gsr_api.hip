@@ -61,6 +61,7 @@ static double now_us() { return std::chrono::duration<double, std::micro>(std::c
 #include "k_marks.h"
 #include "k_measure.h"
 #include "k_density.h"
+#include "k_connect.h"
 static_assert(RS_SRC_BLOCK == GSR_K1_THREADS, "the gathering sort pass reads K1's per-workgroup compaction: 256 slots each");
 static_assert(GSR_PLAN_K1_THREADS == GSR_K1_THREADS && GSR_PLAN_BN_THREADS == BN_THREADS && GSR_PLAN_BK_BUCKETS == BK_BUCKETS &&
               GSR_PLAN_CLUSTER == GSR_CLUSTER, "gsr_frame_plan.h counts its grids in the kernels' constants");
@@ -392,6 +393,12 @@ struct gsr_context {
     EditTally seld;                    // gsr_get_select_density (k_density.h): the calls that selected, the splats the last one hit
     DevVec<uint32_t> den_cnt;          // ... its count word per upload index (kept between calls; allocated by the first one)
     PinnedMem<uint32_t> den_h;         // ... and the pinned words its result block arrives in
+    EditTally selc;                    // gsr_get_select_connected (k_connect.h): the calls that selected, the splats the last one hit
+    DevVec<uint32_t> con_tab;          // ... its cell table and union-find: GSR_CON_TAB_ARRAYS arrays of n + 1 words (kept between calls;
+                                       // allocated by the first one; the per-splat size words are den_cnt's)
+    PinnedMem<uint32_t> con_h;         // ... the pinned words its result block arrives in
+    Event con_ev[8];                   // ... and the events around its stages (gsr_debug_select_connected_stages)
+    double con_stage_ms[6] = {0, 0, 0, 0, 0, 0};
 };
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
@@ -3031,7 +3038,8 @@ extern "C" int gsr_stats_reset(gsr_context* c)
 // ... and read back in upload order: it shares the edits' refusals and pointer check, and k_unpack comes last of all.
 #include "gsr_resident_read.h"
 // ... and selected by screen region: read's contract, and k_select behind k_unpack; by attribute (3.14) and by
-// density (3.17: the one verb of the three that borrows the upload sort's scratch and waits for the frames in flight).
+// density (3.17) and by connectivity (3.18): the two verbs of the four that borrow the upload sort's scratch and wait for the frames
+// in flight.
 #include "gsr_resident_select.h"
 // ... and measured: select's contract; k_measure and k_measure_fold behind k_select_attrs.
 #include "gsr_resident_measure.h"

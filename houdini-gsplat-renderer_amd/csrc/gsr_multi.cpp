@@ -722,6 +722,14 @@ extern "C" int gsr_multi_select_density(gsr_multi* m, const gsr_density_rule* ru
     return rc ? rc : gsr_select_density(m->ctx[0], rule, mask_host, 0, counts_host, 0, result, n_hit, n_set);
 }
 
+// ... and selected by connectivity on rank 0's replica (gsr_select_connected with everything in host memory: the caller's thread)
+extern "C" int gsr_multi_select_connected(gsr_multi* m, const gsr_connect_rule* rule, const uint32_t* seed_host, uint32_t* mask_host,
+                                          uint32_t* labels_host, uint32_t* sizes_host, gsr_connect_result* result, int64_t* n_hit, int64_t* n_set)
+{
+    const int rc = multi_enter(m, rule && mask_host, "gsr_multi_select_connected");
+    return rc ? rc : gsr_select_connected(m->ctx[0], rule, seed_host, 0, mask_host, 0, labels_host, sizes_host, 0, result, n_hit, n_set);
+}
+
 // ... and measured on rank 0's replica (gsr_measure from a host mask: the caller's thread; no rank's state changes)
 extern "C" int gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out)
 {

@@ -529,3 +529,320 @@ extern "C" int gsr_select_density(gsr_context* c, const gsr_density_rule* r, uin
     c->seld.last = (int64_t)hits;
     return GSR_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Selection by connectivity (k_connect.h).  gsr_select_density's grid, population, key kernel, sort and waits; behind
+// the sort a table of the occupied cells, a union-find over it and gsr_select's epilogue.  The per-splat size words are the density
+// verb's count buffer (c->den_cnt: k_density_keys writes every word of it), the per-cell arrays the context's own (c->con_tab), the
+// per-splat labels and the cell of each sorted entry live in the sort's B buffers, which hold nothing once the sort has ended.
+static_assert(GSR_CONNECT_SKIP_HIDDEN == GSR_DENF_SKIP_HIDDEN && GSR_CONNECT_HIT_OUTSIDE == GSR_DENF_HIT_OUTSIDE && GSR_CONNECT_CELLS == GSR_DEN_CELLS &&
+              GSR_CONNECT_MAX_REACH == GSR_DENSITY_MAX_REACH && GSR_CONNECT_HIST_BINS == GSR_CON_BINS && GSR_CONNECT_NO_LABEL == GSR_CON_NOLABEL,
+              "the header's flags and limits are the kernels'");
+static_assert(sizeof(gsr_connect_rule) == 44 && offsetof(gsr_connect_rule, origin) == 4 && offsetof(gsr_connect_rule, reach) == 16 &&
+              offsetof(gsr_connect_rule, flags) == 20 && offsetof(gsr_connect_rule, op) == 24 && offsetof(gsr_connect_rule, reserved_) == 28 &&
+              offsetof(gsr_connect_rule, size_lo) == 32 && offsetof(gsr_connect_rule, size_hi) == 36 && offsetof(gsr_connect_rule, alpha_min) == 40,
+              "the rule is the density rule's 11 dwords, the size range in the place of the count range");
+static_assert(sizeof(gsr_connect_result) == 8 * (6 + 2 * GSR_CONNECT_HIST_BINS) && offsetof(gsr_connect_result, n_components) == 24 &&
+              offsetof(gsr_connect_result, comp_hist) == 48 && offsetof(gsr_connect_result, splat_hist) == 48 + 8 * GSR_CONNECT_HIST_BINS,
+              "the result is 70 counts");
+#define GSR_CON_TAB_ARRAYS 7           // ckey, cstart, parent, croot, csize, clabel, cseed: n + 1 words each
+
+// the density rule that has the connect rule's grid, population and flags: what is wrong with one is what is wrong with the other
+static gsr_density_rule connect_as_density(const gsr_connect_rule* r)
+{
+    gsr_density_rule d{};
+    d.cell = r->cell;
+    for (int k = 0; k < 3; ++k) d.origin[k] = r->origin[k];
+    d.reach = r->reach; d.flags = r->flags; d.op = r->op; d.reserved_ = r->reserved_;
+    d.count_lo = 0u; d.count_hi = 0u;
+    d.alpha_min = r->alpha_min;
+    return d;
+}
+static GsrConnectRule connect_rule(const gsr_connect_rule* r, bool has_seed)
+{
+    const gsr_density_rule d = connect_as_density(r);
+    GsrConnectRule k{};
+    k.den = density_rule(&d);
+    k.size_lo = r->size_lo; k.size_hi = r->size_hi;
+    k.has_seed = has_seed ? 1 : 0;
+    return k;
+}
+
+// The rule on the host.  The classes come from gsr_density_class; the table is the sorted unique keys, as gsr_select_density_eval
+// builds it, with each cell's population, smallest upload index and seed mark; the components come from a SEQUENTIAL union-find over
+// the rows of gsr_connect_row with the kernels' hook rule (gsr_connect_hook), the verdict from gsr_connect_hit.
+extern "C" int gsr_select_connected_eval(const gsr_connect_rule* r, const gsr_visibility* vis, int64_t n, const float* P, const float* alpha,
+                                         const uint32_t* seed_bits, uint8_t* hit_out, uint32_t* labels_out, uint32_t* sizes_out, gsr_connect_result* result)
+{
+    if (!r) return set_err(GSR_E_INVALID, "gsr_select_connected_eval: rule is NULL");
+    const gsr_density_rule as_density = connect_as_density(r);
+    const char* bad = density_rule_error(&as_density);
+    if (!bad) bad = visibility_error(vis);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_select_connected_eval: %s", bad);
+    if (n < 0 || n > 0x7fffffffll || (n > 0 && (!P || !hit_out))) return set_err(GSR_E_INVALID, "gsr_select_connected_eval: bad argument");
+    const gsr_visibility* const hide = (r->flags & GSR_CONNECT_SKIP_HIDDEN) ? vis : nullptr;   // (no visibility: nothing is hidden)
+    const uint32_t* const vmask = hide ? hide->mask : nullptr;
+    if (vmask && hide->mask_splats < n)
+        return set_err(GSR_E_INVALID, "gsr_select_connected_eval: the visibility's mask covers %lld of the %lld splats", (long long)hide->mask_splats, (long long)n);
+    const GsrConnectRule rule = connect_rule(r, seed_bits != nullptr);
+    const GsrVisRule vr = visibility_rule(hide);
+    gsr_connect_result res;
+    std::memset(&res, 0, sizeof res);
+    std::vector<uint32_t> cls((size_t)n);
+    std::vector<std::pair<uint32_t, uint32_t>> pairs;  // (key, upload index) of the population: sorted, the index breaks ties as the stable sort does
+    for (int64_t k = 0; k < n; ++k) {
+        const float px = P[3 * k], py = P[3 * k + 1], pz = P[3 * k + 2];
+        const bool hidden = hide && !gsr_splat_visible(vr, px, py, pz, vmask ? vmask[k >> 5] : 0u, (uint32_t)(k & 31));
+        const uint32_t c = gsr_density_class(rule.den, px, py, pz, alpha ? alpha[k] : 1.0f, hidden);
+        cls[(size_t)k] = c;
+        if (c < GSR_DEN_NOKEY) pairs.emplace_back(c, (uint32_t)k);
+        else if (c == GSR_DEN_OUTSIDE) res.n_outside += 1;
+    }
+    res.n_population = (int64_t)pairs.size();
+    std::sort(pairs.begin(), pairs.end());
+    // the cell table: ukey rising; per cell its population, its smallest upload index and whether it holds a seed
+    std::vector<uint32_t> ukey, cpop, cmin, cseed;
+    for (size_t k = 0; k < pairs.size(); ++k) {
+        if (k == 0 || pairs[k].first != pairs[k - 1].first) { ukey.push_back(pairs[k].first); cpop.push_back(0u); cmin.push_back(pairs[k].second); cseed.push_back(0u); }
+        cpop.back() += 1u;
+        const uint32_t i = pairs[k].second;
+        if (seed_bits && ((seed_bits[i >> 5] >> (i & 31u)) & 1u)) cseed.back() = 1u;
+    }
+    const size_t U = ukey.size();
+    res.n_cells = (int64_t)U;
+    std::vector<uint32_t> parent(U);
+    for (size_t u = 0; u < U; ++u) parent[u] = (uint32_t)u;
+    auto find = [&](uint32_t x) { while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; } return x; };
+    for (size_t u = 0; u < U; ++u)
+        for (int dz = 0; dz <= rule.den.reach; ++dz)
+            for (int dy = -rule.den.reach; dy <= rule.den.reach; ++dy) {
+                uint32_t klo = 0u, khi = 0u;
+                if (!gsr_connect_row(ukey[u], rule.den.reach, dy, dz, &klo, &khi)) continue;
+                for (size_t p = (size_t)(std::lower_bound(ukey.begin(), ukey.end(), klo) - ukey.begin()); p < U && ukey[p] <= khi; ++p) {
+                    const uint32_t a = find((uint32_t)u), b = find((uint32_t)p);
+                    if (a == b) continue;
+                    uint32_t under = 0u, over = 0u;
+                    gsr_connect_hook(a, b, &under, &over);
+                    parent[under] = over;
+                }
+            }
+    // the tally per root: population, smallest upload index, seed
+    std::vector<uint32_t> root(U), size(U, 0u), label(U, GSR_CON_NOLABEL), seeded(U, 0u);
+    for (size_t u = 0; u < U; ++u) {
+        const uint32_t t = root[u] = find((uint32_t)u);
+        size[t] += cpop[u];
+        label[t] = std::min(label[t], cmin[u]);
+        seeded[t] |= cseed[u];
+    }
+    for (size_t u = 0; u < U; ++u) {
+        if (root[u] != (uint32_t)u) continue;
+        res.n_components += 1;
+        res.n_seeded += seeded[u] ? 1 : 0;
+        res.largest = std::max(res.largest, (int64_t)size[u]);
+        res.comp_hist[gsr_connect_bin(size[u])] += 1;
+        res.splat_hist[gsr_connect_bin(size[u])] += (int64_t)size[u];
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t c = cls[(size_t)k];
+        uint32_t word = c == GSR_DEN_OUTSIDE ? GSR_DEN_CNT_OUTSIDE : 0u, lab = GSR_CON_NOLABEL;
+        bool sd = false;
+        if (c < GSR_DEN_NOKEY) {
+            const uint32_t t = root[(size_t)(std::lower_bound(ukey.begin(), ukey.end(), c) - ukey.begin())];
+            word = size[t]; lab = label[t]; sd = seeded[t] != 0u;
+        }
+        hit_out[k] = gsr_connect_hit(rule, word, sd) ? 1 : 0;
+        if (labels_out) labels_out[k] = lab;
+        if (sizes_out) sizes_out[k] = word & ~GSR_DEN_CNT_OUTSIDE;
+    }
+    if (result) *result = res;
+    return GSR_OK;
+}
+
+extern "C" int gsr_get_select_connected(gsr_context* c, int64_t* calls, int64_t* hit_last, double ms[4])
+{
+    if (!c) return set_err(GSR_E_INVALID, "gsr_get_select_connected: ctx is NULL");
+    return c->selc.report(calls, hit_last, ms);
+}
+
+extern "C" int gsr_debug_select_connected_stages(gsr_context* c, double ms[6])
+{
+    if (!c || !ms) return set_err(GSR_E_INVALID, "gsr_debug_select_connected_stages: NULL argument");
+    for (int k = 0; k < 6; ++k) ms[k] = c->con_stage_ms[k];
+    return GSR_OK;
+}
+
+extern "C" int gsr_select_connected(gsr_context* c, const gsr_connect_rule* r, const uint32_t* seed, int seed_is_device, uint32_t* mask, int mask_is_device,
+                                    uint32_t* labels_out, uint32_t* sizes_out, int outs_are_device, gsr_connect_result* result, int64_t* n_hit, int64_t* n_set)
+{
+    const char* const who = "gsr_select_connected";
+    if (!c || !r || !mask) return set_err(GSR_E_INVALID, "gsr_select_connected: NULL argument");
+    int rc = refuse_edit(c, who);
+    if (rc) return rc;
+    const gsr_density_rule as_density = connect_as_density(r);
+    const char* bad = density_rule_error(&as_density);
+    if (bad) return set_err(GSR_E_INVALID, "gsr_select_connected: %s", bad);
+    const uint32_t n = c->n;
+    if (n == 0) {                                      // the empty cloud: no word of the mask or the outputs exists
+        if (n_hit) *n_hit = 0;
+        if (n_set) *n_set = 0;
+        if (result) std::memset(result, 0, sizeof *result);
+        return GSR_OK;
+    }
+    const double t_begin = up_now_ms();
+    HIP_TRY(hipSetDevice(c->device));
+    // before anything is launched: a wrong pointer must never be found out by a kernel
+    const MaskArg mk{mask, mask_is_device != 0, n};
+    const MaskArg sk{seed, seed_is_device != 0, n};
+    if ((rc = mk.check(c, who))) return rc;
+    if (seed && sk.is_device && (rc = check_device_source(c, seed, sk.words() * 4, who, "seed"))) return rc;
+    const bool outs_dev = outs_are_device != 0;
+    if (labels_out && outs_dev && (rc = check_device_source(c, labels_out, (size_t)n * 4, who, "labels_out"))) return rc;
+    if (sizes_out && outs_dev && (rc = check_device_source(c, sizes_out, (size_t)n * 4, who, "sizes_out"))) return rc;
+    // the sort's scratch is shared with the frames' sorts and an upload's: nothing may be in flight (this also waits for whoever
+    // produced a device mask or seed on the public stream)
+    if ((rc = sync_all(c))) return rc;
+    // ---- everything the call needs, before the launch: host masks, host outputs, the result block and the block counts in the arena
+    FrameSlot& sl = c->slot[0];
+    const uint32_t nblocks = div_up(n, (uint32_t)GSR_CONNECT_BLOCK);
+    size_t off = 0;
+    auto place = [&](size_t bytes) { const size_t at = off; off += pad256(bytes); return at; };
+    const size_t oMask = place(mk.stage_bytes()), oSeed = place(sk.stage_bytes()), oRes = place((size_t)GSR_CON_R_WORDS * 4);
+    const size_t oCounts = place((size_t)nblocks * 4), oOffsets = place(((size_t)nblocks + 1) * 4);
+    const size_t oLabels = place(labels_out && !outs_dev ? (size_t)n * 4 : 0), oSizes = place(sizes_out && !outs_dev ? (size_t)n * 4 : 0);
+    const size_t cwords = (size_t)GSR_SEL_COUNTER_SLOTS * GSR_SEL_COUNTER_STRIDE;
+    if ((rc = ensure_stage(c, off)) || (rc = ensure_inverse_perm(c)) || (rc = ensure_sel_counters(c, who))) return rc;
+    for (Event& ev : c->con_ev) {
+        if (ev) continue;
+        const hipError_t ee = ev.create(hipEventDefault);
+        if (ee != hipSuccess) return set_err(ee == hipErrorOutOfMemory ? GSR_E_OOM : GSR_E_HIP, "gsr_select_connected: no event: %s", hipGetErrorString(ee));
+    }
+    if (!c->con_h && c->con_h.alloc((size_t)GSR_CON_R_WORDS, 0)) {
+        (void)hipGetLastError();
+        return set_err(GSR_E_OOM, "gsr_select_connected: no pinned host memory for the result");
+    }
+    if (c->up_sort.hold(n)) return set_err(GSR_E_OOM, "gsr_select_connected: no room for the sort of the cell keys");
+    if ((rc = ensure_counts(sl.hist, (size_t)512 * div_up(n, (uint32_t)RS_THREADS * (uint32_t)RS_ITEMS) + 8))) return rc;
+    if ((rc = c->den_cnt.ensure((size_t)n, (size_t)n + n / 8 + 1024))) return rc;
+    const size_t tab = (size_t)n + 1;                  // words per array of the table (cstart holds a sentinel behind the last cell)
+    if ((rc = c->con_tab.ensure(tab * GSR_CON_TAB_ARRAYS, (tab + tab / 8 + 1024) * GSR_CON_TAB_ARRAYS))) return rc;
+    HIP_TRY(hipStreamSynchronize(sl.own));             // the inverse of the storage order is built there
+    hipStream_t us = sl.stream;                        // where radix_sort queues its passes
+    uint32_t* const dmask = mk.is_device ? mask : reinterpret_cast<uint32_t*>(c->stage + oMask);
+    uint32_t* const dres = reinterpret_cast<uint32_t*>(c->stage + oRes);
+    uint32_t* const dcounts = reinterpret_cast<uint32_t*>(c->stage + oCounts);
+    uint32_t* const doffsets = reinterpret_cast<uint32_t*>(c->stage + oOffsets);
+    uint32_t* const dlabels = !labels_out ? nullptr : outs_dev ? labels_out : reinterpret_cast<uint32_t*>(c->stage + oLabels);
+    uint32_t* const dsizes = !sizes_out ? nullptr : outs_dev ? sizes_out : reinterpret_cast<uint32_t*>(c->stage + oSizes);
+    uint32_t* const t0 = c->con_tab.get();
+    uint32_t *const ckey = t0, *const cstart = t0 + tab, *const parent = t0 + 2 * tab, *const croot = t0 + 3 * tab, *const csize = t0 + 4 * tab,
+             *const clabel = t0 + 5 * tab, *const cseed = t0 + 6 * tab;
+    double copy_ms = 0.0;
+    const uint32_t* dseed = nullptr;
+    if (seed) {                                        // a host seed goes to its own place in the arena: it may be the host mask itself
+        const hipError_t e = sk.to_device(c, us, oSeed, &copy_ms, &dseed);
+        if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_connected: %s", hipGetErrorString(e));
+    }
+    if (!mk.is_device && r->op != GSR_SELECT_REPLACE) {               // every op but REPLACE reads the mask first
+        const uint32_t* staged = nullptr;
+        const hipError_t e = mk.to_device(c, us, oMask, &copy_ms, &staged);
+        if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_connected: %s", hipGetErrorString(e));
+    }
+    const bool vis = c->vis_on, hide = vis && (r->flags & GSR_CONNECT_SKIP_HIDDEN);
+    const GsrConnectRule rule = connect_rule(r, seed != nullptr);
+    const GsrVisRule vrule = hide ? c->vis : GsrVisRule{};
+    const uint32_t* const inv = c->perm ? c->wire_inv : (const uint32_t*)nullptr;
+    const float* const alpha0 = vis ? (const float*)c->alpha0 : nullptr;
+    const uint32_t* const vis_mask = hide ? (const uint32_t*)c->vis_mask : nullptr;
+    uint32_t *kA = c->up_sort.kA, *kB = c->up_sort.kB, *vA = c->up_sort.vA, *vB = c->up_sort.vB;
+    const uint32_t nchunks = div_up(n, GSR_CONNECT_THREADS);
+    const dim3 grid(nchunks), capped(std::min(nchunks, (uint32_t)GSR_DENSITY_BLOCKS)), block(GSR_CONNECT_THREADS);
+    Event* const ev = c->con_ev;
+    hipError_t e = hipMemsetAsync(c->sel_counters, 0, cwords * 8, us);
+    if (e == hipSuccess) e = hipMemsetAsync(dres, 0, (size_t)GSR_CON_R_WORDS * 4, us);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_density_keys, capped, block, 0, us, n, nchunks, inv, c->geoA, alpha0, vis_mask, hide ? 1 : 0, rule.den, vrule, kA, vA, c->den_cnt.get(), dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_connected: %s", hipGetErrorString(e));
+    // the 31-bit keys with their upload indices, in the instantiation morton_order launches (four 8-bit passes): the sentinels sort last
+    if ((rc = radix_sort(sl, kA, vA, kB, vB, n, 31, true, (uint32_t*)nullptr, RS_XCD_DEPTH != 0))) return rc;   // (leaves the result in what kA / vA name now)
+    uint32_t *const ulabel = kB, *const cidx = vB;     // the other two buffers are free from here on
+    e = hipEventRecord(ev[2], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_connect_mark, dim3(nblocks), block, 0, us, n, kA, dres, dcounts);
+        hipLaunchKernelGGL(k_remove_scan, dim3(1), dim3(GSR_REMOVE_SCAN_THREADS), 0, us, nblocks, dcounts, doffsets);
+        hipLaunchKernelGGL(k_connect_table, dim3(nblocks), block, 0, us, n, kA, dres, doffsets, ckey, cstart, parent, csize, clabel, cseed, cidx);
+        if (dseed) hipLaunchKernelGGL(k_connect_seed, capped, block, 0, us, n, nchunks, vA, dres, dseed, cidx, cseed);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[3], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_connect_link, capped, block, 0, us, n, nchunks, (int)r->reach, dres, ckey, parent);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[4], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_connect_flatten, capped, block, 0, us, n, nchunks, dres, vA, cstart, parent, cseed, croot, csize, clabel);
+        hipLaunchKernelGGL(k_connect_stats, capped, block, 0, us, n, nchunks, croot, csize, dres);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[5], us);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_connect_scatter, capped, block, 0, us, n, nchunks, dres, vA, cidx, croot, csize, clabel, c->den_cnt.get(), ulabel);
+        hipLaunchKernelGGL(k_connect_hit, grid, block, 0, us, n, rule, c->den_cnt.get(), ulabel, dlabels, dsizes, dmask, c->sel_counters);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[6], us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    const double t1 = up_now_ms();
+    if (e == hipSuccess) e = hipMemcpyAsync(c->sel_h_counters, c->sel_counters, cwords * 8, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->con_h, dres, (size_t)GSR_CON_R_WORDS * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_connected: %s", hipGetErrorString(e));
+    // the counts the kernels left must add up before a word of the caller's is written
+    const uint32_t* const h = c->con_h;
+    gsr_connect_result res;
+    std::memset(&res, 0, sizeof res);
+    res.n_population = (int64_t)h[GSR_CON_R_POP];
+    res.n_outside = (int64_t)h[GSR_CON_R_OUTSIDE];
+    res.n_cells = (int64_t)h[GSR_CON_R_CELLS];
+    res.n_components = (int64_t)h[GSR_CON_R_COMPS];
+    res.n_seeded = (int64_t)h[GSR_CON_R_SEEDED];
+    res.largest = (int64_t)h[GSR_CON_R_LARGEST];
+    int64_t comps = 0, binned = 0;
+    for (int b = 0; b < GSR_CON_BINS; ++b) {
+        comps += (res.comp_hist[b] = (int64_t)h[GSR_CON_R_CHIST + b]);
+        binned += (res.splat_hist[b] = (int64_t)h[GSR_CON_R_SHIST + b]);
+    }
+    if (res.n_population + res.n_outside > (int64_t)n || res.n_cells > res.n_population || res.n_components > res.n_cells || comps != res.n_components ||
+        binned != res.n_population || res.n_seeded > res.n_components || res.largest > res.n_population)
+        return set_err(GSR_E_HIP, "gsr_select_connected: the kernels counted %lld population, %lld outside, %lld cells, %lld components (%lld binned, %lld splats "
+                       "binned, largest %lld) among %u splats", (long long)res.n_population, (long long)res.n_outside, (long long)res.n_cells,
+                       (long long)res.n_components, (long long)comps, (long long)binned, (long long)res.largest, n);
+    if (!mk.is_device) e = hipMemcpyAsync(mask, dmask, mk.words() * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess && labels_out && !outs_dev) e = hipMemcpyAsync(labels_out, dlabels, (size_t)n * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess && sizes_out && !outs_dev) e = hipMemcpyAsync(sizes_out, dsizes, (size_t)n * 4, hipMemcpyDeviceToHost, us);
+    if (e == hipSuccess) e = hipStreamSynchronize(us);
+    if (e != hipSuccess) return set_err(GSR_E_HIP, "gsr_select_connected: %s", hipGetErrorString(e));
+    copy_ms += up_now_ms() - t1;
+    unsigned long long hits = 0, set = 0;
+    sum_sel_counters(c, &hits, &set);
+    if (n_hit) *n_hit = (int64_t)hits;
+    if (n_set) *n_set = (int64_t)set;
+    if (result) *result = res;
+    double total = 0.0;
+    for (int k = 0; k < 6; ++k) {
+        float ms = 0.0f;
+        c->con_stage_ms[k] = hipEventElapsedTime(&ms, ev[k], ev[k + 1]) == hipSuccess ? (double)ms : 0.0;
+        if (k != 1) total += c->con_stage_ms[k];
+    }
+    c->selc.ms[0] = total;
+    c->selc.ms[1] = copy_ms;
+    c->selc.ms[2] = c->con_stage_ms[1];
+    c->selc.ms[3] = up_now_ms() - t_begin;
+    c->selc.calls += 1;
+    c->selc.last = (int64_t)hits;
+    return GSR_OK;
+}

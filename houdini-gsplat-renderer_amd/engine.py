@@ -160,6 +160,29 @@ class gsr_density_result(C.Structure):
         return (self.n_population, self.n_outside, self.n_cells, tuple(self.count_hist[:]))
 
 
+class gsr_connect_rule(C.Structure):
+    """include/gsplat_hip.h: the rule of gsr_select_connected -- the density rule's grid, reach, alpha floor and flags, and a range of
+    component sizes in the place of the count range"""
+    _fields_ = [("cell", C.c_float), ("origin", C.c_float * 3), ("reach", C.c_int32), ("flags", C.c_int32), ("op", C.c_int32),
+                ("reserved_", C.c_int32), ("size_lo", C.c_uint32), ("size_hi", C.c_uint32), ("alpha_min", C.c_float)]
+
+
+class gsr_connect_result(C.Structure):
+    """include/gsplat_hip.h: what gsr_select_connected reports beside the mask.  hists() -> (comp_hist, splat_hist) as int64 arrays"""
+    _fields_ = [("n_population", C.c_int64), ("n_outside", C.c_int64), ("n_cells", C.c_int64), ("n_components", C.c_int64),
+                ("n_seeded", C.c_int64), ("largest", C.c_int64), ("comp_hist", C.c_int64 * 32), ("splat_hist", C.c_int64 * 32)]
+
+    def hists(self) -> tuple:
+        """(int64 (32,), int64 (32,)): bin b holds the components with floor(log2(size)) == b, and the population splats in them"""
+        return np.array(self.comp_hist[:], np.int64), np.array(self.splat_hist[:], np.int64)
+
+    def fields(self) -> tuple:
+        """(n_population, n_outside, n_cells, n_components, n_seeded, largest, comp_hist, splat_hist as tuples): what two results are
+        compared by"""
+        return (self.n_population, self.n_outside, self.n_cells, self.n_components, self.n_seeded, self.largest,
+                tuple(self.comp_hist[:]), tuple(self.splat_hist[:]))
+
+
 class gsr_hist_spec(C.Structure):
     """include/gsplat_hip.h: one histogram of gsr_measure -- a channel, [lo, hi) in `bins` bins, and what gsr_hist_prepare derives"""
     _fields_ = [("channel", C.c_int32), ("flags", C.c_int32), ("bins", C.c_int32), ("lo", C.c_float), ("hi", C.c_float), ("inv_w", C.c_float)]
@@ -263,6 +286,12 @@ DENSITY_SKIP_HIDDEN, DENSITY_HIT_OUTSIDE = 1, 2
 DENSITY_CELLS = 1024       # GSR_DENSITY_CELLS: cells per axis
 DENSITY_MAX_REACH = 2      # GSR_DENSITY_MAX_REACH
 DENSITY_HIST_BINS = 64     # GSR_DENSITY_HIST_BINS
+# GSR_CONNECT_* (gsr_connect_rule.flags, and the limits of the rule): what gsr_select_connected links and hits
+CONNECT_SKIP_HIDDEN, CONNECT_HIT_OUTSIDE = 1, 2
+CONNECT_CELLS = 1024       # GSR_CONNECT_CELLS: cells per axis
+CONNECT_MAX_REACH = 2      # GSR_CONNECT_MAX_REACH
+CONNECT_HIST_BINS = 32     # GSR_CONNECT_HIST_BINS
+CONNECT_NO_LABEL = 0xffffffff  # GSR_CONNECT_NO_LABEL: labels_out of a splat that is not population
 # GSR_MEASURE_* (gsr_measure_request.what / .flags) and GSR_HIST_* (gsr_hist_spec.channel / .flags): what gsr_measure computes
 MEASURE_BOUNDS, MEASURE_EXTENT, MEASURE_MOMENTS = 1, 2, 4
 MEASURE_SKIP_HIDDEN = 1
@@ -316,6 +345,8 @@ C_ABI_SYMBOLS = [
     "gsr_select", "gsr_select_eval", "gsr_get_select", "gsr_multi_select",
     "gsr_select_attrs", "gsr_select_attrs_eval", "gsr_get_select_attrs", "gsr_multi_select_attrs",
     "gsr_select_density", "gsr_select_density_eval", "gsr_get_select_density", "gsr_multi_select_density",
+    "gsr_select_connected", "gsr_select_connected_eval", "gsr_get_select_connected", "gsr_debug_select_connected_stages",
+    "gsr_multi_select_connected",
     "gsr_render_marks", "gsr_get_marks",
     "gsr_measure", "gsr_measure_eval", "gsr_hist_prepare", "gsr_get_measure", "gsr_multi_measure",
     "gsr_xform_prepare", "gsr_transform_eval", "gsr_transform", "gsr_get_transform", "gsr_multi_transform",
@@ -456,6 +487,12 @@ def load_library() -> C.CDLL:
     L.gsr_select_density_eval.argtypes = [C.POINTER(gsr_density_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, C.POINTER(gsr_density_result)]
     L.gsr_get_select_density.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
     L.gsr_multi_select_density.argtypes = [vp, C.POINTER(gsr_density_rule), vp, vp, C.POINTER(gsr_density_result), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_connected.argtypes = [vp, C.POINTER(gsr_connect_rule), vp, i32, vp, i32, vp, vp, i32, C.POINTER(gsr_connect_result),
+                                       C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gsr_select_connected_eval.argtypes = [C.POINTER(gsr_connect_rule), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp, vp, C.POINTER(gsr_connect_result)]
+    L.gsr_get_select_connected.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double)]
+    L.gsr_debug_select_connected_stages.argtypes = [vp, C.POINTER(C.c_double)]
+    L.gsr_multi_select_connected.argtypes = [vp, C.POINTER(gsr_connect_rule), vp, vp, vp, vp, C.POINTER(gsr_connect_result), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gsr_measure.argtypes = [vp, vp, i32, C.POINTER(gsr_measure_request), C.POINTER(gsr_measure_result), vp]
     L.gsr_measure_eval.argtypes = [C.POINTER(gsr_measure_request), C.POINTER(gsr_visibility), i64, vp, vp, vp, vp, vp, C.POINTER(gsr_measure_result), vp]
     L.gsr_hist_prepare.argtypes = [i32, i32, C.c_double, C.c_double, i32, C.POINTER(gsr_hist_spec)]
@@ -1052,6 +1089,41 @@ def select_density_eval(rule, P, alpha=None, vis=None, counts: bool = False, res
                                                   a.ctypes.data if a is not None and n else None, hit.ctypes.data,
                                                   cnt.ctypes.data if counts else None, C.byref(res) if result else None))
     out = (hit[:n].astype(bool),) + ((cnt[:n],) if counts else ()) + ((res,) if result else ())
+    return out[0] if len(out) == 1 else out
+
+
+def connect_rule(cell, origin, reach: int = 1, size=(1, 0xffffffff), alpha_min: float = float("-inf"), flags: int = 0,
+                 op: int = SELECT_REPLACE) -> gsr_connect_rule:
+    """gsr_connect_rule: density_rule's grid (cell and origin: density_grid makes both from a bounding box), reach = how far apart two
+    occupied cells may be and still be adjacent (0..2); size = (lo, hi), hit iff lo <= the population of the splat's connected
+    component <= hi ((1, k - 1): every clump of fewer than k splats); alpha_min: only splats with a true alpha >= it are population;
+    flags = CONNECT_SKIP_HIDDEN | CONNECT_HIT_OUTSIDE; op = SELECT_*.  What the fields may hold is the library's to refuse."""
+    r = gsr_connect_rule()
+    r.cell = float(cell)
+    r.origin[:] = [float(x) for x in np.asarray(origin, np.float32).reshape(3)]
+    r.reach, r.op, r.flags = int(reach), int(op), int(flags)
+    r.size_lo, r.size_hi = int(size[0]), int(size[1])
+    r.alpha_min = float(alpha_min)
+    return r
+
+
+def select_connected_eval(rule, P, alpha=None, seed=None, vis=None, labels: bool = False, sizes: bool = False, result: bool = False):
+    """gsr_select_connected_eval (host only, no GPU): the rule of gsr_select_connected through the functions the kernels evaluate.  P
+    float32 (n, 3) and alpha float32 (n,) TRUE alphas in read()'s layout (None: every alpha 1); seed: a boolean array over the splats
+    or packed uint32 words (None: no seed clause); vis: the gsr_visibility that CONNECT_SKIP_HIDDEN hides by, or None -> bool (n,) hit;
+    with labels / sizes / result also the uint32 (n,) labels / the uint32 (n,) sizes / the gsr_connect_result, in that order"""
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    n = P.shape[0]
+    a = None if alpha is None else np.ascontiguousarray(alpha, dtype=np.float32).reshape(-1)
+    if a is not None and a.shape[0] != n:
+        raise GsrError(-1, f"select_connected_eval: the arrays hold {sorted({n, a.shape[0]})} rows")
+    sw = None if seed is None else np.concatenate([removal_words(seed, n), np.zeros(1, np.uint32)])
+    hit, lab, siz, res = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32), gsr_connect_result()
+    _check(load_library().gsr_select_connected_eval(C.byref(rule), C.byref(vis) if vis is not None else None, n, P.ctypes.data if n else None,
+                                                    a.ctypes.data if a is not None and n else None, sw.ctypes.data if sw is not None else None,
+                                                    hit.ctypes.data, lab.ctypes.data if labels else None, siz.ctypes.data if sizes else None,
+                                                    C.byref(res) if result else None))
+    out = (hit[:n].astype(bool),) + ((lab[:n],) if labels else ()) + ((siz[:n],) if sizes else ()) + ((res,) if result else ())
     return out[0] if len(out) == 1 else out
 
 
@@ -1840,6 +1912,48 @@ class Engine:
         the sort, wall]}"""
         return self._tally(self.L.gsr_get_select_density, "selects", "hit_last")
 
+    # ---- selection by connectivity (include/gsplat_hip.h, "selection by connectivity")
+    def select_connected(self, rule: gsr_connect_rule, mask=None, seed=None, outputs: bool = False):
+        """gsr_select_connected into a HOST mask: the resident splats whose connected component the rule (connect_rule) hits -> (bool
+        (n,) mask in upload order, n_hit, n_set, the gsr_connect_result[, the uint32 (n,) labels, the uint32 (n,) sizes]).  mask = the
+        prior selection the rule's op combines with, seed = the selection a component must touch (each a boolean array over the resident
+        splats or packed uint32 words; None: nothing selected / no seed clause).  Waits for the frames in flight; changes and invalidates
+        nothing."""
+        n = self.read_info()["n_splats"]
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        sw = None if seed is None else removal_words(seed, n).copy()
+        lab, siz = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_connect_result()
+        _check(self.L.gsr_select_connected(self.h, C.byref(rule), sw.ctypes.data if sw is not None and n else None, 0, words.ctypes.data, 0,
+                                           lab.ctypes.data if outputs else None, siz.ctypes.data if outputs else None, 0, C.byref(res),
+                                           C.byref(hit), C.byref(nset)))
+        return (unpack_mask(words, n), hit.value, nset.value, res) + ((lab[:n], siz[:n]) if outputs else ())
+
+    def select_connected_device(self, rule: gsr_connect_rule, mask_ptr, seed_ptr=None, labels_ptr=None, sizes_ptr=None):
+        """gsr_select_connected into packed uint32 mask words in DEVICE memory (a raw pointer or an object with data_ptr(); ceil(n / 32)
+        words, read first by every op but SELECT_REPLACE); seed_ptr: the seed words in device memory (None: no seed clause; it may be
+        mask_ptr: SELECT_ADD then grows the selection in place); labels_ptr / sizes_ptr: n uint32 each in device memory.  Waits for
+        the frames in flight and the work queued on the stream given to set_stream first; synchronous -> (n_hit, n_set, the
+        gsr_connect_result).  The mask goes straight into remove_device, transform, grade or duplicate: nothing crosses the link."""
+        who = "select_connected_device"
+        ptr = _device_mask_ptr(mask_ptr, who)
+        opt = lambda p: None if p is None else C.c_void_p(_device_mask_ptr(p, who))
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_connect_result()
+        _check(self.L.gsr_select_connected(self.h, C.byref(rule), opt(seed_ptr), 1, C.c_void_p(ptr), 1, opt(labels_ptr), opt(sizes_ptr), 1,
+                                           C.byref(res), C.byref(hit), C.byref(nset)))
+        return hit.value, nset.value, res
+
+    def get_select_connected(self) -> dict:
+        """gsr_get_select_connected -> {selects: calls that selected, hit_last, ms: the last call's clock [the verb's kernels, copies,
+        the sort, wall]}"""
+        return self._tally(self.L.gsr_get_select_connected, "selects", "hit_last")
+
+    def select_connected_stages(self) -> list:
+        """gsr_debug_select_connected_stages -> the last call's kernels, ms: [keys, sort, cell table, link, flatten + stats, scatter + hit]"""
+        ms = (C.c_double * 6)()
+        _check(self.L.gsr_debug_select_connected_stages(self.h, ms))
+        return list(ms)
+
     # ---- measuring a selection (include/gsplat_hip.h, "measuring a selection")
     def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
         """gsr_measure from a HOST mask (a boolean array over the resident splats or packed uint32 words; None: every splat): counts,
@@ -2555,6 +2669,21 @@ class MultiEngine:
         _check(self.L.gsr_multi_select_density(self.h, C.byref(rule), words.ctypes.data, cnt.ctypes.data if counts else None, C.byref(res),
                                                C.byref(hit), C.byref(nset)))
         return (unpack_mask(words, n), hit.value, nset.value, res) + ((cnt[:n],) if counts else ())
+
+    def select_connected(self, rule: gsr_connect_rule, mask=None, seed=None, outputs: bool = False):
+        """gsr_multi_select_connected: Engine.select_connected on rank 0's copy (the cloud is replicated), everything in host memory ->
+        (bool mask, n_hit, n_set, the gsr_connect_result[, the labels, the sizes])"""
+        c64 = C.c_int64(0)
+        _check(self.L.gsr_read_info(self.L.gsr_multi_context(self.h, 0), C.byref(c64), None, None))
+        n = c64.value
+        words = removal_words(np.zeros(n, bool) if mask is None else mask, n).copy()
+        sw = None if seed is None else removal_words(seed, n).copy()
+        lab, siz = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        hit, nset, res = C.c_int64(0), C.c_int64(0), gsr_connect_result()
+        _check(self.L.gsr_multi_select_connected(self.h, C.byref(rule), sw.ctypes.data if sw is not None and n else None, words.ctypes.data,
+                                                 lab.ctypes.data if outputs else None, siz.ctypes.data if outputs else None, C.byref(res),
+                                                 C.byref(hit), C.byref(nset)))
+        return (unpack_mask(words, n), hit.value, nset.value, res) + ((lab[:n], siz[:n]) if outputs else ())
 
     def measure(self, request: gsr_measure_request, mask=None) -> gsr_measure_result:
         """gsr_multi_measure: Engine.measure on rank 0's copy (the cloud is replicated), from a host mask (None: every splat)"""

@@ -746,7 +746,7 @@ int  gsr_get_select_attrs(gsr_context* ctx, int64_t* calls, int64_t* hit_last, d
  * [0] the verb's own kernels (HIP events)   [1] the copies, wall clock   [2] the sort (HIP events)   [3] wall clock of the call.
  * gsr_multi_select_density (below, with the other gsr_multi verbs): rank 0's context, a host mask and host counts.
  * Out of scope: exact k-nearest-neighbour distances or a radius in world units not tied to the grid; more than 1024 cells per axis; a
- * per-splat grid; connected components ("select the clump"); the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for
+ * per-splat grid; connected components (gsr_select_connected, below, is that verb); the GSplatRenderer shim and the HDK glue; gsr_comm_*; a device mask for
  * the multi verb; an asynchronous form; results left in device memory. */
 #define GSR_DENSITY_SKIP_HIDDEN 1   /* flags: a splat the visibility in force hides is not population */
 #define GSR_DENSITY_HIT_OUTSIDE 2   /* flags: a splat outside the grid (that passes the alpha and visibility tests) is hit */
@@ -774,6 +774,85 @@ int  gsr_select_density_eval(const gsr_density_rule* rule, const gsr_visibility*
                              const float* alpha /* NULL: all 1 */, uint8_t* hit_out, uint32_t* counts_out /* NULL */,
                              gsr_density_result* result /* NULL */);   /* host, no context, no GPU */
 int  gsr_get_select_density(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
+
+/* ---- selection by connectivity (resident splats picked by the connected clump of occupied cells they lie in, on the GPU) ------------- */
+/* The mask gsr_select makes, from the CLUMP a splat belongs to.  Floaters come in clumps: five of them in adjacent cells give each other
+ * N >= 5 and gsr_select_density keeps them; what marks them is that the clump is small.  "Every connected group of fewer than k splats"
+ * is size = (1, k - 1); "grow my selection to the object it touches" is a seed mask.  The key kernel and the sort of
+ * gsr_select_density, then a table of the occupied cells, a lock-free union-find over it and gsr_select's mask epilogue (k_connect.h).
+ * THE RULE (one set of functions, evaluated by the kernels and by gsr_select_connected_eval; x86 and gfx950 agree bit for bit).
+ *   1. GRID, POPULATION, OUTSIDE: exactly gsr_select_density's items 1 and 2 -- cell, origin[3], 1024 cells per axis, the key
+ *      ix | iy << 10 | iz << 20, alpha_min, GSR_CONNECT_SKIP_HIDDEN and GSR_CONNECT_HIT_OUTSIDE as the density flags.
+ *   2. ADJACENCY: two OCCUPIED cells (cells that hold at least one population splat) are adjacent iff their indices differ by at most
+ *      `reach` (0..2) on every axis.  The grid does not wrap: (1023, y, z) and (0, y + 1, z), consecutive as keys, are not adjacent.
+ *      At reach 0 no two cells are adjacent.
+ *   3. COMPONENT: an equivalence class of occupied cells under the transitive closure of adjacency.  Every population splat carries
+ *      its component's SIZE, the number of population splats in it (uint32, 1..n), and its LABEL, the smallest upload index among
+ *      them -- canonical, independent of the grid's keys: labels[i] == labels[picked] says "same clump as the one I clicked".
+ *   4. HIT: a population splat iff every clause that is set passes -- size_lo <= size && size <= size_hi as unsigned integers
+ *      (size_lo > size_hi is allowed and hits nothing), and, if a seed mask is given, its component holds at least one POPULATION splat
+ *      whose seed bit is set; an OUTSIDE splat iff GSR_CONNECT_HIT_OUTSIDE, whatever the clauses; nothing else.
+ *      THE SEED (NULL: no seed clause) has the layout of the mask: ceil(n / 32) words in upload order, host (seed_is_device = 0) or
+ *      device / pinned memory (1); bits at or behind n are ignored; a bit on a splat that is not population seeds nothing.  It MAY be
+ *      the mask itself: every word of it is consumed before the mask is written, so op = ADD with seed == mask grows a selection in
+ *      place.
+ *   5. THE MASK, op, n_hit and n_set are gsr_select's (see gsr_select_density, item 5).
+ * THE RESULT (NULL: not wanted): n_population, n_outside, n_cells as gsr_density_result's; n_components; n_seeded, the components that
+ * hold a seed (0 without a seed clause); largest, the largest size; comp_hist[32]: bin b holds the components with
+ * floor(log2(size)) == b; splat_hist[32]: the population splats in those components -- a size_hi is chosen from it.  Integer atomics
+ * only: nothing depends on the order the waves run in.
+ * labels_out / sizes_out (each NULL: skipped): uint32[n] in upload order, both host (outs_are_device = 0) or both device / pinned
+ * memory (1: each checked for 4 n bytes before anything is launched); GSR_CONNECT_NO_LABEL and 0 for a splat that is not population.
+ * gsr_select_connected_eval: the rule on the host, no context and no GPU; P, alpha and vis as gsr_select_density_eval takes them;
+ * seed_bits: ceil(n / 32) packed words or NULL; op is checked and not applied; hit_out[k] = 0 / 1; labels_out, sizes_out and result may
+ * be NULL.  A sequential union-find with the kernels' hook rule (the larger table index under the smaller).
+ * WHAT THE VERB TOUCHES: nothing the context keeps -- no resident bit, depth horizon, cached depth order, policy, visibility state or
+ * entry of gsr_stats -- but a cell table of its own (28 bytes per splat, kept between calls; the 4 bytes per splat of
+ * gsr_select_density's count buffer are shared) and its tally.  Like gsr_select_density it shares the scratch of an upload's sort, so
+ * it WAITS for the frames in flight and the work queued on the public stream.  Synchronous.  A context that never calls it allocates
+ * and launches nothing new.
+ * GSR_E_INVALID, nothing launched and nothing written: NULL ctx, rule or mask; no geometry ever uploaded, or an upload in progress;
+ * what gsr_select_density refuses of cell, origin, reach, flags, op, reserved_ and alpha_min; a device seed, mask, labels_out or
+ * sizes_out that fails the pointer check.  The empty cloud gives GSR_OK, zeros, and touches no word.
+ * gsr_get_select_connected: the calls that selected, the splats hit by the last one, and its clock ms[4]:
+ * [0] the verb's own kernels (HIP events)   [1] the copies, wall clock   [2] the sort (HIP events)   [3] wall clock of the call.
+ * gsr_debug_select_connected_stages: the last call's kernels stage by stage (HIP events, ms): [0] keys   [1] the sort   [2] the cell
+ * table (mark, scan, table, seeds)   [3] link   [4] flatten, tally and stats   [5] scatter and hit.
+ * gsr_multi_select_connected (below, with the other gsr_multi verbs): rank 0's context, host memory only.
+ * Out of scope: adjacency by a world-space radius or by the splats' footprints; more than 1024 cells per axis; a device mask for the
+ * multi verb; the GSplatRenderer shim and the HDK glue; gsr_comm_*; an asynchronous form; results left in device memory; moving
+ * gsr_select_density's counts onto the cell table. */
+#define GSR_CONNECT_SKIP_HIDDEN 1   /* flags: a splat the visibility in force hides is not population */
+#define GSR_CONNECT_HIT_OUTSIDE 2   /* flags: a splat outside the grid (that passes the alpha and visibility tests) is hit */
+#define GSR_CONNECT_CELLS    1024   /* cells per axis */
+#define GSR_CONNECT_MAX_REACH   2
+#define GSR_CONNECT_HIST_BINS  32
+#define GSR_CONNECT_NO_LABEL 0xFFFFFFFFu   /* labels_out of a splat that is not population */
+typedef struct gsr_connect_rule {
+    float    cell;                        /* the cells' edge length: finite, > 0, 1.0f / cell finite */
+    float    origin[3];                   /* the grid's low corner, upload space */
+    int32_t  reach;                       /* 0..GSR_CONNECT_MAX_REACH */
+    int32_t  flags;                       /* GSR_CONNECT_* or 0 */
+    int32_t  op;                          /* GSR_SELECT_REPLACE .. GSR_SELECT_TOGGLE */
+    int32_t  reserved_;                   /* 0 */
+    uint32_t size_lo, size_hi;            /* hit iff size_lo <= size <= size_hi */
+    float    alpha_min;                   /* population iff a >= alpha_min (-INFINITY: every alpha but a NaN) */
+} gsr_connect_rule;
+typedef struct gsr_connect_result {
+    int64_t n_population, n_outside, n_cells;
+    int64_t n_components, n_seeded, largest;
+    int64_t comp_hist[GSR_CONNECT_HIST_BINS];
+    int64_t splat_hist[GSR_CONNECT_HIST_BINS];
+} gsr_connect_result;
+int  gsr_select_connected(gsr_context* ctx, const gsr_connect_rule* rule, const uint32_t* seed /* NULL: no seed clause */, int seed_is_device,
+                          uint32_t* mask, int mask_is_device, uint32_t* labels_out /* NULL */, uint32_t* sizes_out /* NULL */,
+                          int outs_are_device, gsr_connect_result* result /* NULL */, int64_t* n_hit, int64_t* n_set);
+int  gsr_select_connected_eval(const gsr_connect_rule* rule, const gsr_visibility* vis /* NULL: none */, int64_t n, const float* P,
+                               const float* alpha /* NULL: all 1 */, const uint32_t* seed_bits /* NULL: no seed clause */, uint8_t* hit_out,
+                               uint32_t* labels_out /* NULL */, uint32_t* sizes_out /* NULL */,
+                               gsr_connect_result* result /* NULL */);   /* host, no context, no GPU */
+int  gsr_get_select_connected(gsr_context* ctx, int64_t* calls, int64_t* hit_last, double ms[4]);   /* any pointer may be NULL */
+int  gsr_debug_select_connected_stages(gsr_context* ctx, double ms[6]);
 
 /* ---- measuring a selection (counts, bounds, moments and histograms of resident splats, on the GPU) ----------------------------------- */
 /* What a mask of gsr_select SAYS besides its bit count: where the selected splats are (a transform gizmo's pivot, "home on selection", a
@@ -1118,6 +1197,10 @@ int  gsr_multi_select_attrs(gsr_multi* m, const gsr_attr_rule* rule, uint32_t* m
 /* gsr_select_density on rank 0's copy into a HOST mask and HOST counts (NULL: skipped), after the same synchronisation; no rank's state changes */
 int  gsr_multi_select_density(gsr_multi* m, const gsr_density_rule* rule, uint32_t* mask_host, uint32_t* counts_host /* NULL */,
                               gsr_density_result* result /* NULL */, int64_t* n_hit, int64_t* n_set);
+/* gsr_select_connected on rank 0's copy, HOST memory only (seed, labels and sizes may be NULL), after the same synchronisation; no rank's state changes */
+int  gsr_multi_select_connected(gsr_multi* m, const gsr_connect_rule* rule, const uint32_t* seed_host /* NULL */, uint32_t* mask_host,
+                                uint32_t* labels_host /* NULL */, uint32_t* sizes_host /* NULL */, gsr_connect_result* result /* NULL */,
+                                int64_t* n_hit, int64_t* n_set);
 /* gsr_measure on rank 0's copy (the cloud is replicated) from a HOST mask (NULL: every splat), after the same synchronisation; no rank's state changes */
 int  gsr_multi_measure(gsr_multi* m, const uint32_t* mask_host, const gsr_measure_request* request, gsr_measure_result* out, uint32_t* hist_out);
 /* gsr_transform on every rank, after the same synchronisation, from a HOST mask (NULL: every splat).  gsr_multi_remove's agreement
